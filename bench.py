@@ -25,8 +25,14 @@ RCCL), weak scaling.  --exchange allgather (default): frames dealt round-robin, 
 rank all-gathers every rank's [keypoints | descriptors | count] records per launch; --exchange neighbour: contiguous
 frame shards, only the shard's boundary frame is exchanged.
 
-Prints ONE JSON line (rank 0).  `cpu_baseline` times the CPU oracle (a port of the reference algorithm, built -O3 like the reference)
-on a bounded sample of the same frames, on one thread and on all usable host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps of the H2D/D2H-inclusive pipeline once
+(`value`, `ms_per_step`) and prints the line; nothing else is measured.  --full adds everything else: --repeats timed regions (default
+10, `value` = their median), `kernel_pipeline`, `extract_only`, `pcie`, `roofline`, the exchange variants at N > 1, local BA (config 5),
+configs 3 and 4, the extra sections of bench_extras.py and the CPU baselines.  `cpu_baseline` times the CPU oracle (a port of the
+reference algorithm, built -O3 like the reference) on a bounded sample of the same frames, on one thread and on all usable host cores.
+
+--dump-outputs DIR writes what the timed pipeline delivered to pinned host memory in its last launch as DIR/<name>.npy (dump_outputs());
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -314,7 +320,8 @@ class MonoStream:
             own = list(range(lo_g, lo_g + F))
         else:                   # round-robin: global frame g = t * world + rank
             own = [t * world + rank for t in range(F)]
-        self.imgs, _ = stream_render(self.plan, own)
+        # rendering is host work of the setup (~20 ms per frame and thread); the pixels do not depend on the thread count
+        self.imgs, _ = stream_render(self.plan, own, workers=min(16, cpu_info()[2]))
         # The lane streams are created FIRST, before any handle creates streams of its own: the device runs 4 hardware queues and HIP deals
         # streams onto them in creation order (profiles/r02d_queue_overlap.txt).
         self.lane_streams = [torch.cuda.Stream(device=dev) for _ in range(self.LANES)]
@@ -552,8 +559,49 @@ def extract_roofline(w, h, nfeat, n_kp_frame, stages, isolated, frames_per_launc
             "frames_per_extract_launch": frames_per_launch, "pairs_per_match_launch": pairs_per_launch}
 
 
+DUMP_FRAMES = 64   # frames of the fixed sample whose keypoints, descriptors and match lists --dump-outputs writes
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(S, out_dir):
+    """--dump-outputs: what the H2D/D2H-inclusive pipeline delivered to pinned host memory in its last launch (every launch works on the
+    same frames, so the last launch of the last timed step stands for the step; this rank's frames).  Whole-launch arrays:
+    keypoint_counts [F] and match_counts [pairs] (float64).  For DUMP_FRAMES frames drawn once with seed 0 (sample_frames): keypoints
+    [n, cap, 7] (x, y, size, angle, response, octave, class_id), descriptors [n, cap, 32] (the bytes) and matches [n, cap] (the
+    predecessor's keypoint matched to each keypoint, -1 for none or for a frame without a predecessor), float32; slots past a frame's
+    keypoint count are 0 (matches -1).  Returns the bytes written."""
+    import numpy as np
+    from ydorbslam_amd import KP_DTYPE
+    blob, assigned, mcounts = (t.numpy() for t in S.h_out[(S.k - 1) % S.INC_LANES])
+    F, cap = S.F, S.cap
+    n = np.minimum(blob[S.off_n:S.off_n + 4 * F].view(np.int32), cap)
+    kps = blob[:F * cap * 28].view(KP_DTYPE).reshape(F, cap)
+    desc = blob[S.off_desc:S.off_desc + F * cap * 32].reshape(F, cap, 32)
+    pick = np.sort(np.random.default_rng(0).choice(F, size=min(DUMP_FRAMES, F), replace=False))
+    valid = np.arange(cap)[None, :] < n[pick][:, None]
+    k = np.stack([kps[pick][f_].astype(np.float32) for f_ in KP_DTYPE.names], axis=-1)
+    k[~valid] = 0
+    d = desc[pick].astype(np.float32)
+    d[~valid] = 0
+    pair_of = {int(t_): c_ for c_, t_ in enumerate(S.pairs[:, 1])}   # pair c searches target frame pairs[c, 1] for pairs[c, 0]'s keypoints
+    m = np.full((len(pick), cap), -1, np.float32)
+    for i, f_ in enumerate(pick):
+        if int(f_) in pair_of:
+            m[i, :n[f_]] = assigned[pair_of[int(f_)], :n[f_]]
+    arrays = {"keypoint_counts": n.astype(np.float64), "match_counts": mcounts.astype(np.float64), "sample_frames": pick.astype(np.float64),
+              "keypoints": k, "descriptors": d, "matches": m}
+    total = sum(a_.nbytes for a_ in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a_ in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a_)
+    return total
+
+
 def mono_section(ctx, y, link):
-    """Config 2.  Returns (top-level keys of the JSON line, the MonoStream for later sections)."""
+    """Config 2.  Returns (top-level keys of the JSON line, the MonoStream for later sections).  Without --full only the H2D/D2H-inclusive
+    timed region runs (link is then None)."""
     args, torch = ctx.args, ctx.torch
     S = MonoStream(ctx, y)
     W, H, NFEAT, F, world = S.W, S.H, S.NFEAT, S.F, ctx.world
@@ -561,6 +609,8 @@ def mono_section(ctx, y, link):
     # ---- the contract's number: H2D/D2H-inclusive, exactly --steps steps per timed region -----------------------------------------
     t_inc = ctx.timed(lambda: S.step(True), args.steps, args.warmup, args.repeats)
     S.synchronize()
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(S, args.dump_outputs)
     if S.up_trace:   # diagnostic (YDORB_BENCH_UPLOAD_TRACE): duration of the uploads and the gaps between consecutive ones, last region
         tr = S.up_trace[-launches:]
         dur = [a_.elapsed_time(b_) for a_, b_ in tr]
@@ -577,6 +627,41 @@ def mono_section(ctx, y, link):
     rate = lambda dt: kp_total * launches / dt / 1e6
     inc = stats([rate(t) for t in t_inc])
     dt_inc = float(sorted(t_inc)[len(t_inc) // 2])
+    par = "1 GPU"
+    if world > 1:
+        par = {"neighbour": "contiguous frame shards x%d, all-gather of each rank's boundary frame record (60 KB) per launch, local match",
+               "ring": "frames dealt round-robin x%d, every rank sends its [kp|desc|n] slab of the launch to rank + 1 (the only rank that reads it), local match",
+               "allgather": "frames dealt round-robin x%d, ONE all-gather of every rank's [kp|desc|n] slab per launch, "
+                            "local match of the owned frames against rank - 1's slab"}[S.mode] % world
+    out = {"metric": "ORB extract+match Mkeypoints/sec", "value": inc["median"], "unit": "Mkeypoints/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": dt_inc / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "u8", "data": "synthetic", "parity": "partial", "parity_note": PARITY_NOTE,
+           "value_definition": "H2D/D2H-inclusive (SURVEY.md 8(d): 'GPU timed ... around the batch incl. H2D/D2H'; the reference's frames come from host "
+                               "memory, frame.cpp:84-87,129): pinned host frames in, keypoints / descriptors / match lists back in pinned host memory. "
+                               "kernel_pipeline (--full) is the same work with the frames resident in HBM (the figure rounds 1-2 reported as value).",
+           "repeats": {"n": inc["n"], "min": inc["min"], "max": inc["max"], "median": inc["median"], "timed_region_s": dt_inc,
+                       "note": "each repeat = exactly --steps steps bracketed by barrier + synchronize; value = median"},
+           "config": {"workload": "TUM-fr1-size 640x480 mono stream, 1000 feat/frame, extract + consecutive-frame searchByProjection (th 15); "
+                                  "pinned host frames in, results back in pinned host memory",
+                      "frames_per_step_per_gpu": F * args.substeps, "frames_per_launch": F, "launches_per_step": args.substeps,
+                      "distinct_frames": F * world, "frames_per_scene": args.segment,
+                      "pipelining": ("%d lanes (extractor handle + matcher + output set + ONE stream each) take consecutive launches: extraction, matching and "
+                                     "read-back of a launch in its lane's stream order; the uploads run back to back on a stream of their own (the 4th "
+                                     "hardware queue) into a ring of %d image buffers, a lane waits for its frames' event only.  kernel_pipeline / "
+                                     "extract_only: %d lanes, no copies" % (S.INC_LANES, S.NIMG, S.LANES)) if S.s_up is not None else
+                                    ("%d lanes (extractor handle + matcher + image buffer + output set + ONE stream each) take consecutive launches: upload, "
+                                     "extraction, matching and read-back of a launch in its lane's stream order, the lanes overlap each other" % S.LANES),
+                      "motion": "per frame: roll within +-3 deg, shift within +-8 px (bounded walk); prediction = true motion + N(0,1.5^2) px on the translation",
+                      "keypoints_per_frame": kp_local / F, "matches_per_pair": matched_local / max(S.NPAIR, 1),
+                      "matches_note": "what the reference's rules accept: ~770 of 1000 keypoints of a frame re-appear within 2.5 px x scale in the next one "
+                                      "(median Hamming distance 35), but Frame::getKeyPointsInArea keeps only candidates with |dx| > r inside the "
+                                      "window's grid cells (frame.cpp:353, reproduced bit for bit) and the rotation histogram uses the factor 1/30 "
+                                      "(orbMatcher.cpp:78): ~120 pass the distance test, ~50 the rotation check",
+                      "parallelism": par,
+                      "hip_runtime": ctx.hip_runtime or "the one bundled with PyTorch (torch/lib)",
+                      "hardware_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))}}
+    if not args.full:
+        return out, S
     # ---- the same work with the frames resident in HBM and the results left there ---------------------------------------------------
     S.set_profiling(True)     # per-stage device time LIVE in the timed regions (HIP events on the launch stream, read at the next launch, never waited for)
     t_res = ctx.timed(lambda: S.step(False), args.steps, args.warmup, args.repeats)
@@ -613,12 +698,6 @@ def mono_section(ctx, y, link):
                  "frac_note": "upload bytes of the inclusive pipeline per second / peak_GBps (the one-way rate of pinned hipMemcpyAsync measured in this "
                               "process): the frames going in are 5x the results coming back and the link is full duplex, so the upload direction is the "
                               "roof - %.1f Mkeypoints/s at peak_GBps for this workload" % (kp_total / (S.bytes_in / (link["peak_GBps"] * 1e9)) / 1e6 / 1.0)})
-    par = "1 GPU"
-    if world > 1:
-        par = {"neighbour": "contiguous frame shards x%d, all-gather of each rank's boundary frame record (60 KB) per launch, local match",
-               "ring": "frames dealt round-robin x%d, every rank sends its [kp|desc|n] slab of the launch to rank + 1 (the only rank that reads it), local match",
-               "allgather": "frames dealt round-robin x%d, ONE all-gather of every rank's [kp|desc|n] slab per launch, "
-                            "local match of the owned frames against rank - 1's slab"}[S.mode] % world
     variants = None
     if ctx.distributed and world > 1 or (ctx.force_dist and os.environ.get("YDORB_BENCH_VARIANTS")):
         # the other two exchange forms, measured in the same run (3 repeats each): value stays the all-gather form north_star names
@@ -644,39 +723,12 @@ def mono_section(ctx, y, link):
             S2.mode = "ring"
             variants["ring"] = quick(S2)
         del S2
-    out = {"metric": "ORB extract+match Mkeypoints/sec", "value": inc["median"], "unit": "Mkeypoints/s", "n_gpus": world, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": dt_inc / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "u8", "data": "synthetic", "parity": "partial", "parity_note": PARITY_NOTE,
-           "value_definition": "H2D/D2H-inclusive (SURVEY.md 8(d): 'GPU timed ... around the batch incl. H2D/D2H'; the reference's frames come from host "
-                               "memory, frame.cpp:84-87,129): pinned host frames in, keypoints / descriptors / match lists back in pinned host memory. "
-                               "kernel_pipeline is the same work with the frames resident in HBM (the figure rounds 1-2 reported as value).",
-           "repeats": {"n": inc["n"], "min": inc["min"], "max": inc["max"], "median": inc["median"], "timed_region_s": dt_inc,
-                       "note": "each repeat = exactly --steps steps bracketed by barrier + synchronize; value = median"},
-           "config": {"workload": "TUM-fr1-size 640x480 mono stream, 1000 feat/frame, extract + consecutive-frame searchByProjection (th 15); "
-                                  "pinned host frames in, results back in pinned host memory",
-                      "frames_per_step_per_gpu": F * args.substeps, "frames_per_launch": F, "launches_per_step": args.substeps,
-                      "distinct_frames": F * world, "frames_per_scene": args.segment,
-                      "pipelining": ("%d lanes (extractor handle + matcher + output set + ONE stream each) take consecutive launches: extraction, matching and "
-                                     "read-back of a launch in its lane's stream order; the uploads run back to back on a stream of their own (the 4th "
-                                     "hardware queue) into a ring of %d image buffers, a lane waits for its frames' event only.  kernel_pipeline / "
-                                     "extract_only: %d lanes, no copies" % (S.INC_LANES, S.NIMG, S.LANES)) if S.s_up is not None else
-                                    ("%d lanes (extractor handle + matcher + image buffer + output set + ONE stream each) take consecutive launches: upload, "
-                                     "extraction, matching and read-back of a launch in its lane's stream order, the lanes overlap each other" % S.LANES),
-                      "motion": "per frame: roll within +-3 deg, shift within +-8 px (bounded walk); prediction = true motion + N(0,1.5^2) px on the translation",
-                      "keypoints_per_frame": kp_local / F, "matches_per_pair": matched_local / max(S.NPAIR, 1),
-                      "matches_note": "what the reference's rules accept: ~770 of 1000 keypoints of a frame re-appear within 2.5 px x scale in the next one "
-                                      "(median Hamming distance 35), but Frame::getKeyPointsInArea keeps only candidates with |dx| > r inside the "
-                                      "window's grid cells (frame.cpp:353, reproduced bit for bit) and the rotation histogram uses the factor 1/30 "
-                                      "(orbMatcher.cpp:78): ~120 pass the distance test, ~50 the rotation check",
-                      "parallelism": par,
-                      "hip_runtime": ctx.hip_runtime or "the one bundled with PyTorch (torch/lib)",
-                      "hardware_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))},
-           "kernel_pipeline": {"value": res["median"], "unit": "Mkeypoints/s", "ms_per_step": dt_res / args.steps * 1e3, "min": res["min"], "max": res["max"],
-                               "n": res["n"], "timed_region_s": dt_res,
-                               "note": "frames resident in HBM, results left in HBM; the same launches, lanes and streams without the copies"},
-           "extract_only": {"value": ext["median"], "unit": "Mkeypoints/s", "min": ext["min"], "max": ext["max"],
-                            "note": "extraction launches only (frames resident), same handles and streams"},
-           "pcie": pcie, "roofline": roofline}
+    out.update({"kernel_pipeline": {"value": res["median"], "unit": "Mkeypoints/s", "ms_per_step": dt_res / args.steps * 1e3, "min": res["min"],
+                                    "max": res["max"], "n": res["n"], "timed_region_s": dt_res,
+                                    "note": "frames resident in HBM, results left in HBM; the same launches, lanes and streams without the copies"},
+                "extract_only": {"value": ext["median"], "unit": "Mkeypoints/s", "min": ext["min"], "max": ext["max"],
+                                 "note": "extraction launches only (frames resident), same handles and streams"},
+                "pcie": pcie, "roofline": roofline})
     if variants is not None:
         out["exchange"] = {"mode": S.mode, "MB_per_rank_per_launch": (S.slab * (world - 1) if S.mode == "allgather" else S.slab if S.mode == "ring" else S.rec * world) / 1e6,
                            "variants": variants,
@@ -999,7 +1051,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=10, help="timed regions of exactly --steps steps each; value = median")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of exactly --steps steps each; value = median (default 1; 10 with --full)")
+    ap.add_argument("--full", action="store_true", help="measure everything, not only the headline: --repeats regions, kernel_pipeline, extract_only, pcie, "
+                                                         "roofline, exchange variants, local BA, configs 3 / 4, the extra sections, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed launch's outputs as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--frames", type=int, default=2048, help="frames per launch and per GPU (measured, inclusive / resident Mkeypoints/s, uploads on their own "
                                                             "stream: 512 frames 158 / 248, 1024 frames 174 / 250, 2048 frames 180 / 250: longer uploads keep the link busier)")
     ap.add_argument("--substeps", type=int, default=8, help="launches per step (a step = substeps x frames frames: 20 steps are then a timed region of > 1 s)")
@@ -1011,11 +1066,13 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=96, help="frames of the 1-thread CPU-oracle sample")
     ap.add_argument("--ba-threads", type=int, default=64, help="problems of the lock-step batched local-BA figure (ydorb_ba_solve_batch)")
     ap.add_argument("--ba-reps", type=int, default=3, help="solves per timed repeat of the single local-BA figure")
-    ap.add_argument("--no-ba", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--only", default="", help="with extras: run only these sections (comma list of single_call, config3, config4, rest)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-call / config 3 / config 4 / brute-force / next-row sections")
+    ap.add_argument("--no-ba", action="store_true", help="with --full: skip local BA")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--only", default="", help="with --full and extras: run only these sections (comma list of single_call, config3, config4, rest)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the single-call / config 3 / config 4 / brute-force / next-row sections")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
 
     # The HIP runtime deals a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); streams that share one run in turn.  The
     # mono pipeline needs four (its default), config 3's eight lanes need eight.  Read when the runtime loads, so set before anything else.
@@ -1035,13 +1092,13 @@ def main():
     import ydorbslam_amd as y
     # Config 5 first: with the stream pipeline's handles resident (25 GB of batch buffers for four 2048-frame lanes) the same solve takes
     # 8.8 ms instead of 7.9 (device time, not host time: the solver's pooled buffers are then carved out of a crowded address space)
-    ba = None if args.no_ba else ba_section(ctx, y)
-    link = pcie_link(ctx)
+    ba = ba_section(ctx, y) if args.full and not args.no_ba else None
+    link = pcie_link(ctx) if args.full else None
     out, S = mono_section(ctx, y, link)
     if ba is not None:
         out["ba"] = ba
 
-    extras = ctx.world == 1 and not args.no_extras
+    extras = args.full and ctx.world == 1 and not args.no_extras
     only = [x for x in args.only.split(",") if x]
     want = lambda name: extras and (not only or name in only)
     if want("config3"):
@@ -1056,7 +1113,7 @@ def main():
     if extras:
         import bench_extras
         state = bench_extras.run(ctx, y, S, out, want)
-    if ctx.rank == 0 and not args.no_cpu:
+    if args.full and ctx.rank == 0 and not args.no_cpu:
         cpu_baseline_section(ctx, S, out)
         if state is not None:
             import bench_extras

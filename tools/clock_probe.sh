@@ -1,5 +1,5 @@
 # does the extract-only rate depend on the lane count, and what do the clocks do under the sustained load?  results in gpurun_out/
-B="python bench.py --repeats 3 --no-ba --no-cpu --only none --no-extras"
+B="python bench.py --full --repeats 3 --no-ba --no-cpu --only none --no-extras"
 ( for i in $(seq 1 150); do
     echo "t=$i $(cat /sys/class/drm/card*/device/pp_dpm_sclk 2>/dev/null | grep '\*' | tr '\n' ' ') $(cat /sys/class/drm/card*/device/hwmon/hwmon*/power1_average 2>/dev/null | tr '\n' ' ')"
     sleep 0.5
