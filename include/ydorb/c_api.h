@@ -455,6 +455,70 @@ int ydorb_pose_optimize(const YdPoseBatch* batch, uint8_t* outlier, int32_t* n_i
 /* dense SPD solve with the BA's blocked Cholesky (known-answer tests; A is n x n row-major, host pointers) */
 int ydorb_ba_dense_solve(int32_t device, const double* A, int32_t n, const double* b, double* x, int32_t* ok);
 
+/* ------------------------------------------------------------------------------------------
+ * Sim3 RANSAC of the loop-closure check.  Replaces Sim3Solver::iterate (ORB-SLAM2 src/Sim3Solver.cc: iterate, ComputeSim3,
+ * CheckInliers, Project) for a batch of candidate keyframes; LoopClosing::computeSim3 calls it with chunk 5 per candidate.
+ * The constructor's work (camera-frame points, their images, maxError = 9.210 * sigma^2) and setRansacParameters stay with the
+ * caller (include/ydorb/sim3Solver.hpp), which hands over the N kept pairs.  The RANSAC's index triples are inputs, drawn by the
+ * caller in the reference's order (RandomInt over the available-index copy, then swap-remove): the reference draws them from the
+ * process-global rand(), so the result is a pure function of the arguments.  One call runs what repeated iterate(chunk) calls do
+ * from next_hyp on: it stops at the first hypothesis with inliers >= the running best AND > min_inliers (the reference's return),
+ * at max_its, or when the triples run out.  fp32 arithmetic in the written order of DESIGN.md section 2 ("Sim3 RANSAC"): the
+ * result is bit-identical to a CPU restatement compiled with -ffp-contract=off.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdSim3Problem {
+  int32_t n;                     /* kept pairs N (mvX3Dc1.size()) */
+  int32_t fix_scale;             /* mbFixScale */
+  int32_t min_inliers, max_its;  /* mRansacMinInliers, mRansacMaxIts as setRansacParameters left them */
+  const float* X1;               /* [n][3] mvX3Dc1: KF1's points in KF1's camera frame */
+  const float* X2;               /* [n][3] mvX3Dc2 */
+  const float* P1;               /* [n][2] mvP1im1: X1 through K1 */
+  const float* P2;               /* [n][2] mvP2im2 */
+  const float* max_err1;         /* [n] mvnMaxError1 */
+  const float* max_err2;         /* [n] mvnMaxError2 */
+  float K1[4], K2[4];            /* fx, fy, cx, cy */
+  int32_t n_hyp;                 /* triples supplied: hypotheses next_hyp .. next_hyp + n_hyp - 1 */
+  const int32_t* triples;        /* [n_hyp][3] indices into the n pairs, in draw order */
+  int32_t next_hyp;              /* in/out: mnIterations */
+  int32_t best_inliers;          /* in/out: mnBestInliers */
+  float best_T12[13];            /* in/out: mBestT12 as R (row-major 3x3), t, s; on a return = the returned T12 */
+  int32_t ret_hyp;               /* out: global index of the hypothesis at which iterate returns, -1 if none */
+  int32_t no_more;               /* out: bNoMore of the last iterate(chunk) call the sequence ran */
+  int32_t n_calls;               /* out: iterate(chunk) calls the sequence ran */
+  int32_t reserved;
+  uint8_t* inliers;              /* out [n]: the returned inlier set over the pairs (all 0 without a return) */
+  int32_t* hyp_inliers;          /* out [n_hyp], may be NULL: inlier count of every evaluated hypothesis (-1 where none ran) */
+} YdSim3Problem;
+int ydorb_sim3_ransac(YdSim3Problem* probs, int32_t n_probs, int32_t chunk, int32_t device);
+
+/* Optimizer::optimizeSim3 (ORB-SLAM2 Optimizer::OptimizeSim3, src/Optimizer.cc) for a batch of problems, one workgroup per problem:
+ * one VertexSim3Expmap (g2o sim3.h exp map, _fix_scale), two projection edges per pair (EdgeSim3ProjectXYZ against obs1,
+ * EdgeInverseSim3ProjectXYZ against obs2, information I * inv_sigma2, Huber delta sqrtf(th2), central-difference Jacobians with
+ * delta 1e-9) -> optimize(5) -> drop pairs with chi2 > th2 on either edge -> return 0 if fewer than 10 pairs remain -> optimize(nBad ?
+ * 10 : 5) -> count.  Problem p owns pairs [corr_start[p], corr_start[p+1]).  Outputs: outlier[pair] (the pairs the reference sets to
+ * NULL), n_in[p] (the return value; S12 untouched when it is 0 by the early return), optional chi2_log [n][2] (robust chi2 after each
+ * optimize, NaN where it did not run) and trials [n] (LM trials over both stages). */
+typedef struct YdSim3Batch {
+  int32_t n_problems;
+  int32_t device;
+  const int32_t* corr_start;     /* [n_problems + 1] */
+  double* S12;                   /* [n_problems][8] qx, qy, qz, qw, tx, ty, tz, s; in/out */
+  const double* K1;              /* [n_problems][4] fx, fy, cx, cy of KF1 */
+  const double* K2;              /* [n_problems][4] of KF2 */
+  const uint8_t* fix_scale;      /* [n_problems] */
+  const double* X1c;             /* [pairs][3] KF1's point in KF1's camera frame */
+  const double* X2c;             /* [pairs][3] KF2's point in KF2's camera frame */
+  const double* obs1;            /* [pairs][2] kpUn1 */
+  const double* obs2;            /* [pairs][2] kpUn2 */
+  const double* inv_sigma2_1;    /* [pairs] KF1->mvInvLevelSigma2[kpUn1.octave] */
+  const double* inv_sigma2_2;    /* [pairs] */
+  double th2;                    /* the reference's float th2 (10 in loop closing) */
+} YdSim3Batch;
+int ydorb_sim3_optimize(const YdSim3Batch* batch, uint8_t* outlier, int32_t* n_in, double* chi2_log, int32_t* trials);
+
+/* Both Sim3 entries keep device scratch per device between calls; this frees it (waiting for calls in flight). */
+int ydorb_sim3_release(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,56 @@ int optimizePoseImpl(FrameT& frame) {
   return inliers;
 }
 
+// Optimizer::optimizeSim3 (ORB-SLAM2 Optimizer::OptimizeSim3, src/Optimizer.cc): the pairs of matches1 whose two
+// map points are set, not bad and indexed in KF2 go to ydorb_sim3_optimize; the matches it drops are set to null as the reference does.
+// S12 is g2o::Sim3 as 8 doubles (qx, qy, qz, qw, tx, ty, tz, s), in/out; INTEGRATION.md shows the conversion in the forwarding body.
+// Camera-frame points: each product exact in double, summed in double, rounded to float, plus t in float (the float cv::Mat transform
+// the reference does before Converter::toVector3d).
+template <class FrameT, class KeyFramePtr, class MapPointPtr>
+int optimizeSim3Impl(KeyFramePtr kf1, KeyFramePtr kf2, std::vector<MapPointPtr>& matches1, double* S12, const float th2, const bool fixScale,
+                     int device = 0) {
+  const cv::Mat R1 = kf1->getRotation_c2w(), t1 = kf1->getTranslation_c2w(), R2 = kf2->getRotation_c2w(), t2 = kf2->getTranslation_c2w();
+  const std::vector<MapPointPtr> mps1 = kf1->getMatchedMapPointsVec();
+  std::vector<int> idx;
+  std::vector<double> X1, X2, o1, o2, w1, w2;
+  auto cam = [](const cv::Mat& R, const cv::Mat& t, const cv::Mat& Xw, std::vector<double>& out) {
+    for (int r = 0; r < 3; r++) {
+      const double s = ((double)R.at<float>(r, 0) * (double)Xw.at<float>(0) + (double)R.at<float>(r, 1) * (double)Xw.at<float>(1)) +
+                       (double)R.at<float>(r, 2) * (double)Xw.at<float>(2);
+      out.push_back((double)((float)s + t.at<float>(r)));
+    }
+  };
+  for (int i = 0; i < (int)matches1.size(); i++) {
+    if (!matches1[i]) continue;
+    const MapPointPtr mp1 = mps1[i], mp2 = matches1[i];
+    if (!mp1) continue;
+    const int i2 = mp2->getIdxInKeyFrame(kf2);
+    if (mp1->isBad() || mp2->isBad() || i2 < 0) continue;
+    cam(R1, t1, mp1->getPosInWorld(), X1);
+    cam(R2, t2, mp2->getPosInWorld(), X2);
+    const cv::KeyPoint& k1 = kf1->m_v_keyPoints[i];
+    const cv::KeyPoint& k2 = kf2->m_v_keyPoints[i2];
+    o1.push_back(k1.pt.x); o1.push_back(k1.pt.y);
+    o2.push_back(k2.pt.x); o2.push_back(k2.pt.y);
+    w1.push_back(kf1->m_v_invScaleFactorSquares[k1.octave]);
+    w2.push_back(kf2->m_v_invScaleFactorSquares[k2.octave]);
+    idx.push_back(i);
+  }
+  const int32_t start[2] = {0, (int32_t)idx.size()};
+  const double K[4] = {FrameT::m_flt_fx, FrameT::m_flt_fy, FrameT::m_flt_cx, FrameT::m_flt_cy};
+  const uint8_t fix = fixScale ? 1 : 0;
+  YdSim3Batch B{};
+  B.n_problems = 1; B.device = device; B.corr_start = start; B.S12 = S12; B.K1 = K; B.K2 = K; B.fix_scale = &fix;
+  B.X1c = X1.data(); B.X2c = X2.data(); B.obs1 = o1.data(); B.obs2 = o2.data(); B.inv_sigma2_1 = w1.data(); B.inv_sigma2_2 = w2.data();
+  B.th2 = th2;
+  std::vector<uint8_t> outlier(std::max<size_t>(idx.size(), 1));
+  int32_t nIn = 0;
+  if (ydorb_sim3_optimize(&B, outlier.data(), &nIn, nullptr, nullptr) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
+  for (size_t k = 0; k < idx.size(); k++)
+    if (outlier[k]) matches1[idx[k]] = MapPointPtr();
+  return nIn;
+}
+
 // Optimizer::globalBundleAdjust (optimizer.cpp:353-357)
 template <class FrameT, class MapPtr>
 void globalBundleAdjustImpl(MapPtr map, int iterNum, const volatile bool* stop, long int loopKeyFrameID, bool robust) {

@@ -81,6 +81,9 @@ SYMBOLS = {
     "ydorb_ba_solve_batch": (C.c_int, [_VP, _I, _VP, _VP, _I, _VP]),
     "ydorb_ba_dense_solve": (C.c_int, [_I, _VP, _I, _VP, _VP, C.POINTER(_I)]),
     "ydorb_pose_optimize": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "ydorb_sim3_ransac": (C.c_int, [_VP, _I, _I, _I]),
+    "ydorb_sim3_optimize": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "ydorb_sim3_release": (C.c_int, [_I]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -95,6 +98,18 @@ class YdBaProblem(C.Structure):
 class YdPoseBatch(C.Structure):
     _fields_ = [("n_frames", _I), ("device", _I), ("edge_start", _VP), ("poses", _VP), ("points", _VP), ("meas", _VP),
                 ("inv_sigma2", _VP), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("bf", C.c_double)]
+
+
+class YdSim3Problem(C.Structure):
+    _fields_ = [("n", _I), ("fix_scale", _I), ("min_inliers", _I), ("max_its", _I), ("X1", _VP), ("X2", _VP), ("P1", _VP), ("P2", _VP),
+                ("max_err1", _VP), ("max_err2", _VP), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("n_hyp", _I), ("triples", _VP),
+                ("next_hyp", _I), ("best_inliers", _I), ("best_T12", C.c_float * 13), ("ret_hyp", _I), ("no_more", _I), ("n_calls", _I),
+                ("reserved", _I), ("inliers", _VP), ("hyp_inliers", _VP)]
+
+
+class YdSim3Batch(C.Structure):
+    _fields_ = [("n_problems", _I), ("device", _I), ("corr_start", _VP), ("S12", _VP), ("K1", _VP), ("K2", _VP), ("fix_scale", _VP),
+                ("X1c", _VP), ("X2c", _VP), ("obs1", _VP), ("obs2", _VP), ("inv_sigma2_1", _VP), ("inv_sigma2_2", _VP), ("th2", C.c_double)]
 
 
 class YdBaOptions(C.Structure):
