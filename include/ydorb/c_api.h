@@ -519,6 +519,48 @@ int ydorb_sim3_optimize(const YdSim3Batch* batch, uint8_t* outlier, int32_t* n_i
 /* Both Sim3 entries keep device scratch per device between calls; this frees it (waiting for calls in flight). */
 int ydorb_sim3_release(int32_t device);
 
+/* ------------------------------------------------------------------------------------------
+ * EPnP RANSAC of relocalisation.  Replaces PnPsolver::iterate (ORB-SLAM2 src/PnPsolver.cc: iterate, Refine, CheckInliers and
+ * Lepetit's EPnP compute_pose) for a batch of candidate keyframes; Tracking::relocalize calls it with chunk 5 per candidate.
+ * The constructor's work (the N kept matches: world points, undistorted keypoints, maxError = sigma^2 * th2) and
+ * setRansacParameters stay with the caller (include/ydorb/pnpSolver.hpp).  The 4-point sets are inputs, drawn by the caller in the
+ * reference's order (RandomInt over the available-index copy, then swap-remove).  One call runs what repeated iterate(chunk) calls do
+ * from next_hyp on: it stops at the first hypothesis whose Refine succeeds, at the end of the call that sets bNoMore, or when the
+ * quads run out.  fp64 EPnP in the written order of DESIGN.md section 2 ("EPnP RANSAC"): the result is bit-identical to a CPU
+ * restatement compiled with -ffp-contract=off.
+ * ---------------------------------------------------------------------------------------- */
+#define YDORB_PNP_NONE 0      /* iterate returned an empty Mat */
+#define YDORB_PNP_REFINED 1   /* returned Refine's pose at hypothesis ret_hyp */
+#define YDORB_PNP_BEST 2      /* returned the unrefined best pose when the iterations ran out */
+typedef struct YdPnpProblem {
+  int32_t n;                     /* kept matches N (mvP2D.size()) */
+  int32_t min_inliers, max_its;  /* mRansacMinInliers, mRansacMaxIts as setRansacParameters left them */
+  int32_t loop_or;               /* 1: while (mnIterations < maxIts || nCurrent < nIterations) (ORB-SLAM2); 0: the && variant */
+  const float* Xw;               /* [n][3] mvP3Dw */
+  const float* P2D;              /* [n][2] mvP2D */
+  const float* max_err;          /* [n] mvMaxError */
+  float K[4];                    /* fu, fv, uc, vc */
+  int32_t n_hyp;                 /* quads supplied: hypotheses next_hyp .. next_hyp + n_hyp - 1 */
+  const int32_t* quads;          /* [n_hyp][4] indices into the n matches, in draw order */
+  int32_t next_hyp;              /* in/out: mnIterations */
+  int32_t best_inliers;          /* in/out: mnBestInliers */
+  uint8_t* best_mask;            /* in/out [n]: mvbBestInliers (the next Refine reads it) */
+  float best_Tcw[12];            /* in/out: mBestTcw, rows 0..2 of the 4x4 (row-major 3x4) */
+  int32_t ret_hyp;               /* out: global index of the hypothesis whose Refine returned, -1 otherwise */
+  int32_t ret_how;               /* out: YDORB_PNP_NONE / _REFINED / _BEST */
+  int32_t no_more;               /* out: bNoMore of the last iterate(chunk) call the sequence ran */
+  int32_t n_calls;               /* out: iterate(chunk) calls the sequence ran */
+  float Tcw[12];                 /* out: the returned pose (3x4 row-major), zeros with YDORB_PNP_NONE */
+  int32_t n_inliers;             /* out: nInliers */
+  int32_t reserved;
+  uint8_t* inliers;              /* out [n]: the returned inlier set over the matches (all 0 without a return) */
+  int32_t* hyp_inliers;          /* out [n_hyp], may be NULL: inlier count of every evaluated hypothesis (-1 where none ran) */
+} YdPnpProblem;
+int ydorb_pnp_ransac(YdPnpProblem* probs, int32_t n_probs, int32_t chunk, int32_t device);
+
+/* ydorb_pnp_ransac keeps device scratch per device between calls; this frees it (waiting for calls in flight). */
+int ydorb_pnp_release(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

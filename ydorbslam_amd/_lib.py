@@ -84,6 +84,8 @@ SYMBOLS = {
     "ydorb_sim3_ransac": (C.c_int, [_VP, _I, _I, _I]),
     "ydorb_sim3_optimize": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "ydorb_sim3_release": (C.c_int, [_I]),
+    "ydorb_pnp_ransac": (C.c_int, [_VP, _I, _I, _I]),
+    "ydorb_pnp_release": (C.c_int, [_I]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -105,6 +107,13 @@ class YdSim3Problem(C.Structure):
                 ("max_err1", _VP), ("max_err2", _VP), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("n_hyp", _I), ("triples", _VP),
                 ("next_hyp", _I), ("best_inliers", _I), ("best_T12", C.c_float * 13), ("ret_hyp", _I), ("no_more", _I), ("n_calls", _I),
                 ("reserved", _I), ("inliers", _VP), ("hyp_inliers", _VP)]
+
+
+class YdPnpProblem(C.Structure):
+    _fields_ = [("n", _I), ("min_inliers", _I), ("max_its", _I), ("loop_or", _I), ("Xw", _VP), ("P2D", _VP), ("max_err", _VP),
+                ("K", C.c_float * 4), ("n_hyp", _I), ("quads", _VP), ("next_hyp", _I), ("best_inliers", _I), ("best_mask", _VP),
+                ("best_Tcw", C.c_float * 12), ("ret_hyp", _I), ("ret_how", _I), ("no_more", _I), ("n_calls", _I), ("Tcw", C.c_float * 12),
+                ("n_inliers", _I), ("reserved", _I), ("inliers", _VP), ("hyp_inliers", _VP)]
 
 
 class YdSim3Batch(C.Structure):
