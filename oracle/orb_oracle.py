@@ -93,6 +93,8 @@ def lib():
         L.yo_stereo_matches.restype = C.c_int
         L.yo_stereo_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + \
             [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.yo_stereo_matches_trace.restype = C.c_int
+        L.yo_stereo_matches_trace.argtypes = L.yo_stereo_matches.argtypes + [C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -369,9 +371,7 @@ def pose_optimize(prob):
     return dict(pose=pose, outlier=outlier[:E], inliers=n, chi2=chi, trials=trials.value)
 
 
-def stereo_matches(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_scale, bf, b, index_by_keypoint=False):
-    """Frame::computeStereoMatches (frame.cpp:362-477) for one pair.  levels_*: list of 2-D uint8 arrays (the level ROIs).
-    Returns (right_x, depth, n_kept, status)."""
+def _stereo_call(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_scale, bf, b, index_by_keypoint, trace):
     L = lib()
     kl = np.ascontiguousarray(kps_l, KP_DTYPE); kr = np.ascontiguousarray(kps_r, KP_DTYPE)
     dl = np.ascontiguousarray(desc_l, np.uint8); dr = np.ascontiguousarray(desc_r, np.uint8)
@@ -384,10 +384,26 @@ def stereo_matches(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_
     sc = np.ascontiguousarray(scale, np.float32); isc = np.ascontiguousarray(inv_scale, np.float32)
     rx = np.zeros(max(len(kl), 1), np.float32); depth = np.zeros(max(len(kl), 1), np.float32)
     st = C.c_int(0)
-    kept = L.yo_stereo_matches(_p(kl), _p(dl), len(kl), _p(kr), _p(dr), len(kr), C.cast(pl, C.c_void_p), C.cast(pr, C.c_void_p), _p(w), _p(h),
-                               _p(sl), _p(sr), nlv, _p(sc), _p(isc), float(bf), float(b), 1 if index_by_keypoint else 0, _p(rx), _p(depth),
-                               C.byref(st))
-    return rx[:len(kl)], depth[:len(kl)], kept, st.value
+    args = [_p(kl), _p(dl), len(kl), _p(kr), _p(dr), len(kr), C.cast(pl, C.c_void_p), C.cast(pr, C.c_void_p), _p(w), _p(h),
+            _p(sl), _p(sr), nlv, _p(sc), _p(isc), float(bf), float(b), 1 if index_by_keypoint else 0, _p(rx), _p(depth), C.byref(st)]
+    if not trace:
+        kept = L.yo_stereo_matches(*args)
+        return rx[:len(kl)], depth[:len(kl)], kept, st.value
+    ts = np.zeros(max(len(kl), 1), np.int32); tc = np.zeros(max(len(kl), 1), np.uint8)
+    kept = L.yo_stereo_matches_trace(*args, _p(ts), _p(tc))
+    return rx[:len(kl)], depth[:len(kl)], kept, st.value, ts[:len(kl)], tc[:len(kl)]
+
+
+def stereo_matches(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_scale, bf, b, index_by_keypoint=False):
+    """Frame::computeStereoMatches (frame.cpp:362-477) for one pair.  levels_*: list of 2-D uint8 arrays (the level ROIs).
+    Returns (right_x, depth, n_kept, status)."""
+    return _stereo_call(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_scale, bf, b, index_by_keypoint, False)
+
+
+def stereo_matches_trace(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_scale, bf, b, index_by_keypoint=False):
+    """stereo_matches plus the walk's per-step trace: returns (right_x, depth, n_kept, status, s, complete) where s[k] is the index
+    `leftIdx` the step of left keypoint k used (descriptor row and output slot) and complete[k] says whether it reached `leftIdx++`."""
+    return _stereo_call(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_scale, bf, b, index_by_keypoint, True)
 
 
 def distinctive_descriptor(desc):

@@ -49,6 +49,15 @@ float sadL1(const Level& L, int lx, int ly, const Level& R, int rx, int ry) {
 }
 }  // namespace
 
+// traceS / traceComplete (both or neither, nLeft entries): per left keypoint k the index `leftIdx` its step used (for the descriptor
+// row and the output slot) and whether the step reached `leftIdx++` (:462).  Tests use them to say where the lagging index stood at a
+// given keypoint; the outputs do not depend on them.
+static int stereoMatchesImpl(const void* kpsLeft, const uint8_t* descLeft, int nLeft, const void* kpsRight, const uint8_t* descRight,
+                             int nRight, const uint8_t* const* leftPtr, const uint8_t* const* rightPtr, const int* w, const int* h,
+                             const int* strideLeft, const int* strideRight, int nLevels, const float* scale, const float* invScale,
+                             float bf, float b, int flags, float* rightXOut, float* depthOut, int* status, int* traceS,
+                             uint8_t* traceComplete);
+
 extern "C" {
 
 // levels: per side nLevels x {ptr,w,h,stride}; scale / invScale: m_v_scaleFactors / m_v_invScaleFactors.
@@ -59,6 +68,27 @@ int yo_stereo_matches(const void* kpsLeft, const uint8_t* descLeft, int nLeft, c
                       int nRight, const uint8_t* const* leftPtr, const uint8_t* const* rightPtr, const int* w, const int* h,
                       const int* strideLeft, const int* strideRight, int nLevels, const float* scale, const float* invScale,
                       float bf, float b, int flags, float* rightXOut, float* depthOut, int* status) {
+  return stereoMatchesImpl(kpsLeft, descLeft, nLeft, kpsRight, descRight, nRight, leftPtr, rightPtr, w, h, strideLeft, strideRight, nLevels,
+                           scale, invScale, bf, b, flags, rightXOut, depthOut, status, nullptr, nullptr);
+}
+
+// The same walk with the per-step trace (see stereoMatchesImpl).
+int yo_stereo_matches_trace(const void* kpsLeft, const uint8_t* descLeft, int nLeft, const void* kpsRight, const uint8_t* descRight,
+                            int nRight, const uint8_t* const* leftPtr, const uint8_t* const* rightPtr, const int* w, const int* h,
+                            const int* strideLeft, const int* strideRight, int nLevels, const float* scale, const float* invScale,
+                            float bf, float b, int flags, float* rightXOut, float* depthOut, int* status, int* traceS,
+                            uint8_t* traceComplete) {
+  return stereoMatchesImpl(kpsLeft, descLeft, nLeft, kpsRight, descRight, nRight, leftPtr, rightPtr, w, h, strideLeft, strideRight, nLevels,
+                           scale, invScale, bf, b, flags, rightXOut, depthOut, status, traceS, traceComplete);
+}
+
+}  // extern "C"
+
+static int stereoMatchesImpl(const void* kpsLeft, const uint8_t* descLeft, int nLeft, const void* kpsRight, const uint8_t* descRight,
+                             int nRight, const uint8_t* const* leftPtr, const uint8_t* const* rightPtr, const int* w, const int* h,
+                             const int* strideLeft, const int* strideRight, int nLevels, const float* scale, const float* invScale,
+                             float bf, float b, int flags, float* rightXOut, float* depthOut, int* status, int* traceS,
+                             uint8_t* traceComplete) {
   const Kp* KL = (const Kp*)kpsLeft;
   const Kp* KR = (const Kp*)kpsRight;
   const int rowsNum = h[0];
@@ -82,6 +112,10 @@ int yo_stereo_matches(const void* kpsLeft, const uint8_t* descLeft, int nLeft, c
   for (int k = 0; k < nLeft; k++) {
     const Kp& kp = KL[k];
     if (flags & 1) leftIdx = k;
+    if (traceS) {
+      traceS[k] = leftIdx;
+      traceComplete[k] = 0;
+    }
     const int row = (int)kp.y;  // float -> index conversion at :389
     if (!(kp.y >= 0.0f) || row >= rowsNum) {
       st |= 1;
@@ -137,6 +171,7 @@ int yo_stereo_matches(const void* kpsLeft, const uint8_t* descLeft, int nLeft, c
         distIdx.push_back(std::make_pair(sadBest, leftIdx));
       }
     }
+    if (traceS) traceComplete[k] = 1;
     leftIdx++;  // :462
   }
   std::sort(distIdx.begin(), distIdx.end());  // :464-472
@@ -151,5 +186,3 @@ int yo_stereo_matches(const void* kpsLeft, const uint8_t* descLeft, int nLeft, c
   if (status) *status = st;
   return (int)distIdx.size();
 }
-
-}  // extern "C"

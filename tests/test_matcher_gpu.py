@@ -2,7 +2,8 @@
 import numpy as np
 import pytest
 
-from helpers import bow_nodes, feature_vector, projection_queries, shifted_pair
+from helpers import (bow_nodes, contention_case, contention_occurrence, feature_vector, natural_queries, plant_contention, projection_queries,
+                     shifted_pair)
 
 pytestmark = pytest.mark.gpu
 
@@ -426,3 +427,78 @@ def test_match_pairs_on_the_gathered_layouts_of_every_rank(world):
             seen.add(g)
             assert int(c[i]) == int(ref_c[g]) and torch.equal(a[i], ref_a[g]), (rank, g)
     assert seen == set(range(G - 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Contention in the resolve step.  With the gather kernel's (best, second) records k_resolve decides 64 live queries per step, one per
+# lane, and is right only if it notices every query whose outcome depends on a query before it.  The natural scenes above meet such
+# cases by luck; here they are planted (tests/helpers.py: plant_contention) and the serial oracle's output says, before the GPU runs,
+# that each kind really happened (contention_case asserts the counts).
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [0, 1, 2, 7])
+def test_resolve_contention_in_search_by_projection(oracle_lib, scene, mode):
+    """Copies of a query right behind it and a few queries later (observed: the later one loses the keypoint; unobserved, modes 0 and 1:
+    the later one owns the assignment), keypoints taken before the call, and for mode 0 queries whose ratio test flips once an earlier
+    query has taken their second-best keypoint - inside a 64-lane group and across group edges.  Identical integers to the oracle."""
+    import ydorbslam_amd as y
+    s, ratio = scene[0], 0.9
+    case = contention_case(oracle_lib, s, mode, 900 + mode, ratio)           # CPU: the planted situations occurred in the oracle's run
+    fv = y.FrameView(s["kb"], s["db"], s["bounds"], None)
+    for check, (n_ref, a_ref, t_ref) in case["ref"].items():
+        n_gpu, a_gpu, t_gpu = y.OrbMatcher(ratio, check).search_by_projection(mode, fv, case["q"], case["d"], case["taken0"], case["assigned0"], orb_dist=64)
+        bad = np.flatnonzero(a_gpu != a_ref)
+        assert len(bad) == 0, (mode, check, "first keypoints whose owner differs", bad[:8].tolist(), a_gpu[bad[:8]].tolist(), a_ref[bad[:8]].tolist())
+        assert np.array_equal(t_gpu, t_ref) and n_gpu == n_ref, (mode, check, n_gpu, n_ref)
+
+
+def test_resolve_contention_in_the_fuse_search(oracle_lib, scene):
+    """Mode 6 (the fuse / Sim3 window search, nothing is taken): two lanes of a group accept one keypoint and both must keep it."""
+    import ydorbslam_amd as y
+    s = scene[0]
+    case = contention_case(oracle_lib, s, 6, 906)
+    zero = np.zeros(8, np.float32)
+    fv = y.FrameView(s["kb"], s["db"], s["bounds"], None)
+    for max_dist in (50, 100):
+        n_ref, b_ref = case["fo"].fuse_search(case["q"], case["d"], zero, max_dist)
+        n_gpu, b_gpu = y.OrbMatcher(0.6, True).fuse_search(fv, case["q"], case["d"], zero, max_dist)
+        assert n_gpu == n_ref and np.array_equal(b_gpu, b_ref), max_dist
+
+
+def test_resolve_contention_in_match_pairs_device(oracle_lib, scene):
+    """Mode 1 as the device-resident pair search runs it (queries built on the device from frame A's keypoints, every accept takes):
+    duplicated keypoints in frame A whose descriptor is that of a keypoint of frame B.  Equal to the host call and to the oracle."""
+    import torch
+    import ydorbslam_amd as y
+    s = scene[0]
+    kb, db, W, H = s["kb"], s["db"], s["w"], s["h"]
+    sf = s["sf"].astype(np.float32)
+    fo = oracle_lib.FrameOracle(kb, db, s["bounds"], None)
+    case = plant_contention(fo, s, 1, natural_queries(s, "kp", 0), s["da"], 911, kinds=("observed", "distant"), with_taken=False)
+    q, qd = case["q"], case["d"]
+    nq, nt = len(q), len(kb)
+    ref = {check: fo.search_by_projection(1, q, qd, 0.9, check) for check in (False, True)}
+    occurred, place = contention_occurrence(fo, 1, case, 0.9, ref[False][1], ref[False][2])
+    assert occurred["observed"] >= 8 and occurred["distant"] >= 8 and place["observed"][1] >= 1 and place["distant"][1] >= 1, (occurred, place)
+    ka = np.zeros(nq, y.KP_DTYPE)
+    ka["x"], ka["y"], ka["octave"], ka["angle"] = q["u"], q["v"], q["level"], q["angle"]
+    again = natural_queries(dict(s, ka=ka), "kp", 0)                                 # the device derives exactly these queries from ka
+    assert again.tobytes() == q.tobytes()
+    cap = max(nq, nt) + 5
+    kps = np.zeros((2, cap), y.KP_DTYPE); desc = np.zeros((2, cap, 32), np.uint8)
+    kps[0, :nq], kps[1, :nt], desc[0, :nq], desc[1, :nt] = ka, kb, qd, db
+    dev = torch.device("cuda:0")
+    d_kps = torch.from_numpy(kps.view(np.uint8).reshape(2, cap, 28)).to(dev)
+    d_desc = torch.from_numpy(desc).to(dev)
+    d_n = torch.tensor([nq, nt], dtype=torch.int32, device=dev)
+    fs = (d_kps.data_ptr(), d_desc.data_ptr(), d_n.data_ptr(), 2, cap)
+    for check in (False, True):
+        m = y.OrbMatcher(0.9, check)
+        d_assigned = torch.zeros((1, cap), dtype=torch.int32, device=dev)
+        d_counts = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        m.match_pairs_device(fs, fs, [(0, 1)], W, H, 15.0, sf, d_assigned.data_ptr(), d_counts.data_ptr())
+        m.synchronize()
+        n_host, a_host, _ = m.search_by_projection(1, y.FrameView(kb, db, s["bounds"], None), q, qd)
+        a_dev = d_assigned.cpu().numpy()[0, :nt]
+        assert int(d_counts[0]) == n_host == ref[check][0]
+        assert np.array_equal(a_dev, a_host) and np.array_equal(a_host, ref[check][1])

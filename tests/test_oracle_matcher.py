@@ -1,7 +1,9 @@
 """Oracle matcher (oracle/matcher_oracle.cpp): cross-checks against independent numpy statements of the same rules."""
 import numpy as np
 
-from helpers import bow_nodes, feature_vector, projection_queries, shifted_pair
+import pytest
+
+from helpers import bow_nodes, contention_case, feature_vector, projection_queries, shifted_pair
 
 
 def _scene(oracle_lib, idx=50, dx=5, dy=-3):
@@ -264,3 +266,21 @@ def test_hamming_topk_chain_against_numpy(oracle_lib):
             assert list(got[i].tolist()) == exp, (i, got[i], exp)
     assert oracle_lib.hamming_topk(q[:1], t)[0]["best_idx"] == 3 and oracle_lib.hamming_topk(q[:1], t)[0]["second_idx"] == 7
     assert oracle_lib.hamming_topk(q[1:2], t, np.array([0, 1], np.int32), np.array([10], np.int32))[0].tolist() == (256, -1, 256, -1, -1, -1)
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 7, 6])
+def test_planted_contention_occurs_in_the_serial_walk(oracle_lib, mode):
+    """The planted query sets of tests/test_matcher_gpu.py's resolve-contention tests, on the oracle alone: with the seeds those tests
+    use, each planted kind changes the outcome of a later query often enough (contention_case asserts the counts), and every planted
+    query that should find its keypoint does."""
+    ka, da, kb, db, sf = _scene(oracle_lib)
+    s = dict(ka=ka, da=da, kb=kb, db=db, dx=5, dy=-3, sf=sf, w=640, h=480, bounds=(0.0, 640.0, 0.0, 480.0))
+    case = contention_case(oracle_lib, s, mode, 900 + mode)
+    assert len(case["planted"]) >= 64 and len(case["q"]) > len(ka)
+    if mode != 6:
+        n_ref, a_ref, t_ref = case["ref"][False]
+        owners = int(((a_ref >= 0) & (a_ref < len(case["q"]))).sum())
+        assert n_ref >= owners > 50 and (n_ref == owners or mode < 2)          # (unobserved accepts share a keypoint: modes 0 and 1 only)
+        for p in case["planted"]:
+            if p["kind"] == "pretaken":
+                assert t_ref[p["X"]] == 1 and a_ref[p["X"]] == 100000 + p["X"]

@@ -86,11 +86,13 @@ def test_oracle_matches_numpy_statement(oracle_lib):
         rx, depth, kept, st = oracle_lib.stereo_matches(P["kl"], P["dl"], P["kr"], P["dr"], P["lv_l"], P["lv_r"], P["scale"], P["inv"], bf, b, by_kp)
         erx = np.full(len(P["kl"]), -1, np.float32)
         edp = np.full(len(P["kl"]), -1, np.float32)
-        sads, s = [], 0
+        sads, s, used, dones = [], 0, [], []
         for k in range(len(P["kl"])):
             if by_kp:
                 s = k
             done, x, d, sad = _numpy_one(P, k, s, bf, b)
+            used.append(s)
+            dones.append(int(done))
             if x is not None:
                 erx[s], edp[s] = x, d
                 sads.append(sad)
@@ -101,6 +103,54 @@ def test_oracle_matches_numpy_statement(oracle_lib):
         assert kept == len(sads) and st == 0
         assert np.array_equal(rx.view(np.uint32), erx.view(np.uint32)), by_kp
         assert np.array_equal(depth.view(np.uint32), edp.view(np.uint32)), by_kp
+        # the traced walk: the same outputs, and per step the index and the `leftIdx++` flag of the numpy statement
+        t = oracle_lib.stereo_matches_trace(P["kl"], P["dl"], P["kr"], P["dr"], P["lv_l"], P["lv_r"], P["scale"], P["inv"], bf, b, by_kp)
+        assert t[0].tobytes() == rx.tobytes() and t[1].tobytes() == depth.tobytes() and t[2:4] == (kept, st)
+        assert t[4].tolist() == used and t[5].tolist() == dones
+
+
+def _check_trace(rx, depth, s, complete, by_kp):
+    """What the trace must satisfy given the outputs alone."""
+    n = len(s)
+    assert len(complete) == n == len(rx) and set(np.unique(complete).tolist()) <= {0, 1}
+    if n == 0:
+        return
+    assert s[0] == 0
+    if by_kp:
+        assert np.array_equal(s, np.arange(n))
+    else:
+        assert np.array_equal(s[1:], s[:-1] + complete[:-1])                     # s_{k+1} = s_k + complete_k
+    written = np.flatnonzero((depth != -1) | (rx != -1))                          # kept (or culled to -2) outputs
+    assert np.isin(written, s).all()                                              # ... sit at an index some step used
+    assert np.isin(written, s[complete > 0]).all()                                # (a kept step always reaches leftIdx++)
+    assert np.all(rx[s.max() + 1:] == -1) and np.all(depth[s.max() + 1:] == -1)  # nothing beyond the last index used
+
+
+def test_trace_is_consistent_with_the_outputs(oracle_lib):
+    """The optional per-step trace (index used, `leftIdx++` reached) against the untraced call's outputs: natural descriptors, and the
+    noise / copied-descriptor construction that makes the index lag far behind the keypoint."""
+    bf, b = 40.0, 0.1
+    rng = np.random.default_rng(3)
+    for index, spoil in ((0, False), (2, False), (3, True)):
+        P = _pair(oracle_lib, index)
+        dl = P["dl"].copy()
+        if spoil:
+            dl[1::2] = rng.integers(0, 256, dl[1::2].shape, dtype=np.uint8)
+            dl[::3] = P["dr"][len(P["dr"]) // 2]
+        for by_kp in (False, True):
+            args = (P["kl"], dl, P["kr"], P["dr"], P["lv_l"], P["lv_r"], P["scale"], P["inv"], bf, b, by_kp)
+            rx, depth, kept, st = oracle_lib.stereo_matches(*args)
+            t = oracle_lib.stereo_matches_trace(*args)
+            assert t[0].tobytes() == rx.tobytes() and t[1].tobytes() == depth.tobytes() and t[2:4] == (kept, st)
+            _check_trace(rx, depth, t[4], t[5], by_kp)
+            if not by_kp:
+                assert 0 < t[5].sum() < len(t[5])          # both kinds of step occur
+                if spoil:
+                    assert (np.arange(len(t[4])) - t[4]).max() > 4    # the index falls behind by more than the replay kernel keeps in flight
+    # an empty left side
+    P = _pair(oracle_lib, 0, 300)
+    t = oracle_lib.stereo_matches_trace(P["kl"][:0], P["dl"][:0], P["kr"], P["dr"], P["lv_l"], P["lv_r"], P["scale"], P["inv"], bf, b)
+    assert t[2] == 0 and len(t[4]) == 0 == len(t[5])
 
 
 def test_per_keypoint_form_recovers_the_disparity(oracle_lib):

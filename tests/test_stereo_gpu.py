@@ -1,5 +1,13 @@
 """GPU parity: ydorb_stereo_matches (C ABI) vs oracle/stereo_oracle.cpp, the restatement of Frame::computeStereoMatches
-(reference src/frame.cpp:362-477).  Bar: identical float bit patterns.  Parity unpinned (see the oracle's header)."""
+(reference src/frame.cpp:362-477).  Bar: identical float bit patterns.  Parity unpinned (see the oracle's header).
+
+The replay form (the serial `leftIdx` walk) runs as ONE launch per call for fewer than 8 pairs or at most 1024 keypoints, and in
+slices that hand the lagging index from launch to launch otherwise.  The tests of the sliced path, all against the oracle:
+  test_default_slicing_of_a_ragged_batch        12 pairs above 1024 keypoints, no environment variable: nL around the slice edge
+  test_chosen_slices                            YDORB_STEREO_SLICE 37..40 (each wave writes the hand-over), 3 and 1, both candidate forms
+  test_lagging_index_across_slice_boundaries    slice edges placed by the oracle's trace where the index lags and a step did not complete
+  test_sliced_device_resident_form              the device-pointer form of the 12-pair batch
+Every other test here takes the one-launch path."""
 import numpy as np
 import pytest
 
@@ -251,3 +259,227 @@ def test_right_keypoints_crowded_into_a_few_rows(oracle_lib):
     _, (orx, odepth, okept, ostatus) = _oracle_pair(oracle_lib, left, right, 1000, kl=kl2, dl=dl, kr=kr2, dr=dr)
     assert got[2][0] == okept and got[3][0] == ostatus
     assert np.array_equal(got[0][0].view(np.uint32), orx.view(np.uint32)) and np.array_equal(got[1][0].view(np.uint32), odepth.view(np.uint32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The sliced replay.  A batch is several members over ONE extracted pyramid pair (frame step 0): keypoint and descriptor arrays are
+# plain inputs to both sides, so members differ by truncation (ragged nL / nR) and by their left descriptors.
+# ---------------------------------------------------------------------------------------------------------------------------------
+REPLAY_WAVES = 4   # waves that share a pair's walk in k_stereo<true>: three steps are speculated ahead of the exact index
+
+
+def _shared_scene(w, h, nf, index, disparities=(7, 15, 26), gpu=True):
+    """One stereo pair: keypoints, descriptors and level images from the oracle extractor and, with gpu, the same pair extracted
+    by a device extractor whose pyramids the stereo call reads (frames 0 and 1 of its last call)."""
+    from oracle.orb_oracle import OrbExtractorOracle
+    left, right, _ = synth_stereo_pair(w, h, index, disparities=disparities)
+    el, er = OrbExtractorOracle(nf), OrbExtractorOracle(nf)
+    kl, dl = el.extract(left)
+    kr, dr = er.extract(right)
+    lv_l = [el.level_padded(l)[19:19 + el.level_dims(l)[1], 19:19 + el.level_dims(l)[0]] for l in range(8)]
+    lv_r = [er.level_padded(l)[19:19 + er.level_dims(l)[1], 19:19 + er.level_dims(l)[0]] for l in range(8)]
+    t = el.tables()
+    S = dict(kl=kl, dl=dl, kr=kr, dr=dr, lv_l=lv_l, lv_r=lv_r, scale=t["scale"], inv=t["inv_scale"], ex=None)
+    if gpu:
+        import ydorbslam_amd as y
+        ex = y.OrbExtractor(nf, 1.2, 8, 20, 7, max_batch=2)
+        (gkl, gdl), (gkr, gdr) = ex.extract_batch(np.stack([left, right]))
+        assert gkl.tobytes() == kl.tobytes() and gkr.tobytes() == kr.tobytes() and np.array_equal(gdl, dl) and np.array_equal(gdr, dr)
+        S["ex"] = ex
+    return S
+
+
+def _spoiled(S, seed):
+    """Left descriptors of test_index_chain_that_depends_on_the_descriptor_history: every other row noise, every third a copy of one
+    right descriptor - the index then falls behind the keypoint and the kernel's guesses of it fail."""
+    rng = np.random.default_rng(seed)
+    dl = S["dl"].copy()
+    dl[1::2] = rng.integers(0, 256, dl[1::2].shape, dtype=np.uint8)
+    dl[::3] = S["dr"][len(S["dr"]) // 2]
+    return dl
+
+
+def _oracle_members(oracle_lib, S, members):
+    """members: list of (nL, nR, left descriptors [len(kl), 32]).  The oracle's (rx, depth, kept, status, s, complete) per member."""
+    return [oracle_lib.stereo_matches_trace(S["kl"][:nl], dl[:nl], S["kr"][:nr], S["dr"][:nr], S["lv_l"], S["lv_r"], S["scale"], S["inv"], BF, B)
+            for nl, nr, dl in members]
+
+
+def _batch_arrays(S, members):
+    """[members, cap] inputs: every member carries the FULL keypoint / descriptor arrays and only its counts say where it ends, so a
+    kernel that walked past nL or nR would find real data there."""
+    n = len(members)
+    kl = np.ascontiguousarray(np.tile(S["kl"], (n, 1)))
+    kr = np.ascontiguousarray(np.tile(S["kr"], (n, 1)))
+    dl = np.ascontiguousarray(np.stack([m[2] for m in members]))
+    dr = np.ascontiguousarray(np.tile(S["dr"], (n, 1, 1)))
+    nl = np.array([m[0] for m in members], np.int32)
+    nr = np.array([m[1] for m in members], np.int32)
+    return kl, dl, nl, kr, dr, nr
+
+
+def _assert_equals_oracle(got, ref, members, what=""):
+    rx, depth, kept, status = got
+    for p, ((nl, nr, _), (orx, odepth, okept, ostatus, _, _)) in enumerate(zip(members, ref)):
+        assert kept[p] == okept and status[p] == ostatus, (what, p, nl, nr, int(kept[p]), okept, int(status[p]), ostatus)
+        bad = np.flatnonzero((rx[p, :nl].view(np.uint32) != orx.view(np.uint32)) | (depth[p, :nl].view(np.uint32) != odepth.view(np.uint32)))
+        assert len(bad) == 0, (what, p, nl, nr, "first differing output slots", bad[:8].tolist())
+        assert np.all(rx[p, nl:] == -1) and np.all(depth[p, nl:] == -1), (what, p, "padding written")
+
+
+def _run_host(S, members):
+    import ydorbslam_amd as y
+    kl, dl, nl, kr, dr, nr = _batch_arrays(S, members)
+    return y.OrbMatcher().stereo_matches(S["ex"], S["ex"], kl, dl, nl, kr, dr, nr, BF, B, left_frames=(0, 0), right_frames=(1, 0))
+
+
+def _kitti_members(S):
+    """The ragged 12-member batch of the default-slicing tests (slice 1024): counts around the slice edge, natural and spoiled
+    descriptors, short and empty right sides."""
+    n, nr = len(S["kl"]), len(S["kr"])
+    assert n > 1100 and nr > 1100, (n, nr)
+    nat, sp1, sp2 = S["dl"], _spoiled(S, 5), _spoiled(S, 6)
+    return [(n, nr, nat), (1024, nr, sp1), (1025, nr, sp1), (700, nr, nat), (0, nr, nat), (n, nr, sp1), (n - 3, 1200, sp2), (1026, nr, nat),
+            (1023, nr, sp2), (n, 0, nat), (1, nr, nat), (1500, nr, sp2)]
+
+
+@pytest.fixture(scope="module")
+def kitti_scene(oracle_lib):
+    """KITTI-size pair (BASELINE.json config 3): capacity above 1024, so 8 or more members are walked in slices of 1024."""
+    S = _shared_scene(1241, 376, 2000, 11)
+    S["members"] = _kitti_members(S)
+    S["ref"] = _oracle_members(oracle_lib, S, S["members"])
+    return S
+
+
+def test_default_slicing_of_a_ragged_batch(oracle_lib, kitti_scene, monkeypatch):
+    """12 members, capacity > 1024, no environment variable: the host cuts the walk at 1024.  nL == 1024 ends with the first slice
+    (nothing handed over, the second launch returns at once), nL == 1025 leaves one step that wave 0 runs alone, nL above, below, 1, 0."""
+    monkeypatch.delenv("YDORB_STEREO_SLICE", raising=False)
+    monkeypatch.delenv("YDORB_STEREO_NO_ROW_LISTS", raising=False)
+    S = kitti_scene
+    members, ref = S["members"], S["ref"]
+    nls = [m[0] for m in members]
+    assert len(members) >= 8 and len(S["kl"]) > 1024
+    assert sum(nl > 1025 for nl in nls) >= 3 and 1024 in nls and 1025 in nls and 0 in nls and any(0 < nl < 1024 for nl in nls)
+    # the index really is handed over in different states: behind the keypoint for some members, level with it for none of the long ones
+    lag = [1024 - int(r[4][1024]) for (nl, _, _), r in zip(members, ref) if nl > 1024]
+    assert max(lag) > REPLAY_WAVES and sum(r[2] for r in ref) > 100, lag
+    _assert_equals_oracle(_run_host(S, members), ref, members, "default slice")
+
+
+@pytest.mark.parametrize("slice_len,no_lists", [(37, False), (38, False), (39, False), (40, False), (3, False), (39, True), (3, True)])
+def test_chosen_slices(oracle_lib, slice_len, no_lists, monkeypatch):
+    """YDORB_STEREO_SLICE per call.  The wave that ran the last step of a slice writes the hand-over: slices of 37, 38, 39 and 40 steps
+    make that wave 0, 1, 2 and 3; in slices of 3 steps one wave never has a step.  Candidates from the row lists or the band scan."""
+    S = _chosen_scene(oracle_lib)
+    members, ref = S["members"], S["ref"]
+    assert len(members) >= 2 and {(L - 1) % REPLAY_WAVES for L in (37, 38, 39, 40)} == set(range(REPLAY_WAVES)) and 3 < REPLAY_WAVES
+    monkeypatch.setenv("YDORB_STEREO_SLICE", str(slice_len))
+    if no_lists:
+        monkeypatch.setenv("YDORB_STEREO_NO_ROW_LISTS", "1")
+    else:
+        monkeypatch.delenv("YDORB_STEREO_NO_ROW_LISTS", raising=False)
+    _assert_equals_oracle(_run_host(S, members), ref, members, "slice %d" % slice_len)
+
+
+_CHOSEN = {}
+
+
+def _chosen_scene(oracle_lib):
+    """640x480 / 800 features, three members: natural, spoiled and a spoiled one cut short (one extraction for every slice length)."""
+    if not _CHOSEN:
+        S = _shared_scene(640, 480, 800, 21, disparities=(9, 9, 9))
+        n, nr = len(S["kl"]), len(S["kr"])
+        S["members"] = [(n, nr, S["dl"]), (n, nr, _spoiled(S, 3)), (n - 150, nr - 40, _spoiled(S, 4))]
+        S["ref"] = _oracle_members(oracle_lib, S, S["members"])
+        _CHOSEN.update(S)
+    return _CHOSEN
+
+
+def test_slices_of_one_step(oracle_lib, monkeypatch):
+    """Slice 1 on a small frame: every step reads the hand-over and writes it, wave 0 alone (a few hundred launches per call)."""
+    S = _shared_scene(480, 360, 300, 22, disparities=(9, 9, 9))
+    n, nr = len(S["kl"]), len(S["kr"])
+    assert 100 < n < 600
+    members = [(n, nr, S["dl"]), (n - 7, nr, _spoiled(S, 8))]
+    ref = _oracle_members(oracle_lib, S, members)
+    assert all(0 < r[5].sum() < len(r[5]) for r in ref)     # steps that complete and steps that do not
+    monkeypatch.delenv("YDORB_STEREO_NO_ROW_LISTS", raising=False)
+    monkeypatch.setenv("YDORB_STEREO_SLICE", "1")
+    _assert_equals_oracle(_run_host(S, members), ref, members, "slice 1")
+
+
+def _boundary_kinds(ref, members, slice_len):
+    """Over the slice edges kBegin = slice_len, 2 * slice_len, ... < nL of every member, from the oracle's trace: how many follow a step
+    that did not reach `leftIdx++`, how many follow one that did, and at how many the index is more than REPLAY_WAVES behind kBegin."""
+    incomplete = complete = lagging = 0
+    for (nl, _, _), r in zip(members, ref):
+        s, c = r[4], r[5]
+        for kb in range(slice_len, nl, slice_len):
+            incomplete += int(c[kb - 1] == 0)
+            complete += int(c[kb - 1] == 1)
+            lagging += int(kb - int(s[kb]) > REPLAY_WAVES)
+    return incomplete, complete, lagging
+
+
+def _lagging_plan(oracle_lib, gpu=True):
+    """Scene, members, oracle results and slice lengths of test_lagging_index_across_slice_boundaries: 37..40 and three lengths that put
+    an edge right behind a step that did not complete, read off the oracle's trace of the spoiled member."""
+    S = _shared_scene(640, 480, 700, 20, disparities=(9, 9, 9), gpu=gpu)
+    n, nr = len(S["kl"]), len(S["kr"])
+    members = [(n, nr, _spoiled(S, 3)), (n - 61, nr, _spoiled(S, 13))]
+    ref = _oracle_members(oracle_lib, S, members)
+    s, c = ref[0][4], ref[0][5]
+    after_skip = [k + 1 for k in range(40, n - 1) if c[k] == 0 and (k + 1) - int(s[k + 1]) > REPLAY_WAVES]
+    assert len(after_skip) >= 3, "the spoiled descriptors leave no incomplete step with a lagging index"
+    slices = [37, 38, 39, 40] + [after_skip[0], after_skip[len(after_skip) // 2], after_skip[-1]]
+    return S, members, ref, slices
+
+
+def test_lagging_index_across_slice_boundaries(oracle_lib, monkeypatch):
+    """Noise rows and copies of one right descriptor make the index fall behind the keypoint and the speculating waves' guesses fail.
+    Checked on the oracle's trace before anything runs on the GPU: among the slice edges walked there is one behind a step that did not
+    complete, one behind a step that did, and one where the index handed over is more than the wave count behind kBegin."""
+    S, members, ref, slices = _lagging_plan(oracle_lib)
+    totals = np.sum([_boundary_kinds(ref, members, L) for L in slices], axis=0)
+    assert totals[0] >= 1 and totals[1] >= 1 and totals[2] >= 1, totals.tolist()
+    for L in slices[4:]:                              # each of the placed edges has all three properties but `complete`
+        k = _boundary_kinds(ref, members[:1], L)
+        assert k[0] >= 1 and k[2] >= 1, (L, k)
+    monkeypatch.delenv("YDORB_STEREO_NO_ROW_LISTS", raising=False)
+    for L in slices:
+        monkeypatch.setenv("YDORB_STEREO_SLICE", str(L))
+        _assert_equals_oracle(_run_host(S, members), ref, members, "slice %d" % L)
+
+
+def test_sliced_device_resident_form(oracle_lib, kitti_scene, monkeypatch):
+    """The 12-member batch of test_default_slicing_of_a_ragged_batch through the device-pointer form: the same bits as the host form
+    (and so the oracle's), default slices of 1024."""
+    import torch
+    import ydorbslam_amd as y
+    monkeypatch.delenv("YDORB_STEREO_SLICE", raising=False)
+    monkeypatch.delenv("YDORB_STEREO_NO_ROW_LISTS", raising=False)
+    S = kitti_scene
+    members, ref = S["members"], S["ref"]
+    kl, dl, nl, kr, dr, nr = _batch_arrays(S, members)
+    pairs, cap_l, cap_r = len(members), kl.shape[1], kr.shape[1]
+    assert pairs >= 8 and cap_l > 1024
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    d_kl, d_dl, d_nl, d_kr, d_dr, d_nr = up(kl), up(dl), up(nl), up(kr), up(dr), up(nr)
+    d_rx = torch.zeros((pairs, cap_l), dtype=torch.float32, device=dev)
+    d_depth = torch.zeros((pairs, cap_l), dtype=torch.float32, device=dev)
+    d_kept = torch.zeros(pairs, dtype=torch.int32, device=dev)
+    d_status = torch.full((pairs,), 7, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    m = y.OrbMatcher()
+    m.stereo_matches_device(S["ex"], S["ex"], d_kl.data_ptr(), d_dl.data_ptr(), d_nl.data_ptr(), cap_l, d_kr.data_ptr(), d_dr.data_ptr(), d_nr.data_ptr(),
+                            cap_r, pairs, BF, B, d_rx.data_ptr(), d_depth.data_ptr(), d_kept.data_ptr(), d_status.data_ptr(),
+                            left_frames=(0, 0), right_frames=(1, 0))
+    m.synchronize()
+    got = (d_rx.cpu().numpy(), d_depth.cpu().numpy(), d_kept.cpu().numpy(), d_status.cpu().numpy())
+    host = _run_host(S, members)
+    for a, b in zip(got, host):
+        assert np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a, b.view(np.uint32) if b.dtype == np.float32 else b)
+    _assert_equals_oracle(got, ref, members, "device form")

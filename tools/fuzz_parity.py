@@ -1,5 +1,8 @@
 """One-off differential sweep on the GPU box: random image sizes / extractor configurations / matcher inputs / BA and pose problems,
-product vs oracle.  Not part of the test suite (the suite pins fixed cases); run it after kernel changes:  python tools/fuzz_parity.py 120"""
+product vs oracle.  Not part of the test suite (the suite pins fixed cases); run it after kernel changes:  python tools/fuzz_parity.py 120
+Arguments: seconds [seed [stereo batch [stereo slice]]].  A stereo batch of 8 or more members (default 10) walks frames of more than 1024
+keypoints in slices; a stereo slice > 0 is set as YDORB_STEREO_SLICE (read per call), 0 (default) draws one per case: none, 1 for small
+frames, or a random length."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -11,6 +14,8 @@ from helpers import bow_nodes, feature_vector, projection_queries
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 12345)
+stereo_batch = max(1, int(sys.argv[3])) if len(sys.argv) > 3 else 10
+stereo_slice = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 t0 = time.time()
 n_ex = n_ma = n_ba = n_po = n_st = n_bw = 0
 while time.time() - t0 < budget:
@@ -83,6 +88,25 @@ while time.time() - t0 < budget:
                     for i in bad[:5]:
                         print("  slot", i, "gpu", p_[0][0][i], p_[1][0][i], "oracle", o_[0][i], o_[1][i], "kp", lk[i])
                     raise AssertionError(("stereo", w, h, nf, sf, nl, thr, dsp, by_kp, bf, bl))
+            # the sliced replay: a batch over this one pyramid pair (frame step 0), members cut to ragged lengths around the slice edges
+            if stereo_batch > 1 or stereo_slice > 0:
+                n_ = len(lk)
+                sl_ = stereo_slice if stereo_slice > 0 else int(rng.choice([0, 1 if n_ <= 400 else 0, int(rng.integers(2, max(n_, 3)))]))
+                edge = sl_ if sl_ > 0 else 1024
+                cuts = [n_, min(n_, edge), min(n_, edge + 1), max(0, min(n_, edge) - 1), 0] + [int(x) for x in rng.integers(0, n_ + 1, max(stereo_batch - 5, 0))]
+                cuts = cuts[:stereo_batch]
+                if sl_ > 0: os.environ["YDORB_STEREO_SLICE"] = str(sl_)
+                try:
+                    B_ = len(cuts)
+                    p_ = y.OrbMatcher().stereo_matches(g, g2, np.tile(lk, (B_, 1)), np.tile(gd, (B_, 1, 1)), cuts, np.tile(rk, (B_, 1)), np.tile(rd, (B_, 1, 1)),
+                                                       [len(rk)] * B_, bf, bl, False, left_frames=(0, 0), right_frames=(0, 0))
+                finally:
+                    os.environ.pop("YDORB_STEREO_SLICE", None)
+                for i_, c_ in enumerate(cuts):
+                    o_ = oo.stereo_matches(lk[:c_], gd[:c_], rk, rd, lv_l, lv_r, tb["scale"], tb["inv_scale"], bf, bl, False)
+                    ok_ = (p_[2][i_] == o_[2] and p_[3][i_] == o_[3] and p_[0][i_, :c_].tobytes() == o_[0].tobytes() and p_[1][i_, :c_].tobytes() == o_[1].tobytes()
+                           and np.all(p_[1][i_, c_:] == -1))
+                    assert ok_, ("stereo batch", w, h, nf, sf, nl, thr, dsp, bf, bl, "slice", sl_, "member", i_, "nL", c_, "of", n_)
             n_st += 1
     # ---- vocabulary transform + distinctive descriptors on this frame's descriptors
     if len(gk) > 0 and len(gk) <= 8192 and rng.random() < 0.4:

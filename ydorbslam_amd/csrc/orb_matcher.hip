@@ -606,8 +606,10 @@ int ydorb_stereo_matches(ydorb_matcher_t* m, const YdStereoSide* L, const YdSter
   if (flags & YDORB_STEREO_INDEX_BY_KEYPOINT)
     hipLaunchKernelGGL(k_stereo<false>, dim3((L->cap + kStereoChunk - 1) / kStereoChunk, nPairs), dim3(256), lds, s, dP, 0, 0);
   else {
-    // slices of the serial walk (see k_stereo): a batch keeps every launch below ~2 ms; a single pair (the adapter's call) is one launch
-    static const int sliceEnv = getenv("YDORB_STEREO_SLICE") ? atoi(getenv("YDORB_STEREO_SLICE")) : 0;
+    // slices of the serial walk (see k_stereo): a batch keeps every launch below ~2 ms; a single pair (the adapter's call) is one launch.
+    // YDORB_STEREO_SLICE: a per-call diagnostic like YDORB_STEREO_NO_ROW_LISTS (tests walk the same pairs in slices of their choosing)
+    const char* sliceStr = getenv("YDORB_STEREO_SLICE");
+    const int sliceEnv = sliceStr ? atoi(sliceStr) : 0;
     const int slice = sliceEnv > 0 ? sliceEnv : (nPairs >= 8 ? 1024 : L->cap);
     for (int k0 = 0; k0 < L->cap; k0 += slice)
       hipLaunchKernelGGL(k_stereo<true>, dim3(1, nPairs), dim3(256), ldsReplay, s, dP, k0, std::min(k0 + slice, L->cap));
