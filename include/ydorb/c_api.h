@@ -561,6 +561,58 @@ int ydorb_pnp_ransac(YdPnpProblem* probs, int32_t n_probs, int32_t chunk, int32_
 /* ydorb_pnp_ransac keeps device scratch per device between calls; this frees it (waiting for calls in flight). */
 int ydorb_pnp_release(int32_t device);
 
+/* ------------------------------------------------------------------------------------------
+ * KeyFrameDatabase: place-recognition queries.  Replaces KeyFrameDatabase (ORB-SLAM2 src/KeyFrameDatabase.cc; YDORBSLAM
+ * keyFrameDatabase.*) and the DBoW3::Vocabulary::score calls (ScoringObject.cpp) in it and in LoopClosing::detectLoop.  The database
+ * keeps the BowVector of every key frame in HBM; a key frame is known by the slot ydorb_kfdb_add returned.  BowVectors travel in CSR
+ * form: start [n + 1] (start[0] = 0), word ids ascending and unique within a vector (std::map order), double values: the layout
+ * ydorb_vocabulary_transform emits.  A query of more than 8192 words is YDORB_ERR_UNSUPPORTED.  Results are bit-identical to a CPU
+ * restatement compiled with -ffp-contract=off.  Calls on one handle are serialised inside.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ydorb_kfdb ydorb_kfdb_t;
+/* DBoW3::ScoringType.  KL and BHATTACHARYYA are refused with YDORB_ERR_UNSUPPORTED ("unsupported scoring"): they need log(), which
+ * is not bit-reproducible between host libm and the device. */
+#define YDORB_KFDB_L1_NORM 0
+#define YDORB_KFDB_L2_NORM 1
+#define YDORB_KFDB_CHI_SQUARE 2
+#define YDORB_KFDB_KL 3
+#define YDORB_KFDB_BHATTACHARYYA 4
+#define YDORB_KFDB_DOT_PRODUCT 5
+/* status word of a relocalisation query */
+#define YDORB_KFDB_STALE_SCORE 1       /* a neighbour's mRelocScore came from an earlier query (it shares a word but was not scored now) */
+#define YDORB_KFDB_UNWRITTEN_SCORE 2   /* a neighbour's mRelocScore was never written; the reference reads an uninitialised float, here 0.0f */
+
+/* KeyFrameDatabase(voc): scoring = the vocabulary's ScoringType; the capacities are initial sizes, storage grows. */
+int ydorb_kfdb_create(int32_t device, int32_t scoring, int32_t slot_capacity, int64_t word_capacity, ydorb_kfdb_t** out);
+void ydorb_kfdb_destroy(ydorb_kfdb_t* db);
+/* KeyFrameDatabase::add for n key frames: appends each to the database in the given order (the order of the inverted file's lists).
+ * slots [n] out.  A slot freed by erase may be handed out again; the new key frame is a new one in every respect. */
+int ydorb_kfdb_add(ydorb_kfdb_t* db, const int32_t* start, const int32_t* word, const double* value, int32_t n, int32_t* slots);
+/* KeyFrameDatabase::erase */
+int ydorb_kfdb_erase(ydorb_kfdb_t* db, const int32_t* slots, int32_t n);
+/* KeyFrameDatabase::clear */
+int ydorb_kfdb_clear(ydorb_kfdb_t* db);
+/* key frames in the database and slots in use (the length of the diagnostic arrays); either may be NULL */
+int ydorb_kfdb_size(ydorb_kfdb_t* db, int32_t* n_live, int32_t* n_slots);
+/* KeyFrame::getBestCovisibilityKeyFrames(10) of n key frames, as the queries read it: neigh [n][10] slots in the reference's order,
+ * -1 padded.  A neighbour that is not in the database is dropped; one erased later is skipped from then on. */
+int ydorb_kfdb_set_covisibility(ydorb_kfdb_t* db, const int32_t* slots, const int32_t* neigh, int32_t n);
+/* DBoW3::Vocabulary::score(query, key frame) for n slots: LoopClosing::detectLoop's minimum-score loop over the connected key frames. */
+int ydorb_kfdb_score(ydorb_kfdb_t* db, const int32_t* q_word, const double* q_value, int32_t n_words, const int32_t* slots, int32_t n,
+                     double* scores);
+/* KeyFrameDatabase::detectRelocalizationCandidates for n_queries frames, equal to that many single calls in order (mRelocScore of a
+ * key frame carries over from query to query and from call to call).  cand [n_queries][cand_cap]: the returned key frames' slots in
+ * the reference's order; counts [n_queries]: their number (when it exceeds cand_cap only the first cand_cap are written); status
+ * [n_queries], may be NULL: YDORB_KFDB_* bits.  diag_words / diag_score [slots in use], both NULL or both set: common words and
+ * (float)score of the LAST query against every key frame that shares a word with it, 0 elsewhere. */
+int ydorb_kfdb_detect_reloc(ydorb_kfdb_t* db, const int32_t* q_start, const int32_t* q_word, const double* q_value, int32_t n_queries,
+                            int32_t* cand, int32_t cand_cap, int32_t* counts, int32_t* status, int32_t* diag_words, float* diag_score);
+/* KeyFrameDatabase::detectLoopCandidates(pKF, minScore) for n_queries key frames: conn_start [n_queries + 1] / conn_slots = each
+ * query's pKF->getConnectedKeyFrames() (slots; key frames outside the database are left out), min_score [n_queries]. */
+int ydorb_kfdb_detect_loop(ydorb_kfdb_t* db, const int32_t* q_start, const int32_t* q_word, const double* q_value, int32_t n_queries,
+                           const int32_t* conn_start, const int32_t* conn_slots, const float* min_score, int32_t* cand, int32_t cand_cap,
+                           int32_t* counts, int32_t* status, int32_t* diag_words, float* diag_score);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 // (reference thirdParty/DBow3/src/Vocabulary.cpp:752-824, called by Frame::computeBoW / KeyFrame::computeBoW, src/frame.cpp:265-272).
 // System creates `std::make_shared<ydorb::adapter::GpuVocabulary>(path)` where it created a DBoW3::Vocabulary; everything that holds
 // a std::shared_ptr<DBoW3::Vocabulary> (Frame, KeyFrame, KeyFrameDatabase's copy constructor, scoring) keeps working on the base class.
-// Loading, scoring, the inverted file and the other transform overloads stay DBoW3's; only the per-frame transform is replaced.
+// Loading and the other transform overloads stay DBoW3's; only the per-frame transform is replaced here.  Scoring against the stored key
+// frames and the inverted file's queries are include/ydorb/keyFrameDatabase.hpp.
 #ifndef YDORB_ADAPTER_VOCABULARY_HPP
 #define YDORB_ADAPTER_VOCABULARY_HPP
 

@@ -86,6 +86,16 @@ SYMBOLS = {
     "ydorb_sim3_release": (C.c_int, [_I]),
     "ydorb_pnp_ransac": (C.c_int, [_VP, _I, _I, _I]),
     "ydorb_pnp_release": (C.c_int, [_I]),
+    "ydorb_kfdb_create": (C.c_int, [_I, _I, _I, C.c_int64, C.POINTER(_VP)]),
+    "ydorb_kfdb_destroy": (None, [_VP]),
+    "ydorb_kfdb_add": (C.c_int, [_VP, _VP, _VP, _VP, _I, _VP]),
+    "ydorb_kfdb_erase": (C.c_int, [_VP, _VP, _I]),
+    "ydorb_kfdb_clear": (C.c_int, [_VP]),
+    "ydorb_kfdb_size": (C.c_int, [_VP, C.POINTER(_I), C.POINTER(_I)]),
+    "ydorb_kfdb_set_covisibility": (C.c_int, [_VP, _VP, _VP, _I]),
+    "ydorb_kfdb_score": (C.c_int, [_VP, _VP, _VP, _I, _VP, _I, _VP]),
+    "ydorb_kfdb_detect_reloc": (C.c_int, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_kfdb_detect_loop": (C.c_int, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
