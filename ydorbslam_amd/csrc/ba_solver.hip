@@ -21,6 +21,7 @@
 
 #include "../../include/ydorb/c_api.h"
 #include "ba_kernels.hip.h"
+#include "host_buffers.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
@@ -28,32 +29,13 @@ using namespace ydorb::ba;
 
 namespace {
 
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      ydorb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return YDORB_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
-
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool view = false;   // a slice of another DBuf (Ctx::upArena): not owned
-  void setView(void* ptr, size_t bytes) { if (!view && p) (void)hipFree(p); p = ptr; cap = bytes; view = true; }
-  int ensure(size_t bytes) {
-    if (bytes <= cap && !view) return YDORB_OK;
-    if (p && !view) (void)hipFree(p);
-    view = false;
-    p = nullptr; cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    if (hipMalloc(&p, want) != hipSuccess) { set_error("hipMalloc(%zu) failed", want); return YDORB_ERR_HIP; }
-    cap = want;
-    return YDORB_OK;
-  }
-  template <class T> T* as() { return reinterpret_cast<T*>(p); }
-  void release() { if (p && !view) (void)hipFree(p); p = nullptr; cap = 0; view = false; }
+struct DBuf : Mem {   // BA's buffers: 256-byte floor, and a buffer may instead be a slice of another one
+  bool view = false;   // a slice of another DBuf (Ctx::upArena): not owned, so let go of and never freed
+  DBuf() { floor = 256; }
+  void setView(void* ptr, size_t bytes) { release(); p = ptr; cap = bytes; view = true; }
+  void release() { if (view) { p = nullptr; view = false; } Mem::release(); }
+  int alloc(size_t bytes) { release(); return Mem::alloc(bytes); }
+  int ensure(size_t bytes) { return view ? alloc(want(bytes)) : Mem::ensure(bytes); }   // a slice is never grown in place
 };
 
 enum { PH_ERR = 0, PH_BUILD, PH_SCHUR, PH_SOLVE, PH_UPDATE, PH_COUNT };
@@ -69,16 +51,10 @@ struct Ctx {  // per-device scratch, reused across calls (localBundleAdjust runs
   hipEvent_t ev[2 * PH_COUNT + 2]{};
   bool evInit = false;
   double* hPin = nullptr;   // pinned read-back area: scal[8] + status[2] (one stream sync per LM trial)
-  uint8_t* hStage = nullptr;   // pinned staging of the ordered edge arrays on their way up and of the results on their way down: an
-  size_t hStageCap = 0;        // asynchronous copy out of / into pageable memory runs at ~8 GB/s and makes the host wait for the stream
-  int stage(size_t bytes) {
-    if (bytes <= hStageCap) return YDORB_OK;
-    if (hStage) { (void)hipHostFree(hStage); hStage = nullptr; hStageCap = 0; }
-    const size_t cap = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(&hStage, cap) != hipSuccess) { hStage = nullptr; ydorb::set_error("hipHostMalloc(%zu) failed", cap); return YDORB_ERR_HIP; }
-    hStageCap = cap;
-    return YDORB_OK;
-  }
+  Mem hStage;   // pinned staging of the ordered edge arrays on their way up and of the results on their way down: an asynchronous
+                // copy out of / into pageable memory runs at ~8 GB/s and makes the host wait for the stream
+  Ctx() { hStage.host = true; }
+  int stage(size_t bytes) { return bytes <= hStage.cap ? YDORB_OK : hStage.alloc(bytes + bytes / 4 + 4096); }
   DBuf pStart, pPoses, pX, pMeas, pInfo, pErr, pFlags, pOutlier, pInl, pChi, pTrials;   // pose-only batches
   void releaseBuffers() {   // ydorb_ba_release: device scratch and pinned staging back to the system (stream and events stay)
     for (DBuf* b : {&poses[0], &poses[1], &pts[0], &pts[1], &upArena, &ePose, &ePidx, &ePt, &eMeas, &eInfo, &eInfo0, &eRobust, &eOutlier, &eLm, &ptStart,
@@ -86,7 +62,7 @@ struct Ctx {  // per-device scratch, reused across calls (localBundleAdjust runs
                     &xp, &xl, &yv, &scal, &status, &pairCnt, &pairStart, &pairCursor, &pairA, &pairB, &pStart, &pPoses, &pX, &pMeas, &pInfo, &pErr,
                     &pFlags, &pOutlier, &pInl, &pChi, &pTrials})
       b->release();
-    if (hStage) { (void)hipHostFree(hStage); hStage = nullptr; hStageCap = 0; }
+    hStage.release();
   }
 };
 // A small pool of contexts per device: one localBundleAdjust at a time is the reference's use (LocalMapping thread), but the solve
@@ -238,7 +214,7 @@ int prepareStage(Run& R_, bool reuse) {
       // every array is copied into the staging area and its device buffer becomes the slice of the arena at the same offset; ONE
       // hipMemcpyAsync then moves the stage's inputs (twelve calls before: with 16 set-up threads of a batch the runtime's lock was the cost)
       auto up = [&](DBuf& dst, const void* src, size_t bytes) {
-        if (bytes) memcpy(c.hStage + off, src, bytes);
+        if (bytes) memcpy(c.hStage.as<uint8_t>() + off, src, bytes);
         dst.setView(reinterpret_cast<uint8_t*>(c.upArena.p) + off, bytes);
         off += al(bytes);
       };
@@ -247,7 +223,7 @@ int prepareStage(Run& R_, bool reuse) {
       UP(eRobust, hRobust, uint8_t); UP(ptStart, hPtStart, int); UP(poseStart, hPoseStart, int); UP(ptOf, ptOf, int);
       UP(poseEdges, hPoseEdges, int); UP(poseOf, poseOf, int);
   #undef UP
-      if (off) HIPCHK(hipMemcpyAsync(c.upArena.p, c.hStage, off, hipMemcpyHostToDevice, s));
+      if (off) HIPCHK(hipMemcpyAsync(c.upArena.p, c.hStage.as<uint8_t>(), off, hipMemcpyHostToDevice, s));
       // the original information: the chi2 tests between and after the stages use it (k_cull)
       HIPCHK(hipMemcpyAsync(c.eInfo0.p, c.eInfo.p, sizeof(double) * Ea, hipMemcpyDeviceToDevice, s));
       HIPCHK(hipMemsetAsync(c.err.p, 0, sizeof(double) * 3 * Ea, s));   // an edge that is never evaluated (stop flag) has error 0
@@ -524,13 +500,13 @@ int endSolve(Run& R_) {
   const size_t bPoses = sizeof(double) * 7 * P->n_poses, bPts = sizeof(double) * 3 * P->n_points, oPts = (bPoses + 255) & ~(size_t)255,
                oOut = oPts + ((bPts + 255) & ~(size_t)255);
   if ((rc = c.stage(oOut + Y.Ea))) return rc;
-  if (outlier && Y.Ea) HIPCHK(hipMemcpyAsync(c.hStage + oOut, c.eOutlier.p, Y.Ea, hipMemcpyDeviceToHost, c.stream));
-  HIPCHK(hipMemcpyAsync(c.hStage, c.poses[R_.cur].p, bPoses, hipMemcpyDeviceToHost, c.stream));
-  HIPCHK(hipMemcpyAsync(c.hStage + oPts, c.pts[R_.cur].p, bPts, hipMemcpyDeviceToHost, c.stream));
+  if (outlier && Y.Ea) HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>() + oOut, c.eOutlier.p, Y.Ea, hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>(), c.poses[R_.cur].p, bPoses, hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>() + oPts, c.pts[R_.cur].p, bPts, hipMemcpyDeviceToHost, c.stream));
   HIPCHK(hipStreamSynchronize(c.stream));
-  memcpy(P->poses, c.hStage, bPoses);
-  memcpy(P->points, c.hStage + oPts, bPts);
-  if (outlier) for (int i = 0; i < Y.Ea; i++) outlier[Y.act[i]] = c.hStage[oOut + i];   // device edges are in (landmark, pose) order
+  memcpy(P->poses, c.hStage.as<uint8_t>(), bPoses);
+  memcpy(P->points, c.hStage.as<uint8_t>() + oPts, bPts);
+  if (outlier) for (int i = 0; i < Y.Ea; i++) outlier[Y.act[i]] = c.hStage.as<uint8_t>()[oOut + i];   // device edges are in (landmark, pose) order
   if (R_.stopped()) R_.res->stopped = 1;
   return YDORB_OK;
 }
@@ -1035,21 +1011,17 @@ int ydorb_ba_dense_solve(int32_t device, const double* A, int32_t n0, const doub
     for (int j = 0; j < n; j++) hA[(size_t)i * n + j] = (i < n0 && j < n0) ? A[(size_t)i * n0 + j] : (i == j ? 1.0 : 0.0);
     if (i < n0) hb[i] = b[i];
   }
-  double *dA = nullptr, *dD = nullptr, *dI = nullptr, *db = nullptr, *dx = nullptr, *dy = nullptr;
-  int* dst = nullptr;
-  HIPCHK(hipMalloc(&dA, sizeof(double) * n * n));
-  HIPCHK(hipMalloc(&dD, sizeof(double) * nb * NB * NB));
-  HIPCHK(hipMalloc(&dI, sizeof(double) * nb * NB * NB));
-  HIPCHK(hipMalloc(&db, sizeof(double) * n));
-  HIPCHK(hipMalloc(&dx, sizeof(double) * n));
-  HIPCHK(hipMalloc(&dy, sizeof(double) * n));
-  HIPCHK(hipMalloc(&dst, sizeof(int) * 2));
+  ScopedMem mA, mD, mI, mb, mx, my, mst;   // exact sizes; freed on every return
+  if ((rc = mA.alloc(sizeof(double) * n * n)) || (rc = mD.alloc(sizeof(double) * nb * NB * NB)) || (rc = mI.alloc(sizeof(double) * nb * NB * NB)) ||
+      (rc = mb.alloc(sizeof(double) * n)) || (rc = mx.alloc(sizeof(double) * n)) || (rc = my.alloc(sizeof(double) * n)) || (rc = mst.alloc(sizeof(int) * 2)))
+    return rc;
+  double *dA = mA.as<double>(), *dD = mD.as<double>(), *dI = mI.as<double>(), *db = mb.as<double>(), *dx = mx.as<double>(), *dy = my.as<double>();
+  int* dst = mst.as<int>();
   HIPCHK(hipMemcpy(dA, hA.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(db, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(dst, 0, sizeof(int) * 2));
   for (int kb = 0; kb < nb; kb++) hipLaunchKernelGGL(k_chol_step, dim3((nb - kb) * (nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, 0, dA, dD, dI, n, kb, dst, db, dy);
   if (!launch_chol_solve(0, dA, dI, n, dy, db, dx)) {
-    (void)hipFree(dA); (void)hipFree(dD); (void)hipFree(dI); (void)hipFree(db); (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dst);
     set_error("system of %d rows is wider than the solve kernel's LDS (max %d)", n, kCholSolveMaxN);
     return YDORB_ERR_UNSUPPORTED;
   }
@@ -1074,7 +1046,6 @@ int ydorb_ba_dense_solve(int32_t device, const double* A, int32_t n0, const doub
     fprintf(stderr, "us between step starts\n");
   }
 #endif
-  (void)hipFree(dA); (void)hipFree(dD); (void)hipFree(dI); (void)hipFree(db); (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dst);
   return YDORB_OK;
 }
 

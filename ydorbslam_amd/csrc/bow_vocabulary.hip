@@ -20,20 +20,12 @@
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
+#include "host_buffers.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
 
 namespace {
-
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      ydorb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return YDORB_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
 
 constexpr int kBowMaxFeatures = 8192;   // per frame: 64-bit sort keys of one frame stay in LDS (64 KB)
 constexpr int kFeatBits = 13;
@@ -181,29 +173,13 @@ __global__ __launch_bounds__(256) void k_bow_assemble(const int* __restrict__ wo
   if (tid == 0) O.nFvNodes[frame] = nNodes;
 }
 
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return YDORB_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-    if (hipMalloc(&p, want) != hipSuccess) { set_error("hipMalloc(%zu) failed", want); return YDORB_ERR_HIP; }
-    cap = want;
-    return YDORB_OK;
-  }
-  template <class T> T* as() { return reinterpret_cast<T*>(p); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 }  // namespace
 
 struct ydorb_vocabulary {
   int device = 0, nNodes = 0, L = 0, weighting = 0, norm = 1;
   hipStream_t stream = nullptr;
-  DBuf childBegin, childIds, nodeDesc, nodeWeight, nodeWord;   // the tree
-  DBuf desc, nFeat, word, node, weight, status, out;           // per-call scratch
+  Mem childBegin, childIds, nodeDesc, nodeWeight, nodeWord;   // the tree
+  Mem desc, nFeat, word, node, weight, status, out;           // per-call scratch
   std::mutex mu;   // Frame::computeBoW and KeyFrame::computeBoW reach one vocabulary from the tracking, mapping and loop-closing threads
 };
 
@@ -263,7 +239,7 @@ void ydorb_vocabulary_destroy(ydorb_vocabulary_t* v) {
   if (!v) return;
   (void)hipSetDevice(v->device);
   if (v->stream) { (void)hipStreamSynchronize(v->stream); (void)hipStreamDestroy(v->stream); }
-  for (DBuf* b : {&v->childBegin, &v->childIds, &v->nodeDesc, &v->nodeWeight, &v->nodeWord, &v->desc, &v->nFeat, &v->word, &v->node, &v->weight,
+  for (Mem* b : {&v->childBegin, &v->childIds, &v->nodeDesc, &v->nodeWeight, &v->nodeWord, &v->desc, &v->nFeat, &v->word, &v->node, &v->weight,
                   &v->status, &v->out})
     b->release();
   delete v;

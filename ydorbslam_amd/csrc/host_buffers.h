@@ -1,0 +1,95 @@
+// Host-side scaffolding the HIP drivers share: the error-check macro, grow-only device / pinned buffers, the aligned layout of a
+// staging area and the per-device context of the staged solvers.  Included by .hip files only (ydorb_host.h stays free of HIP types).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <mutex>
+
+#include "../../include/ydorb/c_api.h"
+#include "ydorb_host.h"
+
+// A macro, so that __FILE__ / __LINE__ name the call site.
+#define HIPCHK(expr)                                                                          \
+  do {                                                                                        \
+    hipError_t _e = (expr);                                                                   \
+    if (_e != hipSuccess) {                                                                   \
+      ydorb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+      return YDORB_ERR_HIP;                                                                   \
+    }                                                                                         \
+  } while (0)
+
+namespace ydorb {
+
+// Grow-only device buffer, or pinned host buffer when `host` is set; growing does not keep the contents.
+// No destructor, on purpose: the solvers keep their contexts in static arrays, and freeing during static destruction would call
+// into a HIP runtime that may already be gone.  Owners release() explicitly in their destroy / release entry points; a buffer
+// that lives in one function is a ScopedMem.
+struct Mem {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool host = false;
+  size_t slackDiv = 4, floor = 4096;   // growth policy, set once by the owner: request bytes + bytes / slackDiv, at least floor
+  size_t want(size_t bytes) const { return std::max(bytes + bytes / slackDiv, floor); }
+  int ensure(size_t bytes) { return bytes <= cap ? YDORB_OK : alloc(want(bytes)); }
+  int alloc(size_t bytes) {   // drops what it holds and requests exactly `bytes`
+    release();
+    if ((host ? hipHostMalloc(&p, bytes) : hipMalloc(&p, bytes)) != hipSuccess) {
+      p = nullptr;
+      set_error("%s(%zu) failed", host ? "hipHostMalloc" : "hipMalloc", bytes);
+      return YDORB_ERR_HIP;
+    }
+    cap = bytes;
+    return YDORB_OK;
+  }
+  void release() {
+    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
+    p = nullptr; cap = 0;
+  }
+  void take(Mem& o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }   // o's allocation becomes this buffer's
+  template <class T> T* as() { return reinterpret_cast<T*>(p); }
+  template <class T> T* at(size_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(p) + off); }
+};
+
+struct ScopedMem : Mem {   // for function-local buffers only (see Mem)
+  ScopedMem() = default;
+  ScopedMem(const ScopedMem&) = delete;
+  ScopedMem& operator=(const ScopedMem&) = delete;
+  ~ScopedMem() { release(); }
+};
+
+template <class T> T* at(Mem& m, size_t off) { return m.at<T>(off); }
+
+// Lays arrays out at 16-byte aligned offsets of one area: the same offsets address the pinned staging and the device copy.
+struct Layout {
+  size_t bytes = 0;
+  size_t add(size_t n) { const size_t at = bytes; bytes += (n + 15) & ~size_t(15); return at; }
+};
+
+// Per-device scratch of a solver that stages a batch up and its results down, reused between calls.  Every solver keeps its own
+// array of these: solvers run concurrently from different host threads and share neither stream, mutex nor buffers.
+struct StagedCtx {
+  std::mutex mu;
+  hipStream_t stream = nullptr;
+  Mem up, down, scratch, hUp, hDown;
+  StagedCtx() { hUp.host = true; hDown.host = true; }
+  int init(int device) {
+    HIPCHK(hipSetDevice(device));
+    if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    return YDORB_OK;
+  }
+  void releaseBuffers() { up.release(); down.release(); scratch.release(); hUp.release(); hDown.release(); }
+};
+
+// Body of a solver's ydorb_*_release(device): waits for the context's stream and gives its buffers back (the stream stays).
+inline int release_staged(StagedCtx& c, int device) {
+  std::lock_guard<std::mutex> lock(c.mu);
+  HIPCHK(hipSetDevice(device));
+  if (c.stream) (void)hipStreamSynchronize(c.stream);
+  c.releaseBuffers();
+  return YDORB_OK;
+}
+
+}  // namespace ydorb

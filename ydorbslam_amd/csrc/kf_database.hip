@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
+#include "host_buffers.h"
 #include "kfdb_kernels.hip.h"
 #include "ydorb_host.h"
 
@@ -20,51 +21,20 @@ using namespace ydorb::kfdb;
 
 namespace {
 
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      ydorb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return YDORB_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
-
-struct Mem {   // device buffer; grow() keeps the contents, ensure() does not
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return YDORB_OK;
-    release();
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-    if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; set_error("hipMalloc(%zu) failed", want); return YDORB_ERR_HIP; }
-    cap = want;
-    return YDORB_OK;
+// Grows a device buffer to twice `bytes`, zero-filled, keeping its first `keep` bytes; done when it returns.
+int grow(Mem& m, size_t bytes, size_t keep, hipStream_t s) {
+  if (bytes <= m.cap) return YDORB_OK;
+  ScopedMem n;
+  int rc = n.alloc(std::max<size_t>(bytes * 2, 4096));
+  if (rc) return rc;
+  if (hipMemsetAsync(n.p, 0, n.cap, s) != hipSuccess || (m.p && keep && hipMemcpyAsync(n.p, m.p, keep, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    set_error("growing a device buffer failed");
+    return YDORB_ERR_HIP;
   }
-  int grow(size_t bytes, size_t keep, hipStream_t s) {
-    if (bytes <= cap) return YDORB_OK;
-    const size_t want = std::max<size_t>(bytes * 2, 4096);
-    void* n = nullptr;
-    if (hipMalloc(&n, want) != hipSuccess) { set_error("hipMalloc(%zu) failed", want); return YDORB_ERR_HIP; }
-    if (hipMemsetAsync(n, 0, want, s) != hipSuccess || (p && keep && hipMemcpyAsync(n, p, keep, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipFree(n);
-      set_error("growing a device buffer failed");
-      return YDORB_ERR_HIP;
-    }
-    if (p) (void)hipFree(p);
-    p = n; cap = want;
-    return YDORB_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
-struct Layout {
-  size_t bytes = 0;
-  size_t add(size_t n) { const size_t at = bytes; bytes += (n + 15) & ~size_t(15); return at; }
-};
-
-template <class T> T* at(Mem& m, size_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(m.p) + off); }
+  m.take(n);
+  return YDORB_OK;
+}
 
 constexpr int kQueryChunk = 64;   // queries per kernel sequence: bounds the scratch (about 60 bytes per query and slot)
 
@@ -110,11 +80,11 @@ int growSlots(ydorb_kfdb* h, int want) {
   const int cap = std::max(want * 2, 64), keep = h->slotCap;
   hipStream_t s = h->stream;
   int rc;
-  if ((rc = h->dOff.grow(sizeof(long long) * cap, sizeof(long long) * keep, s)) || (rc = h->dLen.grow(sizeof(int) * cap, sizeof(int) * keep, s)) ||
-      (rc = h->dLive.grow(sizeof(int) * cap, sizeof(int) * keep, s)) || (rc = h->dSeq.grow(sizeof(unsigned) * cap, sizeof(unsigned) * keep, s)) ||
-      (rc = h->dNeigh.grow(sizeof(int) * kNeigh * cap, sizeof(int) * kNeigh * keep, s)) ||
-      (rc = h->dNeighSeq.grow(sizeof(unsigned) * kNeigh * cap, sizeof(unsigned) * kNeigh * keep, s)) ||
-      (rc = h->dRelocScore.grow(sizeof(float) * cap, sizeof(float) * keep, s)) || (rc = h->dRelocSeq.grow(sizeof(unsigned) * cap, sizeof(unsigned) * keep, s)))
+  if ((rc = grow(h->dOff, sizeof(long long) * cap, sizeof(long long) * keep, s)) || (rc = grow(h->dLen, sizeof(int) * cap, sizeof(int) * keep, s)) ||
+      (rc = grow(h->dLive, sizeof(int) * cap, sizeof(int) * keep, s)) || (rc = grow(h->dSeq, sizeof(unsigned) * cap, sizeof(unsigned) * keep, s)) ||
+      (rc = grow(h->dNeigh, sizeof(int) * kNeigh * cap, sizeof(int) * kNeigh * keep, s)) ||
+      (rc = grow(h->dNeighSeq, sizeof(unsigned) * kNeigh * cap, sizeof(unsigned) * kNeigh * keep, s)) ||
+      (rc = grow(h->dRelocScore, sizeof(float) * cap, sizeof(float) * keep, s)) || (rc = grow(h->dRelocSeq, sizeof(unsigned) * cap, sizeof(unsigned) * keep, s)))
     return rc;
   h->slotCap = cap;
   return YDORB_OK;
@@ -126,9 +96,8 @@ int growPool(ydorb_kfdb* h, long long extra) {
   const long long cap = std::max<long long>(2 * (h->poolLiveWords + extra), 1024);
   hipStream_t s = h->stream;
   const int H = h->nSlots();
-  void *nw = nullptr, *nv = nullptr;
-  if (hipMalloc(&nw, sizeof(int) * cap) != hipSuccess || hipMalloc(&nv, sizeof(double) * cap) != hipSuccess) {
-    if (nw) (void)hipFree(nw);
+  ScopedMem nw, nv;   // freed on every early return; handed over to dWord / dVal at the end
+  if (nw.alloc(sizeof(int) * cap) != YDORB_OK || nv.alloc(sizeof(double) * cap) != YDORB_OK) {
     set_error("hipMalloc of a pool of %lld words failed", cap);
     return YDORB_ERR_HIP;
   }
@@ -138,26 +107,22 @@ int growPool(ydorb_kfdb* h, long long extra) {
   int rc = YDORB_OK;
   if (H > 0 && used > 0) {
     // the device's table may lag behind the host's: bring it up to date first (old offsets), then move
-    if ((rc = h->dTmp.ensure(sizeof(long long) * H))) { (void)hipFree(nw); (void)hipFree(nv); return rc; }
+    if ((rc = h->dTmp.ensure(sizeof(long long) * H))) return rc;
     if (hipMemcpyAsync(h->dOff.p, h->off.data(), sizeof(long long) * H, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(h->dLen.p, h->len.data(), sizeof(int) * H, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(h->dLive.p, h->live.data(), sizeof(int) * H, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(h->dTmp.p, newOff.data(), sizeof(long long) * H, hipMemcpyHostToDevice, s) != hipSuccess) {
-      (void)hipFree(nw); (void)hipFree(nv);
       set_error("uploading the slot table failed");
       return YDORB_ERR_HIP;
     }
     hipLaunchKernelGGL(k_kfdb_compact, dim3(H), dim3(256), 0, s, h->dWord.as<int>(), h->dVal.as<double>(), h->dOff.as<long long>(),
-                       h->dTmp.as<long long>(), h->dLen.as<int>(), h->dLive.as<int>(), static_cast<int*>(nw), static_cast<double*>(nv));
+                       h->dTmp.as<long long>(), h->dLen.as<int>(), h->dLive.as<int>(), nw.as<int>(), nv.as<double>());
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipFree(nw); (void)hipFree(nv);
       set_error("moving the rows to a larger pool failed");
       return YDORB_ERR_HIP;
     }
   }
-  h->dWord.release(); h->dVal.release();
-  h->dWord.p = nw; h->dWord.cap = sizeof(int) * cap;
-  h->dVal.p = nv; h->dVal.cap = sizeof(double) * cap;
+  h->dWord.take(nw); h->dVal.take(nv);
   for (int i = 0; i < H; i++) if (h->live[i]) h->off[i] = newOff[i];
   h->poolUsed = used; h->poolCap = cap;
   if (H > 0) { h->dirtyLo = 0; h->dirtyHi = H; }

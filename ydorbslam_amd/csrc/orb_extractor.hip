@@ -15,6 +15,7 @@
 
 #include "../../include/ydorb/c_api.h"
 #include "extract_kernels.hip.h"
+#include "host_buffers.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
@@ -109,15 +110,6 @@ struct ydorb_extractor {
 };
 
 namespace {
-
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      ydorb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return YDORB_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
 
 void freeBuffers(ydorb_extractor* e) {
   auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };

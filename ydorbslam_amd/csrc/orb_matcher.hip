@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
+#include "host_buffers.h"
 #include "match_kernels.hip.h"
 #include "stereo_kernels.hip.h"
 #include "ydorb_host.h"
@@ -20,15 +21,6 @@
 using namespace ydorb;
 
 namespace {
-
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      ydorb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return YDORB_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
 
 // k_grid_build keeps one 16-bit cell id per keypoint in dynamic LDS beside ~12 KiB of static tables: frames with more than
 // ~26 k keypoints need the kernel's dynamic-LDS limit raised (the 16-bit index format allows up to 65 535).
@@ -40,23 +32,6 @@ int launchGridBuild(int nFrames, int cap, hipStream_t s, const FrameDev* frames)
   HIPCHK(hipGetLastError());
   return YDORB_OK;
 }
-
-struct Buf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return YDORB_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-    if (hipMalloc(&p, want) != hipSuccess) { set_error("hipMalloc(%zu) failed", want); return YDORB_ERR_HIP; }
-    cap = want;
-    return YDORB_OK;
-  }
-  template <class T> T* as() { return reinterpret_cast<T*>(p); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 __global__ void k_hamming_rows(const uint8_t* a, const uint8_t* b, int n, int* out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -71,7 +46,7 @@ const char* kMatchStageNames[MS_COUNT] = {"grid_build", "gather_distances", "res
 struct ydorb_matcher {
   int device = 0;
   hipStream_t stream = nullptr;
-  Buf kps, desc, rightX, queries, qdesc, taken, assigned, matchQ, qInfo, qPre, cellStart, cellIdx, pool, frames, calls, misc, kps2,
+  Mem kps, desc, rightX, queries, qdesc, taken, assigned, matchQ, qInfo, qPre, cellStart, cellIdx, pool, frames, calls, misc, kps2,
       desc2, feat, valid, qFeat, qRange, qAngle, sf, heads, sortedKp, sortedDesc, kps1, good1, good2, stereoPar, stereoCnt, stereoOut;
   size_t poolRecords = 1u << 20;
   // cached descriptors of the last batched launch (re-uploaded only when they change)
@@ -86,6 +61,11 @@ struct ydorb_matcher {
   double stageMs[MS_COUNT]{};
   int stageCalls = 0;
   bool evPending = false;
+  std::vector<Mem*> buffers() {
+    return {&kps, &desc, &rightX, &queries, &qdesc, &taken, &assigned, &matchQ, &qInfo, &qPre, &cellStart, &cellIdx, &pool, &frames, &calls, &misc, &kps2,
+            &desc2, &feat, &valid, &qFeat, &qRange, &qAngle, &sf, &heads, &sortedKp, &sortedDesc, &kps1, &good1, &good2, &stereoPar, &stereoCnt, &stereoOut};
+  }
+  ydorb_matcher() { for (Mem* b : buffers()) b->slackDiv = 2; }   // 50 % slack instead of the default 25 %
 };
 
 namespace {
@@ -171,11 +151,7 @@ void ydorb_matcher_destroy(ydorb_matcher_t* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   (void)hipStreamSynchronize(m->stream);
-  for (Buf* b : {&m->kps, &m->desc, &m->rightX, &m->queries, &m->qdesc, &m->taken, &m->assigned, &m->matchQ, &m->qInfo, &m->qPre, &m->cellStart,
-                 &m->cellIdx, &m->pool, &m->frames, &m->calls, &m->misc, &m->kps2, &m->desc2, &m->feat, &m->valid, &m->qFeat, &m->qRange,
-                 &m->qAngle, &m->sf, &m->heads, &m->sortedKp, &m->sortedDesc, &m->kps1, &m->good1, &m->good2, &m->stereoPar, &m->stereoCnt,
-                 &m->stereoOut})
-    b->release();
+  for (Mem* b : m->buffers()) b->release();
   for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(m->stream);
   delete m;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
+#include "host_buffers.h"
 #include "pnp_kernels.hip.h"
 #include "ydorb_host.h"
 
@@ -17,57 +18,7 @@ using namespace ydorb::pnp;
 
 namespace {
 
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      ydorb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return YDORB_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
-
-struct Mem {   // grow-only device or pinned host buffer
-  void* p = nullptr;
-  size_t cap = 0;
-  bool host = false;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return YDORB_OK;
-    release();
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-    if ((host ? hipHostMalloc(&p, want) : hipMalloc(&p, want)) != hipSuccess) {
-      p = nullptr;
-      set_error("%s(%zu) failed", host ? "hipHostMalloc" : "hipMalloc", want);
-      return YDORB_ERR_HIP;
-    }
-    cap = want;
-    return YDORB_OK;
-  }
-  void release() {
-    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
-    p = nullptr; cap = 0;
-  }
-};
-
-struct Layout {   // 16-byte aligned offsets of one area: the same offsets address the pinned staging and the device copy
-  size_t bytes = 0;
-  size_t add(size_t n) { const size_t at = bytes; bytes += (n + 15) & ~size_t(15); return at; }
-};
-
-struct Ctx {   // per-device scratch, reused between calls
-  std::mutex mu;
-  hipStream_t stream = nullptr;
-  Mem up, down, scratch, hUp, hDown;
-  Ctx() { hUp.host = true; hDown.host = true; }
-  int init(int device) {
-    HIPCHK(hipSetDevice(device));
-    if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    return YDORB_OK;
-  }
-  void releaseBuffers() { up.release(); down.release(); scratch.release(); hUp.release(); hDown.release(); }
-};
-Ctx g_ctx[16];
-
-template <class T> T* at(Mem& m, size_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(m.p) + off); }
+StagedCtx g_ctx[16];   // this solver's own: nothing is shared with the other staged solvers
 
 }  // namespace
 
@@ -86,7 +37,7 @@ extern "C" int ydorb_pnp_ransac(YdPnpProblem* probs, int32_t n, int32_t chunk, i
   int rc = require_device(device);
   if (rc) return rc;
   if (n == 0) return YDORB_OK;
-  Ctx& c = g_ctx[device];
+  StagedCtx& c = g_ctx[device];
   std::lock_guard<std::mutex> lock(c.mu);
   if ((rc = c.init(device))) return rc;
   // H: hypotheses the iterate(chunk) sequence runs without a return.  With ||, the first call runs until mnIterations >= maxIts and
@@ -183,10 +134,5 @@ extern "C" int ydorb_pnp_release(int32_t device) {
   if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
   int rc = require_device(device);
   if (rc) return rc;
-  Ctx& c = g_ctx[device];
-  std::lock_guard<std::mutex> lock(c.mu);
-  HIPCHK(hipSetDevice(device));
-  if (c.stream) (void)hipStreamSynchronize(c.stream);
-  c.releaseBuffers();
-  return YDORB_OK;
+  return release_staged(g_ctx[device], device);
 }
