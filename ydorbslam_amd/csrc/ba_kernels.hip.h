@@ -19,68 +19,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "g2o_math.hip.h"
 
 #pragma clang fp contract(off)
 
 namespace ydorb {
 namespace ba {
 
-typedef double R;
-struct V3 { R x, y, z; };
-struct Q4 { R x, y, z, w; };
-
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 scale(V3 a, R s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {  // Eigen quaternion * vector
-  V3 qv{q.x, q.y, q.z};
-  V3 uv = cross(qv, v);
-  uv = add(uv, uv);
-  return add(add(v, scale(uv, q.w)), cross(qv, uv));
-}
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
-          a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-__device__ __forceinline__ void qToR(Q4 q, R m[3][3]) {
-  const R tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-  const R twx = tx * q.w, twy = ty * q.w, twz = tz * q.w, txx = tx * q.x, txy = ty * q.x, txz = tz * q.x, tyy = ty * q.y,
-          tyz = tz * q.y, tzz = tz * q.z;
-  m[0][0] = 1 - (tyy + tzz); m[0][1] = txy - twz; m[0][2] = txz + twy;
-  m[1][0] = txy + twz; m[1][1] = 1 - (txx + tzz); m[1][2] = tyz - twx;
-  m[2][0] = txz - twy; m[2][1] = tyz + twx; m[2][2] = 1 - (txx + tyy);
-}
-__device__ __forceinline__ Q4 rToQ(const R a[3][3]) {  // Eigen Quaternion(Matrix3)
-  Q4 q;
-  R t = a[0][0] + a[1][1] + a[2][2];
-  if (t > 0) {
-    t = sqrt(t + 1.0);
-    q.w = 0.5 * t;
-    t = 0.5 / t;
-    q.x = (a[2][1] - a[1][2]) * t;
-    q.y = (a[0][2] - a[2][0]) * t;
-    q.z = (a[1][0] - a[0][1]) * t;
-  } else {
-    int i = 0;
-    if (a[1][1] > a[0][0]) i = 1;
-    if (a[2][2] > a[i][i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = sqrt(a[i][i] - a[j][j] - a[k][k] + 1.0);
-    R c[3];
-    c[i] = 0.5 * t;
-    t = 0.5 / t;
-    q.w = (a[k][j] - a[j][k]) * t;
-    c[j] = (a[j][i] + a[i][j]) * t;
-    c[k] = (a[k][i] + a[i][k]) * t;
-    q.x = c[0]; q.y = c[1]; q.z = c[2];
-  }
-  return q;
-}
-__device__ __forceinline__ void qnormalize(Q4& q) {  // se3quat.h:280-285
-  if (q.w < 0) { q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w; }
-  const R n = sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-  q.x /= n; q.y /= n; q.z /= n; q.w /= n;
-}
+using g2o::R; using g2o::V3; using g2o::Q4;
+using g2o::add; using g2o::cross; using g2o::scale; using g2o::qrot; using g2o::qmul; using g2o::qToR; using g2o::rToQ; using g2o::qnormalize;
+using g2o::huber; using g2o::block_sums; using g2o::block_sum1; using g2o::dense_solve; using g2o::lambda_init; using g2o::lm_judge;
 
 struct Cam { R fx, fy, cx, cy, bf; };
 
@@ -152,11 +100,6 @@ __device__ __forceinline__ void jacobians(V3 t, Q4 q, V3 X, bool stereo, const C
 #pragma unroll
     for (int j = 0; j < 6; j++) B[2][j] = 0;
   }
-}
-__device__ __forceinline__ void huber(R e, R delta, R* rho0, R* rho1) {  // robust_kernel_impl.cpp:65-78
-  const R dsqr = delta * delta;
-  if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
-  else { const R s = sqrt(e); *rho0 = 2 * s * delta - dsqr; *rho1 = delta / s; }
 }
 
 __device__ __forceinline__ R block_sum(R v, R* lds) {  // deterministic workgroup sum (blockDim.x multiple of 64, <= 1024)
@@ -1133,69 +1076,21 @@ __global__ __launch_bounds__(256) void k_cull(const int* __restrict__ ePose, con
 // ------------------------------------------------------------------------------------------------------------------------
 constexpr int kPoseThreads = 256;
 
-__device__ __forceinline__ void pose_block_sums(R (&v)[28], R (*part)[28], R (&out)[28]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 28; k++) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  __syncthreads();                       // the previous reduction's readers are done with `part`
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 28; k++) part[wv][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 28; k++) out[k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
-}
-__device__ __forceinline__ R pose_block_sum1(R v, R (*part)[28]) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][0] = v;
-  __syncthreads();
-  return ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
-}
-// LL^T of the 6x6 system + both substitutions (LinearSolverDense, linear_solver_dense.h:66-109); false when not positive definite
-__device__ __forceinline__ bool pose_solve6(const R (&Hs)[21], R lambda, const R (&b)[6], R (&x)[6]) {
-  R L[6][6];
-  int k = 0;
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-#pragma unroll
-    for (int c = r; c < 6; c++, k++) { L[c][r] = Hs[k] + (r == c ? lambda : 0.0); }   // lower triangle
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    R d = L[j][j];
-#pragma unroll
-    for (int q = 0; q < j; q++) d -= L[j][q] * L[j][q];
-    if (!(d > 0)) return false;
-    d = sqrt(d);
-    L[j][j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      R s2 = L[i][j];
-#pragma unroll
-      for (int q = 0; q < j; q++) s2 -= L[i][q] * L[j][q];
-      L[i][j] = s2 / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    R s2 = b[i];
-#pragma unroll
-    for (int q = 0; q < i; q++) s2 -= L[i][q] * x[q];
-    x[i] = s2 / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    R s2 = x[i];
-#pragma unroll
-    for (int q = i + 1; q < 6; q++) s2 -= L[q][i] * x[q];
-    x[i] = s2 / L[i][i];
-  }
-  return true;
+// computeError of edge e at (t, q), stored as g2o's _error in err[3e..] and returned in r.  Returns the edge's chi2, through Huber
+// unless its robust kernel is off (fl bit1), and the kernel's rho' in *rho1.
+__device__ __forceinline__ R pose_edge_chi(V3 t, Q4 q, int e, uint8_t fl, const R* __restrict__ Xw, const R* __restrict__ meas,
+                                           const R* __restrict__ info, const Cam& cam, R deltaMono, R deltaStereo, R* __restrict__ err,
+                                           R (&r)[3], R* rho1) {
+  const R* z = meas + 3 * e;
+  const bool st = z[2] >= 0;
+  R depth;
+  residual(t, q, V3{Xw[3 * e], Xw[3 * e + 1], Xw[3 * e + 2]}, z, st, cam, r, &depth);
+  err[3 * e] = r[0]; err[3 * e + 1] = r[1]; err[3 * e + 2] = r[2];
+  const R c2 = info[e] * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  R rho0 = c2;
+  *rho1 = 1;
+  if (!(fl & 2)) huber(c2, st ? deltaStereo : deltaMono, &rho0, rho1);
+  return rho0;
 }
 
 // state per edge in global scratch: err[3] (as last computed, stale for inactive edges like g2o's _error), flags (bit0 outlier/level,
@@ -1227,7 +1122,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(int nFrames, con
     t = t0; q = q0;                          // setEstimate(frame pose) at the top of every episode (:455)
     int nAct = 0;
     for (int i = tid; i < E; i += kPoseThreads) nAct += !(flags[e0 + i] & 1);
-    nAct = (int)pose_block_sum1((R)nAct, part);
+    nAct = (int)block_sum1((R)nAct, part);
     if (nAct > 0) {
       R lambda = 0, ni = 2, currentChi = 0;
       for (int it = 0; it < 10; it++) {
@@ -1239,16 +1134,11 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(int nFrames, con
           const int e = e0 + i;
           const uint8_t fl = flags[e];
           if (fl & 1) continue;
-          const R* z = meas + 3 * e;
-          const bool st = z[2] >= 0;
+          R r[3], rho1;
+          acc[27] += pose_edge_chi(t, q, e, fl, Xw, meas, info, cam, deltaMono, deltaStereo, err, r, &rho1);
+          const bool st = meas[3 * e + 2] >= 0;
           const V3 X{Xw[3 * e], Xw[3 * e + 1], Xw[3 * e + 2]};
-          R r[3], depth;
-          residual(t, q, X, z, st, cam, r, &depth);
-          err[3 * e] = r[0]; err[3 * e + 1] = r[1]; err[3 * e + 2] = r[2];
-          const R w = info[e], c2 = w * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-          R rho0 = c2, rho1 = 1;
-          if (!(fl & 2)) huber(c2, st ? deltaStereo : deltaMono, &rho0, &rho1);
-          acc[27] += rho0;
+          const R w = info[e];
           const V3 p = add(qrot(q, X), t);
           const R x = p.x, y = p.y, invz = 1.0 / p.z, invz2 = invz * invz;
           R J[3][6];
@@ -1274,56 +1164,33 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(int nFrames, con
           for (int rr = 0; rr < 6; rr++) acc[21 + rr] += J[0][rr] * omr[0] + J[1][rr] * omr[1] + J[2][rr] * omr[2];
         }
         R S[28];
-        pose_block_sums(acc, part, S);
+        block_sums(acc, part, S);
         R Hs[21], b[6];
 #pragma unroll
         for (int k = 0; k < 21; k++) Hs[k] = S[k];
 #pragma unroll
         for (int k = 0; k < 6; k++) b[k] = S[21 + k];
         currentChi = S[27];
-        if (it == 0) {                       // computeLambdaInit
-          R mx = 0;
-          int k = 0;
-#pragma unroll
-          for (int rr = 0; rr < 6; rr++) { mx = fmax(fabs(Hs[k]), mx); k += 6 - rr; }
-          lambda = 1e-5 * mx; ni = 2;
-        }
+        if (it == 0) { lambda = lambda_init<6>(Hs); ni = 2; }   // computeLambdaInit
         R rho = 0, x6[6] = {0, 0, 0, 0, 0, 0};
         int qmax = 0;
         do {
           const V3 tb = t; const Q4 qb = q;  // push()
-          const bool ok = pose_solve6(Hs, lambda, b, x6);
+          const bool ok = dense_solve<6>(Hs, lambda, b, x6);
           pose_oplus(t, q, x6);              // g2o applies _x even after a failed solve (it then holds the previous step)
           R chi = 0;
           for (int i = tid; i < E; i += kPoseThreads) {
             const int e = e0 + i;
             const uint8_t fl = flags[e];
             if (fl & 1) continue;
-            const R* z = meas + 3 * e;
-            const bool st = z[2] >= 0;
-            R r[3], depth;
-            residual(t, q, V3{Xw[3 * e], Xw[3 * e + 1], Xw[3 * e + 2]}, z, st, cam, r, &depth);
-            err[3 * e] = r[0]; err[3 * e + 1] = r[1]; err[3 * e + 2] = r[2];
-            const R c2 = info[e] * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-            R rho0 = c2, rho1;
-            if (!(fl & 2)) huber(c2, st ? deltaStereo : deltaMono, &rho0, &rho1);
-            chi += rho0;
+            R r[3], rho1;
+            chi += pose_edge_chi(t, q, e, fl, Xw, meas, info, cam, deltaMono, deltaStereo, err, r, &rho1);
           }
-          R tempChi = pose_block_sum1(chi, part);
-          if (!ok) tempChi = 1.7976931348623157e308;
-          rho = currentChi - tempChi;
-          R sc = 1e-3;
+          const R tempChi = block_sum1(chi, part);
+          R sc = 1e-3;                       // computeScale() + 1e-3
 #pragma unroll
           for (int j = 0; j < 6; j++) sc += x6[j] * (lambda * x6[j] + b[j]);
-          rho /= sc;
-          if (rho > 0 && isfinite(tempChi)) {
-            R alpha = 1. - pow((2 * rho - 1), 3.0);
-            alpha = fmin(alpha, 2. / 3.);
-            lambda *= fmax(1. / 3., alpha);
-            ni = 2;
-            currentChi = tempChi;
-          } else {
-            lambda *= ni; ni *= 2;
+          if (!lm_judge(lambda, ni, currentChi, rho, tempChi, sc, ok)) {
             t = tb; q = qb;                  // pop()
             if (!isfinite(lambda)) { qmax++; trials++; break; }
           }
@@ -1340,11 +1207,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(int nFrames, con
       uint8_t fl = flags[e];
       const R* z = meas + 3 * e;
       const bool st = z[2] >= 0;
-      if (fl & 1) {
-        R r[3], depth;
-        residual(t, q, V3{Xw[3 * e], Xw[3 * e + 1], Xw[3 * e + 2]}, z, st, cam, r, &depth);
-        err[3 * e] = r[0]; err[3 * e + 1] = r[1]; err[3 * e + 2] = r[2];
-      }
+      if (fl & 1) { R r[3], rho1; pose_edge_chi(t, q, e, fl, Xw, meas, info, cam, deltaMono, deltaStereo, err, r, &rho1); }
       const float c2 = (float)(info[e] * (err[3 * e] * err[3 * e] + err[3 * e + 1] * err[3 * e + 1] + err[3 * e + 2] * err[3 * e + 2]));
       const bool isBad = c2 > (st ? 7.815f : 5.991f);
       fl = (uint8_t)((fl & 2) | (isBad ? 1 : 0));
@@ -1353,7 +1216,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(int nFrames, con
       outlier[e] = isBad ? 1 : 0;
       myBad += isBad;
     }
-    bad = (int)pose_block_sum1((R)myBad, part);
+    bad = (int)block_sum1((R)myBad, part);
     __syncthreads();                         // flags / err of this episode are visible to the next one
     if (E < 10) break;                       // optimizer.edges().size() < 10 (:494)
   }

@@ -384,25 +384,9 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
       double tempChi;
       if ((rc = computeChi2(nxt, &tempChi, true))) return rc;  // also brings back scal[2], the factorisation status, and leaves err = errors of the trial state
       const double scaleSum = hscal[2];
-      const bool ok2 = hstatus[0] == 0;
-      if (!ok2) tempChi = std::numeric_limits<double>::max();
-      rho = currentChi - tempChi;
-      double scale = scaleSum + 1e-3;
-      rho /= scale;
-      if (rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1. - pow((2 * rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        lambda *= std::max(1. / 3., alpha);
-        ni = 2;
-        currentChi = tempChi;
-        R_.cur = nxt;  // discardTop(): keep the updated estimate
-        lastAccepted = true;
-      } else {
-        lastAccepted = false;
-        lambda *= ni;
-        ni *= 2;  // pop(): the previous estimate is still in poses[cur]
-        if (!std::isfinite(lambda)) { qmax++; R_.res->n_trials++; break; }
-      }
+      lastAccepted = lm_judge(lambda, ni, currentChi, rho, tempChi, scaleSum + 1e-3, hstatus[0] == 0);
+      if (lastAccepted) R_.cur = nxt;  // discardTop(): keep the updated estimate
+      else if (!std::isfinite(lambda)) { qmax++; R_.res->n_trials++; break; }  // pop(): the previous estimate is still in poses[cur]
       qmax++;
       R_.res->n_trials++;
     } while (rho < 0 && qmax < O.max_trials && !R_.stopped());
@@ -748,28 +732,10 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
       Job& X = *J[j];
       if (X.done) continue;
       const double* hs = B.hScal + (size_t)8 * j;
-      double tempChi = hs[0];
-      const double scaleSum = hs[2];
-      const bool ok2 = (int)hs[6] == 0;
-      if (!ok2) tempChi = std::numeric_limits<double>::max();
-      X.rho = X.currentChi - tempChi;
-      const double scale = scaleSum + 1e-3;
-      X.rho /= scale;
-      bool lambdaBroke = false;
-      if (X.rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1. - pow((2 * X.rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        X.lambda *= std::max(1. / 3., alpha);
-        X.ni = 2;
-        X.currentChi = tempChi;
-        X.run->cur ^= 1;  // discardTop(): keep the updated estimate
-        X.lastAccepted = true;
-      } else {
-        X.lastAccepted = false;
-        X.lambda *= X.ni;
-        X.ni *= 2;  // pop(): the previous estimate is still in poses[cur]
-        if (!std::isfinite(X.lambda)) lambdaBroke = true;
-      }
+      const double tempChi = hs[0], scaleSum = hs[2];
+      X.lastAccepted = lm_judge(X.lambda, X.ni, X.currentChi, X.rho, tempChi, scaleSum + 1e-3, (int)hs[6] == 0);
+      if (X.lastAccepted) X.run->cur ^= 1;  // discardTop(): keep the updated estimate; else pop(): the previous one is still in poses[cur]
+      const bool lambdaBroke = !X.lastAccepted && !std::isfinite(X.lambda);
       X.qmax++;
       X.run->res->n_trials++;
       if (lambdaBroke || !(X.rho < 0 && X.qmax < X.O.max_trials && !X.run->stopped())) endIteration(j);

@@ -8,7 +8,8 @@
 //   * Optimizer::OptimizeSim3 (src/Optimizer.cc) over g2o's VertexSim3Expmap (types/sim3.h) with EdgeSim3ProjectXYZ /
 //     EdgeInverseSim3ProjectXYZ (types_seven_dof_expmap.h), BaseBinaryEdge's central-difference Jacobian (delta 1e-9), Huber and the
 //     Levenberg-Marquardt trial loop of core/optimization_algorithm_levenberg.cpp: k_pose_optimize's structure (ba_kernels.hip.h)
-//     with a 7-vector and two edges per pair, in fp64.
+//     with a 7-vector and two edges per pair, in fp64.  The quaternion algebra, Huber, the fixed-order sums, the dense LL^T solve
+//     and the lambda control are those of g2o_math.hip.h, shared with the BA kernels.
 // Layout of the RANSAC: one wave per hypothesis (DESIGN.md section 6c has the comparison with a lane per hypothesis).  Every lane of
 // the wave solves Horn redundantly on the same three pairs (wave-uniform values: no broadcast, no divergence), then the wave strides
 // over the problem's pairs in global memory 64 at a time and counts inliers with a ballot, so a problem of any size needs no LDS.
@@ -16,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "g2o_math.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -230,49 +232,12 @@ __global__ __launch_bounds__(64) void k_sim3_replay(const RansacDev* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------ Sim3 LM (fp64)
-typedef double R;
-struct V3 { R x, y, z; };
-struct Q4 { R x, y, z, w; };
+using g2o::R; using g2o::V3; using g2o::Q4;
+using g2o::add; using g2o::cross; using g2o::scale; using g2o::qrot; using g2o::qmul; using g2o::rToQ;
+using g2o::huber; using g2o::block_sums; using g2o::block_sum1; using g2o::dense_solve; using g2o::lambda_init; using g2o::lm_judge;
+
 struct S3 { Q4 r; V3 t; R s; };
 
-// the quaternion helpers restate Eigen as ba_kernels.hip.h does; that header defines device globals, so it is not included twice
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 scl(V3 a, R s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {   // Eigen quaternion * vector
-  V3 qv{q.x, q.y, q.z};
-  V3 uv = cross(qv, v);
-  uv = add(uv, uv);
-  return add(add(v, scl(uv, q.w)), cross(qv, uv));
-}
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
-          a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-__device__ __forceinline__ Q4 rToQ(const R a[3][3]) {   // Eigen Quaternion(Matrix3)
-  Q4 q;
-  R t = a[0][0] + a[1][1] + a[2][2];
-  if (t > 0) {
-    t = sqrt(t + 1.0);
-    q.w = 0.5 * t;
-    t = 0.5 / t;
-    q.x = (a[2][1] - a[1][2]) * t; q.y = (a[0][2] - a[2][0]) * t; q.z = (a[1][0] - a[0][1]) * t;
-  } else {
-    int i = 0;
-    if (a[1][1] > a[0][0]) i = 1;
-    if (a[2][2] > a[i][i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = sqrt(a[i][i] - a[j][j] - a[k][k] + 1.0);
-    R c[3];
-    c[i] = 0.5 * t;
-    t = 0.5 / t;
-    q.w = (a[k][j] - a[j][k]) * t;
-    c[j] = (a[j][i] + a[i][j]) * t;
-    c[k] = (a[k][i] + a[i][k]) * t;
-    q.x = c[0]; q.y = c[1]; q.z = c[2];
-  }
-  return q;
-}
 // g2o Sim3(const Vector7d& update) (types/sim3.h): omega, upsilon, sigma and its A, B, C branches
 __device__ __forceinline__ S3 sim3Exp(const R* u) {
   const R ox = u[0], oy = u[1], oz = u[2], sigma = u[6];
@@ -320,10 +285,10 @@ __device__ __forceinline__ S3 sim3Exp(const R* u) {
   r.s = s;
   return r;
 }
-__device__ __forceinline__ S3 compose(const S3& a, const S3& b) { return {qmul(a.r, b.r), add(scl(qrot(a.r, b.t), a.s), a.t), a.s * b.s}; }
+__device__ __forceinline__ S3 compose(const S3& a, const S3& b) { return {qmul(a.r, b.r), add(scale(qrot(a.r, b.t), a.s), a.t), a.s * b.s}; }
 __device__ __forceinline__ S3 inverse(const S3& a) {
   const Q4 rc{-a.r.x, -a.r.y, -a.r.z, a.r.w};
-  return {rc, qrot(rc, scl(a.t, -1. / a.s)), 1. / a.s};
+  return {rc, qrot(rc, scale(a.t, -1. / a.s)), 1. / a.s};
 }
 __device__ __forceinline__ S3 oplus(const S3& S, const R* x, bool fix) {   // VertexSim3Expmap::oplusImpl
   R u[7];
@@ -334,83 +299,14 @@ __device__ __forceinline__ S3 oplus(const S3& S, const R* x, bool fix) {   // Ve
 }
 // obs - cam_map(project(S.map(X)))
 __device__ __forceinline__ void projErr(const S3& S, const R* X, const R* K, const R* obs, R* e) {
-  const V3 p = add(scl(qrot(S.r, V3{X[0], X[1], X[2]}), S.s), S.t);
+  const V3 p = add(scale(qrot(S.r, V3{X[0], X[1], X[2]}), S.s), S.t);
   e[0] = obs[0] - ((p.x / p.z) * K[0] + K[2]);
   e[1] = obs[1] - ((p.y / p.z) * K[1] + K[3]);
-}
-__device__ __forceinline__ void huber(R e, R delta, R* rho0, R* rho1) {   // robust_kernel_impl.cpp
-  const R dsqr = delta * delta;
-  if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
-  else { const R s = sqrt(e); *rho0 = 2 * s * delta - dsqr; *rho1 = delta / s; }
 }
 __device__ __forceinline__ R chi2(const R* e, R w) { return e[0] * (w * e[0]) + e[1] * (w * e[1]); }
 
 constexpr int kOptThreads = 256;   // 4 waves
 constexpr int kAcc = 36;           // packed upper 7x7 (28) + b (7) + robust chi2
-
-template <int K>
-__device__ __forceinline__ void block_sums(R (&v)[K], R (*part)[kAcc], R (&out)[K]) {   // fixed order: butterfly, then waves 0..3
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; k++) part[wv][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; k++) out[k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
-}
-__device__ __forceinline__ R block_sum1(R v, R (*part)[kAcc]) {
-  R a[1] = {v}, o[1];
-  block_sums<1>(a, part, o);
-  return o[0];
-}
-
-// LinearSolverDense as ba_kernels.hip.h's pose_solve6 restates it (LL^T, rejected when not positive definite), for 7 unknowns
-__device__ __forceinline__ bool solve7(const R (&Hs)[28], R lambda, const R (&b)[7], R (&x)[7]) {
-  R L[7][7];
-  int k = 0;
-#pragma unroll
-  for (int r = 0; r < 7; r++)
-#pragma unroll
-    for (int c = r; c < 7; c++, k++) L[c][r] = Hs[k] + (r == c ? lambda : 0.0);
-#pragma unroll
-  for (int j = 0; j < 7; j++) {
-    R d = L[j][j];
-#pragma unroll
-    for (int q = 0; q < j; q++) d -= L[j][q] * L[j][q];
-    if (!(d > 0)) return false;
-    d = sqrt(d);
-    L[j][j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 7; i++) {
-      R s2 = L[i][j];
-#pragma unroll
-      for (int q = 0; q < j; q++) s2 -= L[i][q] * L[j][q];
-      L[i][j] = s2 / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 7; i++) {
-    R s2 = b[i];
-#pragma unroll
-    for (int q = 0; q < i; q++) s2 -= L[i][q] * x[q];
-    x[i] = s2 / L[i][i];
-  }
-#pragma unroll
-  for (int i = 6; i >= 0; i--) {
-    R s2 = x[i];
-#pragma unroll
-    for (int q = i + 1; q < 7; q++) s2 -= L[q][i] * x[q];
-    x[i] = s2 / L[i][i];
-  }
-  return true;
-}
 
 struct OptArgs {
   const int* start;
@@ -511,34 +407,18 @@ __device__ R lm_optimize(const OptArgs& a, int e0, int E, S3& S, const R* K1, co
 #pragma unroll
     for (int k = 0; k < 7; k++) b[k] = Sm[28 + k];
     currentChi = Sm[35];
-    if (it == 0) {   // computeLambdaInit
-      R mx = 0;
-      int k = 0;
-#pragma unroll
-      for (int r = 0; r < 7; r++) { mx = fmax(fabs(Hs[k]), mx); k += 7 - r; }
-      lambda = 1e-5 * mx; ni = 2;
-    }
+    if (it == 0) { lambda = lambda_init<7>(Hs); ni = 2; }   // computeLambdaInit
     R rho = 0, x[7] = {0, 0, 0, 0, 0, 0, 0};
     int qmax = 0;
     do {
       const S3 Sb = S;   // push()
-      const bool ok = solve7(Hs, lambda, b, x);
+      const bool ok = dense_solve<7>(Hs, lambda, b, x);
       S = oplus(S, x, fix);   // g2o applies _x even after a failed solve
-      R tempChi = active_chi(a, e0, E, S, inverse(S), K1, K2, L);
-      if (!ok) tempChi = 1.7976931348623157e308;
-      rho = currentChi - tempChi;
-      R sc = 1e-3;
+      const R tempChi = active_chi(a, e0, E, S, inverse(S), K1, K2, L);
+      R sc = 1e-3;   // computeScale() + 1e-3
 #pragma unroll
       for (int j = 0; j < 7; j++) sc += x[j] * (lambda * x[j] + b[j]);
-      rho /= sc;
-      if (rho > 0 && isfinite(tempChi)) {
-        R alpha = 1. - pow((2 * rho - 1), 3.0);
-        alpha = fmin(alpha, 2. / 3.);
-        lambda *= fmax(1. / 3., alpha);
-        ni = 2;
-        currentChi = tempChi;
-      } else {
-        lambda *= ni; ni *= 2;
+      if (!lm_judge(lambda, ni, currentChi, rho, tempChi, sc, ok)) {
         S = Sb;   // pop()
         if (!isfinite(lambda)) { qmax++; trials++; break; }
       }
