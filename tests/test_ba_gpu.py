@@ -444,3 +444,37 @@ def test_release_gives_the_pooled_scratch_back():
     bb = y.Optimizer.local_bundle_adjust_batch([prob] * 3)
     assert a["poses"].tobytes() == b["poses"].tobytes() and a["points"].tobytes() == b["points"].tobytes()
     assert all(x["poses"].tobytes() == a["poses"].tobytes() for x in ba + bb)
+
+
+def test_result_does_not_depend_on_what_the_scratch_held():
+    """A solve's device memory is a few arenas that are re-laid out in place for every problem, so a small problem solved after a
+    large one runs on whatever the large one left there, at other offsets.  Problem B on freshly allocated arenas and B again on
+    arenas that a larger problem A has just used must agree byte for byte - single solve, lock-step batch and pose-only batch -
+    and the batch members must equal the single solve.  Anything a kernel reads before the stage has written it shows up here."""
+    import ydorbslam_amd as y
+    from ydorbslam_amd.synth import synth_pose_problem
+
+    def run(prob, frames):
+        return (y.Optimizer.local_bundle_adjust(prob), y.Optimizer.local_bundle_adjust_batch([prob, prob]),
+                y.Optimizer.optimize_poses(frames))
+
+    def same_ba(a, b):
+        return (a["poses"].tobytes() == b["poses"].tobytes() and a["points"].tobytes() == b["points"].tobytes()
+                and np.array_equal(a["outlier"], b["outlier"]) and a["trials"] == b["trials"] and a["log"].tobytes() == b["log"].tobytes())
+
+    B = synth_ba_problem(5, 150, 4, seed=3)
+    framesB = [synth_pose_problem(n_pts=60, seed=70 + i) for i in range(2)]
+    A = synth_ba_problem(9, 600, 5, seed=4)
+    framesA = [synth_pose_problem(n_pts=200, seed=80 + i) for i in range(4)]
+    y.Optimizer.release(0)
+    fresh = run(B, framesB)
+    y.Optimizer.release(0)
+    big = run(A, framesA)
+    warm = run(B, framesB)
+    for single, batch, _ in (fresh, big, warm):
+        assert all(same_ba(single, m) for m in batch)
+    assert same_ba(fresh[0], warm[0])
+    assert all(same_ba(f, w) for f, w in zip(fresh[1], warm[1]))
+    for f, w in zip(fresh[2], warm[2]):
+        assert f["pose"].tobytes() == w["pose"].tobytes() and np.array_equal(f["outlier"], w["outlier"])
+        assert f["inliers"] == w["inliers"] and f["trials"] == w["trials"] and f["chi2"].tobytes() == w["chi2"].tobytes()

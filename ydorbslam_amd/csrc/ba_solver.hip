@@ -29,41 +29,112 @@ using namespace ydorb::ba;
 
 namespace {
 
-struct DBuf : Mem {   // BA's buffers: 256-byte floor, and a buffer may instead be a slice of another one
-  bool view = false;   // a slice of another DBuf (Ctx::upArena): not owned, so let go of and never freed
-  DBuf() { floor = 256; }
-  void setView(void* ptr, size_t bytes) { release(); p = ptr; cap = bytes; view = true; }
-  void release() { if (view) { p = nullptr; view = false; } Mem::release(); }
-  int alloc(size_t bytes) { release(); return Mem::alloc(bytes); }
-  int ensure(size_t bytes) { return view ? alloc(want(bytes)) : Mem::ensure(bytes); }   // a slice is never grown in place
-};
-
 enum { PH_ERR = 0, PH_BUILD, PH_SCHUR, PH_SOLVE, PH_UPDATE, PH_COUNT };
 
-struct Ctx {  // per-device scratch, reused across calls (localBundleAdjust runs on one thread, localMapping.cpp:29)
+// The reduced system of one optimize() call: stage 1 sizes it, stage 2 re-uses it (and the arenas laid out for it) as it is.
+struct Sys { std::vector<int> act; int nL = 0, nPf = 0, Ea = 0, n = 0, nb = 0, nBlkE = 0, nBuckets = 0, nPoseEdges = 0; size_t nItems = 0; };
+
+// Hands out the arrays of an arena in order, every one 256-byte aligned.  The lay*() functions below run twice per (re)layout: over a
+// null base for the size the arena needs, then over the arena for the pointers.
+struct Carve {
+  uintptr_t base;
+  Layout L{0, 256};
+  explicit Carve(void* p) : base(reinterpret_cast<uintptr_t>(p)) {}
+  template <class T> void take(T*& ptr, size_t count) { ptr = reinterpret_cast<T*>(base + L.add(sizeof(T) * count)); }
+};
+
+// `state`: both copies of the estimate (LM push / pop is a swap of the index).  beginSolve uploads [0]; prepareStage copies cur -> cur ^ 1
+// whole before the first k_update of a stage, which writes the free poses and the active landmarks only.
+struct StatePtrs { double *poses[2], *pts[2]; };
+size_t layState(int K, int NP, void* base, StatePtrs& st) {
+  Carve a(base);
+  for (int i = 0; i < 2; i++) { a.take(st.poses[i], (size_t)7 * K); a.take(st.pts[i], (size_t)3 * NP); }
+  return a.L.bytes;
+}
+
+// `up`: what the host orders and uploads for a stage, through the pinned staging area at the same offsets and with ONE copy (twelve
+// before: with 16 set-up threads of a batch the runtime's lock was the cost).  Written whole by that copy; k_cull later rewrites eInfo / eRobust.
+struct UpPtrs { int *ePose, *ePidx, *ePt, *eLm, *ptStart, *poseStart, *ptOf, *poseEdges, *poseOf; double *eMeas, *eInfo; uint8_t* eRobust; };
+size_t layUp(const Sys& Y, void* base, UpPtrs& u) {
+  Carve a(base);
+  const size_t Ea = Y.Ea;
+  a.take(u.ePose, Ea); a.take(u.ePidx, Ea); a.take(u.ePt, Ea); a.take(u.eLm, Ea); a.take(u.eMeas, 3 * Ea); a.take(u.eInfo, Ea); a.take(u.eRobust, Ea);
+  a.take(u.ptStart, Y.nL + 1); a.take(u.poseStart, Y.nPf + 1); a.take(u.ptOf, Y.nL); a.take(u.poseEdges, Y.nPoseEdges); a.take(u.poseOf, Y.nPf);
+  return a.L.bytes;
+}
+
+// `work`: everything the device itself writes during a stage.  Nothing is cleared at allocation and the arena keeps whatever an earlier,
+// differently laid out solve left, so every array needs a first writer inside the stage.  Who that is ("free edge" = pidx >= 0; the
+// lock-step kb_* wrappers leave before the body when blockIdx.x is past the member's OWN count, so a member smaller than the grid reads
+// and writes exactly what its single solve does; it keeps scal / status in the pool's dScal, with the same writers):
+//   eInfo0    copy of eInfo right after the upload;  eOutlier: k_cull(final), every edge, before the read-back
+//   err       memset at stage 1 (an edge that is never evaluated has error 0), then k_errors for every edge with information != 0
+//   pair*     pairCnt: memset, then k_pair_count;  pairStart: k_excl_scan, [0 .. nBuckets];  pairCursor: copy of pairStart;  pairA: k_pair_fill,
+//             pairB: k_pair_sort, all nItems entries each.  With nBuckets == 0 none of the five is written or read.
+//   partial   [0, nBlkE) k_errors and [nBlkE, ..) k_scale, one per workgroup; k_sum_partials reads exactly those counts
+//   Hll, bl   k_build_points, every landmark;  Hpl: k_build_points, every free edge (zeros for a culled one), the only ones read
+//   Hpp | bp  k_build_poses, every free pose;  Dinv, db: k_dinv, every landmark;  BD: k_bd, every free edge
+//   status    k_dinv, the first kernel of every trial, before k_chol_step / k_sum_partials touch it
+//   S | bs | diagInv   ONE memset at the start of every stage.  Per trial k_schur_pairs writes the lower 6x6 blocks and the padding, k_bs bs;
+//             the diagonal 32x32 tiles above the block diagonal are only written by the rank-32 updates and loaded (not used) by the next
+//             factorisation: hence the clear of S.  diagInv[kb] is written by launch kb of k_chol_step UNLESS a pivot is not positive: the
+//             panel then leaves early, and the later launches and k_chol_solve read diagInv[kb ..] as the last trial left it.  That step is
+//             rejected, yet its scale sum decides the sign of rho: before diagInv was cleared with S, a failed first factorisation of a
+//             solve read whatever the memory held.  diagL is write-only.
+//   yv        [0, n - 32) by the forward-substitution workgroup of k_chol_step launches 1 .. nb - 1, all k_chol_solve reads
+//   xp        k_chol_solve, [0, n);  xl: k_backsub, every landmark
+//   scal      [0] and [2] k_sum_partials, [1] k_max_diag (first iteration), [6], [7] the status copies; [3 .. 5] are never written: they
+//             travel to the host with every read-back and nothing there reads them
+struct WorkPtrs {
+  double *eInfo0, *err, *partial, *Hll, *bl, *Hpl, *BD, *Hpp, *S, *diagInv, *diagL, *Dinv, *db, *xp, *xl, *yv, *scal;
+  uint8_t* eOutlier;
+  int *status, *pairCnt, *pairStart, *pairCursor;
+  int2 *pairA, *pairB;
+  double* bp(const Sys& Y) const { return Hpp + (size_t)36 * Y.nPf; }   // Hpp | bp: one all-reduce covers both
+  double* bs(const Sys& Y) const { return S + (size_t)Y.n * Y.n; }      // S | bs likewise
+};
+size_t layWork(const Sys& Y, void* base, WorkPtrs& w) {
+  Carve a(base);
+  const size_t Ea = Y.Ea, nL = Y.nL, nPf = Y.nPf, n = Y.n, tiles = (size_t)Y.nb * NB * NB, nBk = (size_t)Y.nBuckets + 1, items = std::max<size_t>(Y.nItems, 1);
+  a.take(w.eInfo0, Ea); a.take(w.eOutlier, Ea); a.take(w.err, 3 * Ea); a.take(w.partial, Y.nBlkE + (6 * nPf + 3 * nL + 255) / 256 + 1);
+  a.take(w.Hll, 6 * nL); a.take(w.bl, 3 * nL); a.take(w.Hpl, 18 * Ea); a.take(w.BD, 18 * Ea); a.take(w.Hpp, 42 * std::max<size_t>(nPf, 1));
+  a.take(w.S, n * n + n + tiles); w.diagInv = w.S + n * n + n;   // one array on purpose: cleared together
+  a.take(w.diagL, tiles); a.take(w.Dinv, 6 * nL); a.take(w.db, 3 * nL); a.take(w.xp, n); a.take(w.yv, n); a.take(w.xl, 3 * nL);
+  a.take(w.scal, 8); a.take(w.status, 2); a.take(w.pairCnt, nBk); a.take(w.pairStart, nBk); a.take(w.pairCursor, nBk); a.take(w.pairA, items); a.take(w.pairB, items);
+  return a.L.bytes;
+}
+
+// `pose`: the arrays of one ydorb_pose_optimize batch; the first five are uploaded, the rest written by k_pose_optimize.
+struct PosePtrs { int *start, *inl, *trials; double *poses, *X, *meas, *info, *err, *chi; uint8_t *flags, *outlier; };
+size_t layPose(int n, size_t E, void* base, PosePtrs& q) {
+  Carve a(base);
+  a.take(q.start, n + 1); a.take(q.poses, (size_t)7 * n); a.take(q.X, 3 * E); a.take(q.meas, 3 * E); a.take(q.info, E);
+  a.take(q.err, 3 * E); a.take(q.flags, E); a.take(q.outlier, E); a.take(q.inl, n); a.take(q.chi, (size_t)4 * n); a.take(q.trials, n);
+  return a.L.bytes;
+}
+
+// The device memory and staging of ONE solve: a single solve's context and a lock-step batch member hold one each.  An arena grows
+// with 25 % slack when a solve needs more than it has and is otherwise re-laid out in place.
+struct SolveMem {
   int device = -1;
-  hipStream_t stream = nullptr;
-  DBuf poses[2], pts[2];
-  DBuf upArena;   // the ordered edge arrays and index lists of a stage, laid out like the pinned staging area: ONE upload per stage; the twelve buffers
-                  // below that the host fills (ePose .. ptOf except eInfo0 / eOutlier) are views into it
-  DBuf ePose, ePidx, ePt, eMeas, eInfo, eInfo0, eRobust, eOutlier, eLm, ptStart, poseStart, poseEdges, poseOf, ptOf;
-  DBuf err, partial, Hll, bl, Hpl, BD, Hpp, bp, S, diagL, diagInv, bs, Dinv, db, xp, xl, yv, scal, status, pairCnt, pairStart, pairCursor, pairA, pairB;
-  hipEvent_t ev[2 * PH_COUNT + 2]{};
-  bool evInit = false;
-  double* hPin = nullptr;   // pinned read-back area: scal[8] + status[2] (one stream sync per LM trial)
-  Mem hStage;   // pinned staging of the ordered edge arrays on their way up and of the results on their way down: an asynchronous
-                // copy out of / into pageable memory runs at ~8 GB/s and makes the host wait for the stream
-  Ctx() { hStage.host = true; }
+  hipStream_t stream = nullptr;   // a batch member: the set-up or the batch's stream (not owned)
+  Mem state, up, work;
+  StatePtrs st{};   // where the arrays of the three arenas are (layState / layUp / layWork)
+  UpPtrs u{};
+  WorkPtrs w{};
+  PinnedMem hStage;   // pinned staging of the ordered edge arrays on their way up and of the results on their way down: an asynchronous
+                      // copy out of / into pageable memory runs at ~8 GB/s and makes the host wait for the stream
   int stage(size_t bytes) { return bytes <= hStage.cap ? YDORB_OK : hStage.alloc(bytes + bytes / 4 + 4096); }
-  DBuf pStart, pPoses, pX, pMeas, pInfo, pErr, pFlags, pOutlier, pInl, pChi, pTrials;   // pose-only batches
-  void releaseBuffers() {   // ydorb_ba_release: device scratch and pinned staging back to the system (stream and events stay)
-    for (DBuf* b : {&poses[0], &poses[1], &pts[0], &pts[1], &upArena, &ePose, &ePidx, &ePt, &eMeas, &eInfo, &eInfo0, &eRobust, &eOutlier, &eLm, &ptStart,
-                    &poseStart, &poseEdges, &poseOf, &ptOf, &err, &partial, &Hll, &bl, &Hpl, &BD, &Hpp, &bp, &S, &diagL, &diagInv, &bs, &Dinv, &db,
-                    &xp, &xl, &yv, &scal, &status, &pairCnt, &pairStart, &pairCursor, &pairA, &pairB, &pStart, &pPoses, &pX, &pMeas, &pInfo, &pErr,
-                    &pFlags, &pOutlier, &pInl, &pChi, &pTrials})
-      b->release();
-    hStage.release();
-  }
+  void releaseBuffers() { for (Mem* m : {&state, &up, &work, static_cast<Mem*>(&hStage)}) m->release(); }
+};
+
+struct Ctx {  // per-device context of the single solves and the pose batches, reused across calls (localBundleAdjust runs on one thread, localMapping.cpp:29)
+  SolveMem mem;
+  Mem pose;   // pose-only batches (layPose)
+  hipEvent_t ev[2 * PH_COUNT + 2]{};
+  PinnedMem hPin;   // read-back area: scal[8] + status[2] (one stream sync per LM trial); lives as long as the stream and the events
+  // ydorb_ba_release: device scratch and pinned staging back to the system (stream, events and hPin stay)
+  void releaseBuffers() { mem.releaseBuffers(); pose.release(); }
 };
 // A small pool of contexts per device: one localBundleAdjust at a time is the reference's use (LocalMapping thread), but the solve
 // is a latency chain that leaves most of the GPU idle, so several host threads (several maps / sessions) may solve concurrently,
@@ -73,8 +144,30 @@ std::mutex g_mu[16][kCtxPool];
 Ctx g_ctx[16][kCtxPool];
 std::mutex g_pick;
 
+// Locks a free context of the device's pool (all busy: queues behind slot 0) and creates its stream, events and read-back area on first
+// use.  Null when that failed; the error text is set.
+Ctx* acquireCtx(int device, std::unique_lock<std::mutex>& lock) {
+  int slot = -1;
+  {
+    std::lock_guard<std::mutex> pick(g_pick);
+    for (int i = 0; i < kCtxPool && slot < 0; i++)
+      if (g_mu[device][i].try_lock()) slot = i;
+  }
+  if (slot < 0) { slot = 0; g_mu[device][0].lock(); }
+  lock = std::unique_lock<std::mutex>(g_mu[device][slot], std::adopt_lock);
+  Ctx& c = g_ctx[device][slot];
+  auto init = [&]() -> int {
+    c.mem.device = device;
+    HIPCHK(hipStreamCreateWithFlags(&c.mem.stream, hipStreamNonBlocking));
+    for (auto& e : c.ev) HIPCHK(hipEventCreate(&e));
+    return c.hPin.alloc(sizeof(double) * 16);
+  };
+  if (!c.mem.stream && init() != YDORB_OK) return nullptr;
+  return &c;
+}
+
 struct Run {
-  Ctx* c;
+  SolveMem* c;
   const YdBaProblem* P;
   const YdBaOptions* O;
   YdBaResult* res;
@@ -84,7 +177,9 @@ struct Run {
   bool phaseTimes = false;   // YDORB_BA_PHASE_TIMES
   double phaseMs[PH_COUNT] = {0, 0, 0, 0, 0};
   bool pending[PH_COUNT] = {false, false, false, false, false};
-  struct Sys { std::vector<int> act; int nL = 0, nPf = 0, Ea = 0, n = 0, nb = 0, nBlkE = 0, nBuckets = 0; } sys;   // stage 1's system, re-used by stage 2
+  Sys sys;
+  hipEvent_t* ev = nullptr;   // Ctx::ev and Ctx::hPin of a single solve (optimize()); a lock-step batch member has neither
+  double* hPin = nullptr;
   bool stopped() const { return P->stop && *P->stop; }
 };
 
@@ -109,7 +204,7 @@ static void trace(const char* what) {
 
 struct PhaseTimer {
   Run& r; int ph; hipEvent_t a, b; bool on;
-  PhaseTimer(Run& r_, int ph_) : r(r_), ph(ph_), a(r_.c->ev[2 * ph_]), b(r_.c->ev[2 * ph_ + 1]), on(r_.phaseTimes) {
+  PhaseTimer(Run& r_, int ph_) : r(r_), ph(ph_), a(r_.ev[2 * ph_]), b(r_.ev[2 * ph_ + 1]), on(r_.phaseTimes) {
     if (!on) return;   // YDORB_BA_PHASE_TIMES not asked for: no events on the stream
     collect(r_, ph_);  // an earlier recording of this phase's events must be read before they are re-recorded
     (void)hipEventRecord(a, r.c->stream);
@@ -118,7 +213,7 @@ struct PhaseTimer {
   static void collect(Run& r_, int ph_) {
     if (!r_.pending[ph_]) return;
     float ms = 0;
-    if (hipEventSynchronize(r_.c->ev[2 * ph_ + 1]) == hipSuccess && hipEventElapsedTime(&ms, r_.c->ev[2 * ph_], r_.c->ev[2 * ph_ + 1]) == hipSuccess)
+    if (hipEventSynchronize(r_.ev[2 * ph_ + 1]) == hipSuccess && hipEventElapsedTime(&ms, r_.ev[2 * ph_], r_.ev[2 * ph_ + 1]) == hipSuccess)
       r_.phaseMs[ph_] += ms;
     r_.pending[ph_] = false;
   }
@@ -128,13 +223,13 @@ struct PhaseTimer {
 // refreshed information / robust flags on stage 1's structures (stage 2); leaves S cleared and both estimate buffers in agreement.
 // R_.sys.Ea == 0 afterwards means there is nothing to optimise.
 int prepareStage(Run& R_, bool reuse) {
-  Ctx& c = *R_.c;
+  SolveMem& c = *R_.c;
   const YdBaProblem& P = *R_.P;
   const YdBaOptions& O = *R_.O;
   hipStream_t s = c.stream;
   const int K = P.n_poses, NP = P.n_points, E = P.n_edges;
   trace("optimize: begin");
-  Run::Sys& Y = R_.sys;
+  Sys& Y = R_.sys;
   // Stage 2 (after the chi2 cull) re-uses stage 1's device structures: a culled edge keeps its slot with information 0, which
   // every kernel treats as "skip" — no second host ordering, upload or pair-bucket build.  Landmarks / poses that lose all their
   // edges stay in the system with H = lambda*I, b = 0, i.e. dx = 0: the same estimate g2o keeps by leaving them out.
@@ -150,14 +245,13 @@ int prepareStage(Run& R_, bool reuse) {
       for (int k = 0; k < K; k++) if (pu[k] && !P.pose_fixed[k]) { poseIdx[k] = (int)poseOf.size(); poseOf.push_back(k); }
       for (int p = 0; p < NP; p++) if (qu[p]) { ptIdx[p] = (int)ptOf.size(); ptOf.push_back(p); }
     }
-    const int nP = (int)poseOf.size(), nL = (int)ptOf.size(), Ea = (int)act.size();
+    const int nL = (int)ptOf.size(), Ea = (int)act.size();
     if (O.world > 1) {
       // every rank must factorise the same reduced system: the free-pose set comes from the caller's fixed mask only
       poseOf.clear();
       for (int k = 0; k < K; k++) { poseIdx[k] = -1; if (!P.pose_fixed[k]) { poseIdx[k] = (int)poseOf.size(); poseOf.push_back(k); } }
     }
     const int nPf = (int)poseOf.size();
-    (void)nP;
     {  // order by (landmark index, pose index, edge index): counting sort by landmark, then a tiny insertion sort per landmark
       std::vector<int> start(nL + 1, 0), sorted(Ea);
       for (int e : act) start[ptIdx[P.edge_point[e]] + 1]++;
@@ -192,66 +286,52 @@ int prepareStage(Run& R_, bool reuse) {
       std::vector<int> fill(hPoseStart.begin(), hPoseStart.end() - 1);
       for (int i = 0; i < Ea; i++) if (hPidx[i] >= 0) hPoseEdges[fill[hPidx[i]]++] = i;
     }
-    const int n = std::max(NB, (6 * nPf + NB - 1) / NB * NB), nb = n / NB;
-    const int nBlkE = (Ea + 255) / 256;
-    int rc;
-    if ((rc = c.eInfo0.ensure(sizeof(double) * Ea)) || (rc = c.eOutlier.ensure(Ea)) || (rc = c.err.ensure(sizeof(double) * 3 * Ea)) || (rc = c.partial.ensure(sizeof(double) * (nBlkE + (6 * nPf + 3 * nL + 255) / 256 + 1))) ||
-        (rc = c.Hll.ensure(sizeof(double) * 6 * nL)) || (rc = c.bl.ensure(sizeof(double) * 3 * nL)) || (rc = c.Hpl.ensure(sizeof(double) * 18 * (size_t)Ea)) ||
-        (rc = c.BD.ensure(sizeof(double) * 18 * (size_t)Ea)) ||
-        (rc = c.Hpp.ensure(sizeof(double) * 42 * std::max(nPf, 1))) || (rc = c.S.ensure(sizeof(double) * ((size_t)n * n + n))) ||
-        (rc = c.diagL.ensure(sizeof(double) * (size_t)nb * NB * NB)) || (rc = c.diagInv.ensure(sizeof(double) * (size_t)nb * NB * NB)) || (rc = c.Dinv.ensure(sizeof(double) * 6 * nL)) || (rc = c.db.ensure(sizeof(double) * 3 * nL)) ||
-        (rc = c.xp.ensure(sizeof(double) * n)) || (rc = c.yv.ensure(sizeof(double) * n)) || (rc = c.xl.ensure(sizeof(double) * 3 * nL)) || (rc = c.scal.ensure(sizeof(double) * 8)) ||
-        (rc = c.status.ensure(sizeof(int) * 2)))
-      return rc;
-    // Hpp and bp are contiguous ([36 nPf | 6 nPf]) so one all-reduce covers both; bs follows S for the same reason
-    trace("optimize: host ordering done");
-    {  // through the context's pinned staging area (true asynchronous copies at PCIe rate; the area is free again at the sync below)
-      auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-      const size_t total = 4 * al(sizeof(int) * Ea) + al(sizeof(double) * 3 * Ea) + al(sizeof(double) * Ea) + al(Ea) + al(sizeof(int) * (nL + 1)) +
-                           al(sizeof(int) * (nPf + 1)) + al(sizeof(int) * ptOf.size()) + al(sizeof(int) * hPoseEdges.size()) + al(sizeof(int) * poseOf.size());
-      if ((rc = c.stage(total)) || (rc = c.upArena.ensure(total))) return rc;
-      size_t off = 0;
-      // every array is copied into the staging area and its device buffer becomes the slice of the arena at the same offset; ONE
-      // hipMemcpyAsync then moves the stage's inputs (twelve calls before: with 16 set-up threads of a batch the runtime's lock was the cost)
-      auto up = [&](DBuf& dst, const void* src, size_t bytes) {
-        if (bytes) memcpy(c.hStage.as<uint8_t>() + off, src, bytes);
-        dst.setView(reinterpret_cast<uint8_t*>(c.upArena.p) + off, bytes);
-        off += al(bytes);
-      };
-  #define UP(buf, vec, T) up(c.buf, vec.data(), sizeof(T) * vec.size())
-      UP(ePose, hPose, int); UP(ePidx, hPidx, int); UP(ePt, hPt, int); UP(eLm, hLm, int); UP(eMeas, hMeas, double); UP(eInfo, hInfo, double);
-      UP(eRobust, hRobust, uint8_t); UP(ptStart, hPtStart, int); UP(poseStart, hPoseStart, int); UP(ptOf, ptOf, int);
-      UP(poseEdges, hPoseEdges, int); UP(poseOf, poseOf, int);
-  #undef UP
-      if (off) HIPCHK(hipMemcpyAsync(c.upArena.p, c.hStage.as<uint8_t>(), off, hipMemcpyHostToDevice, s));
-      // the original information: the chi2 tests between and after the stages use it (k_cull)
-      HIPCHK(hipMemcpyAsync(c.eInfo0.p, c.eInfo.p, sizeof(double) * Ea, hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemsetAsync(c.err.p, 0, sizeof(double) * 3 * Ea, s));   // an edge that is never evaluated (stop flag) has error 0
-    }
-    trace("optimize: uploads enqueued");
-    // pose-pair buckets of the Schur complement (structure is fixed for this optimize() call)
-    const int nBuckets = nPf * (nPf + 1) / 2;
-    size_t nItems = 0;
+    Sys Z;
+    Z.nL = nL; Z.nPf = nPf; Z.Ea = Ea; Z.nPoseEdges = (int)hPoseEdges.size();
+    Z.n = std::max(NB, (6 * nPf + NB - 1) / NB * NB); Z.nb = Z.n / NB;
+    Z.nBlkE = (Ea + 255) / 256;
+    Z.nBuckets = nPf * (nPf + 1) / 2;   // pose-pair buckets of the Schur complement (structure is fixed for this optimize() call)
     for (int l = 0; l < nL; l++) {
       size_t m = 0;
       for (int i = hPtStart[l]; i < hPtStart[l + 1]; i++) m += hPidx[i] >= 0;
-      nItems += m * (m + 1) / 2;
+      Z.nItems += m * (m + 1) / 2;
     }
-    if ((rc = c.pairCnt.ensure(sizeof(int) * (nBuckets + 1))) || (rc = c.pairStart.ensure(sizeof(int) * (nBuckets + 1))) ||
-        (rc = c.pairCursor.ensure(sizeof(int) * (nBuckets + 1))) || (rc = c.pairA.ensure(sizeof(int2) * std::max<size_t>(nItems, 1))) ||
-        (rc = c.pairB.ensure(sizeof(int2) * std::max<size_t>(nItems, 1))))
-      return rc;
-    if (nBuckets > 0) {
-      EdgeSoA Ed{c.ePose.as<int>(), c.ePidx.as<int>(), c.ePt.as<int>(), c.eMeas.as<double>(), c.eInfo.as<double>(), c.eRobust.as<uint8_t>(), Ea};
-      HIPCHK(hipMemsetAsync(c.pairCnt.p, 0, sizeof(int) * (nBuckets + 1), s));
-      hipLaunchKernelGGL(k_pair_count, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, c.ptStart.as<int>(), nL, c.pairCnt.as<int>());
-      hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(256), 0, s, c.pairCnt.as<int>(), nBuckets, c.pairStart.as<int>());
-      HIPCHK(hipMemcpyAsync(c.pairCursor.p, c.pairStart.p, sizeof(int) * (nBuckets + 1), hipMemcpyDeviceToDevice, s));
-      hipLaunchKernelGGL(k_pair_fill, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, c.ptStart.as<int>(), nL, c.pairCursor.as<int>(), c.pairA.as<int2>());
-      hipLaunchKernelGGL(k_pair_sort, dim3((nBuckets + 3) / 4), dim3(256), 0, s, c.pairStart.as<int>(), nBuckets, c.pairA.as<int2>(), c.pairB.as<int2>());
+    trace("optimize: host ordering done");
+    // the two arenas of the stage: sized, grown if need be (at most two hipMalloc where every array had its own), then laid out
+    const size_t upBytes = layUp(Z, nullptr, c.u);
+    int rc;
+    if ((rc = c.stage(upBytes)) || (rc = c.up.ensure(upBytes)) || (rc = c.work.ensure(layWork(Z, nullptr, c.w)))) return rc;
+    layUp(Z, c.up.p, c.u);
+    layWork(Z, c.work.p, c.w);
+    const UpPtrs& u = c.u;
+    const WorkPtrs& w = c.w;
+    {  // through the context's pinned staging area (true asynchronous copies at PCIe rate; the area is free again at the sync below)
+      auto up = [&](const void* dst, const void* src, size_t bytes) {   // into the staging area at the array's offset in the arena
+        if (bytes) memcpy(c.hStage.as<uint8_t>() + (static_cast<const uint8_t*>(dst) - c.up.as<uint8_t>()), src, bytes);
+      };
+      auto upv = [&](const auto* dst, const auto& vec) { up(dst, vec.data(), sizeof(vec[0]) * vec.size()); };
+      upv(u.ePose, hPose); upv(u.ePidx, hPidx); upv(u.ePt, hPt); upv(u.eLm, hLm); upv(u.eMeas, hMeas); upv(u.eInfo, hInfo);
+      upv(u.eRobust, hRobust); upv(u.ptStart, hPtStart); upv(u.poseStart, hPoseStart); upv(u.ptOf, ptOf);
+      upv(u.poseEdges, hPoseEdges); upv(u.poseOf, poseOf);
+      HIPCHK(hipMemcpyAsync(c.up.p, c.hStage.p, upBytes, hipMemcpyHostToDevice, s));
+      // the original information: the chi2 tests between and after the stages use it (k_cull)
+      HIPCHK(hipMemcpyAsync(w.eInfo0, u.eInfo, sizeof(double) * Ea, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemsetAsync(w.err, 0, sizeof(double) * 3 * Ea, s));   // an edge that is never evaluated (stop flag) has error 0
+    }
+    trace("optimize: uploads enqueued");
+    if (Z.nBuckets > 0) {
+      const int nBuckets = Z.nBuckets;
+      EdgeSoA Ed{u.ePose, u.ePidx, u.ePt, u.eMeas, u.eInfo, u.eRobust, Ea};
+      HIPCHK(hipMemsetAsync(w.pairCnt, 0, sizeof(int) * (nBuckets + 1), s));
+      hipLaunchKernelGGL(k_pair_count, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, w.pairCnt);
+      hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(256), 0, s, w.pairCnt, nBuckets, w.pairStart);
+      HIPCHK(hipMemcpyAsync(w.pairCursor, w.pairStart, sizeof(int) * (nBuckets + 1), hipMemcpyDeviceToDevice, s));
+      hipLaunchKernelGGL(k_pair_fill, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, w.pairCursor, w.pairA);
+      hipLaunchKernelGGL(k_pair_sort, dim3((nBuckets + 3) / 4), dim3(256), 0, s, w.pairStart, nBuckets, w.pairA, w.pairB);
     }
     HIPCHK(hipStreamSynchronize(s));   // the host staging vectors above die with this scope
-    Y.act.swap(act); Y.nL = nL; Y.nPf = nPf; Y.Ea = Ea; Y.n = n; Y.nb = nb; Y.nBlkE = nBlkE; Y.nBuckets = nBuckets;
+    Z.act.swap(act);
+    Y = std::move(Z);
     return YDORB_OK;
   };
   int rc;
@@ -262,9 +342,9 @@ int prepareStage(Run& R_, bool reuse) {
   // cleared the robust flags on the device)
   if (Y.Ea == 0) return YDORB_OK;
   // the two estimate buffers must agree on everything the update kernel does not write (fixed poses, points without edges)
-  HIPCHK(hipMemcpyAsync(c.poses[R_.cur ^ 1].p, c.poses[R_.cur].p, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(c.pts[R_.cur ^ 1].p, c.pts[R_.cur].p, sizeof(double) * 3 * NP, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemsetAsync(c.S.p, 0, sizeof(double) * ((size_t)Y.n * Y.n + Y.n), s));
+  HIPCHK(hipMemcpyAsync(c.st.poses[R_.cur ^ 1], c.st.poses[R_.cur], sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(c.st.pts[R_.cur ^ 1], c.st.pts[R_.cur], sizeof(double) * 3 * NP, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemsetAsync(c.w.S, 0, sizeof(double) * ((size_t)Y.n * Y.n + Y.n + (size_t)Y.nb * NB * NB), s));   // S | bs | diagInv (see WorkPtrs)
   return YDORB_OK;
 }
 
@@ -272,33 +352,30 @@ int prepareStage(Run& R_, bool reuse) {
 int optimize(Run& R_, int iterations, int stage, bool reuse) {
   int rc = prepareStage(R_, reuse);
   if (rc) return rc;
-  Ctx& c = *R_.c;
-  const YdBaProblem& P = *R_.P;
+  SolveMem& c = *R_.c;
   const YdBaOptions& O = *R_.O;
   hipStream_t s = c.stream;
-  Run::Sys& Y = R_.sys;
+  const Sys& Y = R_.sys;
   if (Y.Ea == 0) return YDORB_OK;
-  (void)P;
   const int nL = Y.nL, nPf = Y.nPf, Ea = Y.Ea, n = Y.n, nb = Y.nb, nBlkE = Y.nBlkE, nBuckets = Y.nBuckets;
-  // Hpp and bp are contiguous ([36 nPf | 6 nPf]) so one all-reduce covers both; bs follows S for the same reason
-  double* dHpp = c.Hpp.as<double>();
-  double* dbp = dHpp + (size_t)36 * nPf;
-  double* dS = c.S.as<double>();
-  double* dbs = dS + (size_t)n * n;
-  EdgeSoA Ed{c.ePose.as<int>(), c.ePidx.as<int>(), c.ePt.as<int>(), c.eMeas.as<double>(), c.eInfo.as<double>(), c.eRobust.as<uint8_t>(), Ea};
+  const UpPtrs& u = c.u;
+  const WorkPtrs& w = c.w;
+  double* const* poses = c.st.poses;
+  double* const* pts = c.st.pts;
+  double *dHpp = w.Hpp, *dbp = w.bp(Y), *dS = w.S, *dbs = w.bs(Y);
+  EdgeSoA Ed{u.ePose, u.ePidx, u.ePt, u.eMeas, u.eInfo, u.eRobust, Ea};
   const double dM = O.delta_mono, dSt = O.delta_stereo;
-  double* hscal = c.hPin;
-  int* hstatus = reinterpret_cast<int*>(c.hPin + 8);
+  double* hscal = R_.hPin;
+  int* hstatus = reinterpret_cast<int*>(R_.hPin + 8);
   const bool multi = O.world > 1 && O.allreduce;
 
   auto computeChi2 = [&](int buf, double* out, bool withStatus) -> int {
     PhaseTimer t(R_, PH_ERR);
-    hipLaunchKernelGGL(k_errors, dim3(nBlkE), dim3(256), 0, s, Ed, c.poses[buf].as<double>(), c.pts[buf].as<double>(), R_.cam, dM, dSt,
-                       c.err.as<double>(), c.partial.as<double>());
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c.partial.as<double>(), nBlkE, c.scal.as<double>(), 0, withStatus ? c.status.as<int>() : nullptr);
+    hipLaunchKernelGGL(k_errors, dim3(nBlkE), dim3(256), 0, s, Ed, poses[buf], pts[buf], R_.cam, dM, dSt, w.err, w.partial);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, w.partial, nBlkE, w.scal, 0, withStatus ? w.status : nullptr);
     t.stop();
-    if (multi) { int r2 = allreduce(R_, c.scal.p, 1, 0); if (r2) return r2; }
-    HIPCHK(hipMemcpyAsync(hscal, c.scal.p, sizeof(double) * 8, hipMemcpyDeviceToHost, s));
+    if (multi) { int r2 = allreduce(R_, w.scal, 1, 0); if (r2) return r2; }
+    HIPCHK(hipMemcpyAsync(hscal, w.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (withStatus) { hstatus[0] = (int)hscal[6]; hstatus[1] = (int)hscal[7]; }
     *out = hscal[0];
@@ -310,24 +387,22 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
   bool lastAccepted = true;
   for (int it = 0; it < iterations && !R_.stopped(); it++) {
     // computeActiveErrors + activeRobustChi2 at the top of an iteration: after the first iteration the state is the trial
-    // that was just accepted, whose errors (c.err) and chi2 are already there — same kernel, same inputs, same bits.
+    // that was just accepted, whose errors (err) and chi2 are already there — same kernel, same inputs, same bits.
     // A trial can also end rejected without terminating the loop (rho = NaN: `rho < 0` and `rho == 0` are both false); then err
     // and chi2 belong to the rejected state and are recomputed on the kept one, as g2o does at the top of every iteration.
     if ((it == 0 || !lastAccepted) && (rc = computeChi2(R_.cur, &currentChi, false))) return rc;
     {  // buildSystem
       PhaseTimer t(R_, PH_BUILD);
-      hipLaunchKernelGGL(k_build_points, dim3((nL + 127) / 128), dim3(128), 0, s, Ed, c.ptStart.as<int>(), nL, c.poses[R_.cur].as<double>(),
-                         c.pts[R_.cur].as<double>(), R_.cam, dM, dSt, c.err.as<double>(), c.Hll.as<double>(), c.bl.as<double>(), c.Hpl.as<double>());
+      hipLaunchKernelGGL(k_build_points, dim3((nL + 127) / 128), dim3(128), 0, s, Ed, u.ptStart, nL, poses[R_.cur], pts[R_.cur], R_.cam, dM, dSt, w.err, w.Hll, w.bl, w.Hpl);
       if (nPf)
-        hipLaunchKernelGGL(k_build_poses, dim3(nPf), dim3(256), 0, s, Ed, c.poseStart.as<int>(), c.poseEdges.as<int>(), c.poses[R_.cur].as<double>(),
-                           c.pts[R_.cur].as<double>(), R_.cam, dM, dSt, c.err.as<double>(), dHpp, dbp);
+        hipLaunchKernelGGL(k_build_poses, dim3(nPf), dim3(256), 0, s, Ed, u.poseStart, u.poseEdges, poses[R_.cur], pts[R_.cur], R_.cam, dM, dSt, w.err, dHpp, dbp);
       t.stop();
       if (multi && nPf) { if ((rc = allreduce(R_, dHpp, (int64_t)42 * nPf, 0))) return rc; }
     }
     if (it == 0) {  // computeLambdaInit
-      hipLaunchKernelGGL(k_max_diag, dim3(1), dim3(256), 0, s, dHpp, nPf, c.Hll.as<double>(), nL, c.scal.as<double>(), 1);
-      if (multi) { if ((rc = allreduce(R_, c.scal.as<double>() + 1, 1, 1))) return rc; }
-      HIPCHK(hipMemcpyAsync(hscal, c.scal.p, sizeof(double) * 8, hipMemcpyDeviceToHost, s));
+      hipLaunchKernelGGL(k_max_diag, dim3(1), dim3(256), 0, s, dHpp, nPf, w.Hll, nL, w.scal, 1);
+      if (multi) { if ((rc = allreduce(R_, w.scal + 1, 1, 1))) return rc; }
+      HIPCHK(hipMemcpyAsync(hscal, w.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       lambda = 1e-5 * hscal[1];
       ni = 2;
@@ -339,13 +414,11 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
       {
         PhaseTimer t(R_, PH_SCHUR);
         const double contrib = (!multi || O.rank == 0) ? 1.0 : 0.0;
-        hipLaunchKernelGGL(k_dinv, dim3((nL + 255) / 256), dim3(256), 0, s, c.Hll.as<double>(), c.bl.as<double>(), nL, lambda, c.Dinv.as<double>(), c.db.as<double>(), c.status.as<int>());
-        hipLaunchKernelGGL(k_bd, dim3(nBlkE), dim3(256), 0, s, Ed, c.eLm.as<int>(), c.Hpl.as<double>(), c.Dinv.as<double>(), c.BD.as<double>());
+        hipLaunchKernelGGL(k_dinv, dim3((nL + 255) / 256), dim3(256), 0, s, w.Hll, w.bl, nL, lambda, w.Dinv, w.db, w.status);
+        hipLaunchKernelGGL(k_bd, dim3(nBlkE), dim3(256), 0, s, Ed, u.eLm, w.Hpl, w.Dinv, w.BD);
         if (nPf)
-          hipLaunchKernelGGL(k_bs, dim3(nPf), dim3(256), 0, s, Ed, c.poseStart.as<int>(), c.poseEdges.as<int>(), c.eLm.as<int>(), c.Hpl.as<double>(),
-                             c.db.as<double>(), dbp, contrib, dbs);
-        hipLaunchKernelGGL(k_schur_pairs, dim3(nBuckets + 1), dim3(64 * kSchurWaves), 0, s, c.pairStart.as<int>(), c.pairB.as<int2>(), nPf, nBuckets,
-                           c.BD.as<double>(), c.Hpl.as<double>(), dHpp, lambda, contrib, n, dS, dbs);
+          hipLaunchKernelGGL(k_bs, dim3(nPf), dim3(256), 0, s, Ed, u.poseStart, u.poseEdges, u.eLm, w.Hpl, w.db, dbp, contrib, dbs);
+        hipLaunchKernelGGL(k_schur_pairs, dim3(nBuckets + 1), dim3(64 * kSchurWaves), 0, s, w.pairStart, w.pairB, nPf, nBuckets, w.BD, w.Hpl, dHpp, lambda, contrib, n, dS, dbs);
         t.stop();
       }
       if (multi) {  // sum of the per-rank landmark contributions (+ rank 0's Hpp, lambda, bp)
@@ -354,32 +427,27 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
       {
         PhaseTimer t(R_, PH_SOLVE);
         for (int kb = 0; kb < nb; kb++)
-          hipLaunchKernelGGL(k_chol_step, dim3((nb - kb) * (nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, s, dS, c.diagL.as<double>(), c.diagInv.as<double>(), n, kb,
-                             c.status.as<int>(), dbs, c.yv.as<double>());
-        if (!launch_chol_solve(s, dS, c.diagInv.as<double>(), n, c.yv.as<double>(), dbs, c.xp.as<double>())) {
+          hipLaunchKernelGGL(k_chol_step, dim3((nb - kb) * (nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, s, dS, w.diagL, w.diagInv, n, kb, w.status, dbs, w.yv);
+        if (!launch_chol_solve(s, dS, w.diagInv, n, w.yv, dbs, w.xp)) {
           set_error("reduced camera system of %d rows is wider than the solve kernel's LDS (max %d)", n, kCholSolveMaxN);
           return YDORB_ERR_UNSUPPORTED;
         }
-        hipLaunchKernelGGL(k_backsub, dim3((nL + 127) / 128), dim3(128), 0, s, Ed, c.ptStart.as<int>(), nL, c.Hpl.as<double>(), c.Dinv.as<double>(),
-                           c.bl.as<double>(), c.xp.as<double>(), c.xl.as<double>());
+        hipLaunchKernelGGL(k_backsub, dim3((nL + 127) / 128), dim3(128), 0, s, Ed, u.ptStart, nL, w.Hpl, w.Dinv, w.bl, w.xp, w.xl);
         t.stop();
         HIPCHK(hipGetLastError());
       }
       {
         PhaseTimer t(R_, PH_UPDATE);
-        hipLaunchKernelGGL(k_update, dim3((std::max(nPf, nL) + 255) / 256), dim3(256), 0, s, c.poses[R_.cur].as<double>(), c.pts[R_.cur].as<double>(),
-                           c.poses[nxt].as<double>(), c.pts[nxt].as<double>(), c.poseOf.as<int>(), nPf, c.ptOf.as<int>(), nL, c.xp.as<double>(),
-                           c.xl.as<double>());
+        hipLaunchKernelGGL(k_update, dim3((std::max(nPf, nL) + 255) / 256), dim3(256), 0, s, poses[R_.cur], pts[R_.cur], poses[nxt], pts[nxt], u.poseOf, nPf, u.ptOf, nL, w.xp, w.xl);
         // computeScale: pose part once (rank 0), landmark part per rank
         {
           const int np6 = (!multi || O.rank == 0) ? 6 * nPf : 0;
           const int nb2 = (np6 + 3 * nL + 255) / 256;
-          hipLaunchKernelGGL(k_scale, dim3(nb2), dim3(256), 0, s, c.xp.as<double>(), dbp, np6, c.xl.as<double>(), c.bl.as<double>(), 3 * nL, lambda,
-                             c.partial.as<double>() + nBlkE);
-          hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c.partial.as<double>() + nBlkE, nb2, c.scal.as<double>(), 2, nullptr);
+          hipLaunchKernelGGL(k_scale, dim3(nb2), dim3(256), 0, s, w.xp, dbp, np6, w.xl, w.bl, 3 * nL, lambda, w.partial + nBlkE);
+          hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, w.partial + nBlkE, nb2, w.scal, 2, nullptr);
         }
         t.stop();
-        if (multi) { if ((rc = allreduce(R_, c.scal.as<double>() + 2, 1, 0))) return rc; }
+        if (multi) { if ((rc = allreduce(R_, w.scal + 2, 1, 0))) return rc; }
       }
       double tempChi;
       if ((rc = computeChi2(nxt, &tempChi, true))) return rc;  // also brings back scal[2], the factorisation status, and leaves err = errors of the trial state
@@ -403,8 +471,6 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
   trace("optimize: errors read back");
   return YDORB_OK;
 }
-
-
 
 // validation shared by the single and the batched entry points; fills *Oout with the effective options
 int checkProblem(const YdBaProblem* P, const YdBaOptions* optIn, YdBaResult* res, YdBaOptions* Oout) {
@@ -432,7 +498,7 @@ int checkProblem(const YdBaProblem* P, const YdBaOptions* optIn, YdBaResult* res
 
 // state upload at the start of a solve (the vertices g2o is handed at optimizer.cpp:185-230)
 int beginSolve(Run& R_) {
-  Ctx& c = *R_.c;
+  SolveMem& c = *R_.c;
   const YdBaProblem* P = R_.P;
   const YdBaOptions& O = *R_.O;
   const int K = P->n_poses, NP = P->n_points;
@@ -440,8 +506,8 @@ int beginSolve(Run& R_) {
   R_.noRobust = (O.flags & YDORB_BA_NO_ROBUST) != 0;
   R_.phaseTimes = (O.flags & YDORB_BA_PHASE_TIMES) != 0;
   R_.cam = Cam{P->fx, P->fy, P->cx, P->cy, P->bf};
-  for (int i = 0; i < 2; i++)
-    if ((rc = c.poses[i].ensure(sizeof(double) * 7 * K)) || (rc = c.pts[i].ensure(sizeof(double) * 3 * NP))) return rc;
+  if ((rc = c.state.ensure(layState(K, NP, nullptr, c.st)))) return rc;
+  layState(K, NP, c.state.p, c.st);
   {  // SE3Quat's 7-vector constructor normalises the rotation (se3quat.h:80-86)
     std::vector<double> hp(P->poses, P->poses + (size_t)7 * K);
     for (int k = 0; k < K; k++) {
@@ -450,21 +516,20 @@ int beginSolve(Run& R_) {
       const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
       for (int d = 0; d < 4; d++) q[d] /= nrm;
     }
-    HIPCHK(hipMemcpyAsync(c.poses[0].p, hp.data(), sizeof(double) * 7 * K, hipMemcpyHostToDevice, c.stream));
+    HIPCHK(hipMemcpyAsync(c.st.poses[0], hp.data(), sizeof(double) * 7 * K, hipMemcpyHostToDevice, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));   // hp dies here
   }
-  HIPCHK(hipMemcpyAsync(c.pts[0].p, P->points, sizeof(double) * 3 * NP, hipMemcpyHostToDevice, c.stream));
+  HIPCHK(hipMemcpyAsync(c.st.pts[0], P->points, sizeof(double) * 3 * NP, hipMemcpyHostToDevice, c.stream));
   return YDORB_OK;
 }
 
 int launchCull(Run& R_, int final) {
-  Ctx& c = *R_.c;
+  SolveMem& c = *R_.c;
   const YdBaOptions& O = *R_.O;
   const int Ea = R_.sys.Ea;
   if (Ea == 0) return YDORB_OK;
-  hipLaunchKernelGGL(k_cull, dim3((Ea + 255) / 256), dim3(256), 0, c.stream, c.ePose.as<int>(), c.ePt.as<int>(), c.eMeas.as<double>(), Ea, c.eInfo0.as<double>(),
-                     c.err.as<double>(), c.poses[R_.cur].as<double>(), c.pts[R_.cur].as<double>(), O.chi2_mono, O.chi2_stereo, final, c.eInfo.as<double>(),
-                     c.eRobust.as<uint8_t>(), c.eOutlier.as<uint8_t>());
+  hipLaunchKernelGGL(k_cull, dim3((Ea + 255) / 256), dim3(256), 0, c.stream, c.u.ePose, c.u.ePt, c.u.eMeas, Ea, c.w.eInfo0, c.w.err,
+                     c.st.poses[R_.cur], c.st.pts[R_.cur], O.chi2_mono, O.chi2_stereo, final, c.u.eInfo, c.u.eRobust, c.w.eOutlier);
   HIPCHK(hipGetLastError());
   return YDORB_OK;
 }
@@ -474,9 +539,9 @@ int cullAfterFirstStage(Run& R_) { return launchCull(R_, 0); }
 
 // optimizer.cpp:315-351 up to the write-back: the final outlier list and the estimates
 int endSolve(Run& R_) {
-  Ctx& c = *R_.c;
+  SolveMem& c = *R_.c;
   const YdBaProblem* P = R_.P;
-  const Run::Sys& Y = R_.sys;
+  const Sys& Y = R_.sys;
   int rc = launchCull(R_, 1);
   if (rc) return rc;
   uint8_t* outlier = R_.res->edge_outlier;
@@ -484,9 +549,9 @@ int endSolve(Run& R_) {
   const size_t bPoses = sizeof(double) * 7 * P->n_poses, bPts = sizeof(double) * 3 * P->n_points, oPts = (bPoses + 255) & ~(size_t)255,
                oOut = oPts + ((bPts + 255) & ~(size_t)255);
   if ((rc = c.stage(oOut + Y.Ea))) return rc;
-  if (outlier && Y.Ea) HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>() + oOut, c.eOutlier.p, Y.Ea, hipMemcpyDeviceToHost, c.stream));
-  HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>(), c.poses[R_.cur].p, bPoses, hipMemcpyDeviceToHost, c.stream));
-  HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>() + oPts, c.pts[R_.cur].p, bPts, hipMemcpyDeviceToHost, c.stream));
+  if (outlier && Y.Ea) HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>() + oOut, c.w.eOutlier, Y.Ea, hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>(), c.st.poses[R_.cur], bPoses, hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(hipMemcpyAsync(c.hStage.as<uint8_t>() + oPts, c.st.pts[R_.cur], bPts, hipMemcpyDeviceToHost, c.stream));
   HIPCHK(hipStreamSynchronize(c.stream));
   memcpy(P->poses, c.hStage.as<uint8_t>(), bPoses);
   memcpy(P->points, c.hStage.as<uint8_t>() + oPts, bPts);
@@ -503,7 +568,7 @@ int endSolve(Run& R_) {
 // that is done with a stage goes through the same cull / second stage / read-back steps as a single solve while the others go on.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct Job {
-  Ctx ctx;                 // its own buffers; ctx.stream is the batch's stream (not owned)
+  SolveMem mem;            // its own arenas; mem.stream is a set-up stream or the batch's (not owned)
   YdBaOptions O;
   Run* run = nullptr;
   int stage = 1, it = 0, iterations = 0, qmax = 0;
@@ -519,27 +584,27 @@ struct BatchPool {   // per device: contexts, stream and staging of the lock-ste
   hipStream_t stream = nullptr;
   std::vector<Job*> jobs;          // grown on demand; buffers are kept between calls
   std::vector<hipStream_t> setupStreams;
-  DBuf dDev, dScal;                // BaDev[B]; per problem 8 doubles (chi2, max diag, scale sum, ..., status copies) + 2 ints of status
-  BaDev* hDev = nullptr;           // pinned
-  double* hScal = nullptr;         // pinned
-  int cap = 0;
+  Mem dDev, dScal;                 // BaDev[B]; per problem 8 doubles (chi2, max diag, scale sum, ..., status copies) + 2 ints of status
+  PinnedMem hDev, hScal;           // BaDev[B] as the host writes it before every round; the read-back of dScal's doubles
 };
 BatchPool g_batch[16];
 constexpr int kSetupThreads = 16;  // host threads of a batch's set-up phase
 constexpr int kBatchGroup = 64;    // problems per lock-step group (C5-sized problems take ~40 MB each)
 
 void fillDev(Job& J, BaDev& D, const BaDev* dDevBase, double* dScal, int* dStatus) {
-  Ctx& c = J.ctx;
-  const Run::Sys& Y = J.run->sys;
+  const UpPtrs& u = J.mem.u;
+  const WorkPtrs& w = J.mem.w;
+  const StatePtrs& st = J.mem.st;
+  const Sys& Y = J.run->sys;
   memset(&D, 0, sizeof(D));
   auto off = [&](const void* p) { return (long long)(reinterpret_cast<const char*>(p) - reinterpret_cast<const char*>(dDevBase)); };   // see BaDev
-  D.ePose = off(c.ePose.p); D.ePidx = off(c.ePidx.p); D.ePt = off(c.ePt.p); D.eMeas = off(c.eMeas.p); D.eInfo = off(c.eInfo.p); D.eRobust = off(c.eRobust.p);
-  D.ptStart = off(c.ptStart.p); D.poseStart = off(c.poseStart.p); D.poseEdges = off(c.poseEdges.p); D.eLm = off(c.eLm.p);
-  D.poseOf = off(c.poseOf.p); D.ptOf = off(c.ptOf.p); D.pairStart = off(c.pairStart.p); D.pairItems = off(c.pairB.p);
-  for (int i = 0; i < 2; i++) { D.poses[i] = off(c.poses[i].p); D.pts[i] = off(c.pts[i].p); }
-  D.err = off(c.err.p); D.partial = off(c.partial.p); D.Hll = off(c.Hll.p); D.bl = off(c.bl.p); D.Hpl = off(c.Hpl.p);
-  D.BD = off(c.BD.p); D.Hpp = off(c.Hpp.p); D.S = off(c.S.p); D.diagL = off(c.diagL.p); D.diagInv = off(c.diagInv.p);
-  D.Dinv = off(c.Dinv.p); D.db = off(c.db.p); D.xp = off(c.xp.p); D.yv = off(c.yv.p); D.xl = off(c.xl.p);
+  D.ePose = off(u.ePose); D.ePidx = off(u.ePidx); D.ePt = off(u.ePt); D.eMeas = off(u.eMeas); D.eInfo = off(u.eInfo); D.eRobust = off(u.eRobust);
+  D.ptStart = off(u.ptStart); D.poseStart = off(u.poseStart); D.poseEdges = off(u.poseEdges); D.eLm = off(u.eLm);
+  D.poseOf = off(u.poseOf); D.ptOf = off(u.ptOf); D.pairStart = off(w.pairStart); D.pairItems = off(w.pairB);
+  for (int i = 0; i < 2; i++) { D.poses[i] = off(st.poses[i]); D.pts[i] = off(st.pts[i]); }
+  D.err = off(w.err); D.partial = off(w.partial); D.Hll = off(w.Hll); D.bl = off(w.bl); D.Hpl = off(w.Hpl);
+  D.BD = off(w.BD); D.Hpp = off(w.Hpp); D.S = off(w.S); D.diagL = off(w.diagL); D.diagInv = off(w.diagInv);
+  D.Dinv = off(w.Dinv); D.db = off(w.db); D.xp = off(w.xp); D.yv = off(w.yv); D.xl = off(w.xl);
   D.scal = off(dScal); D.status = off(dStatus);
   D.cam = J.run->cam; D.dM = J.O.delta_mono; D.dSt = J.O.delta_stereo;
   D.nL = Y.nL; D.nPf = Y.nPf; D.Ea = Y.Ea; D.n = Y.n; D.nb = Y.nb; D.nBlkE = Y.nBlkE; D.nBuckets = Y.nBuckets;
@@ -549,6 +614,8 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
   hipStream_t s = B.stream;
   int rc;
   if ((rc = B.dDev.ensure(sizeof(BaDev) * n)) || (rc = B.dScal.ensure((sizeof(double) * 8 + sizeof(int) * 2) * n))) return rc;
+  BaDev* hDev = B.hDev.as<BaDev>();
+  double* hScal = B.hScal.as<double>();
   double* dScalAll = B.dScal.as<double>();
   int* dStatusAll = reinterpret_cast<int*>(dScalAll + (size_t)8 * n);
   std::vector<Job*> J(B.jobs.begin(), B.jobs.begin() + n);
@@ -564,7 +631,7 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
     if (r) { fail(j, r); return; }
     if (X.run->sys.Ea == 0) { endStage(j); return; }
     if (X.run->sys.n > kCholSolveMaxN) { set_error("reduced camera system of %d rows is wider than the solve kernel's LDS (max %d)", X.run->sys.n, kCholSolveMaxN); fail(j, YDORB_ERR_UNSUPPORTED); return; }
-    fillDev(X, B.hDev[j], B.dDev.as<BaDev>(), dScalAll + (size_t)8 * j, dStatusAll + (size_t)2 * j);
+    fillDev(X, hDev[j], B.dDev.as<BaDev>(), dScalAll + (size_t)8 * j, dStatusAll + (size_t)2 * j);
     if (!(X.it < X.iterations && !X.run->stopped())) { endStage(j); return; }   // `for (it = 0; it < iterations && !terminate(); ...)`
     X.needBuild = true;
   };
@@ -625,8 +692,8 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
         if (!r) {
           if (P->stop && *P->stop) { res[j].stopped = 1; X.done = true; continue; }
           if (P->n_edges == 0 || P->n_poses == 0 || P->n_points == 0) { X.done = true; continue; }
-          X.ctx.device = Oin.device; X.ctx.stream = st;
-          X.run = new Run{&X.ctx, P, &X.O, &res[j]};
+          X.mem.device = Oin.device; X.mem.stream = st;
+          X.run = new Run{&X.mem, P, &X.O, &res[j]};
           r = beginSolve(*X.run);
         }
         if (!r) {
@@ -635,7 +702,7 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
         }
         if (r) { X.errText = ydorb_last_error(); fail(j, r); }
         if (hipStreamSynchronize(st) != hipSuccess && !r) { X.errText = "hipStreamSynchronize failed"; fail(j, YDORB_ERR_HIP); }
-        X.ctx.stream = s;
+        X.mem.stream = s;
       }
     };
     std::vector<std::thread> pool;
@@ -657,7 +724,7 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
     bool anyBuild = false, anyChi = false, anyDiag = false;
     for (int j = 0; j < n; j++) {
       Job& X = *J[j];
-      BaDev& D = B.hDev[j];
+      BaDev& D = hDev[j];
       D.trial = 0;
       D.build = !X.done && X.needBuild;
       D.chi2 = D.build && (X.it == 0 || !X.lastAccepted);
@@ -666,14 +733,14 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
       D.lambda = X.lambda;
       anyBuild = anyBuild || D.build; anyChi = anyChi || D.chi2; anyDiag = anyDiag || D.maxdiag;
     }
-    const int gE = maxOver([](const Run::Sys& Y) { return Y.nBlkE; }), gL128 = maxOver([](const Run::Sys& Y) { return (Y.nL + 127) / 128; }),
-              gL256 = maxOver([](const Run::Sys& Y) { return (Y.nL + 255) / 256; }), gP = maxOver([](const Run::Sys& Y) { return Y.nPf; }),
-              gBk = maxOver([](const Run::Sys& Y) { return Y.nBuckets + 1; }), gNb = maxOver([](const Run::Sys& Y) { return Y.nb; }),
-              gUpd = maxOver([](const Run::Sys& Y) { return (std::max(Y.nPf, Y.nL) + 255) / 256; }),
-              gScale = maxOver([](const Run::Sys& Y) { return (6 * Y.nPf + 3 * Y.nL + 255) / 256; }), gN = maxOver([](const Run::Sys& Y) { return Y.n; });
+    const int gE = maxOver([](const Sys& Y) { return Y.nBlkE; }), gL128 = maxOver([](const Sys& Y) { return (Y.nL + 127) / 128; }),
+              gL256 = maxOver([](const Sys& Y) { return (Y.nL + 255) / 256; }), gP = maxOver([](const Sys& Y) { return Y.nPf; }),
+              gBk = maxOver([](const Sys& Y) { return Y.nBuckets + 1; }), gNb = maxOver([](const Sys& Y) { return Y.nb; }),
+              gUpd = maxOver([](const Sys& Y) { return (std::max(Y.nPf, Y.nL) + 255) / 256; }),
+              gScale = maxOver([](const Sys& Y) { return (6 * Y.nPf + 3 * Y.nL + 255) / 256; }), gN = maxOver([](const Sys& Y) { return Y.n; });
     const BaDev* dDev = B.dDev.as<BaDev>();
     if (anyBuild) {
-      HIPCHK(hipMemcpyAsync(B.dDev.p, B.hDev, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(B.dDev.p, hDev, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
       if (anyChi) {
         hipLaunchKernelGGL(kb_errors, dim3(gE, 1, n), dim3(256), 0, s, dDev, 0);
         hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 0);
@@ -683,28 +750,28 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
       if (anyDiag) hipLaunchKernelGGL(kb_max_diag, dim3(1, 1, n), dim3(256), 0, s, dDev);
       HIPCHK(hipGetLastError());
       if (anyChi || anyDiag) {
-        HIPCHK(hipMemcpyAsync(B.hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
       }
       for (int j = 0; j < n; j++) {
         Job& X = *J[j];
-        const BaDev& D = B.hDev[j];
+        const BaDev& D = hDev[j];
         if (!D.build) continue;
-        if (D.chi2) X.currentChi = B.hScal[8 * j + 0];
-        if (D.maxdiag) { X.lambda = 1e-5 * B.hScal[8 * j + 1]; X.ni = 2; }   // computeLambdaInit
+        if (D.chi2) X.currentChi = hScal[8 * j + 0];
+        if (D.maxdiag) { X.lambda = 1e-5 * hScal[8 * j + 1]; X.ni = 2; }   // computeLambdaInit
         X.needBuild = false;
       }
     }
     // (b) one LM trial of every unfinished problem ----------------------------------------------------------------------------------
     for (int j = 0; j < n; j++) {
       Job& X = *J[j];
-      BaDev& D = B.hDev[j];
+      BaDev& D = hDev[j];
       D.build = D.chi2 = D.maxdiag = 0;
       D.trial = !X.done;
       D.lambda = X.lambda;
       D.cur = X.done ? 0 : X.run->cur;
     }
-    HIPCHK(hipMemcpyAsync(B.dDev.p, B.hDev, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(B.dDev.p, hDev, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(kb_dinv, dim3(gL256, 1, n), dim3(256), 0, s, dDev);
     hipLaunchKernelGGL(kb_bd, dim3(gE, 1, n), dim3(256), 0, s, dDev);
     if (gP) hipLaunchKernelGGL(kb_bs, dim3(gP, 1, n), dim3(256), 0, s, dDev);
@@ -724,14 +791,14 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
     hipLaunchKernelGGL(kb_errors, dim3(gE, 1, n), dim3(256), 0, s, dDev, 1);
     hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 1);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(B.hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     trace("batch: round synchronised");
     // (c) the LM decision of every problem (optimization_algorithm_levenberg.cpp:95-146, as in optimize()) -----------------------------------
     for (int j = 0; j < n; j++) {
       Job& X = *J[j];
       if (X.done) continue;
-      const double* hs = B.hScal + (size_t)8 * j;
+      const double* hs = hScal + (size_t)8 * j;
       const double tempChi = hs[0], scaleSum = hs[2];
       X.lastAccepted = lm_judge(X.lambda, X.ni, X.currentChi, X.rho, tempChi, scaleSum + 1e-3, (int)hs[6] == 0);
       if (X.lastAccepted) X.run->cur ^= 1;  // discardTop(): keep the updated estimate; else pop(): the previous one is still in poses[cur]
@@ -765,9 +832,9 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
         Job& X = *J[j];
         if (!X.pendingEnd) continue;
         X.pendingEnd = false;
-        X.ctx.stream = B.setupStreams[t];
+        X.mem.stream = B.setupStreams[t];
         const int r = endSolve(*X.run);
-        X.ctx.stream = s;
+        X.mem.stream = s;
         if (r) { X.errText = ydorb_last_error(); fail(j, r); }
       }
     };
@@ -809,26 +876,16 @@ int ydorb_ba_solve(const YdBaProblem* P, const YdBaOptions* optIn, YdBaResult* r
   if ((rc = require_device(O.device))) return rc;
   g_t0 = std::chrono::steady_clock::now();
   trace("solve: begin");
-  int slot = -1;
-  {
-    std::lock_guard<std::mutex> pick(g_pick);
-    for (int i = 0; i < kCtxPool && slot < 0; i++)
-      if (g_mu[O.device][i].try_lock()) slot = i;
-  }
-  if (slot < 0) { slot = 0; g_mu[O.device][0].lock(); }   // all busy: queue behind slot 0
-  std::lock_guard<std::mutex> lock(g_mu[O.device][slot], std::adopt_lock);
-  Ctx& c = g_ctx[O.device][slot];
-  if (!c.stream) {
-    c.device = O.device;
-    HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    for (auto& e : c.ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipHostMalloc(&c.hPin, sizeof(double) * 16));
-  }
-  Run R_{&c, P, &O, res};
+  std::unique_lock<std::mutex> lock;
+  Ctx* ctx = acquireCtx(O.device, lock);
+  if (!ctx) return YDORB_ERR_HIP;
+  Ctx& c = *ctx;
+  Run R_{&c.mem, P, &O, res};
+  R_.ev = c.ev; R_.hPin = c.hPin.as<double>();
   if ((rc = beginSolve(R_))) return rc;
   trace("solve: state uploaded");
   hipEvent_t t0 = c.ev[2 * PH_COUNT], t1 = c.ev[2 * PH_COUNT + 1];
-  HIPCHK(hipEventRecord(t0, c.stream));
+  HIPCHK(hipEventRecord(t0, c.mem.stream));
 
   if ((rc = optimize(R_, O.iters1, 1, false))) return rc;
   if (O.flags & YDORB_BA_SINGLE_STAGE) {
@@ -840,7 +897,7 @@ int ydorb_ba_solve(const YdBaProblem* P, const YdBaOptions* optIn, YdBaResult* r
   } else {
     res->stopped = 1;
   }
-  HIPCHK(hipEventRecord(t1, c.stream));
+  HIPCHK(hipEventRecord(t1, c.mem.stream));
   if ((rc = endSolve(R_))) return rc;
   (void)hipEventElapsedTime(&res->ms_total, t0, t1);
   trace("solve: results read back");
@@ -863,50 +920,33 @@ int ydorb_pose_optimize(const YdPoseBatch* B, uint8_t* outlier, int32_t* n_inlie
   if (E > 0 && (!B->points || !B->meas || !B->inv_sigma2 || !outlier)) { set_error("null edge arrays"); return YDORB_ERR_INVALID_ARG; }
   int rc = require_device(B->device);
   if (rc) return rc;
-  int slot = -1;
-  {
-    std::lock_guard<std::mutex> pick(g_pick);
-    for (int i = 0; i < kCtxPool && slot < 0; i++)
-      if (g_mu[B->device][i].try_lock()) slot = i;
-  }
-  if (slot < 0) { slot = 0; g_mu[B->device][0].lock(); }
-  std::lock_guard<std::mutex> lock(g_mu[B->device][slot], std::adopt_lock);
-  Ctx& c = g_ctx[B->device][slot];
-  if (!c.stream) {
-    c.device = B->device;
-    HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    for (auto& e : c.ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipHostMalloc(&c.hPin, sizeof(double) * 16));
-  }
-  hipStream_t s = c.stream;
+  std::unique_lock<std::mutex> lock;
+  Ctx* c = acquireCtx(B->device, lock);
+  if (!c) return YDORB_ERR_HIP;
+  hipStream_t s = c->mem.stream;
   const size_t Ez = (size_t)std::max(E, 1);
-  if ((rc = c.pStart.ensure(sizeof(int) * (n + 1))) || (rc = c.pPoses.ensure(sizeof(double) * 7 * n)) || (rc = c.pX.ensure(sizeof(double) * 3 * Ez)) ||
-      (rc = c.pMeas.ensure(sizeof(double) * 3 * Ez)) || (rc = c.pInfo.ensure(sizeof(double) * Ez)) || (rc = c.pErr.ensure(sizeof(double) * 3 * Ez)) ||
-      (rc = c.pFlags.ensure(Ez)) || (rc = c.pOutlier.ensure(Ez)) || (rc = c.pInl.ensure(sizeof(int) * n)) || (rc = c.pChi.ensure(sizeof(double) * 4 * n)) ||
-      (rc = c.pTrials.ensure(sizeof(int) * n)))
-    return rc;
-  HIPCHK(hipMemcpyAsync(c.pStart.p, B->edge_start, sizeof(int) * (n + 1), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(c.pPoses.p, B->poses, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+  PosePtrs q;
+  if ((rc = c->pose.ensure(layPose(n, Ez, nullptr, q)))) return rc;
+  layPose(n, Ez, c->pose.p, q);
+  HIPCHK(hipMemcpyAsync(q.start, B->edge_start, sizeof(int) * (n + 1), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(q.poses, B->poses, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
   if (E) {
-    HIPCHK(hipMemcpyAsync(c.pX.p, B->points, sizeof(double) * 3 * E, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c.pMeas.p, B->meas, sizeof(double) * 3 * E, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c.pInfo.p, B->inv_sigma2, sizeof(double) * E, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(q.X, B->points, sizeof(double) * 3 * E, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(q.meas, B->meas, sizeof(double) * 3 * E, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(q.info, B->inv_sigma2, sizeof(double) * E, hipMemcpyHostToDevice, s));
   }
   const Cam cam{B->fx, B->fy, B->cx, B->cy, B->bf};
   const double dM = (double)(float)sqrt(5.991), dS = (double)(float)sqrt(7.815);   // optimizer.cpp:381-382
-  hipLaunchKernelGGL(k_pose_optimize, dim3(n), dim3(kPoseThreads), 0, s, n, c.pStart.as<int>(), c.pPoses.as<double>(), c.pX.as<double>(),
-                     c.pMeas.as<double>(), c.pInfo.as<double>(), cam, dM, dS, c.pErr.as<double>(), c.pFlags.as<uint8_t>(),
-                     c.pOutlier.as<uint8_t>(), c.pInl.as<int>(), c.pChi.as<double>(), c.pTrials.as<int>());
+  hipLaunchKernelGGL(k_pose_optimize, dim3(n), dim3(kPoseThreads), 0, s, n, q.start, q.poses, q.X, q.meas, q.info, cam, dM, dS, q.err, q.flags, q.outlier, q.inl, q.chi, q.trials);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(B->poses, c.pPoses.p, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(n_inliers, c.pInl.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
-  if (E) HIPCHK(hipMemcpyAsync(outlier, c.pOutlier.p, E, hipMemcpyDeviceToHost, s));
-  if (chi2_log) HIPCHK(hipMemcpyAsync(chi2_log, c.pChi.p, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, s));
-  if (trials) HIPCHK(hipMemcpyAsync(trials, c.pTrials.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(B->poses, q.poses, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(n_inliers, q.inl, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+  if (E) HIPCHK(hipMemcpyAsync(outlier, q.outlier, E, hipMemcpyDeviceToHost, s));
+  if (chi2_log) HIPCHK(hipMemcpyAsync(chi2_log, q.chi, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, s));
+  if (trials) HIPCHK(hipMemcpyAsync(trials, q.trials, sizeof(int) * n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return YDORB_OK;
 }
-
 
 int ydorb_ba_solve_batch(const YdBaProblem* probs, int32_t n, const YdBaOptions* opt, YdBaResult* res, int32_t threads, int32_t* rcEach) {
   if (n < 0 || (n > 0 && (!probs || !res))) { set_error("invalid argument"); return YDORB_ERR_INVALID_ARG; }
@@ -924,14 +964,7 @@ int ydorb_ba_solve_batch(const YdBaProblem* probs, int32_t n, const YdBaOptions*
   if (!B.stream) HIPCHK(hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking));
   // `threads` is the number of problems advanced together (0 = as many as fit one group); the lock-step batch needs no host threads
   const int group = std::max(1, std::min<int>(threads > 0 ? threads : kBatchGroup, kBatchGroup));
-  if (B.cap < group) {
-    if (B.hDev) (void)hipHostFree(B.hDev);
-    if (B.hScal) (void)hipHostFree(B.hScal);
-    B.hDev = nullptr; B.hScal = nullptr; B.cap = 0;
-    HIPCHK(hipHostMalloc(&B.hDev, sizeof(BaDev) * group));
-    HIPCHK(hipHostMalloc(&B.hScal, sizeof(double) * 8 * group));
-    B.cap = group;
-  }
+  if ((rc = B.hDev.ensure(sizeof(BaDev) * group)) || (rc = B.hScal.ensure(sizeof(double) * 8 * group))) return rc;
   while ((int)B.jobs.size() < group) B.jobs.push_back(new Job());
   int first = YDORB_OK;
   std::string firstText;
@@ -952,18 +985,15 @@ int ydorb_ba_release(int32_t device) {
   for (int i = 0; i < kCtxPool; i++) {          // waits for a solve that holds the context
     std::lock_guard<std::mutex> lock(g_mu[device][i]);
     Ctx& c = g_ctx[device][i];
-    if (c.stream) (void)hipStreamSynchronize(c.stream);
+    if (c.mem.stream) (void)hipStreamSynchronize(c.mem.stream);
     c.releaseBuffers();
   }
   BatchPool& B = g_batch[device];
   std::lock_guard<std::mutex> lock(B.mu);
   if (B.stream) (void)hipStreamSynchronize(B.stream);
-  for (Job* j : B.jobs) { j->ctx.releaseBuffers(); delete j; }
+  for (Job* j : B.jobs) { j->mem.releaseBuffers(); delete j; }
   B.jobs.clear();
-  B.dDev.release(); B.dScal.release();
-  if (B.hDev) (void)hipHostFree(B.hDev);
-  if (B.hScal) (void)hipHostFree(B.hScal);
-  B.hDev = nullptr; B.hScal = nullptr; B.cap = 0;
+  for (Mem* m : {&B.dDev, &B.dScal, static_cast<Mem*>(&B.hDev), static_cast<Mem*>(&B.hScal)}) m->release();
   return YDORB_OK;
 }
 
@@ -977,12 +1007,14 @@ int ydorb_ba_dense_solve(int32_t device, const double* A, int32_t n0, const doub
     for (int j = 0; j < n; j++) hA[(size_t)i * n + j] = (i < n0 && j < n0) ? A[(size_t)i * n0 + j] : (i == j ? 1.0 : 0.0);
     if (i < n0) hb[i] = b[i];
   }
-  ScopedMem mA, mD, mI, mb, mx, my, mst;   // exact sizes; freed on every return
-  if ((rc = mA.alloc(sizeof(double) * n * n)) || (rc = mD.alloc(sizeof(double) * nb * NB * NB)) || (rc = mI.alloc(sizeof(double) * nb * NB * NB)) ||
-      (rc = mb.alloc(sizeof(double) * n)) || (rc = mx.alloc(sizeof(double) * n)) || (rc = my.alloc(sizeof(double) * n)) || (rc = mst.alloc(sizeof(int) * 2)))
-    return rc;
-  double *dA = mA.as<double>(), *dD = mD.as<double>(), *dI = mI.as<double>(), *db = mb.as<double>(), *dx = mx.as<double>(), *dy = my.as<double>();
-  int* dst = mst.as<int>();
+  Layout L;
+  const size_t tiles = sizeof(double) * nb * NB * NB;
+  const size_t oA = L.add(sizeof(double) * n * n), oD = L.add(tiles), oI = L.add(tiles), ob = L.add(sizeof(double) * n), ox = L.add(sizeof(double) * n),
+               oy = L.add(sizeof(double) * n), ost = L.add(sizeof(int) * 2);
+  ScopedMem m;   // exact size; freed on every return
+  if ((rc = m.alloc(L.bytes))) return rc;
+  double *dA = m.at<double>(oA), *dD = m.at<double>(oD), *dI = m.at<double>(oI), *db = m.at<double>(ob), *dx = m.at<double>(ox), *dy = m.at<double>(oy);
+  int* dst = m.at<int>(ost);
   HIPCHK(hipMemcpy(dA, hA.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(db, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(dst, 0, sizeof(int) * 2));

@@ -24,6 +24,8 @@
 namespace ydorb {
 
 // Grow-only device buffer, or pinned host buffer when `host` is set; growing does not keep the contents.
+// A Mem always owns the allocation `p` points at.  A slice of a buffer is a typed pointer computed from a Layout offset, never a
+// second Mem: release / alloc / take on a Mem that pointed into another one would free an interior pointer.
 // No destructor, on purpose: the solvers keep their contexts in static arrays, and freeing during static destruction would call
 // into a HIP runtime that may already be gone.  Owners release() explicitly in their destroy / release entry points; a buffer
 // that lives in one function is a ScopedMem.
@@ -53,6 +55,10 @@ struct Mem {
   template <class T> T* at(size_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(p) + off); }
 };
 
+struct PinnedMem : Mem {   // pinned host memory: staging and read-back areas
+  PinnedMem() { host = true; }
+};
+
 struct ScopedMem : Mem {   // for function-local buffers only (see Mem)
   ScopedMem() = default;
   ScopedMem(const ScopedMem&) = delete;
@@ -62,10 +68,12 @@ struct ScopedMem : Mem {   // for function-local buffers only (see Mem)
 
 template <class T> T* at(Mem& m, size_t off) { return m.at<T>(off); }
 
-// Lays arrays out at 16-byte aligned offsets of one area: the same offsets address the pinned staging and the device copy.
+// Lays arrays out at aligned offsets of one area: the same offsets address the pinned staging and the device copy.  `align` is a
+// power of two, set before the first add(): 16 bytes serve any element type; BA asks for 256 so that every array of an arena
+// starts on the boundary a buffer of its own had (hipMalloc returns at least that).
 struct Layout {
-  size_t bytes = 0;
-  size_t add(size_t n) { const size_t at = bytes; bytes += (n + 15) & ~size_t(15); return at; }
+  size_t bytes = 0, align = 16;
+  size_t add(size_t n) { const size_t at = bytes; bytes += (n + align - 1) & ~(align - 1); return at; }
 };
 
 // Per-device scratch of a solver that stages a batch up and its results down, reused between calls.  Every solver keeps its own
@@ -73,8 +81,8 @@ struct Layout {
 struct StagedCtx {
   std::mutex mu;
   hipStream_t stream = nullptr;
-  Mem up, down, scratch, hUp, hDown;
-  StagedCtx() { hUp.host = true; hDown.host = true; }
+  Mem up, down, scratch;
+  PinnedMem hUp, hDown;
   int init(int device) {
     HIPCHK(hipSetDevice(device));
     if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
