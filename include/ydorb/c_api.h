@@ -613,6 +613,59 @@ int ydorb_kfdb_detect_loop(ydorb_kfdb_t* db, const int32_t* q_start, const int32
                            const int32_t* conn_start, const int32_t* conn_slots, const float* min_score, int32_t* cand, int32_t cand_cap,
                            int32_t* counts, int32_t* status, int32_t* diag_words, float* diag_score);
 
+/* ------------------------------------------------------------------------------------------
+ * LocalMapping::createNewMapPoints: the geometry between searchForTriangulation's match list and the new MapPoints (ORB-SLAM2
+ * LocalMapping::CreateNewMapPoints' inner loop, which YDORBSLAM renames): ray and stereo parallax, the 4x4 linear
+ * triangulation or the stereo unprojection, both depth tests, both reprojection chi-square tests and the scale-consistency test, one
+ * GPU lane per match.  A batch holds n_problems keyframe pairs over n_views shared views (one current keyframe meets 10-20
+ * neighbours); problem p pairs views first_view[p] / second_view[p] and owns the matches match_start[p] .. match_start[p+1] of idx1
+ * (keypoint of the first view) / idx2 (of the second).  Results are bit-identical to a CPU restatement compiled with
+ * -ffp-contract=off ("createNewMapPoints").
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdTriView {      /* one keyframe */
+  const YdKeyPoint* kps;        /* [n] m_v_keyPoints (x, y and octave are read) */
+  const float* right_x;         /* [n] m_v_rightXcords: >= 0 marks a stereo feature */
+  const float* depth;           /* [n] m_v_depth */
+  int32_t n;
+  float Tcw[12];                /* 3x4 row-major; Rwc = Rcw^T and Ow as the reference's getters return them: */
+  float Rwc[9], Ow[3];
+  float fx, fy, cx, cy, invfx, invfy, b, bf;
+  const float* level_sigma2;    /* [n_levels] m_v_scaleFactorSquares */
+  const float* scale_factors;   /* [n_levels] m_v_scaleFactors */
+  int32_t n_levels;
+} YdTriView;
+typedef struct YdTriBatch {
+  int32_t device, n_views, n_problems;
+  const YdTriView* views;
+  const int32_t* first_view; const int32_t* second_view;   /* [n_problems] */
+  const int32_t* match_start;                              /* [n_problems+1], match_start[0] = 0, non-decreasing */
+  const int32_t* idx1; const int32_t* idx2;                /* [match_start[n_problems]] */
+  const float* ratio_factor;                               /* [n_problems] = 1.5f * first view's scale factor */
+} YdTriBatch;
+/* status byte of a match.  Low nibble = where the reference's loop body left (0 = it reached the new MapPoint): */
+#define YDORB_TRI_ACCEPTED 0
+#define YDORB_TRI_NO_METHOD 1        /* neither the linear nor a stereo branch applies */
+#define YDORB_TRI_W_ZERO 2           /* homogeneous w == 0 */
+#define YDORB_TRI_DEPTH_FIRST 3      /* z1 <= 0 */
+#define YDORB_TRI_DEPTH_SECOND 4     /* z2 <= 0 */
+#define YDORB_TRI_REPROJ_FIRST 5
+#define YDORB_TRI_REPROJ_SECOND 6
+#define YDORB_TRI_ZERO_DISTANCE 7
+#define YDORB_TRI_SCALE_RATIO 8
+#define YDORB_TRI_BAD_STEREO_DEPTH 9 /* the stereo unprojection was chosen for a feature whose depth is not > 0 (undefined in the reference) */
+/* bits 4-5 = the source of x3d: */
+#define YDORB_TRI_SRC_LINEAR 1
+#define YDORB_TRI_SRC_UNPROJECT_FIRST 2
+#define YDORB_TRI_SRC_UNPROJECT_SECOND 3
+#define YDORB_TRI_NOT_FINITE 0x80    /* bit 7: a component of x3d is NaN or infinite (the reference's tests are all false on NaN: such a point is accepted) */
+/* x3d [M][3], status [M] with M = match_start[n_problems]; n_accepted [n_problems] or NULL.  x3d[m] is the triangulated / unprojected
+ * point whenever a source produced one, for rejected matches too, and 0 0 0 otherwise (exits 1, 2 and 9).  Null arrays, a view or a
+ * keypoint index out of range, an octave outside [0, n_levels) of a referenced keypoint and a malformed match_start return
+ * YDORB_ERR_INVALID_ARG before any device work. */
+int ydorb_triangulate_matches(const YdTriBatch* batch, float* x3d, uint8_t* status, int32_t* n_accepted);
+/* ydorb_triangulate_matches keeps device scratch per device between calls; this frees it (waiting for calls in flight). */
+int ydorb_triangulate_release(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

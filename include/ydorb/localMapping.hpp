@@ -1,0 +1,150 @@
+// Drop-in body of LocalMapping::createNewMapPoints (ORB-SLAM2 LocalMapping::CreateNewMapPoints, which YDORBSLAM renames; SURVEY 3.3,
+// DESIGN.md section 6f) on top of the ydorb C ABI.  A function template over the reference's own KeyFrame / MapPoint / Map / Frame
+// types (included by the translation unit that instantiates it), so the member function becomes a one-line forward:
+//   void LocalMapping::createNewMapPoints()
+//   { ydorb::adapter::createNewMapPointsImpl<Frame, std::shared_ptr<KeyFrame>, MapPoint>(ydorb::adapter::matcher(), m_sptr_currentKeyFrame,
+//       m_sptr_map, m_list_recentAddedMapPoints, [this] { return checkNewKeyFrames(); }); }
+// Per neighbour of getBestCovisibilityKeyFrames(10), in the reference's order: abortCheck() for i > 0, the baseline test, F12 on the host,
+// the searchForTriangulation adapter (GPU), ONE ydorb_triangulate_matches call for the neighbour's matches (GPU), then the reference's
+// bookkeeping for the accepted matches in match order.  The loop stays one call per neighbour on purpose: a point accepted with
+// neighbour i sets the current keyframe's map point at idx1 and so changes what searchForTriangulation may match with neighbour i + 1.
+// Assumed spellings, as in the other adapters: m_v_keyPoints, m_v_rightXcords, m_v_depth, m_v_scaleFactors, m_v_scaleFactorSquares,
+// getRotation_c2w / getTranslation_c2w / getCameraOriginInWorld, FrameT::m_flt_fx .. m_flt_baseLineTimesFx; invfx = 1.0f / fx as the
+// reference stores it; the MapPoint constructor MapPoint(pos, keyFrame, map).
+#ifndef YDORB_ADAPTER_LOCALMAPPING_HPP
+#define YDORB_ADAPTER_LOCALMAPPING_HPP
+
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <opencv2/core.hpp>
+
+#include "c_api.h"
+#include "orbMatcher.hpp"
+
+namespace ydorb {
+namespace adapter {
+
+// one keyframe as ydorb_triangulate_matches reads it; Rwc = Rcw^T in plain loops (a transpose rounds nothing)
+template <class FrameT, class KeyFramePtr>
+inline YdTriView triView(const KeyFramePtr& kf) {
+  static_assert(sizeof(cv::KeyPoint) == sizeof(YdKeyPoint), "cv::KeyPoint layout");
+  YdTriView v;
+  std::memset(&v, 0, sizeof v);
+  v.kps = reinterpret_cast<const YdKeyPoint*>(kf->m_v_keyPoints.data());
+  v.right_x = kf->m_v_rightXcords.data();
+  v.depth = kf->m_v_depth.data();
+  v.n = (int32_t)kf->m_v_keyPoints.size();
+  const cv::Mat R = kf->getRotation_c2w(), t = kf->getTranslation_c2w(), O = kf->getCameraOriginInWorld();
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) { v.Tcw[4 * r + c] = R.at<float>(r, c); v.Rwc[3 * c + r] = R.at<float>(r, c); }
+    v.Tcw[4 * r + 3] = t.at<float>(r);
+    v.Ow[r] = O.at<float>(r);
+  }
+  v.fx = FrameT::m_flt_fx; v.fy = FrameT::m_flt_fy; v.cx = FrameT::m_flt_cx; v.cy = FrameT::m_flt_cy;
+  v.invfx = 1.0f / FrameT::m_flt_fx; v.invfy = 1.0f / FrameT::m_flt_fy;
+  v.b = FrameT::m_flt_baseLine; v.bf = FrameT::m_flt_baseLineTimesFx;
+  v.level_sigma2 = kf->m_v_scaleFactorSquares.data();
+  v.scale_factors = kf->m_v_scaleFactors.data();
+  v.n_levels = (int32_t)kf->m_v_scaleFactors.size();
+  return v;
+}
+
+// LocalMapping::computeF12: F12 = K^-T [t12]x R12 K^-1 with R12 = R1w R2w^T, t12 = -R12 t2w + t1w, in plain 3x3 float loops (each
+// product rounded, sums in ascending k); K^-1 in closed form from fx, fy, cx, cy
+template <class FrameT, class KeyFramePtr>
+inline cv::Mat computeF12(const KeyFramePtr& kf1, const KeyFramePtr& kf2) {
+  const cv::Mat R1 = kf1->getRotation_c2w(), t1 = kf1->getTranslation_c2w(), R2 = kf2->getRotation_c2w(), t2 = kf2->getTranslation_c2w();
+  float R12[3][3], t12[3];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) {
+      float s = 0.f;
+      for (int k = 0; k < 3; k++) s = s + R1.at<float>(r, k) * R2.at<float>(c, k);
+      R12[r][c] = s;
+    }
+  for (int r = 0; r < 3; r++) {
+    float s = 0.f;
+    for (int k = 0; k < 3; k++) s = s + R12[r][k] * t2.at<float>(k);
+    t12[r] = -s + t1.at<float>(r);
+  }
+  const float tx[3][3] = {{0.f, -t12[2], t12[1]}, {t12[2], 0.f, -t12[0]}, {-t12[1], t12[0], 0.f}};
+  const float ifx = 1.0f / FrameT::m_flt_fx, ify = 1.0f / FrameT::m_flt_fy;
+  const float Kinv[3][3] = {{ifx, 0.f, -FrameT::m_flt_cx * ifx}, {0.f, ify, -FrameT::m_flt_cy * ify}, {0.f, 0.f, 1.f}};
+  float M[3][3], N[3][3];
+  auto mul = [](const float (*A)[3], const float (*B)[3], float (*C)[3], bool transposeA) {
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) {
+        float s = 0.f;
+        for (int k = 0; k < 3; k++) s = s + (transposeA ? A[k][r] : A[r][k]) * B[k][c];
+        C[r][c] = s;
+      }
+  };
+  mul(Kinv, tx, M, true);    // K^-T [t12]x
+  mul(M, R12, N, false);
+  mul(N, Kinv, M, false);
+  cv::Mat F(3, 3, CV_32F);
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) F.at<float>(r, c) = M[r][c];
+  return F;
+}
+
+// Returns the number of MapPoints created.  MapPointT is the pointee (std::make_shared<MapPointT>(pos, keyFrame, map)).  `device` is
+// the device that `m` was created on (matcher(device)), so that the search and the triangulation of a neighbour run on the same GPU.
+template <class FrameT, class KeyFramePtr, class MapPointT, class MapPtr, class RecentList, class AbortCheck>
+int createNewMapPointsImpl(ydorb_matcher_t* m, KeyFramePtr current, MapPtr map, RecentList& recentAddedMapPoints, AbortCheck abortCheck,
+                           int device = 0) {
+  const std::vector<KeyFramePtr> neighbours = current->getBestCovisibilityKeyFrames(10);
+  const cv::Mat Ow1 = current->getCameraOriginInWorld();
+  const float ratioFactor = 1.5f * current->m_v_scaleFactors[1];   // 1.5f * mfScaleFactor
+  YdTriView views[2];
+  views[0] = triView<FrameT>(current);   // pose and intrinsics of the current keyframe, read once before the loop as the reference does
+  int created = 0;
+  for (size_t i = 0; i < neighbours.size(); i++) {
+    if (i > 0 && abortCheck()) return created;
+    KeyFramePtr kf2 = neighbours[i];
+    const cv::Mat baselineVec = kf2->getCameraOriginInWorld() - Ow1;
+    const float baseline = (float)cv::norm(baselineVec);
+    if (baseline < FrameT::m_flt_baseLine) continue;
+    const cv::Mat F12 = computeF12<FrameT>(current, kf2);
+    std::vector<std::pair<int, int>> pairs;
+    searchForTriangulation<KeyFramePtr, FrameT>(m, current, kf2, F12, pairs, false, false);   // ORBmatcher(0.6, false)
+    const int32_t n = (int32_t)pairs.size();
+    if (n == 0) continue;
+    views[1] = triView<FrameT>(kf2);
+    std::vector<int32_t> idx1(n), idx2(n);
+    for (int32_t k = 0; k < n; k++) { idx1[k] = pairs[k].first; idx2[k] = pairs[k].second; }
+    const int32_t first = 0, second = 1, start[2] = {0, n};
+    YdTriBatch B;
+    std::memset(&B, 0, sizeof B);
+    B.device = device; B.n_views = 2; B.n_problems = 1; B.views = views; B.first_view = &first; B.second_view = &second;
+    B.match_start = start; B.idx1 = idx1.data(); B.idx2 = idx2.data(); B.ratio_factor = &ratioFactor;
+    std::vector<float> x3d(3 * (size_t)n);
+    std::vector<uint8_t> status(n);
+    if (ydorb_triangulate_matches(&B, x3d.data(), status.data(), nullptr) != YDORB_OK)
+      throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
+    for (int32_t k = 0; k < n; k++) {
+      if ((status[k] & 15) != YDORB_TRI_ACCEPTED) continue;
+      cv::Mat pos(3, 1, CV_32F);
+      for (int r = 0; r < 3; r++) pos.at<float>(r) = x3d[3 * (size_t)k + r];
+      auto mp = std::make_shared<MapPointT>(pos, current, map);
+      mp->addObservation(current, idx1[k]);
+      mp->addObservation(kf2, idx2[k]);
+      current->addMapPoint(mp, idx1[k]);
+      kf2->addMapPoint(mp, idx2[k]);
+      mp->computeDistinctiveDescriptors();
+      mp->updateNormalAndDepth();
+      map->addMapPoint(mp);
+      recentAddedMapPoints.push_back(mp);
+      created++;
+    }
+  }
+  return created;
+}
+
+}  // namespace adapter
+}  // namespace ydorb
+#endif

@@ -96,6 +96,8 @@ SYMBOLS = {
     "ydorb_kfdb_score": (C.c_int, [_VP, _VP, _VP, _I, _VP, _I, _VP]),
     "ydorb_kfdb_detect_reloc": (C.c_int, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
     "ydorb_kfdb_detect_loop": (C.c_int, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_triangulate_matches": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "ydorb_triangulate_release": (C.c_int, [_I]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -129,6 +131,17 @@ class YdPnpProblem(C.Structure):
 class YdSim3Batch(C.Structure):
     _fields_ = [("n_problems", _I), ("device", _I), ("corr_start", _VP), ("S12", _VP), ("K1", _VP), ("K2", _VP), ("fix_scale", _VP),
                 ("X1c", _VP), ("X2c", _VP), ("obs1", _VP), ("obs2", _VP), ("inv_sigma2_1", _VP), ("inv_sigma2_2", _VP), ("th2", C.c_double)]
+
+
+class YdTriView(C.Structure):
+    _fields_ = [("kps", _VP), ("right_x", _VP), ("depth", _VP), ("n", _I), ("Tcw", C.c_float * 12), ("Rwc", C.c_float * 9),
+                ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float),
+                ("invfy", C.c_float), ("b", C.c_float), ("bf", C.c_float), ("level_sigma2", _VP), ("scale_factors", _VP), ("n_levels", _I)]
+
+
+class YdTriBatch(C.Structure):
+    _fields_ = [("device", _I), ("n_views", _I), ("n_problems", _I), ("views", _VP), ("first_view", _VP), ("second_view", _VP),
+                ("match_start", _VP), ("idx1", _VP), ("idx2", _VP), ("ratio_factor", _VP)]
 
 
 class YdBaOptions(C.Structure):
