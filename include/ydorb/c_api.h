@@ -130,8 +130,10 @@ int ydorb_extractor_stage_times(ydorb_extractor_t* h, int32_t max_stages, const 
  * search-by-projection and search-by-BoW families.  Frame / KeyFrame / MapPoint objects do not cross the
  * ABI: a map point is a query row (descriptor + projected position + flags) and `assigned[idx]` stands
  * for frame.m_v_sptrMapPoints[idx] (a query index, or -1 for null).  The float geometry that projects map
- * points (cv::Mat products at orbMatcher.cpp:84-93,171-177; Frame::isInCameraFrustum, frame.cpp:295-326)
- * stays in the adapter class, which fills YdQuery with the very floats the reference computes.
+ * points (cv::Mat products at orbMatcher.cpp:84-93,171-177) stays in the adapter class, which fills YdQuery
+ * with the very floats the reference computes.  Frame::isInCameraFrustum (frame.cpp:295-326), the geometry of
+ * Tracking::searchLocalPoints, is the exception: ydorb_frustum_cull and ydorb_search_local_points ("Local map
+ * tracking" below) run it on the GPU.
  * ---------------------------------------------------------------------------------------- */
 typedef struct YdQuery {
   float u, v;          /* projected image position */
@@ -665,6 +667,68 @@ typedef struct YdTriBatch {
 int ydorb_triangulate_matches(const YdTriBatch* batch, float* x3d, uint8_t* status, int32_t* n_accepted);
 /* ydorb_triangulate_matches keeps device scratch per device between calls; this frees it (waiting for calls in flight). */
 int ydorb_triangulate_release(int32_t device);
+
+/* ------------------------------------------------------------------------------------------
+ * Local map tracking: Tracking::searchLocalPoints (tracking.cpp:570-604), i.e. Frame::isInCameraFrustum (frame.cpp:295-326) per
+ * local map point with MapPoint::predictScaleLevel, then searchByProjectionInFrameAndMapPoint (orbMatcher.cpp:24-64).  The
+ * semantics restate ORB-SLAM2's Frame::isInFrustum and MapPoint::PredictScale, which YDORBSLAM renames; DESIGN.md section 2
+ * ("isInCameraFrustum") fixes the fp32 operation order and lists the assumptions.  One GPU lane per (view, map point); results are
+ * bit-identical to a CPU restatement compiled with -ffp-contract=off.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdFrustumView {  /* one frame: pose, intrinsics, image bounds and the scale pyramid */
+  float Rcw[9], tcw[3], Ow[3];  /* m_cvMat_R_c2w row-major, m_cvMat_t_c2w, m_cvMat_origin: as the frame holds them */
+  float fx, fy, cx, cy, bf;
+  float min_x, max_x, min_y, max_y;
+  float viewing_cos_limit;      /* 0.5 in searchLocalPoints */
+  int32_t n_levels;             /* 1..8 */
+  float level_ratio[7];         /* [n_levels-1] used: level_ratio[k] = the largest float ratio for which
+                                   ceil(log(ratio) / logScaleFactor) <= k; the predicted level is the number of entries strictly below
+                                   maxDistance / dist.  Built on the host with the reference's own log (tracking.hpp levelRatioTable) */
+  float scale_factors[8];       /* m_v_scaleFactors; read by ydorb_search_local_points only */
+} YdFrustumView;
+typedef struct YdMapPointTable { /* the map points shared by all views of a call */
+  const float* pos_min;         /* [n][4]: getPosInWorld() x y z, getMinDistanceInvariance() */
+  const float* normal_max;      /* [n][4]: getNormal() x y z, getMaxDistanceInvariance() */
+  const float* max_distance;    /* [n]: the raw m_flt_maxDistance (predictScaleLevel divides it by the distance) */
+  const uint8_t* desc;          /* [n][32] getDescriptor(); read by ydorb_search_local_points only, may be NULL otherwise */
+  int32_t n;
+} YdMapPointTable;
+typedef struct YdFrustumBatch {
+  int32_t device, n_views;
+  const YdFrustumView* views;   /* [n_views] */
+  YdMapPointTable table;
+  const int32_t* list_start;    /* [n_views+1], list_start[0] = 0, non-decreasing: view f tests entries list_start[f] .. list_start[f+1] */
+  const int32_t* point_idx;     /* [list_start[n_views]] index into the table */
+  const uint8_t* skip;          /* [list_start[n_views]] 1 = the caller skips this point (isBad(), or last seen in this frame) */
+} YdFrustumBatch;
+typedef struct YdTrackView {    /* what isInCameraFrustum leaves on a map point in view; all zero otherwise */
+  float u, v, ur, view_cos;     /* m_flt_trackProjX, m_flt_trackProjY, m_flt_trackProjRightX, m_flt_trackViewCos */
+  int32_t level;                /* m_int_trackScaleLevel */
+} YdTrackView;
+/* status byte of a list entry: the first exit that fires, in the reference's order */
+#define YDORB_FRUSTUM_IN_VIEW 0
+#define YDORB_FRUSTUM_SKIPPED 1     /* the caller's skip flag */
+#define YDORB_FRUSTUM_BEHIND 2      /* PcZ < 0.0f */
+#define YDORB_FRUSTUM_OUT_U 3       /* u < minX || u > maxX */
+#define YDORB_FRUSTUM_OUT_V 4       /* v < minY || v > maxY */
+#define YDORB_FRUSTUM_DISTANCE 5    /* dist < minDistInv || dist > maxDistInv */
+#define YDORB_FRUSTUM_VIEW_ANGLE 6  /* viewCos < viewingCosLimit */
+/* rows [L], status [L] with L = list_start[n_views]; n_in_view [n_views] or NULL.  A NaN passes every exit and PcZ == 0 gives inf / NaN
+ * projections that fail no bounds test, as in the reference.  Null arrays, a malformed list_start, a point index outside the table
+ * and n_levels outside 1..8 return YDORB_ERR_INVALID_ARG before any device work. */
+int ydorb_frustum_cull(const YdFrustumBatch* batch, YdTrackView* rows, uint8_t* status, int32_t* n_in_view);
+/* ydorb_frustum_cull keeps device scratch per device between calls; this frees it (waiting for calls in flight). */
+int ydorb_frustum_release(int32_t device);
+/* Tracking::searchLocalPoints' numeric part in one call.  The result is defined as the composition of (1) ydorb_frustum_cull with one
+ * view over the points 0 .. table->n-1 (skip [n]), (2) the query build of searchByProjectionInFrameAndMapPoint (orbMatcher.cpp:28-38):
+ * radius = th * (view_cos > 0.998 ? 2.5f : 4.0f), r = rs = radius * scale_factors[level], level window level-1 .. level, flags =
+ * 1 | (has_observations[i] ? 2 : 0), flags = 0 for points not in view, and (3) ydorb_search_by_projection(mode 0, ratio) with
+ * table->desc as the queries' descriptors; the queries are built on the device and never visit the host.  taken / assigned as in
+ * ydorb_search_by_projection (assigned[idx] = point index); rows [n], status [n] as in ydorb_frustum_cull; *n_to_match = the number
+ * of points in view (the reference searches only when it is > 0: with 0, *n_matches = 0 and assigned is untouched). */
+int ydorb_search_local_points(ydorb_matcher_t* h, const YdFrameView* frame, const YdFrustumView* view, const YdMapPointTable* table,
+                              const uint8_t* skip, const uint8_t* has_observations, float th, float ratio, uint8_t* taken,
+                              int32_t* assigned, YdTrackView* rows, uint8_t* status, int32_t* n_to_match, int32_t* n_matches);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@ from .sim3 import Sim3Solver, optimize_sim3  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401
 from .kfdb import KeyFrameDatabase  # noqa: F401
 from .triangulate import triangulate_matches  # noqa: F401
+from .frustum import frustum_cull, search_local_points  # noqa: F401
 
 __all__ = ["YdorbError", "lib", "library_path", "build_library", "OrbExtractor", "KP_DTYPE", "OrbMatcher", "FrameView",
            "FeatureVector", "QUERY_DTYPE", "Optimizer", "Vocabulary", "Sim3Solver", "optimize_sim3", "PnPsolver", "KeyFrameDatabase",
-           "triangulate_matches"]
+           "triangulate_matches", "frustum_cull", "search_local_points"]

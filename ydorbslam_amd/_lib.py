@@ -98,6 +98,9 @@ SYMBOLS = {
     "ydorb_kfdb_detect_loop": (C.c_int, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
     "ydorb_triangulate_matches": (C.c_int, [_VP, _VP, _VP, _VP]),
     "ydorb_triangulate_release": (C.c_int, [_I]),
+    "ydorb_frustum_cull": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "ydorb_frustum_release": (C.c_int, [_I]),
+    "ydorb_search_local_points": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP, C.POINTER(_I), C.POINTER(_I)]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -142,6 +145,21 @@ class YdTriView(C.Structure):
 class YdTriBatch(C.Structure):
     _fields_ = [("device", _I), ("n_views", _I), ("n_problems", _I), ("views", _VP), ("first_view", _VP), ("second_view", _VP),
                 ("match_start", _VP), ("idx1", _VP), ("idx2", _VP), ("ratio_factor", _VP)]
+
+
+class YdFrustumView(C.Structure):
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("viewing_cos_limit", C.c_float), ("n_levels", _I), ("level_ratio", C.c_float * 7), ("scale_factors", C.c_float * 8)]
+
+
+class YdMapPointTable(C.Structure):
+    _fields_ = [("pos_min", _VP), ("normal_max", _VP), ("max_distance", _VP), ("desc", _VP), ("n", _I)]
+
+
+class YdFrustumBatch(C.Structure):
+    _fields_ = [("device", _I), ("n_views", _I), ("views", _VP), ("table", YdMapPointTable), ("list_start", _VP), ("point_idx", _VP),
+                ("skip", _VP)]
 
 
 class YdBaOptions(C.Structure):

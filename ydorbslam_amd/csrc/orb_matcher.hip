@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
+#include "frustum_kernels.hip.h"
 #include "host_buffers.h"
 #include "match_kernels.hip.h"
 #include "stereo_kernels.hip.h"
@@ -47,7 +48,9 @@ struct ydorb_matcher {
   int device = 0;
   hipStream_t stream = nullptr;
   Mem kps, desc, rightX, queries, qdesc, taken, assigned, matchQ, qInfo, qPre, cellStart, cellIdx, pool, frames, calls, misc, kps2,
-      desc2, feat, valid, qFeat, qRange, qAngle, sf, heads, sortedKp, sortedDesc, kps1, good1, good2, stereoPar, stereoCnt, stereoOut;
+      desc2, feat, valid, qFeat, qRange, qAngle, sf, heads, sortedKp, sortedDesc, kps1, good1, good2, stereoPar, stereoCnt, stereoOut,
+      frustumIn, frustumOut;         // ydorb_search_local_points: the map-point table as uploaded, track rows + status bytes
+  PinnedMem frustumUp, frustumDown;  // ... and their pinned staging / read-back areas
   size_t poolRecords = 1u << 20;
   // cached descriptors of the last batched launch (re-uploaded only when they change)
   std::vector<FrameDev> hFrames;
@@ -63,7 +66,8 @@ struct ydorb_matcher {
   bool evPending = false;
   std::vector<Mem*> buffers() {
     return {&kps, &desc, &rightX, &queries, &qdesc, &taken, &assigned, &matchQ, &qInfo, &qPre, &cellStart, &cellIdx, &pool, &frames, &calls, &misc, &kps2,
-            &desc2, &feat, &valid, &qFeat, &qRange, &qAngle, &sf, &heads, &sortedKp, &sortedDesc, &kps1, &good1, &good2, &stereoPar, &stereoCnt, &stereoOut};
+            &desc2, &feat, &valid, &qFeat, &qRange, &qAngle, &sf, &heads, &sortedKp, &sortedDesc, &kps1, &good1, &good2, &stereoPar, &stereoCnt, &stereoOut,
+            &frustumIn, &frustumOut, &frustumUp, &frustumDown};
   }
   ydorb_matcher() { for (Mem* b : buffers()) b->slackDiv = 2; }   // 50 % slack instead of the default 25 %
 };
@@ -205,6 +209,8 @@ int ydorb_distinctive_descriptors(ydorb_matcher_t* m, const uint8_t* desc, const
   return YDORB_OK;
 }
 
+// queries == nullptr: the nq query rows are in m->queries already (ydorb_search_local_points builds them there with a kernel queued on
+// m->stream; nothing below writes them, so a record-pool replay finds them unchanged)
 static int searchProjectionImpl(ydorb_matcher_t* m, int32_t mode, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc,
                                 int32_t nq, float ratio, int32_t orbDist, int32_t checkOri, uint8_t* taken, int32_t* assigned,
                                 int32_t* nMatches, std::vector<uint32_t>* recordsOut, const float* invSigma2 = nullptr, int nLevels = 0,
@@ -222,7 +228,7 @@ static int searchProjectionImpl(ydorb_matcher_t* m, int32_t mode, const YdFrameV
         (rc = m->qPre.ensure(sizeof(uint2) * nq)) ||
         (rc = m->pool.ensure(sizeof(uint32_t) * ((size_t)nq * kSlot + m->poolRecords))) || (rc = m->calls.ensure(sizeof(CallDev))) || (rc = resetMisc(m, m->stream)))
       return rc;
-    HIPCHK(hipMemcpyAsync(m->queries.p, queries, sizeof(YdQuery) * nq, hipMemcpyHostToDevice, m->stream));
+    if (queries) HIPCHK(hipMemcpyAsync(m->queries.p, queries, sizeof(YdQuery) * nq, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->qdesc.p, qdesc, (size_t)32 * nq, hipMemcpyHostToDevice, m->stream));
     if (taken) HIPCHK(hipMemcpyAsync(m->taken.p, taken, n, hipMemcpyHostToDevice, m->stream));
     else HIPCHK(hipMemsetAsync(m->taken.p, 0, n, m->stream));
@@ -277,6 +283,56 @@ int ydorb_search_by_projection(ydorb_matcher_t* m, int32_t mode, const YdFrameVi
   }
   if (mode == 7) checkOri = 0;   // searchByProjectionInSim has no rotation-consistency step
   return searchProjectionImpl(m, mode, fv, queries, qdesc, nq, ratio, orbDist, checkOri, taken, assigned, nMatches, nullptr);
+}
+
+int ydorb_search_local_points(ydorb_matcher_t* m, const YdFrameView* fv, const YdFrustumView* view, const YdMapPointTable* table,
+                              const uint8_t* skip, const uint8_t* hasObs, float th, float ratio, uint8_t* taken, int32_t* assigned,
+                              YdTrackView* rows, uint8_t* status, int32_t* nToMatch, int32_t* nMatches) {
+  if (!m || !fv || !view || !table || !nToMatch || !nMatches) { set_error("search_local_points: null argument"); return YDORB_ERR_INVALID_ARG; }
+  if (view->n_levels < 1 || view->n_levels > 8) { set_error("search_local_points: n_levels %d outside 1..8", view->n_levels); return YDORB_ERR_INVALID_ARG; }
+  const int np = table->n, n = fv->n;
+  if (np < 0 || n < 0) { set_error("search_local_points: negative size"); return YDORB_ERR_INVALID_ARG; }
+  if (np > 0 && (!table->pos_min || !table->normal_max || !table->max_distance || !table->desc || !skip || !hasObs || !rows || !status)) {
+    set_error("search_local_points: null map-point table, flag or output arrays");
+    return YDORB_ERR_INVALID_ARG;
+  }
+  if ((n > 0 && (!fv->kps || !fv->desc || !assigned)) || !(fv->max_x > fv->min_x) || !(fv->max_y > fv->min_y)) {
+    set_error("search_local_points: invalid frame view");
+    return YDORB_ERR_INVALID_ARG;
+  }
+  *nToMatch = 0; *nMatches = 0;
+  if (np == 0) return YDORB_OK;
+  HIPCHK(hipSetDevice(m->device));
+  const size_t p = np;
+  Layout U;
+  const size_t oPos = U.add(16 * p), oNrm = U.add(16 * p), oMax = U.add(4 * p), oSkip = U.add(p), oObs = U.add(p);
+  Layout D;
+  const size_t dRows = D.add(sizeof(YdTrackView) * p), dSt = D.add(p);
+  int rc;
+  if ((rc = m->frustumIn.ensure(U.bytes)) || (rc = m->frustumUp.ensure(U.bytes)) || (rc = m->frustumOut.ensure(D.bytes)) ||
+      (rc = m->frustumDown.ensure(D.bytes)) || (rc = m->queries.ensure(sizeof(YdQuery) * p)))
+    return rc;
+  std::memcpy(at<void>(m->frustumUp, oPos), table->pos_min, 16 * p);
+  std::memcpy(at<void>(m->frustumUp, oNrm), table->normal_max, 16 * p);
+  std::memcpy(at<void>(m->frustumUp, oMax), table->max_distance, 4 * p);
+  std::memcpy(at<void>(m->frustumUp, oSkip), skip, p);
+  std::memcpy(at<void>(m->frustumUp, oObs), hasObs, p);
+  HIPCHK(hipMemcpyAsync(m->frustumIn.p, m->frustumUp.p, U.bytes, hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(frustum::k_frustum_queries<QueryDev>, dim3((np + frustum::kThreads - 1) / frustum::kThreads), dim3(frustum::kThreads), 0, m->stream, *view,
+                     np, at<float4>(m->frustumIn, oPos), at<float4>(m->frustumIn, oNrm), at<float>(m->frustumIn, oMax), at<uint8_t>(m->frustumIn, oSkip),
+                     at<uint8_t>(m->frustumIn, oObs), th, m->queries.as<QueryDev>(), at<YdTrackView>(m->frustumOut, dRows), at<uint8_t>(m->frustumOut, dSt));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(m->frustumDown.p, m->frustumOut.p, D.bytes, hipMemcpyDeviceToHost, m->stream));
+  // the search follows on the same stream without a host round trip: with no point in view every query has flags 0, nothing matches and
+  // assigned / taken come back as they went up, which is the reference's skipped search
+  if ((rc = searchProjectionImpl(m, YDORB_SEARCH_FRAME_MAPPOINT, fv, nullptr, table->desc, np, ratio, 0, 0, taken, assigned, nMatches, nullptr))) return rc;
+  HIPCHK(hipStreamSynchronize(m->stream));   // the search returns early, without one, for a frame without keypoints
+  std::memcpy(rows, at<void>(m->frustumDown, dRows), sizeof(YdTrackView) * p);
+  std::memcpy(status, at<void>(m->frustumDown, dSt), p);
+  int inView = 0;
+  for (int i = 0; i < np; i++) inView += status[i] == YDORB_FRUSTUM_IN_VIEW;
+  *nToMatch = inView;
+  return YDORB_OK;
 }
 
 int ydorb_fuse_search(ydorb_matcher_t* m, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc, int32_t nq,
