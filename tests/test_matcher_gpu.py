@@ -502,3 +502,172 @@ def test_resolve_contention_in_match_pairs_device(oracle_lib, scene):
         a_dev = d_assigned.cpu().numpy()[0, :nt]
         assert int(d_counts[0]) == n_host == ref[check][0]
         assert np.array_equal(a_dev, a_host) and np.array_equal(a_host, ref[check][1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# One handle, both kinds of call.  The device-resident pair search is asynchronous and keeps a sticky overflow status until
+# synchronize; the host calls run on the handle's own stream meanwhile.  Neither may disturb the other.  Shapes sit just above the
+# 64-lane / 64-record-slot boundaries (70 keypoints, 65 descriptors in a group) and a few hundred beyond.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _planted_frame(rng, n, near=None):
+    """n keypoints at octave 1 / 2 with random positions and descriptors; with `near` = (kps, desc) every keypoint is one of that frame's
+    moved 20 px to the left and one octave down, with a few descriptor bits flipped (never in byte 0, which picks the vocabulary node).
+    frame.cpp:353 offers a window's keypoints only where |dx| > r, and :349 skips octaves below the window's upper level, so these are
+    the pairs the pair search (th = 15, levels octave - 1 .. octave + 1) can match."""
+    import ydorbslam_amd as y
+    k = np.zeros(n, y.KP_DTYPE)
+    if near is None:
+        k["x"], k["y"] = rng.uniform(40, 600, n), rng.uniform(20, 460, n)
+        k["octave"], k["angle"], k["size"] = rng.integers(1, 3, n), rng.uniform(0, 360, n), 31
+        d = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    else:
+        src = rng.choice(len(near[0]), n, replace=False)
+        k[:] = near[0][src]
+        k["x"] -= np.float32(20)
+        k["octave"] -= 1
+        d = near[1][src].copy()
+        d[np.arange(n)[:, None], rng.integers(1, 32, (n, 3))] ^= np.uint8(1) << rng.integers(0, 8, (n, 3)).astype(np.uint8)
+    return k, d
+
+
+def _queries_left_of(k, d, nq, rng, sf):
+    """nq queries 20 px to the left of the frame's first nq keypoints (th = 10: r < 20 at octaves 0 .. 2; no level window), with their
+    descriptors but for one bit."""
+    import ydorbslam_amd as y
+    q = np.zeros(nq, y.QUERY_DTYPE)
+    q["u"], q["v"] = k["x"][:nq] - np.float32(20), k["y"][:nq]
+    q["r"] = (np.float32(10.0) * sf[k["octave"][:nq]]).astype(np.float32)
+    q["min_level"], q["max_level"] = -1, -1
+    q["angle"], q["level"], q["flags"] = k["angle"][:nq], k["octave"][:nq], 3
+    qd = d[:nq].copy()
+    qd[np.arange(nq), rng.integers(1, 32, nq)] ^= np.uint8(16)
+    return q, qd
+
+
+def _device_set(frames, cap):
+    """[(kps, desc), ...] as a device-resident frame set (kps, desc, n tensors; the tuple match_pairs_device takes)."""
+    import torch
+    import ydorbslam_amd as y
+    kps = np.zeros((len(frames), cap), y.KP_DTYPE); desc = np.zeros((len(frames), cap, 32), np.uint8)
+    for f, (k, d) in enumerate(frames):
+        kps[f, :len(k)], desc[f, :len(k)] = k, d
+    dev = torch.device("cuda:0")
+    t = (torch.from_numpy(kps.view(np.uint8).reshape(len(frames), cap, 28)).to(dev), torch.from_numpy(desc).to(dev),
+         torch.tensor([len(k) for k, _ in frames], dtype=torch.int32, device=dev))
+    return t, (t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), len(frames), cap)
+
+
+def _as_bytes(result):
+    return b"".join(np.asarray(r).tobytes() for r in (result if isinstance(result, tuple) else (result,)))
+
+
+def test_host_calls_between_device_calls_on_one_handle():
+    """match_pairs_device on a stream of the caller's, not waited for; then every kind of host call on the same handle; synchronize; the
+    batched call again into other output tensors.  Every host-call result equals, byte for byte, that of the same call on a fresh handle,
+    and both batched results equal each other and a fresh handle's."""
+    import torch
+    import ydorbslam_amd as y
+    rng = np.random.default_rng(2024)
+    sf = np.power(np.float32(1.2), np.arange(8)).astype(np.float32)
+    W, H, cap = 640, 480, 768
+    kl, dl = _planted_frame(rng, 700)
+    ks, ds = _planted_frame(rng, 70, near=(kl, dl))
+    bounds = (0.0, float(W), 0.0, float(H))
+    fl, fs = y.FrameView(kl, dl, bounds), y.FrameView(ks, ds, bounds)
+    ql, qdl = _queries_left_of(kl, dl, 500, rng, sf)
+    qs, qds = _queries_left_of(ks, ds, 50, rng, sf)
+    fvl, fvs = y.FeatureVector(*feature_vector(bow_nodes(dl))), y.FeatureVector(*feature_vector(bow_nodes(ds)))
+    vl, vs = (rng.random(700) > 0.15).astype(np.uint8), (rng.random(70) > 0.15).astype(np.uint8)
+    mpl, mps = (rng.random(700) < 0.3).astype(np.uint8), (rng.random(70) < 0.3).astype(np.uint8)
+    rl = np.where(rng.random(700) < 0.5, kl["x"] - 5, -1).astype(np.float32)
+    rs = np.where(rng.random(70) < 0.5, ks["x"] - 5, -1).astype(np.float32)
+    F = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)          # epipolar line of a pure shift along x: y' = y
+    sizes = rng.integers(0, 130, 500); sizes[3] = 0; sizes[4] = 65
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    cand = rng.integers(0, 700, int(offs[-1])).astype(np.int32)
+    groups = [dl[:70], dl[70:73], np.zeros((0, 32), np.uint8), dl[100:165], ds]
+    zero = np.zeros(8, np.float32)
+    host_calls = [
+        ("projection, large frame", lambda m: m.search_by_projection(1, fl, ql, qdl)),
+        ("projection, small frame", lambda m: m.search_by_projection(1, fs, qs, qds)),
+        ("bow", lambda m: m.search_by_bow(4, kl, dl, vl, fvl, ks, ds, vs, fvs)),
+        ("triangulation", lambda m: m.search_for_triangulation(kl, dl, mpl, rl, fvl, ks, ds, mps, rs, fvs, F, (-900.0, 240.0), sf, sf * sf)),
+        ("hamming_topk", lambda m: m.hamming_topk(qdl, dl, offs, cand)),
+        ("distinctive_descriptors", lambda m: m.distinctive_descriptors(groups)),
+        ("fuse_search", lambda m: m.fuse_search(fl, ql, qdl, zero, 100)),
+        ("projection, large frame again", lambda m: m.search_by_projection(1, fl, ql, qdl)),
+    ]
+    want = [_as_bytes(call(y.OrbMatcher(0.9, True))) for _, call in host_calls]
+    assert host_calls[0][1](y.OrbMatcher(0.9, True))[0] > 100 and host_calls[2][1](y.OrbMatcher(0.9, True))[0] > 20      # real matches exist
+
+    dev = torch.device("cuda:0")
+    keep, fset = _device_set([(ks, ds), (kl, dl)], cap)
+    pairs = [(0, 1), (1, 0)]
+
+    def batched(m, stream=None):
+        a = torch.zeros((2, cap), dtype=torch.int32, device=dev); c = torch.zeros(2, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()                                             # the zero fills ran on torch's stream
+        m.match_pairs_device(fset, fset, pairs, W, H, 15.0, sf, a.data_ptr(), c.data_ptr(), stream=stream)
+        return a, c
+
+    fresh = y.OrbMatcher(0.9, True)
+    ref_a, ref_c = batched(fresh)
+    fresh.synchronize()
+    assert int(ref_c.sum()) > 60
+    side = torch.cuda.Stream(device=dev)
+    m = y.OrbMatcher(0.9, True)
+    a1, c1 = batched(m, side.cuda_stream)
+    for (name, call), ref in zip(host_calls, want):
+        assert _as_bytes(call(m)) == ref, name
+    m.synchronize()
+    a2, c2 = batched(m, side.cuda_stream)
+    m.synchronize()
+    for a, c in ((a1, c1), (a2, c2)):
+        assert torch.equal(a, ref_a) and torch.equal(c, ref_c)
+
+
+def test_batched_overflow_status_survives_a_host_call(oracle_lib):
+    """A record-pool overflow of the device-resident search is reported by the next synchronize, whatever host calls the handle serves in
+    between (the status word was cleared by every host-call search once).  100 queries at octave 0 whose windows all hold the other
+    frame's 100 keypoints, which are one octave up (frame.cpp:349): by the oracle's count more than the first call's overflow region (16 records per keypoint of capacity) takes and no more
+    than the enlarged one (64), so the call after the reported overflow is complete and equals the oracle."""
+    import torch
+    import ydorbslam_amd as y
+    rng = np.random.default_rng(7)
+    sf = np.power(np.float32(1.2), np.arange(8)).astype(np.float32)
+    W, H, cap, n = 640, 480, 256, 100
+    ka = np.zeros(n, y.KP_DTYPE)
+    ka["x"], ka["y"], ka["size"] = 300 + rng.uniform(-2, 2, n), 240 + rng.uniform(-2, 2, n), 31           # octave 0: r = th = 15
+    da = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    kb, db = ka.copy(), da.copy()
+    kb["x"] += np.float32(20)                                                                              # |dx| > r, |dy| < r
+    kb["octave"] = 1
+    db[np.arange(n), rng.integers(0, 32, n)] ^= np.uint8(4)
+    frames = [(ka, da), (kb, db)]
+    pairs = [(0, 1)]
+    bounds = (0.0, float(W), 0.0, float(H))
+    oracles = [oracle_lib.FrameOracle(k, d, bounds) for k, d in frames]
+    for qf, tf in pairs:                                                     # precondition, on the CPU: the overflow region's demand per pair
+        kq = frames[qf][0]
+        counts = [len(oracles[tf].keypoints_in_area(kq["x"][i], kq["y"][i], np.float32(15.0), -1, 1)) for i in range(n)]
+        demand = sum(c for c in counts if c > 64)
+        assert 16 * cap < demand <= 64 * cap, (qf, tf, demand)
+    dev = torch.device("cuda:0")
+    keep, fset = _device_set(frames, cap)
+    a = torch.zeros((1, cap), dtype=torch.int32, device=dev); c = torch.zeros(1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    m = y.OrbMatcher(0.9, True)
+    m.match_pairs_device(fset, fset, pairs, W, H, 15.0, sf, a.data_ptr(), c.data_ptr())
+    q, qd = _queries_left_of(kb, db, 10, rng, sf)
+    m.search_by_projection(1, y.FrameView(kb, db, bounds), q, qd)
+    with pytest.raises(y.YdorbError):
+        m.synchronize()
+    m.match_pairs_device(fset, fset, pairs, W, H, 15.0, sf, a.data_ptr(), c.data_ptr())
+    m.synchronize()
+    for i, (qf, tf) in enumerate(pairs):
+        kq, dq = frames[qf]
+        q = np.zeros(n, y.QUERY_DTYPE)
+        q["u"], q["v"], q["r"] = kq["x"], kq["y"], np.float32(15.0)
+        q["min_level"], q["max_level"], q["flags"] = -1, 1, 3
+        n_ref, a_ref, _ = oracles[tf].search_by_projection(1, q, dq, 0.9, True)
+        assert int(c[i]) == n_ref and np.array_equal(a[i, :n].cpu().numpy(), a_ref)

@@ -34,15 +34,6 @@ enum { PH_ERR = 0, PH_BUILD, PH_SCHUR, PH_SOLVE, PH_UPDATE, PH_COUNT };
 // The reduced system of one optimize() call: stage 1 sizes it, stage 2 re-uses it (and the arenas laid out for it) as it is.
 struct Sys { std::vector<int> act; int nL = 0, nPf = 0, Ea = 0, n = 0, nb = 0, nBlkE = 0, nBuckets = 0, nPoseEdges = 0; size_t nItems = 0; };
 
-// Hands out the arrays of an arena in order, every one 256-byte aligned.  The lay*() functions below run twice per (re)layout: over a
-// null base for the size the arena needs, then over the arena for the pointers.
-struct Carve {
-  uintptr_t base;
-  Layout L{0, 256};
-  explicit Carve(void* p) : base(reinterpret_cast<uintptr_t>(p)) {}
-  template <class T> void take(T*& ptr, size_t count) { ptr = reinterpret_cast<T*>(base + L.add(sizeof(T) * count)); }
-};
-
 // `state`: both copies of the estimate (LM push / pop is a swap of the index).  beginSolve uploads [0]; prepareStage copies cur -> cur ^ 1
 // whole before the first k_update of a stage, which writes the free poses and the active landmarks only.
 struct StatePtrs { double *poses[2], *pts[2]; };

@@ -69,11 +69,20 @@ struct ScopedMem : Mem {   // for function-local buffers only (see Mem)
 template <class T> T* at(Mem& m, size_t off) { return m.at<T>(off); }
 
 // Lays arrays out at aligned offsets of one area: the same offsets address the pinned staging and the device copy.  `align` is a
-// power of two, set before the first add(): 16 bytes serve any element type; BA asks for 256 so that every array of an arena
-// starts on the boundary a buffer of its own had (hipMalloc returns at least that).
+// power of two, set before the first add(): 16 bytes serve any element type; the arenas (Carve) ask for 256 so that every array of
+// one starts on the boundary a buffer of its own had (hipMalloc returns at least that).
 struct Layout {
   size_t bytes = 0, align = 16;
   size_t add(size_t n) { const size_t at = bytes; bytes += (n + align - 1) & ~(align - 1); return at; }
+};
+
+// Hands out the arrays of an arena in order, every one 256-byte aligned.  A driver's lay*() functions run twice per (re)layout: over a
+// null base for the size the arena needs, then over the arena for the pointers.
+struct Carve {
+  uintptr_t base;
+  Layout L{0, 256};
+  explicit Carve(void* p) : base(reinterpret_cast<uintptr_t>(p)) {}
+  template <class T> void take(T*& ptr, size_t count) { ptr = reinterpret_cast<T*>(base + L.add(sizeof(T) * count)); }
 };
 
 // Per-device scratch of a solver that stages a batch up and its results down, reused between calls.  Every solver keeps its own

@@ -42,39 +42,121 @@ __global__ void k_hamming_rows(const uint8_t* a, const uint8_t* b, int n, int* o
 enum { MS_GRID = 0, MS_GATHER, MS_RESOLVE, MS_COUNT };
 const char* kMatchStageNames[MS_COUNT] = {"grid_build", "gather_distances", "resolve"};
 
+// Device memory: one arena per path, laid out afresh by every call (Carve, host_buffers.h).
+// k_resolve writes the taken flags back in whole 32-bit words of its LDS copy, up to 31 bytes past the last keypoint's
+constexpr size_t kTakenPad = 31;
+
+// Sizes a layout over a null base, grows the arena if need be and lays it out for real.
+template <class Lay> int layOut(Mem& arena, Lay lay) {
+  const int rc = arena.ensure(lay(nullptr));
+  if (rc == YDORB_OK) lay(arena.p);
+  return rc;
+}
+
+// `batch`: ydorb_match_pairs_device.  The descriptors come first: they are uploaded only when they change, and where they lie depends on
+// the frame and call counts alone.  The record pool, by far the largest, comes last.
+struct BatchPtrs {
+  FrameDev* frames; CallDev* calls; float *sf, *ident;   // descriptors; ident = one identity affine per call
+  QueryDev* queries; uint8_t* taken; int* matchQ; int2* qInfo; uint2* qPre; unsigned* heads;
+  int *cellStart, *cellIdx; float4* sortedKp; uint8_t* sortedDesc;
+  uint32_t* pool;
+};
+size_t layBatch(size_t cap, size_t nCalls, size_t nFrames, size_t poolPerCall, void* base, BatchPtrs& p) {
+  Carve a(base);
+  a.take(p.frames, nFrames); a.take(p.calls, nCalls); a.take(p.sf, 8); a.take(p.ident, 6 * nCalls);
+  a.take(p.queries, cap * nCalls); a.take(p.taken, cap * nCalls + kTakenPad); a.take(p.matchQ, cap * nCalls); a.take(p.qInfo, cap * nCalls);
+  a.take(p.qPre, cap * nCalls); a.take(p.heads, nCalls); a.take(p.cellStart, (kGridCells + 1) * nFrames); a.take(p.cellIdx, cap * nFrames);
+  a.take(p.sortedKp, cap * nFrames); a.take(p.sortedDesc, 32 * cap * nFrames);
+  a.take(p.pool, poolPerCall * nCalls);
+  return a.L.bytes;
+}
+
+// `call`, projection family: a frame of n keypoints and its grid, nq queries.  status = [0] pool head (unsigned), [1] overflow status, [2] match
+// count, cleared per attempt.  table / track (ydorb_search_local_points only): the map-point table as the pinned area holds it, track rows + status.
+struct ProjPtrs {
+  int* status; FrameDev* frame; CallDev* call;
+  KeyPointDev* kps; uint8_t* desc; float* rightX; int *cellStart, *cellIdx; float4* sortedKp; uint8_t* sortedDesc;
+  QueryDev* queries; uint8_t *qdesc, *taken; int *assigned, *matchQ; int2* qInfo; uint2* qPre;
+  uint8_t *table, *track;
+};
+size_t layProjection(size_t n, bool stereo, size_t nq, size_t tableBytes, size_t trackBytes, void* base, ProjPtrs& p) {
+  Carve a(base);
+  a.take(p.status, 16); a.take(p.frame, 1); a.take(p.call, 1);
+  a.take(p.kps, n); a.take(p.desc, 32 * n); a.take(p.rightX, stereo ? n : 0); a.take(p.cellStart, kGridCells + 1); a.take(p.cellIdx, n);
+  a.take(p.sortedKp, n); a.take(p.sortedDesc, 32 * n);
+  a.take(p.queries, nq); a.take(p.qdesc, 32 * nq); a.take(p.taken, n + kTakenPad); a.take(p.assigned, n); a.take(p.matchQ, nq); a.take(p.qInfo, nq);
+  a.take(p.qPre, nq); a.take(p.table, tableBytes); a.take(p.track, trackBytes);
+  return a.L.bytes;
+}
+
+// `call`, BoW family: nq (feature of A, bucket of B) queries; kpsA / goodA / goodB for searchForTriangulation only.  status as above.
+struct BowPtrs {
+  int* status; CallDev* call;
+  uint8_t *descA, *descB, *valid, *goodA, *goodB; KeyPointDev *kpsA, *kpsB; int *feat, *qFeat, *assigned, *matchQ; int2 *qRange, *qInfo; float* qAngle;
+};
+size_t layBow(size_t nA, size_t nB, size_t nFeatB, size_t nq, bool tri, void* base, BowPtrs& p) {
+  Carve a(base);
+  a.take(p.status, 16); a.take(p.call, 1);
+  a.take(p.descA, 32 * nA); a.take(p.descB, 32 * nB); a.take(p.kpsB, nB); a.take(p.feat, nFeatB); a.take(p.valid, nB);
+  a.take(p.qFeat, nq); a.take(p.qRange, nq); a.take(p.qAngle, nq); a.take(p.qInfo, nq); a.take(p.matchQ, nq); a.take(p.assigned, std::max(nq, nB));
+  a.take(p.kpsA, tri ? nA : 0); a.take(p.goodA, tri ? nA : 0); a.take(p.goodB, tri ? nB : 0);
+  return a.L.bytes;
+}
+
+// `call`, descriptor rows (Hamming rows, distinctive descriptors, top-2): two descriptor sets, a CSR over them, one int or TopkOut per row
+struct RowsPtrs { uint8_t *a, *b; int *offsets, *idx, *out; TopkOut* top; };
+size_t layRows(size_t nA, size_t nB, size_t nOffsets, size_t nIdx, size_t nOut, size_t nTop, void* base, RowsPtrs& r) {
+  Carve a(base);
+  a.take(r.a, 32 * nA); a.take(r.b, 32 * nB); a.take(r.offsets, nOffsets); a.take(r.idx, nIdx); a.take(r.out, nOut); a.take(r.top, nTop);
+  return a.L.bytes;
+}
+
+// `stereo`: counters and per-pair outputs first (the device-pointer form needs no more, so they lie where they lay whichever form the
+// last call had); then, for the host-pointer form (nl / nr keypoint rows), what is uploaded and the results on their way down.
+struct StereoPtrs { int *counters, *kept, *status, *nL, *nR; KeyPointDev *kpsL, *kpsR; uint8_t *descL, *descR; float *rightX, *depth; };
+size_t layStereo(size_t nPairs, size_t nl, size_t nr, void* base, StereoPtrs& p) {
+  Carve a(base);
+  a.take(p.counters, 4 * nPairs); a.take(p.kept, nPairs); a.take(p.status, nPairs);
+  a.take(p.kpsL, nl); a.take(p.descL, 32 * nl); a.take(p.kpsR, nr); a.take(p.descR, 32 * nr); a.take(p.nL, nl ? nPairs : 0); a.take(p.nR, nl ? nPairs : 0);
+  a.take(p.rightX, nl); a.take(p.depth, nl);
+  return a.L.bytes;
+}
+
 }  // namespace
 
+// Host-call and batched paths share no device state on a handle: a batched call may still be running on its caller's stream, and its
+// sticky status still be unread, while a host call runs on the handle's own stream.
 struct ydorb_matcher {
   int device = 0;
   hipStream_t stream = nullptr;
-  Mem kps, desc, rightX, queries, qdesc, taken, assigned, matchQ, qInfo, qPre, cellStart, cellIdx, pool, frames, calls, misc, kps2,
-      desc2, feat, valid, qFeat, qRange, qAngle, sf, heads, sortedKp, sortedDesc, kps1, good1, good2, stereoPar, stereoCnt, stereoOut,
-      frustumIn, frustumOut;         // ydorb_search_local_points: the map-point table as uploaded, track rows + status bytes
-  PinnedMem frustumUp, frustumDown;  // ... and their pinned staging / read-back areas
-  size_t poolRecords = 1u << 20;
-  // cached descriptors of the last batched launch (re-uploaded only when they change)
-  std::vector<FrameDev> hFrames;
-  std::vector<CallDev> hCalls;
-  float hSf[8] = {0};
-  bool hIdentAffine = false;
-  std::vector<int32_t> consecPairs;
-  int ovfPerKeypoint = 16;
+  Mem call;              // every synchronous host-call entry point: each ends in a stream synchronise, so the next one lays it out afresh
+  Mem pool;              // the host calls' record pool: grows by poolRecords, not by a call's shape, and a replay after an overflow
+  size_t poolRecords = 1u << 20;   // ... finds everything else where it was
+  Mem stereo;            // ydorb_stereo_matches (layStereo)
+  PinnedMem hUp, hDown;  // ydorb_search_local_points: pinned staging of the map-point table, read-back of track rows + status bytes
+  // What ydorb_match_pairs_device / ydorb_match_consecutive_device keep; nothing but them, synchronize and destroy touches it.
+  struct Batch {
+    Mem arena;           // layBatch
+    Mem status;          // 64 bytes; word [1] is the overflow status, sticky until synchronize reads it
+    // the descriptors the arena holds, re-uploaded only when they change.  Emptied when the arena is regrown: the new one holds none,
+    // wherever it lies.  `at`: where they went; an upload stays valid only while a call's layout puts them there again.
+    std::vector<FrameDev> hFrames;
+    std::vector<CallDev> hCalls;
+    float hSf[8] = {0};
+    bool hIdentAffine = false;
+    BatchPtrs at{};
+    int ovfPerKeypoint = 16;
+  } batch;
   bool profiling = false;
   hipEvent_t ev[MS_COUNT + 1]{};
   double stageMs[MS_COUNT]{};
   int stageCalls = 0;
   bool evPending = false;
-  std::vector<Mem*> buffers() {
-    return {&kps, &desc, &rightX, &queries, &qdesc, &taken, &assigned, &matchQ, &qInfo, &qPre, &cellStart, &cellIdx, &pool, &frames, &calls, &misc, &kps2,
-            &desc2, &feat, &valid, &qFeat, &qRange, &qAngle, &sf, &heads, &sortedKp, &sortedDesc, &kps1, &good1, &good2, &stereoPar, &stereoCnt, &stereoOut,
-            &frustumIn, &frustumOut, &frustumUp, &frustumDown};
-  }
+  std::vector<Mem*> buffers() { return {&call, &pool, &stereo, &hUp, &hDown, &batch.arena, &batch.status}; }
   ydorb_matcher() { for (Mem* b : buffers()) b->slackDiv = 2; }   // 50 % slack instead of the default 25 %
 };
 
-namespace {
-
-void collect(ydorb_matcher* m) {
+static void collect(ydorb_matcher* m) {
   if (!m->profiling || !m->evPending) return;
   m->evPending = false;
   if (hipEventQuery(m->ev[MS_COUNT]) != hipSuccess) return;   // a pipelined caller launched again before the events completed: sample dropped, never waited for
@@ -85,49 +167,21 @@ void collect(ydorb_matcher* m) {
   m->stageCalls++;
 }
 
-// misc layout: [0] poolHead (unsigned), [1] status (int), [2] count (int)
-int resetMisc(ydorb_matcher* m, hipStream_t s) {
-  int rc = m->misc.ensure(64);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(m->misc.p, 0, 64, s));
-  return YDORB_OK;
+static bool validFrameView(const YdFrameView* fv) {
+  return fv && fv->n >= 0 && (fv->n == 0 || (fv->kps && fv->desc)) && fv->max_x > fv->min_x && fv->max_y > fv->min_y;
 }
-
-FrameDev makeFrame(const YdFrameView& v, const KeyPointDev* dk, const uint8_t* dd, const float* drx, int* cellStart, int* cellIdx, float4* skp,
-                   uint8_t* sdesc) {
-  FrameDev F{};
-  F.kps = dk; F.desc = dd; F.rightX = drx; F.nPtr = nullptr; F.n = v.n;
-  F.minX = v.min_x; F.minY = v.min_y;
-  F.gridWInv = static_cast<float>(kGridCols) / (v.max_x - v.min_x);  // frame.cpp:99-100
-  F.gridHInv = static_cast<float>(kGridRows) / (v.max_y - v.min_y);
-  F.cellStart = cellStart; F.cellIdx = cellIdx; F.sortedKp = skp; F.sortedDesc = sdesc;
-  return F;
-}
-
-int uploadFrame(ydorb_matcher* m, const YdFrameView* fv, FrameDev* out) {
-  const int n = std::max(fv->n, 1);
-  int rc;
-  if ((rc = m->kps.ensure(sizeof(YdKeyPoint) * n)) || (rc = m->desc.ensure((size_t)32 * n)) || (rc = m->cellStart.ensure(sizeof(int) * (kGridCells + 1))) ||
-      (rc = m->cellIdx.ensure(sizeof(int) * n)) || (rc = m->frames.ensure(sizeof(FrameDev))) || (rc = m->sortedKp.ensure(sizeof(float4) * n)) ||
-      (rc = m->sortedDesc.ensure((size_t)32 * n)))
-    return rc;
-  if (fv->right_x && (rc = m->rightX.ensure(sizeof(float) * n))) return rc;
-  if (fv->n > 0) {
-    HIPCHK(hipMemcpyAsync(m->kps.p, fv->kps, sizeof(YdKeyPoint) * fv->n, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->desc.p, fv->desc, (size_t)32 * fv->n, hipMemcpyHostToDevice, m->stream));
-    if (fv->right_x) HIPCHK(hipMemcpyAsync(m->rightX.p, fv->right_x, sizeof(float) * fv->n, hipMemcpyHostToDevice, m->stream));
-  }
-  *out = makeFrame(*fv, m->kps.as<KeyPointDev>(), m->desc.as<uint8_t>(), fv->right_x ? m->rightX.as<float>() : nullptr,
-                   m->cellStart.as<int>(), m->cellIdx.as<int>(), m->sortedKp.as<float4>(), m->sortedDesc.as<uint8_t>());
-  HIPCHK(hipMemcpyAsync(m->frames.p, out, sizeof(FrameDev), hipMemcpyHostToDevice, m->stream));
-  return launchGridBuild(1, n, m->stream, m->frames.as<FrameDev>());
-}
-
-}  // namespace
 
 extern "C" {
 
-void ydorb_matcher_destroy(ydorb_matcher_t* m);
+void ydorb_matcher_destroy(ydorb_matcher_t* m) {
+  if (!m) return;
+  (void)hipSetDevice(m->device);
+  (void)hipStreamSynchronize(m->stream);
+  for (Mem* b : m->buffers()) b->release();
+  for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
+  (void)hipStreamDestroy(m->stream);
+  delete m;
+}
 
 int ydorb_matcher_create(int32_t device, ydorb_matcher_t** out) {
   if (!out) { set_error("null argument"); return YDORB_ERR_INVALID_ARG; }
@@ -142,23 +196,13 @@ int ydorb_matcher_create(int32_t device, ydorb_matcher_t** out) {
     return YDORB_ERR_HIP;
   }
   for (auto& e : m->ev) (void)hipEventCreate(&e);
-  if (m->misc.ensure(64) != YDORB_OK || hipMemset(m->misc.p, 0, 64) != hipSuccess) {
+  if (m->batch.status.ensure(64) != YDORB_OK || hipMemset(m->batch.status.p, 0, 64) != hipSuccess) {
     set_error("matcher scratch allocation failed");
     ydorb_matcher_destroy(m);
     return YDORB_ERR_HIP;
   }
   *out = m;
   return YDORB_OK;
-}
-
-void ydorb_matcher_destroy(ydorb_matcher_t* m) {
-  if (!m) return;
-  (void)hipSetDevice(m->device);
-  (void)hipStreamSynchronize(m->stream);
-  for (Mem* b : m->buffers()) b->release();
-  for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
-  (void)hipStreamDestroy(m->stream);
-  delete m;
 }
 
 int ydorb_descriptor_distance(const uint8_t* a, const uint8_t* b) {
@@ -176,12 +220,12 @@ int ydorb_descriptor_distance_rows(ydorb_matcher_t* m, const uint8_t* a, const u
   if (!m || !a || !b || !out || n < 0) { set_error("invalid argument"); return YDORB_ERR_INVALID_ARG; }
   if (n == 0) return YDORB_OK;
   HIPCHK(hipSetDevice(m->device));
-  int rc;
-  if ((rc = m->desc.ensure((size_t)32 * n)) || (rc = m->desc2.ensure((size_t)32 * n)) || (rc = m->assigned.ensure(sizeof(int) * n))) return rc;
-  HIPCHK(hipMemcpyAsync(m->desc.p, a, (size_t)32 * n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->desc2.p, b, (size_t)32 * n, hipMemcpyHostToDevice, m->stream));
-  hipLaunchKernelGGL(k_hamming_rows, dim3((n + 255) / 256), dim3(256), 0, m->stream, m->desc.as<uint8_t>(), m->desc2.as<uint8_t>(), n, m->assigned.as<int>());
-  HIPCHK(hipMemcpyAsync(out, m->assigned.p, sizeof(int) * n, hipMemcpyDeviceToHost, m->stream));
+  RowsPtrs r;
+  if (const int rc = layOut(m->call, [&](void* base) { return layRows(n, n, 0, 0, n, 0, base, r); })) return rc;
+  HIPCHK(hipMemcpyAsync(r.a, a, (size_t)32 * n, hipMemcpyHostToDevice, m->stream));
+  HIPCHK(hipMemcpyAsync(r.b, b, (size_t)32 * n, hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(k_hamming_rows, dim3((n + 255) / 256), dim3(256), 0, m->stream, r.a, r.b, n, r.out);
+  HIPCHK(hipMemcpyAsync(out, r.out, sizeof(int) * n, hipMemcpyDeviceToHost, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   return YDORB_OK;
 }
@@ -196,61 +240,67 @@ int ydorb_distinctive_descriptors(ydorb_matcher_t* m, const uint8_t* desc, const
     if (cnt < 0 || cnt > 65535) { set_error("map point %d holds %d descriptors (0..65535 supported)", p, cnt); return YDORB_ERR_INVALID_ARG; }
   }
   HIPCHK(hipSetDevice(m->device));
-  int rc;
-  if ((rc = m->desc.ensure((size_t)32 * std::max(total, 1))) || (rc = m->qRange.ensure(sizeof(int) * (nPoints + 1))) ||
-      (rc = m->assigned.ensure(sizeof(int) * nPoints)))
-    return rc;
-  if (total) HIPCHK(hipMemcpyAsync(m->desc.p, desc, (size_t)32 * total, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->qRange.p, offsets, sizeof(int) * (nPoints + 1), hipMemcpyHostToDevice, m->stream));
-  hipLaunchKernelGGL(k_distinctive, dim3((nPoints + 3) / 4), dim3(256), 0, m->stream, m->desc.as<uint8_t>(), m->qRange.as<int>(), nPoints, m->assigned.as<int>());
+  RowsPtrs r;
+  if (const int rc = layOut(m->call, [&](void* base) { return layRows(std::max(total, 1), 0, nPoints + 1, 0, nPoints, 0, base, r); })) return rc;
+  if (total) HIPCHK(hipMemcpyAsync(r.a, desc, (size_t)32 * total, hipMemcpyHostToDevice, m->stream));
+  HIPCHK(hipMemcpyAsync(r.offsets, offsets, sizeof(int) * (nPoints + 1), hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(k_distinctive, dim3((nPoints + 3) / 4), dim3(256), 0, m->stream, r.a, r.offsets, nPoints, r.out);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(best, m->assigned.p, sizeof(int) * nPoints, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipMemcpyAsync(best, r.out, sizeof(int) * nPoints, hipMemcpyDeviceToHost, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   return YDORB_OK;
 }
 
-// queries == nullptr: the nq query rows are in m->queries already (ydorb_search_local_points builds them there with a kernel queued on
-// m->stream; nothing below writes them, so a record-pool replay finds them unchanged)
+// laid != nullptr: the caller has laid the call arena out (layProjection) and the nq query rows are in laid->queries already
+// (ydorb_search_local_points builds them there with a kernel queued on m->stream; nothing below writes them or regrows the arena, so a
+// record-pool replay finds them unchanged)
 static int searchProjectionImpl(ydorb_matcher_t* m, int32_t mode, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc,
                                 int32_t nq, float ratio, int32_t orbDist, int32_t checkOri, uint8_t* taken, int32_t* assigned,
                                 int32_t* nMatches, std::vector<uint32_t>* recordsOut, const float* invSigma2 = nullptr, int nLevels = 0,
-                                int32_t* bestOut = nullptr) {
+                                int32_t* bestOut = nullptr, const ProjPtrs* laid = nullptr) {
   HIPCHK(hipSetDevice(m->device));
   const int n = fv->n;
   if (n > 65535) { set_error("frames with more than 65535 keypoints are not supported"); return YDORB_ERR_UNSUPPORTED; }
   if (nq == 0 || n == 0) { *nMatches = 0; return YDORB_OK; }
+  int rc;
+  ProjPtrs p;
+  if (laid) p = *laid;
+  else if ((rc = layOut(m->call, [&](void* base) { return layProjection(n, fv->right_x, nq, 0, 0, base, p); }))) return rc;
   for (int attempt = 0; attempt < 6; attempt++) {
-    int rc;
-    FrameDev F;
-    if ((rc = uploadFrame(m, fv, &F))) return rc;
-    if ((rc = m->queries.ensure(sizeof(YdQuery) * nq)) || (rc = m->qdesc.ensure((size_t)32 * nq)) || (rc = m->taken.ensure(n)) ||
-        (rc = m->assigned.ensure(sizeof(int) * n)) || (rc = m->matchQ.ensure(sizeof(int) * nq)) || (rc = m->qInfo.ensure(sizeof(int2) * nq)) ||
-        (rc = m->qPre.ensure(sizeof(uint2) * nq)) ||
-        (rc = m->pool.ensure(sizeof(uint32_t) * ((size_t)nq * kSlot + m->poolRecords))) || (rc = m->calls.ensure(sizeof(CallDev))) || (rc = resetMisc(m, m->stream)))
-      return rc;
-    if (queries) HIPCHK(hipMemcpyAsync(m->queries.p, queries, sizeof(YdQuery) * nq, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->qdesc.p, qdesc, (size_t)32 * nq, hipMemcpyHostToDevice, m->stream));
-    if (taken) HIPCHK(hipMemcpyAsync(m->taken.p, taken, n, hipMemcpyHostToDevice, m->stream));
-    else HIPCHK(hipMemsetAsync(m->taken.p, 0, n, m->stream));
-    if (assigned) HIPCHK(hipMemcpyAsync(m->assigned.p, assigned, sizeof(int) * n, hipMemcpyHostToDevice, m->stream));
+    const size_t poolCap = (size_t)nq * kSlot + m->poolRecords;
+    if ((rc = m->pool.ensure(sizeof(uint32_t) * poolCap))) return rc;
+    HIPCHK(hipMemcpyAsync(p.kps, fv->kps, sizeof(YdKeyPoint) * n, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(p.desc, fv->desc, (size_t)32 * n, hipMemcpyHostToDevice, m->stream));
+    if (fv->right_x) HIPCHK(hipMemcpyAsync(p.rightX, fv->right_x, sizeof(float) * n, hipMemcpyHostToDevice, m->stream));
+    FrameDev F{};
+    F.kps = p.kps; F.desc = p.desc; F.rightX = fv->right_x ? p.rightX : nullptr; F.nPtr = nullptr; F.n = n;
+    F.minX = fv->min_x; F.minY = fv->min_y;
+    F.gridWInv = static_cast<float>(kGridCols) / (fv->max_x - fv->min_x);  // frame.cpp:99-100
+    F.gridHInv = static_cast<float>(kGridRows) / (fv->max_y - fv->min_y);
+    F.cellStart = p.cellStart; F.cellIdx = p.cellIdx; F.sortedKp = p.sortedKp; F.sortedDesc = p.sortedDesc;
+    HIPCHK(hipMemcpyAsync(p.frame, &F, sizeof(FrameDev), hipMemcpyHostToDevice, m->stream));
+    if ((rc = launchGridBuild(1, n, m->stream, p.frame))) return rc;
+    HIPCHK(hipMemsetAsync(p.status, 0, 64, m->stream));
+    if (queries) HIPCHK(hipMemcpyAsync(p.queries, queries, sizeof(YdQuery) * nq, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(p.qdesc, qdesc, (size_t)32 * nq, hipMemcpyHostToDevice, m->stream));
+    if (taken) HIPCHK(hipMemcpyAsync(p.taken, taken, n, hipMemcpyHostToDevice, m->stream));
+    else HIPCHK(hipMemsetAsync(p.taken, 0, n, m->stream));
+    if (assigned) HIPCHK(hipMemcpyAsync(p.assigned, assigned, sizeof(int) * n, hipMemcpyHostToDevice, m->stream));
     CallDev C{};
-    C.frame = 0; C.tkps = F.kps; C.qAngle = nullptr;
-    C.queries = m->queries.as<QueryDev>(); C.qdesc = m->qdesc.as<uint8_t>(); C.nqPtr = nullptr; C.nq = nq;
-    C.qInfo = m->qInfo.as<int2>(); C.taken = m->taken.as<uint8_t>(); C.assigned = m->assigned.as<int>(); C.matchQ = m->matchQ.as<int>();
-    C.qPre = m->qPre.as<uint2>(); C.takenClear = taken ? 0 : 1;
-    C.count = m->misc.as<int>() + 2; C.mode = mode; C.ratio = ratio; C.orbDist = orbDist; C.checkOri = checkOri;
+    C.tkps = p.kps; C.queries = p.queries; C.qdesc = p.qdesc; C.nq = nq; C.qInfo = p.qInfo; C.qPre = p.qPre;   // frame 0, counts from the host
+    C.taken = p.taken; C.takenClear = taken ? 0 : 1; C.assigned = p.assigned; C.matchQ = p.matchQ;
+    C.count = p.status + 2; C.mode = mode; C.ratio = ratio; C.orbDist = orbDist; C.checkOri = checkOri;
     for (int i = 0; i < 8; i++) C.invSigma2[i] = (invSigma2 && i < nLevels) ? invSigma2[i] : 0.f;
-    HIPCHK(hipMemcpyAsync(m->calls.p, &C, sizeof(CallDev), hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(k_gather_projection, dim3((nq + 4 * kGatherQpw - 1) / (4 * kGatherQpw), 1), dim3(256), 0, m->stream, m->calls.as<CallDev>(), m->frames.as<FrameDev>(), nq,
-                       m->pool.as<uint32_t>(), m->misc.as<unsigned>(), (unsigned)((size_t)nq * kSlot + m->poolRecords), m->misc.as<int>() + 1);
+    HIPCHK(hipMemcpyAsync(p.call, &C, sizeof(CallDev), hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(k_gather_projection, dim3((nq + 4 * kGatherQpw - 1) / (4 * kGatherQpw), 1), dim3(256), 0, m->stream, p.call, p.frame, nq,
+                       m->pool.as<uint32_t>(), reinterpret_cast<unsigned*>(p.status), (unsigned)poolCap, p.status + 1);
     int hmisc[3];
     if (!recordsOut) {
       const int takenWords = (n + 31) / 32;
-      hipLaunchKernelGGL(k_resolve, dim3(1), dim3(64), 2 * sizeof(unsigned) * takenWords, m->stream, m->calls.as<CallDev>(), m->frames.as<FrameDev>(),
-                         m->pool.as<uint32_t>(), takenWords);
+      hipLaunchKernelGGL(k_resolve, dim3(1), dim3(64), 2 * sizeof(unsigned) * takenWords, m->stream, p.call, p.frame, m->pool.as<uint32_t>(), takenWords);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hmisc, m->misc.p, sizeof(hmisc), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(hmisc, p.status, sizeof(hmisc), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     if (hmisc[1] != 0) {  // record pool too small: grow and replay (the kernels wrote nothing past the pool)
       m->poolRecords = std::max<size_t>(m->poolRecords * 4, (size_t)(unsigned)hmisc[0] + 1024);
@@ -258,14 +308,14 @@ static int searchProjectionImpl(ydorb_matcher_t* m, int32_t mode, const YdFrameV
     }
     if (recordsOut) {
       std::vector<int2> info(nq);
-      HIPCHK(hipMemcpy(info.data(), m->qInfo.p, sizeof(int2) * nq, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(info.data(), p.qInfo, sizeof(int2) * nq, hipMemcpyDeviceToHost));
       recordsOut->resize(info[0].y);
       if (info[0].y) HIPCHK(hipMemcpy(recordsOut->data(), m->pool.as<uint32_t>() + info[0].x, sizeof(uint32_t) * info[0].y, hipMemcpyDeviceToHost));
       return YDORB_OK;
     }
-    if (taken) HIPCHK(hipMemcpy(taken, m->taken.p, n, hipMemcpyDeviceToHost));
-    if (assigned) HIPCHK(hipMemcpy(assigned, m->assigned.p, sizeof(int) * n, hipMemcpyDeviceToHost));
-    if (bestOut) HIPCHK(hipMemcpy(bestOut, m->matchQ.p, sizeof(int) * nq, hipMemcpyDeviceToHost));
+    if (taken) HIPCHK(hipMemcpy(taken, p.taken, n, hipMemcpyDeviceToHost));
+    if (assigned) HIPCHK(hipMemcpy(assigned, p.assigned, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (bestOut) HIPCHK(hipMemcpy(bestOut, p.matchQ, sizeof(int) * nq, hipMemcpyDeviceToHost));
     *nMatches = hmisc[2];
     return YDORB_OK;
   }
@@ -273,11 +323,98 @@ static int searchProjectionImpl(ydorb_matcher_t* m, int32_t mode, const YdFrameV
   return YDORB_ERR_CAPACITY;
 }
 
+// One search of the BoW family (orbMatcher.cpp:303-462, :463-565): the features of A marked eligible are matched against the features of B
+// that share their vocabulary node.
+struct BowJob {
+  struct Side {
+    const YdKeyPoint* kps; const uint8_t* desc; int n; const YdFeatureVector* fv;
+    const uint8_t* ok;     // [n] A: may be a query; B: may be a candidate, null = every feature
+    const uint8_t* good;   // [n] searchForTriangulation: has a stereo coordinate
+  } A, B;
+  int mode;                // CallDev::mode: 3, 4 or 5
+  float ratio;
+  int checkOri;
+  BowCallDev geom;         // searchForTriangulation (geom.tri != 0): F, epipole, level tables; bowSearch fills the pointers in
+};
+
+// Join, layout, uploads, gather + resolve, read-back.  qFeat[q] = the feature of A behind query q (empty: nothing to match, res is not
+// written); res = the resolved assignment: per feature of B the query it went to (mode 3), else per query its feature of B, or -1.
+static int bowSearch(ydorb_matcher_t* m, const BowJob& J, std::vector<int>& qFeat, std::vector<int>& res, int32_t* nMatches) {
+  // which vocabulary nodes meet: merge-join of the two ascending id lists (orbMatcher.cpp:317-361, :484-541)
+  std::vector<int2> qRange;
+  std::vector<float> qAngle;
+  size_t records = 0;
+  const YdFeatureVector &fa = *J.A.fv, &fb = *J.B.fv;
+  for (int a = 0, b = 0; a < fa.n_nodes && b < fb.n_nodes;) {
+    if (fa.node_ids[a] == fb.node_ids[b]) {
+      for (int ia = fa.node_start[a]; ia < fa.node_start[a + 1]; ia++) {
+        const int idxA = fa.feat[ia];
+        if (!J.A.ok[idxA]) continue;
+        qFeat.push_back(idxA);
+        qRange.push_back(make_int2(fb.node_start[b], fb.node_start[b + 1]));
+        qAngle.push_back(J.A.kps[idxA].angle);
+        records += (size_t)(fb.node_start[b + 1] - fb.node_start[b]);
+      }
+      a++; b++;
+    } else if (fa.node_ids[a] < fb.node_ids[b]) {
+      a = (int)(std::lower_bound(fa.node_ids, fa.node_ids + fa.n_nodes, fb.node_ids[b]) - fa.node_ids);
+    } else {
+      b = (int)(std::lower_bound(fb.node_ids, fb.node_ids + fb.n_nodes, fa.node_ids[a]) - fb.node_ids);
+    }
+  }
+  const int nq = (int)qFeat.size();
+  if (nq == 0) return YDORB_OK;
+  const int nFeatB = fb.node_start[fb.n_nodes], nA = J.A.n, nB = J.B.n;
+  m->poolRecords = std::max<size_t>(m->poolRecords, records + 1024);
+  int rc;
+  BowPtrs p;
+  if ((rc = layOut(m->call, [&](void* base) { return layBow(nA, nB, std::max(nFeatB, 1), nq, J.geom.tri, base, p); })) ||
+      (rc = m->pool.ensure(sizeof(uint32_t) * m->poolRecords)))
+    return rc;
+  hipStream_t s = m->stream;
+  HIPCHK(hipMemsetAsync(p.status, 0, 64, s));
+  HIPCHK(hipMemcpyAsync(p.descA, J.A.desc, (size_t)32 * nA, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(p.descB, J.B.desc, (size_t)32 * nB, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(p.kpsB, J.B.kps, sizeof(YdKeyPoint) * nB, hipMemcpyHostToDevice, s));
+  if (nFeatB) HIPCHK(hipMemcpyAsync(p.feat, fb.feat, sizeof(int) * nFeatB, hipMemcpyHostToDevice, s));
+  if (J.B.ok) HIPCHK(hipMemcpyAsync(p.valid, J.B.ok, nB, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(p.qFeat, qFeat.data(), sizeof(int) * nq, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(p.qRange, qRange.data(), sizeof(int2) * nq, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(p.qAngle, qAngle.data(), sizeof(float) * nq, hipMemcpyHostToDevice, s));
+  res.resize(std::max(nq, nB));
+  HIPCHK(hipMemsetAsync(p.assigned, 0xFF, sizeof(int) * res.size(), s));
+  BowCallDev BC = J.geom;
+  BC.descA = p.descA; BC.descB = p.descB; BC.qFeat = p.qFeat; BC.qRange = p.qRange;
+  BC.featB = p.feat; BC.validB = J.B.ok ? p.valid : nullptr; BC.nq = nq; BC.qInfo = p.qInfo;
+  if (BC.tri) {
+    HIPCHK(hipMemcpyAsync(p.kpsA, J.A.kps, sizeof(YdKeyPoint) * nA, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(p.goodA, J.A.good, nA, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(p.goodB, J.B.good, nB, hipMemcpyHostToDevice, s));
+    BC.kpsA = p.kpsA; BC.kpsB = p.kpsB; BC.goodA = p.goodA; BC.goodB = p.goodB;
+  }
+  hipLaunchKernelGGL(k_gather_bow, dim3((nq + 3) / 4), dim3(256), 0, s, BC, m->pool.as<uint32_t>(), reinterpret_cast<unsigned*>(p.status),
+                     (unsigned)m->poolRecords, p.status + 1);
+  CallDev C{};
+  C.tkps = p.kpsB; C.qAngle = p.qAngle; C.nq = nq; C.qInfo = p.qInfo; C.assigned = p.assigned; C.matchQ = p.matchQ;   // no frame, query rows or taken flags
+  C.count = p.status + 2; C.mode = J.mode; C.ratio = J.ratio; C.checkOri = J.checkOri;
+  HIPCHK(hipMemcpyAsync(p.call, &C, sizeof(CallDev), hipMemcpyHostToDevice, s));
+  const int takenWords = (nB + 31) / 32;
+  hipLaunchKernelGGL(k_resolve, dim3(1), dim3(64), 2 * sizeof(unsigned) * takenWords, s, p.call, (const FrameDev*)nullptr, m->pool.as<uint32_t>(), takenWords);
+  HIPCHK(hipGetLastError());
+  int hmisc[3];
+  HIPCHK(hipMemcpyAsync(hmisc, p.status, sizeof(hmisc), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(res.data(), p.assigned, sizeof(int) * res.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (hmisc[1] != 0) { set_error("bow record pool overflow"); return YDORB_ERR_CAPACITY; }
+  *nMatches = hmisc[2];
+  return YDORB_OK;
+}
+
 int ydorb_search_by_projection(ydorb_matcher_t* m, int32_t mode, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc,
                                int32_t nq, float ratio, int32_t orbDist, int32_t checkOri, uint8_t* taken, int32_t* assigned,
                                int32_t* nMatches) {
-  if (!m || !fv || !nMatches || mode < 0 || (mode > 2 && mode != 7) || nq < 0 || fv->n < 0 || (nq > 0 && (!queries || !qdesc)) ||
-      (fv->n > 0 && (!fv->kps || !fv->desc || !assigned)) || !(fv->max_x > fv->min_x) || !(fv->max_y > fv->min_y)) {
+  if (!m || !validFrameView(fv) || !nMatches || mode < 0 || (mode > 2 && mode != 7) || nq < 0 || (nq > 0 && (!queries || !qdesc)) ||
+      (fv->n > 0 && !assigned)) {
     set_error("invalid argument");
     return YDORB_ERR_INVALID_ARG;
   }
@@ -296,7 +433,7 @@ int ydorb_search_local_points(ydorb_matcher_t* m, const YdFrameView* fv, const Y
     set_error("search_local_points: null map-point table, flag or output arrays");
     return YDORB_ERR_INVALID_ARG;
   }
-  if ((n > 0 && (!fv->kps || !fv->desc || !assigned)) || !(fv->max_x > fv->min_x) || !(fv->max_y > fv->min_y)) {
+  if (!validFrameView(fv) || (n > 0 && !assigned)) {
     set_error("search_local_points: invalid frame view");
     return YDORB_ERR_INVALID_ARG;
   }
@@ -308,30 +445,32 @@ int ydorb_search_local_points(ydorb_matcher_t* m, const YdFrameView* fv, const Y
   const size_t oPos = U.add(16 * p), oNrm = U.add(16 * p), oMax = U.add(4 * p), oSkip = U.add(p), oObs = U.add(p);
   Layout D;
   const size_t dRows = D.add(sizeof(YdTrackView) * p), dSt = D.add(p);
+  // table, track rows and status lie in the call arena with the search's arrays: it is grown, if at all, before k_frustum_queries
+  // writes the query rows into it
   int rc;
-  if ((rc = m->frustumIn.ensure(U.bytes)) || (rc = m->frustumUp.ensure(U.bytes)) || (rc = m->frustumOut.ensure(D.bytes)) ||
-      (rc = m->frustumDown.ensure(D.bytes)) || (rc = m->queries.ensure(sizeof(YdQuery) * p)))
-    return rc;
-  std::memcpy(at<void>(m->frustumUp, oPos), table->pos_min, 16 * p);
-  std::memcpy(at<void>(m->frustumUp, oNrm), table->normal_max, 16 * p);
-  std::memcpy(at<void>(m->frustumUp, oMax), table->max_distance, 4 * p);
-  std::memcpy(at<void>(m->frustumUp, oSkip), skip, p);
-  std::memcpy(at<void>(m->frustumUp, oObs), hasObs, p);
-  HIPCHK(hipMemcpyAsync(m->frustumIn.p, m->frustumUp.p, U.bytes, hipMemcpyHostToDevice, m->stream));
+  ProjPtrs q;
+  if ((rc = m->hUp.ensure(U.bytes)) || (rc = m->hDown.ensure(D.bytes))) return rc;
+  if ((rc = layOut(m->call, [&](void* base) { return layProjection(std::max(n, 1), fv->right_x, np, U.bytes, D.bytes, base, q); }))) return rc;
+  std::memcpy(at<void>(m->hUp, oPos), table->pos_min, 16 * p);
+  std::memcpy(at<void>(m->hUp, oNrm), table->normal_max, 16 * p);
+  std::memcpy(at<void>(m->hUp, oMax), table->max_distance, 4 * p);
+  std::memcpy(at<void>(m->hUp, oSkip), skip, p);
+  std::memcpy(at<void>(m->hUp, oObs), hasObs, p);
+  HIPCHK(hipMemcpyAsync(q.table, m->hUp.p, U.bytes, hipMemcpyHostToDevice, m->stream));
   hipLaunchKernelGGL(frustum::k_frustum_queries<QueryDev>, dim3((np + frustum::kThreads - 1) / frustum::kThreads), dim3(frustum::kThreads), 0, m->stream, *view,
-                     np, at<float4>(m->frustumIn, oPos), at<float4>(m->frustumIn, oNrm), at<float>(m->frustumIn, oMax), at<uint8_t>(m->frustumIn, oSkip),
-                     at<uint8_t>(m->frustumIn, oObs), th, m->queries.as<QueryDev>(), at<YdTrackView>(m->frustumOut, dRows), at<uint8_t>(m->frustumOut, dSt));
+                     np, (const float4*)(q.table + oPos), (const float4*)(q.table + oNrm), (const float*)(q.table + oMax), q.table + oSkip, q.table + oObs, th,
+                     q.queries, (YdTrackView*)(q.track + dRows), q.track + dSt);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(m->frustumDown.p, m->frustumOut.p, D.bytes, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipMemcpyAsync(m->hDown.p, q.track, D.bytes, hipMemcpyDeviceToHost, m->stream));
   // the search follows on the same stream without a host round trip: with no point in view every query has flags 0, nothing matches and
   // assigned / taken come back as they went up, which is the reference's skipped search
-  if ((rc = searchProjectionImpl(m, YDORB_SEARCH_FRAME_MAPPOINT, fv, nullptr, table->desc, np, ratio, 0, 0, taken, assigned, nMatches, nullptr))) return rc;
+  if ((rc = searchProjectionImpl(m, YDORB_SEARCH_FRAME_MAPPOINT, fv, nullptr, table->desc, np, ratio, 0, 0, taken, assigned, nMatches, nullptr, nullptr, 0,
+                                 nullptr, &q)))
+    return rc;
   HIPCHK(hipStreamSynchronize(m->stream));   // the search returns early, without one, for a frame without keypoints
-  std::memcpy(rows, at<void>(m->frustumDown, dRows), sizeof(YdTrackView) * p);
-  std::memcpy(status, at<void>(m->frustumDown, dSt), p);
-  int inView = 0;
-  for (int i = 0; i < np; i++) inView += status[i] == YDORB_FRUSTUM_IN_VIEW;
-  *nToMatch = inView;
+  std::memcpy(rows, at<void>(m->hDown, dRows), sizeof(YdTrackView) * p);
+  std::memcpy(status, at<void>(m->hDown, dSt), p);
+  for (int i = 0; i < np; i++) *nToMatch += status[i] == YDORB_FRUSTUM_IN_VIEW;
   return YDORB_OK;
 }
 
@@ -342,8 +481,8 @@ int ydorb_fuse_search(ydorb_matcher_t* m, const YdFrameView* fv, const YdQuery* 
 
 int ydorb_window_search(ydorb_matcher_t* m, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc, int32_t nq,
                         const float* invSigma2, int32_t nLevels, int32_t maxDist, int32_t* best, int32_t* nFound) {
-  if (!m || !fv || !nFound || nq < 0 || maxDist < 0 || maxDist > 256 || fv->n < 0 || (nq > 0 && (!queries || !qdesc || !best)) || !invSigma2 || nLevels < 1 || nLevels > 8 ||
-      (fv->n > 0 && (!fv->kps || !fv->desc)) || !(fv->max_x > fv->min_x) || !(fv->max_y > fv->min_y)) {
+  if (!m || !validFrameView(fv) || !nFound || nq < 0 || maxDist < 0 || maxDist > 256 || (nq > 0 && (!queries || !qdesc || !best)) || !invSigma2 || nLevels < 1 ||
+      nLevels > 8) {
     set_error("invalid argument");
     return YDORB_ERR_INVALID_ARG;
   }
@@ -356,7 +495,7 @@ int ydorb_window_search(ydorb_matcher_t* m, const YdFrameView* fv, const YdQuery
 
 int ydorb_frame_keypoints_in_area(ydorb_matcher_t* m, const YdFrameView* fv, float x, float y, float r, int32_t minLevel, int32_t maxLevel,
                                   int32_t* outIdx, int32_t cap, int32_t* nOut) {
-  if (!m || !fv || !nOut || (cap > 0 && !outIdx) || fv->n < 0 || !(fv->max_x > fv->min_x) || !(fv->max_y > fv->min_y)) {
+  if (!m || !validFrameView(fv) || !nOut || (cap > 0 && !outIdx)) {
     set_error("invalid argument");
     return YDORB_ERR_INVALID_ARG;
   }
@@ -388,78 +527,15 @@ int ydorb_search_by_bow(ydorb_matcher_t* m, int32_t mode, const YdBowSide* A, co
   *nMatches = 0;
   if (A->n == 0 || B->n == 0) return YDORB_OK;
   if (B->n > 65535) { set_error("more than 65535 features per frame are not supported"); return YDORB_ERR_UNSUPPORTED; }
-  // which vocabulary nodes meet: merge-join of the two ascending id lists (orbMatcher.cpp:317-361)
-  std::vector<int> qFeat;
-  std::vector<int2> qRange;
-  std::vector<float> qAngle;
-  size_t records = 0;
-  {
-    int a = 0, b = 0;
-    const YdFeatureVector &fa = A->fv, &fb = B->fv;
-    while (a < fa.n_nodes && b < fb.n_nodes) {
-      if (fa.node_ids[a] == fb.node_ids[b]) {
-        for (int ia = fa.node_start[a]; ia < fa.node_start[a + 1]; ia++) {
-          const int idxA = fa.feat[ia];
-          if (!A->valid[idxA]) continue;
-          qFeat.push_back(idxA);
-          qRange.push_back(make_int2(fb.node_start[b], fb.node_start[b + 1]));
-          qAngle.push_back(A->kps[idxA].angle);
-          records += (size_t)(fb.node_start[b + 1] - fb.node_start[b]);
-        }
-        a++; b++;
-      } else if (fa.node_ids[a] < fb.node_ids[b]) {
-        a = (int)(std::lower_bound(fa.node_ids, fa.node_ids + fa.n_nodes, fb.node_ids[b]) - fa.node_ids);
-      } else {
-        b = (int)(std::lower_bound(fb.node_ids, fb.node_ids + fb.n_nodes, fa.node_ids[a]) - fb.node_ids);
-      }
-    }
-  }
-  const int nq = (int)qFeat.size();
-  if (nq == 0) return YDORB_OK;
-  const int nFeatB = B->fv.node_start[B->fv.n_nodes];
-  m->poolRecords = std::max<size_t>(m->poolRecords, records + 1024);
-  int rc;
-  if ((rc = m->desc.ensure((size_t)32 * A->n)) || (rc = m->desc2.ensure((size_t)32 * B->n)) || (rc = m->kps2.ensure(sizeof(YdKeyPoint) * B->n)) ||
-      (rc = m->feat.ensure(sizeof(int) * std::max(nFeatB, 1))) || (rc = m->valid.ensure(B->n)) || (rc = m->qFeat.ensure(sizeof(int) * nq)) ||
-      (rc = m->qRange.ensure(sizeof(int2) * nq)) || (rc = m->qAngle.ensure(sizeof(float) * nq)) || (rc = m->qInfo.ensure(sizeof(int2) * nq)) ||
-      (rc = m->matchQ.ensure(sizeof(int) * nq)) || (rc = m->assigned.ensure(sizeof(int) * std::max(nq, B->n))) ||
-      (rc = m->pool.ensure(sizeof(uint32_t) * m->poolRecords)) || (rc = m->calls.ensure(sizeof(CallDev))) || (rc = resetMisc(m, m->stream)))
-    return rc;
-  HIPCHK(hipMemcpyAsync(m->desc.p, A->desc, (size_t)32 * A->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->desc2.p, B->desc, (size_t)32 * B->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->kps2.p, B->kps, sizeof(YdKeyPoint) * B->n, hipMemcpyHostToDevice, m->stream));
-  if (nFeatB) HIPCHK(hipMemcpyAsync(m->feat.p, B->fv.feat, sizeof(int) * nFeatB, hipMemcpyHostToDevice, m->stream));
-  if (mode == 4) HIPCHK(hipMemcpyAsync(m->valid.p, B->valid, B->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->qFeat.p, qFeat.data(), sizeof(int) * nq, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->qRange.p, qRange.data(), sizeof(int2) * nq, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->qAngle.p, qAngle.data(), sizeof(float) * nq, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemsetAsync(m->assigned.p, 0xFF, sizeof(int) * std::max(nq, B->n), m->stream));
-  BowCallDev BC{};
-  BC.descA = m->desc.as<uint8_t>(); BC.descB = m->desc2.as<uint8_t>(); BC.qFeat = m->qFeat.as<int>(); BC.qRange = m->qRange.as<int2>();
-  BC.featB = m->feat.as<int>(); BC.validB = mode == 4 ? m->valid.as<uint8_t>() : nullptr; BC.nq = nq; BC.qInfo = m->qInfo.as<int2>();
-  hipLaunchKernelGGL(k_gather_bow, dim3((nq + 3) / 4), dim3(256), 0, m->stream, BC, m->pool.as<uint32_t>(), m->misc.as<unsigned>(),
-                     (unsigned)m->poolRecords, m->misc.as<int>() + 1);
-  CallDev C{};
-  C.frame = 0; C.tkps = m->kps2.as<KeyPointDev>(); C.qAngle = m->qAngle.as<float>(); C.queries = nullptr; C.qdesc = nullptr; C.nqPtr = nullptr;
-  C.nq = nq; C.qInfo = m->qInfo.as<int2>(); C.taken = nullptr; C.assigned = m->assigned.as<int>(); C.matchQ = m->matchQ.as<int>();
-  C.count = m->misc.as<int>() + 2; C.mode = mode; C.ratio = ratio; C.orbDist = 0; C.checkOri = checkOri;
-  HIPCHK(hipMemcpyAsync(m->calls.p, &C, sizeof(CallDev), hipMemcpyHostToDevice, m->stream));
-  const int takenWords = (B->n + 31) / 32;
-  hipLaunchKernelGGL(k_resolve, dim3(1), dim3(64), 2 * sizeof(unsigned) * takenWords, m->stream, m->calls.as<CallDev>(), (const FrameDev*)nullptr,
-                     m->pool.as<uint32_t>(), takenWords);
-  HIPCHK(hipGetLastError());
-  int hmisc[3];
-  std::vector<int> res(std::max(nq, B->n));
-  HIPCHK(hipMemcpyAsync(hmisc, m->misc.p, sizeof(hmisc), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipMemcpyAsync(res.data(), m->assigned.p, sizeof(int) * res.size(), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  if (hmisc[1] != 0) { set_error("bow record pool overflow"); return YDORB_ERR_CAPACITY; }
+  const BowJob J{{A->kps, A->desc, A->n, &A->fv, A->valid, nullptr}, {B->kps, B->desc, B->n, &B->fv, mode == 4 ? B->valid : nullptr, nullptr}, mode, ratio, checkOri, {}};
+  std::vector<int> qFeat, res;
+  const int rc = bowSearch(m, J, qFeat, res, nMatches);
+  if (rc || qFeat.empty()) return rc;
   if (mode == 3) {
     for (int i = 0; i < B->n; i++) out[i] = res[i] >= 0 ? qFeat[res[i]] : -1;
   } else {
-    for (int q = 0; q < nq; q++) out[qFeat[q]] = res[q];
+    for (size_t q = 0; q < qFeat.size(); q++) out[qFeat[q]] = res[q];
   }
-  *nMatches = hmisc[2];
   return YDORB_OK;
 }
 
@@ -479,84 +555,18 @@ int ydorb_search_for_triangulation(ydorb_matcher_t* m, const YdTriSide* A, const
   for (int i = 0; i < B->n; i++)
     if (B->kps[i].octave < 0 || B->kps[i].octave >= nLevels) { set_error("second keyframe: octave %d outside the %d-level tables", B->kps[i].octave, nLevels); return YDORB_ERR_INVALID_ARG; }
   // eligibility (:491-492, :497-500) is static: no map point yet, and a good stereo coordinate when only stereo points are wanted
-  std::vector<uint8_t> goodA(A->n), goodB(B->n), validB(B->n);
-  for (int i = 0; i < A->n; i++) goodA[i] = A->right_x[i] >= 0;
+  std::vector<uint8_t> goodA(A->n), goodB(B->n), eligibleA(A->n), validB(B->n);
+  for (int i = 0; i < A->n; i++) { goodA[i] = A->right_x[i] >= 0; eligibleA[i] = !A->has_map_point[i] && (!stereoOnly || goodA[i]); }
   for (int i = 0; i < B->n; i++) { goodB[i] = B->right_x[i] >= 0; validB[i] = !B->has_map_point[i] && (!stereoOnly || goodB[i]); }
-  std::vector<int> qFeat;
-  std::vector<int2> qRange;
-  std::vector<float> qAngle;
-  size_t records = 0;
-  {
-    int a = 0, b = 0;
-    const YdFeatureVector &fa = A->fv, &fb = B->fv;
-    while (a < fa.n_nodes && b < fb.n_nodes) {   // merge-join of the two ascending node id lists (:484-541)
-      if (fa.node_ids[a] == fb.node_ids[b]) {
-        for (int ia = fa.node_start[a]; ia < fa.node_start[a + 1]; ia++) {
-          const int i1 = fa.feat[ia];
-          if (A->has_map_point[i1] || (stereoOnly && !goodA[i1])) continue;
-          qFeat.push_back(i1);
-          qRange.push_back(make_int2(fb.node_start[b], fb.node_start[b + 1]));
-          qAngle.push_back(A->kps[i1].angle);
-          records += (size_t)(fb.node_start[b + 1] - fb.node_start[b]);
-        }
-        a++; b++;
-      } else if (fa.node_ids[a] < fb.node_ids[b]) {
-        a = (int)(std::lower_bound(fa.node_ids, fa.node_ids + fa.n_nodes, fb.node_ids[b]) - fa.node_ids);
-      } else {
-        b = (int)(std::lower_bound(fb.node_ids, fb.node_ids + fb.n_nodes, fa.node_ids[a]) - fb.node_ids);
-      }
-    }
-  }
-  const int nq = (int)qFeat.size();
-  if (nq == 0) return YDORB_OK;
-  const int nFeatB = B->fv.node_start[B->fv.n_nodes];
-  m->poolRecords = std::max<size_t>(m->poolRecords, records + 1024);
-  int rc;
-  if ((rc = m->desc.ensure((size_t)32 * A->n)) || (rc = m->desc2.ensure((size_t)32 * B->n)) || (rc = m->kps2.ensure(sizeof(YdKeyPoint) * B->n)) ||
-      (rc = m->kps1.ensure(sizeof(YdKeyPoint) * A->n)) || (rc = m->good1.ensure(A->n)) || (rc = m->good2.ensure(B->n)) ||
-      (rc = m->feat.ensure(sizeof(int) * std::max(nFeatB, 1))) || (rc = m->valid.ensure(B->n)) || (rc = m->qFeat.ensure(sizeof(int) * nq)) ||
-      (rc = m->qRange.ensure(sizeof(int2) * nq)) || (rc = m->qAngle.ensure(sizeof(float) * nq)) || (rc = m->qInfo.ensure(sizeof(int2) * nq)) ||
-      (rc = m->matchQ.ensure(sizeof(int) * nq)) || (rc = m->assigned.ensure(sizeof(int) * std::max(nq, B->n))) ||
-      (rc = m->pool.ensure(sizeof(uint32_t) * m->poolRecords)) || (rc = m->calls.ensure(sizeof(CallDev))) || (rc = resetMisc(m, m->stream)))
-    return rc;
-  HIPCHK(hipMemcpyAsync(m->desc.p, A->desc, (size_t)32 * A->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->desc2.p, B->desc, (size_t)32 * B->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->kps1.p, A->kps, sizeof(YdKeyPoint) * A->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->kps2.p, B->kps, sizeof(YdKeyPoint) * B->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->good1.p, goodA.data(), A->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->good2.p, goodB.data(), B->n, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->valid.p, validB.data(), B->n, hipMemcpyHostToDevice, m->stream));
-  if (nFeatB) HIPCHK(hipMemcpyAsync(m->feat.p, B->fv.feat, sizeof(int) * nFeatB, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->qFeat.p, qFeat.data(), sizeof(int) * nq, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->qRange.p, qRange.data(), sizeof(int2) * nq, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemcpyAsync(m->qAngle.p, qAngle.data(), sizeof(float) * nq, hipMemcpyHostToDevice, m->stream));
-  HIPCHK(hipMemsetAsync(m->assigned.p, 0xFF, sizeof(int) * std::max(nq, B->n), m->stream));
-  BowCallDev BC{};
-  BC.descA = m->desc.as<uint8_t>(); BC.descB = m->desc2.as<uint8_t>(); BC.qFeat = m->qFeat.as<int>(); BC.qRange = m->qRange.as<int2>();
-  BC.featB = m->feat.as<int>(); BC.validB = m->valid.as<uint8_t>(); BC.nq = nq; BC.qInfo = m->qInfo.as<int2>();
-  BC.tri = 1; BC.kpsA = m->kps1.as<KeyPointDev>(); BC.kpsB = m->kps2.as<KeyPointDev>(); BC.goodA = m->good1.as<uint8_t>(); BC.goodB = m->good2.as<uint8_t>();
-  for (int i = 0; i < 9; i++) BC.F[i] = F[i];
-  BC.ex = ex; BC.ey = ey;
-  for (int i = 0; i < 8; i++) { BC.sfB[i] = i < nLevels ? sfB[i] : 0.f; BC.sf2B[i] = i < nLevels ? sf2B[i] : 0.f; }
-  hipLaunchKernelGGL(k_gather_bow, dim3((nq + 3) / 4), dim3(256), 0, m->stream, BC, m->pool.as<uint32_t>(), m->misc.as<unsigned>(),
-                     (unsigned)m->poolRecords, m->misc.as<int>() + 1);
-  CallDev C{};
-  C.frame = 0; C.tkps = m->kps2.as<KeyPointDev>(); C.qAngle = m->qAngle.as<float>(); C.queries = nullptr; C.qdesc = nullptr; C.nqPtr = nullptr;
-  C.nq = nq; C.qInfo = m->qInfo.as<int2>(); C.taken = nullptr; C.assigned = m->assigned.as<int>(); C.matchQ = m->matchQ.as<int>();
-  C.count = m->misc.as<int>() + 2; C.mode = 5; C.ratio = 0.f; C.orbDist = 0; C.checkOri = checkOri;
-  HIPCHK(hipMemcpyAsync(m->calls.p, &C, sizeof(CallDev), hipMemcpyHostToDevice, m->stream));
-  const int takenWords = (B->n + 31) / 32;
-  hipLaunchKernelGGL(k_resolve, dim3(1), dim3(64), 2 * sizeof(unsigned) * takenWords, m->stream, m->calls.as<CallDev>(), (const FrameDev*)nullptr,
-                     m->pool.as<uint32_t>(), takenWords);
-  HIPCHK(hipGetLastError());
-  int hmisc[3];
-  std::vector<int> res(std::max(nq, B->n));
-  HIPCHK(hipMemcpyAsync(hmisc, m->misc.p, sizeof(hmisc), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipMemcpyAsync(res.data(), m->assigned.p, sizeof(int) * res.size(), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  if (hmisc[1] != 0) { set_error("bow record pool overflow"); return YDORB_ERR_CAPACITY; }
-  for (int q = 0; q < nq; q++) out[qFeat[q]] = res[q];
-  *nMatches = hmisc[2];
+  BowJob J{{A->kps, A->desc, A->n, &A->fv, eligibleA.data(), goodA.data()}, {B->kps, B->desc, B->n, &B->fv, validB.data(), goodB.data()}, 5, 0.f, checkOri, {}};
+  J.geom.tri = 1;
+  for (int i = 0; i < 9; i++) J.geom.F[i] = F[i];
+  J.geom.ex = ex; J.geom.ey = ey;
+  for (int i = 0; i < 8; i++) { J.geom.sfB[i] = i < nLevels ? sfB[i] : 0.f; J.geom.sf2B[i] = i < nLevels ? sf2B[i] : 0.f; }
+  std::vector<int> qFeat, res;
+  const int rc = bowSearch(m, J, qFeat, res, nMatches);
+  if (rc) return rc;
+  for (size_t q = 0; q < qFeat.size(); q++) out[qFeat[q]] = res[q];
   return YDORB_OK;
 }
 
@@ -585,9 +595,8 @@ int ydorb_stereo_matches(ydorb_matcher_t* m, const YdStereoSide* L, const YdSter
   const bool dev = flags & YDORB_STEREO_DEVICE_POINTERS;
   hipStream_t s = stream ? (hipStream_t)stream : m->stream;
   const size_t nl = (size_t)nPairs * L->cap, nr = (size_t)nPairs * R->cap;
-  if ((rc = m->stereoPar.ensure(sizeof(StereoDev))) || (rc = m->stereoCnt.ensure(sizeof(int) * 4 * nPairs)) ||
-      (rc = m->stereoOut.ensure(sizeof(int) * 2 * nPairs)))
-    return rc;
+  StereoPtrs sp;
+  if ((rc = layOut(m->stereo, [&](void* base) { return layStereo(nPairs, dev ? 0 : nl, dev ? 0 : nr, base, sp); }))) return rc;
   StereoDev P{};
   if (dev) {
     P.kpsL = reinterpret_cast<const KeyPointDev*>(L->kps); P.descL = L->desc; P.nL = L->n;
@@ -597,18 +606,15 @@ int ydorb_stereo_matches(ydorb_matcher_t* m, const YdStereoSide* L, const YdSter
     // the pyramids must be complete before the kernels read them from another stream
     HIPCHK(hipStreamSynchronize((hipStream_t)vl.stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)vr.stream));
-    if ((rc = m->kps1.ensure(sizeof(YdKeyPoint) * nl)) || (rc = m->desc.ensure(32 * nl)) || (rc = m->kps2.ensure(sizeof(YdKeyPoint) * nr)) ||
-        (rc = m->desc2.ensure(32 * nr)) || (rc = m->qRange.ensure(sizeof(int) * 2 * nPairs)) || (rc = m->rightX.ensure(sizeof(float) * 2 * nl)))
-      return rc;
-    HIPCHK(hipMemcpyAsync(m->kps1.p, L->kps, sizeof(YdKeyPoint) * nl, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->desc.p, L->desc, 32 * nl, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->kps2.p, R->kps, sizeof(YdKeyPoint) * nr, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->desc2.p, R->desc, 32 * nr, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->qRange.p, L->n, sizeof(int) * nPairs, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->qRange.as<int>() + nPairs, R->n, sizeof(int) * nPairs, hipMemcpyHostToDevice, s));
-    P.kpsL = m->kps1.as<KeyPointDev>(); P.descL = m->desc.as<uint8_t>(); P.nL = m->qRange.as<int>();
-    P.kpsR = m->kps2.as<KeyPointDev>(); P.descR = m->desc2.as<uint8_t>(); P.nR = m->qRange.as<int>() + nPairs;
-    P.rightX = m->rightX.as<float>(); P.depth = m->rightX.as<float>() + nl;
+    HIPCHK(hipMemcpyAsync(sp.kpsL, L->kps, sizeof(YdKeyPoint) * nl, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sp.descL, L->desc, 32 * nl, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sp.kpsR, R->kps, sizeof(YdKeyPoint) * nr, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sp.descR, R->desc, 32 * nr, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sp.nL, L->n, sizeof(int) * nPairs, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sp.nR, R->n, sizeof(int) * nPairs, hipMemcpyHostToDevice, s));
+    P.kpsL = sp.kpsL; P.descL = sp.descL; P.nL = sp.nL;
+    P.kpsR = sp.kpsR; P.descR = sp.descR; P.nR = sp.nR;
+    P.rightX = sp.rightX; P.depth = sp.depth;
   }
   for (int l = 0; l < vl.nLevels; l++) {
     P.pyrL[l] = vl.roi[l]; P.pyrR[l] = vr.roi[l];
@@ -618,7 +624,7 @@ int ydorb_stereo_matches(ydorb_matcher_t* m, const YdStereoSide* L, const YdSter
   P.frameStrideL = vl.frameStride; P.frameStrideR = vr.frameStride;
   P.capL = L->cap; P.capR = R->cap; P.frameL0 = L->first_frame; P.frameLStep = L->frame_step; P.frameR0 = R->first_frame; P.frameRStep = R->frame_step;
   P.nLevels = vl.nLevels; P.flags = flags; P.bf = bf; P.maxD = bf / b;   // :382
-  P.counters = m->stereoCnt.as<int>(); P.keptOut = m->stereoOut.as<int>(); P.statusOut = m->stereoOut.as<int>() + nPairs;
+  P.counters = sp.counters; P.keptOut = sp.kept; P.statusOut = sp.status;
   // replay form: the right-keypoint table (8 bytes each) + the index sorted by first band row (row starts, fill cursors, 2 bytes per keypoint)
   size_t ldsReplay = (size_t)R->cap * 8;
   {
@@ -628,7 +634,7 @@ int ydorb_stereo_matches(ydorb_matcher_t* m, const YdStereoSide* L, const YdSter
   }
   // P travels as a kernel argument: an asynchronous copy out of pageable host memory makes the host wait for everything queued on
   // the stream before it - here the extraction the association waits for - and a caller that pipelines steps would run in lock step
-  HIPCHK(hipMemsetAsync(m->stereoCnt.p, 0, sizeof(int) * 4 * nPairs, s));
+  HIPCHK(hipMemsetAsync(sp.counters, 0, sizeof(int) * 4 * nPairs, s));
   HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.rightX), 0xBF800000u, nl, s));   // -1.0f, :363-364
   HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.depth), 0xBF800000u, nl, s));
   const size_t lds = (size_t)R->cap * 8;
@@ -685,77 +691,74 @@ int ydorb_match_pairs_device(ydorb_matcher_t* m, const YdFrameSetDev* Q, const Y
     const int tf = pairs[2 * c + 1];
     if (tmap[tf] < 0) { tmap[tf] = (int)tused.size(); tused.push_back(tf); }
   }
+  auto& B = m->batch;
   const int cap = Q->cap, nFrames = (int)tused.size();
-  const size_t poolPerCall = (size_t)cap * kSlot + (size_t)cap * m->ovfPerKeypoint;  // fixed slots + overflow region (records of queries with > kSlot candidates)
-  int rc;
-  if ((rc = m->queries.ensure(sizeof(QueryDev) * (size_t)cap * nCalls)) || (rc = m->taken.ensure((size_t)cap * nCalls)) ||
-      (rc = m->matchQ.ensure(sizeof(int) * (size_t)cap * nCalls)) || (rc = m->qInfo.ensure(sizeof(int2) * (size_t)cap * nCalls)) ||
-      (rc = m->qPre.ensure(sizeof(uint2) * (size_t)cap * nCalls)) ||
-      (rc = m->cellStart.ensure(sizeof(int) * (size_t)(kGridCells + 1) * nFrames)) || (rc = m->cellIdx.ensure(sizeof(int) * (size_t)cap * nFrames)) ||
-      (rc = m->pool.ensure(sizeof(uint32_t) * poolPerCall * nCalls)) || (rc = m->frames.ensure(sizeof(FrameDev) * nFrames)) ||
-      (rc = m->calls.ensure(sizeof(CallDev) * nCalls)) || (rc = m->sf.ensure(sizeof(float) * 8 + sizeof(float) * 6 * nCalls)) || (rc = m->misc.ensure(64)) ||
-      (rc = m->heads.ensure(sizeof(unsigned) * nCalls)) || (rc = m->sortedKp.ensure(sizeof(float4) * (size_t)cap * nFrames)) ||
-      (rc = m->sortedDesc.ensure((size_t)32 * cap * nFrames)))
-    return rc;
+  const size_t poolPerCall = (size_t)cap * kSlot + (size_t)cap * B.ovfPerKeypoint;  // fixed slots + overflow region (records of queries with > kSlot candidates)
+  BatchPtrs p;
+  const size_t had = B.arena.cap;
+  const int rc = layOut(B.arena, [&](void* base) { return layBatch(cap, nCalls, nFrames, poolPerCall, base, p); });
+  if (B.arena.cap != had) B.hFrames.clear();
+  if (rc) return rc;
   std::vector<FrameDev> hf(nFrames);
   std::vector<CallDev> hc(nCalls);
   const float minX = 0.f, minY = 0.f, maxX = (float)width, maxY = (float)height;  // Frame::computeImageBounds without distortion
   for (int f = 0; f < nFrames; f++) {
     const int tf = tused[f];
-    FrameDev F{};
+    FrameDev& F = hf[f];
     F.kps = reinterpret_cast<const KeyPointDev*>(T->d_kps) + (size_t)tf * cap; F.desc = T->d_desc + (size_t)tf * cap * 32; F.rightX = nullptr;
     F.nPtr = T->d_n + tf; F.n = 0; F.minX = minX; F.minY = minY;
     F.gridWInv = static_cast<float>(kGridCols) / (maxX - minX); F.gridHInv = static_cast<float>(kGridRows) / (maxY - minY);
-    F.cellStart = m->cellStart.as<int>() + (size_t)f * (kGridCells + 1); F.cellIdx = m->cellIdx.as<int>() + (size_t)f * cap;
-    F.sortedKp = m->sortedKp.as<float4>() + (size_t)f * cap; F.sortedDesc = m->sortedDesc.as<uint8_t>() + (size_t)f * cap * 32;
-    hf[f] = F;
+    F.cellStart = p.cellStart + (size_t)f * (kGridCells + 1); F.cellIdx = p.cellIdx + (size_t)f * cap;
+    F.sortedKp = p.sortedKp + (size_t)f * cap; F.sortedDesc = p.sortedDesc + (size_t)f * cap * 32;
   }
   for (int c = 0; c < nCalls; c++) {
     const int qf = pairs[2 * c], tf = tmap[pairs[2 * c + 1]];
-    CallDev C{};
-    C.frame = tf; C.tkps = hf[tf].kps; C.qAngle = nullptr; C.queries = m->queries.as<QueryDev>() + (size_t)c * cap;
+    CallDev& C = hc[c];
+    C.frame = tf; C.tkps = hf[tf].kps; C.qAngle = nullptr; C.queries = p.queries + (size_t)c * cap;
     C.qkps = reinterpret_cast<const KeyPointDev*>(Q->d_kps) + (size_t)qf * cap;
-    C.qdesc = Q->d_desc + (size_t)qf * cap * 32; C.nqPtr = Q->d_n + qf; C.nq = 0; C.qInfo = m->qInfo.as<int2>() + (size_t)c * cap;
-    C.qPre = m->qPre.as<uint2>() + (size_t)c * cap; C.takenClear = 1;
-    C.taken = m->taken.as<uint8_t>() + (size_t)c * cap; C.assigned = d_assigned + (size_t)c * cap; C.matchQ = m->matchQ.as<int>() + (size_t)c * cap;
+    C.qdesc = Q->d_desc + (size_t)qf * cap * 32; C.nqPtr = Q->d_n + qf; C.nq = 0; C.qInfo = p.qInfo + (size_t)c * cap;
+    C.qPre = p.qPre + (size_t)c * cap; C.takenClear = 1;
+    C.taken = p.taken + (size_t)c * cap; C.assigned = d_assigned + (size_t)c * cap; C.matchQ = p.matchQ + (size_t)c * cap;
     C.count = d_counts + c; C.mode = 1; C.ratio = 0.9f; C.orbDist = 0; C.checkOri = checkOri;
-    hc[c] = C;
   }
   float hsf[8] = {0};
   for (int l = 0; l < nLevels; l++) hsf[l] = scaleFactors[l];
-  const bool same = m->hFrames.size() == hf.size() && m->hCalls.size() == hc.size() && !memcmp(m->hFrames.data(), hf.data(), sizeof(FrameDev) * hf.size()) &&
-                    !memcmp(m->hCalls.data(), hc.data(), sizeof(CallDev) * hc.size()) && !memcmp(m->hSf, hsf, sizeof(hsf)) && m->hIdentAffine == !d_affine;
+  const bool same = p.frames == B.at.frames && p.calls == B.at.calls && p.sf == B.at.sf && p.ident == B.at.ident &&
+                    B.hFrames.size() == hf.size() && B.hCalls.size() == hc.size() && !memcmp(B.hFrames.data(), hf.data(), sizeof(FrameDev) * hf.size()) &&
+                    !memcmp(B.hCalls.data(), hc.data(), sizeof(CallDev) * hc.size()) && !memcmp(B.hSf, hsf, sizeof(hsf)) && B.hIdentAffine == !d_affine;
   if (!same) {
     HIPCHK(hipStreamSynchronize(s));
-    m->hFrames = hf;
-    m->hCalls = hc;
-    memcpy(m->hSf, hsf, sizeof(hsf));
-    m->hIdentAffine = !d_affine;
-    HIPCHK(hipMemcpy(m->frames.p, m->hFrames.data(), sizeof(FrameDev) * nFrames, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m->calls.p, m->hCalls.data(), sizeof(CallDev) * nCalls, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m->sf.p, hsf, sizeof(hsf), hipMemcpyHostToDevice));
+    B.hFrames.clear();   // nothing is cached until all four copies are through
+    HIPCHK(hipMemcpy(p.frames, hf.data(), sizeof(FrameDev) * nFrames, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p.calls, hc.data(), sizeof(CallDev) * nCalls, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p.sf, hsf, sizeof(hsf), hipMemcpyHostToDevice));
     if (!d_affine) {
       std::vector<float> ident((size_t)6 * nCalls, 0.f);
       for (int c = 0; c < nCalls; c++) { ident[6 * c] = 1.f; ident[6 * c + 4] = 1.f; }
-      HIPCHK(hipMemcpy(m->sf.as<float>() + 8, ident.data(), sizeof(float) * ident.size(), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(p.ident, ident.data(), sizeof(float) * ident.size(), hipMemcpyHostToDevice));
     }
+    B.hFrames.swap(hf);
+    B.hCalls.swap(hc);
+    memcpy(B.hSf, hsf, sizeof(hsf));
+    B.hIdentAffine = !d_affine;
+    B.at = p;
   }
-  const float* aff = d_affine ? d_affine : m->sf.as<float>() + 8;
+  const float* aff = d_affine ? d_affine : p.ident;
   const bool prof = m->profiling;
   collect(m);
-  // per-call pool heads, taken flags and the all -1 assignment are written by k_queries_from_keypoints (the overflow status, misc[1], is
-  // sticky until synchronize reads it)
+  // per-call pool heads, taken flags and the all -1 assignment are written by k_queries_from_keypoints (the overflow status, word [1] of
+  // the batch status, is sticky until synchronize reads it)
+  int* const ovf = B.status.as<int>() + 1;
   if (prof) HIPCHK(hipEventRecord(m->ev[0], s));
-  hipLaunchKernelGGL(k_queries_from_keypoints, dim3((cap + 255) / 256, nCalls), dim3(256), 0, s, m->calls.as<CallDev>(), cap, aff, th, m->sf.as<float>(),
-                     nLevels, minX, maxX, minY, maxY, m->heads.as<unsigned>());
-  { const int rcg = launchGridBuild(nFrames, cap, s, m->frames.as<FrameDev>()); if (rcg) return rcg; }
+  hipLaunchKernelGGL(k_queries_from_keypoints, dim3((cap + 255) / 256, nCalls), dim3(256), 0, s, p.calls, cap, aff, th, p.sf, nLevels, minX, maxX, minY, maxY,
+                     p.heads);
+  { const int rcg = launchGridBuild(nFrames, cap, s, p.frames); if (rcg) return rcg; }
   if (prof) HIPCHK(hipEventRecord(m->ev[1], s));
-  hipLaunchKernelGGL(k_gather_projection, dim3((cap + 4 * kGatherQpw - 1) / (4 * kGatherQpw), nCalls), dim3(256), 0, s, m->calls.as<CallDev>(), m->frames.as<FrameDev>(), cap,
-                     m->pool.as<uint32_t>(), m->heads.as<unsigned>(), (unsigned)poolPerCall, m->misc.as<int>() + 1);
+  hipLaunchKernelGGL(k_gather_projection, dim3((cap + 4 * kGatherQpw - 1) / (4 * kGatherQpw), nCalls), dim3(256), 0, s, p.calls, p.frames, cap, p.pool, p.heads,
+                     (unsigned)poolPerCall, ovf);
   if (prof) HIPCHK(hipEventRecord(m->ev[2], s));
   const int takenWords = (cap + 31) / 32;
-  hipLaunchKernelGGL(k_resolve, dim3(nCalls), dim3(64), 2 * sizeof(unsigned) * takenWords, s, m->calls.as<CallDev>(), m->frames.as<FrameDev>(),
-                     m->pool.as<uint32_t>(), takenWords);
+  hipLaunchKernelGGL(k_resolve, dim3(nCalls), dim3(64), 2 * sizeof(unsigned) * takenWords, s, p.calls, p.frames, p.pool, takenWords);
   if (prof) { HIPCHK(hipEventRecord(m->ev[3], s)); m->evPending = true; }
   HIPCHK(hipGetLastError());
   return YDORB_OK;
@@ -766,11 +769,9 @@ int ydorb_match_consecutive_device(ydorb_matcher_t* m, const YdKeyPoint* d_kps, 
                                    const float* d_affine, int32_t checkOri, int32_t* d_assigned, int32_t* d_counts, void* stream) {
   if (!m || nFrames < 2) { set_error("invalid argument"); return YDORB_ERR_INVALID_ARG; }
   const YdFrameSetDev S{d_kps, d_desc, d_n, nFrames, cap};
-  if ((int)m->consecPairs.size() != 2 * (nFrames - 1)) {
-    m->consecPairs.resize((size_t)2 * (nFrames - 1));
-    for (int c = 0; c < nFrames - 1; c++) { m->consecPairs[2 * c] = c; m->consecPairs[2 * c + 1] = c + 1; }
-  }
-  return ydorb_match_pairs_device(m, &S, &S, m->consecPairs.data(), nFrames - 1, width, height, th, scaleFactors, nLevels, d_affine, checkOri, d_assigned,
+  std::vector<int32_t> pairs((size_t)2 * (nFrames - 1));
+  for (int c = 0; c < nFrames - 1; c++) { pairs[2 * c] = c; pairs[2 * c + 1] = c + 1; }
+  return ydorb_match_pairs_device(m, &S, &S, pairs.data(), nFrames - 1, width, height, th, scaleFactors, nLevels, d_affine, checkOri, d_assigned,
                                   d_counts, stream);
 }
 
@@ -795,19 +796,17 @@ int ydorb_hamming_topk(ydorb_matcher_t* m, const uint8_t* q, int32_t nq, const u
     nCand = (size_t)candOffsets[nq];
   }
   hipStream_t s = m->stream;
-  if ((rc = m->qdesc.ensure((size_t)32 * nq)) || (rc = m->desc.ensure((size_t)32 * std::max(nt, 1))) || (rc = m->pool.ensure(sizeof(TopkOut) * (size_t)nq)) ||
-      (rc = m->cellStart.ensure(sizeof(int) * ((size_t)nq + 1))) || (rc = m->cellIdx.ensure(sizeof(int) * std::max<size_t>(nCand, 1))))
-    return rc;
-  HIPCHK(hipMemcpyAsync(m->qdesc.p, q, (size_t)32 * nq, hipMemcpyHostToDevice, s));
-  if (nt) HIPCHK(hipMemcpyAsync(m->desc.p, t, (size_t)32 * nt, hipMemcpyHostToDevice, s));
+  RowsPtrs r;
+  if ((rc = layOut(m->call, [&](void* base) { return layRows(nq, std::max(nt, 1), (size_t)nq + 1, std::max<size_t>(nCand, 1), 0, nq, base, r); }))) return rc;
+  HIPCHK(hipMemcpyAsync(r.a, q, (size_t)32 * nq, hipMemcpyHostToDevice, s));
+  if (nt) HIPCHK(hipMemcpyAsync(r.b, t, (size_t)32 * nt, hipMemcpyHostToDevice, s));
   if (candOffsets) {
-    HIPCHK(hipMemcpyAsync(m->cellStart.p, candOffsets, sizeof(int) * ((size_t)nq + 1), hipMemcpyHostToDevice, s));
-    if (nCand) HIPCHK(hipMemcpyAsync(m->cellIdx.p, candIdx, sizeof(int) * nCand, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(r.offsets, candOffsets, sizeof(int) * ((size_t)nq + 1), hipMemcpyHostToDevice, s));
+    if (nCand) HIPCHK(hipMemcpyAsync(r.idx, candIdx, sizeof(int) * nCand, hipMemcpyHostToDevice, s));
   }
-  hipLaunchKernelGGL(k_topk_csr, dim3((nq + 3) / 4), dim3(256), 0, s, m->qdesc.as<uint8_t>(), nq, m->desc.as<uint8_t>(), nt,
-                     candOffsets ? m->cellStart.as<int>() : nullptr, candOffsets ? m->cellIdx.as<int>() : nullptr, m->pool.as<TopkOut>());
+  hipLaunchKernelGGL(k_topk_csr, dim3((nq + 3) / 4), dim3(256), 0, s, r.a, nq, r.b, nt, candOffsets ? r.offsets : nullptr, candOffsets ? r.idx : nullptr, r.top);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, m->pool.p, sizeof(TopkOut) * (size_t)nq, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(out, r.top, sizeof(TopkOut) * (size_t)nq, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return YDORB_OK;
 }
@@ -830,14 +829,14 @@ int ydorb_matcher_synchronize(ydorb_matcher_t* m) {
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipDeviceSynchronize());
   collect(m);
-  if (m->misc.p) {
+  if (Mem& st = m->batch.status; st.p) {
     int hmisc[2];
-    HIPCHK(hipMemcpy(hmisc, m->misc.p, sizeof(hmisc), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hmisc, st.p, sizeof(hmisc), hipMemcpyDeviceToHost));
     if (hmisc[1] != 0) {
-      (void)hipMemset(m->misc.p, 0, 8);
-      m->ovfPerKeypoint *= 4;   // the next batched call gets a larger overflow region
+      (void)hipMemset(st.p, 0, 8);
+      m->batch.ovfPerKeypoint *= 4;   // the next batched call gets a larger overflow region
       set_error("candidate record pool overflow in the batched search: results of that call are incomplete; the overflow region is now %d records per keypoint, call again",
-                m->ovfPerKeypoint);
+                m->batch.ovfPerKeypoint);
       return YDORB_ERR_CAPACITY;
     }
   }
