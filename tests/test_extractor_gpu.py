@@ -317,3 +317,78 @@ def test_batched_handle_paths_match_the_oracle(oracle_lib, w, h, nf, single):
         ck, cd = OrbExtractorOracle(nf, 1.2, 8, 20, 7).extract(img)
         _same_kps(res[f][0], ck)
         assert np.array_equal(res[f][1], cd)
+
+
+def _reference(cfg, img):
+    """(keypoints, descriptors, [padded level, cut to w + 38 columns]) of the oracle for one frame."""
+    from oracle.orb_oracle import OrbExtractorOracle
+    cpu = OrbExtractorOracle(*cfg, 7)
+    ck, cd = cpu.extract(img)
+    return ck, cd, [cpu.level_padded(l)[:, :cpu.level_dims(l)[0] + 38] for l in range(cfg[2])]
+
+
+def _equals_reference(gpu, res, refs):
+    """Every frame of the handle's last call: keypoints, descriptors and every byte of every padded pyramid level."""
+    assert len(res) == len(refs)
+    for f, ((gk, gd), (ck, cd, levels)) in enumerate(zip(res, refs)):
+        _same_kps(gk, ck)
+        assert np.array_equal(gd, cd), "descriptors, frame %d" % f
+        for l, ref in enumerate(levels):
+            assert np.array_equal(gpu.read_level(l, f), ref), "frame %d pyramid level %d" % (f, l)
+
+
+@pytest.mark.parametrize("cfg,steps", [
+    # the batch outgrows max_batch (a re-plan at the same size), then a size change, then back
+    ((300, 1.2, 8, 20), [(131, 97, 1), (131, 97, 3), (259, 203, 1), (131, 97, 1)]),
+    # the pass kernel's node tables lie in HBM here (test_other_pyramid_configurations): a non-empty nodeScratch, empty above
+    ((4000, 1.5, 2, 12), [(661, 370, 1), (640, 480, 1), (661, 370, 1)]),
+], ids=["default-pyramid", "hbm-node-tables"])
+def test_replan_on_one_handle(oracle_lib, cfg, steps):
+    """Every call here re-plans: the handle drops all its memory and lays it out afresh for the new size or batch.  Each step must give
+    the oracle's keypoints, descriptors and padded levels, and the last one what the first gave, byte for byte."""
+    import ydorbslam_amd as y
+    gpu = y.OrbExtractor(*cfg, 7, max_batch=1)
+    refs, results = {}, []
+    for (w, h, n) in steps:
+        imgs = [synth_frame(w, h, 70 + i) for i in range(n)]
+        res = gpu.extract_batch(np.stack(imgs)) if n > 1 else [gpu.extract(imgs[0])]
+        for i, img in enumerate(imgs):
+            if (w, h, i) not in refs:
+                refs[(w, h, i)] = _reference(cfg, img)
+        _equals_reference(gpu, res, [refs[(w, h, i)] for i in range(n)])
+        results.append(res)
+    assert steps[0] == steps[-1]
+    for a, b in zip(results[0][0], results[-1][0]):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_host_call_after_device_calls(oracle_lib):
+    """A handle driven through ydorb_extract_batch_device holds no host staging.  The first host call adds it beside a plan and a
+    pyramid that exist already: it must disturb neither, and the device path must go on giving the same bytes."""
+    import torch
+    import ydorbslam_amd as y
+    cfg = (400, 1.2, 8, 20)
+    w, h, n = 259, 203, 3
+    imgs = np.stack([synth_frame(w, h, 80 + i) for i in range(n)])
+    refs = [_reference(cfg, img) for img in imgs]
+    gpu = y.OrbExtractor(*cfg, 7, max_batch=n)
+    cap = gpu.max_keypoints
+    dev = torch.device("cuda", 0)
+    d_img = torch.from_numpy(imgs).to(dev)
+
+    def device_call():
+        d_kps = torch.zeros((n, cap, 7), dtype=torch.int32, device=dev)
+        d_desc = torch.zeros((n, cap, 32), dtype=torch.uint8, device=dev)
+        d_n = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        gpu.extract_batch_device(d_img.data_ptr(), w, h, w, w * h, n, d_kps.data_ptr(), d_desc.data_ptr(), cap, d_n.data_ptr())
+        gpu.synchronize()
+        cnt, kps, desc = d_n.cpu().numpy(), d_kps.cpu().numpy(), d_desc.cpu().numpy()
+        return [(np.ascontiguousarray(kps[f, :cnt[f]]).view(y.KP_DTYPE).reshape(-1), desc[f, :cnt[f]]) for f in range(n)]
+
+    first = device_call()
+    _equals_reference(gpu, first, refs)
+    _equals_reference(gpu, gpu.extract_batch(imgs), refs)
+    second = device_call()
+    for (k1, d1), (k2, d2) in zip(first, second):
+        assert k1.tobytes() == k2.tobytes() and d1.tobytes() == d2.tobytes()

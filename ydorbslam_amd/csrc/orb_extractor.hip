@@ -52,6 +52,48 @@ struct HostPlan {
 enum Stage { ST_PYR = 0, ST_FAST, ST_QT, ST_BLUR, ST_DESC, ST_COUNT };
 const char* kStageNames[ST_COUNT] = {"pyramid", "fast_cells", "blur", "quadtree_after_blur", "orient_describe"};
 
+// Device and pinned memory: one exactly sized arena per lifetime, laid out once per plan (Carve, host_buffers.h).  An array of zero
+// elements takes no room and shares its address with the next one; nothing reads it.
+// `tables`: what buildPlan() computed for the kernels.  The same layout over a host block is the upload's source.
+struct TablePtrs { CellDev* cells; int* tabInt; short* tabShort; PyrPadEntry* padTab; PyrColEntry* colTab; int2* rowTab; };
+size_t layTables(const HostPlan& P, void* base, TablePtrs& t) {
+  Carve a(base);
+  a.take(t.cells, P.cells.size()); a.take(t.tabInt, P.tabInt.size()); a.take(t.tabShort, P.tabShort.size());
+  a.take(t.padTab, P.padTab.size()); a.take(t.colTab, P.colTab.size()); a.take(t.rowTab, P.rowTab.size());
+  return a.L.bytes;
+}
+
+// `work`: what the kernels of a call of up to B frames read and write.  pyr is cleared whole (its pitch slack beyond w + 38 is never
+// written); needPass .. passList[0] must read zero before the first call and lie together so that one memset clears them.
+//   nodeScratch: HBM node tables of the levels whose quota does not fit the LDS (usually none)
+//   needPass [frame][level]: 1 = k_qt_fast left the unit to the pass kernel
+//   lvlMaxN: largest candidate count seen per level (device max) + [kMaxLevels] the last hand-over list length
+//   passList [1 + frames * levels]: count, then the units k_qt_fast handed over in this call
+struct WorkPtrs {
+  uint8_t *pyr, *blur; uint32_t *cellCount, *cellCand, *qtCand; uint16_t* qtNode; uint8_t* nodeScratch; uint32_t* lvlKp; float* lvlAngle; int* lvlCount;
+  uint8_t* needPass; int *lvlMaxN, *status, *passList;
+};
+size_t layWork(const HostPlan& P, size_t B, void* base, WorkPtrs& w) {
+  const PlanDev& D = P.dev;
+  Carve a(base);
+  a.take(w.pyr, P.pyrFrameStride * B); a.take(w.blur, P.blurFrameStride * B);
+  a.take(w.cellCount, D.nCellsTotal * B); a.take(w.cellCand, (size_t)D.nCellsTotal * D.cellCap * B);
+  a.take(w.qtCand, 2 * P.qtFrameStride * B); a.take(w.qtNode, 2 * P.qtFrameStride * B); a.take(w.nodeScratch, D.nodeTabFrameStride * B);
+  a.take(w.lvlKp, D.sumQuota * B); a.take(w.lvlAngle, D.sumQuota * B); a.take(w.lvlCount, kMaxLevels * B);
+  a.take(w.needPass, kMaxLevels * B); a.take(w.lvlMaxN, kMaxLevels + 1); a.take(w.status, 1); a.take(w.passList, kMaxLevels * B + 1);
+  return a.L.bytes;
+}
+
+// `io` / `hIo`: staging of the host entry point (ydorb_extract_batch), B frames of imgBytes and Q keypoint slots each; the same layout
+// serves the device arena (kps as YdKeyPointDev) and its pinned twin
+struct IoPtrs { uint8_t* img; YdKeyPoint* kps; uint8_t* desc; int* nOut; };
+size_t layIo(size_t imgBytes, size_t Q, size_t B, void* base, IoPtrs& p) {
+  static_assert(sizeof(YdKeyPoint) == sizeof(YdKeyPointDev), "one layout for the device and the pinned staging");
+  Carve a(base);
+  a.take(p.img, imgBytes * B); a.take(p.kps, Q * B); a.take(p.desc, 32 * Q * B); a.take(p.nOut, B);
+  return a.L.bytes;
+}
+
 }  // namespace
 
 struct ydorb_extractor {
@@ -70,36 +112,22 @@ struct ydorb_extractor {
   HostPlan plan;
   bool planValid = false;
   int batchCap = 0;
-  // device buffers (sized for plan x batchCap)
-  uint8_t *d_img = nullptr, *d_pyr = nullptr, *d_blur = nullptr;
-  uint32_t *d_cellCount = nullptr, *d_cellCand = nullptr, *d_qtCand = nullptr, *d_qtKeys = nullptr, *d_lvlKp = nullptr;
-  uint16_t* d_qtNode = nullptr;
-  uint8_t* d_nodeScratch = nullptr;  // HBM node tables of the levels whose quota does not fit the LDS (usually none)
-  uint8_t* d_needPass = nullptr;   // [frame][level]: 1 = k_qt_fast left the unit to the pass kernel
-  int* d_passList = nullptr;       // [1 + frames * levels]: count, then the units k_qt_fast handed over in this call
-  int *d_lvlCount = nullptr, *d_status = nullptr, *d_nOut = nullptr;
-  uint8_t* h_pyr = nullptr;           // pinned staging of one frame's pyramid block (ydorb_extractor_read_pyramid)
-  size_t h_pyrBytes = 0;
-  hipStream_t lastStream = nullptr;   // stream of the last enqueue (a caller's stream on the device-resident path)
-  int *d_lvlMaxN = nullptr, *h_lvlMaxN = nullptr;   // largest candidate count seen per level (device max) + [kMaxLevels] the last hand-over list length; copied back after every call
-  float* d_lvlAngle = nullptr;
-  CellDev* d_cells = nullptr;
-  int* d_tabInt = nullptr;
-  short* d_tabShort = nullptr;
-  PyrPadEntry* d_padTab = nullptr;
-  PyrColEntry* d_colTab = nullptr;
-  int2* d_rowTab = nullptr;
-  bool noFusedPads = false;   // YDORB_PYR_FUSED=0 at create: level kernels + one border launch (the tests compare both)
-  YdKeyPointDev* d_kps = nullptr;
-  uint8_t* d_desc = nullptr;
   size_t imgBytes = 0;
-  // pinned host staging for the host-pointer entry points
-  uint8_t* h_img = nullptr;
-  YdKeyPoint* h_kps = nullptr;
-  uint8_t* h_desc = nullptr;
-  int* h_nOut = nullptr;
-  int* h_status = nullptr;
-  int lastFrames = 0;
+  // Memory.  tables, work and hSync live from one re-plan to the next (ensurePlan); io and hIo are added to a plan by the first
+  // ydorb_extract_batch after it and go with it, so a handle that is only ever given device pointers never holds them.
+  Mem tables;        // layTables -> tab
+  Mem work;          // layWork, plan x batchCap -> d
+  Mem io; PinnedMem hIo;   // layIo, batchCap frames -> dIo and, pinned, hIoAt
+  PinnedMem hSync;   // every path's read-backs: [kMaxLevels + 1] the copy of d.lvlMaxN that follows every call, then the status word
+  PinnedMem h_pyr;   // one frame's pyramid block, grown by ydorb_extractor_read_pyramid
+  TablePtrs tab{};
+  WorkPtrs d{};
+  IoPtrs dIo{}, hIoAt{};
+  int *h_lvlMaxN = nullptr, *h_status = nullptr;   // into hSync
+  std::vector<Mem*> buffers() { return {&tables, &work, &io, &hIo, &hSync, &h_pyr}; }
+  hipStream_t lastStream = nullptr;   // stream of the last enqueue (a caller's stream on the device-resident path)
+  int lastFrames = 0;                 // frames of the pyramid `work` holds; 0 after a re-plan until the next call
+  bool noFusedPads = false;   // YDORB_PYR_FUSED=0 at create: level kernels + one border launch (the tests compare both)
   // profiling
   bool profiling = false;
   bool profPending = false;       // the stage events of the last launch have not been read yet
@@ -111,15 +139,18 @@ struct ydorb_extractor {
 
 namespace {
 
-void freeBuffers(ydorb_extractor* e) {
-  auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  F(e->d_img); F(e->d_pyr); F(e->d_blur); F(e->d_cellCount); F(e->d_cellCand); F(e->d_qtCand); F(e->d_qtKeys);
-  F(e->d_lvlKp); F(e->d_qtNode); F(e->d_needPass); F(e->d_passList); F(e->d_nodeScratch); F(e->d_lvlCount); F(e->d_lvlMaxN); F(e->d_status); F(e->d_nOut); F(e->d_lvlAngle); F(e->d_cells);
-  F(e->d_tabInt); F(e->d_tabShort); F(e->d_padTab); F(e->d_colTab); F(e->d_rowTab); F(e->d_kps); F(e->d_desc);
-  auto H = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
-  H(e->h_img); H(e->h_kps); H(e->h_desc); H(e->h_nOut); H(e->h_status); H(e->h_lvlMaxN); H(e->h_pyr);
-  e->h_pyrBytes = 0;
+// Drops the plan and all memory with it.  The caller has waited for the streams whose work uses it.
+void release(ydorb_extractor* e) {
+  for (Mem* b : e->buffers()) b->release();
   e->planValid = false;
+  e->lastStream = nullptr; e->lastFrames = 0;   // the pyramid is gone: the pyramid queries refuse until the next call
+}
+
+// Waits for the handle's stream and for the caller's stream of the last device-resident call.
+int syncStreams(ydorb_extractor* e) {
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (e->lastStream && e->lastStream != e->stream) HIPCHK(hipStreamSynchronize(e->lastStream));
+  return YDORB_OK;
 }
 
 // Level sizes, cell grid, scratch layout, resize tables for a w x h input.
@@ -355,62 +386,61 @@ int buildPlan(ydorb_extractor* e, int w, int h, HostPlan& P) {
   return YDORB_OK;
 }
 
+// LDS of a k_fast_cells launch over levels [la, lb): sized for the largest cell of the levels it covers (one level with 40-px cells -
+// 1241 x 376: level 5 - would otherwise put every launch on the 80-byte tile pitch and 66 KB per workgroup)
+size_t fastGeom(const HostPlan& P, int la, int lb, FastLds& fl, bool& narrow) {
+  int dim = 1;
+  for (int l = la; l < lb; l++) dim = std::max(dim, P.levelCellDim[l]);
+  const int maxT = dim + 6, maxB = dim;
+  narrow = maxT <= 44;
+  const int pitch = narrow ? 48 : 80;
+  fl.tileBytes = alignUp((maxT + 3) * pitch, 16);                 // + 3 rows: lanes outside the band still read (and discard) a ring
+  fl.scoreBytes = alignUp((maxB + 2) * (maxB + 2) + 4, 16);
+  fl.listBytes = alignUp(2 * maxB * maxB, 16);
+  return (size_t)4 * (fl.tileBytes + fl.scoreBytes + fl.listBytes);
+}
+
+template <class T> void copyTable(T* dst, const std::vector<T>& v) { if (!v.empty()) memcpy(dst, v.data(), sizeof(T) * v.size()); }
+
 int ensurePlan(ydorb_extractor* e, int w, int h, int nFrames) {
   if (e->planValid && e->plan.w == w && e->plan.h == h && nFrames <= e->batchCap) return YDORB_OK;
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HostPlan P;
-  int rc = buildPlan(e, w, h, P);
+  // the last call's kernels may still run, on the handle's stream or - device-resident path - on the caller's
+  int rc = syncStreams(e);
   if (rc) return rc;
-  freeBuffers(e);
-  const int B = std::max(nFrames, std::max(1, e->cfg.max_batch));
-  e->plan = P;
-  e->batchCap = B;
-  e->imgBytes = (size_t)w * h;
+  HostPlan P;
+  if ((rc = buildPlan(e, w, h, P))) return rc;
+  // Failure path: this clears planValid, and only the last line of this function sets it again.  Whatever stops a re-plan half-way
+  // therefore leaves a handle that the next call re-plans from scratch, beginning here with the release of what this attempt got.
+  release(e);
+  const size_t B = std::max(nFrames, std::max(1, e->cfg.max_batch));
   const PlanDev& D = P.dev;
-  HIPCHK(hipMalloc(&e->d_img, e->imgBytes * B));
-  HIPCHK(hipMalloc(&e->d_pyr, P.pyrFrameStride * B));
-  HIPCHK(hipMemsetAsync(e->d_pyr, 0, P.pyrFrameStride * B, e->stream));   // pitch slack beyond w + 38 is never written: keep it zero
-  HIPCHK(hipMalloc(&e->d_blur, P.blurFrameStride * B));
-  HIPCHK(hipMalloc(&e->d_cellCount, sizeof(uint32_t) * D.nCellsTotal * B));
-  HIPCHK(hipMalloc(&e->d_cellCand, sizeof(uint32_t) * (size_t)D.nCellsTotal * D.cellCap * B));
-  HIPCHK(hipMalloc(&e->d_qtCand, sizeof(uint32_t) * 2 * P.qtFrameStride * B));
-  HIPCHK(hipMalloc(&e->d_qtNode, sizeof(uint16_t) * 2 * P.qtFrameStride * B));
-  if (D.nodeTabFrameStride) HIPCHK(hipMalloc(&e->d_nodeScratch, (size_t)D.nodeTabFrameStride * B));
-  HIPCHK(hipMalloc(&e->d_needPass, (size_t)kMaxLevels * B));
-  HIPCHK(hipMemsetAsync(e->d_needPass, 0, (size_t)kMaxLevels * B, e->stream));
-  HIPCHK(hipMalloc(&e->d_passList, sizeof(int) * ((size_t)kMaxLevels * B + 1)));
-  HIPCHK(hipMemsetAsync(e->d_passList, 0, sizeof(int), e->stream));
-
-  HIPCHK(hipMalloc(&e->d_lvlKp, sizeof(uint32_t) * (size_t)D.sumQuota * B));
-  HIPCHK(hipMalloc(&e->d_lvlAngle, sizeof(float) * (size_t)D.sumQuota * B));
-  HIPCHK(hipMalloc(&e->d_lvlCount, sizeof(int) * kMaxLevels * B));
-  HIPCHK(hipMalloc(&e->d_lvlMaxN, sizeof(int) * (kMaxLevels + 1)));
-  HIPCHK(hipMemsetAsync(e->d_lvlMaxN, 0, sizeof(int) * (kMaxLevels + 1), e->stream));
-  HIPCHK(hipHostMalloc(&e->h_lvlMaxN, sizeof(int) * (kMaxLevels + 1)));
-  memset(e->h_lvlMaxN, 0, sizeof(int) * (kMaxLevels + 1));
-  HIPCHK(hipMalloc(&e->d_status, sizeof(int)));
-  HIPCHK(hipMalloc(&e->d_nOut, sizeof(int) * B));
-  HIPCHK(hipMalloc(&e->d_cells, sizeof(CellDev) * std::max<size_t>(P.cells.size(), 1)));
-  HIPCHK(hipMalloc(&e->d_tabInt, sizeof(int) * std::max<size_t>(P.tabInt.size(), 1)));
-  HIPCHK(hipMalloc(&e->d_tabShort, sizeof(short) * std::max<size_t>(P.tabShort.size(), 1)));
-  HIPCHK(hipMalloc(&e->d_kps, sizeof(YdKeyPointDev) * (size_t)D.sumQuota * B));
-  HIPCHK(hipMalloc(&e->d_desc, (size_t)32 * D.sumQuota * B));
-  HIPCHK(hipHostMalloc(&e->h_img, e->imgBytes * B));
-  HIPCHK(hipHostMalloc(&e->h_kps, sizeof(YdKeyPoint) * (size_t)D.sumQuota * B));
-  HIPCHK(hipHostMalloc(&e->h_desc, (size_t)32 * D.sumQuota * B));
-  HIPCHK(hipHostMalloc(&e->h_nOut, sizeof(int) * B));
-  HIPCHK(hipHostMalloc(&e->h_status, sizeof(int)));
-  if (!P.cells.empty()) HIPCHK(hipMemcpyAsync(e->d_cells, P.cells.data(), sizeof(CellDev) * P.cells.size(), hipMemcpyHostToDevice, e->stream));
-  if (!P.tabInt.empty()) HIPCHK(hipMemcpyAsync(e->d_tabInt, P.tabInt.data(), sizeof(int) * P.tabInt.size(), hipMemcpyHostToDevice, e->stream));
-  if (!P.tabShort.empty()) HIPCHK(hipMemcpyAsync(e->d_tabShort, P.tabShort.data(), sizeof(short) * P.tabShort.size(), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMalloc(&e->d_padTab, sizeof(PyrPadEntry) * std::max<size_t>(P.padTab.size(), 1)));
-  HIPCHK(hipMalloc(&e->d_colTab, sizeof(PyrColEntry) * std::max<size_t>(P.colTab.size(), 1)));
-  HIPCHK(hipMalloc(&e->d_rowTab, sizeof(int2) * std::max<size_t>(P.rowTab.size(), 1)));
-  if (!P.padTab.empty()) HIPCHK(hipMemcpyAsync(e->d_padTab, P.padTab.data(), sizeof(PyrPadEntry) * P.padTab.size(), hipMemcpyHostToDevice, e->stream));
-  if (!P.colTab.empty()) HIPCHK(hipMemcpyAsync(e->d_colTab, P.colTab.data(), sizeof(PyrColEntry) * P.colTab.size(), hipMemcpyHostToDevice, e->stream));
-  if (!P.rowTab.empty()) HIPCHK(hipMemcpyAsync(e->d_rowTab, P.rowTab.data(), sizeof(int2) * P.rowTab.size(), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  std::vector<uint8_t> hTables(layTables(P, nullptr, e->tab));
+  if ((rc = e->tables.alloc(hTables.size())) || (rc = e->work.alloc(layWork(P, B, nullptr, e->d))) ||
+      (rc = e->hSync.alloc(sizeof(int) * (kMaxLevels + 2)))) return rc;
+  layWork(P, B, e->work.p, e->d);
+  e->h_lvlMaxN = e->hSync.as<int>();
+  e->h_status = e->h_lvlMaxN + kMaxLevels + 1;
+  memset(e->hSync.p, 0, e->hSync.cap);
+  TablePtrs ht;
+  layTables(P, hTables.data(), ht);
+  copyTable(ht.cells, P.cells); copyTable(ht.tabInt, P.tabInt); copyTable(ht.tabShort, P.tabShort);
+  copyTable(ht.padTab, P.padTab); copyTable(ht.colTab, P.colTab); copyTable(ht.rowTab, P.rowTab);
+  layTables(P, e->tables.p, e->tab);
+  if (!hTables.empty()) HIPCHK(hipMemcpyAsync(e->tables.p, hTables.data(), hTables.size(), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemsetAsync(e->d.pyr, 0, P.pyrFrameStride * B, e->stream));   // pitch slack beyond w + 38 is never written: keep it zero
+  HIPCHK(hipMemsetAsync(e->d.needPass, 0, (uint8_t*)(e->d.passList + 1) - e->d.needPass, e->stream));   // needPass, lvlMaxN, status, passList[0]
+  HIPCHK(hipStreamSynchronize(e->stream));   // hTables is done with
+  e->plan = P;
+  e->batchCap = (int)B;
+  e->imgBytes = (size_t)w * h;
+  {
+    FastLds fl; bool narrow;
+    const size_t dynAll = fastGeom(P, 0, D.nLevels, fl, narrow);
+    if (dynAll > 48 * 1024) {   // the largest any level group can ask for
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fast_cells<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynAll));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fast_cells<80>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynAll));
+    }
+  }
   if (std::max(P.qtLdsMax, P.qtPassLds) > 48 * 1024)
   {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_quadtree), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(P.qtLdsMax, P.qtPassLds)));
@@ -427,6 +457,18 @@ int ensurePlan(ydorb_extractor* e, int w, int h, int nFrames) {
     }
   }
   e->planValid = true;
+  return YDORB_OK;
+}
+
+// The host entry point's staging for the plan's batchCap frames, device and pinned: allocated by the first host call after a re-plan,
+// beside a plan (and perhaps a pyramid) that exist already.  Released with the plan, so a pointer here never outlives its sizes.
+int ensureIo(ydorb_extractor* e) {
+  if (e->io.p && e->hIo.p) return YDORB_OK;
+  const size_t bytes = layIo(e->imgBytes, e->sumQuota, e->batchCap, nullptr, e->dIo);
+  int rc;
+  if ((rc = e->io.alloc(bytes)) || (rc = e->hIo.alloc(bytes))) return rc;
+  layIo(e->imgBytes, e->sumQuota, e->batchCap, e->io.p, e->dIo);
+  layIo(e->imgBytes, e->sumQuota, e->batchCap, e->hIo.p, e->hIoAt);
   return YDORB_OK;
 }
 
@@ -462,27 +504,27 @@ int enqueue(ydorb_extractor* e, const uint8_t* d_img, int stride, size_t frameSt
       return dim3((((L.w + 2 * kPad + 3) >> 2) + shift + 63) / 64, (L.h + 4 * kPyrRowsF - 1) / (4 * kPyrRowsF), nFrames);
     };
     if (P.fused[0].on) {
-      hipLaunchKernelGGL(k_pyr_level0_f, fusedGrid(L0, P.fused[0].shift), dim3(256), 0, s, d_img, stride, frameStride, e->d_pyr, P.pyrFrameStride, L0,
-                         e->d_padTab + P.fused[0].padOff, P.fused[0].shift);
+      hipLaunchKernelGGL(k_pyr_level0_f, fusedGrid(L0, P.fused[0].shift), dim3(256), 0, s, d_img, stride, frameStride, e->d.pyr, P.pyrFrameStride, L0,
+                         e->tab.padTab + P.fused[0].padOff, P.fused[0].shift);
     } else {
       dim3 g((L0.pitch / 4 + 63) / 64, (L0.h + 4 * kPyrRows - 1) / (4 * kPyrRows), nFrames);
-      hipLaunchKernelGGL(k_pyr_level0, g, dim3(256), 0, s, d_img, stride, frameStride, e->d_pyr, P.pyrFrameStride, L0);
+      hipLaunchKernelGGL(k_pyr_level0, g, dim3(256), 0, s, d_img, stride, frameStride, e->d.pyr, P.pyrFrameStride, L0);
     }
     for (int l = 1; l < D.nLevels; l++) {
       const LevelDev& L = D.lv[l];
       const double scaleX = 1. / ((double)L.w / D.lv[l - 1].w);
       if (P.fused[l].on) {
         const HostPlan::FusedLevel& F = P.fused[l];
-        hipLaunchKernelGGL(k_pyr_resize_f, fusedGrid(L, F.shift), dim3(256), 0, s, e->d_pyr, P.pyrFrameStride, D.lv[l - 1], L, scaleX,
-                           e->d_colTab + F.colOff, e->d_padTab + F.padOff, e->d_rowTab + F.rowOff, F.shift);
+        hipLaunchKernelGGL(k_pyr_resize_f, fusedGrid(L, F.shift), dim3(256), 0, s, e->d.pyr, P.pyrFrameStride, D.lv[l - 1], L, scaleX,
+                           e->tab.colTab + F.colOff, e->tab.padTab + F.padOff, e->tab.rowTab + F.rowOff, F.shift);
       } else {
         dim3 gl((L.pitch / 4 + 63) / 64, (L.h + 4 * kPyrRows - 1) / (4 * kPyrRows), nFrames);
-        hipLaunchKernelGGL(k_pyr_resize, gl, dim3(256), 0, s, e->d_pyr, P.pyrFrameStride, D.lv[l - 1], L, scaleX,
-                           e->d_tabShort + P.tab[l].alpha, e->d_tabInt + P.tab[l].yofs, e->d_tabShort + P.tab[l].beta);
+        hipLaunchKernelGGL(k_pyr_resize, gl, dim3(256), 0, s, e->d.pyr, P.pyrFrameStride, D.lv[l - 1], L, scaleX,
+                           e->tab.tabShort + P.tab[l].alpha, e->tab.tabInt + P.tab[l].yofs, e->tab.tabShort + P.tab[l].beta);
       }
     }
     if (D.borderBegin[D.nLevels] > 0)
-      hipLaunchKernelGGL(k_pyr_borders, dim3(D.borderBegin[D.nLevels] / 256, nFrames), dim3(256), 0, s, e->d_pyr, P.pyrFrameStride, D);
+      hipLaunchKernelGGL(k_pyr_borders, dim3(D.borderBegin[D.nLevels] / 256, nFrames), dim3(256), 0, s, e->d.pyr, P.pyrFrameStride, D);
   }
   if (prof) HIPCHK(hipEventRecord(e->ev[1], s));
   hipEvent_t fastEv[kMaxLevels]{};
@@ -490,27 +532,6 @@ int enqueue(ydorb_extractor* e, const uint8_t* d_img, int stride, size_t frameSt
   {
     // one wave per cell, 4 cells per workgroup; the per-wave LDS (tile, score map, candidate list) is sized for the plan's largest cell
     const int thr = std::min(std::max(e->cfg.ini_fast_thr, 0), 255);
-    // LDS of a launch: sized for the largest cell of the levels it covers (one level with 40-px cells - 1241 x 376: level 5 - would
-    // otherwise put every launch on the 80-byte tile pitch and 66 KB per workgroup)
-    auto fastGeom = [&](int la, int lb, FastLds& fl, bool& narrow) -> size_t {
-      int dim = 1;
-      for (int l = la; l < lb; l++) dim = std::max(dim, P.levelCellDim[l]);
-      const int maxT = dim + 6, maxB = dim;
-      narrow = maxT <= 44;
-      const int pitch = narrow ? 48 : 80;
-      fl.tileBytes = alignUp((maxT + 3) * pitch, 16);                 // + 3 rows: lanes outside the band still read (and discard) a ring
-      fl.scoreBytes = alignUp((maxB + 2) * (maxB + 2) + 4, 16);
-      fl.listBytes = alignUp(2 * maxB * maxB, 16);
-      return (size_t)4 * (fl.tileBytes + fl.scoreBytes + fl.listBytes);
-    };
-    {
-      FastLds flAll; bool nAll;
-      const size_t dynAll = fastGeom(0, D.nLevels, flAll, nAll);
-      if (dynAll > 48 * 1024) {   // the largest any group can ask for
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fast_cells<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynAll));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fast_cells<80>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynAll));
-      }
-    }
     // The cells are launched in level groups - the first fastGroups - 1 levels each on their own, the rest together - so that the
     // quad-tree of a big level (its own stream, below) starts while the cells of the smaller levels are still being searched.
     int l0 = 0;
@@ -519,10 +540,10 @@ int enqueue(ydorb_extractor* e, const uint8_t* d_img, int stride, size_t frameSt
       const int c0 = D.lv[l0].cellBegin, c1 = D.lv[l1 - 1].cellBegin + D.lv[l1 - 1].nCells;
       if (c1 > c0 && D.nCellsTotal > 0) {
         FastLds fl; bool narrow;
-        const size_t dyn = fastGeom(l0, l1, fl, narrow);
+        const size_t dyn = fastGeom(P, l0, l1, fl, narrow);
         const dim3 grid(((c1 - c0 + 3) / 4 + 7) / 8 * 8, nFrames);
-        if (narrow) hipLaunchKernelGGL(k_fast_cells<48>, grid, dim3(256), dyn, s, e->d_pyr, P.pyrFrameStride, D, e->d_cells, c0, c1, thr, fl, e->d_cellCount, e->d_cellCand);
-        else hipLaunchKernelGGL(k_fast_cells<80>, grid, dim3(256), dyn, s, e->d_pyr, P.pyrFrameStride, D, e->d_cells, c0, c1, thr, fl, e->d_cellCount, e->d_cellCand);
+        if (narrow) hipLaunchKernelGGL(k_fast_cells<48>, grid, dim3(256), dyn, s, e->d.pyr, P.pyrFrameStride, D, e->tab.cells, c0, c1, thr, fl, e->d.cellCount, e->d.cellCand);
+        else hipLaunchKernelGGL(k_fast_cells<80>, grid, dim3(256), dyn, s, e->d.pyr, P.pyrFrameStride, D, e->tab.cells, c0, c1, thr, fl, e->d.cellCount, e->d.cellCand);
       }
       HIPCHK(hipEventRecord(e->evFast[l0], s));
       fastEv[l0] = e->evFast[l0];
@@ -535,7 +556,7 @@ int enqueue(ydorb_extractor* e, const uint8_t* d_img, int stride, size_t frameSt
   // fork: the blur (needs only the pyramid) goes first on `s` so that it heads its hardware queue; the quad-tree launches, one
   // per level on the side streams, wait for the FAST results only and overlap it
   HIPCHK(hipEventRecord(e->evFork, s));
-  hipLaunchKernelGGL(k_blur, dim3((D.blurTileBegin[D.nLevels] + 7) / 8 * 8, nFrames), dim3(256), 0, s, e->d_pyr, P.pyrFrameStride, e->d_blur,
+  hipLaunchKernelGGL(k_blur, dim3((D.blurTileBegin[D.nLevels] + 7) / 8 * 8, nFrames), dim3(256), 0, s, e->d.pyr, P.pyrFrameStride, e->d.blur,
                      P.blurFrameStride, D);
   if (prof) HIPCHK(hipEventRecord(e->ev[3], s));   // end of the blur; the quad-tree stage is the interval up to the join below
   // Quad-tree thinning: ONE launch of k_qt_fast per FAST level group (grid = frames x the group's levels), on the group's side stream or
@@ -554,8 +575,8 @@ int enqueue(ydorb_extractor* e, const uint8_t* d_img, int stride, size_t frameSt
     const size_t lds = qt_fast_lds_bytes(qmax, tabLen);
     if (!e->forcePassQuadtree && lds <= 150 * 1024) {
       const dim3 grid(nFrames, l1 - l0);
-#define YD_QT_FAST(IT) hipLaunchKernelGGL(k_qt_fast<IT>, grid, dim3(kQfThreads), lds, qs, D, e->d_cellCount, e->d_cellCand, l0, qmax, tabLen, e->d_lvlKp, \
-                                          e->d_lvlCount, e->d_needPass, e->d_lvlMaxN, e->d_passList, e->d_passList + 1)
+#define YD_QT_FAST(IT) hipLaunchKernelGGL(k_qt_fast<IT>, grid, dim3(kQfThreads), lds, qs, D, e->d.cellCount, e->d.cellCand, l0, qmax, tabLen, e->d.lvlKp, \
+                                          e->d.lvlCount, e->d.needPass, e->d.lvlMaxN, e->d.passList, e->d.passList + 1)
       if (items <= 8) YD_QT_FAST(8);
       else if (items <= 16) YD_QT_FAST(16);
       else YD_QT_FAST(32);
@@ -564,8 +585,8 @@ int enqueue(ydorb_extractor* e, const uint8_t* d_img, int stride, size_t frameSt
     } else {
       for (int l = l0; l < l1; l++) {
         const HostPlan::QtLevel& Q = P.qt[l];
-        hipLaunchKernelGGL(k_quadtree, dim3(1, nFrames), dim3(kQtThreads), Q.lds, qs, D, e->d_cellCount, e->d_cellCand, e->d_qtCand, e->d_qtNode,
-                           P.qtFrameStride, Q.nodeCap, Q.candCap, l, e->d_lvlKp, e->d_lvlCount, e->d_status, e->d_nodeScratch);
+        hipLaunchKernelGGL(k_quadtree, dim3(1, nFrames), dim3(kQtThreads), Q.lds, qs, D, e->d.cellCount, e->d.cellCand, e->d.qtCand, e->d.qtNode,
+                           P.qtFrameStride, Q.nodeCap, Q.candCap, l, e->d.lvlKp, e->d.lvlCount, e->d.status, e->d.nodeScratch);
       }
     }
     if (!e->qtInline) HIPCHK(hipEventRecord(e->evJoin[g], qs));
@@ -574,26 +595,26 @@ int enqueue(ydorb_extractor* e, const uint8_t* d_img, int stride, size_t frameSt
   if (anyFast) {  // units k_qt_fast handed over (rare): node table in LDS, candidates in HBM scratch; the list's counter is cleared for the next call
     const int seen = e->h_lvlMaxN[kMaxLevels];   // hand-over list length of an earlier call (copied back below)
     const int listGrid = std::max(1, std::min({kQtPassWorkgroups, D.nLevels * nFrames, seen + seen / 4}));
-    hipLaunchKernelGGL(k_quadtree_list, dim3(listGrid), dim3(kQtListThreads), P.qtPassLds, s, D, e->d_cellCount, e->d_cellCand,
-                       e->d_qtCand, e->d_qtNode, P.qtFrameStride, -std::max(P.qtPassNodes, 1), e->d_lvlKp, e->d_lvlCount, e->d_status, e->d_passList,
-                       e->d_passList + 1, e->d_nodeScratch, e->d_lvlMaxN + kMaxLevels);
-    HIPCHK(hipMemsetAsync(e->d_passList, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_quadtree_list, dim3(listGrid), dim3(kQtListThreads), P.qtPassLds, s, D, e->d.cellCount, e->d.cellCand,
+                       e->d.qtCand, e->d.qtNode, P.qtFrameStride, -std::max(P.qtPassNodes, 1), e->d.lvlKp, e->d.lvlCount, e->d.status, e->d.passList,
+                       e->d.passList + 1, e->d.nodeScratch, e->d.lvlMaxN + kMaxLevels);
+    HIPCHK(hipMemsetAsync(e->d.passList, 0, sizeof(int), s));
   }
   if (prof) HIPCHK(hipEventRecord(e->ev[4], s));
   {
     const int kpw = e->descKpw;   // keypoints per wave (YDORB_DESC_KPW: 1, 2 or 4)
     const dim3 gd(((D.sumQuota + 4 * kpw - 1) / (4 * kpw) + 7) / 8 * 8, nFrames);
-#define YD_DESC(K) hipLaunchKernelGGL((k_orient_describe_n<K>), gd, dim3(256), 0, s, e->d_pyr, P.pyrFrameStride, e->d_blur, P.blurFrameStride, D, \
-                                         e->d_lvlKp, e->d_lvlCount, d_kps, d_desc, cap, d_nOut, e->d_lvlAngle)
+#define YD_DESC(K) hipLaunchKernelGGL((k_orient_describe_n<K>), gd, dim3(256), 0, s, e->d.pyr, P.pyrFrameStride, e->d.blur, P.blurFrameStride, D, \
+                                         e->d.lvlKp, e->d.lvlCount, d_kps, d_desc, cap, d_nOut, e->d.lvlAngle)
     if (kpw == 1)
-      hipLaunchKernelGGL(k_orient_describe, gd, dim3(256), 0, s, e->d_pyr, P.pyrFrameStride, e->d_blur,
-                         P.blurFrameStride, D, e->d_lvlKp, e->d_lvlCount, d_kps, d_desc, cap, d_nOut, e->d_lvlAngle);
+      hipLaunchKernelGGL(k_orient_describe, gd, dim3(256), 0, s, e->d.pyr, P.pyrFrameStride, e->d.blur,
+                         P.blurFrameStride, D, e->d.lvlKp, e->d.lvlCount, d_kps, d_desc, cap, d_nOut, e->d.lvlAngle);
     else if (kpw == 2) YD_DESC(2);
     else YD_DESC(4);
 #undef YD_DESC
   }
   if (prof) { HIPCHK(hipEventRecord(e->ev[5], s)); e->profPending = true; }
-  HIPCHK(hipMemcpyAsync(e->h_lvlMaxN, e->d_lvlMaxN, sizeof(int) * (kMaxLevels + 1), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(e->h_lvlMaxN, e->d.lvlMaxN, sizeof(int) * (kMaxLevels + 1), hipMemcpyDeviceToHost, s));
   HIPCHK(hipGetLastError());
   e->lastFrames = nFrames;
   e->lastStream = s;
@@ -625,7 +646,7 @@ int ydorb::extractor_pyramid_view(const ydorb_extractor* e, PyramidView* v) {
   v->stream = e->stream;
   for (int l = 0; l < e->cfg.n_levels; l++) {
     const LevelDev& L = e->plan.dev.lv[l];
-    v->roi[l] = e->d_pyr + L.padOff + (size_t)kPad * L.pitch + kPad;
+    v->roi[l] = e->d.pyr + L.padOff + (size_t)kPad * L.pitch + kPad;
     v->w[l] = L.w; v->h[l] = L.h; v->pitch[l] = L.pitch;
     v->scale[l] = e->sf[l]; v->invScale[l] = e->isf[l];
     v->quota[l] = e->perLevel[l];
@@ -721,7 +742,7 @@ void ydorb_extractor_destroy(ydorb_extractor_t* e) {
   if (!e) return;
   (void)hipSetDevice(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  freeBuffers(e);
+  release(e);
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (int l = 0; l < kMaxLevels; l++) {
     if (e->qtStream[l]) {
@@ -769,14 +790,13 @@ int ydorb_extract_batch_device(ydorb_extractor_t* e, const uint8_t* d_img, int32
 int ydorb_extractor_synchronize(ydorb_extractor_t* e) {
   if (!e) { set_error("null handle"); return YDORB_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(e->cfg.device));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  if (e->lastStream && e->lastStream != e->stream) HIPCHK(hipStreamSynchronize(e->lastStream));
-  if (!e->d_status) return YDORB_OK;
+  int rc = syncStreams(e);
+  if (rc || !e->planValid) return rc;
   // the device-resident entry point reports capacity errors of its quad-tree kernels here (the host entry point reads the
   // same word itself): candidates > 65535 in a level, node-table overflow, a level the pass kernel cannot take
-  HIPCHK(hipMemcpy(e->h_status, e->d_status, sizeof(int), hipMemcpyDeviceToHost));
-  const int rc = checkStatus(e);
-  if (rc) HIPCHK(hipMemset(e->d_status, 0, sizeof(int)));   // reported once; later calls start clean
+  HIPCHK(hipMemcpy(e->h_status, e->d.status, sizeof(int), hipMemcpyDeviceToHost));
+  rc = checkStatus(e);
+  if (rc) HIPCHK(hipMemset(e->d.status, 0, sizeof(int)));   // reported once; later calls start clean
   return rc;
 }
 
@@ -790,29 +810,30 @@ int ydorb_extract_batch(ydorb_extractor_t* e, const uint8_t* img, int32_t w, int
   if (!kps || !desc || stride < w) { set_error("invalid argument"); return YDORB_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(e->cfg.device));
   int rc = ensurePlan(e, w, h, n_frames);
-  if (rc) return rc;
+  if (rc || (rc = ensureIo(e))) return rc;
   const int Q = e->sumQuota;
+  YdKeyPointDev* d_kps = reinterpret_cast<YdKeyPointDev*>(e->dIo.kps);
   for (int f = 0; f < n_frames; f++)
-    for (int y = 0; y < h; y++) memcpy(e->h_img + (size_t)f * e->imgBytes + (size_t)y * w, img + f * frame_stride + (size_t)y * stride, w);
-  HIPCHK(hipMemcpyAsync(e->d_img, e->h_img, e->imgBytes * n_frames, hipMemcpyHostToDevice, e->stream));
-  rc = enqueue(e, e->d_img, w, e->imgBytes, n_frames, e->d_kps, e->d_desc, Q, e->d_nOut, e->stream);
+    for (int y = 0; y < h; y++) memcpy(e->hIoAt.img + (size_t)f * e->imgBytes + (size_t)y * w, img + f * frame_stride + (size_t)y * stride, w);
+  HIPCHK(hipMemcpyAsync(e->dIo.img, e->hIoAt.img, e->imgBytes * n_frames, hipMemcpyHostToDevice, e->stream));
+  rc = enqueue(e, e->dIo.img, w, e->imgBytes, n_frames, d_kps, e->dIo.desc, Q, e->dIo.nOut, e->stream);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(e->h_nOut, e->d_nOut, sizeof(int) * n_frames, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(e->h_status, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(e->h_kps, e->d_kps, sizeof(YdKeyPoint) * (size_t)Q * n_frames, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(e->h_desc, e->d_desc, (size_t)32 * Q * n_frames, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(e->hIoAt.nOut, e->dIo.nOut, sizeof(int) * n_frames, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(e->h_status, e->d.status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(e->hIoAt.kps, d_kps, sizeof(YdKeyPoint) * (size_t)Q * n_frames, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(e->hIoAt.desc, e->dIo.desc, (size_t)32 * Q * n_frames, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   collectProfile(e);
   rc = checkStatus(e);
   if (rc) {
-    HIPCHK(hipMemset(e->d_status, 0, sizeof(int)));   // reported once; the next call starts clean
+    HIPCHK(hipMemset(e->d.status, 0, sizeof(int)));   // reported once; the next call starts clean
     return rc;
   }
   for (int f = 0; f < n_frames; f++) {
-    const int n = e->h_nOut[f];
+    const int n = e->hIoAt.nOut[f];
     if (n > cap) { set_error("frame %d has %d keypoints, caller capacity %d", f, n, cap); return YDORB_ERR_CAPACITY; }
-    memcpy(kps + (size_t)f * cap, e->h_kps + (size_t)f * Q, sizeof(YdKeyPoint) * n);
-    memcpy(desc + (size_t)f * cap * 32, e->h_desc + (size_t)f * Q * 32, (size_t)32 * n);
+    memcpy(kps + (size_t)f * cap, e->hIoAt.kps + (size_t)f * Q, sizeof(YdKeyPoint) * n);
+    memcpy(desc + (size_t)f * cap * 32, e->hIoAt.desc + (size_t)f * Q * 32, (size_t)32 * n);
     n_out[f] = n;
   }
   return YDORB_OK;
@@ -830,7 +851,7 @@ int ydorb_extractor_pyramid(const ydorb_extractor_t* e, int32_t frame, int32_t l
     return YDORB_ERR_INVALID_ARG;
   }
   const LevelDev& L = e->plan.dev.lv[level];
-  if (d_roi) *d_roi = e->d_pyr + (size_t)frame * e->plan.pyrFrameStride + L.padOff + (size_t)kPad * L.pitch + kPad;
+  if (d_roi) *d_roi = e->d.pyr + (size_t)frame * e->plan.pyrFrameStride + L.padOff + (size_t)kPad * L.pitch + kPad;
   if (w) *w = L.w;
   if (h) *h = L.h;
   if (stride) *stride = L.pitch;
@@ -864,19 +885,15 @@ int ydorb_extractor_read_pyramid(ydorb_extractor_t* e, int32_t frame, uint8_t* c
   HIPCHK(hipSetDevice(e->cfg.device));
   // ONE device-to-host copy of the frame's pyramid block (levels sit back to back, rows at a 64-byte pitch) into pinned staging,
   // then the rows are repacked on the host: eight pitched copies into pageable memory cost ~1.6 ms each.
-  if (e->h_pyrBytes < P.pyrFrameStride) {
-    if (e->h_pyr) (void)hipHostFree(e->h_pyr);
-    e->h_pyr = nullptr; e->h_pyrBytes = 0;
-    HIPCHK(hipHostMalloc(&e->h_pyr, P.pyrFrameStride));
-    e->h_pyrBytes = P.pyrFrameStride;
-  }
+  if (const int rc = e->h_pyr.ensure(P.pyrFrameStride)) return rc;
+  const uint8_t* h_pyr = e->h_pyr.as<uint8_t>();
   hipStream_t s = e->lastStream ? e->lastStream : e->stream;
-  HIPCHK(hipMemcpyAsync(e->h_pyr, e->d_pyr + (size_t)frame * P.pyrFrameStride, P.pyrFrameStride, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(e->h_pyr.p, e->d.pyr + (size_t)frame * P.pyrFrameStride, P.pyrFrameStride, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   for (int l = 0; l < n_levels; l++) {
     const LevelDev& L = P.dev.lv[l];
     const int rowBytes = L.w + 2 * kPad;
-    for (int y = 0; y < L.h + 2 * kPad; y++) memcpy(dst_levels[l] + (size_t)y * rowBytes, e->h_pyr + L.padOff + (size_t)y * L.pitch, rowBytes);
+    for (int y = 0; y < L.h + 2 * kPad; y++) memcpy(dst_levels[l] + (size_t)y * rowBytes, h_pyr + L.padOff + (size_t)y * L.pitch, rowBytes);
   }
   return YDORB_OK;
 }
@@ -895,15 +912,15 @@ int ydorb_extractor_debug_read(ydorb_extractor_t* e, int32_t what, int32_t frame
   if (what == 0) {
     const size_t need = (size_t)L.w * L.h;
     if (dst_bytes < need) { set_error("need %zu bytes", need); return YDORB_ERR_CAPACITY; }
-    HIPCHK(hipMemcpy2D(dst, L.w, e->d_blur + (size_t)frame * P.blurFrameStride + L.blurOff, L.blurPitch, L.w, L.h, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(dst, L.w, e->d.blur + (size_t)frame * P.blurFrameStride + L.blurOff, L.blurPitch, L.w, L.h, hipMemcpyDeviceToHost));
     *written = need;
     return YDORB_OK;
   }
   if (what == 1) {
     std::vector<uint32_t> cnt(L.nCells), buf((size_t)L.nCells * D.cellCap);
     if (L.nCells) {
-      HIPCHK(hipMemcpy(cnt.data(), e->d_cellCount + (size_t)frame * D.nCellsTotal + L.cellBegin, sizeof(uint32_t) * L.nCells, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(buf.data(), e->d_cellCand + ((size_t)frame * D.nCellsTotal + L.cellBegin) * D.cellCap,
+      HIPCHK(hipMemcpy(cnt.data(), e->d.cellCount + (size_t)frame * D.nCellsTotal + L.cellBegin, sizeof(uint32_t) * L.nCells, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(buf.data(), e->d.cellCand + ((size_t)frame * D.nCellsTotal + L.cellBegin) * D.cellCap,
                        sizeof(uint32_t) * buf.size(), hipMemcpyDeviceToHost));
     }
     YdKeyPoint* o = (YdKeyPoint*)dst;
@@ -919,14 +936,14 @@ int ydorb_extractor_debug_read(ydorb_extractor_t* e, int32_t what, int32_t frame
   }
   if (what == 2) {
     int counts[kMaxLevels];
-    HIPCHK(hipMemcpy(counts, e->d_lvlCount + frame * kMaxLevels, sizeof(counts), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(counts, e->d.lvlCount + frame * kMaxLevels, sizeof(counts), hipMemcpyDeviceToHost));
     const int n = counts[level];
     if ((size_t)n * sizeof(YdKeyPoint) > dst_bytes) { set_error("keypoint buffer too small"); return YDORB_ERR_CAPACITY; }
     std::vector<uint32_t> pk(std::max(n, 1));
     std::vector<float> ang(std::max(n, 1));
     if (n) {
-      HIPCHK(hipMemcpy(pk.data(), e->d_lvlKp + (size_t)frame * D.sumQuota + L.kpOff, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(ang.data(), e->d_lvlAngle + (size_t)frame * D.sumQuota + L.kpOff, sizeof(float) * n, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(pk.data(), e->d.lvlKp + (size_t)frame * D.sumQuota + L.kpOff, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ang.data(), e->d.lvlAngle + (size_t)frame * D.sumQuota + L.kpOff, sizeof(float) * n, hipMemcpyDeviceToHost));
     }
     YdKeyPoint* o = (YdKeyPoint*)dst;
     for (int i = 0; i < n; i++)
@@ -940,7 +957,7 @@ int ydorb_extractor_debug_read(ydorb_extractor_t* e, int32_t what, int32_t frame
     int qmaxAll = 1, tabAll = 2;
     for (int l = 0; l < D.nLevels; l++) { qmaxAll = std::max(qmaxAll, D.lv[l].quota); tabAll = std::max(tabAll, std::max(D.lv[l].w - 2 * kBorder, 0) + std::max(D.lv[l].h - 2 * kBorder, 0) + 2); }
     if (!e->forcePassQuadtree && qt_fast_lds_bytes(qmaxAll, tabAll) <= 150 * 1024)   // (conservative: a group's own largest quota decides at launch)
-      HIPCHK(hipMemcpy(&v, e->d_needPass + (size_t)frame * kMaxLevels + level, 1, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&v, e->d.needPass + (size_t)frame * kMaxLevels + level, 1, hipMemcpyDeviceToHost));
     *(uint8_t*)dst = v;
     *written = 1;
     return YDORB_OK;
