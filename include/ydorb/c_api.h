@@ -399,6 +399,11 @@ typedef struct YdBaOptions {
 /* fill YdBaResult.ms_errors .. ms_update: a pair of stream events round every phase of every LM trial, ~10 us of stream time each
  * (8 % of a 100-keyframe solve), so the breakdown is opt-in; ms_total is always measured */
 #define YDORB_BA_PHASE_TIMES 4
+/* TEST ONLY, honoured by ydorb_ba_solve_batch alone: every upload of the per-problem round record is preceded on the batch's stream
+ * by a host function that sleeps 200 us, so that the copy reads its pinned source long after the host has gone on.  A host write
+ * into an area whose upload is still in flight then shows as a wrong result instead of once in a long while.  At most two uploads
+ * per round, a few dozen rounds per group. */
+#define YDORB_BA_TEST_LATE_UPLOADS 8
 
 typedef struct YdBaResult {
   int32_t n_trials;              /* LM trials executed (each = linearise/Schur/solve/update/chi2) */

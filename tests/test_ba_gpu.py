@@ -6,6 +6,7 @@ robust chi2 trajectory within 1e-6 relative; the outlier mask (integer decisions
 import numpy as np
 import pytest
 
+from ba_support import check_against_oracle
 from ydorbslam_amd.synth import synth_ba_problem
 
 pytestmark = pytest.mark.gpu
@@ -15,15 +16,7 @@ def _check(prob, oracle_lib, options=None):
     import ydorbslam_amd as y
     ref = oracle_lib.ba_solve(prob)
     got = y.Optimizer.local_bundle_adjust(prob, options)
-    assert got["trials"] == ref["trials"]
-    assert len(got["log"]) == len(ref["log"])
-    assert np.allclose(got["log"][:, 0], ref["log"][:, 0], rtol=1e-6, atol=0)       # chi2 per outer iteration
-    assert np.allclose(got["log"][:, 1], ref["log"][:, 1], rtol=1e-6, atol=0)       # lambda
-    assert np.array_equal(got["log"][:, 2:], ref["log"][:, 2:])                     # trials, stage
-    assert np.array_equal(got["outlier"], ref["outlier"])
-    p32, r32 = got["poses"].astype(np.float32), ref["poses"].astype(np.float32)     # what Converter hands back (float cv::Mat)
-    assert np.allclose(p32, r32, rtol=1e-4, atol=1e-6)
-    assert np.allclose(got["points"].astype(np.float32), ref["points"].astype(np.float32), rtol=1e-4, atol=1e-6)
+    check_against_oracle(ref, got)
     return ref, got
 
 
@@ -269,13 +262,16 @@ def test_batch_with_mixed_sizes_empty_stopped_and_invalid_members(oracle_lib):
     small = synth_ba_problem(4, 30, 3, seed=32)
     empty = dict(small); empty["edge_pose"] = np.zeros(0, np.int32); empty["edge_point"] = np.zeros(0, np.int32)
     empty["meas"] = np.zeros((0, 3)); empty["info"] = np.zeros(0)
-    probs = [big, small, empty, synth_ba_problem(9, 300, 5, seed=33, n_fixed=3)]
-    single = [y.Optimizer.local_bundle_adjust(p) for p in probs]
-    batch = y.Optimizer.local_bundle_adjust_batch(probs)
+    probs = [big, small, empty, synth_ba_problem(9, 300, 5, seed=33, n_fixed=3), small]
+    stops = [None] * 4 + [np.ones(1, np.uint8)]                                      # the last member's stop flag is already set
+    single = [y.Optimizer.local_bundle_adjust(p, stop=st) for p, st in zip(probs, stops)]
+    batch = y.Optimizer.local_bundle_adjust_batch(probs, stops=stops)
     for a, b in zip(single, batch):
         assert a["poses"].tobytes() == b["poses"].tobytes() and a["points"].tobytes() == b["points"].tobytes()
         assert np.array_equal(a["outlier"], b["outlier"]) and a["trials"] == b["trials"] and a["log"].tobytes() == b["log"].tobytes()
     assert batch[2]["trials"] == 0
+    assert batch[4]["stopped"] and batch[4]["trials"] == 0 and not batch[1]["stopped"]
+    assert np.array_equal(batch[4]["poses"], small["poses"]) and np.array_equal(batch[4]["points"], small["points"])
     # global-BA options (single stage, no robust kernel) through the batch as well
     go = y.Optimizer.global_options(6, False)
     gs = [y.Optimizer.local_bundle_adjust(p, go) for p in probs[:2]]

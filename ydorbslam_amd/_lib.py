@@ -170,6 +170,7 @@ class YdBaOptions(C.Structure):
 
 
 BA_SINGLE_STAGE, BA_NO_ROBUST, BA_PHASE_TIMES = 1, 2, 4
+BA_TEST_LATE_UPLOADS = 8   # test only: see c_api.h
 
 
 class YdBaResult(C.Structure):

@@ -330,7 +330,8 @@ int prepareStage(Run& R_, bool reuse) {
     if ((rc = prepare())) return rc;
   }
   // (stage 2 re-uses stage 1's device structures as they are: k_cull already zeroed the information of the culled edges and
-  // cleared the robust flags on the device)
+  // cleared the robust flags on the device.  The host does not learn how many edges survived; a cull that left NONE shows at the
+  // stage's first iteration as a system whose largest diagonal entry is exactly 0, see noEdgesLeft)
   if (Y.Ea == 0) return YDORB_OK;
   // the two estimate buffers must agree on everything the update kernel does not write (fixed poses, points without edges)
   HIPCHK(hipMemcpyAsync(c.st.poses[R_.cur ^ 1], c.st.poses[R_.cur], sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
@@ -338,6 +339,11 @@ int prepareStage(Run& R_, bool reuse) {
   HIPCHK(hipMemsetAsync(c.w.S, 0, sizeof(double) * ((size_t)Y.n * Y.n + Y.n + (size_t)Y.nb * NB * NB), s));   // S | bs | diagInv (see WorkPtrs)
   return YDORB_OK;
 }
+
+// Second stage only: initializeOptimization(0) finds no level-0 edge when the cull removed them all, and optimize() returns without an
+// iteration (SparseOptimizer::optimize: "0 vertices to optimize"; the oracle's `if (act.empty()) return`).  Here the culled edges keep their slots with information 0, so the stage is entered; its
+// first buildSystem then gives H = 0, whereas one surviving edge puts fx^2 / z^2 * information > 0 on its landmark's diagonal.
+inline bool noEdgesLeft(int stage, double maxDiag) { return stage == 2 && maxDiag == 0; }
 
 // one SparseOptimizer::optimize(iterations) on the level-0 edges
 int optimize(Run& R_, int iterations, int stage, bool reuse) {
@@ -395,6 +401,7 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
       if (multi) { if ((rc = allreduce(R_, w.scal + 1, 1, 1))) return rc; }
       HIPCHK(hipMemcpyAsync(hscal, w.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
+      if (noEdgesLeft(stage, hscal[1])) break;   // nothing logged, no trial: the stage did not take place
       lambda = 1e-5 * hscal[1];
       ni = 2;
     }
@@ -560,6 +567,7 @@ int endSolve(Run& R_) {
 // ---------------------------------------------------------------------------------------------------------------------------
 struct Job {
   SolveMem mem;            // its own arenas; mem.stream is a set-up stream or the batch's (not owned)
+  BaDev dev{};             // its record of the stage at hand (offsets, sizes); both upload images of a round start from it
   YdBaOptions O;
   Run* run = nullptr;
   int stage = 1, it = 0, iterations = 0, qmax = 0;
@@ -570,17 +578,22 @@ struct Job {
   std::string errText;
   ~Job() { delete run; }
 };
+// A pinned area that an enqueued copy reads is not written again until the stream has been waited on past that copy.
 struct BatchPool {   // per device: contexts, stream and staging of the lock-step batches (one batch at a time per device)
   std::mutex mu;
   hipStream_t stream = nullptr;
   std::vector<Job*> jobs;          // grown on demand; buffers are kept between calls
   std::vector<hipStream_t> setupStreams;
   Mem dDev, dScal;                 // BaDev[B]; per problem 8 doubles (chi2, max diag, scale sum, ..., status copies) + 2 ints of status
-  PinnedMem hDev, hScal;           // BaDev[B] as the host writes it before every round; the read-back of dScal's doubles
+  PinnedMem hDev, hScal;           // two images of BaDev[B], the one phase (a) of a round uploads and the one phase (b) uploads: (a) does not
+                                   // always wait before the host goes on to (b); the read-back of dScal's doubles
 };
 BatchPool g_batch[16];
 constexpr int kSetupThreads = 16;  // host threads of a batch's set-up phase
 constexpr int kBatchGroup = 64;    // problems per lock-step group (C5-sized problems take ~40 MB each)
+
+// YDORB_BA_TEST_LATE_UPLOADS: enqueued in front of a BaDev upload, so that the copy reads its pinned source 200 us after the host went on
+void lateUpload(void*) { std::this_thread::sleep_for(std::chrono::microseconds(200)); }
 
 void fillDev(Job& J, BaDev& D, const BaDev* dDevBase, double* dScal, int* dStatus) {
   const UpPtrs& u = J.mem.u;
@@ -603,9 +616,11 @@ void fillDev(Job& J, BaDev& D, const BaDev* dDevBase, double* dScal, int* dStatu
 
 int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, YdBaResult* res, int n, int* rcEach) {
   hipStream_t s = B.stream;
+  const bool lateUploads = (Oin.flags & YDORB_BA_TEST_LATE_UPLOADS) != 0;
   int rc;
   if ((rc = B.dDev.ensure(sizeof(BaDev) * n)) || (rc = B.dScal.ensure((sizeof(double) * 8 + sizeof(int) * 2) * n))) return rc;
-  BaDev* hDev = B.hDev.as<BaDev>();
+  BaDev* hDevA = B.hDev.as<BaDev>();   // phase (a)'s image: next written in the following round, after the wait that ends phase (b)
+  BaDev* hDevB = hDevA + n;            // phase (b)'s image: uploaded and waited on within phase (b)
   double* hScal = B.hScal.as<double>();
   double* dScalAll = B.dScal.as<double>();
   int* dStatusAll = reinterpret_cast<int*>(dScalAll + (size_t)8 * n);
@@ -622,7 +637,7 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
     if (r) { fail(j, r); return; }
     if (X.run->sys.Ea == 0) { endStage(j); return; }
     if (X.run->sys.n > kCholSolveMaxN) { set_error("reduced camera system of %d rows is wider than the solve kernel's LDS (max %d)", X.run->sys.n, kCholSolveMaxN); fail(j, YDORB_ERR_UNSUPPORTED); return; }
-    fillDev(X, hDev[j], B.dDev.as<BaDev>(), dScalAll + (size_t)8 * j, dStatusAll + (size_t)2 * j);
+    fillDev(X, X.dev, B.dDev.as<BaDev>(), dScalAll + (size_t)8 * j, dStatusAll + (size_t)2 * j);
     if (!(X.it < X.iterations && !X.run->stopped())) { endStage(j); return; }   // `for (it = 0; it < iterations && !terminate(); ...)`
     X.needBuild = true;
   };
@@ -715,7 +730,8 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
     bool anyBuild = false, anyChi = false, anyDiag = false;
     for (int j = 0; j < n; j++) {
       Job& X = *J[j];
-      BaDev& D = hDev[j];
+      BaDev& D = hDevA[j];
+      D = X.dev;
       D.trial = 0;
       D.build = !X.done && X.needBuild;
       D.chi2 = D.build && (X.it == 0 || !X.lastAccepted);
@@ -731,7 +747,8 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
               gScale = maxOver([](const Sys& Y) { return (6 * Y.nPf + 3 * Y.nL + 255) / 256; }), gN = maxOver([](const Sys& Y) { return Y.n; });
     const BaDev* dDev = B.dDev.as<BaDev>();
     if (anyBuild) {
-      HIPCHK(hipMemcpyAsync(B.dDev.p, hDev, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
+      if (lateUploads) HIPCHK(hipLaunchHostFunc(s, lateUpload, nullptr));
+      HIPCHK(hipMemcpyAsync(B.dDev.p, hDevA, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
       if (anyChi) {
         hipLaunchKernelGGL(kb_errors, dim3(gE, 1, n), dim3(256), 0, s, dDev, 0);
         hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 0);
@@ -746,23 +763,26 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
       }
       for (int j = 0; j < n; j++) {
         Job& X = *J[j];
-        const BaDev& D = hDev[j];
+        const BaDev& D = hDevA[j];
         if (!D.build) continue;
         if (D.chi2) X.currentChi = hScal[8 * j + 0];
         if (D.maxdiag) { X.lambda = 1e-5 * hScal[8 * j + 1]; X.ni = 2; }   // computeLambdaInit
         X.needBuild = false;
+        if (D.maxdiag && noEdgesLeft(X.stage, hScal[8 * j + 1])) endStage(j);   // as in optimize(): no trial, nothing logged
       }
     }
     // (b) one LM trial of every unfinished problem ----------------------------------------------------------------------------------
     for (int j = 0; j < n; j++) {
       Job& X = *J[j];
-      BaDev& D = hDev[j];
+      BaDev& D = hDevB[j];
+      D = X.dev;
       D.build = D.chi2 = D.maxdiag = 0;
       D.trial = !X.done;
       D.lambda = X.lambda;
       D.cur = X.done ? 0 : X.run->cur;
     }
-    HIPCHK(hipMemcpyAsync(B.dDev.p, hDev, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
+    if (lateUploads) HIPCHK(hipLaunchHostFunc(s, lateUpload, nullptr));
+    HIPCHK(hipMemcpyAsync(B.dDev.p, hDevB, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(kb_dinv, dim3(gL256, 1, n), dim3(256), 0, s, dDev);
     hipLaunchKernelGGL(kb_bd, dim3(gE, 1, n), dim3(256), 0, s, dDev);
     if (gP) hipLaunchKernelGGL(kb_bs, dim3(gP, 1, n), dim3(256), 0, s, dDev);
@@ -955,7 +975,7 @@ int ydorb_ba_solve_batch(const YdBaProblem* probs, int32_t n, const YdBaOptions*
   if (!B.stream) HIPCHK(hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking));
   // `threads` is the number of problems advanced together (0 = as many as fit one group); the lock-step batch needs no host threads
   const int group = std::max(1, std::min<int>(threads > 0 ? threads : kBatchGroup, kBatchGroup));
-  if ((rc = B.hDev.ensure(sizeof(BaDev) * group)) || (rc = B.hScal.ensure(sizeof(double) * 8 * group))) return rc;
+  if ((rc = B.hDev.ensure(sizeof(BaDev) * 2 * group)) || (rc = B.hScal.ensure(sizeof(double) * 8 * group))) return rc;
   while ((int)B.jobs.size() < group) B.jobs.push_back(new Job());
   int first = YDORB_OK;
   std::string firstText;

@@ -76,8 +76,9 @@ class Optimizer:
         check(lib().ydorb_ba_release(device))
 
     @staticmethod
-    def local_bundle_adjust_batch(probs, options=None, threads=0):
+    def local_bundle_adjust_batch(probs, options=None, threads=0, stops=None):
         """n independent problems in one ydorb_ba_solve_batch call (host threads inside the library, one pooled context each).
+        stops: optional list with one uint8[1] stop flag or None per problem (YdBaProblem.stop).
         Returns a list of the dicts local_bundle_adjust returns."""
         L = lib()
         o = options if options is not None else Optimizer.default_options()
@@ -97,7 +98,8 @@ class Optimizer:
             info = np.ascontiguousarray(prob["info"], np.float64)
             outlier = np.zeros(max(len(ep), 1), np.uint8)
             cam = [float(v) for v in prob["camera"]]
-            P[i] = YdBaProblem(len(poses), len(points), len(ep), _p(poses), _p(fixed), _p(points), _p(ep), _p(eq), _p(meas), _p(info), *cam, None)
+            P[i] = YdBaProblem(len(poses), len(points), len(ep), _p(poses), _p(fixed), _p(points), _p(ep), _p(eq), _p(meas), _p(info), *cam,
+                               None if stops is None else _p(stops[i]))
             R[i].edge_outlier = outlier.ctypes.data_as(C.c_void_p).value
             keep.append((poses, points, fixed, ep, eq, meas, info, outlier))
         check(L.ydorb_ba_solve_batch(P, n, C.byref(o), R, int(threads), None))
