@@ -3,12 +3,11 @@
 // (src/optimizer.cpp:284-334), SparseOptimizer::initializeOptimization/optimize
 // (thirdParty/g2o/g2o/core/sparse_optimizer.cpp:208-280, 366-440) and the Levenberg-Marquardt trial loop
 // (core/optimization_algorithm_levenberg.cpp:57-173).  All arithmetic on the graph runs in ba_kernels.hip.h;
-// the host only sorts the edge list, keeps lambda / nu, and reads three scalars per trial.
+// the host only sorts the edge list, steps the LM schedule (lm_schedule.h), and reads three scalars per trial.
 #include <hip/hip_runtime.h>
 #include <chrono>
 
 #include <algorithm>
-#include <functional>
 #include <string>
 #include <thread>
 #include <atomic>
@@ -17,11 +16,13 @@
 #include <limits>
 #include <mutex>
 #include <numeric>
+#include <optional>
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
 #include "ba_kernels.hip.h"
 #include "host_buffers.h"
+#include "lm_schedule.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
@@ -123,7 +124,7 @@ struct Ctx {  // per-device context of the single solves and the pose batches, r
   SolveMem mem;
   Mem pose;   // pose-only batches (layPose)
   hipEvent_t ev[2 * PH_COUNT + 2]{};
-  PinnedMem hPin;   // read-back area: scal[8] + status[2] (one stream sync per LM trial); lives as long as the stream and the events
+  PinnedMem hPin;   // read-back area: scal[8] (one stream sync per LM trial); lives as long as the stream and the events
   // ydorb_ba_release: device scratch and pinned staging back to the system (stream, events and hPin stay)
   void releaseBuffers() { mem.releaseBuffers(); pose.release(); }
 };
@@ -171,8 +172,14 @@ struct Run {
   Sys sys;
   hipEvent_t* ev = nullptr;   // Ctx::ev and Ctx::hPin of a single solve (optimize()); a lock-step batch member has neither
   double* hPin = nullptr;
-  bool stopped() const { return P->stop && *P->stop; }
+  LmSchedule lm;   // lambda, nu, the counters and every decision on them
+  bool stopped() const { return LmSchedule::raised(P->stop); }
 };
+
+int tooWideForSolve(int n) {
+  set_error("reduced camera system of %d rows is wider than the solve kernel's LDS (max %d)", n, kCholSolveMaxN);
+  return YDORB_ERR_UNSUPPORTED;
+}
 
 int allreduce(Run& R_, void* d_buf, int64_t count, int op) {
   const YdBaOptions* O = R_.O;
@@ -331,7 +338,7 @@ int prepareStage(Run& R_, bool reuse) {
   }
   // (stage 2 re-uses stage 1's device structures as they are: k_cull already zeroed the information of the culled edges and
   // cleared the robust flags on the device.  The host does not learn how many edges survived; a cull that left NONE shows at the
-  // stage's first iteration as a system whose largest diagonal entry is exactly 0, see noEdgesLeft)
+  // stage's first iteration as a system whose largest diagonal entry is exactly 0, see LmSchedule::setMaxDiag)
   if (Y.Ea == 0) return YDORB_OK;
   // the two estimate buffers must agree on everything the update kernel does not write (fixed poses, points without edges)
   HIPCHK(hipMemcpyAsync(c.st.poses[R_.cur ^ 1], c.st.poses[R_.cur], sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
@@ -340,14 +347,10 @@ int prepareStage(Run& R_, bool reuse) {
   return YDORB_OK;
 }
 
-// Second stage only: initializeOptimization(0) finds no level-0 edge when the cull removed them all, and optimize() returns without an
-// iteration (SparseOptimizer::optimize: "0 vertices to optimize"; the oracle's `if (act.empty()) return`).  Here the culled edges keep their slots with information 0, so the stage is entered; its
-// first buildSystem then gives H = 0, whereas one surviving edge puts fx^2 / z^2 * information > 0 on its landmark's diagonal.
-inline bool noEdgesLeft(int stage, double maxDiag) { return stage == 2 && maxDiag == 0; }
-
-// one SparseOptimizer::optimize(iterations) on the level-0 edges
-int optimize(Run& R_, int iterations, int stage, bool reuse) {
-  int rc = prepareStage(R_, reuse);
+// one SparseOptimizer::optimize(iterations) on the level-0 edges: the stage R_.lm is at
+int optimize(Run& R_) {
+  LmSchedule& lm = R_.lm;
+  int rc = prepareStage(R_, lm.stage == 2);
   if (rc) return rc;
   SolveMem& c = *R_.c;
   const YdBaOptions& O = *R_.O;
@@ -363,10 +366,9 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
   EdgeSoA Ed{u.ePose, u.ePidx, u.ePt, u.eMeas, u.eInfo, u.eRobust, Ea};
   const double dM = O.delta_mono, dSt = O.delta_stereo;
   double* hscal = R_.hPin;
-  int* hstatus = reinterpret_cast<int*>(R_.hPin + 8);
   const bool multi = O.world > 1 && O.allreduce;
 
-  auto computeChi2 = [&](int buf, double* out, bool withStatus) -> int {
+  auto computeChi2 = [&](int buf, bool withStatus) -> int {   // into hscal[0]
     PhaseTimer t(R_, PH_ERR);
     hipLaunchKernelGGL(k_errors, dim3(nBlkE), dim3(256), 0, s, Ed, poses[buf], pts[buf], R_.cam, dM, dSt, w.err, w.partial);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, w.partial, nBlkE, w.scal, 0, withStatus ? w.status : nullptr);
@@ -374,20 +376,16 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
     if (multi) { int r2 = allreduce(R_, w.scal, 1, 0); if (r2) return r2; }
     HIPCHK(hipMemcpyAsync(hscal, w.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (withStatus) { hstatus[0] = (int)hscal[6]; hstatus[1] = (int)hscal[7]; }
-    *out = hscal[0];
     return YDORB_OK;
   };
 
   trace("optimize: pair buckets enqueued");
-  double lambda = 0, ni = 2, currentChi = 0;
-  bool lastAccepted = true;
-  for (int it = 0; it < iterations && !R_.stopped(); it++) {
-    // computeActiveErrors + activeRobustChi2 at the top of an iteration: after the first iteration the state is the trial
-    // that was just accepted, whose errors (err) and chi2 are already there — same kernel, same inputs, same bits.
-    // A trial can also end rejected without terminating the loop (rho = NaN: `rho < 0` and `rho == 0` are both false); then err
-    // and chi2 belong to the rejected state and are recomputed on the kept one, as g2o does at the top of every iteration.
-    if ((it == 0 || !lastAccepted) && (rc = computeChi2(R_.cur, &currentChi, false))) return rc;
+  const double& lambda = lm.lambda;
+  for (bool more = lm.firstIteration(R_.P->stop); more;) {
+    if (lm.needChi2()) {
+      if ((rc = computeChi2(R_.cur, false))) return rc;
+      lm.setChi2(hscal[0]);
+    }
     {  // buildSystem
       PhaseTimer t(R_, PH_BUILD);
       hipLaunchKernelGGL(k_build_points, dim3((nL + 127) / 128), dim3(128), 0, s, Ed, u.ptStart, nL, poses[R_.cur], pts[R_.cur], R_.cam, dM, dSt, w.err, w.Hll, w.bl, w.Hpl);
@@ -396,17 +394,14 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
       t.stop();
       if (multi && nPf) { if ((rc = allreduce(R_, dHpp, (int64_t)42 * nPf, 0))) return rc; }
     }
-    if (it == 0) {  // computeLambdaInit
+    if (lm.needLambdaInit()) {
       hipLaunchKernelGGL(k_max_diag, dim3(1), dim3(256), 0, s, dHpp, nPf, w.Hll, nL, w.scal, 1);
       if (multi) { if ((rc = allreduce(R_, w.scal + 1, 1, 1))) return rc; }
       HIPCHK(hipMemcpyAsync(hscal, w.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
-      if (noEdgesLeft(stage, hscal[1])) break;   // nothing logged, no trial: the stage did not take place
-      lambda = 1e-5 * hscal[1];
-      ni = 2;
+      if (!lm.setMaxDiag(hscal[1])) break;
     }
-    double rho = 0;
-    int qmax = 0;
+    LmSchedule::Next next;
     do {
       const int nxt = R_.cur ^ 1;
       {
@@ -426,10 +421,7 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
         PhaseTimer t(R_, PH_SOLVE);
         for (int kb = 0; kb < nb; kb++)
           hipLaunchKernelGGL(k_chol_step, dim3((nb - kb) * (nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, s, dS, w.diagL, w.diagInv, n, kb, w.status, dbs, w.yv);
-        if (!launch_chol_solve(s, dS, w.diagInv, n, w.yv, dbs, w.xp)) {
-          set_error("reduced camera system of %d rows is wider than the solve kernel's LDS (max %d)", n, kCholSolveMaxN);
-          return YDORB_ERR_UNSUPPORTED;
-        }
+        if (!launch_chol_solve(s, dS, w.diagInv, n, w.yv, dbs, w.xp)) return tooWideForSolve(n);
         hipLaunchKernelGGL(k_backsub, dim3((nL + 127) / 128), dim3(128), 0, s, Ed, u.ptStart, nL, w.Hpl, w.Dinv, w.bl, w.xp, w.xl);
         t.stop();
         HIPCHK(hipGetLastError());
@@ -447,22 +439,11 @@ int optimize(Run& R_, int iterations, int stage, bool reuse) {
         t.stop();
         if (multi) { if ((rc = allreduce(R_, w.scal + 2, 1, 0))) return rc; }
       }
-      double tempChi;
-      if ((rc = computeChi2(nxt, &tempChi, true))) return rc;  // also brings back scal[2], the factorisation status, and leaves err = errors of the trial state
-      const double scaleSum = hscal[2];
-      lastAccepted = lm_judge(lambda, ni, currentChi, rho, tempChi, scaleSum + 1e-3, hstatus[0] == 0);
-      if (lastAccepted) R_.cur = nxt;  // discardTop(): keep the updated estimate
-      else if (!std::isfinite(lambda)) { qmax++; R_.res->n_trials++; break; }  // pop(): the previous estimate is still in poses[cur]
-      qmax++;
-      R_.res->n_trials++;
-    } while (rho < 0 && qmax < O.max_trials && !R_.stopped());
-    YdBaResult* res = R_.res;
-    if (res->n_log < 32) {
-      res->log_chi2[res->n_log] = currentChi; res->log_lambda[res->n_log] = lambda; res->log_trials[res->n_log] = qmax; res->log_stage[res->n_log] = stage;
-      res->n_log++;
-    }
-    res->n_iterations++;
-    if (qmax == O.max_trials || rho == 0 || !std::isfinite(lambda)) break;  // SolverResult::Terminate
+      if ((rc = computeChi2(nxt, true))) return rc;  // also brings back scal[2], the factorisation status, and leaves err = errors of the trial state
+      next = lm.trial(hscal[0], hscal[2], (int)hscal[6] == 0, R_.P->stop);
+      if (lm.lastAccepted) R_.cur = nxt;
+    } while (next == LmSchedule::Retry);
+    more = next == LmSchedule::NextIteration;
   }
   trace("optimize: LM loop done");
   for (int ph = 0; ph < PH_COUNT; ph++) PhaseTimer::collect(R_, ph);
@@ -504,6 +485,7 @@ int beginSolve(Run& R_) {
   R_.noRobust = (O.flags & YDORB_BA_NO_ROBUST) != 0;
   R_.phaseTimes = (O.flags & YDORB_BA_PHASE_TIMES) != 0;
   R_.cam = Cam{P->fx, P->fy, P->cx, P->cy, P->bf};
+  R_.lm.begin(O, R_.res);
   if ((rc = c.state.ensure(layState(K, NP, nullptr, c.st)))) return rc;
   layState(K, NP, c.state.p, c.st);
   {  // SE3Quat's 7-vector constructor normalises the rotation (se3quat.h:80-86)
@@ -521,6 +503,7 @@ int beginSolve(Run& R_) {
   return YDORB_OK;
 }
 
+// final == 0, optimizer.cpp:290-311: edges whose chi2 exceeds the threshold or whose depth is not positive leave the second stage
 int launchCull(Run& R_, int final) {
   SolveMem& c = *R_.c;
   const YdBaOptions& O = *R_.O;
@@ -531,9 +514,6 @@ int launchCull(Run& R_, int final) {
   HIPCHK(hipGetLastError());
   return YDORB_OK;
 }
-
-// optimizer.cpp:290-311: edges whose chi2 exceeds the threshold or whose depth is not positive leave the second stage; no kernels any more
-int cullAfterFirstStage(Run& R_) { return launchCull(R_, 0); }
 
 // optimizer.cpp:315-351 up to the write-back: the final outlier list and the estimates
 int endSolve(Run& R_) {
@@ -560,8 +540,8 @@ int endSolve(Run& R_) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // ydorb_ba_solve_batch: independent problems advance in LOCK STEP through one set of launches per phase (blockIdx.z = problem,
-// ba_kernels.hip.h "Lock-step batch").  The host keeps one LM state per problem - exactly the scalars and decisions of optimize()
-// above - and every round (a) builds the system of the problems that start an iteration, (b) runs one LM trial of every unfinished
+// ba_kernels.hip.h "Lock-step batch").  The host keeps one LmSchedule per problem - the one optimize() above steps -
+// and every round (a) builds the system of the problems that start an iteration, (b) runs one LM trial of every unfinished
 // problem, (c) reads all problems' three scalars back with ONE copy and decides accept / retry / terminate per problem.  A problem
 // that is done with a stage goes through the same cull / second stage / read-back steps as a single solve while the others go on.
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -569,14 +549,12 @@ struct Job {
   SolveMem mem;            // its own arenas; mem.stream is a set-up stream or the batch's (not owned)
   BaDev dev{};             // its record of the stage at hand (offsets, sizes); both upload images of a round start from it
   YdBaOptions O;
-  Run* run = nullptr;
-  int stage = 1, it = 0, iterations = 0, qmax = 0;
-  double lambda = 0, ni = 2, currentChi = 0, rho = 0;
-  bool lastAccepted = true, needBuild = false, done = false;
+  std::optional<Run> run;  // of the call at hand; none for a member that was invalid, empty or stopped on arrival
+  bool needBuild = false;  // at the start of an iteration: phase (a) of the next round is for it
+  bool done = false;
   bool pendingEnd = false;   // finished its LM schedule: final cull + read-back still to do (all of a group together, on the set-up threads)
   int rc = YDORB_OK;
   std::string errText;
-  ~Job() { delete run; }
 };
 // A pinned area that an enqueued copy reads is not written again until the stream has been waited on past that copy.
 struct BatchPool {   // per device: contexts, stream and staging of the lock-step batches (one batch at a time per device)
@@ -627,199 +605,170 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
   std::vector<Job*> J(B.jobs.begin(), B.jobs.begin() + n);
   auto fail = [&](int j, int code) { J[j]->rc = code; J[j]->done = true; if (rcEach) rcEach[j] = code; };
 
-  // stage transitions (per problem, on the shared stream) -----------------------------------------------------------------
-  std::function<void(int)> finalize, endStage;
-  auto startStage = [&](int j, int stage) {
+  // Stage transitions (per problem, on its stream).  over == false: the member enters the stage its schedule is at; true: that stage is
+  // over and the schedule says what follows.  Finished members wait for the final cull, read-back and outlier scatter (~0.1 ms each,
+  // mostly host) until the rounds have ended, see below.
+  auto nextStage = [&](int j, bool over) {
     Job& X = *J[j];
-    X.stage = stage; X.it = 0; X.qmax = 0; X.rho = 0; X.lastAccepted = true;
-    X.iterations = stage == 1 ? X.O.iters1 : X.O.iters2;
-    int r = prepareStage(*X.run, stage == 2);
-    if (r) { fail(j, r); return; }
-    if (X.run->sys.Ea == 0) { endStage(j); return; }
-    if (X.run->sys.n > kCholSolveMaxN) { set_error("reduced camera system of %d rows is wider than the solve kernel's LDS (max %d)", X.run->sys.n, kCholSolveMaxN); fail(j, YDORB_ERR_UNSUPPORTED); return; }
-    fillDev(X, X.dev, B.dDev.as<BaDev>(), dScalAll + (size_t)8 * j, dStatusAll + (size_t)2 * j);
-    if (!(X.it < X.iterations && !X.run->stopped())) { endStage(j); return; }   // `for (it = 0; it < iterations && !terminate(); ...)`
-    X.needBuild = true;
-  };
-  finalize = [&](int j) {   // the final cull, read-back and outlier scatter of a problem (~0.1 ms each, mostly host): deferred, see the end
-    J[j]->pendingEnd = true;
-    J[j]->done = true;
-  };
-  endStage = [&](int j) {
-    Job& X = *J[j];
+    Run& R_ = *X.run;
     X.needBuild = false;
-    int r;
-    if (X.stage == 1 && !(X.O.flags & YDORB_BA_SINGLE_STAGE)) {
-      if (!X.run->stopped()) {   // optimizer.cpp:290-314
-        if ((r = cullAfterFirstStage(*X.run))) { fail(j, r); return; }
-        startStage(j, 2);
-        return;
+    for (int r;; over = true) {
+      if (over) {
+        if (!R_.lm.handOver(R_.P->stop)) { X.pendingEnd = X.done = true; return; }
+        if ((r = launchCull(R_, 0))) { fail(j, r); return; }
       }
-      X.run->res->stopped = 1;
+      if ((r = prepareStage(R_, R_.lm.stage == 2))) { fail(j, r); return; }
+      if (R_.sys.Ea == 0) continue;
+      if (R_.sys.n > kCholSolveMaxN) { fail(j, tooWideForSolve(R_.sys.n)); return; }
+      fillDev(X, X.dev, B.dDev.as<BaDev>(), dScalAll + (size_t)8 * j, dStatusAll + (size_t)2 * j);
+      if (R_.lm.firstIteration(R_.P->stop)) { X.needBuild = true; return; }
     }
-    finalize(j);
   };
-  // end of an outer iteration: the log entry and SolverResult::Terminate, as in optimize()
-  auto endIteration = [&](int j) {
-    Job& X = *J[j];
-    YdBaResult* r = X.run->res;
-    if (r->n_log < 32) {
-      r->log_chi2[r->n_log] = X.currentChi; r->log_lambda[r->n_log] = X.lambda; r->log_trials[r->n_log] = X.qmax; r->log_stage[r->n_log] = X.stage;
-      r->n_log++;
-    }
-    r->n_iterations++;
-    const bool terminate = X.qmax == X.O.max_trials || X.rho == 0 || !std::isfinite(X.lambda);
-    X.it++;
-    if (terminate || !(X.it < X.iterations && !X.run->stopped())) { endStage(j); return; }
-    X.needBuild = true; X.qmax = 0; X.rho = 0;
-  };
-
-  // Set-up of every problem (validation, edge ordering, uploads, pose-pair buckets): ~2 ms of host work and pageable copies per C5-sized
-  // problem, independent of the others, so it is spread over a few host threads, each on its own set-up stream; the lock-step
-  // rounds below then run on the batch's one stream.
-  {
+  // fn(j, stream) for every member, spread over a few host threads, each with a set-up stream of its own; then the error text of a
+  // member that failed becomes the calling thread's
+  auto spread = [&](auto fn) {
     const int nt = std::max(1, std::min(n, kSetupThreads));
-    while ((int)B.setupStreams.size() < nt) {
-      hipStream_t st = nullptr;
-      HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      B.setupStreams.push_back(st);
-    }
     std::atomic<int> next{0};
     auto worker = [&](int t) {
       (void)hipSetDevice(Oin.device);
-      hipStream_t st = B.setupStreams[t];
-      for (int j = next.fetch_add(1); j < n; j = next.fetch_add(1)) {
-        Job& X = *J[j];
-        X.done = false; X.pendingEnd = false; X.rc = YDORB_OK; X.errText.clear();
-        delete X.run; X.run = nullptr;
-        if (rcEach) rcEach[j] = YDORB_OK;
-        int r = checkProblem(&probs[j], &Oin, &res[j], &X.O);
-        const YdBaProblem* P = &probs[j];
-        if (!r) {
-          if (P->stop && *P->stop) { res[j].stopped = 1; X.done = true; continue; }
-          if (P->n_edges == 0 || P->n_poses == 0 || P->n_points == 0) { X.done = true; continue; }
-          X.mem.device = Oin.device; X.mem.stream = st;
-          X.run = new Run{&X.mem, P, &X.O, &res[j]};
-          r = beginSolve(*X.run);
-        }
-        if (!r) {
-          startStage(j, 1);
-          r = X.rc;
-        }
-        if (r) { X.errText = ydorb_last_error(); fail(j, r); }
-        if (hipStreamSynchronize(st) != hipSuccess && !r) { X.errText = "hipStreamSynchronize failed"; fail(j, YDORB_ERR_HIP); }
-        X.mem.stream = s;
-      }
+      for (int j = next.fetch_add(1); j < n; j = next.fetch_add(1)) fn(j, B.setupStreams[t]);
     };
     std::vector<std::thread> pool;
     for (int t = 1; t < nt; t++) pool.emplace_back(worker, t);
     worker(0);
     for (std::thread& th : pool) th.join();
-    for (int j = 0; j < n; j++) if (J[j]->rc != YDORB_OK) set_error("%s", J[j]->errText.c_str());
+    for (int j = 0; j < n; j++) if (J[j]->rc != YDORB_OK && !J[j]->errText.empty()) set_error("%s", J[j]->errText.c_str());
+  };
+
+  // Set-up of every problem (validation, edge ordering, uploads, pose-pair buckets): ~2 ms of host work and pageable copies per C5-sized
+  // problem, independent of the others, so it is spread over a few host threads, each on its own set-up stream; the lock-step
+  // rounds below then run on the batch's one stream.
+  while ((int)B.setupStreams.size() < std::min(n, kSetupThreads)) {
+    hipStream_t st = nullptr;
+    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    B.setupStreams.push_back(st);
   }
+  spread([&](int j, hipStream_t st) {
+    Job& X = *J[j];
+    X.done = false; X.pendingEnd = false; X.rc = YDORB_OK; X.errText.clear();
+    X.run.reset();
+    if (rcEach) rcEach[j] = YDORB_OK;
+    int r = checkProblem(&probs[j], &Oin, &res[j], &X.O);
+    const YdBaProblem* P = &probs[j];
+    if (!r) {
+      if (P->stop && *P->stop) { res[j].stopped = 1; X.done = true; return; }
+      if (P->n_edges == 0 || P->n_poses == 0 || P->n_points == 0) { X.done = true; return; }
+      X.mem.device = Oin.device; X.mem.stream = st;
+      X.run.emplace(Run{&X.mem, P, &X.O, &res[j]});
+      r = beginSolve(*X.run);
+    }
+    if (!r) {
+      nextStage(j, false);
+      r = X.rc;
+    }
+    if (r) { X.errText = ydorb_last_error(); fail(j, r); }
+    if (hipStreamSynchronize(st) != hipSuccess && !r) { X.errText = "hipStreamSynchronize failed"; fail(j, YDORB_ERR_HIP); }
+    X.mem.stream = s;
+  });
   trace("batch: set-up done");
 
   auto maxOver = [&](auto fn) { int m = 0; for (int j = 0; j < n; j++) if (!J[j]->done) m = std::max(m, fn(J[j]->run->sys)); return m; };
   auto rounds = [&]() -> int {
-  while (true) {
-    bool any = false;
-    for (int j = 0; j < n; j++) any = any || !J[j]->done;
-    if (!any) break;
-    trace("batch: round begins");
-    // (a) iteration starts: chi2 of the current estimate where needed, H and b, initial lambda -----------------------------------
-    bool anyBuild = false, anyChi = false, anyDiag = false;
-    for (int j = 0; j < n; j++) {
-      Job& X = *J[j];
-      BaDev& D = hDevA[j];
-      D = X.dev;
-      D.trial = 0;
-      D.build = !X.done && X.needBuild;
-      D.chi2 = D.build && (X.it == 0 || !X.lastAccepted);
-      D.maxdiag = D.build && X.it == 0;
-      D.cur = X.done ? 0 : X.run->cur;
-      D.lambda = X.lambda;
-      anyBuild = anyBuild || D.build; anyChi = anyChi || D.chi2; anyDiag = anyDiag || D.maxdiag;
-    }
-    const int gE = maxOver([](const Sys& Y) { return Y.nBlkE; }), gL128 = maxOver([](const Sys& Y) { return (Y.nL + 127) / 128; }),
-              gL256 = maxOver([](const Sys& Y) { return (Y.nL + 255) / 256; }), gP = maxOver([](const Sys& Y) { return Y.nPf; }),
-              gBk = maxOver([](const Sys& Y) { return Y.nBuckets + 1; }), gNb = maxOver([](const Sys& Y) { return Y.nb; }),
-              gUpd = maxOver([](const Sys& Y) { return (std::max(Y.nPf, Y.nL) + 255) / 256; }),
-              gScale = maxOver([](const Sys& Y) { return (6 * Y.nPf + 3 * Y.nL + 255) / 256; }), gN = maxOver([](const Sys& Y) { return Y.n; });
-    const BaDev* dDev = B.dDev.as<BaDev>();
-    if (anyBuild) {
-      if (lateUploads) HIPCHK(hipLaunchHostFunc(s, lateUpload, nullptr));
-      HIPCHK(hipMemcpyAsync(B.dDev.p, hDevA, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
-      if (anyChi) {
-        hipLaunchKernelGGL(kb_errors, dim3(gE, 1, n), dim3(256), 0, s, dDev, 0);
-        hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 0);
-      }
-      hipLaunchKernelGGL(kb_build_points, dim3(gL128, 1, n), dim3(128), 0, s, dDev);
-      if (gP) hipLaunchKernelGGL(kb_build_poses, dim3(gP, 1, n), dim3(256), 0, s, dDev);
-      if (anyDiag) hipLaunchKernelGGL(kb_max_diag, dim3(1, 1, n), dim3(256), 0, s, dDev);
-      HIPCHK(hipGetLastError());
-      if (anyChi || anyDiag) {
-        HIPCHK(hipMemcpyAsync(hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-      }
+    while (true) {
+      bool any = false;
+      for (int j = 0; j < n; j++) any = any || !J[j]->done;
+      if (!any) break;
+      trace("batch: round begins");
+      // (a) iteration starts: chi2 of the current estimate where needed, H and b, initial lambda -----------------------------------
+      bool anyBuild = false, anyChi = false, anyDiag = false;
       for (int j = 0; j < n; j++) {
         Job& X = *J[j];
-        const BaDev& D = hDevA[j];
-        if (!D.build) continue;
-        if (D.chi2) X.currentChi = hScal[8 * j + 0];
-        if (D.maxdiag) { X.lambda = 1e-5 * hScal[8 * j + 1]; X.ni = 2; }   // computeLambdaInit
-        X.needBuild = false;
-        if (D.maxdiag && noEdgesLeft(X.stage, hScal[8 * j + 1])) endStage(j);   // as in optimize(): no trial, nothing logged
+        BaDev& D = hDevA[j];
+        D = X.dev;
+        D.trial = 0;
+        D.build = !X.done && X.needBuild;
+        D.chi2 = D.build && X.run->lm.needChi2();
+        D.maxdiag = D.build && X.run->lm.needLambdaInit();
+        D.cur = X.done ? 0 : X.run->cur;
+        D.lambda = X.run ? X.run->lm.lambda : 0;
+        anyBuild = anyBuild || D.build; anyChi = anyChi || D.chi2; anyDiag = anyDiag || D.maxdiag;
+      }
+      const int gE = maxOver([](const Sys& Y) { return Y.nBlkE; }), gL128 = maxOver([](const Sys& Y) { return (Y.nL + 127) / 128; }),
+                gL256 = maxOver([](const Sys& Y) { return (Y.nL + 255) / 256; }), gP = maxOver([](const Sys& Y) { return Y.nPf; }),
+                gBk = maxOver([](const Sys& Y) { return Y.nBuckets + 1; }), gNb = maxOver([](const Sys& Y) { return Y.nb; }),
+                gUpd = maxOver([](const Sys& Y) { return (std::max(Y.nPf, Y.nL) + 255) / 256; }),
+                gScale = maxOver([](const Sys& Y) { return (6 * Y.nPf + 3 * Y.nL + 255) / 256; }), gN = maxOver([](const Sys& Y) { return Y.n; });
+      const BaDev* dDev = B.dDev.as<BaDev>();
+      if (anyBuild) {
+        if (lateUploads) HIPCHK(hipLaunchHostFunc(s, lateUpload, nullptr));
+        HIPCHK(hipMemcpyAsync(B.dDev.p, hDevA, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
+        if (anyChi) {
+          hipLaunchKernelGGL(kb_errors, dim3(gE, 1, n), dim3(256), 0, s, dDev, 0);
+          hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 0);
+        }
+        hipLaunchKernelGGL(kb_build_points, dim3(gL128, 1, n), dim3(128), 0, s, dDev);
+        if (gP) hipLaunchKernelGGL(kb_build_poses, dim3(gP, 1, n), dim3(256), 0, s, dDev);
+        if (anyDiag) hipLaunchKernelGGL(kb_max_diag, dim3(1, 1, n), dim3(256), 0, s, dDev);
+        HIPCHK(hipGetLastError());
+        if (anyChi || anyDiag) {
+          HIPCHK(hipMemcpyAsync(hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
+          HIPCHK(hipStreamSynchronize(s));
+        }
+        for (int j = 0; j < n; j++) {
+          Job& X = *J[j];
+          const BaDev& D = hDevA[j];
+          if (!D.build) continue;
+          if (D.chi2) X.run->lm.setChi2(hScal[8 * j + 0]);
+          X.needBuild = false;
+          if (D.maxdiag && !X.run->lm.setMaxDiag(hScal[8 * j + 1])) nextStage(j, true);
+        }
+      }
+      // (b) one LM trial of every unfinished problem ----------------------------------------------------------------------------------
+      for (int j = 0; j < n; j++) {
+        Job& X = *J[j];
+        BaDev& D = hDevB[j];
+        D = X.dev;
+        D.build = D.chi2 = D.maxdiag = 0;
+        D.trial = !X.done;
+        D.lambda = X.run ? X.run->lm.lambda : 0;
+        D.cur = X.done ? 0 : X.run->cur;
+      }
+      if (lateUploads) HIPCHK(hipLaunchHostFunc(s, lateUpload, nullptr));
+      HIPCHK(hipMemcpyAsync(B.dDev.p, hDevB, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(kb_dinv, dim3(gL256, 1, n), dim3(256), 0, s, dDev);
+      hipLaunchKernelGGL(kb_bd, dim3(gE, 1, n), dim3(256), 0, s, dDev);
+      if (gP) hipLaunchKernelGGL(kb_bs, dim3(gP, 1, n), dim3(256), 0, s, dDev);
+      hipLaunchKernelGGL(kb_schur_pairs, dim3(gBk, 1, n), dim3(64 * kSchurWaves), 0, s, dDev);
+      for (int kb = 0; kb < gNb; kb++)
+        hipLaunchKernelGGL(kb_chol_step, dim3((gNb - kb) * (gNb - kb + 1) / 2 + (kb > 0), 1, n), dim3(256), 0, s, dDev, kb);
+      {
+        const size_t dyn = sizeof(double) * (size_t)gN;
+        if (dyn > 48 * 1024)
+          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kb_chol_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+        hipLaunchKernelGGL(kb_chol_solve, dim3(1, 1, n), dim3(1024), dyn, s, dDev);
+      }
+      hipLaunchKernelGGL(kb_backsub, dim3(gL128, 1, n), dim3(128), 0, s, dDev);
+      hipLaunchKernelGGL(kb_update, dim3(gUpd, 1, n), dim3(256), 0, s, dDev);
+      hipLaunchKernelGGL(kb_scale, dim3(gScale, 1, n), dim3(256), 0, s, dDev);
+      hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 2);
+      hipLaunchKernelGGL(kb_errors, dim3(gE, 1, n), dim3(256), 0, s, dDev, 1);
+      hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 1);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      trace("batch: round synchronised");
+      // (c) the LM decision of every problem (optimization_algorithm_levenberg.cpp:95-146, as in optimize()) -----------------------------------
+      for (int j = 0; j < n; j++) {
+        Job& X = *J[j];
+        if (X.done) continue;
+        const double* hs = hScal + (size_t)8 * j;
+        const LmSchedule::Next next = X.run->lm.trial(hs[0], hs[2], (int)hs[6] == 0, X.run->P->stop);
+        if (X.run->lm.lastAccepted) X.run->cur ^= 1;
+        X.needBuild = next == LmSchedule::NextIteration;
+        if (next == LmSchedule::StageOver) nextStage(j, true);
       }
     }
-    // (b) one LM trial of every unfinished problem ----------------------------------------------------------------------------------
-    for (int j = 0; j < n; j++) {
-      Job& X = *J[j];
-      BaDev& D = hDevB[j];
-      D = X.dev;
-      D.build = D.chi2 = D.maxdiag = 0;
-      D.trial = !X.done;
-      D.lambda = X.lambda;
-      D.cur = X.done ? 0 : X.run->cur;
-    }
-    if (lateUploads) HIPCHK(hipLaunchHostFunc(s, lateUpload, nullptr));
-    HIPCHK(hipMemcpyAsync(B.dDev.p, hDevB, sizeof(BaDev) * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(kb_dinv, dim3(gL256, 1, n), dim3(256), 0, s, dDev);
-    hipLaunchKernelGGL(kb_bd, dim3(gE, 1, n), dim3(256), 0, s, dDev);
-    if (gP) hipLaunchKernelGGL(kb_bs, dim3(gP, 1, n), dim3(256), 0, s, dDev);
-    hipLaunchKernelGGL(kb_schur_pairs, dim3(gBk, 1, n), dim3(64 * kSchurWaves), 0, s, dDev);
-    for (int kb = 0; kb < gNb; kb++)
-      hipLaunchKernelGGL(kb_chol_step, dim3((gNb - kb) * (gNb - kb + 1) / 2 + (kb > 0), 1, n), dim3(256), 0, s, dDev, kb);
-    {
-      const size_t dyn = sizeof(double) * (size_t)gN;
-      if (dyn > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kb_chol_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-      hipLaunchKernelGGL(kb_chol_solve, dim3(1, 1, n), dim3(1024), dyn, s, dDev);
-    }
-    hipLaunchKernelGGL(kb_backsub, dim3(gL128, 1, n), dim3(128), 0, s, dDev);
-    hipLaunchKernelGGL(kb_update, dim3(gUpd, 1, n), dim3(256), 0, s, dDev);
-    hipLaunchKernelGGL(kb_scale, dim3(gScale, 1, n), dim3(256), 0, s, dDev);
-    hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 2);
-    hipLaunchKernelGGL(kb_errors, dim3(gE, 1, n), dim3(256), 0, s, dDev, 1);
-    hipLaunchKernelGGL(kb_sum_partials, dim3(1, 1, n), dim3(256), 0, s, dDev, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hScal, dScalAll, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    trace("batch: round synchronised");
-    // (c) the LM decision of every problem (optimization_algorithm_levenberg.cpp:95-146, as in optimize()) -----------------------------------
-    for (int j = 0; j < n; j++) {
-      Job& X = *J[j];
-      if (X.done) continue;
-      const double* hs = hScal + (size_t)8 * j;
-      const double tempChi = hs[0], scaleSum = hs[2];
-      X.lastAccepted = lm_judge(X.lambda, X.ni, X.currentChi, X.rho, tempChi, scaleSum + 1e-3, (int)hs[6] == 0);
-      if (X.lastAccepted) X.run->cur ^= 1;  // discardTop(): keep the updated estimate; else pop(): the previous one is still in poses[cur]
-      const bool lambdaBroke = !X.lastAccepted && !std::isfinite(X.lambda);
-      X.qmax++;
-      X.run->res->n_trials++;
-      if (lambdaBroke || !(X.rho < 0 && X.qmax < X.O.max_trials && !X.run->stopped())) endIteration(j);
-    }
-  }
-  return YDORB_OK;
+    return YDORB_OK;
   };
   {
     // a HIP error inside the rounds ends the group: every member that has not been read back reports it (its poses / points / outlier
@@ -834,27 +783,15 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
       return rr;
     }
   }
-  {  // endSolve of every finished problem, spread over the set-up threads and streams (the lock-step stream has drained)
-    const int nt = std::max(1, std::min(n, (int)B.setupStreams.size()));
-    std::atomic<int> next{0};
-    auto worker = [&](int t) {
-      (void)hipSetDevice(Oin.device);
-      for (int j = next.fetch_add(1); j < n; j = next.fetch_add(1)) {
-        Job& X = *J[j];
-        if (!X.pendingEnd) continue;
-        X.pendingEnd = false;
-        X.mem.stream = B.setupStreams[t];
-        const int r = endSolve(*X.run);
-        X.mem.stream = s;
-        if (r) { X.errText = ydorb_last_error(); fail(j, r); }
-      }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; t++) pool.emplace_back(worker, t);
-    worker(0);
-    for (std::thread& th : pool) th.join();
-    for (int j = 0; j < n; j++) if (J[j]->rc != YDORB_OK && !J[j]->errText.empty()) set_error("%s", J[j]->errText.c_str());
-  }
+  spread([&](int j, hipStream_t st) {   // endSolve of every finished problem (the lock-step stream has drained)
+    Job& X = *J[j];
+    if (!X.pendingEnd) return;
+    X.pendingEnd = false;
+    X.mem.stream = st;
+    const int r = endSolve(*X.run);
+    X.mem.stream = s;
+    if (r) { X.errText = ydorb_last_error(); fail(j, r); }
+  });
   trace("batch: done");
   int first = YDORB_OK;
   for (int j = 0; j < n; j++) if (J[j]->rc != YDORB_OK && first == YDORB_OK) first = J[j]->rc;
@@ -898,15 +835,11 @@ int ydorb_ba_solve(const YdBaProblem* P, const YdBaOptions* optIn, YdBaResult* r
   hipEvent_t t0 = c.ev[2 * PH_COUNT], t1 = c.ev[2 * PH_COUNT + 1];
   HIPCHK(hipEventRecord(t0, c.mem.stream));
 
-  if ((rc = optimize(R_, O.iters1, 1, false))) return rc;
-  if (O.flags & YDORB_BA_SINGLE_STAGE) {
-    // bundleAdjust: one optimize() call, nothing culled
-  } else if (!R_.stopped()) {  // optimizer.cpp:290-314
-    if ((rc = cullAfterFirstStage(R_))) return rc;
+  for (;;) {   // bundleAdjust: one optimize() call, nothing culled; localBundleAdjust: two, unless stopped in between
+    if ((rc = optimize(R_))) return rc;
+    if (!R_.lm.handOver(P->stop)) break;
+    if ((rc = launchCull(R_, 0))) return rc;
     trace("solve: depths read");
-    if ((rc = optimize(R_, O.iters2, 2, true))) return rc;
-  } else {
-    res->stopped = 1;
   }
   HIPCHK(hipEventRecord(t1, c.mem.stream));
   if ((rc = endSolve(R_))) return rc;

@@ -1,13 +1,16 @@
 // The g2o / Eigen pieces that every Levenberg-Marquardt back-end here restates, once: local and global BA and the pose-only
 // optimisation (ba_kernels.hip.h, ba_solver.hip) and the Sim3 check (sim3_kernels.hip.h).  Quaternion algebra of Eigen and
 // types/slam3d/se3quat.h, Huber of core/robust_kernel_impl.cpp, the fixed-order workgroup sums the bit-exact contract rests on,
-// LinearSolverDense for a handful of unknowns, and the lambda control of core/optimization_algorithm_levenberg.cpp.
+// LinearSolverDense for a handful of unknowns, and the lambda control of core/optimization_algorithm_levenberg.cpp (lm_judge, which
+// comes from the HIP-free lm_schedule.h so that the host schedule of BA shares it).
 // Functions and types only - no __device__ / __constant__ variable and no kernel - so any translation unit includes it freely.
 // The oracle and tests/*_ref stay independent restatements and do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
+
+#include "lm_schedule.h"
 
 #pragma clang fp contract(off)
 
@@ -154,28 +157,6 @@ __device__ __forceinline__ R lambda_init(const R (&Hs)[N * (N + 1) / 2]) {
 #pragma unroll
   for (int r = 0; r < N; r++) { mx = fmax(fabs(Hs[k]), mx); k += N - r; }
   return 1e-5 * mx;
-}
-
-// The verdict on one LM trial (optimization_algorithm_levenberg.cpp:95-146), for the device loops and the host loops alike.
-// tempChi is the chi2 of the trial estimate - g2o applies _x and evaluates it even when the solve failed (solved == false) and then
-// overrides it with DBL_MAX.  scale is computeScale() + 1e-3, formed by the caller in the order its results have always had (the dense
-// device loops start their sum from the 1e-3, the BA host loops add it to the device's sum), because results are compared bit for bit.
-// Accept: lambda shrinks, ni = 2, currentChi = tempChi; reject: lambda *= ni, ni doubles.  The caller keeps its own push / pop, trial
-// counters and the non-finite-lambda break.
-__host__ __device__ __forceinline__ bool lm_judge(R& lambda, R& ni, R& currentChi, R& rho, R tempChi, R scale, bool solved) {
-  if (!solved) tempChi = 1.7976931348623157e308;   // DBL_MAX
-  rho = currentChi - tempChi;
-  rho /= scale;
-  if (rho > 0 && std::isfinite(tempChi)) {
-    R alpha = 1. - pow((2 * rho - 1), 3.0);
-    alpha = fmin(alpha, 2. / 3.);
-    lambda *= fmax(1. / 3., alpha);
-    ni = 2;
-    currentChi = tempChi;
-    return true;
-  }
-  lambda *= ni; ni *= 2;
-  return false;
 }
 
 }  // namespace g2o
