@@ -735,6 +735,77 @@ int ydorb_search_local_points(ydorb_matcher_t* h, const YdFrameView* frame, cons
                               const uint8_t* skip, const uint8_t* has_observations, float th, float ratio, uint8_t* taken,
                               int32_t* assigned, YdTrackView* rows, uint8_t* status, int32_t* n_to_match, int32_t* n_matches);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame construction.  The tail of the RGB-D Frame constructor after extractAndCompute (src/frame.cpp:99-100,134-145):
+ * undistortKeyPoints, computeStereoFromRGBD, computeImageBounds and assignKeyPointsToGrid.  The reference source is restated from
+ * ORB-SLAM2's Frame::UndistortKeyPoints / ComputeStereoFromRGBD / ComputeImageBounds / AssignFeaturesToGrid, which YDORBSLAM renames;
+ * DESIGN.md section 2 ("Frame tail: the arithmetic contract") states the arithmetic and lists what a maintainer with the reference
+ * must check.  Its undistorted keypoints are what every matcher entry above takes as "the undistorted ones".
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdCamera {       /* m_cvMat_intParMat and m_cvMat_distCoef as floats (frame.cpp:134-145) */
+  float fx, fy, cx, cy;
+  float dist[5];                /* k1 k2 p1 p2 k3 */
+  int32_t n_iter;               /* iterations of cv::undistortPoints: 5 = its public overload's criterion; >= 1 */
+} YdCamera;
+/* Undistortion, in fp64 on floats widened to double: x0 = x = (u - cx) * (1.0 / fx), y0 = y = (v - cy) * (1.0 / fy); n_iter times
+ * r2 = x x + y y, icdist = 1.0 / (1.0 + ((k3 r2 + k2) r2 + k1) r2), [icdist < 0: x = x0, y = y0, stop, status bit 2],
+ * dX = 2.0 p1 x y + p2 (r2 + 2.0 x x), dY = p1 (r2 + 2.0 y y) + 2.0 p2 x y, x = (x0 - dX) icdist, y = (y0 - dY) icdist; the result is
+ * (float)(fx x + cx), (float)(fy y + cy).  k1 == 0.0f copies the points, whatever the other coefficients are (frame.cpp:134-145). */
+/* xy, xy_out: float [n][2] (host).  frame.cpp:134-145 */
+int ydorb_undistort_points(const YdCamera* cam, const float* xy, int32_t n, float* xy_out, int32_t device);
+/* Frame::computeImageBounds, frame.cpp:99-100: the corners (0,0) (w,0) (0,h) (w,h) through the undistortion above, on the device;
+ * bounds = min_x, max_x, min_y, max_y = min(c0.x, c2.x), max(c1.x, c3.x), min(c0.y, c1.y), max(c2.y, c3.y); k1 == 0: 0, w, 0, h. */
+int ydorb_image_bounds(const YdCamera* cam, int32_t w, int32_t hgt, float* bounds, int32_t device);
+
+#define YDORB_DEPTH_NONE 0      /* monocular tail: right_x = depth = -1 */
+#define YDORB_DEPTH_U16 1       /* uint16 image, d = (float)raw * depth_factor (imDepth.convertTo(CV_32F, factor)) */
+#define YDORB_DEPTH_F32 2       /* float image, as it is */
+#define YDORB_DEPTH_SAMPLES 3   /* float [n_frames][cap]: one scaled sample per keypoint, gathered by the caller */
+#define YDORB_FRAME_DEPTH_AT_UNDISTORTED 1 /* index the depth image with the undistorted keypoint (default: the raw one) */
+#define YDORB_FRAME_DEVICE_POINTERS 2      /* every array is a device pointer; asynchronous on `stream` */
+#define YDORB_FRAME_STATUS_DEPTH_INDEX 1   /* status bit 0: a keypoint's depth pixel lay outside the image (no depth) */
+#define YDORB_FRAME_STATUS_ICDIST 4        /* status bit 2: icdist < 0 ended a keypoint's undistortion */
+typedef struct YdFrameTail {
+  const YdKeyPoint* kps;        /* [n_frames][cap] as extracted */
+  const int32_t* n;             /* [n_frames], each <= cap */
+  int32_t n_frames, cap;
+  const void* depth;            /* image of frame f at depth + f * depth_frame_stride bytes; samples: float [n_frames][cap]; NULL with NONE */
+  int32_t depth_type;           /* YDORB_DEPTH_* */
+  int32_t depth_w, depth_h;     /* image forms */
+  int64_t depth_row_stride;     /* bytes per image row, >= depth_w elements */
+  int64_t depth_frame_stride;   /* bytes between the images of consecutive frames */
+  float depth_factor;           /* U16 only (m_flt_depthMapFactor) */
+  float bf;                     /* m_flt_baseLineTimesFx */
+  YdCamera cam;
+  float bounds[4];              /* min_x, max_x, min_y, max_y of ydorb_image_bounds; read for the grid only */
+  int32_t flags;                /* YDORB_FRAME_* */
+  int32_t device;
+} YdFrameTail;
+/* frame.cpp:134-145 for a batch of frames.  Outputs, each may be NULL and is then skipped: kps_un [n_frames][cap] (the other keypoint
+ * fields are copied); right_x, depth [n_frames][cap] = m_v_rightXcords / m_v_depth: the depth pixel is ((int)kp.y, (int)kp.x) of the
+ * raw keypoint, truncating (a coordinate in (-1, size) is inside; anything else, NaN included, is an unchecked Mat::at in the
+ * reference and gives no depth and status bit 0 here); d > 0 gives depth = d, right_x = un.x - bf / d (float), anything else -1 / -1;
+ * cell_start [n_frames][3073], cell_idx [n_frames][cap]: the 64x48 grid of kps_un as a CSR, cell ix * 48 + iy, indices ascending in
+ * a cell, keypoints outside the grid left out, with the matcher's cell rule (it rounds and offsets y by min_x); status [n_frames].
+ * Slots n .. cap of an output are unspecified.  Host form: one upload, the kernels, one read-back, one synchronise.  With
+ * YDORB_FRAME_DEVICE_POINTERS the call is asynchronous on `stream` (a hipStream_t, or the tail's own when NULL), ordered by the caller
+ * behind ydorb_extract_batch_device; it does not synchronise and allocates nothing after the first call of a size; kps_un is then what
+ * ydorb_match_consecutive_device / YdFrameSetDev take.  cap <= 65535 when the grid is asked for. */
+int ydorb_frame_tail(const YdFrameTail* tail, YdKeyPoint* kps_un, float* right_x, float* depth, int32_t* cell_start, int32_t* cell_idx,
+                     int32_t* status, void* stream);
+/* The RGB-D constructor's device work in one call, on one stream with one synchronise (frame.cpp:99-100,134-145 behind
+ * extractAndCompute): upload of gray and depth, ydorb_extract_batch_device, the tail kernels, one read-back; the extractor's capacity
+ * status (ydorb_extractor_synchronize on its then idle streams) is checked behind it.  depth: image of the
+ * gray image's size with depth_stride bytes per row, depth_type NONE (or depth NULL: the monocular tail), U16 or F32.  kps_raw, desc,
+ * n_out as ydorb_extract fills them; the remaining outputs as ydorb_frame_tail's for one frame, each may be NULL (bounds may be NULL
+ * when no grid is asked for).  An empty image returns YDORB_OK with *n_out = 0. */
+int ydorb_extract_rgbd(ydorb_extractor_t* h, const uint8_t* gray, int32_t w, int32_t hgt, int32_t stride, const void* depth,
+                       int32_t depth_type, int32_t depth_stride, float depth_factor, const YdCamera* cam, float bf, const float* bounds,
+                       int32_t flags, YdKeyPoint* kps_raw, YdKeyPoint* kps_un, uint8_t* desc, float* right_x, float* depth_out,
+                       int32_t* cell_start, int32_t* cell_idx, int32_t cap, int32_t* n_out, int32_t* status);
+/* The frame-construction entries keep device scratch per device between calls; this frees it (waiting for calls in flight). */
+int ydorb_frame_release(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

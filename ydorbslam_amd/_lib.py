@@ -101,6 +101,12 @@ SYMBOLS = {
     "ydorb_frustum_cull": (C.c_int, [_VP, _VP, _VP, _VP]),
     "ydorb_frustum_release": (C.c_int, [_I]),
     "ydorb_search_local_points": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP, C.POINTER(_I), C.POINTER(_I)]),
+    "ydorb_undistort_points": (C.c_int, [_VP, _VP, _I, _VP, _I]),
+    "ydorb_image_bounds": (C.c_int, [_VP, _I, _I, _VP, _I]),
+    "ydorb_frame_tail": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_extract_rgbd": (C.c_int, [_VP, _VP, _I, _I, _I, _VP, _I, _I, C.c_float, _VP, C.c_float, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I,
+                                     C.POINTER(_I), C.POINTER(_I)]),
+    "ydorb_frame_release": (C.c_int, [_I]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -160,6 +166,16 @@ class YdMapPointTable(C.Structure):
 class YdFrustumBatch(C.Structure):
     _fields_ = [("device", _I), ("n_views", _I), ("views", _VP), ("table", YdMapPointTable), ("list_start", _VP), ("point_idx", _VP),
                 ("skip", _VP)]
+
+
+class YdCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("dist", C.c_float * 5), ("n_iter", _I)]
+
+
+class YdFrameTail(C.Structure):
+    _fields_ = [("kps", _VP), ("n", _VP), ("n_frames", _I), ("cap", _I), ("depth", _VP), ("depth_type", _I), ("depth_w", _I), ("depth_h", _I),
+                ("depth_row_stride", C.c_int64), ("depth_frame_stride", C.c_int64), ("depth_factor", C.c_float), ("bf", C.c_float),
+                ("cam", YdCamera), ("bounds", C.c_float * 4), ("flags", _I), ("device", _I)]
 
 
 class YdBaOptions(C.Structure):

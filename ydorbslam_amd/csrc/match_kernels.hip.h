@@ -20,11 +20,12 @@
 
 #include <type_traits>
 
+#include "grid_build.hip.h"
+
 #pragma clang fp contract(off)
 
 namespace ydorb {
 
-constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;  // frame.hpp:137-138
 constexpr int kHistLen = 30, kThHigh = 100, kThLow = 50;                             // orbMatcher.cpp:7-9
 
 // A pointer that a kernel reads out of a record in memory (CallDev, FrameDev, ...) is a FLAT pointer to the compiler: its loads and
@@ -33,26 +34,12 @@ constexpr int kHistLen = 30, kThHigh = 100, kThLow = 50;                        
 template <class T> using gptr = __attribute__((address_space(1))) T*;
 template <class T> __device__ __forceinline__ gptr<T> G(T* p) { return (gptr<T>)p; }
 
-struct KeyPointDev { float x, y, size, angle, response; int octave, class_id; };
 struct QueryDev {  // == YdQuery
   float u, v, r;
   int minLevel, maxLevel;
   float ur, rs, angle;
   int level, flags;
 };
-struct FrameDev {  // one target frame of a batched call
-  const KeyPointDev* kps;
-  const uint8_t* desc;
-  const float* rightX;  // may be null (monocular: every entry <= 0)
-  const int* nPtr;      // device count (batched pipeline) or null
-  int n;                // used when nPtr is null
-  float minX, minY, gridWInv, gridHInv;
-  int* cellStart;       // [kGridCells + 1]
-  int* cellIdx;         // [cap]
-  float4* sortedKp;     // [cap] (x, y, octave bits, index bits) in grid (CSR) order: a window column is one contiguous run
-  uint8_t* sortedDesc;  // [cap][32] descriptors in the same order
-};
-__device__ __forceinline__ int frame_n(const FrameDev& F) { return F.nPtr ? *F.nPtr : F.n; }
 
 // ---------------------------------------------------------------------------------------------------
 // Frame::assignKeyPointsToGrid + computeLocationInGrid (frame.cpp:249-264,327-336): rounds, and uses minX for y.
@@ -62,54 +49,7 @@ __global__ __launch_bounds__(256) void k_grid_build(const FrameDev* __restrict__
   __shared__ int wsum[4];
   extern __shared__ int16_t cellOf[];  // [cap]
   const FrameDev F = frames[blockIdx.x];
-  const int n = min(frame_n(F), cap);
-  for (int c = threadIdx.x; c < kGridCells; c += 256) hist[c] = 0;
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const KeyPointDev kp = F.kps[i];
-    const int lx = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.minX), F.gridWInv));
-    const int ly = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.minX), F.gridHInv));
-    int cell = -1;
-    if (!(lx < 0 || lx >= kGridCols || ly < 0 || ly >= kGridRows)) {
-      cell = lx * kGridRows + ly;
-      atomicAdd(&hist[cell], 1);
-    }
-    cellOf[i] = (int16_t)cell;
-  }
-  __syncthreads();
-  // exclusive scan of 3072 counts: 12 per thread
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int local[12], s = 0;
-#pragma unroll
-  for (int k = 0; k < 12; k++) { local[k] = s; s += hist[threadIdx.x * 12 + k]; }
-  int x = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-  if (lane == 63) wsum[wv] = x;
-  __syncthreads();
-  int off = x - s;
-  for (int j = 0; j < wv; j++) off += wsum[j];
-#pragma unroll
-  for (int k = 0; k < 12; k++) F.cellStart[threadIdx.x * 12 + k] = off + local[k];
-  if (threadIdx.x == 255) F.cellStart[kGridCells] = off + s;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 12; k++) hist[threadIdx.x * 12 + k] = off + local[k];  // now: start offsets
-  __syncthreads();
-  // stable fill: rank inside the cell = number of earlier keypoints with the same cell
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int cell = cellOf[i];
-    if (cell < 0) continue;
-    int rank = 0;
-    for (int j = 0; j < i; j++) rank += cellOf[j] == cell;
-    const int pos = hist[cell] + rank;
-    F.cellIdx[pos] = i;
-    const KeyPointDev kp = F.kps[i];
-    F.sortedKp[pos] = make_float4(kp.x, kp.y, __int_as_float(kp.octave), __int_as_float(i));
-    const uint4* d = reinterpret_cast<const uint4*>(F.desc + (size_t)i * 32);
-    uint4* o = reinterpret_cast<uint4*>(F.sortedDesc + (size_t)pos * 32);
-    o[0] = d[0]; o[1] = d[1];
-  }
+  grid_build<true>(F, cap, hist, wsum, cellOf);
 }
 
 __device__ __forceinline__ int hamming256(const uint8_t* a, const uint8_t* b) {
