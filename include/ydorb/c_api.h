@@ -361,6 +361,10 @@ int ydorb_vocabulary_transform(ydorb_vocabulary_t* h, const uint8_t* desc, const
  * adapter; this call receives the flat graph that :175-283 would hand to g2o and runs :284-334 on the GPU:
  * optimize(5) with Huber kernels -> mark edges with chi2 > 5.991 (mono) / 7.815 (stereo) or non-positive depth and drop
  * the kernels -> optimize(10) on the inliers -> final outlier list.
+ * Precondition: at most ONE edge per (pose, point) pair, fixed poses included.  The reference cannot produce two: a map point's
+ * observations are a std::map<shared_ptr<KeyFrame>, size_t> (MapPoint::getObservations(), walked at optimizer.cpp:232-282), one
+ * entry per keyframe.  A problem that repeats a pair is refused with YDORB_ERR_INVALID_ARG on the host, before any kernel runs
+ * and with poses / points untouched (ydorb_ba_solve, every member of ydorb_ba_solve_batch on its own, every rank of a sharded solve).
  * ---------------------------------------------------------------------------------------- */
 typedef struct YdBaProblem {
   int32_t n_poses, n_points, n_edges;

@@ -250,18 +250,31 @@ int prepareStage(Run& R_, bool reuse) {
       for (int k = 0; k < K; k++) { poseIdx[k] = -1; if (!P.pose_fixed[k]) { poseIdx[k] = (int)poseOf.size(); poseOf.push_back(k); } }
     }
     const int nPf = (int)poseOf.size();
-    {  // order by (landmark index, pose index, edge index): counting sort by landmark, then a tiny insertion sort per landmark
+    {  // order by (landmark index, free-pose index, caller's pose index): counting sort by landmark, then a tiny insertion sort per
+       // landmark.  The fixed poses all have free-pose index -1, so the caller's index orders them: the device order, and with it every
+       // summation order, depends on the SET of edges and not on the order the caller lists them in.
       std::vector<int> start(nL + 1, 0), sorted(Ea);
       for (int e : act) start[ptIdx[P.edge_point[e]] + 1]++;
       for (int l = 0; l < nL; l++) start[l + 1] += start[l];
       std::vector<int> fill(start.begin(), start.end() - 1);
-      for (int e : act) sorted[fill[ptIdx[P.edge_point[e]]]++] = e;   // act is ascending: stable
+      for (int e : act) sorted[fill[ptIdx[P.edge_point[e]]]++] = e;
+      auto after = [&](int x, int y) {   // edge x belongs behind edge y of the same landmark
+        const int px = poseIdx[P.edge_pose[x]], py = poseIdx[P.edge_pose[y]];
+        return px != py ? px > py : P.edge_pose[x] > P.edge_pose[y];
+      };
       for (int l = 0; l < nL; l++)
         for (int a = start[l] + 1; a < start[l + 1]; a++) {
-          const int e = sorted[a], pe = poseIdx[P.edge_pose[e]];
+          const int e = sorted[a];
           int b = a - 1;
-          while (b >= start[l] && (poseIdx[P.edge_pose[sorted[b]]] > pe || (poseIdx[P.edge_pose[sorted[b]]] == pe && sorted[b] > e))) { sorted[b + 1] = sorted[b]; b--; }
+          while (b >= start[l] && after(sorted[b], e)) { sorted[b + 1] = sorted[b]; b--; }
           sorted[b + 1] = e;
+          // One edge per (pose, landmark), fixed poses included (c_api.h, YdBaProblem): e now follows the edge it does not sort behind, and
+          // that one is of the same pose exactly when the pair repeats.  k_pair_sort ranks the items of a pose-pair bucket by their first
+          // edge; two items with one key would share a slot of its output and leave another slot unwritten.
+          if (b >= start[l] && P.edge_pose[sorted[b]] == P.edge_pose[e]) {
+            set_error("edges %d and %d are both the observation of point %d by pose %d", sorted[b], e, P.edge_point[e], P.edge_pose[e]);
+            return YDORB_ERR_INVALID_ARG;
+          }
         }
       act.swap(sorted);
     }
