@@ -243,6 +243,46 @@ def scenario(n_kf, seed, q_sizes=(1, 7, 64)):
     return ops
 
 
+def growth_scenario(seed=22, n_first=40, n_second=50):
+    """Growth after use, for a database created with slot_capacity=1, word_capacity=1 (64 slots, 1024 words): add n_first key frames in one
+    call / covisibility / relocalisation queries (they write scores) / erase every third key frame / add n_second key frames in one call /
+    covisibility / queries in both forms / score.  The second add takes the freed slots and n_second - n_first // 3 more, which passes 64
+    slots while scores are resident; it holds more words than the first, and the pool's capacity is twice what the first stored, so the
+    pool is compacted over erased rows while the device's slot table lags behind the host's.  Both batches draw from every place of
+    the world (a random order of creation), so the new key frames have old ones as neighbours and the later queries read old scores."""
+    n = n_first + n_second
+    W = World(seed, n)
+    rng = W.rng
+    world_of = [int(x) for x in rng.permutation(n)]            # creation index -> index into W.vectors
+    kf_of = {w: k for k, w in enumerate(world_of)}
+
+    def words(kfs):
+        return sum(len(W.vectors[world_of[k]][0]) for k in kfs)
+
+    def covis(kfs, live):
+        return ("covis", list(kfs), [[kf_of[m] for m in W.covisibility(world_of[k]) if kf_of[m] in live] for k in kfs])
+
+    def reloc(Q):
+        return ("reloc", [W.query(int(rng.integers(1, 4))) for _ in range(Q)])
+
+    first, second = list(range(n_first)), list(range(n_first, n))
+    gone = first[::3]
+    live = set(first) - set(gone)
+    assert len(second) > len(live) and n_first + len(second) - len(gone) > 64
+    assert words(first) > 1024 and words(second) > words(first)
+    ops = [("add", [W.vectors[world_of[k]] for k in first]), covis(first, set(first)), reloc(6), ("erase", gone),
+           ("add", [W.vectors[world_of[k]] for k in second])]
+    live |= set(second)
+    ops.append(covis(sorted(live), live))
+    ops.append(reloc(7))
+    Q = 5
+    conn = [[int(x) for x in rng.choice(sorted(live), int(rng.integers(0, 15)), replace=False)] for _ in range(Q)]
+    ops.append(("loop", [W.query(2) for _ in range(Q)], conn, [float(np.float32(rng.choice([0.0, 0.005, 0.02]))) for _ in range(Q)]))
+    ops.append(reloc(1))
+    ops.append(("score", W.query(2), sorted(live)[::4]))
+    return ops
+
+
 # name -> (key frames, seed).  tests/test_kfdb_cpu.py asserts on the restatement that these are not trivial.  n0 and n1 cannot return two
 # candidates; n90, n150 and n600 are there so that, over the whole set, at least half of the queries still do.
 SCENARIOS = {"n0": (0, 11), "n1": (1, 12), "n37": (37, 13), "n90": (90, 17), "n150": (150, 15), "n600": (600, 16), "n3000": (3000, 14)}
@@ -274,9 +314,10 @@ def replay_ref(ops, scoring, diag="last"):
     return out
 
 
-def replay_gpu(ops, scoring, batch=True, **create):
+def replay_gpu(ops, scoring, batch=True, sizes=None, **create):
     """The scenario on the product; key frames are mapped to slots here.  batch=False issues every query in a call of its own.
-    Records as replay_ref's, with key-frame numbers in place of slots; the diagnostics are those of the last query of each operation."""
+    Records as replay_ref's, with key-frame numbers in place of slots; the diagnostics are those of the last query of each operation.
+    sizes: a list that receives db.size() after every add."""
     from ydorbslam_amd.kfdb import KeyFrameDatabase
     db = KeyFrameDatabase(scoring, **create)
     slot_of, kf_of, created = {}, {}, 0
@@ -294,6 +335,8 @@ def replay_gpu(ops, scoring, batch=True, **create):
                 slot_of[created] = s
                 kf_of[s] = created
                 created += 1
+            if sizes is not None:
+                sizes.append(db.size())
         elif op[0] == "erase":
             db.erase([slot_of[k] for k in op[1]])
             for k in op[1]:

@@ -34,6 +34,26 @@ def test_transform_matches_the_oracle(oracle_lib, weighting, norm):
     _check(oracle_lib, tree, voc, descs[:2], 4, weighting, norm)   # levelsup >= L: everything under the root
 
 
+def test_call_memory_reused_across_shapes(oracle_lib):
+    """One handle, batches whose per-call memory is laid out differently each time: 1 x 1 (an odd number of result ints before the
+    doubles), 3 frames up to 2048 with an empty one, 1 and 0 descriptors, 5 frames up to 300.  Then the first batch on a fresh handle
+    equals the first batch on the used one, array for array."""
+    import ydorbslam_amd as y
+    tree = synth_vocabulary(10, 4, seed=3)
+    voc = y.Vocabulary(tree)
+    shapes = [(1,), (2048, 0, 777), (1, 0), (300, 17, 255, 64, 129)]
+    batches = [[_descriptors(tree, n, 300 + 10 * b + i) for i, n in enumerate(ns)] for b, ns in enumerate(shapes)]
+    first = voc.transform(batches[0], 2)
+    for descs in batches:
+        _check(oracle_lib, tree, voc, descs, 2, "TF_IDF", "L1", expect_status=0)
+    fresh = y.Vocabulary(tree).transform(batches[0], 2)
+    for used in (first, voc.transform(batches[0], 2)):   # the handle's first call, and the same batch after the other shapes
+        assert len(used) == len(fresh) == 1
+        for a, b in zip(used[0][:5], fresh[0][:5]):
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+        assert used[0][5] == fresh[0][5]
+
+
 def test_orb_vocabulary_shape_on_extracted_descriptors(oracle_lib):
     """k = 10, L = 6 is the shape of the reference's ORB vocabulary (frame.cpp:269-270); 10^6 words would be 35 MB of node
     descriptors, so the synthetic tree thins out below level 3.  Descriptors come from the extractor."""

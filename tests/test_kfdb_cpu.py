@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from kfdb_support import ROOT, SCENARIOS, SCORINGS, STALE, UNWRITTEN, RefDatabase, World, numpy_score, replay_ref, scenario
+from kfdb_support import ROOT, SCENARIOS, SCORINGS, STALE, UNWRITTEN, RefDatabase, World, growth_scenario, numpy_score, replay_ref, scenario
 
 
 def vec(words, values=None):
@@ -169,6 +169,24 @@ def test_scenarios_are_not_trivial():
           % (queries, multi, stale, unwritten, dedup, cut))
     assert queries > 1000 and 2 * multi >= queries   # over the whole set, the queries on the empty and one-key-frame databases included
     assert stale >= 1 and unwritten >= 1 and dedup >= 1 and cut >= 1
+
+
+def test_growth_scenario_reads_scores_written_before_the_growth():
+    """On the restatement alone: after the second add of growth_scenario (the one that grows the slot table and compacts the pool), the
+    queries return lists and read relocalisation scores that an earlier query wrote; the very first of them can only read scores
+    written before the growth."""
+    ops = growth_scenario()
+    assert [op[0] for op in ops].count("add") == 2
+    recs = replay_ref(ops, "L1_NORM")
+    n_before = sum(op[0] in ("reloc", "loop", "score") for op in ops[:max(i for i, op in enumerate(ops) if op[0] == "add")])
+    assert n_before >= 1 and recs[n_before][0] == "reloc"
+    after = [r for rec in recs[n_before:] if rec[0] != "score" for r in rec[1]]
+    stale = sum(bool(r["status"] & STALE) for r in after)
+    multi = sum(len(r["candidates"]) >= 2 for r in after)
+    written = sum(r["stats"]["scored"] for rec in recs[:n_before] if rec[0] == "reloc" for r in rec[1])
+    print("queries after the growth %d, stale %d, with >= 2 candidates %d; scores written before it %d" % (len(after), stale, multi, written))
+    assert written >= 1 and stale >= 1 and multi >= 1
+    assert recs[n_before][1][0]["status"] & STALE
 
 
 def test_abi_symbols_and_unsupported_scorings():

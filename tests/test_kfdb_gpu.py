@@ -8,7 +8,7 @@ list order; maxima are order-free; the result order is an integer key (first com
 import numpy as np
 import pytest
 
-from kfdb_support import SCENARIOS, SCORINGS, STALE, UNWRITTEN, World, compare, replay_gpu, replay_ref, scenario
+from kfdb_support import SCENARIOS, SCORINGS, STALE, UNWRITTEN, World, compare, growth_scenario, replay_gpu, replay_ref, scenario
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,18 @@ def test_one_by_one_equals_batch(name, scoring):
         else:
             for ra, rb in zip(a[1], b[1]):
                 assert np.array_equal(ra["candidates"], rb["candidates"]) and ra["status"] == rb["status"] and ra["count"] == rb["count"]
+
+
+def test_growth_after_use_equals_restatement():
+    """The slot table grows past its first 64 slots while relocalisation scores are resident, and the pool is compacted over erased rows
+    while the device's slot table lags behind the host's (growth_scenario); queries batched and one by one."""
+    ops = growth_scenario()
+    want = replay_ref(ops, "L1_NORM", diag="all")
+    for batch in (True, False):
+        sizes = []
+        got = replay_gpu(ops, "L1_NORM", batch=batch, sizes=sizes, slot_capacity=1, word_capacity=1)
+        assert len(sizes) == 2 and sizes[0][1] <= 64 and sizes[1][1] > 64
+        compare(want, got)
 
 
 def test_stale_and_unwritten_status_bits_are_raised():

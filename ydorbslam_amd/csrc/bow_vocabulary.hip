@@ -11,7 +11,7 @@
 //                   bitonic sort of (id << 13 | feature) keys in LDS, run boundaries by a block scan, then per word the value the
 //                   reference's sequence of `+=` produces (the same weight added count times, in order) and the normalisation
 //                   with its sequential sum in word order (one thread; the order of a floating-point sum is part of the result).
-// No CPU fallback; the host only uploads the tree and sizes buffers.
+// No CPU fallback; the host only uploads the tree and sizes buffers: two arenas, the tree (layTree) and the memory of a call (layCall).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -173,15 +173,67 @@ __global__ __launch_bounds__(256) void k_bow_assemble(const int* __restrict__ wo
   if (tid == 0) O.nFvNodes[frame] = nNodes;
 }
 
+// The tree on the device: written once by ydorb_vocabulary_create, read by k_bow_descend (as a BowTreeDev).
+struct Tree { int* childBegin; int* childIds; uint8_t* nodeDesc; double* nodeWeight; int* nodeWord; };
+
+Tree layTree(Carve& a, size_t nNodes, size_t nChildren) {
+  Tree t;
+  a.take(t.childBegin, nNodes + 1); a.take(t.childIds, nChildren); a.take(t.nodeDesc, 32 * nNodes); a.take(t.nodeWeight, nNodes);
+  a.take(t.nodeWord, nNodes);
+  return t;
+}
+
+// Memory of one transform call: what the host uploads (desc, nFeat), what k_bow_descend hands to k_bow_assemble (word, node, weight;
+// status is zeroed by the host) and the seven result arrays.
+struct Call {
+  uint8_t* desc; int* nFeat; int* status;   // [frames][cap][32], [frames], [frames]
+  int* word; int* node; double* weight;     // [frames][cap]
+  BowOut out;
+};
+
+Call layCall(Carve& a, size_t nFrames, size_t cap) {
+  const size_t tot = nFrames * cap;
+  Call c;
+  a.take(c.desc, 32 * tot); a.take(c.nFeat, nFrames); a.take(c.status, nFrames);
+  a.take(c.word, tot); a.take(c.node, tot); a.take(c.weight, tot);
+  a.take(c.out.bowWord, tot); a.take(c.out.bowValue, tot); a.take(c.out.nWords, nFrames);
+  a.take(c.out.fvNode, tot); a.take(c.out.fvStart, nFrames * (cap + 1)); a.take(c.out.fvFeat, tot); a.take(c.out.nFvNodes, nFrames);
+  return c;
+}
+
 }  // namespace
 
 struct ydorb_vocabulary {
-  int device = 0, nNodes = 0, L = 0, weighting = 0, norm = 1;
+  int device = 0, weighting = 0, norm = 1;
   hipStream_t stream = nullptr;
-  Mem childBegin, childIds, nodeDesc, nodeWeight, nodeWord;   // the tree
-  Mem desc, nFeat, word, node, weight, status, out;           // per-call scratch
+  Mem tree, call;   // arenas: the tree (T points into it) and the memory of a call, laid out afresh by every call
+  BowTreeDev T{};
   std::mutex mu;   // Frame::computeBoW and KeyFrame::computeBoW reach one vocabulary from the tracking, mapping and loop-closing threads
 };
+
+namespace {
+
+// The device half of ydorb_vocabulary_create; the caller destroys the handle when it fails.  The tree goes up straight from the
+// caller's arrays: it can be tens of megabytes, and a staging copy would only add a pass.
+int uploadTree(ydorb_vocabulary* v, const YdVocabularyTree* t) {
+  const size_t nn = t->n_nodes, nc = t->child_begin[nn];
+  HIPCHK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+  Carve size(nullptr);
+  layTree(size, nn, nc);
+  const int rc = v->tree.alloc(size.L.bytes);
+  if (rc) return rc;
+  Carve a(v->tree.p);
+  const Tree d = layTree(a, nn, nc);
+  HIPCHK(hipMemcpy(d.childBegin, t->child_begin, sizeof(int) * (nn + 1), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.childIds, t->child_ids, sizeof(int) * nc, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.nodeDesc, t->node_desc, 32 * nn, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.nodeWeight, t->node_weight, sizeof(double) * nn, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.nodeWord, t->node_word, sizeof(int) * nn, hipMemcpyHostToDevice));
+  v->T = BowTreeDev{d.childBegin, d.childIds, d.nodeDesc, d.nodeWeight, d.nodeWord, t->n_nodes, t->levels};
+  return YDORB_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -217,20 +269,8 @@ int ydorb_vocabulary_create(const YdVocabularyTree* t, int32_t device, ydorb_voc
   int rc = require_device(device);
   if (rc) return rc;
   ydorb_vocabulary* v = new ydorb_vocabulary;
-  v->device = device; v->nNodes = nn; v->L = t->levels; v->weighting = t->weighting; v->norm = t->norm;
-  auto fail = [&](int code) { ydorb_vocabulary_destroy(v); return code; };
-  if (hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(YDORB_ERR_HIP); }
-  if ((rc = v->childBegin.ensure(sizeof(int) * (nn + 1))) || (rc = v->childIds.ensure(sizeof(int) * std::max(nc, 1))) ||
-      (rc = v->nodeDesc.ensure((size_t)32 * nn)) || (rc = v->nodeWeight.ensure(sizeof(double) * nn)) || (rc = v->nodeWord.ensure(sizeof(int) * nn)))
-    return fail(rc);
-  if (hipMemcpy(v->childBegin.p, t->child_begin, sizeof(int) * (nn + 1), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->childIds.p, t->child_ids, sizeof(int) * nc, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->nodeDesc.p, t->node_desc, (size_t)32 * nn, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->nodeWeight.p, t->node_weight, sizeof(double) * nn, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->nodeWord.p, t->node_word, sizeof(int) * nn, hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("uploading the vocabulary failed");
-    return fail(YDORB_ERR_HIP);
-  }
+  v->device = device; v->weighting = t->weighting; v->norm = t->norm;
+  if ((rc = uploadTree(v, t))) { ydorb_vocabulary_destroy(v); return rc; }
   *out = v;
   return YDORB_OK;
 }
@@ -239,9 +279,7 @@ void ydorb_vocabulary_destroy(ydorb_vocabulary_t* v) {
   if (!v) return;
   (void)hipSetDevice(v->device);
   if (v->stream) { (void)hipStreamSynchronize(v->stream); (void)hipStreamDestroy(v->stream); }
-  for (Mem* b : {&v->childBegin, &v->childIds, &v->nodeDesc, &v->nodeWeight, &v->nodeWord, &v->desc, &v->nFeat, &v->word, &v->node, &v->weight,
-                  &v->status, &v->out})
-    b->release();
+  v->tree.release(); v->call.release();
   delete v;
 }
 
@@ -258,31 +296,25 @@ int ydorb_vocabulary_transform(ydorb_vocabulary_t* v, const uint8_t* desc, const
   std::lock_guard<std::mutex> lock(v->mu);
   HIPCHK(hipSetDevice(v->device));
   const size_t tot = (size_t)nFrames * cap;
-  // out: bowWord | fvNode | fvFeat | fvStart (cap + 1 per frame) | nWords | nFvNodes (ints), then bowValue (doubles)
-  const size_t outInts = 3 * tot + (size_t)nFrames * (cap + 1) + 2 * (size_t)nFrames, outIntsPad = (outInts + 1) & ~(size_t)1;
-  int rc;
-  if ((rc = v->desc.ensure(32 * tot)) || (rc = v->nFeat.ensure(sizeof(int) * nFrames)) || (rc = v->word.ensure(sizeof(int) * tot)) ||
-      (rc = v->node.ensure(sizeof(int) * tot)) || (rc = v->weight.ensure(sizeof(double) * tot)) || (rc = v->status.ensure(sizeof(int) * nFrames)) ||
-      (rc = v->out.ensure(sizeof(int) * outIntsPad + sizeof(double) * tot)))
-    return rc;
+  Carve size(nullptr);
+  layCall(size, nFrames, cap);
+  const int rc = v->call.ensure(size.L.bytes);
+  if (rc) return rc;
+  Carve a(v->call.p);
+  const Call c = layCall(a, nFrames, cap);
+  const BowOut& O = c.out;
   hipStream_t s = v->stream;
-  HIPCHK(hipMemcpyAsync(v->desc.p, desc, 32 * tot, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(v->nFeat.p, n, sizeof(int) * nFrames, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(v->status.p, 0, sizeof(int) * nFrames, s));
-  BowTreeDev T{v->childBegin.as<int>(), v->childIds.as<int>(), v->nodeDesc.as<uint8_t>(), v->nodeWeight.as<double>(), v->nodeWord.as<int>(), v->nNodes, v->L};
-  hipLaunchKernelGGL(k_bow_descend, dim3((cap + 255) / 256, nFrames), dim3(256), 0, s, T, v->desc.as<uint8_t>(), v->nFeat.as<int>(), cap, levelsup,
-                     v->word.as<int>(), v->node.as<int>(), v->weight.as<double>(), v->status.as<int>());
-  int* oi = v->out.as<int>();
-  BowOut O;
-  O.bowWord = oi; O.fvNode = oi + tot; O.fvFeat = oi + 2 * tot; O.fvStart = oi + 3 * tot;
-  O.nWords = O.fvStart + (size_t)nFrames * (cap + 1); O.nFvNodes = O.nWords + nFrames;
-  O.bowValue = reinterpret_cast<double*>(oi + outIntsPad);
+  HIPCHK(hipMemcpyAsync(c.desc, desc, 32 * tot, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c.nFeat, n, sizeof(int) * nFrames, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(c.status, 0, sizeof(int) * nFrames, s));
+  hipLaunchKernelGGL(k_bow_descend, dim3((cap + 255) / 256, nFrames), dim3(256), 0, s, v->T, c.desc, c.nFeat, cap, levelsup, c.word, c.node, c.weight,
+                     c.status);
+  HIPCHK(hipGetLastError());
   int n2 = 256;
   while (n2 < cap) n2 <<= 1;
   const size_t lds = (size_t)n2 * 8;
   if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bow_assemble), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_bow_assemble, dim3(nFrames), dim3(256), lds, s, v->word.as<int>(), v->node.as<int>(), v->weight.as<double>(), v->nFeat.as<int>(), cap,
-                     n2, v->weighting, v->norm, O);
+  hipLaunchKernelGGL(k_bow_assemble, dim3(nFrames), dim3(256), lds, s, c.word, c.node, c.weight, c.nFeat, cap, n2, v->weighting, v->norm, O);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(bowWord, O.bowWord, sizeof(int) * tot, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(bowValue, O.bowValue, sizeof(double) * tot, hipMemcpyDeviceToHost, s));
@@ -291,7 +323,7 @@ int ydorb_vocabulary_transform(ydorb_vocabulary_t* v, const uint8_t* desc, const
   HIPCHK(hipMemcpyAsync(fvStart, O.fvStart, sizeof(int) * (size_t)nFrames * (cap + 1), hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(fvFeat, O.fvFeat, sizeof(int) * tot, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(nFvNodes, O.nFvNodes, sizeof(int) * nFrames, hipMemcpyDeviceToHost, s));
-  if (status) HIPCHK(hipMemcpyAsync(status, v->status.p, sizeof(int) * nFrames, hipMemcpyDeviceToHost, s));
+  if (status) HIPCHK(hipMemcpyAsync(status, c.status,sizeof(int) * nFrames, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return YDORB_OK;
 }
