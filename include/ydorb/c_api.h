@@ -810,6 +810,50 @@ int ydorb_extract_rgbd(ydorb_extractor_t* h, const uint8_t* gray, int32_t w, int
 /* The frame-construction entries keep device scratch per device between calls; this frees it (waiting for calls in flight). */
 int ydorb_frame_release(int32_t device);
 
+/* ------------------------------------------------------------------------------------------
+ * Essential-graph optimisation of loop closing.  Replaces Optimizer::optimizeEssentialGraph (ORB-SLAM2
+ * Optimizer::OptimizeEssentialGraph, src/Optimizer.cc): one VertexSim3Expmap per keyframe, EdgeSim3 edges with identity information
+ * and no robust kernel (error = log(Sji * Siw * Sjw^-1)), BaseBinaryEdge's numeric Jacobians (delta 1e-9), Levenberg-Marquardt with
+ * setUserLambdaInit(lambda_init), optimize(iterations), then the map-point correction.  The graph (which keyframes, which edges) is
+ * built by the caller (include/ydorb/optimizer.hpp).  The normal equations are assembled DENSE, 7 rows per free vertex, and
+ * factorised by the BA's blocked Cholesky: more than 19 200 / 7 = 2 742 free vertices return YDORB_ERR_UNSUPPORTED.  fp64 under the
+ * contract of DESIGN.md section 2 ("Essential graph: the arithmetic contract"); two calls on the same graph give the same bits.
+ * Checked before any device work (YDORB_ERR_INVALID_ARG): null arrays, a vertex index outside 0..n_vertices-1, edge_v0 == edge_v1,
+ * no fixed vertex, every vertex fixed, non-positive iterations / max_trials / lambda_init / scale (vertex or measurement).
+ * An edge between two fixed vertices counts in chi2 only; a repeated pair is legal and summed in edge order.
+ * res: the iteration log as the single-stage BA writes it (log_stage = 1; edge_outlier is not used); ms_build / ms_schur / ms_solve /
+ * ms_update / ms_errors = device time of linearize / assemble / factorise + solve / update / trial chi2 when
+ * ydorb_essential_graph_set_profiling switched the event pairs on (they cost a few microseconds per launch), 0 otherwise.
+ * points_out [n_points][3] = float(correctedSwr.map(Srw.map(double(points[p])))) with Srw the reference vertex's estimate as it came
+ * in and correctedSwr the inverse of its estimate as it goes out; may be NULL when n_points == 0.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdEssentialGraph {
+  int32_t device, n_vertices, n_edges, n_points;
+  double* sim3;             /* [n_vertices][8] qx qy qz qw tx ty tz s: initial estimate in (vScw), optimised estimate out */
+  const uint8_t* fixed;     /* [n_vertices] 1 = the loop keyframe's vertex */
+  const int32_t* edge_v0;   /* [n_edges] vertex(0) = i */
+  const int32_t* edge_v1;   /* [n_edges] vertex(1) = j */
+  const double* edge_meas;  /* [n_edges][8] Sji */
+  const float* points;      /* [n_points][3] world positions, may be NULL when n_points == 0 */
+  const int32_t* point_ref; /* [n_points] vertex of the reference (or correcting) keyframe */
+  int32_t fix_scale, iterations /* 20 */, max_trials /* 10 */;
+  double lambda_init;       /* 1e-16: setUserLambdaInit */
+} YdEssentialGraph;
+int ydorb_essential_graph_optimize(const YdEssentialGraph* g, float* points_out, YdBaResult* res);
+/* TEST / DEBUG: linearises the graph once at the estimate handed in (same argument checks, nothing is optimised or written back) and
+ * returns what k_ess_linearize stored: err [n_edges][7], J0 and J1 [n_edges][7][7] (row = error component, column = update dimension;
+ * zero for a fixed vertex) and chi2 [n_edges].  Each output may be NULL. */
+int ydorb_essential_graph_linearize(const YdEssentialGraph* g, double* err, double* J0, double* J1, double* chi2);
+/* TEST / DEBUG: the solve of one LM trial at the estimate handed in (same argument checks, nothing is written back): linearise,
+ * assemble H + lambda I, factorise, solve.  x [7 * free vertices] = the update the trial would apply, free vertices in vertex order;
+ * *solved = 0 when a pivot was not positive (x is then not a solution). */
+int ydorb_essential_graph_trial_step(const YdEssentialGraph* g, double lambda, double* x, int32_t* solved);
+/* 1: ydorb_essential_graph_optimize on `device` fills the ms_* fields of its result from HIP event pairs; 0 (default): no events. */
+int ydorb_essential_graph_set_profiling(int32_t device, int32_t on);
+/* The entries keep device scratch and, once profiling was on, ten HIP events per device between calls; this frees them (waiting for a
+ * call in flight). */
+int ydorb_essential_graph_release(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,13 +7,17 @@
 #ifndef YDORB_ADAPTER_OPTIMIZER_HPP
 #define YDORB_ADAPTER_OPTIMIZER_HPP
 
+#include <algorithm>
 #include <cmath>
 #include <list>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <Eigen/Core>
@@ -297,6 +301,210 @@ int optimizeSim3Impl(KeyFramePtr kf1, KeyFramePtr kf2, std::vector<MapPointPtr>&
   for (size_t k = 0; k < idx.size(); k++)
     if (outlier[k]) matches1[idx[k]] = MapPointPtr();
   return nIn;
+}
+
+// Optimizer::optimizeEssentialGraph (ORB-SLAM2 Optimizer::OptimizeEssentialGraph, src/Optimizer.cc).  The body of
+//   void Optimizer::optimizeEssentialGraph(map, loopKF, curKF, nonCorrectedSim3, correctedSim3, loopConnections, fixScale)
+// becomes  ydorb::adapter::optimizeEssentialGraphImpl<Frame>(map, loopKF, curKF, nonCorrectedSim3, correctedSim3, loopConnections, fixScale);
+// Member spellings assumed beyond the ones used above (the reference is not at hand; ORB-SLAM2's names in the project's lowerCamelCase):
+//   KeyFrame  getParent(), hasChild(kf), getLoopEdges() -> std::set<KeyFramePtr>, getCovisiblesByWeight(int) -> std::vector<KeyFramePtr>,
+//             getWeight(kf), getRotation_c2w(), getTranslation_c2w(), setCameraPoseByTransform_c2w(cv::Mat), m_int_keyFrameID
+//   MapPoint  m_int_correctedByKeyFrameID, m_int_correctedReference (mnCorrectedByKF, mnCorrectedReference), getReferenceKeyFrame()
+//   Map       getAllKeyFrames(), getAllMapPoints(), m_mutex_updateMap
+//   the maps  KeyFrameAndPose = std::map<KeyFramePtr, Sim3T>; Sim3T is read through rotation().x() .. w(), translation()[k], scale() only,
+//             so the host keeps g2o::Sim3 or replaces it by any type with those three members
+// Differences from the reference's text, all where it would dereference a null vertex: a bad keyframe gets no vertex (as there), and here
+// it also gets no edges, no pose write-back, and a map point whose reference keyframe has no vertex is left alone.  One more difference:
+// the map points' world positions are read before the call and outside Map::m_mutex_updateMap (the GPU corrects them in the same call),
+// where the reference reads each one under the lock after the optimisation; a position written by another thread during the call is
+// overwritten.  correctLoop runs with LocalMapping stopped, so nothing writes them then.
+struct Sim3d {   // g2o::Sim3 as the C ABI stores it
+  double q[4], t[3], s;   // q = x y z w
+  static void rot(const double* q, const double* v, double* o) {   // Eigen quaternion * vector
+    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+    for (int k = 0; k < 3; k++) uv[k] = uv[k] + uv[k];
+    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+    for (int k = 0; k < 3; k++) o[k] = (v[k] + uv[k] * q[3]) + c[k];
+  }
+  Sim3d operator*(const Sim3d& b) const {   // r = r * b.r, t = s * (r * b.t) + t, s = s * b.s
+    Sim3d o;
+    o.q[0] = q[3] * b.q[0] + q[0] * b.q[3] + q[1] * b.q[2] - q[2] * b.q[1];
+    o.q[1] = q[3] * b.q[1] + q[1] * b.q[3] + q[2] * b.q[0] - q[0] * b.q[2];
+    o.q[2] = q[3] * b.q[2] + q[2] * b.q[3] + q[0] * b.q[1] - q[1] * b.q[0];
+    o.q[3] = q[3] * b.q[3] - q[0] * b.q[0] - q[1] * b.q[1] - q[2] * b.q[2];
+    double r[3];
+    rot(q, b.t, r);
+    for (int k = 0; k < 3; k++) o.t[k] = r[k] * s + t[k];
+    o.s = s * b.s;
+    return o;
+  }
+  Sim3d inverse() const {   // (r^-1, r^-1 * ((-1 / s) * t), 1 / s)
+    Sim3d o;
+    o.q[0] = -q[0]; o.q[1] = -q[1]; o.q[2] = -q[2]; o.q[3] = q[3];
+    const double f = -1. / s, v[3] = {t[0] * f, t[1] * f, t[2] * f};
+    rot(o.q, v, o.t);
+    o.s = 1. / s;
+    return o;
+  }
+  template <class Sim3T> static Sim3d from(const Sim3T& S) {
+    Sim3d o;
+    o.q[0] = S.rotation().x(); o.q[1] = S.rotation().y(); o.q[2] = S.rotation().z(); o.q[3] = S.rotation().w();
+    for (int k = 0; k < 3; k++) o.t[k] = S.translation()[k];
+    o.s = S.scale();
+    return o;
+  }
+};
+
+// The graph of one optimizeEssentialGraph call: vertices in the order of the map's keyframes (bad ones skipped, mnId compacted to dense
+// indices), edges in the reference's order.
+template <class KeyFramePtr>
+struct EssentialGraphData {
+  std::vector<KeyFramePtr> vertexKF;
+  std::map<long int, int> vertexOf;   // mnId -> vertex
+  std::vector<double> sim3;           // [V][8], vScw
+  std::vector<uint8_t> fixed;
+  std::vector<int32_t> v0, v1;
+  std::vector<double> meas;           // [E][8]
+};
+
+template <class KeyFramePtr, class MapPtr, class PoseMap, class ConnMap>
+EssentialGraphData<KeyFramePtr> buildEssentialGraph(MapPtr map, KeyFramePtr loopKF, KeyFramePtr curKF, const PoseMap& nonCorrectedSim3,
+                                                    const PoseMap& correctedSim3, const ConnMap& loopConnections) {
+  EssentialGraphData<KeyFramePtr> G;
+  const std::vector<KeyFramePtr> kfs = map->getAllKeyFrames();
+  const int minFeat = 100;
+  std::vector<Sim3d> vScw;
+  for (const KeyFramePtr& kf : kfs) {   // Set KeyFrame vertices
+    if (kf->isBad()) continue;
+    Sim3d S;
+    const auto it = correctedSim3.find(kf);
+    if (it != correctedSim3.end()) {
+      S = Sim3d::from(it->second);
+    } else {   // g2o::Sim3(Rcw, tcw, 1.0): the float pose in double, the quaternion Eigen makes of the matrix
+      const cv::Mat Rcw = kf->getRotation_c2w(), tcw = kf->getTranslation_c2w();
+      Eigen::Matrix3d R;
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R(i, j) = Rcw.at<float>(i, j);
+      const Eigen::Quaterniond q(R);
+      S.q[0] = q.x(); S.q[1] = q.y(); S.q[2] = q.z(); S.q[3] = q.w();
+      for (int k = 0; k < 3; k++) S.t[k] = tcw.at<float>(k);
+      S.s = 1.0;
+    }
+    G.vertexOf[kf->m_int_keyFrameID] = (int)G.vertexKF.size();
+    G.vertexKF.push_back(kf);
+    vScw.push_back(S);
+    G.fixed.push_back(kf == loopKF ? 1 : 0);
+  }
+  auto vertex = [&](const KeyFramePtr& kf) -> int {
+    const auto it = G.vertexOf.find(kf->m_int_keyFrameID);
+    return it == G.vertexOf.end() ? -1 : it->second;
+  };
+  auto addEdge = [&](int i, int j, const Sim3d& Sji) {   // vertex(0) = i, vertex(1) = j
+    G.v0.push_back(i); G.v1.push_back(j);
+    for (int k = 0; k < 4; k++) G.meas.push_back(Sji.q[k]);
+    for (int k = 0; k < 3; k++) G.meas.push_back(Sji.t[k]);
+    G.meas.push_back(Sji.s);
+  };
+  auto nonCorrected = [&](const KeyFramePtr& kf, int v) -> Sim3d {   // the pose before the loop correction, where the keyframe had one
+    const auto it = nonCorrectedSim3.find(kf);
+    return it != nonCorrectedSim3.end() ? Sim3d::from(it->second) : vScw[v];
+  };
+  std::set<std::pair<long int, long int>> inserted;
+  for (const auto& conn : loopConnections) {   // Set Loop edges
+    const KeyFramePtr& kf = conn.first;
+    const int vi = vertex(kf);
+    if (vi < 0) continue;
+    const long int idi = kf->m_int_keyFrameID;
+    const Sim3d Swi = vScw[vi].inverse();
+    for (const KeyFramePtr& other : conn.second) {
+      const long int idj = other->m_int_keyFrameID;
+      if ((idi != curKF->m_int_keyFrameID || idj != loopKF->m_int_keyFrameID) && kf->getWeight(other) < minFeat) continue;
+      const int vj = vertex(other);
+      if (vj < 0) continue;
+      addEdge(vi, vj, vScw[vj] * Swi);
+      inserted.insert(std::make_pair(std::min(idi, idj), std::max(idi, idj)));
+    }
+  }
+  for (const KeyFramePtr& kf : kfs) {   // Set normal edges
+    const int vi = vertex(kf);
+    if (vi < 0) continue;
+    const long int idi = kf->m_int_keyFrameID;
+    const Sim3d Swi = nonCorrected(kf, vi).inverse();
+    const KeyFramePtr parent = kf->getParent();
+    if (parent) {   // Spanning tree edge
+      const int vj = vertex(parent);
+      if (vj >= 0) addEdge(vi, vj, nonCorrected(parent, vj) * Swi);
+    }
+    const auto loopEdges = kf->getLoopEdges();   // Loop edges
+    for (const KeyFramePtr& l : loopEdges) {
+      if (l->m_int_keyFrameID >= idi) continue;
+      const int vl = vertex(l);
+      if (vl >= 0) addEdge(vi, vl, nonCorrected(l, vl) * Swi);
+    }
+    for (const KeyFramePtr& n : kf->getCovisiblesByWeight(minFeat)) {   // Covisibility graph edges
+      if (!n || n == parent || kf->hasChild(n) || loopEdges.count(n)) continue;
+      if (n->isBad() || n->m_int_keyFrameID >= idi) continue;
+      if (inserted.count(std::make_pair(std::min(idi, (long int)n->m_int_keyFrameID), std::max(idi, (long int)n->m_int_keyFrameID)))) continue;
+      const int vn = vertex(n);
+      if (vn >= 0) addEdge(vi, vn, nonCorrected(n, vn) * Swi);
+    }
+  }
+  G.sim3.resize(8 * vScw.size());
+  for (size_t v = 0; v < vScw.size(); v++) {
+    for (int k = 0; k < 4; k++) G.sim3[8 * v + k] = vScw[v].q[k];
+    for (int k = 0; k < 3; k++) G.sim3[8 * v + 4 + k] = vScw[v].t[k];
+    G.sim3[8 * v + 7] = vScw[v].s;
+  }
+  return G;
+}
+
+template <class FrameT, class KeyFramePtr, class MapPtr, class PoseMap, class ConnMap>
+void optimizeEssentialGraphImpl(MapPtr map, KeyFramePtr loopKF, KeyFramePtr curKF, const PoseMap& nonCorrectedSim3, const PoseMap& correctedSim3,
+                                const ConnMap& loopConnections, const bool& fixScale, int device = 0) {
+  EssentialGraphData<KeyFramePtr> G = buildEssentialGraph(map, loopKF, curKF, nonCorrectedSim3, correctedSim3, loopConnections);
+  // every good map point with the vertex of its reference keyframe, or of the keyframe that corrected it in correctLoop
+  const auto mps = map->getAllMapPoints();
+  typedef typename std::decay<decltype(mps[0])>::type MapPointPtr;
+  std::vector<MapPointPtr> pointMP;
+  std::vector<float> points;
+  std::vector<int32_t> pointRef;
+  for (const MapPointPtr& mp : mps) {
+    if (!mp || mp->isBad()) continue;
+    const long int idr = mp->m_int_correctedByKeyFrameID == curKF->m_int_keyFrameID ? (long int)mp->m_int_correctedReference
+                                                                                    : (long int)mp->getReferenceKeyFrame()->m_int_keyFrameID;
+    const auto it = G.vertexOf.find(idr);
+    if (it == G.vertexOf.end()) continue;
+    const cv::Mat X = mp->getPosInWorld();
+    for (int d = 0; d < 3; d++) points.push_back(X.at<float>(d));
+    pointRef.push_back(it->second);
+    pointMP.push_back(mp);
+  }
+  YdEssentialGraph P{};
+  P.device = device; P.n_vertices = (int32_t)G.vertexKF.size(); P.n_edges = (int32_t)G.v0.size(); P.n_points = (int32_t)pointMP.size();
+  P.sim3 = G.sim3.data(); P.fixed = G.fixed.data(); P.edge_v0 = G.v0.data(); P.edge_v1 = G.v1.data(); P.edge_meas = G.meas.data();
+  P.points = points.data(); P.point_ref = pointRef.data();
+  P.fix_scale = fixScale ? 1 : 0; P.iterations = 20; P.max_trials = 10; P.lambda_init = 1e-16;
+  std::vector<float> corrected(points.size() + 3);
+  YdBaResult res{};
+  if (ydorb_essential_graph_optimize(&P, corrected.data(), &res) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
+  std::unique_lock<std::mutex> lock(map->m_mutex_updateMap);
+  for (size_t v = 0; v < G.vertexKF.size(); v++) {   // SE3 pose recovering: Sim3 [sR t; 0 1] -> SE3 [R t/s; 0 1]
+    const double* S = &G.sim3[8 * v];
+    const Eigen::Matrix3d R = Eigen::Quaterniond(S[3], S[0], S[1], S[2]).toRotationMatrix();
+    const double inv = 1. / S[7];
+    cv::Mat Tiw = cv::Mat::eye(4, 4, CV_32F);
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) Tiw.at<float>(i, j) = (float)R(i, j);
+      Tiw.at<float>(i, 3) = (float)(S[4 + i] * inv);
+    }
+    G.vertexKF[v]->setCameraPoseByTransform_c2w(Tiw);
+  }
+  for (size_t p = 0; p < pointMP.size(); p++) {   // correct points
+    cv::Mat X(3, 1, CV_32F);
+    for (int d = 0; d < 3; d++) X.at<float>(d) = corrected[3 * p + d];
+    pointMP[p]->setPosInWorld(X);
+    pointMP[p]->updateNormalAndDepth();
+  }
 }
 
 // Optimizer::globalBundleAdjust (optimizer.cpp:353-357)

@@ -107,6 +107,11 @@ SYMBOLS = {
     "ydorb_extract_rgbd": (C.c_int, [_VP, _VP, _I, _I, _I, _VP, _I, _I, C.c_float, _VP, C.c_float, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I,
                                      C.POINTER(_I), C.POINTER(_I)]),
     "ydorb_frame_release": (C.c_int, [_I]),
+    "ydorb_essential_graph_optimize": (C.c_int, [_VP, _VP, _VP]),
+    "ydorb_essential_graph_linearize": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "ydorb_essential_graph_trial_step": (C.c_int, [_VP, C.c_double, _VP, C.POINTER(_I)]),
+    "ydorb_essential_graph_set_profiling": (C.c_int, [_I, _I]),
+    "ydorb_essential_graph_release": (C.c_int, [_I]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -140,6 +145,12 @@ class YdPnpProblem(C.Structure):
 class YdSim3Batch(C.Structure):
     _fields_ = [("n_problems", _I), ("device", _I), ("corr_start", _VP), ("S12", _VP), ("K1", _VP), ("K2", _VP), ("fix_scale", _VP),
                 ("X1c", _VP), ("X2c", _VP), ("obs1", _VP), ("obs2", _VP), ("inv_sigma2_1", _VP), ("inv_sigma2_2", _VP), ("th2", C.c_double)]
+
+
+class YdEssentialGraph(C.Structure):
+    _fields_ = [("device", _I), ("n_vertices", _I), ("n_edges", _I), ("n_points", _I), ("sim3", _VP), ("fixed", _VP), ("edge_v0", _VP),
+                ("edge_v1", _VP), ("edge_meas", _VP), ("points", _VP), ("point_ref", _VP), ("fix_scale", _I), ("iterations", _I),
+                ("max_trials", _I), ("lambda_init", C.c_double)]
 
 
 class YdTriView(C.Structure):

@@ -813,6 +813,22 @@ int solveGroup(BatchPool& B, const YdBaProblem* probs, const YdBaOptions& Oin, Y
 
 }  // namespace
 
+// ydorb_host.h: the factorisation's launch sequence for a system another driver assembled (ydorb_ba_dense_solve, essential_graph.hip)
+static_assert(ydorb::kCholTile == NB, "ydorb_host.h states the tile of the blocked Cholesky");
+int ydorb::chol_max_rows() { return kCholSolveMaxN; }
+int ydorb::chol_factor_solve(void* stream, double* S, double* diagL, double* diagInv, int n, int* status, double* b, double* yv, double* x) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nb = n / NB;
+  for (int kb = 0; kb < nb; kb++)
+    hipLaunchKernelGGL(k_chol_step, dim3((nb - kb) * (nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, s, S, diagL, diagInv, n, kb, status, b, yv);
+  if (!launch_chol_solve(s, S, diagInv, n, yv, b, x)) {
+    set_error("system of %d rows is wider than the solve kernel's LDS (max %d)", n, kCholSolveMaxN);
+    return YDORB_ERR_UNSUPPORTED;
+  }
+  HIPCHK(hipGetLastError());
+  return YDORB_OK;
+}
+
 extern "C" {
 
 void ydorb_ba_default_options(YdBaOptions* o) {
@@ -975,12 +991,7 @@ int ydorb_ba_dense_solve(int32_t device, const double* A, int32_t n0, const doub
   HIPCHK(hipMemcpy(dA, hA.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(db, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(dst, 0, sizeof(int) * 2));
-  for (int kb = 0; kb < nb; kb++) hipLaunchKernelGGL(k_chol_step, dim3((nb - kb) * (nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, 0, dA, dD, dI, n, kb, dst, db, dy);
-  if (!launch_chol_solve(0, dA, dI, n, dy, db, dx)) {
-    set_error("system of %d rows is wider than the solve kernel's LDS (max %d)", n, kCholSolveMaxN);
-    return YDORB_ERR_UNSUPPORTED;
-  }
-  HIPCHK(hipGetLastError());
+  if ((rc = chol_factor_solve(nullptr, dA, dD, dI, n, dst, db, dy, dx))) return rc;
   std::vector<double> hx(n);
   int hst[2];
   HIPCHK(hipMemcpy(hx.data(), dx, sizeof(double) * n, hipMemcpyDeviceToHost));

@@ -58,6 +58,7 @@ struct LmSchedule {
   int stage = 1, it = 0, iterations = 0, qmax = 0, iters2 = 0, maxTrials = 0;
   bool singleStage = false, lastAccepted = true;
   double lambda = 0, ni = 2, currentChi = 0, rho = 0;
+  double userLambdaInit = 0;   // setUserLambdaInit: > 0 replaces computeLambdaInit's 1e-5 * maxDiag; off by default, set after begin()
   YdBaResult* res = nullptr;
 
   static bool raised(Stop stop) { return stop && *stop; }
@@ -83,7 +84,7 @@ struct LmSchedule {
   // Nothing is logged and no trial runs: the stage did not take place.
   bool setMaxDiag(double maxDiag) {
     if (stage == 2 && maxDiag == 0) return false;
-    lambda = 1e-5 * maxDiag; ni = 2;
+    lambda = userLambdaInit > 0 ? userLambdaInit : 1e-5 * maxDiag; ni = 2;
     return true;
   }
 

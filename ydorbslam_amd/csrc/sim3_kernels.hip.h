@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "g2o_math.hip.h"
+#include "sim3_math.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -232,71 +233,6 @@ __global__ __launch_bounds__(64) void k_sim3_replay(const RansacDev* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------ Sim3 LM (fp64)
-using g2o::R; using g2o::V3; using g2o::Q4;
-using g2o::add; using g2o::cross; using g2o::scale; using g2o::qrot; using g2o::qmul; using g2o::rToQ;
-using g2o::huber; using g2o::block_sums; using g2o::block_sum1; using g2o::dense_solve; using g2o::lambda_init; using g2o::lm_judge;
-
-struct S3 { Q4 r; V3 t; R s; };
-
-// g2o Sim3(const Vector7d& update) (types/sim3.h): omega, upsilon, sigma and its A, B, C branches
-__device__ __forceinline__ S3 sim3Exp(const R* u) {
-  const R ox = u[0], oy = u[1], oz = u[2], sigma = u[6];
-  const R theta = sqrt(ox * ox + oy * oy + oz * oz);
-  const R Om[3][3] = {{0, -oz, oy}, {oz, 0, -ox}, {-oy, ox, 0}};
-  R Om2[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int b = 0; b < 3; b++) Om2[a][b] = Om[a][0] * Om[0][b] + Om[a][1] * Om[1][b] + Om[a][2] * Om[2][b];
-  const R s = exp(sigma), eps = 0.00001;
-  R A, B, C, ca, cb;
-  const bool small = theta < eps;
-  if (small) { ca = 1; cb = 1; }
-  else { ca = sin(theta) / theta; cb = (1 - cos(theta)) / (theta * theta); }
-  if (fabs(sigma) < eps) {
-    C = 1;
-    if (small) { A = 1. / 2.; B = 1. / 6.; }
-    else { const R th2 = theta * theta; A = (1 - cos(theta)) / th2; B = (theta - sin(theta)) / (th2 * theta); }
-  } else {
-    C = (s - 1) / sigma;
-    if (small) {
-      const R sg2 = sigma * sigma;
-      A = ((sigma - 1) * s + 1) / sg2;
-      B = ((0.5 * sg2 - sigma + 1) * s) / (sg2 * sigma);
-    } else {
-      const R a = s * sin(theta), b = s * cos(theta), th2 = theta * theta, sg2 = sigma * sigma, c = th2 + sg2;
-      A = (a * sigma + (1 - b) * theta) / (theta * c);
-      B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / th2;
-    }
-  }
-  R Rm[3][3], W[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int b = 0; b < 3; b++) {
-      const R I = a == b ? 1.0 : 0.0;
-      Rm[a][b] = (I + ca * Om[a][b]) + cb * Om2[a][b];
-      W[a][b] = (A * Om[a][b] + B * Om2[a][b]) + C * I;
-    }
-  S3 r;
-  r.r = rToQ(Rm);
-  r.t = {W[0][0] * u[3] + W[0][1] * u[4] + W[0][2] * u[5], W[1][0] * u[3] + W[1][1] * u[4] + W[1][2] * u[5],
-         W[2][0] * u[3] + W[2][1] * u[4] + W[2][2] * u[5]};
-  r.s = s;
-  return r;
-}
-__device__ __forceinline__ S3 compose(const S3& a, const S3& b) { return {qmul(a.r, b.r), add(scale(qrot(a.r, b.t), a.s), a.t), a.s * b.s}; }
-__device__ __forceinline__ S3 inverse(const S3& a) {
-  const Q4 rc{-a.r.x, -a.r.y, -a.r.z, a.r.w};
-  return {rc, qrot(rc, scale(a.t, -1. / a.s)), 1. / a.s};
-}
-__device__ __forceinline__ S3 oplus(const S3& S, const R* x, bool fix) {   // VertexSim3Expmap::oplusImpl
-  R u[7];
-#pragma unroll
-  for (int k = 0; k < 7; k++) u[k] = x[k];
-  if (fix) u[6] = 0;
-  return compose(sim3Exp(u), S);
-}
 // obs - cam_map(project(S.map(X)))
 __device__ __forceinline__ void projErr(const S3& S, const R* X, const R* K, const R* obs, R* e) {
   const V3 p = add(scale(qrot(S.r, V3{X[0], X[1], X[2]}), S.s), S.t);

@@ -20,4 +20,12 @@ struct PyramidView {
   void* stream;
 };
 int extractor_pyramid_view(const ydorb_extractor* e, PyramidView* out);
+// The BA's blocked dense Cholesky for another driver's system (defined in ba_solver.hip, whose translation unit holds the kernels):
+// queues on `stream` (a hipStream_t) the factorisation of S + the forward substitution and the backward solve, over device memory the
+// caller owns.  S is [n][n] row-major, n a multiple of kCholTile, lower tiles and whole diagonal tiles set; it is overwritten by the
+// factor.  diagL / diagInv hold n * kCholTile doubles each, b / yv / x hold n; b is consumed.  status[0] must be 0 on entry and is raised
+// when a pivot is not positive (x is then not a solution).  Nothing is synchronised.  YDORB_ERR_UNSUPPORTED past chol_max_rows().
+constexpr int kCholTile = 32;
+int chol_max_rows();
+int chol_factor_solve(void* stream, double* S, double* diagL, double* diagInv, int n, int* status, double* b, double* yv, double* x);
 }  // namespace ydorb
