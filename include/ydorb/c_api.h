@@ -815,9 +815,17 @@ int ydorb_frame_release(int32_t device);
  * Optimizer::OptimizeEssentialGraph, src/Optimizer.cc): one VertexSim3Expmap per keyframe, EdgeSim3 edges with identity information
  * and no robust kernel (error = log(Sji * Siw * Sjw^-1)), BaseBinaryEdge's numeric Jacobians (delta 1e-9), Levenberg-Marquardt with
  * setUserLambdaInit(lambda_init), optimize(iterations), then the map-point correction.  The graph (which keyframes, which edges) is
- * built by the caller (include/ydorb/optimizer.hpp).  The normal equations are assembled DENSE, 7 rows per free vertex, and
- * factorised by the BA's blocked Cholesky: more than 19 200 / 7 = 2 742 free vertices return YDORB_ERR_UNSUPPORTED.  fp64 under the
- * contract of DESIGN.md section 2 ("Essential graph: the arithmetic contract"); two calls on the same graph give the same bits.
+ * built by the caller (include/ydorb/optimizer.hpp).  Two solvers factorise the normal equations (7 rows per free vertex):
+ *   DENSE    assembled dense and factorised by the BA's blocked Cholesky.  Its limit: more than 19 200 / 7 = 2 742 free vertices return
+ *            YDORB_ERR_UNSUPPORTED.  ydorb_essential_graph_optimize / _trial_step always take it.
+ *   SKYLINE  a block-skyline Cholesky over the envelope of the 7x7 blocks: no limit on the vertex count; its
+ *            limit is the envelope's size in bytes, YdEssentialSolverOptions::max_factor_bytes (default: the largest dense matrix,
+ *            19 200^2 * 8).  The bytes bound the memory only; one workgroup walks the factor, so a second, fixed limit bounds the work:
+ *            more than 2^24 block updates per trial (the sum over the block columns of m (m + 1) / 2, m = the rows that reach the
+ *            column: a dense envelope of 465 keyframes, or a band of 6 over a million) return YDORB_ERR_UNSUPPORTED as well.
+ *            Chosen through the _with entries below.
+ * fp64 under the contract of DESIGN.md section 2 ("Essential graph: the arithmetic contract"); two calls on the same graph with the
+ * same solver and ordering give the same bits.
  * Checked before any device work (YDORB_ERR_INVALID_ARG): null arrays, a vertex index outside 0..n_vertices-1, edge_v0 == edge_v1,
  * no fixed vertex, every vertex fixed, non-positive iterations / max_trials / lambda_init / scale (vertex or measurement).
  * An edge between two fixed vertices counts in chi2 only; a repeated pair is legal and summed in edge order.
@@ -853,6 +861,38 @@ int ydorb_essential_graph_set_profiling(int32_t device, int32_t on);
 /* The entries keep device scratch and, once profiling was on, ten HIP events per device between calls; this frees them (waiting for a
  * call in flight). */
 int ydorb_essential_graph_release(int32_t device);
+
+/* The choice of solver.  AUTO: DENSE whenever the graph fits the dense limit (every call that succeeds through the entries above then
+ * returns the same bytes), SKYLINE above it.  DENSE above its limit fails as above.  ordering (SKYLINE): the order of the free vertices
+ * in the factor, NATURAL = the caller's, RCM = reverse Cuthill-McKee (pseudo-peripheral start, ties by vertex index, components by their
+ * lowest vertex), SMALLER = the one with the smaller envelope, NATURAL on a tie.  A NULL options pointer means all zeros. */
+enum { YDORB_ESS_SOLVER_AUTO = 0, YDORB_ESS_SOLVER_DENSE = 1, YDORB_ESS_SOLVER_SKYLINE = 2 };
+enum { YDORB_ESS_ORDER_SMALLER = 0, YDORB_ESS_ORDER_NATURAL = 1, YDORB_ESS_ORDER_RCM = 2 };
+typedef struct YdEssentialSolverOptions {
+  int32_t solver, ordering;
+  int64_t max_factor_bytes; /* 0 = default */
+} YdEssentialSolverOptions;
+/* What was planned: the envelope counts 7x7 blocks (392 bytes each), a row from its first connected column to the diagonal.
+ * ordering_used is NATURAL or RCM; envelope_blocks / max_row_blocks (the longest row) belong to it.  factor_bytes: the matrix the
+ * solver used holds (DENSE: the padded square). */
+typedef struct YdEssentialSolverInfo {
+  int32_t solver_used, ordering_used, n_free, max_row_blocks;
+  int64_t envelope_blocks, envelope_blocks_natural, envelope_blocks_rcm, factor_bytes;
+} YdEssentialSolverInfo;
+/* Host only, no device is touched: the argument checks of ydorb_essential_graph_optimize, then the order and the envelope.
+ * perm [free vertices]: perm[k] = the free vertex (counted in vertex order) at position k of the factor; first [free vertices]:
+ * first[k] = the first column of row k's envelope, by position.  Either may be NULL.  YDORB_ERR_UNSUPPORTED (the text names both
+ * sizes) when SKYLINE is asked for and the envelope exceeds max_factor_bytes or the work limit, or DENSE above its limit. */
+int ydorb_essential_graph_plan(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, YdEssentialSolverInfo* info, int32_t* perm,
+                               int32_t* first);
+/* ydorb_essential_graph_optimize with the solver chosen; info may be NULL.  With DENSE it is that entry. */
+int ydorb_essential_graph_optimize_with(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, float* points_out, YdBaResult* res,
+                                        YdEssentialSolverInfo* info);
+/* TEST / DEBUG: ydorb_essential_graph_trial_step with the solver chosen and any lambda (it is not range-checked here: a negative one
+ * makes a pivot non-positive, *solved = 0).  H_out [7F][7F] (F free vertices, caller's vertex order, full symmetric) and b_out [7F]:
+ * copies of the assembled H, without lambda, and of b, whichever solver stored them; either may be NULL; 7F > 4096 is refused. */
+int ydorb_essential_graph_trial_step_with(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, double lambda, double* x,
+                                          int32_t* solved, double* H_out, double* b_out);
 
 #ifdef __cplusplus
 }

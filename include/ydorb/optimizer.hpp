@@ -460,7 +460,7 @@ EssentialGraphData<KeyFramePtr> buildEssentialGraph(MapPtr map, KeyFramePtr loop
 
 template <class FrameT, class KeyFramePtr, class MapPtr, class PoseMap, class ConnMap>
 void optimizeEssentialGraphImpl(MapPtr map, KeyFramePtr loopKF, KeyFramePtr curKF, const PoseMap& nonCorrectedSim3, const PoseMap& correctedSim3,
-                                const ConnMap& loopConnections, const bool& fixScale, int device = 0) {
+                                const ConnMap& loopConnections, const bool& fixScale, int device = 0, int solver = YDORB_ESS_SOLVER_AUTO) {
   EssentialGraphData<KeyFramePtr> G = buildEssentialGraph(map, loopKF, curKF, nonCorrectedSim3, correctedSim3, loopConnections);
   // every good map point with the vertex of its reference keyframe, or of the keyframe that corrected it in correctLoop
   const auto mps = map->getAllMapPoints();
@@ -486,7 +486,11 @@ void optimizeEssentialGraphImpl(MapPtr map, KeyFramePtr loopKF, KeyFramePtr curK
   P.fix_scale = fixScale ? 1 : 0; P.iterations = 20; P.max_trials = 10; P.lambda_init = 1e-16;
   std::vector<float> corrected(points.size() + 3);
   YdBaResult res{};
-  if (ydorb_essential_graph_optimize(&P, corrected.data(), &res) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
+  // AUTO: the dense solver while the map fits it (2 742 free keyframes), the block-skyline one above
+  YdEssentialSolverOptions opt{};
+  opt.solver = solver;
+  if (ydorb_essential_graph_optimize_with(&P, &opt, corrected.data(), &res, nullptr) != YDORB_OK)
+    throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
   std::unique_lock<std::mutex> lock(map->m_mutex_updateMap);
   for (size_t v = 0; v < G.vertexKF.size(); v++) {   // SE3 pose recovering: Sim3 [sR t; 0 1] -> SE3 [R t/s; 0 1]
     const double* S = &G.sim3[8 * v];

@@ -112,6 +112,9 @@ SYMBOLS = {
     "ydorb_essential_graph_trial_step": (C.c_int, [_VP, C.c_double, _VP, C.POINTER(_I)]),
     "ydorb_essential_graph_set_profiling": (C.c_int, [_I, _I]),
     "ydorb_essential_graph_release": (C.c_int, [_I]),
+    "ydorb_essential_graph_plan": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "ydorb_essential_graph_optimize_with": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "ydorb_essential_graph_trial_step_with": (C.c_int, [_VP, _VP, C.c_double, _VP, C.POINTER(_I), _VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -151,6 +154,19 @@ class YdEssentialGraph(C.Structure):
     _fields_ = [("device", _I), ("n_vertices", _I), ("n_edges", _I), ("n_points", _I), ("sim3", _VP), ("fixed", _VP), ("edge_v0", _VP),
                 ("edge_v1", _VP), ("edge_meas", _VP), ("points", _VP), ("point_ref", _VP), ("fix_scale", _I), ("iterations", _I),
                 ("max_trials", _I), ("lambda_init", C.c_double)]
+
+
+ESS_SOLVER_AUTO, ESS_SOLVER_DENSE, ESS_SOLVER_SKYLINE = 0, 1, 2
+ESS_ORDER_SMALLER, ESS_ORDER_NATURAL, ESS_ORDER_RCM = 0, 1, 2
+
+
+class YdEssentialSolverOptions(C.Structure):
+    _fields_ = [("solver", _I), ("ordering", _I), ("max_factor_bytes", C.c_int64)]
+
+
+class YdEssentialSolverInfo(C.Structure):
+    _fields_ = [("solver_used", _I), ("ordering_used", _I), ("n_free", _I), ("max_row_blocks", _I), ("envelope_blocks", C.c_int64),
+                ("envelope_blocks_natural", C.c_int64), ("envelope_blocks_rcm", C.c_int64), ("factor_bytes", C.c_int64)]
 
 
 class YdTriView(C.Structure):

@@ -1,10 +1,11 @@
 // Host driver of the essential-graph optimisation + its C ABI (include/ydorb/c_api.h, "Essential-graph optimisation"):
 // ydorb_essential_graph_optimize, ydorb_essential_graph_linearize, ydorb_essential_graph_trial_step, ydorb_essential_graph_set_profiling,
-// ydorb_essential_graph_release.
+// ydorb_essential_graph_release, and ydorb_essential_graph_plan / _optimize_with / _trial_step_with, which choose the solver.
 // A call checks its arguments, builds the per-vertex lists of incident edges, lays its device memory out once (three arenas of the
 // per-device StagedCtx: the uploaded graph, the work area, the results), uploads in one copy and steps g2o's Levenberg-Marquardt
 // schedule (lm_schedule.h) with one read-back of three scalars per trial.  The kernels are essential_kernels.hip.h's; the dense
-// factorisation is the BA's, queued through chol_factor_solve (ydorb_host.h).
+// factorisation is the BA's, queued through chol_factor_solve (ydorb_host.h); the block-skyline one (essential_skyline.hip.h, planned
+// on the host by skyline_plan.h) differs in the assemble and solve phases of a trial only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,8 +16,10 @@
 
 #include "../../include/ydorb/c_api.h"
 #include "essential_kernels.hip.h"
+#include "essential_skyline.hip.h"
 #include "host_buffers.h"
 #include "lm_schedule.h"
+#include "skyline_plan.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
@@ -36,11 +39,13 @@ enum { PH_LIN = 0, PH_ASM, PH_SOLVE, PH_UPD, PH_CHI, PH_COUNT };
 struct Graph {
   int nV = 0, nE = 0, nP = 0, nF = 0, n = 0;
   std::vector<int> freeOf, vertOf, incStart, incE, incN, incO;
+  bool sky = false;   // the block-skyline solver: P is planned, n = 7 nF
+  sky::Plan P;
 };
 
 int fail(const char* what) { set_error("essential graph: %s", what); return YDORB_ERR_INVALID_ARG; }
 
-// Every check of the ABI, before any device work.
+// Every check of the ABI but the solver's size limit (chooseSolver), before any device work.
 int checkGraph(const YdEssentialGraph* g, bool optimise, Graph& G) {
   if (!g) return fail("null graph");
   if (g->device < 0 || g->device >= 16) return fail("invalid device");
@@ -65,12 +70,6 @@ int checkGraph(const YdEssentialGraph* g, bool optimise, Graph& G) {
   }
   for (int p = 0; p < G.nP; p++)
     if (g->point_ref[p] < 0 || g->point_ref[p] >= G.nV) { set_error("essential graph: point %d references a vertex out of range", p); return YDORB_ERR_INVALID_ARG; }
-  const int maxFree = chol_max_rows() / 7;
-  if (G.nF > maxFree) {
-    set_error("essential graph: %d free vertices, the dense solve takes at most %d (%d rows)", G.nF, maxFree, chol_max_rows());
-    return YDORB_ERR_UNSUPPORTED;
-  }
-  G.n = (7 * G.nF + kCholTile - 1) / kCholTile * kCholTile;
   // incident edges per free vertex, in edge order; then the same entries ordered by neighbour (stable: edge order inside a neighbour)
   G.incStart.assign(G.nF + 1, 0);
   for (int e = 0; e < G.nE; e++) {
@@ -98,12 +97,69 @@ int checkGraph(const YdEssentialGraph* g, bool optimise, Graph& G) {
   return YDORB_OK;
 }
 
-struct UpPtrs { double *est0, *meas; int *v0, *v1, *freeOf, *vertOf, *incStart, *incE, *incN, *incO, *pref; float* pts; };
+const YdEssentialSolverOptions kDenseOptions = {YDORB_ESS_SOLVER_DENSE, YDORB_ESS_ORDER_SMALLER, 0};
+constexpr long long kSkyMaxPairUpdates = 1LL << 24;   // 1.2e10 flop per trial; a dense envelope of 465 block rows, or a band of 6 over a million keyframes
+
+// The solver of this call and its size limit; for SKYLINE, and whenever `info` is asked for, the plan.  Host only.
+int chooseSolver(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, Graph& G, YdEssentialSolverInfo* info) {
+  const YdEssentialSolverOptions O = opt ? *opt : YdEssentialSolverOptions{};
+  if (O.solver < YDORB_ESS_SOLVER_AUTO || O.solver > YDORB_ESS_SOLVER_SKYLINE) return fail("unknown solver");
+  if (O.ordering < YDORB_ESS_ORDER_SMALLER || O.ordering > YDORB_ESS_ORDER_RCM) return fail("unknown ordering");
+  if (O.max_factor_bytes < 0) return fail("negative max_factor_bytes");
+  const int maxFree = chol_max_rows() / 7;
+  G.sky = O.solver == YDORB_ESS_SOLVER_SKYLINE || (O.solver == YDORB_ESS_SOLVER_AUTO && G.nF > maxFree);
+  if (!G.sky && G.nF > maxFree) {
+    set_error("essential graph: %d free vertices, the dense solve takes at most %d (%d rows)", G.nF, maxFree, chol_max_rows());
+    return YDORB_ERR_UNSUPPORTED;
+  }
+  G.n = G.sky ? 7 * G.nF : (7 * G.nF + kCholTile - 1) / kCholTile * kCholTile;
+  if (G.sky || info) {
+    std::vector<int> fa(G.nE), fb(G.nE);
+    for (int e = 0; e < G.nE; e++) { fa[e] = G.freeOf[g->edge_v0[e]]; fb[e] = G.freeOf[g->edge_v1[e]]; }
+    G.P = sky::makePlan(G.nF, G.nE, fa.data(), fb.data(), O.ordering);
+  }
+  if (G.sky) {
+    const long long limit = O.max_factor_bytes ? (long long)O.max_factor_bytes : (long long)chol_max_rows() * chol_max_rows() * 8;
+    const long long bytes = (long long)(G.P.envBlocks * sky::kBlockBytes);
+    if (bytes > limit) {
+      set_error("essential graph: the skyline envelope takes %lld bytes (%lld blocks, %s order), max_factor_bytes is %lld", bytes,
+                (long long)G.P.envBlocks, G.P.orderingUsed == YDORB_ESS_ORDER_RCM ? "RCM" : "natural", limit);
+      return YDORB_ERR_UNSUPPORTED;
+    }
+    // The bytes bound the memory, not the time: one workgroup walks the columns, and a dense envelope within the default bytes would
+    // keep it busy for tens of minutes in one launch that nothing can interrupt.  kSkyMaxPairUpdates block updates (686 flop each)
+    // are a few seconds of that walk per trial at the rate measured on a band; a map's envelope stays orders below.
+    if (G.P.pairUpdates > kSkyMaxPairUpdates) {
+      set_error("essential graph: the skyline factorisation takes %lld block updates per trial (%lld envelope blocks, %s order), at most %lld "
+                "are run in one workgroup", (long long)G.P.pairUpdates, (long long)G.P.envBlocks,
+                G.P.orderingUsed == YDORB_ESS_ORDER_RCM ? "RCM" : "natural", (long long)kSkyMaxPairUpdates);
+      return YDORB_ERR_UNSUPPORTED;
+    }
+    sky::buildColumns(G.P);
+  }
+  if (info) {
+    info->solver_used = G.sky ? YDORB_ESS_SOLVER_SKYLINE : YDORB_ESS_SOLVER_DENSE;
+    info->ordering_used = G.P.orderingUsed; info->n_free = G.nF; info->max_row_blocks = G.P.maxRowBlocks;
+    info->envelope_blocks = G.P.envBlocks; info->envelope_blocks_natural = G.P.envNatural; info->envelope_blocks_rcm = G.P.envRcm;
+    info->factor_bytes = G.sky ? G.P.envBlocks * sky::kBlockBytes : (int64_t)G.n * G.n * 8;
+  }
+  return YDORB_OK;
+}
+
+// The plan's arrays on the device (SKYLINE only; null otherwise)
+struct SkyPtrs { int *inv, *perm, *first, *colRows; long long *rowOff, *colStart, *colBlk; };
+struct UpPtrs { double *est0, *meas; int *v0, *v1, *freeOf, *vertOf, *incStart, *incE, *incN, *incO, *pref; float* pts; SkyPtrs k; };
 size_t layUp(const Graph& G, void* base, UpPtrs& u) {
   Carve a(base);
   const size_t nInc = std::max<size_t>(G.incE.size(), 1), E = std::max(G.nE, 1), P = std::max(G.nP, 1);
   a.take(u.est0, 8 * (size_t)G.nV); a.take(u.meas, 8 * E); a.take(u.v0, E); a.take(u.v1, E); a.take(u.freeOf, G.nV); a.take(u.vertOf, G.nF);
   a.take(u.incStart, G.nF + 1); a.take(u.incE, nInc); a.take(u.incN, nInc); a.take(u.incO, nInc); a.take(u.pts, 3 * P); a.take(u.pref, P);
+  if (G.sky) {
+    a.take(u.k.inv, G.nF); a.take(u.k.perm, G.nF); a.take(u.k.first, G.nF); a.take(u.k.rowOff, G.nF + 1); a.take(u.k.colStart, G.nF + 1);
+    a.take(u.k.colRows, std::max<size_t>(G.P.colRows.size(), 1)); a.take(u.k.colBlk, std::max<size_t>(G.P.colBlk.size(), 1));
+  } else {
+    u.k = SkyPtrs{};
+  }
   return a.L.bytes;
 }
 // The work area.  It keeps what earlier, differently sized calls left, so every array has a first writer inside the call:
@@ -112,13 +168,15 @@ size_t layUp(const Graph& G, void* base, UpPtrs& u) {
 //   diagInv         one memset per call (a panel that meets a non-positive pivot leaves its tile as it was: see ba_solver.hip)
 //   diagL           write-only;  yv: [0, n - 32) by the factorisation's forward substitution, all the solve reads;  x: the solve, [0, n)
 //   sv              k_ess_update, every free vertex
+// SKYLINE: S is the envelope (49 doubles per block), written whole by k_ess_assemble_sky every trial with bkeep, bwork and status;
+// x and diagInv (here the 7 nF reciprocal pivots) by k_ess_sky_solve, every free vertex; diagL and yv are not used and take no room.
 struct WorkPtrs { double *est[2], *err, *chiE, *J, *Hb, *bb, *S, *bkeep, *bwork, *diagInv, *diagL, *yv, *x, *sv; int* status; };
 size_t layWork(const Graph& G, void* base, WorkPtrs& w) {
   Carve a(base);
-  const size_t E = std::max(G.nE, 1), n = G.n;
+  const size_t E = std::max(G.nE, 1), n = G.n, nS = G.sky ? 49 * (size_t)G.P.envBlocks : n * n, nT = G.sky ? 0 : n * kCholTile, nI = G.sky ? n : nT, nY = G.sky ? 0 : n;
   a.take(w.est[0], 8 * (size_t)G.nV); a.take(w.est[1], 8 * (size_t)G.nV); a.take(w.err, 7 * E); a.take(w.chiE, E); a.take(w.J, kJ * E);
-  a.take(w.Hb, kH * E); a.take(w.bb, kB * E); a.take(w.S, n * n); a.take(w.bkeep, n); a.take(w.bwork, n); a.take(w.diagInv, n * kCholTile);
-  a.take(w.diagL, n * kCholTile); a.take(w.yv, n); a.take(w.x, n); a.take(w.sv, G.nF); a.take(w.status, 2);
+  a.take(w.Hb, kH * E); a.take(w.bb, kB * E); a.take(w.S, nS); a.take(w.bkeep, n); a.take(w.bwork, n); a.take(w.diagInv, nI);
+  a.take(w.diagL, nT); a.take(w.yv, nY); a.take(w.x, n); a.take(w.sv, G.nF); a.take(w.status, 2);
   return a.L.bytes;
 }
 struct DownPtrs { double *scal, *est; float* pts; };
@@ -158,11 +216,19 @@ int begin(Run& R_) {
   std::memcpy(h.incStart, G.incStart.data(), 4 * (size_t)(G.nF + 1));
   if (nInc) { std::memcpy(h.incE, G.incE.data(), 4 * nInc); std::memcpy(h.incN, G.incN.data(), 4 * nInc); std::memcpy(h.incO, G.incO.data(), 4 * nInc); }
   if (P) { std::memcpy(h.pts, g->points, 12 * P); std::memcpy(h.pref, g->point_ref, 4 * P); }
+  if (G.sky) {
+    const sky::Plan& K = G.P;
+    std::memcpy(h.k.inv, K.inv.data(), 4 * (size_t)G.nF); std::memcpy(h.k.perm, K.perm.data(), 4 * (size_t)G.nF);
+    std::memcpy(h.k.first, K.first.data(), 4 * (size_t)G.nF);
+    static_assert(sizeof(long long) == sizeof(int64_t), "the plan's offsets go to the device as they are");
+    std::memcpy(h.k.rowOff, K.rowOff.data(), 8 * (size_t)(G.nF + 1)); std::memcpy(h.k.colStart, K.colStart.data(), 8 * (size_t)(G.nF + 1));
+    if (!K.colRows.empty()) { std::memcpy(h.k.colRows, K.colRows.data(), 4 * K.colRows.size()); std::memcpy(h.k.colBlk, K.colBlk.data(), 8 * K.colBlk.size()); }
+  }
   hipStream_t s = c.stream;
   HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, ub, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(R_.w.est[0], R_.u.est0, 64 * (size_t)G.nV, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipMemcpyAsync(R_.w.est[1], R_.u.est0, 64 * (size_t)G.nV, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemsetAsync(R_.w.diagInv, 0, sizeof(double) * (size_t)G.n * kCholTile, s));
+  if (!G.sky) HIPCHK(hipMemsetAsync(R_.w.diagInv, 0, sizeof(double) * (size_t)G.n * kCholTile, s));
   return YDORB_OK;
 }
 
@@ -187,6 +253,30 @@ void linearize(Run& R_, const double* est) {
   if (G.nE)
     hipLaunchKernelGGL(k_ess_linearize, dim3(G.nE), dim3(64), 0, R_.c.stream, G.nE, est, R_.u.freeOf, R_.u.v0, R_.u.v1, R_.u.meas, R_.g->fix_scale,
                        R_.w.err, R_.w.chiE, R_.w.J, R_.w.Hb, R_.w.bb);
+}
+
+// H + lambda I and b of the linearised graph, into the solver's storage
+void assemble(Run& R_, double lambda) {
+  const Graph& G = R_.G;
+  WorkPtrs& w = R_.w;
+  const UpPtrs& u = R_.u;
+  if (G.sky)
+    hipLaunchKernelGGL(k_ess_assemble_sky, dim3(G.nF + 1), dim3(64), 0, R_.c.stream, G.nF, lambda, u.incStart, u.incE, u.incN, u.incO, w.Hb, w.bb, u.k.inv,
+                       u.k.first, u.k.rowOff, w.S, w.bkeep, w.bwork, w.status);
+  else
+    hipLaunchKernelGGL(k_ess_assemble, dim3(G.nF + 1), dim3(64), 0, R_.c.stream, G.nF, G.n, lambda, u.incStart, u.incE, u.incN, u.incO, w.Hb, w.bb, w.S,
+                       w.bkeep, w.bwork, w.status);
+}
+
+// factorise and solve what assemble() left: x, and status[0] raised on a non-positive pivot
+int solve(Run& R_) {
+  const Graph& G = R_.G;
+  WorkPtrs& w = R_.w;
+  if (!G.sky) return chol_factor_solve(R_.c.stream, w.S, w.diagL, w.diagInv, G.n, w.status, w.bwork, w.yv, w.x);
+  const SkyPtrs& k = R_.u.k;
+  hipLaunchKernelGGL(k_ess_sky_solve, dim3(1), dim3(256), 0, R_.c.stream, G.nF, k.first, k.rowOff, k.colStart, k.colRows, k.colBlk, k.perm, w.S, w.bwork, w.x,
+                     w.diagInv, w.status);
+  return YDORB_OK;
 }
 
 int readScal(Run& R_) {
@@ -226,12 +316,11 @@ int optimize(Run& R_, YdBaResult* res, int* curOut) {
       const int nxt = cur ^ 1;
       {
         Phase t(R_, PH_ASM);
-        hipLaunchKernelGGL(k_ess_assemble, dim3(G.nF + 1), dim3(64), 0, s, G.nF, G.n, lm.lambda, R_.u.incStart, R_.u.incE, R_.u.incN, R_.u.incO, w.Hb, w.bb,
-                           w.S, w.bkeep, w.bwork, w.status);
+        assemble(R_, lm.lambda);
       }
       {
         Phase t(R_, PH_SOLVE);
-        if ((rc = chol_factor_solve(s, w.S, w.diagL, w.diagInv, G.n, w.status, w.bwork, w.yv, w.x))) return rc;
+        if ((rc = solve(R_))) return rc;
       }
       {
         Phase t(R_, PH_UPD);
@@ -255,13 +344,29 @@ int optimize(Run& R_, YdBaResult* res, int* curOut) {
 
 }  // namespace
 
-extern "C" int ydorb_essential_graph_optimize(const YdEssentialGraph* g, float* points_out, YdBaResult* res) {
+extern "C" int ydorb_essential_graph_plan(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, YdEssentialSolverInfo* info, int32_t* perm,
+                                          int32_t* first) {
+  if (!info) return fail("null info");
+  std::memset(info, 0, sizeof *info);
+  Graph G;
+  int rc = checkGraph(g, true, G);
+  if (rc) return rc;
+  if ((rc = chooseSolver(g, opt, G, info))) return rc;
+  if (perm) std::memcpy(perm, G.P.perm.data(), 4 * (size_t)G.nF);
+  if (first) std::memcpy(first, G.P.first.data(), 4 * (size_t)G.nF);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_essential_graph_optimize_with(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, float* points_out, YdBaResult* res,
+                                                   YdEssentialSolverInfo* info) {
   if (!res) return fail("null result");
   std::memset(res, 0, sizeof *res);
+  if (info) std::memset(info, 0, sizeof *info);
   EssCtx* ctx = g && g->device >= 0 && g->device < 16 ? &g_ctx[g->device] : &g_ctx[0];
   Run R_(*ctx, g);
   int rc = checkGraph(g, true, R_.G);
   if (rc) return rc;
+  if ((rc = chooseSolver(g, opt, R_.G, info))) return rc;
   if (g->n_points && !points_out) return fail("null points_out");
   if ((rc = require_device(g->device))) return rc;
   EssCtx& c = *ctx;
@@ -288,11 +393,16 @@ extern "C" int ydorb_essential_graph_optimize(const YdEssentialGraph* g, float* 
   return YDORB_OK;
 }
 
+extern "C" int ydorb_essential_graph_optimize(const YdEssentialGraph* g, float* points_out, YdBaResult* res) {
+  return ydorb_essential_graph_optimize_with(g, &kDenseOptions, points_out, res, nullptr);
+}
+
 extern "C" int ydorb_essential_graph_linearize(const YdEssentialGraph* g, double* err, double* J0, double* J1, double* chi2) {
   EssCtx* ctx = g && g->device >= 0 && g->device < 16 ? &g_ctx[g->device] : &g_ctx[0];
   Run R_(*ctx, g);
   int rc = checkGraph(g, false, R_.G);
   if (rc) return rc;
+  if ((rc = chooseSolver(g, &kDenseOptions, R_.G, nullptr))) return rc;
   if ((rc = require_device(g->device))) return rc;
   EssCtx& c = *ctx;
   std::lock_guard<std::mutex> lock(c.mu);
@@ -319,11 +429,53 @@ extern "C" int ydorb_essential_graph_linearize(const YdEssentialGraph* g, double
 }
 
 extern "C" int ydorb_essential_graph_trial_step(const YdEssentialGraph* g, double lambda, double* x, int32_t* solved) {
+  {   // the order of the checks as ever: the graph, the dense limit, then the outputs and lambda
+    Graph G;
+    int rc = checkGraph(g, false, G);
+    if (rc || (rc = chooseSolver(g, &kDenseOptions, G, nullptr))) return rc;
+    if (!x || !solved || !(lambda > 0)) return fail("trial step: null output or non-positive lambda");
+  }
+  return ydorb_essential_graph_trial_step_with(g, &kDenseOptions, lambda, x, solved, nullptr, nullptr);
+}
+
+// The assembled system (lambda = 0) out of the solver's storage, expanded to dense in the caller's vertex order.
+int copySystem(Run& R_, double* H_out, double* b_out) {
+  const Graph& G = R_.G;
+  hipStream_t s = R_.c.stream;
+  const size_t N = 7 * (size_t)G.nF;
+  if (b_out) HIPCHK(hipMemcpyAsync(b_out, R_.w.bkeep, 8 * N, hipMemcpyDeviceToHost, s));
+  if (!H_out) { HIPCHK(hipStreamSynchronize(s)); return YDORB_OK; }
+  std::vector<double> S(G.sky ? 49 * (size_t)G.P.envBlocks : (size_t)G.n * G.n);
+  HIPCHK(hipMemcpyAsync(S.data(), R_.w.S, 8 * S.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (!G.sky) {
+    for (size_t r = 0; r < N; r++) std::memcpy(H_out + r * N, S.data() + r * G.n, 8 * N);
+    return YDORB_OK;
+  }
+  std::fill(H_out, H_out + N * N, 0.0);
+  const sky::Plan& K = G.P;
+  for (int i = 0; i < G.nF; i++)
+    for (int j = K.first[i]; j <= i; j++) {
+      const double* B = S.data() + 49 * (size_t)(K.rowOff[i] + (j - K.first[i]));
+      const size_t a = 7 * (size_t)K.perm[i], o = 7 * (size_t)K.perm[j];
+      for (int r = 0; r < 7; r++)
+        for (int c = 0; c < 7; c++) {
+          H_out[(a + r) * N + o + c] = B[7 * r + c];
+          if (i != j) H_out[(o + c) * N + a + r] = B[7 * r + c];
+        }
+    }
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_essential_graph_trial_step_with(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, double lambda, double* x,
+                                                     int32_t* solved, double* H_out, double* b_out) {
   EssCtx* ctx = g && g->device >= 0 && g->device < 16 ? &g_ctx[g->device] : &g_ctx[0];
   Run R_(*ctx, g);
   int rc = checkGraph(g, false, R_.G);
   if (rc) return rc;
-  if (!x || !solved || !(lambda > 0)) return fail("trial step: null output or non-positive lambda");
+  if (!x || !solved) return fail("trial step: null output or non-positive lambda");
+  if ((rc = chooseSolver(g, opt, R_.G, nullptr))) return rc;
+  if ((H_out || b_out) && 7 * R_.G.nF > 4096) return fail("trial step: H_out / b_out are copied for at most 4096 rows");
   if ((rc = require_device(g->device))) return rc;
   EssCtx& c = *ctx;
   std::lock_guard<std::mutex> lock(c.mu);
@@ -335,9 +487,12 @@ extern "C" int ydorb_essential_graph_trial_step(const YdEssentialGraph* g, doubl
   c.profiling = false;
   linearize(R_, w.est[0]);
   c.profiling = was;
-  hipLaunchKernelGGL(k_ess_assemble, dim3(G.nF + 1), dim3(64), 0, c.stream, G.nF, G.n, lambda, R_.u.incStart, R_.u.incE, R_.u.incN, R_.u.incO, w.Hb, w.bb, w.S,
-                     w.bkeep, w.bwork, w.status);
-  if ((rc = chol_factor_solve(c.stream, w.S, w.diagL, w.diagInv, G.n, w.status, w.bwork, w.yv, w.x))) return rc;
+  if (H_out || b_out) {
+    assemble(R_, 0.0);
+    if ((rc = copySystem(R_, H_out, b_out))) return rc;
+  }
+  assemble(R_, lambda);
+  if ((rc = solve(R_))) return rc;
   int status[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(x, w.x, sizeof(double) * 7 * (size_t)G.nF, hipMemcpyDeviceToHost, c.stream));
   HIPCHK(hipMemcpyAsync(status, w.status, sizeof(int), hipMemcpyDeviceToHost, c.stream));
