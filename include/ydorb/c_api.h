@@ -466,6 +466,46 @@ int ydorb_pose_optimize(const YdPoseBatch* batch, uint8_t* outlier, int32_t* n_i
 /* dense SPD solve with the BA's blocked Cholesky (known-answer tests; A is n x n row-major, host pointers) */
 int ydorb_ba_dense_solve(int32_t device, const double* A, int32_t n, const double* b, double* x, int32_t* ok);
 
+/* The reduced camera system's second solver.  DENSE holds S as (6 nPf)^2 doubles, nPf the free poses, and stops
+ * at dense_max_rows = 19 200 rows, 3 200 free keyframes.  SKYLINE holds the envelope of S's 6x6 blocks under an order of the free
+ * poses: memory and work follow the covisibility band, the pose-pair buckets are the covisible pairs + nPf instead of
+ * nPf (nPf + 1) / 2, and nothing is sized by nPf^2.  AUTO is DENSE whenever 6 nPf <= dense_max_rows and SKYLINE above: a call that
+ * succeeded before returns the same bytes, a call that was refused now succeeds.  `ordering` is YDORB_ESS_ORDER_SMALLER / NATURAL /
+ * RCM (below, "Essential graph").  SKYLINE is refused with YDORB_ERR_UNSUPPORTED on the host, before any kernel runs and before the
+ * stage's device memory is sized (ydorb_ba_plan gives the same answer without touching a device),
+ *   - when world > 1 (the all-reduce of S stays dense only);
+ *   - when the envelope takes more than max_factor_bytes (0 = 19 200^2 * 8 B, the largest dense S);
+ *   - when the factorisation takes more than 2^24 block updates per trial (sum over the block columns of m (m + 1) / 2, m = the rows
+ *     below the diagonal that reach the column; 432 flop each, 7.2e9 flop): one workgroup walks the columns in one launch that
+ *     nothing can interrupt, and section 6j allows such a launch 1.2e10 flop.
+ * The error text names the size and the limit.  ydorb_ba_solve is ydorb_ba_solve_with(DENSE); ydorb_ba_solve_batch stays dense only. */
+enum { YDORB_BA_SOLVER_AUTO = 0, YDORB_BA_SOLVER_DENSE = 1, YDORB_BA_SOLVER_SKYLINE = 2 };
+typedef struct YdBaSolverOptions {
+  int32_t solver, ordering;
+  int64_t max_factor_bytes;      /* 0 = default */
+} YdBaSolverOptions;
+typedef struct YdBaSolverInfo {
+  int32_t solver_used, ordering_used, n_free, max_row_blocks, dense_max_rows, reserved;
+  int64_t covisible_pairs;       /* pairs of free poses that share a landmark; the skyline path has covisible_pairs + n_free buckets */
+  int64_t envelope_blocks, envelope_blocks_natural, envelope_blocks_rcm;
+  int64_t pair_updates;          /* block updates of one factorisation */
+  int64_t factor_bytes;          /* of S as the solver used holds it */
+} YdBaSolverInfo;
+/* Host only, touches no device: the solver a solve of `prob` would use and its plan.  perm [n_free] (free pose at each position of
+ * the order) and first [n_free] (first block column of each row) may be NULL.  NULL sopt = AUTO. */
+int ydorb_ba_plan(const YdBaProblem* prob, const YdBaOptions* opt, const YdBaSolverOptions* sopt, YdBaSolverInfo* info, int32_t* perm,
+                  int32_t* first);
+/* ydorb_ba_solve with the solver chosen; info may be NULL.  NULL sopt = AUTO. */
+int ydorb_ba_solve_with(const YdBaProblem* prob, const YdBaOptions* opt, const YdBaSolverOptions* sopt, YdBaResult* res, YdBaSolverInfo* info);
+/* TEST / DEBUG: one linearisation at the given estimate and one Schur complement with `lambda` (not range-checked: a negative one
+ * must give *solved = 0), S expanded on the host to [6F][6F] full symmetric in the caller's free-pose order, bs [6F] and the solve
+ * x [6F].  Refused when 6F > 4096.  prob is not written. */
+int ydorb_ba_reduced_system_with(const YdBaProblem* prob, const YdBaOptions* opt, const YdBaSolverOptions* sopt, double lambda,
+                                 double* S_out, double* bs_out, double* x_out, int32_t* solved);
+/* TEST / DEBUG: the counterpart of ydorb_ba_dense_solve.  A is n x n row-major, n a multiple of 6 and <= 4096; the block pattern is
+ * the set of non-zero 6x6 blocks of A. */
+int ydorb_ba_skyline_solve(int32_t device, const double* A, int32_t n, const double* b, int32_t ordering, double* x, int32_t* ok);
+
 /* ------------------------------------------------------------------------------------------
  * Sim3 RANSAC of the loop-closure check.  Replaces Sim3Solver::iterate (ORB-SLAM2 src/Sim3Solver.cc: iterate, ComputeSim3,
  * CheckInliers, Project) for a batch of candidate keyframes; LoopClosing::computeSim3 calls it with chunk 5 per candidate.

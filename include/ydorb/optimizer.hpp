@@ -52,7 +52,7 @@ inline cv::Mat se3QuatToPose(const double* p7) {
 }
 
 template <class KeyFramePtr, class MapPtr, class FrameT>
-void localBundleAdjustImpl(KeyFramePtr kf0, MapPtr map, const volatile bool* stop) {
+void localBundleAdjustImpl(KeyFramePtr kf0, MapPtr map, const volatile bool* stop, int solver = YDORB_BA_SOLVER_AUTO) {
   typedef decltype(kf0->getMatchedMapPointsVec()) MapPointVec;
   typedef typename MapPointVec::value_type MapPointPtr;
   const long int tag = kf0->m_int_keyFrameID;
@@ -121,7 +121,8 @@ void localBundleAdjustImpl(KeyFramePtr kf0, MapPtr map, const volatile bool* sto
   std::vector<uint8_t> outlier(ePose.size() + 1, 0);
   YdBaResult res{};
   res.edge_outlier = outlier.data();
-  if (ydorb_ba_solve(&P, nullptr, &res) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
+  const YdBaSolverOptions SO = {solver, YDORB_ESS_ORDER_SMALLER, 0};   // AUTO: the dense solve up to its 3 200 free keyframes, block-skyline above
+  if (ydorb_ba_solve_with(&P, nullptr, &SO, &res, nullptr) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
   // write-back (:336-351)
   std::unique_lock<std::mutex> lock(map->m_mutex_updateMap);
   for (size_t e = 0; e < ePose.size(); e++)
@@ -145,7 +146,7 @@ void localBundleAdjustImpl(KeyFramePtr kf0, MapPtr map, const volatile bool* sto
 // becomes  ydorb::adapter::bundleAdjustImpl<Frame>(kfs, mps, iterNum, &stop == nullptr ? nullptr : &stop, loopKFid, robust);
 template <class FrameT, class KeyFramePtr, class MapPointPtr>
 void bundleAdjustImpl(const std::vector<KeyFramePtr>& kfs, const std::vector<MapPointPtr>& mps, int iterNum, const volatile bool* stop,
-                      long int loopKeyFrameID, bool robust) {
+                      long int loopKeyFrameID, bool robust, int solver = YDORB_BA_SOLVER_AUTO) {
   std::vector<KeyFramePtr> poseKF;
   std::map<long int, int> poseIndex;
   std::vector<double> poses;
@@ -192,7 +193,8 @@ void bundleAdjustImpl(const std::vector<KeyFramePtr>& kfs, const std::vector<Map
   O.delta_mono = (double)(float)std::sqrt(5.99);   // `const float monoDelta = sqrt(5.99)`, :37
   O.flags = YDORB_BA_SINGLE_STAGE | (robust ? 0 : YDORB_BA_NO_ROBUST);
   YdBaResult res{};
-  if (ydorb_ba_solve(&P, &O, &res) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
+  const YdBaSolverOptions SO = {solver, YDORB_ESS_ORDER_SMALLER, 0};   // AUTO: the dense solve up to its 3 200 free keyframes, block-skyline above
+  if (ydorb_ba_solve_with(&P, &O, &SO, &res, nullptr) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
   for (size_t k = 0; k < poseKF.size(); k++) {   // :113-124
     const cv::Mat T = se3QuatToPose(&poses[7 * k]);
     if (loopKeyFrameID == 0) {
@@ -513,8 +515,8 @@ void optimizeEssentialGraphImpl(MapPtr map, KeyFramePtr loopKF, KeyFramePtr curK
 
 // Optimizer::globalBundleAdjust (optimizer.cpp:353-357)
 template <class FrameT, class MapPtr>
-void globalBundleAdjustImpl(MapPtr map, int iterNum, const volatile bool* stop, long int loopKeyFrameID, bool robust) {
-  bundleAdjustImpl<FrameT>(map->getAllKeyFrames(), map->getAllMapPoints(), iterNum, stop, loopKeyFrameID, robust);
+void globalBundleAdjustImpl(MapPtr map, int iterNum, const volatile bool* stop, long int loopKeyFrameID, bool robust, int solver = YDORB_BA_SOLVER_AUTO) {
+  bundleAdjustImpl<FrameT>(map->getAllKeyFrames(), map->getAllMapPoints(), iterNum, stop, loopKeyFrameID, robust, solver);
 }
 
 }  // namespace adapter

@@ -80,6 +80,10 @@ SYMBOLS = {
     "ydorb_ba_solve": (C.c_int, [_VP, _VP, _VP]),
     "ydorb_ba_solve_batch": (C.c_int, [_VP, _I, _VP, _VP, _I, _VP]),
     "ydorb_ba_dense_solve": (C.c_int, [_I, _VP, _I, _VP, _VP, C.POINTER(_I)]),
+    "ydorb_ba_plan": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_ba_solve_with": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "ydorb_ba_reduced_system_with": (C.c_int, [_VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.POINTER(_I)]),
+    "ydorb_ba_skyline_solve": (C.c_int, [_I, _VP, _I, _VP, _I, _VP, C.POINTER(_I)]),
     "ydorb_pose_optimize": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "ydorb_sim3_ransac": (C.c_int, [_VP, _I, _I, _I]),
     "ydorb_sim3_optimize": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
@@ -214,6 +218,19 @@ class YdBaOptions(C.Structure):
 
 BA_SINGLE_STAGE, BA_NO_ROBUST, BA_PHASE_TIMES = 1, 2, 4
 BA_TEST_LATE_UPLOADS = 8   # test only: see c_api.h
+
+
+BA_SOLVER_AUTO, BA_SOLVER_DENSE, BA_SOLVER_SKYLINE = 0, 1, 2   # orderings: ESS_ORDER_*
+
+
+class YdBaSolverOptions(C.Structure):
+    _fields_ = [("solver", _I), ("ordering", _I), ("max_factor_bytes", C.c_int64)]
+
+
+class YdBaSolverInfo(C.Structure):
+    _fields_ = [("solver_used", _I), ("ordering_used", _I), ("n_free", _I), ("max_row_blocks", _I), ("dense_max_rows", _I), ("reserved", _I),
+                ("covisible_pairs", C.c_int64), ("envelope_blocks", C.c_int64), ("envelope_blocks_natural", C.c_int64),
+                ("envelope_blocks_rcm", C.c_int64), ("pair_updates", C.c_int64), ("factor_bytes", C.c_int64)]
 
 
 class YdBaResult(C.Structure):

@@ -21,6 +21,8 @@
 
 #include "../../include/ydorb/c_api.h"
 #include "ba_kernels.hip.h"
+#include "ba_pairs.h"
+#include "ba_skyline.hip.h"
 #include "host_buffers.h"
 #include "lm_schedule.h"
 #include "ydorb_host.h"
@@ -33,7 +35,14 @@ namespace {
 enum { PH_ERR = 0, PH_BUILD, PH_SCHUR, PH_SOLVE, PH_UPDATE, PH_COUNT };
 
 // The reduced system of one optimize() call: stage 1 sizes it, stage 2 re-uses it (and the arenas laid out for it) as it is.
-struct Sys { std::vector<int> act; int nL = 0, nPf = 0, Ea = 0, n = 0, nb = 0, nBlkE = 0, nBuckets = 0, nPoseEdges = 0; size_t nItems = 0; };
+// sky: the block-skyline solver (ba_skyline.hip.h).  n = 6 nPf then, nBuckets = the covisible pairs + nPf, and `plan` holds the envelope.
+struct Sys {
+  std::vector<int> act; int nL = 0, nPf = 0, Ea = 0, n = 0, nb = 0, nBlkE = 0, nBuckets = 0, nPoseEdges = 0; size_t nItems = 0;
+  bool sky = false;
+  sky::Plan plan;
+  size_t envDoubles() const { return 36 * (size_t)plan.envBlocks; }
+};
+static_assert(bapairs::kDenseMaxRows == kCholSolveMaxN, "ba_pairs.h states the dense limit for the host-only plan");
 
 // `state`: both copies of the estimate (LM push / pop is a swap of the index).  beginSolve uploads [0]; prepareStage copies cur -> cur ^ 1
 // whole before the first k_update of a stage, which writes the free poses and the active landmarks only.
@@ -46,12 +55,20 @@ size_t layState(int K, int NP, void* base, StatePtrs& st) {
 
 // `up`: what the host orders and uploads for a stage, through the pinned staging area at the same offsets and with ONE copy (twelve
 // before: with 16 set-up threads of a batch the runtime's lock was the cost).  Written whole by that copy; k_cull later rewrites eInfo / eRobust.
-struct UpPtrs { int *ePose, *ePidx, *ePt, *eLm, *ptStart, *poseStart, *ptOf, *poseEdges, *poseOf; double *eMeas, *eInfo; uint8_t* eRobust; };
+// SKYLINE adds the pair table (PairList: rowStart, i1, i2 and each bucket's place in the envelope) and the plan's arrays.
+struct SkyPtrs { int *pairRow, *pairI1, *pairI2, *perm, *first, *colRows; long long *pairDst, *rowOff, *colStart, *colBlk; };
+struct UpPtrs { int *ePose, *ePidx, *ePt, *eLm, *ptStart, *poseStart, *ptOf, *poseEdges, *poseOf; double *eMeas, *eInfo; uint8_t* eRobust; SkyPtrs k; };
 size_t layUp(const Sys& Y, void* base, UpPtrs& u) {
   Carve a(base);
   const size_t Ea = Y.Ea;
   a.take(u.ePose, Ea); a.take(u.ePidx, Ea); a.take(u.ePt, Ea); a.take(u.eLm, Ea); a.take(u.eMeas, 3 * Ea); a.take(u.eInfo, Ea); a.take(u.eRobust, Ea);
   a.take(u.ptStart, Y.nL + 1); a.take(u.poseStart, Y.nPf + 1); a.take(u.ptOf, Y.nL); a.take(u.poseEdges, Y.nPoseEdges); a.take(u.poseOf, Y.nPf);
+  u.k = SkyPtrs{};
+  if (Y.sky) {
+    const size_t nB = Y.nBuckets, nF = Y.nPf, nCol = Y.plan.colRows.size();
+    a.take(u.k.pairRow, nF + 1); a.take(u.k.pairI1, nB); a.take(u.k.pairI2, nB); a.take(u.k.pairDst, nB); a.take(u.k.perm, nF); a.take(u.k.first, nF);
+    a.take(u.k.rowOff, nF + 1); a.take(u.k.colStart, nF + 1); a.take(u.k.colRows, nCol); a.take(u.k.colBlk, nCol);
+  }
   return a.L.bytes;
 }
 
@@ -75,23 +92,29 @@ size_t layUp(const Sys& Y, void* base, UpPtrs& u) {
 //             solve read whatever the memory held.  diagL is write-only.
 //   yv        [0, n - 32) by the forward-substitution workgroup of k_chol_step launches 1 .. nb - 1, all k_chol_solve reads
 //   xp        k_chol_solve, [0, n);  xl: k_backsub, every landmark
+//   SKYLINE   S is the envelope (36 doubles per block) | bs: the envelope is cleared and then written by k_sky_schur_pairs in EVERY trial
+//             (the factorisation overwrites it, and the blocks no pair writes are its fill), bs by k_bs as above.  skyW [12 nPf]: b by
+//             position, then the reciprocal pivots, both written whole by k_sky_solve before it reads them.  diagInv, diagL and yv take
+//             no room.  pair*: as above with the pair table's buckets.
 //   scal      [0] and [2] k_sum_partials, [1] k_max_diag (first iteration), [6], [7] the status copies; [3 .. 5] are never written: they
 //             travel to the host with every read-back and nothing there reads them
 struct WorkPtrs {
-  double *eInfo0, *err, *partial, *Hll, *bl, *Hpl, *BD, *Hpp, *S, *diagInv, *diagL, *Dinv, *db, *xp, *xl, *yv, *scal;
+  double *eInfo0, *err, *partial, *Hll, *bl, *Hpl, *BD, *Hpp, *S, *diagInv, *diagL, *Dinv, *db, *xp, *xl, *yv, *skyW, *scal;
   uint8_t* eOutlier;
   int *status, *pairCnt, *pairStart, *pairCursor;
   int2 *pairA, *pairB;
   double* bp(const Sys& Y) const { return Hpp + (size_t)36 * Y.nPf; }   // Hpp | bp: one all-reduce covers both
-  double* bs(const Sys& Y) const { return S + (size_t)Y.n * Y.n; }      // S | bs likewise
+  double* bs(const Sys& Y) const { return S + (Y.sky ? Y.envDoubles() : (size_t)Y.n * Y.n); }      // S | bs likewise
 };
 size_t layWork(const Sys& Y, void* base, WorkPtrs& w) {
   Carve a(base);
-  const size_t Ea = Y.Ea, nL = Y.nL, nPf = Y.nPf, n = Y.n, tiles = (size_t)Y.nb * NB * NB, nBk = (size_t)Y.nBuckets + 1, items = std::max<size_t>(Y.nItems, 1);
+  const size_t Ea = Y.Ea, nL = Y.nL, nPf = Y.nPf, n = Y.n, tiles = Y.sky ? 0 : (size_t)Y.nb * NB * NB, nBk = (size_t)Y.nBuckets + 1, items = std::max<size_t>(Y.nItems, 1);
   a.take(w.eInfo0, Ea); a.take(w.eOutlier, Ea); a.take(w.err, 3 * Ea); a.take(w.partial, Y.nBlkE + (6 * nPf + 3 * nL + 255) / 256 + 1);
   a.take(w.Hll, 6 * nL); a.take(w.bl, 3 * nL); a.take(w.Hpl, 18 * Ea); a.take(w.BD, 18 * Ea); a.take(w.Hpp, 42 * std::max<size_t>(nPf, 1));
-  a.take(w.S, n * n + n + tiles); w.diagInv = w.S + n * n + n;   // one array on purpose: cleared together
-  a.take(w.diagL, tiles); a.take(w.Dinv, 6 * nL); a.take(w.db, 3 * nL); a.take(w.xp, n); a.take(w.yv, n); a.take(w.xl, 3 * nL);
+  const size_t nS = Y.sky ? Y.envDoubles() : n * n;
+  a.take(w.S, nS + n + tiles); w.diagInv = w.S + nS + n;   // one array on purpose: cleared together
+  a.take(w.diagL, tiles); a.take(w.Dinv, 6 * nL); a.take(w.db, 3 * nL); a.take(w.xp, n); a.take(w.yv, Y.sky ? 0 : n); a.take(w.skyW, Y.sky ? 2 * n : 0);
+  a.take(w.xl, 3 * nL);
   a.take(w.scal, 8); a.take(w.status, 2); a.take(w.pairCnt, nBk); a.take(w.pairStart, nBk); a.take(w.pairCursor, nBk); a.take(w.pairA, items); a.take(w.pairB, items);
   return a.L.bytes;
 }
@@ -173,12 +196,53 @@ struct Run {
   hipEvent_t* ev = nullptr;   // Ctx::ev and Ctx::hPin of a single solve (optimize()); a lock-step batch member has neither
   double* hPin = nullptr;
   LmSchedule lm;   // lambda, nu, the counters and every decision on them
+  const YdBaSolverOptions* SO = nullptr;   // null: DENSE (ydorb_ba_solve, the lock-step batch)
+  YdBaSolverInfo* info = nullptr;
   bool stopped() const { return LmSchedule::raised(P->stop); }
 };
 
 int tooWideForSolve(int n) {
   set_error("reduced camera system of %d rows is wider than the solve kernel's LDS (max %d)", n, kCholSolveMaxN);
   return YDORB_ERR_UNSUPPORTED;
+}
+
+int denseRows(int nPf) { return std::max(NB, (6 * nPf + NB - 1) / NB * NB); }
+
+// The solver of a problem with nPf free poses, host only.  For SKYLINE, and whenever `info` is asked for, `pairs` is built by
+// makePairs() and the envelope planned (with the column lists when `columns`).  Nothing here touches a device: a refusal comes before the
+// stage's arenas are sized and before any of its kernels.
+template <class MakePairs>
+int chooseSolver(const YdBaSolverOptions* opt, int world, int nPf, MakePairs makePairs, bool columns, bapairs::PairList& pairs, sky::Plan& plan,
+                 bool& sky, YdBaSolverInfo* info) {
+  const YdBaSolverOptions O = opt ? *opt : YdBaSolverOptions{YDORB_BA_SOLVER_DENSE, YDORB_ESS_ORDER_SMALLER, 0};
+  if (O.solver < YDORB_BA_SOLVER_AUTO || O.solver > YDORB_BA_SOLVER_SKYLINE) { set_error("BA: unknown solver"); return YDORB_ERR_INVALID_ARG; }
+  if (O.ordering < YDORB_ESS_ORDER_SMALLER || O.ordering > YDORB_ESS_ORDER_RCM) { set_error("BA: unknown ordering"); return YDORB_ERR_INVALID_ARG; }
+  if (O.max_factor_bytes < 0) { set_error("BA: negative max_factor_bytes"); return YDORB_ERR_INVALID_ARG; }
+  if (O.solver == YDORB_BA_SOLVER_SKYLINE && world > 1) {
+    set_error("BA: the skyline solver runs on one rank (the all-reduce of S is dense only)");
+    return YDORB_ERR_UNSUPPORTED;
+  }
+  const bool over = 6 * (long long)nPf > kCholSolveMaxN;
+  sky = O.solver == YDORB_BA_SOLVER_SKYLINE || (O.solver == YDORB_BA_SOLVER_AUTO && over && world <= 1);
+  if (!sky && over) return tooWideForSolve(denseRows(nPf));
+  if (info) memset(info, 0, sizeof(*info));
+  if (sky || info) {
+    pairs = makePairs();
+    std::string err;
+    if (pairs.buckets() > bapairs::kMaxBuckets) { set_error("BA: %lld pose-pair buckets, at most %lld", (long long)pairs.buckets(), (long long)bapairs::kMaxBuckets); return YDORB_ERR_UNSUPPORTED; }
+    if (!bapairs::planEnvelope(pairs, O.ordering, O.max_factor_bytes, sky && columns, plan, err) && sky) {
+      set_error("%s", err.c_str());
+      return YDORB_ERR_UNSUPPORTED;
+    }
+  }
+  if (info) {
+    info->solver_used = sky ? YDORB_BA_SOLVER_SKYLINE : YDORB_BA_SOLVER_DENSE;
+    info->ordering_used = plan.orderingUsed; info->n_free = nPf; info->max_row_blocks = plan.maxRowBlocks; info->dense_max_rows = kCholSolveMaxN;
+    info->covisible_pairs = pairs.covisiblePairs; info->envelope_blocks = plan.envBlocks; info->envelope_blocks_natural = plan.envNatural;
+    info->envelope_blocks_rcm = plan.envRcm; info->pair_updates = plan.pairUpdates;
+    info->factor_bytes = sky ? plan.envBlocks * bapairs::kBlockBytes : (int64_t)denseRows(nPf) * denseRows(nPf) * 8;
+  }
+  return YDORB_OK;
 }
 
 int allreduce(Run& R_, void* d_buf, int64_t count, int op) {
@@ -301,11 +365,21 @@ int prepareStage(Run& R_, bool reuse) {
     Z.nL = nL; Z.nPf = nPf; Z.Ea = Ea; Z.nPoseEdges = (int)hPoseEdges.size();
     Z.n = std::max(NB, (6 * nPf + NB - 1) / NB * NB); Z.nb = Z.n / NB;
     Z.nBlkE = (Ea + 255) / 256;
-    Z.nBuckets = nPf * (nPf + 1) / 2;   // pose-pair buckets of the Schur complement (structure is fixed for this optimize() call)
+    Z.nBuckets = (int)std::min<long long>((long long)nPf * (nPf + 1) / 2, std::numeric_limits<int>::max());   // pose-pair buckets of the Schur complement (structure is fixed for this optimize() call); SKYLINE sets its own below
     for (int l = 0; l < nL; l++) {
       size_t m = 0;
       for (int i = hPtStart[l]; i < hPtStart[l + 1]; i++) m += hPidx[i] >= 0;
       Z.nItems += m * (m + 1) / 2;
+    }
+    bapairs::PairList pairs;
+    std::vector<int64_t> pairDst;
+    {
+      int rc = chooseSolver(R_.SO, O.world, nPf, [&] { return bapairs::buildPairs(nPf, nL, hPtStart.data(), hPidx.data()); }, true, pairs, Z.plan, Z.sky, R_.info);
+      if (rc) return rc;
+      if (Z.sky) {   // nothing on this path is sized by nPf^2
+        Z.n = 6 * nPf; Z.nb = 0; Z.nBuckets = (int)pairs.buckets();
+        pairDst = bapairs::bucketDestinations(pairs, Z.plan);
+      }
     }
     trace("optimize: host ordering done");
     // the two arenas of the stage: sized, grown if need be (at most two hipMalloc where every array had its own), then laid out
@@ -324,6 +398,11 @@ int prepareStage(Run& R_, bool reuse) {
       upv(u.ePose, hPose); upv(u.ePidx, hPidx); upv(u.ePt, hPt); upv(u.eLm, hLm); upv(u.eMeas, hMeas); upv(u.eInfo, hInfo);
       upv(u.eRobust, hRobust); upv(u.ptStart, hPtStart); upv(u.poseStart, hPoseStart); upv(u.ptOf, ptOf);
       upv(u.poseEdges, hPoseEdges); upv(u.poseOf, poseOf);
+      if (Z.sky) {
+        const sky::Plan& K = Z.plan;
+        upv(u.k.pairRow, pairs.rowStart); upv(u.k.pairI1, pairs.i1); upv(u.k.pairI2, pairs.i2); upv(u.k.pairDst, pairDst); upv(u.k.perm, K.perm);
+        upv(u.k.first, K.first); upv(u.k.rowOff, K.rowOff); upv(u.k.colStart, K.colStart); upv(u.k.colRows, K.colRows); upv(u.k.colBlk, K.colBlk);
+      }
       HIPCHK(hipMemcpyAsync(c.up.p, c.hStage.p, upBytes, hipMemcpyHostToDevice, s));
       // the original information: the chi2 tests between and after the stages use it (k_cull)
       HIPCHK(hipMemcpyAsync(w.eInfo0, u.eInfo, sizeof(double) * Ea, hipMemcpyDeviceToDevice, s));
@@ -334,10 +413,12 @@ int prepareStage(Run& R_, bool reuse) {
       const int nBuckets = Z.nBuckets;
       EdgeSoA Ed{u.ePose, u.ePidx, u.ePt, u.eMeas, u.eInfo, u.eRobust, Ea};
       HIPCHK(hipMemsetAsync(w.pairCnt, 0, sizeof(int) * (nBuckets + 1), s));
-      hipLaunchKernelGGL(k_pair_count, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, w.pairCnt);
+      if (Z.sky) hipLaunchKernelGGL(k_sky_pair_count, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, u.k.pairRow, u.k.pairI1, w.pairCnt);
+      else hipLaunchKernelGGL(k_pair_count, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, w.pairCnt);
       hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(256), 0, s, w.pairCnt, nBuckets, w.pairStart);
       HIPCHK(hipMemcpyAsync(w.pairCursor, w.pairStart, sizeof(int) * (nBuckets + 1), hipMemcpyDeviceToDevice, s));
-      hipLaunchKernelGGL(k_pair_fill, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, w.pairCursor, w.pairA);
+      if (Z.sky) hipLaunchKernelGGL(k_sky_pair_fill, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, u.k.pairRow, u.k.pairI1, w.pairCursor, w.pairA);
+      else hipLaunchKernelGGL(k_pair_fill, dim3((nL + 255) / 256), dim3(256), 0, s, Ed, u.ptStart, nL, w.pairCursor, w.pairA);
       hipLaunchKernelGGL(k_pair_sort, dim3((nBuckets + 3) / 4), dim3(256), 0, s, w.pairStart, nBuckets, w.pairA, w.pairB);
     }
     HIPCHK(hipStreamSynchronize(s));   // the host staging vectors above die with this scope
@@ -356,7 +437,46 @@ int prepareStage(Run& R_, bool reuse) {
   // the two estimate buffers must agree on everything the update kernel does not write (fixed poses, points without edges)
   HIPCHK(hipMemcpyAsync(c.st.poses[R_.cur ^ 1], c.st.poses[R_.cur], sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipMemcpyAsync(c.st.pts[R_.cur ^ 1], c.st.pts[R_.cur], sizeof(double) * 3 * NP, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemsetAsync(c.w.S, 0, sizeof(double) * ((size_t)Y.n * Y.n + Y.n + (size_t)Y.nb * NB * NB), s));   // S | bs | diagInv (see WorkPtrs)
+  if (!Y.sky) HIPCHK(hipMemsetAsync(c.w.S, 0, sizeof(double) * ((size_t)Y.n * Y.n + Y.n + (size_t)Y.nb * NB * NB), s));   // S | bs | diagInv (see WorkPtrs)
+  return YDORB_OK;
+}
+
+// The Schur complement of one LM trial, S | bs from Hpp, Hpl, Hll and lambda, and its solve into xp: the two phases that differ
+// between the solvers.  optimize() and ydorb_ba_reduced_system_with queue the same launches.
+int launchSchur(Run& R_, double lambda, double contrib) {
+  SolveMem& c = *R_.c;
+  const Sys& Y = R_.sys;
+  const UpPtrs& u = c.u;
+  const WorkPtrs& w = c.w;
+  hipStream_t s = c.stream;
+  EdgeSoA Ed{u.ePose, u.ePidx, u.ePt, u.eMeas, u.eInfo, u.eRobust, Y.Ea};
+  double *dbp = w.bp(Y), *dbs = w.bs(Y);
+  hipLaunchKernelGGL(k_dinv, dim3((Y.nL + 255) / 256), dim3(256), 0, s, w.Hll, w.bl, Y.nL, lambda, w.Dinv, w.db, w.status);
+  hipLaunchKernelGGL(k_bd, dim3(Y.nBlkE), dim3(256), 0, s, Ed, u.eLm, w.Hpl, w.Dinv, w.BD);
+  if (Y.nPf)
+    hipLaunchKernelGGL(k_bs, dim3(Y.nPf), dim3(256), 0, s, Ed, u.poseStart, u.poseEdges, u.eLm, w.Hpl, w.db, dbp, contrib, dbs);
+  if (!Y.sky) {
+    hipLaunchKernelGGL(k_schur_pairs, dim3(Y.nBuckets + 1), dim3(64 * kSchurWaves), 0, s, w.pairStart, w.pairB, Y.nPf, Y.nBuckets, w.BD, w.Hpl, w.Hpp, lambda, contrib, Y.n, w.S, dbs);
+  } else if (Y.nBuckets) {
+    HIPCHK(hipMemsetAsync(w.S, 0, sizeof(double) * Y.envDoubles(), s));   // the fill: blocks of the envelope that no bucket writes
+    hipLaunchKernelGGL(k_sky_schur_pairs, dim3(Y.nBuckets), dim3(64 * kSchurWaves), 0, s, w.pairStart, w.pairB, Y.nBuckets, u.k.pairI1, u.k.pairI2, u.k.pairDst, w.BD, w.Hpl, w.Hpp, lambda, w.S);
+  }
+  return YDORB_OK;
+}
+int launchSolve(Run& R_) {
+  SolveMem& c = *R_.c;
+  const Sys& Y = R_.sys;
+  const WorkPtrs& w = c.w;
+  hipStream_t s = c.stream;
+  if (Y.sky) {
+    const SkyPtrs& k = c.u.k;
+    if (Y.nPf)
+      hipLaunchKernelGGL(k_sky_solve, dim3(1), dim3(kSkyThreads), 0, s, Y.nPf, k.first, k.rowOff, k.colStart, k.colRows, k.colBlk, k.perm, w.bs(Y), w.S, w.skyW, w.xp, w.status);
+    return YDORB_OK;
+  }
+  for (int kb = 0; kb < Y.nb; kb++)
+    hipLaunchKernelGGL(k_chol_step, dim3((Y.nb - kb) * (Y.nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, s, w.S, w.diagL, w.diagInv, Y.n, kb, w.status, w.bs(Y), w.yv);
+  if (!launch_chol_solve(s, w.S, w.diagInv, Y.n, w.yv, w.bs(Y), w.xp)) return tooWideForSolve(Y.n);
   return YDORB_OK;
 }
 
@@ -370,12 +490,12 @@ int optimize(Run& R_) {
   hipStream_t s = c.stream;
   const Sys& Y = R_.sys;
   if (Y.Ea == 0) return YDORB_OK;
-  const int nL = Y.nL, nPf = Y.nPf, Ea = Y.Ea, n = Y.n, nb = Y.nb, nBlkE = Y.nBlkE, nBuckets = Y.nBuckets;
+  const int nL = Y.nL, nPf = Y.nPf, Ea = Y.Ea, n = Y.n, nBlkE = Y.nBlkE;
   const UpPtrs& u = c.u;
   const WorkPtrs& w = c.w;
   double* const* poses = c.st.poses;
   double* const* pts = c.st.pts;
-  double *dHpp = w.Hpp, *dbp = w.bp(Y), *dS = w.S, *dbs = w.bs(Y);
+  double *dHpp = w.Hpp, *dbp = w.bp(Y), *dS = w.S;
   EdgeSoA Ed{u.ePose, u.ePidx, u.ePt, u.eMeas, u.eInfo, u.eRobust, Ea};
   const double dM = O.delta_mono, dSt = O.delta_stereo;
   double* hscal = R_.hPin;
@@ -420,11 +540,7 @@ int optimize(Run& R_) {
       {
         PhaseTimer t(R_, PH_SCHUR);
         const double contrib = (!multi || O.rank == 0) ? 1.0 : 0.0;
-        hipLaunchKernelGGL(k_dinv, dim3((nL + 255) / 256), dim3(256), 0, s, w.Hll, w.bl, nL, lambda, w.Dinv, w.db, w.status);
-        hipLaunchKernelGGL(k_bd, dim3(nBlkE), dim3(256), 0, s, Ed, u.eLm, w.Hpl, w.Dinv, w.BD);
-        if (nPf)
-          hipLaunchKernelGGL(k_bs, dim3(nPf), dim3(256), 0, s, Ed, u.poseStart, u.poseEdges, u.eLm, w.Hpl, w.db, dbp, contrib, dbs);
-        hipLaunchKernelGGL(k_schur_pairs, dim3(nBuckets + 1), dim3(64 * kSchurWaves), 0, s, w.pairStart, w.pairB, nPf, nBuckets, w.BD, w.Hpl, dHpp, lambda, contrib, n, dS, dbs);
+        if ((rc = launchSchur(R_, lambda, contrib))) return rc;
         t.stop();
       }
       if (multi) {  // sum of the per-rank landmark contributions (+ rank 0's Hpp, lambda, bp)
@@ -432,9 +548,7 @@ int optimize(Run& R_) {
       }
       {
         PhaseTimer t(R_, PH_SOLVE);
-        for (int kb = 0; kb < nb; kb++)
-          hipLaunchKernelGGL(k_chol_step, dim3((nb - kb) * (nb - kb + 1) / 2 + (kb > 0)), dim3(256), 0, s, dS, w.diagL, w.diagInv, n, kb, w.status, dbs, w.yv);
-        if (!launch_chol_solve(s, dS, w.diagInv, n, w.yv, dbs, w.xp)) return tooWideForSolve(n);
+        if ((rc = launchSolve(R_))) return rc;
         hipLaunchKernelGGL(k_backsub, dim3((nL + 127) / 128), dim3(128), 0, s, Ed, u.ptStart, nL, w.Hpl, w.Dinv, w.bl, w.xp, w.xl);
         t.stop();
         HIPCHK(hipGetLastError());
@@ -844,6 +958,13 @@ void ydorb_ba_default_options(YdBaOptions* o) {
 }
 
 int ydorb_ba_solve(const YdBaProblem* P, const YdBaOptions* optIn, YdBaResult* res) {
+  const YdBaSolverOptions dense = {YDORB_BA_SOLVER_DENSE, YDORB_ESS_ORDER_SMALLER, 0};
+  return ydorb_ba_solve_with(P, optIn, &dense, res, nullptr);
+}
+
+int ydorb_ba_solve_with(const YdBaProblem* P, const YdBaOptions* optIn, const YdBaSolverOptions* sopt, YdBaResult* res, YdBaSolverInfo* info) {
+  const YdBaSolverOptions SO = sopt ? *sopt : YdBaSolverOptions{YDORB_BA_SOLVER_AUTO, YDORB_ESS_ORDER_SMALLER, 0};
+  if (info) memset(info, 0, sizeof(*info));
   YdBaOptions O;
   int rc = checkProblem(P, optIn, res, &O);
   if (rc) return rc;
@@ -859,6 +980,7 @@ int ydorb_ba_solve(const YdBaProblem* P, const YdBaOptions* optIn, YdBaResult* r
   Ctx& c = *ctx;
   Run R_{&c.mem, P, &O, res};
   R_.ev = c.ev; R_.hPin = c.hPin.as<double>();
+  R_.SO = &SO; R_.info = info;
   if ((rc = beginSolve(R_))) return rc;
   trace("solve: state uploaded");
   hipEvent_t t0 = c.ev[2 * PH_COUNT], t1 = c.ev[2 * PH_COUNT + 1];
@@ -1012,6 +1134,153 @@ int ydorb_ba_dense_solve(int32_t device, const double* A, int32_t n0, const doub
     fprintf(stderr, "us between step starts\n");
   }
 #endif
+  return YDORB_OK;
+}
+
+int ydorb_ba_plan(const YdBaProblem* P, const YdBaOptions* optIn, const YdBaSolverOptions* sopt, YdBaSolverInfo* info, int32_t* perm, int32_t* first) {
+  if (!P || !info) { set_error("null argument"); return YDORB_ERR_INVALID_ARG; }
+  YdBaResult res{};
+  YdBaOptions O;
+  int rc = checkProblem(P, optIn, &res, &O);
+  if (rc) return rc;
+  const YdBaSolverOptions SO = sopt ? *sopt : YdBaSolverOptions{YDORB_BA_SOLVER_AUTO, YDORB_ESS_ORDER_SMALLER, 0};
+  // the free poses as prepareStage numbers them: not fixed and, on one rank, seen by an edge
+  int nPf = 0;
+  {
+    std::vector<uint8_t> used(P->n_poses, O.world > 1 ? 1 : 0);
+    for (int e = 0; e < P->n_edges; e++) used[P->edge_pose[e]] = 1;
+    for (int k = 0; k < P->n_poses; k++) nPf += used[k] && !P->pose_fixed[k];
+  }
+  bapairs::PairList pairs;
+  sky::Plan plan;
+  bool sky = false;
+  rc = chooseSolver(&SO, O.world, nPf, [&] { return bapairs::buildPairsFromEdges(P->n_poses, P->n_points, P->n_edges, P->pose_fixed, P->edge_pose, P->edge_point, O.world > 1); },
+                    false, pairs, plan, sky, info);
+  if (rc) return rc;
+  for (int i = 0; i < nPf && (int)plan.perm.size() == nPf; i++) {
+    if (perm) perm[i] = plan.perm[i];
+    if (first) first[i] = plan.first[i];
+  }
+  return YDORB_OK;
+}
+
+int ydorb_ba_reduced_system_with(const YdBaProblem* P, const YdBaOptions* optIn, const YdBaSolverOptions* sopt, double lambda, double* S_out,
+                                 double* bs_out, double* x_out, int32_t* solved) {
+  if (!S_out || !bs_out || !x_out || !solved) { set_error("null argument"); return YDORB_ERR_INVALID_ARG; }
+  const YdBaSolverOptions SO = sopt ? *sopt : YdBaSolverOptions{YDORB_BA_SOLVER_AUTO, YDORB_ESS_ORDER_SMALLER, 0};
+  YdBaResult res{};
+  YdBaOptions O;
+  int rc = checkProblem(P, optIn, &res, &O);
+  if (rc) return rc;
+  if (P->n_edges == 0 || O.world > 1) { set_error("reduced system: needs edges and a single rank"); return YDORB_ERR_INVALID_ARG; }
+  if ((rc = require_device(O.device))) return rc;
+  std::unique_lock<std::mutex> lock;
+  Ctx* ctx = acquireCtx(O.device, lock);
+  if (!ctx) return YDORB_ERR_HIP;
+  Ctx& c = *ctx;
+  Run R_{&c.mem, P, &O, &res};
+  R_.ev = c.ev; R_.hPin = c.hPin.as<double>();
+  R_.SO = &SO;
+  if ((rc = beginSolve(R_))) return rc;
+  if ((rc = prepareStage(R_, false))) return rc;
+  const Sys& Y = R_.sys;
+  const int F = Y.nPf, n6 = 6 * F;
+  if (Y.Ea == 0 || F == 0) { set_error("reduced system: no free pose"); return YDORB_ERR_INVALID_ARG; }
+  if (n6 > 4096) { set_error("reduced system: %d rows, at most 4096 are expanded", n6); return YDORB_ERR_UNSUPPORTED; }
+  hipStream_t s = c.mem.stream;
+  const UpPtrs& u = c.mem.u;
+  const WorkPtrs& w = c.mem.w;
+  EdgeSoA Ed{u.ePose, u.ePidx, u.ePt, u.eMeas, u.eInfo, u.eRobust, Y.Ea};
+  const double *poses = c.mem.st.poses[R_.cur], *pts = c.mem.st.pts[R_.cur];
+  hipLaunchKernelGGL(k_errors, dim3(Y.nBlkE), dim3(256), 0, s, Ed, poses, pts, R_.cam, O.delta_mono, O.delta_stereo, w.err, w.partial);
+  hipLaunchKernelGGL(k_build_points, dim3((Y.nL + 127) / 128), dim3(128), 0, s, Ed, u.ptStart, Y.nL, poses, pts, R_.cam, O.delta_mono, O.delta_stereo, w.err, w.Hll, w.bl, w.Hpl);
+  hipLaunchKernelGGL(k_build_poses, dim3(F), dim3(256), 0, s, Ed, u.poseStart, u.poseEdges, poses, pts, R_.cam, O.delta_mono, O.delta_stereo, w.err, w.Hpp, w.bp(Y));
+  if ((rc = launchSchur(R_, lambda, 1.0))) return rc;
+  const size_t nS = Y.sky ? Y.envDoubles() : (size_t)Y.n * Y.n;
+  std::vector<double> hS(nS), hx(Y.n);
+  int hst[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(hS.data(), w.S, sizeof(double) * nS, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(bs_out, w.bs(Y), sizeof(double) * n6, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));   // the factorisation overwrites S
+  if ((rc = launchSolve(R_))) return rc;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(hx.data(), w.xp, sizeof(double) * Y.n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(hst, w.status, sizeof(hst), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *solved = hst[0] == 0;
+  for (int i = 0; i < n6; i++) x_out[i] = hx[i];
+  // the lower triangle of either storage, mirrored
+  auto put = [&](int r, int cc, double v) { S_out[(size_t)r * n6 + cc] = v; S_out[(size_t)cc * n6 + r] = v; };
+  memset(S_out, 0, sizeof(double) * n6 * n6);
+  if (!Y.sky) {
+    for (int r = 0; r < n6; r++)
+      for (int cc = 0; cc <= r; cc++) put(r, cc, hS[(size_t)r * Y.n + cc]);
+  } else {
+    const sky::Plan& K = Y.plan;
+    for (int i = 0; i < F; i++)
+      for (int j = K.first[i]; j <= i; j++) {
+        const double* B = &hS[36 * (size_t)(K.rowOff[i] + j - K.first[i])];
+        for (int r = 0; r < 6; r++)
+          for (int cc = 0; cc < (j == i ? r + 1 : 6); cc++) put(6 * K.perm[i] + r, 6 * K.perm[j] + cc, B[6 * r + cc]);
+      }
+  }
+  return YDORB_OK;
+}
+
+int ydorb_ba_skyline_solve(int32_t device, const double* A, int32_t n, const double* b, int32_t ordering, double* x, int32_t* ok) {
+  if (!A || !b || !x || !ok || n < 6 || n % 6 || n > 4096 || device < 0 || device >= 16 || ordering < YDORB_ESS_ORDER_SMALLER || ordering > YDORB_ESS_ORDER_RCM) {
+    set_error("invalid argument");
+    return YDORB_ERR_INVALID_ARG;
+  }
+  int rc = require_device(device);
+  if (rc) return rc;
+  const int F = n / 6;
+  // every non-zero block off the diagonal as a landmark that its two poses share
+  std::vector<int> start(1, 0), pidx;
+  for (int i = 0; i < F; i++)
+    for (int j = 0; j < i; j++) {
+      bool any = false;
+      for (int r = 0; r < 6 && !any; r++)
+        for (int cc = 0; cc < 6; cc++)
+          if (A[(size_t)(6 * i + r) * n + 6 * j + cc] != 0.0 || A[(size_t)(6 * j + cc) * n + 6 * i + r] != 0.0) { any = true; break; }
+      if (any) { pidx.push_back(j); pidx.push_back(i); start.push_back((int)pidx.size()); }
+    }
+  const bapairs::PairList pairs = bapairs::buildPairs(F, (int)start.size() - 1, start.data(), pidx.data());
+  sky::Plan K;
+  std::string err;
+  if (!bapairs::planEnvelope(pairs, ordering, 0, true, K, err)) { set_error("%s", err.c_str()); return YDORB_ERR_UNSUPPORTED; }
+  std::vector<double> env(36 * (size_t)K.envBlocks, 0.0);
+  for (int i = 0; i < F; i++)
+    for (int j = K.first[i]; j <= i; j++) {
+      double* B = &env[36 * (size_t)(K.rowOff[i] + j - K.first[i])];
+      for (int r = 0; r < 6; r++)
+        for (int cc = 0; cc < 6; cc++) B[6 * r + cc] = A[(size_t)(6 * K.perm[i] + r) * n + 6 * K.perm[j] + cc];
+    }
+  Layout L;
+  const size_t nCol = K.colRows.size();
+  const size_t oA = L.add(sizeof(double) * env.size()), ob = L.add(sizeof(double) * n), ow = L.add(sizeof(double) * 2 * n), ox = L.add(sizeof(double) * n),
+               ost = L.add(sizeof(int) * 2), oFirst = L.add(sizeof(int) * F), oPerm = L.add(sizeof(int) * F), oRow = L.add(sizeof(long long) * (F + 1)),
+               oCs = L.add(sizeof(long long) * (F + 1)), oCr = L.add(sizeof(int) * nCol), oCb = L.add(sizeof(long long) * nCol);
+  ScopedMem m;   // exact size; freed on every return
+  if ((rc = m.alloc(L.bytes))) return rc;
+  HIPCHK(hipMemcpy(m.at<double>(oA), env.data(), sizeof(double) * env.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(m.at<double>(ob), b, sizeof(double) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(m.at<int>(ost), 0, sizeof(int) * 2));
+  HIPCHK(hipMemcpy(m.at<int>(oFirst), K.first.data(), sizeof(int) * F, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(m.at<int>(oPerm), K.perm.data(), sizeof(int) * F, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(m.at<long long>(oRow), K.rowOff.data(), sizeof(long long) * (F + 1), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(m.at<long long>(oCs), K.colStart.data(), sizeof(long long) * (F + 1), hipMemcpyHostToDevice));
+  if (nCol) {
+    HIPCHK(hipMemcpy(m.at<int>(oCr), K.colRows.data(), sizeof(int) * nCol, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.at<long long>(oCb), K.colBlk.data(), sizeof(long long) * nCol, hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(k_sky_solve, dim3(1), dim3(kSkyThreads), 0, nullptr, F, m.at<int>(oFirst), m.at<long long>(oRow), m.at<long long>(oCs), m.at<int>(oCr),
+                     m.at<long long>(oCb), m.at<int>(oPerm), m.at<double>(ob), m.at<double>(oA), m.at<double>(ow), m.at<double>(ox), m.at<int>(ost));
+  HIPCHK(hipGetLastError());
+  int hst[2];
+  HIPCHK(hipMemcpy(x, m.at<double>(ox), sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hst, m.at<int>(ost), sizeof(hst), hipMemcpyDeviceToHost));
+  *ok = hst[0] == 0;
   return YDORB_OK;
 }
 

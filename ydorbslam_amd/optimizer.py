@@ -5,11 +5,35 @@ The graph is passed flat (what optimizer.cpp:175-283 hands to g2o); the covisibi
 import ctypes as C
 import numpy as np
 
-from ._lib import BA_ALLREDUCE_FN, YdBaOptions, YdBaProblem, YdBaResult, YdPoseBatch, check, lib
+from ._lib import (BA_ALLREDUCE_FN, YdBaOptions, YdBaProblem, YdBaResult, YdBaSolverInfo, YdBaSolverOptions, YdPoseBatch, check, lib)
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _solver_options(solver, ordering, max_factor_bytes):
+    """solver: a BA_SOLVER_* value or a YdBaSolverOptions."""
+    if isinstance(solver, YdBaSolverOptions):
+        return solver
+    return YdBaSolverOptions(int(solver), int(ordering), int(max_factor_bytes))
+
+
+def _info_dict(info):
+    return {name: int(getattr(info, name)) for name, _ in YdBaSolverInfo._fields_ if name != "reserved"}
+
+
+def _flat_problem(prob, stop=None):
+    """The YdBaProblem of a problem dict and the arrays it points into (poses and points are copies: the solve writes them)."""
+    poses = np.ascontiguousarray(prob["poses"], np.float64).copy()
+    points = np.ascontiguousarray(prob["points"], np.float64).copy()
+    keep = [poses, points, np.ascontiguousarray(prob["fixed"], np.uint8), np.ascontiguousarray(prob["edge_pose"], np.int32),
+            np.ascontiguousarray(prob["edge_point"], np.int32), np.ascontiguousarray(prob["meas"], np.float64),
+            np.ascontiguousarray(prob["info"], np.float64)]
+    cam = [float(v) for v in prob["camera"]]
+    P = YdBaProblem(len(poses), len(points), len(keep[3]), _p(poses), _p(keep[2]), _p(points), _p(keep[3]), _p(keep[4]), _p(keep[5]),
+                    _p(keep[6]), *cam, None if stop is None else _p(stop))
+    return P, keep
 
 
 class Optimizer:
@@ -35,8 +59,11 @@ class Optimizer:
         return o
 
     @staticmethod
-    def local_bundle_adjust(prob, options=None, stop=None, allreduce=None, comm_tensor_ptr=None, comm_doubles=0, rank=0, world=1):
+    def local_bundle_adjust(prob, options=None, stop=None, allreduce=None, comm_tensor_ptr=None, comm_doubles=0, rank=0, world=1, solver=None,
+                            ordering=0, max_factor_bytes=0):
         """prob: dict(poses[K,7], fixed[K], points[P,3], edge_pose, edge_point, meas[E,3], info[E], camera[5]).
+        solver: None = ydorb_ba_solve (the dense reduced camera solve); a BA_SOLVER_* value (with `ordering`, an ESS_ORDER_* value, and
+        `max_factor_bytes`) or a YdBaSolverOptions = ydorb_ba_solve_with, and the result carries `info`, the YdBaSolverInfo as a dict.
         Returns dict(poses, points, outlier, log (chi2, lambda, trials, stage), trials, iterations, ms)."""
         L = lib()
         o = options if options is not None else Optimizer.default_options()
@@ -61,14 +88,62 @@ class Optimizer:
             o.rank, o.world = rank, world
         res = YdBaResult()
         res.edge_outlier = outlier.ctypes.data_as(C.c_void_p).value
-        check(L.ydorb_ba_solve(C.byref(P), C.byref(o), C.byref(res)))
+        info = None
+        if solver is None:
+            check(L.ydorb_ba_solve(C.byref(P), C.byref(o), C.byref(res)))
+        else:
+            so, info = _solver_options(solver, ordering, max_factor_bytes), YdBaSolverInfo()
+            check(L.ydorb_ba_solve_with(C.byref(P), C.byref(o), C.byref(so), C.byref(res), C.byref(info)))
         n = res.n_log
         log = np.stack([np.array(res.log_chi2[:n]), np.array(res.log_lambda[:n]), np.array(res.log_trials[:n], np.float64),
                         np.array(res.log_stage[:n], np.float64)], axis=1) if n else np.zeros((0, 4))
         return dict(poses=poses, points=points, outlier=outlier[:E], log=log, trials=res.n_trials, iterations=res.n_iterations,
-                    stopped=bool(res.stopped),
+                    stopped=bool(res.stopped), info=None if info is None else _info_dict(info),
                     ms=dict(total=res.ms_total, errors=res.ms_errors, build=res.ms_build, schur=res.ms_schur, solve=res.ms_solve,
                             update=res.ms_update))
+
+    @staticmethod
+    def plan(prob, options=None, solver=0, ordering=0, max_factor_bytes=0, world=1):
+        """ydorb_ba_plan: the solver a solve of `prob` would use and its envelope, on the host alone (no device is touched).
+        Returns the YdBaSolverInfo as a dict with perm (free pose at each position of the order) and first (first block column per row)."""
+        o = YdBaOptions.from_buffer_copy(options if options is not None else Optimizer.default_options())   # the caller's stay as they are
+        o.world = world
+        P, keep = _flat_problem(prob)
+        so, info = _solver_options(solver, ordering, max_factor_bytes), YdBaSolverInfo()
+        n_free_max = len(keep[0])
+        perm = np.full(max(n_free_max, 1), -1, np.int32)
+        first = np.full(max(n_free_max, 1), -1, np.int32)
+        check(lib().ydorb_ba_plan(C.byref(P), C.byref(o), C.byref(so), C.byref(info), _p(perm), _p(first)))
+        out = _info_dict(info)
+        out["perm"], out["first"] = perm[:info.n_free].copy(), first[:info.n_free].copy()
+        return out
+
+    @staticmethod
+    def reduced_system(prob, lam, options=None, solver=0, ordering=0, max_factor_bytes=0):
+        """ydorb_ba_reduced_system_with (test / debug): one linearisation of `prob` and one Schur complement with lambda = lam.
+        Returns dict(S [6F,6F] full symmetric in free-pose order, bs [6F], x [6F], solved)."""
+        o = options if options is not None else Optimizer.default_options()
+        P, keep = _flat_problem(prob)
+        fixed, ep = keep[2], keep[3]
+        used = np.zeros(len(fixed), bool)
+        used[ep] = True
+        n = 6 * int(np.count_nonzero(used & (fixed == 0)))
+        S, bs, x = np.zeros((max(n, 1), max(n, 1))), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        solved = C.c_int32(0)
+        so = _solver_options(solver, ordering, max_factor_bytes)
+        check(lib().ydorb_ba_reduced_system_with(C.byref(P), C.byref(o), C.byref(so), float(lam), _p(S), _p(bs), _p(x), C.byref(solved)))
+        return dict(S=S[:n, :n], bs=bs[:n], x=x[:n], solved=bool(solved.value))
+
+    @staticmethod
+    def skyline_solve(A, b, ordering=1, device=0):
+        """ydorb_ba_skyline_solve (test / debug): A x = b with the block-skyline factorisation, the block pattern taken from A's non-zero
+        6x6 blocks.  Returns (x, ok)."""
+        A = np.ascontiguousarray(A, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        x = np.zeros(len(b), np.float64)
+        ok = C.c_int32(0)
+        check(lib().ydorb_ba_skyline_solve(device, _p(A), len(b), _p(b), int(ordering), _p(x), C.byref(ok)))
+        return x, bool(ok.value)
 
     @staticmethod
     def release(device=0):

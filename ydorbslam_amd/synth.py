@@ -300,3 +300,70 @@ def synth_stream(w=640, h=480, n_frames=64, seed=0, segment=64, stereo=False, di
     plan = stream_plan(w, h, n_frames, seed, segment, pred_sigma)
     frames, right = stream_render(plan, range(n_frames), stereo, disparities, margin)
     return dict(frames=frames, right=right, affine=plan["affine"], predicted=plan["predicted"], cut=plan["cut"])
+
+
+def _quat_to_rot(q):
+    """Rotation matrices [K, 3, 3] of quaternions [K, 4] in (x, y, z, w) order, normalised first."""
+    q = q / np.linalg.norm(q, axis=-1, keepdims=True)
+    x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], axis=-1),
+                     np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], axis=-1),
+                     np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], axis=-1)], axis=1)
+
+
+TRAJECTORY_CLOSURE = 3
+
+
+def trajectory_ba_problem(K, span=3, per_kf=4, loop=False, seed=1, noise_px=0.5, pose_sigma=0.005, point_sigma=0.03, fixed=(0,)):
+    """A map as a trajectory leaves it, in synth_ba_problem's layout.  K keyframes 0.3 m apart, all looking along +z; per_kf points start
+    at every keyframe k and are seen, in stereo, by the keyframes k .. k + span - 1 that exist.  loop=False: the keyframes move along +x
+    (a chain).  loop=True: the path turns half way and comes back 0.3 m beside itself, and the last TRAJECTORY_CLOSURE keyframes, which are back at
+    the start, also see the points that started at keyframes 0 and 1: one loop closure.  Pixel noise noise_px, keyframes in `fixed` keep
+    their true pose, the others start pose_sigma (rad, m) off and the points point_sigma off.  Everything from default_rng(seed),
+    vectorised (K = 20 000 takes well under a second)."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = camera = np.array([500.0, 500.0, 320.0, 240.0, 40.0])
+    k = np.arange(K)
+    back = loop & (k > K // 2)
+    centre = np.stack([0.3 * np.where(back, K - k, k), np.where(back, 0.3, 0.0), np.zeros(K)], axis=1)
+    q = np.tile(np.array([0.0, 0.0, 0.0, 1.0]), (K, 1))
+    Rm = _quat_to_rot(q)
+    t = -centre
+    truth_poses = np.concatenate([t, q], axis=1)
+    P = K * per_kf
+    k0 = np.repeat(k, per_kf)
+    mid = centre[np.minimum(k0 + (span - 1) // 2, K - 1)]
+    pts = np.stack([mid[:, 0] + rng.uniform(-0.5, 0.5, P), mid[:, 1] + rng.uniform(-1.0, 1.0, P), rng.uniform(4.0, 8.0, P)], axis=1)
+    ep = (k0[:, None] + np.arange(span)[None, :])
+    eq = np.repeat(np.arange(P), span).reshape(P, span)
+    keep = ep < K
+    ep, eq = ep[keep], eq[keep]
+    if loop:
+        assert K >= 2 * TRAJECTORY_CLOSURE + span + 2
+        first_pts = np.arange(2 * per_kf)
+        ep = np.concatenate([ep, np.repeat(np.arange(K - TRAJECTORY_CLOSURE, K), len(first_pts))])
+        eq = np.concatenate([eq, np.tile(first_pts, TRAJECTORY_CLOSURE)])
+    Xc = np.einsum("eij,ej->ei", Rm[ep], pts[eq]) + t[ep]
+    E = len(ep)
+    u = fx * Xc[:, 0] / Xc[:, 2] + cx + rng.normal(0, noise_px, E)
+    v = fy * Xc[:, 1] / Xc[:, 2] + cy + rng.normal(0, noise_px, E)
+    ur = u - bf / Xc[:, 2]
+    assert (Xc[:, 2] > 1.0).all() and (ur > 0).all()
+    fixed_mask = np.zeros(K, np.uint8)
+    fixed_mask[list(fixed)] = 1
+    poses = truth_poses.copy()
+    free = fixed_mask == 0
+    d = rng.normal(0, pose_sigma, (K, 6))
+    dq = np.concatenate([0.5 * d[:, :3], np.ones((K, 1))], axis=1)      # a small rotation, normalised by the solver's upload
+    dR = _quat_to_rot(dq)
+    qn = np.stack([dq[:, 3] * q[:, 0] + dq[:, 0] * q[:, 3] + dq[:, 1] * q[:, 2] - dq[:, 2] * q[:, 1],
+                   dq[:, 3] * q[:, 1] + dq[:, 1] * q[:, 3] + dq[:, 2] * q[:, 0] - dq[:, 0] * q[:, 2],
+                   dq[:, 3] * q[:, 2] + dq[:, 2] * q[:, 3] + dq[:, 0] * q[:, 1] - dq[:, 1] * q[:, 0],
+                   dq[:, 3] * q[:, 3] - dq[:, 0] * q[:, 0] - dq[:, 1] * q[:, 1] - dq[:, 2] * q[:, 2]], axis=1)
+    qn /= np.linalg.norm(qn, axis=1, keepdims=True)
+    poses[free, :3] = (np.einsum("kij,kj->ki", dR, t) + d[:, 3:])[free]
+    poses[free, 3:] = qn[free]
+    points = pts + rng.normal(0, point_sigma, (P, 3))
+    order = rng.permutation(E)
+    return dict(poses=poses, fixed=fixed_mask, points=points, edge_pose=ep[order].astype(np.int32), edge_point=eq[order].astype(np.int32),
+                meas=np.stack([u, v, ur], axis=1)[order], info=np.ones(E), camera=camera, truth_poses=truth_poses, truth_points=pts)
