@@ -934,6 +934,66 @@ int ydorb_essential_graph_optimize_with(const YdEssentialGraph* g, const YdEssen
 int ydorb_essential_graph_trial_step_with(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt, double lambda, double* x,
                                           int32_t* solved, double* H_out, double* b_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Map maintenance: the three passes over the observation table (map point -> the keyframes that observe it) that run between
+ * processNewKeyFrame and the next keyframe.  They restate ORB-SLAM2's MapPoint::UpdateNormalAndDepth, the counting loop of
+ * KeyFrame::UpdateConnections and the counting of LocalMapping::KeyFrameCulling (YDORBSLAM: updateNormalAndDepth, updateConnections,
+ * keyFrameCulling).  The reference source is absent from this repository: the semantics are restated from ORB-SLAM2, and DESIGN.md
+ * section 2 ("Map maintenance") fixes the fp32 operation order.  Assumptions for a maintainer who holds the reference to check:
+ *   - normal / double is OpenCV's scale by 1./s, applied to CV_32F data with a float factor;
+ *   - the observation container iterates in an address-dependent order, so this ABI takes the order and the adapter passes the
+ *     container's own;
+ *   - the scale factors are one pyramid for all keyframes;
+ *   - thObs = 3, a stereo observation weighs 2 in observations(), the covisibility threshold is 15, the culling verdict is the
+ *     double compare nRedundant > 0.9 * nMPs, and culling skips the first keyframe of the map (the caller omits it).
+ * All three read one flattened table, local to the call; keyframe slots 0 .. n_keyframes-1 are chosen by the caller.  Integer
+ * results are exact and the fp32 results are bit-identical to a CPU restatement compiled with -ffp-contract=off.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG before any device work, the message naming the first offender: null arrays, a
+ * *_start that does not begin at 0 or decreases, a slot or point index out of range, a level >= n_levels where scale_factors is
+ * read, device outside 0..15.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdObservationTable {
+  int32_t n_points, n_keyframes;
+  const int32_t* obs_start;   /* [n_points+1], obs_start[0] = 0, non-decreasing */
+  const int32_t* obs_kf;      /* [N] observing keyframe slot, in the iteration order of the reference's observation map */
+  const uint8_t* obs_level;   /* [N] bits 0-6: octave of the observing keypoint; bit 7: stereo observation (right x >= 0) */
+  const uint8_t* bad;         /* [n_points] isBad() */
+} YdObservationTable;
+/* status byte of a map point */
+#define YDORB_MAP_UPDATED 0
+#define YDORB_MAP_BAD 1              /* isBad(): the reference returns before it reads anything */
+#define YDORB_MAP_NO_OBSERVATIONS 2  /* the observation map is empty: the reference returns */
+/* MapPoint::updateNormalAndDepth for every point of the table.  pos [n_points][3]; centre [n_keyframes][3] = the camera origins;
+ * ref_kf / ref_level [n_points] = the reference keyframe's slot and the octave of its observing keypoint (read for updated points
+ * only); scale_factors [n_levels], n_levels in 1..8.  normal [n_points][3], min_distance / max_distance [n_points] are the raw
+ * members (not the 0.8x / 1.2x getters), all zero for a point that is not updated.  A point at an observer's centre gives NaN
+ * components, as in the reference. */
+int ydorb_map_update_normal_depth(const YdObservationTable* table, const float* pos, const float* centre, const int32_t* ref_kf,
+                                  const uint8_t* ref_level, const float* scale_factors, int32_t n_levels, int32_t device, float* normal,
+                                  float* min_distance, float* max_distance, uint8_t* status);
+/* The counter map of KeyFrame::updateConnections for n_queries keyframes.  query_kf [n_queries] slots; list_start [n_queries+1] /
+ * point_idx = each keyframe's non-null map-point entries (a point listed twice counts twice); out_start [n_queries+1] = where each
+ * query's results go and how many fit (min(n_keyframes - 1, sum of the listed points' spans) always fits).  Bad points and the
+ * query's own slot are skipped.  Per query: conn_kf / conn_weight [out_start[q] .. + counts[q]) = the keyframes with a non-zero
+ * count, ascending by slot; counts [n_queries]; status [n_queries]: 0 = ok, 1 = capacity too small (nothing is written for that
+ * query, counts holds the needed size).  The threshold of 15, the keep-the-best rule and the sort stay with the caller. */
+int ydorb_map_covisibility(const YdObservationTable* table, const int32_t* query_kf, int32_t n_queries, const int32_t* list_start,
+                           const int32_t* point_idx, const int32_t* out_start, int32_t device, int32_t* conn_kf, int32_t* conn_weight,
+                           int32_t* counts, uint8_t* status);
+/* The counting of LocalMapping::keyFrameCulling for n_candidates keyframes.  cand_kf [n_candidates] slots; list_start
+ * [n_candidates+1] / point_idx / own_level = each candidate's entries whose map point is non-null and whose depth passes
+ * !(depth > thDepth || depth < 0) (the caller's float test), with the octave of the candidate's own keypoint; removed
+ * [n_keyframes] or NULL = keyframes culled since the table was flattened; th_obs = 3.  With w(p) = the sum over p's observers not
+ * in `removed` of (stereo ? 2 : 1), an entry is skipped when bad[p], or when p has an observer in `removed` and w(p) <= 2 (what
+ * eraseObservation does to such a point); otherwise it counts into n_counted, and into n_redundant when w(p) > th_obs and at least
+ * th_obs observers other than the candidate, not removed, have level <= own_level + 1.
+ * cull[k] = (double)n_redundant[k] > 0.9 * (double)n_counted[k]. */
+int ydorb_map_keyframe_redundancy(const YdObservationTable* table, const int32_t* cand_kf, int32_t n_candidates,
+                                  const int32_t* list_start, const int32_t* point_idx, const uint8_t* own_level, const uint8_t* removed,
+                                  int32_t th_obs, int32_t device, int32_t* n_counted, int32_t* n_redundant, uint8_t* cull);
+/* The three entries above keep device scratch per device between calls; this frees it (waiting for calls in flight). */
+int ydorb_map_release(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <opencv2/core.hpp>
 
 #include "c_api.h"
+#include "mapPoint.hpp"
 #include "orbMatcher.hpp"
 
 namespace ydorb {
@@ -143,6 +144,79 @@ int createNewMapPointsImpl(ydorb_matcher_t* m, KeyFramePtr current, MapPtr map, 
     }
   }
   return created;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Drop-in body of LocalMapping::keyFrameCulling (ORB-SLAM2 LocalMapping::KeyFrameCulling):
+//   void LocalMapping::keyFrameCulling()
+//   { ydorb::adapter::keyFrameCullingImpl<std::shared_ptr<KeyFrame>, std::shared_ptr<MapPoint>>(m_sptr_currentKeyFrame, thDepth); }
+// One flatten of the covisible keyframes' map points and one ydorb_map_keyframe_redundancy call judge every candidate; the walk then
+// follows the reference's order.  The first candidate with `cull` gets setBadFlag(); when that made it isBad(), its observations are
+// gone from every map point, so its byte in `removed` is set and the candidates after it are asked for again over the same table (no
+// second flatten).  A keyframe that setNotErase() protects is only marked by setBadFlag(): it stays unmasked and the walk goes on.
+// Additional assumed spellings: KeyFrame getVectorCovisibleKeyFrames(), m_int_keyFrameID (0 = the first keyframe of the map, never
+// culled), m_v_depth, setBadFlag(), isBad(); the depth test !(depth > thDepth || depth < 0) is always made (stereo / RGB-D).
+template <class KeyFramePtr, class MapPointPtr>
+struct CullingFlat {
+  ObservationFlat<KeyFramePtr, MapPointPtr> obs;
+  std::vector<KeyFramePtr> candidates;
+  std::vector<int32_t> candKf, listStart{0}, pointIdx;
+  std::vector<uint8_t> ownLevel;
+};
+
+template <class KeyFramePtr, class MapPointPtr>
+inline void flattenCulling(const KeyFramePtr& current, float thDepth, CullingFlat<KeyFramePtr, MapPointPtr>& F) {
+  for (const KeyFramePtr& kf : current->getVectorCovisibleKeyFrames()) {
+    if (kf->m_int_keyFrameID == 0) continue;
+    F.candidates.push_back(kf);
+    F.candKf.push_back(F.obs.slot(kf));
+    const std::vector<MapPointPtr> mps = kf->getMapPointMatches();
+    for (size_t i = 0; i < mps.size(); i++) {
+      if (!mps[i]) continue;
+      if (kf->m_v_depth[i] > thDepth || kf->m_v_depth[i] < 0) continue;   // the caller's float test (a bad point is skipped either way)
+      F.pointIdx.push_back(F.obs.point(mps[i]));
+      F.ownLevel.push_back((uint8_t)kf->m_v_keyPoints[i].octave);
+    }
+    if (F.pointIdx.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX culling entries");
+    F.listStart.push_back((int32_t)F.pointIdx.size());
+  }
+}
+
+// Returns the keyframes setBadFlag() was called on, in order.
+template <class KeyFramePtr, class MapPointPtr>
+inline std::vector<KeyFramePtr> keyFrameCullingImpl(const KeyFramePtr& current, float thDepth, int device = 0) {
+  CullingFlat<KeyFramePtr, MapPointPtr> F;
+  flattenCulling(current, thDepth, F);
+  std::vector<KeyFramePtr> flagged;
+  const int32_t K = (int32_t)F.candidates.size();
+  if (K == 0) return flagged;
+  const YdObservationTable T = F.obs.table();
+  std::vector<uint8_t> removed((size_t)T.n_keyframes, 0), cull(K);
+  std::vector<int32_t> nCounted(K), nRedundant(K), start;
+  bool masked = false;
+  int32_t at = 0;
+  while (at < K) {
+    const int32_t n = K - at, base = F.listStart[at];
+    start.assign((size_t)n + 1, 0);
+    for (int32_t k = 0; k <= n; k++) start[k] = F.listStart[at + k] - base;
+    mapCheck(ydorb_map_keyframe_redundancy(&T, F.candKf.data() + at, n, start.data(), F.pointIdx.data() + base, F.ownLevel.data() + base,
+                                           masked ? removed.data() : nullptr, 3, device, nCounted.data(), nRedundant.data(), cull.data()));
+    int32_t k = 0;
+    for (; k < n; k++) {
+      if (!cull[k]) continue;
+      const KeyFramePtr& kf = F.candidates[at + k];
+      kf->setBadFlag();
+      flagged.push_back(kf);
+      if (kf->isBad()) {   // erased: the verdicts after it are stale
+        removed[F.candKf[at + k]] = 1;
+        masked = true;
+        k++;
+        break;
+      }
+    }
+    at += k;
+  }
+  return flagged;
 }
 
 }  // namespace adapter

@@ -119,6 +119,10 @@ SYMBOLS = {
     "ydorb_essential_graph_plan": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "ydorb_essential_graph_optimize_with": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "ydorb_essential_graph_trial_step_with": (C.c_int, [_VP, _VP, C.c_double, _VP, C.POINTER(_I), _VP, _VP]),
+    "ydorb_map_update_normal_depth": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_map_covisibility": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_map_keyframe_redundancy": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
+    "ydorb_map_release": (C.c_int, [_I]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -197,6 +201,10 @@ class YdMapPointTable(C.Structure):
 class YdFrustumBatch(C.Structure):
     _fields_ = [("device", _I), ("n_views", _I), ("views", _VP), ("table", YdMapPointTable), ("list_start", _VP), ("point_idx", _VP),
                 ("skip", _VP)]
+
+
+class YdObservationTable(C.Structure):
+    _fields_ = [("n_points", _I), ("n_keyframes", _I), ("obs_start", _VP), ("obs_kf", _VP), ("obs_level", _VP), ("bad", _VP)]
 
 
 class YdCamera(C.Structure):
