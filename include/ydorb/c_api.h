@@ -994,6 +994,67 @@ int ydorb_map_keyframe_redundancy(const YdObservationTable* table, const int32_t
 /* The three entries above keep device scratch per device between calls; this frees it (waiting for calls in flight). */
 int ydorb_map_release(int32_t device);
 
+/* ------------------------------------------------------------------------------------------
+ * Resident map table: the observation table of the three passes above, kept in HBM between calls, changed
+ * by deltas and queried with no table upload.  The caller chooses the slots: a map point's slot and a keyframe's slot are its for as
+ * long as the caller says (the adapter include/ydorb/mapMirror.hpp keeps pointer -> slot maps with free lists).  The device keeps
+ * per point slot a fixed record (where its span lies in the pool, bad, reference keyframe slot and level, position), per keyframe
+ * slot the camera centre, and one pool of observations.  A replaced span is appended at the pool's tail and the old one becomes
+ * garbage; when an append does not fit, the live spans are repacked in ascending slot order into a fresh arena of the same capacity
+ * when live + incoming <= capacity / 2, of 2 x (live + incoming) otherwise (at most INT32_MAX entries).
+ * The set_* entries do no device work: they validate and stage.  A slot named several times between two queries is applied once,
+ * with its last value.  The next query (or export) uploads one delta, repacks if needed, applies it, and then runs the pass; with
+ * nothing staged no table byte moves.  One mutex per handle: LocalMapping may stage while LoopClosing queries.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG with the first offender named, before any device work: null arrays, starts
+ * that do not begin at 0 or decrease, a negative slot, obs_kf or ref_kf outside 0..n_keyframes-1 (set a new keyframe's centre before
+ * points name it), a query slot outside 0..n_points-1, ref_level >= n_levels for a point the query updates, a pool past INT32_MAX
+ * entries.  A set_points / set_positions call that fails validation stages nothing.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ydorb_mapdb ydorb_mapdb_t;
+typedef struct YdMapDbStats {
+  int32_t n_points, n_keyframes;        /* 1 + the highest slot named so far (staged changes included) */
+  int64_t n_observations;               /* live observations (staged changes included): what ydorb_mapdb_export returns */
+  int64_t pool_used, pool_capacity;     /* pool entries used (live + garbage) and allocated, as of the last sync */
+  int32_t repacks_kept, repacks_grown;  /* repacks into an arena of the same capacity / of a larger one */
+  int32_t point_table_growths, keyframe_table_growths;
+  int32_t point_capacity, keyframe_capacity;   /* as of the last sync */
+  int64_t last_sync_bytes;              /* what the most recent query (or export) uploaded for the table: 0 when nothing was staged */
+  int64_t last_sync_records;            /* ... and its point + position + centre records; the query's own arrays are in neither */
+} YdMapDbStats;
+/* The capacities are initial (>= 0): every table grows on demand. */
+int ydorb_mapdb_create(int32_t device, int32_t point_capacity, int32_t keyframe_capacity, int64_t observation_capacity,
+                       ydorb_mapdb_t** out);
+void ydorb_mapdb_destroy(ydorb_mapdb_t* db);
+/* Map::clear: no points, no keyframes, an empty pool.  Capacities and the repack / growth counters stay. */
+int ydorb_mapdb_clear(ydorb_mapdb_t* db);
+/* Camera centres of n keyframe slots, centre [n][3].  n_keyframes becomes 1 + the highest slot ever named. */
+int ydorb_mapdb_set_centres(ydorb_mapdb_t* db, const int32_t* kf_slots, int32_t n, const float* centre);
+/* Replaces the whole record of each named point: obs_start [n+1] / obs_kf / obs_level = its observers in the container's iteration
+ * order (level byte as in YdObservationTable), bad, ref_kf, ref_level [n], pos [n][3].  An empty span with bad = 1 is an erased
+ * point.  n_points becomes 1 + the highest slot named; a slot below n_points that was never set reads as bad with no observations. */
+int ydorb_mapdb_set_points(ydorb_mapdb_t* db, const int32_t* slots, int32_t n, const int32_t* obs_start, const int32_t* obs_kf,
+                           const uint8_t* obs_level, const uint8_t* bad, const int32_t* ref_kf, const uint8_t* ref_level,
+                           const float* pos);
+/* Positions alone, pos [n][3] (a BA write-back that changes no topology).  The slots must be below n_points. */
+int ydorb_mapdb_set_positions(ydorb_mapdb_t* db, const int32_t* slots, int32_t n, const float* pos);
+/* ydorb_map_update_normal_depth for the n named points only, results in the order given ([n] and [n][3]); a slot may repeat. */
+int ydorb_mapdb_update_normal_depth(ydorb_mapdb_t* db, const int32_t* slots, int32_t n, const float* scale_factors, int32_t n_levels,
+                                    float* normal, float* min_distance, float* max_distance, uint8_t* status);
+/* ydorb_map_covisibility / ydorb_map_keyframe_redundancy over the resident table: point_idx holds point slots, query_kf / cand_kf /
+ * removed [n_keyframes] keyframe slots.  Results, status codes and the capacity rule are those of the flat entries. */
+int ydorb_mapdb_covisibility(ydorb_mapdb_t* db, const int32_t* query_kf, int32_t n_queries, const int32_t* list_start,
+                             const int32_t* point_idx, const int32_t* out_start, int32_t* conn_kf, int32_t* conn_weight, int32_t* counts,
+                             uint8_t* status);
+int ydorb_mapdb_keyframe_redundancy(ydorb_mapdb_t* db, const int32_t* cand_kf, int32_t n_candidates, const int32_t* list_start,
+                                    const int32_t* point_idx, const uint8_t* own_level, const uint8_t* removed, int32_t th_obs,
+                                    int32_t* n_counted, int32_t* n_redundant, uint8_t* cull);
+int ydorb_mapdb_stats(ydorb_mapdb_t* db, YdMapDbStats* stats);
+/* Reads the device's table back (after applying what is staged) as one flat YdObservationTable plus the four arrays: obs_start
+ * [n_points+1], obs_kf / obs_level [n_observations], bad / ref_kf / ref_level [n_points], pos [n_points][3], centre
+ * [n_keyframes][3], sized from ydorb_mapdb_stats. */
+int ydorb_mapdb_export(ydorb_mapdb_t* db, int32_t* obs_start, int32_t* obs_kf, uint8_t* obs_level, uint8_t* bad, int32_t* ref_kf,
+                       uint8_t* ref_level, float* pos, float* centre);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,345 @@
+// The resident map table behind the three map-maintenance adapters (c_api.h "Resident map table"): a class
+// template over the reference's own KeyFrame / MapPoint types that owns one ydorb_mapdb_t and the pointer -> slot maps, with free
+// lists.  Where mapPoint.hpp, keyFrame.hpp and keyFrameCullingImpl flatten the observation containers on every call, a MapMirror is
+// told what changed:
+//   touch(mp)          re-reads the point's observations, bad flag, reference keyframe and position at the next flush
+//   touchPosition(mp)  re-reads its position only (a BA write-back)
+//   touch(kf)          re-reads the camera centre
+//   forget(mp / kf)    gives the slot back (a forgotten point is erased from the table)
+// INTEGRATION.md ("Resident map table") lists where the reference needs each.  flush() makes at most one call of each set_* entry; the
+// three queries flush first and then walk only the keyframes' map-point vectors, never the observation maps.  A missed touch does not
+// fail: results then differ from the reference's, and verify() names the slot.
+// One thread at a time per MapMirror (the handle below it has its own mutex; the pointer maps here do not).
+// Assumed spellings: those of mapPoint.hpp, keyFrame.hpp and localMapping.hpp.
+#ifndef YDORB_ADAPTER_MAPMIRROR_HPP
+#define YDORB_ADAPTER_MAPMIRROR_HPP
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <stdexcept>
+#include <vector>
+
+#include <opencv2/core.hpp>
+
+#include "c_api.h"
+#include "mapPoint.hpp"
+
+namespace ydorb {
+namespace adapter {
+
+template <class KeyFramePtr, class MapPointPtr>
+class MapMirror {
+ public:
+  explicit MapMirror(int device = 0, int32_t pointCapacity = 1 << 16, int32_t keyFrameCapacity = 1024, int64_t observationCapacity = 1 << 19) {
+    mapCheck(ydorb_mapdb_create(device, pointCapacity, keyFrameCapacity, observationCapacity, &db_));
+  }
+  ~MapMirror() { ydorb_mapdb_destroy(db_); }
+  MapMirror(const MapMirror&) = delete;
+  MapMirror& operator=(const MapMirror&) = delete;
+
+  ydorb_mapdb_t* handle() const { return db_; }
+  int32_t slotOf(const MapPointPtr& mp) const { const auto it = pointSlot_.find(mp); return it == pointSlot_.end() ? -1 : it->second; }
+  int32_t slotOf(const KeyFramePtr& kf) const { const auto it = kfSlot_.find(kf); return it == kfSlot_.end() ? -1 : it->second; }
+
+  void touch(const MapPointPtr& mp) { mark(pointDirty_, dirtyPoints_, pointSlotFor(mp), kFull); }
+  void touchPosition(const MapPointPtr& mp) { mark(pointDirty_, dirtyPoints_, pointSlotFor(mp), kPos); }
+  void touch(const KeyFramePtr& kf) { mark(kfDirty_, dirtyKfs_, kfSlotFor(kf), kFull); }
+  void forget(const MapPointPtr& mp) {
+    const auto it = pointSlot_.find(mp);
+    if (it == pointSlot_.end()) return;
+    const int32_t s = it->second;
+    pointSlot_.erase(it);
+    pointOf_[s] = MapPointPtr();
+    freePoints_.push_back(s);
+    mark(pointDirty_, dirtyPoints_, s, kFull);   // the next flush erases it, or writes the point that took the slot since
+  }
+  void forget(const KeyFramePtr& kf) {
+    const auto it = kfSlot_.find(kf);
+    if (it == kfSlot_.end()) return;
+    kfOf_[it->second] = KeyFramePtr();
+    freeKfs_.push_back(it->second);
+    kfSlot_.erase(it);
+  }
+  void clear() {   // Map::clear
+    mapCheck(ydorb_mapdb_clear(db_));
+    pointSlot_.clear(); pointOf_.clear(); freePoints_.clear(); pointDirty_.clear(); dirtyPoints_.clear(); span_.clear();
+    kfSlot_.clear(); kfOf_.clear(); freeKfs_.clear(); kfDirty_.clear(); dirtyKfs_.clear();
+  }
+
+  // At most one call of each set_* entry: the centres first (a point may name a keyframe that got its slot while the point was read).
+  void flush() {
+    std::vector<int32_t> slots, start{0}, obsKf, refKf, posSlots;
+    std::vector<uint8_t> obsLevel, bad, refLevel;
+    std::vector<float> pos, posOnly;
+    for (const int32_t s : dirtyPoints_) {
+      const uint8_t how = pointDirty_[s];
+      pointDirty_[s] = kClean;
+      if (how == kPos && pointOf_[s]) {
+        posSlots.push_back(s);
+        const cv::Mat P = pointOf_[s]->getPosInWorld();
+        for (int r = 0; r < 3; r++) posOnly.push_back(P.template at<float>(r));
+        continue;
+      }
+      if (!pointOf_[s] && kfOf_.empty()) continue;   // no keyframe was ever named: nothing of this slot reached the table
+      const Record rec = pointOf_[s] ? read(pointOf_[s], true) : Record();
+      slots.push_back(s);
+      obsKf.insert(obsKf.end(), rec.kf.begin(), rec.kf.end()); obsLevel.insert(obsLevel.end(), rec.level.begin(), rec.level.end());
+      if (obsKf.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX observations in one flush");
+      start.push_back((int32_t)obsKf.size());
+      bad.push_back(rec.bad); refKf.push_back(rec.refKf); refLevel.push_back(rec.refLevel);
+      pos.insert(pos.end(), rec.pos, rec.pos + 3);
+      span_[s] = (int32_t)rec.kf.size();
+    }
+    dirtyPoints_.clear();
+    if (!dirtyKfs_.empty()) {
+      std::vector<int32_t> ks;
+      std::vector<float> centre;
+      for (const int32_t k : dirtyKfs_) {
+        kfDirty_[k] = kClean;
+        if (!kfOf_[k]) continue;   // forgotten since: the slot keeps its last centre until it is taken again
+        ks.push_back(k);
+        const cv::Mat O = kfOf_[k]->getCameraOriginInWorld();
+        for (int r = 0; r < 3; r++) centre.push_back(O.template at<float>(r));
+      }
+      dirtyKfs_.clear();
+      if (!ks.empty()) mapCheck(ydorb_mapdb_set_centres(db_, ks.data(), (int32_t)ks.size(), centre.data()));
+    }
+    if (!slots.empty())
+      mapCheck(ydorb_mapdb_set_points(db_, slots.data(), (int32_t)slots.size(), start.data(), obsKf.data(), obsLevel.data(), bad.data(), refKf.data(),
+                                      refLevel.data(), pos.data()));
+    if (!posSlots.empty()) mapCheck(ydorb_mapdb_set_positions(db_, posSlots.data(), (int32_t)posSlots.size(), posOnly.data()));
+  }
+
+  // updateNormalAndDepthBatch of mapPoint.hpp over the resident table: apply(mp, normal (3x1 CV_32F), minDistance, maxDistance) for every
+  // point the reference would have updated, each distinct point once, in the order of `points`.  Returns their number.
+  template <class Points, class Apply>
+  int updateNormalAndDepth(const Points& points, Apply apply) {
+    std::vector<int32_t> slots;
+    std::vector<MapPointPtr> asked;
+    std::vector<uint8_t> seen(pointOf_.size(), 0);
+    for (const MapPointPtr& mp : points) {
+      if (!mp) continue;
+      const int32_t s = known(mp);
+      if ((size_t)s >= seen.size()) seen.resize((size_t)s + 1, 0);
+      if (seen[s]) continue;
+      seen[s] = 1;
+      slots.push_back(s);
+      asked.push_back(mp);
+    }
+    flush();
+    const size_t n = slots.size();
+    if (n == 0) return 0;
+    const std::vector<float> sf = scaleFactors();
+    std::vector<float> normal(3 * n), minD(n), maxD(n);
+    std::vector<uint8_t> status(n);
+    mapCheck(ydorb_mapdb_update_normal_depth(db_, slots.data(), (int32_t)n, sf.data(), (int32_t)sf.size(), normal.data(), minD.data(), maxD.data(),
+                                             status.data()));
+    int updated = 0;
+    for (size_t p = 0; p < n; p++) {
+      if (status[p] != YDORB_MAP_UPDATED) continue;
+      cv::Mat nrm(3, 1, CV_32F);
+      for (int r = 0; r < 3; r++) nrm.template at<float>(r) = normal[3 * p + r];
+      apply(asked[p], nrm, minD[p], maxD[p]);
+      updated++;
+    }
+    return updated;
+  }
+
+  // covisibilityCounter of keyFrame.hpp over the resident table
+  std::map<KeyFramePtr, int> covisibilityCounter(const KeyFramePtr& keyFrame) {
+    const int32_t query = kfSlotFor(keyFrame);
+    std::vector<int32_t> pointIdx;
+    for (const MapPointPtr& mp : keyFrame->getMapPointMatches())
+      if (mp) pointIdx.push_back(known(mp));       // per entry of the vector: a point listed twice counts twice
+    flush();
+    std::map<KeyFramePtr, int> counter;
+    if (pointIdx.empty()) return counter;
+    int64_t spans = 0;
+    for (const int32_t p : pointIdx) spans += span_[p];
+    const int32_t capacity = (int32_t)std::max<int64_t>(0, std::min<int64_t>((int64_t)kfOf_.size() - 1, spans));   // what always fits
+    const int32_t listStart[2] = {0, (int32_t)pointIdx.size()}, outStart[2] = {0, capacity};
+    std::vector<int32_t> kf((size_t)capacity + 1), weight((size_t)capacity + 1);
+    int32_t count = 0;
+    uint8_t status = 0;
+    mapCheck(ydorb_mapdb_covisibility(db_, &query, 1, listStart, pointIdx.data(), outStart, kf.data(), weight.data(), &count, &status));
+    if (status != 0) throw std::runtime_error("ydorb: covisibility capacity bound violated");
+    for (int32_t i = 0; i < count; i++) counter[kfOf_[kf[i]]] = weight[i];
+    return counter;
+  }
+
+  // keyFrameCullingImpl of localMapping.hpp over the resident table: the same walk, the same `removed` mask.  Returns the keyframes
+  // setBadFlag() was called on, in order.  What setBadFlag() changes reaches the table through the touches it makes, at the next flush.
+  std::vector<KeyFramePtr> keyFrameCulling(const KeyFramePtr& current, float thDepth) {
+    std::vector<KeyFramePtr> candidates, flagged;
+    std::vector<int32_t> candKf, listStart{0}, pointIdx;
+    std::vector<uint8_t> ownLevel;
+    for (const KeyFramePtr& kf : current->getVectorCovisibleKeyFrames()) {
+      if (kf->m_int_keyFrameID == 0) continue;
+      candidates.push_back(kf);
+      candKf.push_back(kfSlotFor(kf));
+      const std::vector<MapPointPtr> mps = kf->getMapPointMatches();
+      for (size_t i = 0; i < mps.size(); i++) {
+        if (!mps[i]) continue;
+        if (kf->m_v_depth[i] > thDepth || kf->m_v_depth[i] < 0) continue;
+        pointIdx.push_back(known(mps[i]));
+        ownLevel.push_back((uint8_t)kf->m_v_keyPoints[i].octave);
+      }
+      if (pointIdx.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX culling entries");
+      listStart.push_back((int32_t)pointIdx.size());
+    }
+    flush();
+    const int32_t K = (int32_t)candidates.size();
+    if (K == 0) return flagged;
+    std::vector<uint8_t> removed(kfOf_.size(), 0), cull(K);
+    std::vector<int32_t> nCounted(K), nRedundant(K), start;
+    bool masked = false;
+    int32_t at = 0;
+    while (at < K) {
+      const int32_t n = K - at, base = listStart[at];
+      start.assign((size_t)n + 1, 0);
+      for (int32_t k = 0; k <= n; k++) start[k] = listStart[at + k] - base;
+      mapCheck(ydorb_mapdb_keyframe_redundancy(db_, candKf.data() + at, n, start.data(), pointIdx.data() + base, ownLevel.data() + base,
+                                               masked ? removed.data() : nullptr, 3, nCounted.data(), nRedundant.data(), cull.data()));
+      int32_t k = 0;
+      for (; k < n; k++) {
+        if (!cull[k]) continue;
+        const KeyFramePtr& kf = candidates[at + k];
+        kf->setBadFlag();
+        flagged.push_back(kf);
+        if (kf->isBad()) {   // erased: the verdicts after it are stale
+          removed[candKf[at + k]] = 1;
+          masked = true;
+          k++;
+          break;
+        }
+      }
+      at += k;
+    }
+    return flagged;
+  }
+
+  struct Difference {
+    std::vector<int32_t> pointSlots, keyFrameSlots;
+    bool empty() const { return pointSlots.empty() && keyFrameSlots.empty(); }
+  };
+  // Flushes, re-reads everything the mirror knows and compares it with the device's table (ydorb_mapdb_export): the point slots whose
+  // record differs and the keyframe slots whose centre differs.  Empty when every change was touched.
+  Difference verify() {
+    flush();
+    YdMapDbStats st;
+    mapCheck(ydorb_mapdb_stats(db_, &st));
+    const size_t np = (size_t)st.n_points, nk = (size_t)st.n_keyframes, N = (size_t)st.n_observations;
+    std::vector<int32_t> start(np + 1), obsKf(N + 1), refKf(np + 1);
+    std::vector<uint8_t> obsLevel(N + 1), bad(np + 1), refLevel(np + 1);
+    std::vector<float> pos(3 * np + 3), centre(3 * nk + 3);
+    mapCheck(ydorb_mapdb_export(db_, start.data(), obsKf.data(), obsLevel.data(), bad.data(), refKf.data(), refLevel.data(), pos.data(), centre.data()));
+    Difference d;
+    for (size_t s = 0; s < pointOf_.size(); s++) {
+      const Record want = pointOf_[s] ? read(pointOf_[s], false) : Record();
+      bool same = s < np || (!pointOf_[s] && want.kf.empty());   // a slot past the table: only a free one that was never sent
+      if (s < np) {
+        const size_t len = (size_t)(start[s + 1] - start[s]);
+        same = len == want.kf.size() && bad[s] == want.bad;
+        same = same && (len == 0 || (std::memcmp(&obsKf[start[s]], want.kf.data(), 4 * len) == 0 && std::memcmp(&obsLevel[start[s]], want.level.data(), len) == 0));
+        if (pointOf_[s]) same = same && refKf[s] == want.refKf && refLevel[s] == want.refLevel && std::memcmp(&pos[3 * s], want.pos, 12) == 0;
+      }
+      if (!same) d.pointSlots.push_back((int32_t)s);
+    }
+    for (size_t k = 0; k < kfOf_.size(); k++) {
+      if (!kfOf_[k]) continue;
+      const cv::Mat O = kfOf_[k]->getCameraOriginInWorld();
+      float c[3];
+      for (int r = 0; r < 3; r++) c[r] = O.template at<float>(r);
+      if (k >= nk || std::memcmp(&centre[3 * k], c, 12) != 0) d.keyFrameSlots.push_back((int32_t)k);
+    }
+    return d;
+  }
+
+ private:
+  enum : uint8_t { kClean = 0, kPos = 1, kFull = 2 };
+  struct Record {   // what set_points takes for one point; the default is an erased point
+    std::vector<int32_t> kf;
+    std::vector<uint8_t> level;
+    uint8_t bad = 1, refLevel = 0;
+    int32_t refKf = 0;
+    float pos[3] = {0.f, 0.f, 0.f};
+  };
+
+  static void mark(std::vector<uint8_t>& state, std::vector<int32_t>& list, int32_t s, uint8_t how) {
+    if (state[s] == kClean) list.push_back(s);
+    state[s] = std::max(state[s], how);
+  }
+  int32_t pointSlotFor(const MapPointPtr& mp) {
+    const auto it = pointSlot_.find(mp);
+    if (it != pointSlot_.end()) return it->second;
+    int32_t s;
+    if (!freePoints_.empty()) { s = freePoints_.back(); freePoints_.pop_back(); }
+    else { s = (int32_t)pointOf_.size(); pointOf_.push_back(MapPointPtr()); pointDirty_.push_back(kClean); span_.push_back(0); }
+    pointOf_[s] = mp;
+    pointSlot_[mp] = s;
+    return s;
+  }
+  int32_t kfSlotFor(const KeyFramePtr& kf) {   // a keyframe met for the first time gets a slot and its centre is sent
+    const auto it = kfSlot_.find(kf);
+    if (it != kfSlot_.end()) return it->second;
+    int32_t s;
+    if (!freeKfs_.empty()) { s = freeKfs_.back(); freeKfs_.pop_back(); }
+    else { s = (int32_t)kfOf_.size(); kfOf_.push_back(KeyFramePtr()); kfDirty_.push_back(kClean); }
+    kfOf_[s] = kf;
+    kfSlot_[kf] = s;
+    mark(kfDirty_, dirtyKfs_, s, kFull);
+    return s;
+  }
+  // the slot of a point a query names; one the mirror has never been told of is read now (its observation map is walked this once)
+  int32_t known(const MapPointPtr& mp) {
+    const auto it = pointSlot_.find(mp);
+    if (it != pointSlot_.end()) return it->second;
+    const int32_t s = pointSlotFor(mp);
+    mark(pointDirty_, dirtyPoints_, s, kFull);
+    return s;
+  }
+  // assign: a keyframe without a slot gets one (flush); otherwise it reads as slot -1, which no table holds (verify)
+  Record read(const MapPointPtr& mp, bool assign) {
+    Record r;
+    r.bad = mp->isBad() ? 1 : 0;
+    const auto observations = mp->getObservations();
+    for (const auto& ob : observations) {   // the container's own order
+      r.kf.push_back(assign ? kfSlotFor(ob.first) : slotOf(ob.first));
+      const int octave = ob.first->m_v_keyPoints[ob.second].octave;
+      r.level.push_back((uint8_t)((octave & 0x7f) | (ob.first->m_v_rightXcords[ob.second] >= 0 ? 0x80 : 0)));
+    }
+    const KeyFramePtr ref = mp->getReferenceKeyFrame();
+    if (ref) {
+      r.refKf = assign ? kfSlotFor(ref) : slotOf(ref);
+      if (!r.bad && !r.kf.empty()) {   // the reference reads its reference keyframe only past both early returns
+        const auto it = observations.find(ref);
+        r.refLevel = (uint8_t)ref->m_v_keyPoints[it != observations.end() ? it->second : 0].octave;
+      }
+    } else if (kfOf_.empty()) {
+      throw std::runtime_error("ydorb: a map point without a reference keyframe in a mirror without keyframes");
+    }
+    const cv::Mat P = mp->getPosInWorld();
+    for (int i = 0; i < 3; i++) r.pos[i] = P.template at<float>(i);
+    return r;
+  }
+  std::vector<float> scaleFactors() const {   // one pyramid for all keyframes
+    for (const KeyFramePtr& kf : kfOf_) if (kf) return kf->m_v_scaleFactors;
+    return std::vector<float>(1, 1.0f);
+  }
+
+  ydorb_mapdb_t* db_ = nullptr;
+  std::map<MapPointPtr, int32_t> pointSlot_;
+  std::vector<MapPointPtr> pointOf_;
+  std::vector<int32_t> freePoints_, dirtyPoints_, span_;
+  std::vector<uint8_t> pointDirty_;
+  std::map<KeyFramePtr, int32_t> kfSlot_;
+  std::vector<KeyFramePtr> kfOf_;
+  std::vector<int32_t> freeKfs_, dirtyKfs_;
+  std::vector<uint8_t> kfDirty_;
+};
+
+}  // namespace adapter
+}  // namespace ydorb
+#endif

@@ -8,7 +8,15 @@ before timing.  Flat arrays flatter the CPU side against the reference's mutex-g
 outside both figures: --flatten runs tests/cpp_host/mapmaint_run.cpp on the local size and reports its host time per flattening.
 The kernels alone: run this tool under `rocprofv3 --kernel-trace --stats -- python tools/map_maintenance_bench.py --size local` (and
 `--size map`) and read the k_normal_depth / k_covisibility / k_redundancy rows; --kernel-ms NAME=MS turns such a figure into the
-normal-and-depth kernel's achieved bytes per second.  Prints one JSON line."""
+normal-and-depth kernel's achieved bytes per second.
+--resident times the resident map table (ydorb_mapdb_*) instead: the map-size table is loaded into one handle
+once; then, per repetition and alternating with the flat entry on the same data, the resident normal-and-depth call for the local
+window's 7 750 points after 0, 300 and 7 750 of them were touched (staging and query timed apart), and the resident covisibility and
+redundancy calls for the local window's lists; outputs are compared exactly before timing.  Two further handles, created without
+spare pool room, each time one query that has to repack: the map-size table, and 20 000 points of 300 observers.  It ends with tests/cpp_host/mapdb_run.cpp
+on local-size stand-ins: the three adapters through MapMirror beside the flattening adapters, and the price of a flush.  The kernels
+k_mapdb_apply / k_mapdb_repack: `rocprofv3 --kernel-trace --stats -- python tools/map_maintenance_bench.py --resident --reps 5`.
+Prints one JSON line."""
 import argparse
 import ctypes as C
 import json
@@ -127,6 +135,175 @@ def bench_size(name, reps):
     return out
 
 
+def stat(ts):
+    return [round(float(v) * 1e3, 4) for v in (np.median(ts), min(ts), max(ts))]
+
+
+def bench_resident(reps):
+    import mapdb_support as D
+    from ydorbslam_amd._lib import YdMapDbStats
+    n_kf, n_points, window = SIZES["map"]
+    L = y.lib()
+    d = make_map(n_kf, n_points, window)
+    T, sf = d["T"], S.scale_factors()
+    out = dict(keyframes=n_kf, points=n_points, observations=d["n_obs"])
+    h = C.c_void_p()
+    y._lib.check(L.ydorb_mapdb_create(0, n_points, n_kf, 2 * d["n_obs"], C.byref(h)))
+    all_slots, kf_slots = np.arange(n_points, dtype=np.int32), np.arange(n_kf, dtype=np.int32)
+
+    def stats():
+        st = YdMapDbStats()
+        L.ydorb_mapdb_stats(h, C.byref(st))
+        return {k: int(getattr(st, k)) for k, _ in YdMapDbStats._fields_}
+
+    def set_points(slots):
+        """Re-sends the records of `slots` (ascending) as they are."""
+        m = np.diff(T.obs_start.astype(np.int64))[slots]
+        start = np.concatenate([[0], np.cumsum(m)]).astype(np.int32)
+        take = np.concatenate([np.arange(T.obs_start[p], T.obs_start[p + 1]) for p in slots]) if len(slots) else np.zeros(0, np.int64)
+        args = [np.ascontiguousarray(a) for a in (slots, start, T.obs_kf[take], T.obs_level[take], T.bad[slots], d["ref_kf"][slots], d["ref_level"][slots], d["pos"][slots])]
+        return lambda: L.ydorb_mapdb_set_points(h, p(args[0]), len(slots), *[p(a) for a in args[1:]]), args
+
+    t0 = time.perf_counter()
+    assert L.ydorb_mapdb_set_centres(h, p(kf_slots), n_kf, p(d["centre"])) == 0
+    assert L.ydorb_mapdb_set_points(h, p(all_slots), n_points, p(T.obs_start), p(T.obs_kf), p(T.obs_level), p(T.bad), p(d["ref_kf"]), p(d["ref_level"]), p(d["pos"])) == 0, L.ydorb_last_error()
+    k0 = n_kf // 2
+    local_kfs = np.arange(k0, k0 + window, dtype=np.int32)
+    # the local window's 7 750 points: keyframes of the map-size table hold fewer points each, so the window's points are those of as
+    # many neighbouring keyframes as it takes
+    wide = np.arange(k0, min(k0 + 4 * window, n_kf))
+    local = np.unique(np.concatenate([d["kf_points"][d["kf_start"][k]:d["kf_start"][k + 1]] for k in wide]))[:SIZES["local"][1]].astype(np.int32)
+    n = len(local)
+    res = [np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)]
+    resident_nd = lambda: L.ydorb_mapdb_update_normal_depth(h, p(local), n, p(sf), 8, *[p(a) for a in res])
+    assert resident_nd() == 0, L.ydorb_last_error()
+    out["load_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
+    out["load_sync_bytes"] = stats()["last_sync_bytes"]
+    flat = [np.zeros((n_points, 3), np.float32), np.zeros(n_points, np.float32), np.zeros(n_points, np.float32), np.zeros(n_points, np.uint8)]
+    flat_nd = lambda: L.ydorb_map_update_normal_depth(C.byref(T.struct), p(d["pos"]), p(d["centre"]), p(d["ref_kf"]), p(d["ref_level"]), p(sf), 8, 0, *[p(a) for a in flat])
+    assert flat_nd() == 0
+    for a, b in zip(res, flat):
+        assert np.array_equal(a.view(np.uint8), b[local].view(np.uint8))
+    # the flat entry over the local window alone: a table of the local points over the same keyframe slots
+    m = np.diff(T.obs_start.astype(np.int64))[local]
+    take = np.concatenate([np.arange(T.obs_start[q], T.obs_start[q + 1]) for q in local])
+    TL = M.ObservationTable.from_arrays(n_kf, np.concatenate([[0], np.cumsum(m)]).astype(np.int32), T.obs_kf[take], T.obs_level[take], T.bad[local])
+    lpos, lref, llvl = [np.ascontiguousarray(d[k][local]) for k in ("pos", "ref_kf", "ref_level")]
+    fl = [np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)]
+    flat_local = lambda: L.ydorb_map_update_normal_depth(C.byref(TL.struct), p(lpos), p(d["centre"]), p(lref), p(llvl), p(sf), 8, 0, *[p(a) for a in fl])
+    assert flat_local() == 0
+    for a, b in zip(res, fl):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    rows = {}
+    for touched in (0, 300, n):
+        stage, keep = set_points(local[:touched])
+        ts = dict(stage=[], query=[], flat_map=[], flat_local=[])
+        sync_bytes = 0
+        for r in range(reps + 1):
+            t = [time.perf_counter()]
+            if touched:
+                assert stage() == 0
+            t.append(time.perf_counter())
+            assert resident_nd() == 0
+            t.append(time.perf_counter())
+            sync_bytes = stats()["last_sync_bytes"]
+            u = [time.perf_counter()]
+            flat_nd()
+            u.append(time.perf_counter())
+            flat_local()
+            u.append(time.perf_counter())
+            if r:
+                ts["stage"].append(t[1] - t[0]); ts["query"].append(t[2] - t[1]); ts["flat_map"].append(u[1] - u[0]); ts["flat_local"].append(u[2] - u[1])
+        for a, b in zip(res, fl):
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+        rows["touched_%d" % touched] = dict(stage_ms=stat(ts["stage"]), resident_query_ms=stat(ts["query"]), flat_map_ms=stat(ts["flat_map"]),
+                                            flat_local_ms=stat(ts["flat_local"]), sync_bytes=sync_bytes)
+    out["normal_depth_local_points"] = dict(points=n, **rows)
+
+    # covisibility and redundancy of the local window's lists against the map-size table
+    start = np.concatenate([[0], np.cumsum(d["kf_start"][local_kfs + 1] - d["kf_start"][local_kfs])]).astype(np.int32)
+    idx = np.ascontiguousarray(np.concatenate([d["kf_points"][d["kf_start"][k]:d["kf_start"][k + 1]] for k in local_kfs]).astype(np.int32))
+    own = np.ascontiguousarray(np.concatenate([d["kf_levels"][d["kf_start"][k]:d["kf_start"][k + 1]] for k in local_kfs]).astype(np.uint8))
+    span = T.span_lengths()
+    caps = [min(n_kf - 1, int(span[idx[start[i]:start[i + 1]]].sum())) for i in range(window)]
+    out_start = np.concatenate([[0], np.cumsum(caps)]).astype(np.int32)
+    tot = int(out_start[-1])
+    mk = lambda: [np.full(tot, -1, np.int32), np.full(tot, -1, np.int32), np.zeros(window, np.int32), np.zeros(window, np.uint8)]
+    ra, fa = mk(), mk()
+    pairs = dict(covisibility=(lambda: L.ydorb_mapdb_covisibility(h, p(local_kfs), window, p(start), p(idx), p(out_start), *[p(a) for a in ra]),
+                               lambda: L.ydorb_map_covisibility(C.byref(T.struct), p(local_kfs), window, p(start), p(idx), p(out_start), 0, *[p(a) for a in fa]), ra, fa))
+    rb, fb = [np.zeros(window, np.int32), np.zeros(window, np.int32), np.zeros(window, np.uint8)], [np.zeros(window, np.int32), np.zeros(window, np.int32), np.zeros(window, np.uint8)]
+    pairs["redundancy"] = (lambda: L.ydorb_mapdb_keyframe_redundancy(h, p(local_kfs), window, p(start), p(idx), p(own), None, 3, *[p(a) for a in rb]),
+                           lambda: L.ydorb_map_keyframe_redundancy(C.byref(T.struct), p(local_kfs), window, p(start), p(idx), p(own), None, 3, 0, *[p(a) for a in fb]), rb, fb)
+    for label, (rf, ff, ro, fo) in pairs.items():
+        assert rf() == 0 and ff() == 0, L.ydorb_last_error()
+        for a, b in zip(ro, fo):
+            assert np.array_equal(a, b), label
+        tr, tf = [], []
+        for r in range(reps + 1):
+            t0 = time.perf_counter(); rf(); t1 = time.perf_counter(); ff(); t2 = time.perf_counter()
+            if r:
+                tr.append(t1 - t0); tf.append(t2 - t1)
+        out[label + "_local_lists"] = dict(queries=window, list_entries=int(start[-1]), resident_ms=stat(tr), flat_map_ms=stat(tf))
+    # one repack at the map size, once: a second handle whose pool has no room for the 7 750 re-sent spans
+    h2 = C.c_void_p()
+    y._lib.check(L.ydorb_mapdb_create(0, n_points, n_kf, d["n_obs"] + 1000, C.byref(h2)))
+    L.ydorb_mapdb_set_centres(h2, p(kf_slots), n_kf, p(d["centre"]))
+    L.ydorb_mapdb_set_points(h2, p(all_slots), n_points, p(T.obs_start), p(T.obs_kf), p(T.obs_level), p(T.bad), p(d["ref_kf"]), p(d["ref_level"]), p(d["pos"]))
+    again = lambda: L.ydorb_mapdb_update_normal_depth(h2, p(local), n, p(sf), 8, *[p(a) for a in res])
+    assert again() == 0
+    _, args = set_points(local)
+    assert L.ydorb_mapdb_set_points(h2, p(args[0]), n, *[p(a) for a in args[1:]]) == 0
+    t0 = time.perf_counter()
+    assert again() == 0
+    t1 = time.perf_counter()
+    st2 = YdMapDbStats()
+    L.ydorb_mapdb_stats(h2, C.byref(st2))
+    out["query_with_a_repack_at_map_size"] = dict(ms_once=round((t1 - t0) * 1e3, 4), repacks_grown=int(st2.repacks_grown), sync_bytes=int(st2.last_sync_bytes),
+                                                  pool_capacity=int(st2.pool_capacity))
+    for a, b in zip(res, fl):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    L.ydorb_mapdb_destroy(h2)
+    # ... and one repack of long spans: 20 000 points of 300 observers each, the pool again without room
+    rng = np.random.default_rng(3)
+    nl, ll = 20000, 300
+    lkf = np.ascontiguousarray(np.argsort(rng.uniform(size=(nl, 512)), axis=1)[:, :ll].astype(np.int32).reshape(-1) + rng.integers(0, n_kf - 512, nl).repeat(ll).astype(np.int32))
+    lstart = (np.arange(nl + 1, dtype=np.int64) * ll).astype(np.int32)
+    llev, lbad, lslots = np.zeros(nl * ll, np.uint8), np.zeros(nl, np.uint8), np.arange(nl, dtype=np.int32)
+    lref, lrl, lp = np.ascontiguousarray(lkf[::ll]), np.zeros(nl, np.uint8), np.ascontiguousarray(d["pos"][:nl])
+    h3 = C.c_void_p()
+    y._lib.check(L.ydorb_mapdb_create(0, nl, n_kf, nl * ll + 1000, C.byref(h3)))
+    L.ydorb_mapdb_set_centres(h3, p(kf_slots), n_kf, p(d["centre"]))
+    assert L.ydorb_mapdb_set_points(h3, p(lslots), nl, p(lstart), p(lkf), p(llev), p(lbad), p(lref), p(lrl), p(lp)) == 0, L.ydorb_last_error()
+    some = np.arange(100, dtype=np.int32)
+    lres = [np.zeros((100, 3), np.float32), np.zeros(100, np.float32), np.zeros(100, np.float32), np.zeros(100, np.uint8)]
+    ask = lambda: L.ydorb_mapdb_update_normal_depth(h3, p(some), 100, p(sf), 8, *[p(a) for a in lres])
+    assert ask() == 0
+    before = [a.copy() for a in lres]
+    assert L.ydorb_mapdb_set_points(h3, p(some), 100, p(lstart[:101]), p(lkf[:100 * ll]), p(llev), p(lbad), p(lref), p(lrl), p(lp)) == 0
+    t0 = time.perf_counter()
+    assert ask() == 0
+    t1 = time.perf_counter()
+    L.ydorb_mapdb_stats(h3, C.byref(st2))
+    for a, b in zip(lres, before):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    out["query_with_a_repack_of_long_spans"] = dict(points=nl, span=ll, ms_once=round((t1 - t0) * 1e3, 4), repacks_grown=int(st2.repacks_grown))
+    L.ydorb_mapdb_destroy(h3)
+    st = stats()
+    out["handle"] = {k: st[k] for k in ("pool_used", "pool_capacity", "repacks_kept", "repacks_grown", "point_table_growths", "keyframe_table_growths")}
+    L.ydorb_mapdb_destroy(h)
+
+    # adapter level, on stand-ins at the local size
+    m = S.random_map(5, 31, 7750, 4, 8, level_spread=1)
+    scene = S.adapter_scene(m, 8.0, seed=2)
+    tmp = tempfile.mkdtemp(prefix="mdbench")
+    exe = D.build_mirror_exe(os.path.join(tmp, "mapdb_run"))
+    run = D.run_mirror(exe, tmp, scene, 0, list(range(31)), [15], S.scale_factors(), reps=reps)
+    assert all(run[ph + k] == 1 for ph in "ABC" for k in ("_normal_same", "_covisibility_same", "_culling_same"))
+    out["adapters_local_stand_ins_ms"] = {k[len("time_"):-len("_ms")]: v for k, v in run.items() if k.startswith("time_")}
+    return out
+
+
 def flatten_times():
     """Host time of the adapters' three flattenings on stand-ins at the local size (31 keyframes, 7 750 points)."""
     m = S.random_map(5, 31, 7750, 4, 8, level_spread=1)
@@ -142,8 +319,14 @@ def main():
     ap.add_argument("--size", choices=["local", "map", "both"], default="both")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--flatten", action="store_true")
+    ap.add_argument("--resident", action="store_true", help="time the resident map table (ydorb_mapdb_*) beside the flat entries instead")
     ap.add_argument("--kernel-ms", action="append", default=[], help="SIZE=MS: k_normal_depth's time from a kernel trace, for the bytes-per-second figure")
     a = ap.parse_args()
+    if a.resident:
+        res = bench_resident(a.reps)
+        M.release()
+        print(json.dumps(res))
+        return
     res = {}
     for name in (["local", "map"] if a.size == "both" else [a.size]):
         res[name] = bench_size(name, a.reps)

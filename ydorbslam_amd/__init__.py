@@ -19,8 +19,9 @@ from .frustum import frustum_cull, search_local_points  # noqa: F401
 from .frame import extract_rgbd, frame_tail, image_bounds, undistort_points  # noqa: F401
 from .essential_graph import optimize_essential_graph  # noqa: F401
 from .map_maintenance import COVIS_WINDOW, ObservationTable, covisibility, keyframe_redundancy, update_normal_depth  # noqa: F401
+from .map_resident import MapDb  # noqa: F401
 
 __all__ = ["YdorbError", "lib", "library_path", "build_library", "OrbExtractor", "KP_DTYPE", "OrbMatcher", "FrameView",
            "FeatureVector", "QUERY_DTYPE", "Optimizer", "Vocabulary", "Sim3Solver", "optimize_sim3", "PnPsolver", "KeyFrameDatabase",
            "triangulate_matches", "frustum_cull", "search_local_points", "extract_rgbd", "frame_tail", "image_bounds", "undistort_points",
-           "optimize_essential_graph", "ObservationTable", "update_normal_depth", "covisibility", "keyframe_redundancy", "COVIS_WINDOW"]
+           "optimize_essential_graph", "ObservationTable", "update_normal_depth", "covisibility", "keyframe_redundancy", "COVIS_WINDOW", "MapDb"]

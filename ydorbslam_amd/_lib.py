@@ -123,6 +123,17 @@ SYMBOLS = {
     "ydorb_map_covisibility": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
     "ydorb_map_keyframe_redundancy": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     "ydorb_map_release": (C.c_int, [_I]),
+    "ydorb_mapdb_create": (C.c_int, [_I, _I, _I, C.c_int64, C.POINTER(_VP)]),
+    "ydorb_mapdb_destroy": (None, [_VP]),
+    "ydorb_mapdb_clear": (C.c_int, [_VP]),
+    "ydorb_mapdb_set_centres": (C.c_int, [_VP, _VP, _I, _VP]),
+    "ydorb_mapdb_set_points": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_set_positions": (C.c_int, [_VP, _VP, _I, _VP]),
+    "ydorb_mapdb_update_normal_depth": (C.c_int, [_VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_covisibility": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_keyframe_redundancy": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    "ydorb_mapdb_stats": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -205,6 +216,12 @@ class YdFrustumBatch(C.Structure):
 
 class YdObservationTable(C.Structure):
     _fields_ = [("n_points", _I), ("n_keyframes", _I), ("obs_start", _VP), ("obs_kf", _VP), ("obs_level", _VP), ("bad", _VP)]
+
+
+class YdMapDbStats(C.Structure):
+    _fields_ = [("n_points", _I), ("n_keyframes", _I), ("n_observations", C.c_int64), ("pool_used", C.c_int64), ("pool_capacity", C.c_int64),
+                ("repacks_kept", _I), ("repacks_grown", _I), ("point_table_growths", _I), ("keyframe_table_growths", _I),
+                ("point_capacity", _I), ("keyframe_capacity", _I), ("last_sync_bytes", C.c_int64), ("last_sync_records", C.c_int64)]
 
 
 class YdCamera(C.Structure):

@@ -11,6 +11,8 @@
 //                   sweep over all windows sizes the result and decides the overflow status before a second one writes.
 //   k_redundancy    one lane per list entry; a wave whose lanes all belong to one candidate adds its two sums with one integer atomic
 //                   each, a wave that straddles candidates adds per lane.
+// The passes serve the flat entries and the resident table (map_resident.hip) alike: a point's span is obsStart[p] .. obsEnd[p], and
+// k_normal_depth takes an optional list of the points asked for.
 // No float atomics, no inline assembly, no device-side assert / printf.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,7 +32,8 @@ static_assert(kWindow % kThreads == 0, "every wave compacts a whole number of 64
 
 struct Table {
   int nPoints, nKeyframes;
-  const int* obsStart;        // [nPoints + 1]
+  const int* obsStart;        // [nPoints] where point p's span begins ...
+  const int* obsEnd;          // [nPoints] ... and ends: obsStart + 1 for a flat table, an array of its own for the resident one
   const int* obsKf;           // [N]
   const uint8_t* obsLevel;    // [N]
   const uint8_t* bad;         // [nPoints]
@@ -44,10 +47,12 @@ struct NormalArgs {
   const uint8_t* refLevel;    // [nPoints]
   float scaleFactors[8];
   int nLevels;
-  float* normal;              // [nPoints][3]
-  float* minDistance;         // [nPoints]
-  float* maxDistance;         // [nPoints]
-  uint8_t* status;            // [nPoints]
+  const int* slots;           // [n] the points asked for (a slot may repeat), or null: all nPoints in order
+  int n;                      // lanes: results i = 0 .. n-1
+  float* normal;              // [n][3]
+  float* minDistance;         // [n]
+  float* maxDistance;         // [n]
+  uint8_t* status;            // [n]
 };
 
 // sqrt of the squared length: the squares exact in double, summed in ascending index (cv::norm returns a double)
@@ -56,9 +61,10 @@ __device__ __forceinline__ double norm3(float x, float y, float z) {
 }
 
 static __global__ __launch_bounds__(kThreads) void k_normal_depth(NormalArgs g) {
-  const int p = blockIdx.x * kThreads + threadIdx.x;
-  if (p >= g.t.nPoints) return;
-  const int b = g.t.obsStart[p], e = g.t.obsStart[p + 1];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= g.n) return;
+  const int p = g.slots ? g.slots[i] : i;
+  const int b = g.t.obsStart[p], e = g.t.obsEnd[p];
   float nx = 0.f, ny = 0.f, nz = 0.f, mn = 0.f, mx = 0.f;
   int code = YDORB_MAP_UPDATED;
   if (g.t.bad[p]) code = YDORB_MAP_BAD;
@@ -82,9 +88,9 @@ static __global__ __launch_bounds__(kThreads) void k_normal_depth(NormalArgs g) 
     mx = dist * sfRef;
     mn = mx / sfTop;
   }
-  g.normal[3 * p] = nx; g.normal[3 * p + 1] = ny; g.normal[3 * p + 2] = nz;
-  g.minDistance[p] = mn; g.maxDistance[p] = mx;
-  g.status[p] = (uint8_t)code;
+  g.normal[3 * i] = nx; g.normal[3 * i + 1] = ny; g.normal[3 * i + 2] = nz;
+  g.minDistance[i] = mn; g.maxDistance[i] = mx;
+  g.status[i] = (uint8_t)code;
 }
 
 struct CovisArgs {
@@ -120,7 +126,7 @@ static __global__ __launch_bounds__(kThreads) void k_covisibility(CovisArgs g) {
         for (int e = lb + tid; e < le; e += kThreads) {
           const int p = g.pointIdx[e];
           if (g.t.bad[p]) continue;
-          const int ob = g.t.obsStart[p], oe = g.t.obsStart[p + 1];
+          const int ob = g.t.obsStart[p], oe = g.t.obsEnd[p];
           for (int q = ob; q < oe; q++) {
             const int k = g.t.obsKf[q];
             if (k != self && k >= w0 && k - w0 < kWindow) atomicAdd(&hist[k - w0], 1);
@@ -186,7 +192,7 @@ static __global__ __launch_bounds__(kThreads) void k_redundancy(RedundancyArgs g
     const int p = g.pointIdx[e];
     if (!g.t.bad[p]) {
       const int self = g.candKf[c], limit = (int)g.ownLevel[e] + 1;
-      const int ob = g.t.obsStart[p], oe = g.t.obsStart[p + 1];
+      const int ob = g.t.obsStart[p], oe = g.t.obsEnd[p];
       int weight = 0, near = 0;
       bool lost = false;
       for (int q = ob; q < oe; q++) {

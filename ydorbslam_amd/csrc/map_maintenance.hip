@@ -38,7 +38,7 @@ struct TableAt {
   Table device(Mem& d, const YdObservationTable* T) const {
     Table t;
     t.nPoints = T->n_points; t.nKeyframes = T->n_keyframes;
-    t.obsStart = at<int>(d, start); t.obsKf = at<int>(d, kf); t.obsLevel = at<uint8_t>(d, level); t.bad = at<uint8_t>(d, bad);
+    t.obsStart = at<int>(d, start); t.obsEnd = t.obsStart + 1; t.obsKf = at<int>(d, kf); t.obsLevel = at<uint8_t>(d, level); t.bad = at<uint8_t>(d, bad);
     return t;
   }
 };
@@ -84,6 +84,7 @@ extern "C" int ydorb_map_update_normal_depth(const YdObservationTable* T, const 
   a.pos = at<float>(c.up, oPos); a.centre = at<float>(c.up, oCen); a.refKf = at<int>(c.up, oRef); a.refLevel = at<uint8_t>(c.up, oLvl);
   for (int i = 0; i < 8; i++) a.scaleFactors[i] = i < n_levels ? scale_factors[i] : 0.f;
   a.nLevels = n_levels;
+  a.slots = nullptr; a.n = T->n_points;
   a.normal = at<float>(c.down, dNrm); a.minDistance = at<float>(c.down, dMin); a.maxDistance = at<float>(c.down, dMax);
   a.status = at<uint8_t>(c.down, dSt);
   hipLaunchKernelGGL(k_normal_depth, dim3((unsigned)((np + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);

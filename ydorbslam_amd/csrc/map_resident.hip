@@ -1,0 +1,404 @@
+// Host driver of the resident map table + its C ABI (include/ydorb/c_api.h, "Resident map table").  The handle
+// owns the slot tables, the camera centres and the observation pool in device arenas, and mapdb_host.h's Host, which validates, stages
+// and plans.  The set_* entries only stage.  A query, on the handle's one stream: if anything is staged, one upload of the packed delta,
+// the table growths (device-to-device copies), k_mapdb_repack if the pool needs it and k_mapdb_apply; then the query's own arrays in one
+// upload, the pass of map_kernels.hip.h, one read-back and one synchronise.  With nothing staged no table byte moves.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/ydorb/c_api.h"
+#include "host_buffers.h"
+#include "map_kernels.hip.h"
+#include "map_table.h"
+#include "mapdb_host.h"
+#include "mapdb_kernels.hip.h"
+#include "ydorb_host.h"
+
+using namespace ydorb;
+
+struct ydorb_mapdb {
+  int device = 0;
+  StagedCtx c;                 // c.mu: LocalMapping stages while LoopClosing queries.  c.up / c.down: a query's arrays and results
+  mapdb::Host host;
+  Mem points, centres, pool;   // arenas: T and the pool pointers point into them
+  Mem delta;                   // the packed delta on the device, staged in hDelta
+  PinnedMem hDelta;
+  mapdb::SlotTables T{};
+  int* poolKf = nullptr;
+  uint8_t* poolLevel = nullptr;
+  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc) {}
+};
+
+namespace {
+
+int invalid(const std::string& what) { set_error("resident map table: %s", what.c_str()); return YDORB_ERR_INVALID_ARG; }
+
+size_t layPoints(Carve& C, mapdb::SlotTables& T, size_t cap) {
+  C.take(T.start, cap); C.take(T.end, cap); C.take(T.refKf, cap); C.take(T.pos, 3 * cap); C.take(T.bad, cap); C.take(T.refLevel, cap);
+  return C.L.bytes;
+}
+size_t layPool(Carve& C, int*& kf, uint8_t*& level, size_t cap) {
+  C.take(kf, cap); C.take(level, cap);
+  return C.L.bytes;
+}
+
+// A fresh point arena of `cap` slots: all zero, every slot bad (a slot never set reads as bad with no observations)
+int allocPoints(hipStream_t s, Mem& m, mapdb::SlotTables& T, size_t cap) {
+  mapdb::SlotTables sizing{};
+  Carve sz(nullptr);
+  int rc = m.alloc(layPoints(sz, sizing, cap));
+  if (rc) return rc;
+  Carve cv(m.p);
+  layPoints(cv, T, cap);
+  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
+  HIPCHK(hipMemsetAsync(T.bad, 1, cap, s));
+  return YDORB_OK;
+}
+int allocCentres(hipStream_t s, Mem& m, float*& centre, size_t cap) {
+  int rc = m.alloc(12 * cap);
+  if (rc) return rc;
+  centre = m.as<float>();
+  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
+  return YDORB_OK;
+}
+int allocPool(Mem& m, int*& kf, uint8_t*& level, size_t cap) {
+  int* k0 = nullptr; uint8_t* l0 = nullptr;
+  Carve sz(nullptr);
+  int rc = m.alloc(layPool(sz, k0, l0, cap));
+  if (rc) return rc;
+  Carve cv(m.p);
+  layPool(cv, kf, level, cap);
+  return YDORB_OK;
+}
+
+#define D2D(dst, src, bytes) \
+  do { if ((bytes) > 0) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, s)); } while (0)
+
+// Applies what is staged.  Called with the mutex held and the device set; everything it enqueues goes to the handle's stream, and the
+// arenas it replaces are freed only after that stream has drained.
+int sync(ydorb_mapdb* h) {
+  if (!h->host.dirty()) { h->host.nothingToSync(); return YDORB_OK; }
+  hipStream_t s = h->c.stream;
+  const mapdb::Plan P = h->host.plan();
+  int rc;
+  if ((rc = h->delta.ensure(P.bytes)) || (rc = h->hDelta.ensure(P.bytes))) return rc;
+  ScopedMem newPoints, newCentres, newPool;   // become the handle's arenas below; freed here on an early return
+  mapdb::SlotTables T = h->T;
+  int* poolKf = h->poolKf;
+  uint8_t* poolLevel = h->poolLevel;
+  if (P.pointCap != P.pointCapBefore) {
+    if ((rc = allocPoints(s, newPoints, T, (size_t)P.pointCap))) return rc;
+  }
+  if (P.kfCap != P.kfCapBefore) {
+    if ((rc = allocCentres(s, newCentres, T.centre, (size_t)P.kfCap))) return rc;
+  }
+  if (P.repack) {
+    if ((rc = allocPool(newPool, poolKf, poolLevel, (size_t)P.poolCap))) return rc;
+  }
+  h->host.pack(P, h->hDelta.as<uint8_t>());   // nothing below can be refused for a reason of the caller's: the delta counts as applied
+  HIPCHK(hipMemcpyAsync(h->delta.p, h->hDelta.p, P.bytes, hipMemcpyHostToDevice, s));
+  if (newPoints.p) {
+    const size_t n = (size_t)P.nPointsBefore;
+    D2D(T.start, h->T.start, 4 * n); D2D(T.end, h->T.end, 4 * n); D2D(T.refKf, h->T.refKf, 4 * n); D2D(T.pos, h->T.pos, 12 * n);
+    D2D(T.bad, h->T.bad, n); D2D(T.refLevel, h->T.refLevel, n);
+  }
+  if (newCentres.p) D2D(T.centre, h->T.centre, 12 * (size_t)P.nKeyframesBefore);
+  if (P.repack && P.nPointsBefore > 0) {
+    mapdb::RepackArgs a;
+    a.nPoints = P.nPointsBefore; a.start = T.start; a.end = T.end; a.newOff = at<int>(h->delta, P.oNewOff);
+    a.oldKf = h->poolKf; a.oldLevel = h->poolLevel; a.newKf = poolKf; a.newLevel = poolLevel;
+    hipLaunchKernelGGL(mapdb::k_mapdb_repack, dim3((unsigned)((P.nPointsBefore + mapdb::kThreads - 1) / mapdb::kThreads)), dim3(mapdb::kThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  {
+    mapdb::ApplyArgs a;
+    a.t = T;
+    a.nPointRec = P.nPointRec; a.nPosRec = P.nPosRec; a.nCentreRec = P.nCentreRec; a.nPayload = (int)P.nPayload; a.tail = (int)P.tail;
+    a.point = at<mapdb::PointRec>(h->delta, P.oPoint); a.position = at<mapdb::Vec3Rec>(h->delta, P.oPos); a.centre = at<mapdb::Vec3Rec>(h->delta, P.oCentre);
+    a.payKf = at<int>(h->delta, P.oPayKf); a.payLevel = at<uint8_t>(h->delta, P.oPayLevel);
+    a.poolKf = poolKf; a.poolLevel = poolLevel;
+    const size_t nFixed = (size_t)P.nPointRec + P.nPosRec + P.nCentreRec;
+    const size_t forFixed = (nFixed + mapdb::kThreads - 1) / mapdb::kThreads;
+    const size_t forPayload = std::min<size_t>(((size_t)P.nPayload + mapdb::kThreads - 1) / mapdb::kThreads, 2048);   // lanes stride past that
+    hipLaunchKernelGGL(mapdb::k_mapdb_apply, dim3((unsigned)std::max<size_t>(std::max(forFixed, forPayload), 1)), dim3(mapdb::kThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (newPoints.p || newCentres.p || newPool.p) {   // the old arenas are still read by what was enqueued
+    HIPCHK(hipStreamSynchronize(s));
+    if (newPoints.p) h->points.take(newPoints);
+    if (newCentres.p) h->centres.take(newCentres);
+    if (newPool.p) h->pool.take(newPool);
+  }
+  h->T = T; h->poolKf = poolKf; h->poolLevel = poolLevel;
+  return YDORB_OK;
+}
+
+mapmaint::Table tableOf(const ydorb_mapdb* h) {
+  mapmaint::Table t;
+  t.nPoints = h->host.nPoints(); t.nKeyframes = h->host.nKeyframes();
+  t.obsStart = h->T.start; t.obsEnd = h->T.end; t.obsKf = h->poolKf; t.obsLevel = h->poolLevel; t.bad = h->T.bad;
+  return t;
+}
+
+int ensure(StagedCtx& c, const Layout& U, const Layout& D) {
+  int rc;
+  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(D.bytes)) || (rc = c.hDown.ensure(D.bytes))) return rc;
+  return YDORB_OK;
+}
+
+}  // namespace
+
+extern "C" int ydorb_mapdb_create(int32_t device, int32_t point_capacity, int32_t keyframe_capacity, int64_t observation_capacity,
+                                  ydorb_mapdb_t** out) {
+  if (!out) return invalid("null out");
+  if (device < 0 || device >= 16) return invalid("device " + std::to_string(device) + " outside 0..15");
+  if (point_capacity < 0 || keyframe_capacity < 0 || observation_capacity < 0) return invalid("negative capacity");
+  if (observation_capacity > INT32_MAX) return invalid("a pool past INT32_MAX entries");
+  int rc = require_device(device);
+  if (rc) return rc;
+  ydorb_mapdb* h = new ydorb_mapdb(point_capacity, keyframe_capacity, observation_capacity);
+  h->device = device;
+  if (!(rc = h->c.init(device)) && !(rc = allocPoints(h->c.stream, h->points, h->T, (size_t)h->host.pointCap())) &&
+      !(rc = allocCentres(h->c.stream, h->centres, h->T.centre, (size_t)h->host.kfCap())) &&
+      !(rc = allocPool(h->pool, h->poolKf, h->poolLevel, (size_t)h->host.poolCap())) && hipStreamSynchronize(h->c.stream) != hipSuccess) {
+    set_error("hipStreamSynchronize failed");
+    rc = YDORB_ERR_HIP;
+  }
+  if (rc) { ydorb_mapdb_destroy(h); return rc; }
+  *out = h;
+  return YDORB_OK;
+}
+
+extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->c.stream) { (void)hipStreamSynchronize(h->c.stream); (void)hipStreamDestroy(h->c.stream); }
+  h->c.releaseBuffers();
+  h->points.release(); h->centres.release(); h->pool.release(); h->delta.release(); h->hDelta.release();
+  delete h;
+}
+
+extern "C" int ydorb_mapdb_clear(ydorb_mapdb_t* h) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  HIPCHK(hipSetDevice(h->device));
+  h->host.clear();
+  hipStream_t s = h->c.stream;   // every slot reads as never set again
+  HIPCHK(hipMemsetAsync(h->points.p, 0, h->points.cap, s));
+  HIPCHK(hipMemsetAsync(h->T.bad, 1, (size_t)h->host.pointCap(), s));
+  HIPCHK(hipMemsetAsync(h->centres.p, 0, h->centres.cap, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_set_centres(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n, const float* centre) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  return h->host.setCentres(kf_slots, n, centre, err) ? YDORB_OK : invalid(err);
+}
+
+extern "C" int ydorb_mapdb_set_points(ydorb_mapdb_t* h, const int32_t* slots, int32_t n, const int32_t* obs_start, const int32_t* obs_kf,
+                                      const uint8_t* obs_level, const uint8_t* bad, const int32_t* ref_kf, const uint8_t* ref_level,
+                                      const float* pos) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  return h->host.setPoints(slots, n, obs_start, obs_kf, obs_level, bad, ref_kf, ref_level, pos, err) ? YDORB_OK : invalid(err);
+}
+
+extern "C" int ydorb_mapdb_set_positions(ydorb_mapdb_t* h, const int32_t* slots, int32_t n, const float* pos) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  return h->host.setPositions(slots, n, pos, err) ? YDORB_OK : invalid(err);
+}
+
+extern "C" int ydorb_mapdb_stats(ydorb_mapdb_t* h, YdMapDbStats* stats) {
+  if (!h || !stats) return invalid("null handle or stats");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  h->host.stats(*stats);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_update_normal_depth(ydorb_mapdb_t* h, const int32_t* slots, int32_t n, const float* scale_factors, int32_t n_levels,
+                                               float* normal, float* min_distance, float* max_distance, uint8_t* status) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!h->host.checkNormalDepth(slots, n, scale_factors, n_levels, normal, min_distance, max_distance, status, err)) return invalid(err);
+  if (n == 0) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  const size_t np = (size_t)n;
+  Layout U;
+  const size_t oSlots = U.add(4 * np);
+  Layout D;
+  const size_t dNrm = D.add(12 * np), dMin = D.add(4 * np), dMax = D.add(4 * np), dSt = D.add(np);
+  if ((rc = ensure(c, U, D))) return rc;
+  std::memcpy(at<void>(c.hUp, oSlots), slots, 4 * np);
+  hipStream_t s = c.stream;
+  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  mapmaint::NormalArgs a;
+  a.t = tableOf(h);
+  a.pos = h->T.pos; a.centre = h->T.centre; a.refKf = h->T.refKf; a.refLevel = h->T.refLevel;
+  for (int i = 0; i < 8; i++) a.scaleFactors[i] = i < n_levels ? scale_factors[i] : 0.f;
+  a.nLevels = n_levels;
+  a.slots = at<int>(c.up, oSlots); a.n = n;
+  a.normal = at<float>(c.down, dNrm); a.minDistance = at<float>(c.down, dMin); a.maxDistance = at<float>(c.down, dMax);
+  a.status = at<uint8_t>(c.down, dSt);
+  hipLaunchKernelGGL(mapmaint::k_normal_depth, dim3((unsigned)((np + mapmaint::kThreads - 1) / mapmaint::kThreads)), dim3(mapmaint::kThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(normal, at<void>(c.hDown, dNrm), 12 * np);
+  std::memcpy(min_distance, at<void>(c.hDown, dMin), 4 * np);
+  std::memcpy(max_distance, at<void>(c.hDown, dMax), 4 * np);
+  std::memcpy(status, at<void>(c.hDown, dSt), np);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_covisibility(ydorb_mapdb_t* h, const int32_t* query_kf, int32_t n_queries, const int32_t* list_start,
+                                        const int32_t* point_idx, const int32_t* out_start, int32_t* conn_kf, int32_t* conn_weight,
+                                        int32_t* counts, uint8_t* status) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  const YdObservationTable hdr = h->host.counts();
+  if (!maptable::checkLists(&hdr, "query_kf", query_kf, n_queries, list_start, point_idx, err) ||
+      !maptable::checkStarts("out_start", out_start, n_queries, err))
+    return invalid(err);
+  if (n_queries > 0 && (!counts || !status)) return invalid("null counts or status");
+  if (out_start[n_queries] > 0 && (!conn_kf || !conn_weight)) return invalid("null conn_kf or conn_weight");
+  const size_t nq = (size_t)n_queries;
+  if (nq == 0) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  const size_t L = (size_t)list_start[nq], cap = (size_t)out_start[nq];
+  Layout U;
+  const size_t oQ = U.add(4 * nq), oLs = U.add(4 * (nq + 1)), oIdx = U.add(4 * L), oOs = U.add(4 * (nq + 1));
+  Layout D;
+  const size_t dKf = D.add(4 * cap), dW = D.add(4 * cap), dCnt = D.add(4 * nq), dSt = D.add(nq);
+  if ((rc = ensure(c, U, D))) return rc;
+  std::memcpy(at<void>(c.hUp, oQ), query_kf, 4 * nq);
+  std::memcpy(at<void>(c.hUp, oLs), list_start, 4 * (nq + 1));
+  if (L) std::memcpy(at<void>(c.hUp, oIdx), point_idx, 4 * L);
+  std::memcpy(at<void>(c.hUp, oOs), out_start, 4 * (nq + 1));
+  hipStream_t s = c.stream;
+  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  mapmaint::CovisArgs a;
+  a.t = tableOf(h);
+  a.nQueries = n_queries;
+  a.queryKf = at<int>(c.up, oQ); a.listStart = at<int>(c.up, oLs); a.pointIdx = at<int>(c.up, oIdx); a.outStart = at<int>(c.up, oOs);
+  a.connKf = at<int>(c.down, dKf); a.connWeight = at<int>(c.down, dW); a.counts = at<int>(c.down, dCnt); a.status = at<uint8_t>(c.down, dSt);
+  hipLaunchKernelGGL(mapmaint::k_covisibility, dim3((unsigned)nq), dim3(mapmaint::kThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(counts, at<void>(c.hDown, dCnt), 4 * nq);
+  std::memcpy(status, at<void>(c.hDown, dSt), nq);
+  const int32_t* hKf = at<int32_t>(c.hDown, dKf);
+  const int32_t* hW = at<int32_t>(c.hDown, dW);
+  for (size_t q = 0; q < nq; q++) {   // only what a query wrote, as in the flat entry
+    if (status[q] != 0 || counts[q] == 0) continue;
+    std::memcpy(conn_kf + out_start[q], hKf + out_start[q], 4 * (size_t)counts[q]);
+    std::memcpy(conn_weight + out_start[q], hW + out_start[q], 4 * (size_t)counts[q]);
+  }
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_keyframe_redundancy(ydorb_mapdb_t* h, const int32_t* cand_kf, int32_t n_candidates, const int32_t* list_start,
+                                               const int32_t* point_idx, const uint8_t* own_level, const uint8_t* removed, int32_t th_obs,
+                                               int32_t* n_counted, int32_t* n_redundant, uint8_t* cull) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  const YdObservationTable hdr = h->host.counts();
+  if (!maptable::checkLists(&hdr, "cand_kf", cand_kf, n_candidates, list_start, point_idx, err)) return invalid(err);
+  if (list_start[n_candidates] > 0 && !own_level) return invalid("null own_level");
+  if (n_candidates > 0 && (!n_counted || !n_redundant || !cull)) return invalid("null output arrays");
+  const size_t nc = (size_t)n_candidates, nk = (size_t)hdr.n_keyframes;
+  if (nc == 0) return YDORB_OK;
+  const size_t L = (size_t)list_start[nc];
+  std::memset(n_counted, 0, 4 * nc);
+  std::memset(n_redundant, 0, 4 * nc);
+  std::memset(cull, 0, nc);
+  if (L == 0) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  Layout U;
+  const size_t oC = U.add(4 * nc), oLs = U.add(4 * (nc + 1)), oIdx = U.add(4 * L), oOwn = U.add(L), oRem = U.add(nk);
+  Layout D;
+  const size_t dCnt = D.add(4 * nc), dRed = D.add(4 * nc);
+  if ((rc = ensure(c, U, D))) return rc;
+  std::memcpy(at<void>(c.hUp, oC), cand_kf, 4 * nc);
+  std::memcpy(at<void>(c.hUp, oLs), list_start, 4 * (nc + 1));
+  std::memcpy(at<void>(c.hUp, oIdx), point_idx, 4 * L);
+  std::memcpy(at<void>(c.hUp, oOwn), own_level, L);
+  if (removed) std::memcpy(at<void>(c.hUp, oRem), removed, nk);
+  else std::memset(at<void>(c.hUp, oRem), 0, nk);
+  hipStream_t s = c.stream;
+  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(c.down.p, 0, D.bytes, s));
+  mapmaint::RedundancyArgs a;
+  a.t = tableOf(h);
+  a.nCand = n_candidates; a.nEntries = (int)L; a.thObs = th_obs;
+  a.candKf = at<int>(c.up, oC); a.listStart = at<int>(c.up, oLs); a.pointIdx = at<int>(c.up, oIdx); a.ownLevel = at<uint8_t>(c.up, oOwn);
+  a.removed = at<uint8_t>(c.up, oRem);
+  a.nCounted = at<int>(c.down, dCnt); a.nRedundant = at<int>(c.down, dRed);
+  hipLaunchKernelGGL(mapmaint::k_redundancy, dim3((unsigned)((L + mapmaint::kThreads - 1) / mapmaint::kThreads)), dim3(mapmaint::kThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(n_counted, at<void>(c.hDown, dCnt), 4 * nc);
+  std::memcpy(n_redundant, at<void>(c.hDown, dRed), 4 * nc);
+  for (size_t k = 0; k < nc; k++) cull[k] = maptable::cullVerdict(n_redundant[k], n_counted[k]);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_export(ydorb_mapdb_t* h, int32_t* obs_start, int32_t* obs_kf, uint8_t* obs_level, uint8_t* bad, int32_t* ref_kf,
+                                  uint8_t* ref_level, float* pos, float* centre) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  const size_t np = (size_t)h->host.nPoints(), nk = (size_t)h->host.nKeyframes();
+  const size_t live = (size_t)h->host.liveAfterSync();
+  if (!obs_start) return invalid("null obs_start");
+  if (np > 0 && (!bad || !ref_kf || !ref_level || !pos)) return invalid("null bad, ref_kf, ref_level or pos");
+  if (live > 0 && (!obs_kf || !obs_level)) return invalid("null obs_kf or obs_level");
+  if (nk > 0 && !centre) return invalid("null centre");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  const size_t used = (size_t)h->host.poolUsed();
+  Layout D;
+  const size_t dStart = D.add(4 * np), dEnd = D.add(4 * np), dRef = D.add(4 * np), dPos = D.add(12 * np), dBad = D.add(np), dLvl = D.add(np),
+               dCen = D.add(12 * nk), dKf = D.add(4 * used), dOl = D.add(used);
+  if ((rc = c.hDown.ensure(D.bytes))) return rc;
+  hipStream_t s = c.stream;
+#define DOWN(off, src, bytes) \
+  do { if ((bytes) > 0) HIPCHK(hipMemcpyAsync(at<void>(c.hDown, off), (src), (bytes), hipMemcpyDeviceToHost, s)); } while (0)
+  DOWN(dStart, h->T.start, 4 * np); DOWN(dEnd, h->T.end, 4 * np); DOWN(dRef, h->T.refKf, 4 * np); DOWN(dPos, h->T.pos, 12 * np);
+  DOWN(dBad, h->T.bad, np); DOWN(dLvl, h->T.refLevel, np); DOWN(dCen, h->T.centre, 12 * nk);
+  DOWN(dKf, h->poolKf, 4 * used); DOWN(dOl, h->poolLevel, used);
+#undef DOWN
+  HIPCHK(hipStreamSynchronize(s));
+  mapdb::flatten((int32_t)np, at<int32_t>(c.hDown, dStart), at<int32_t>(c.hDown, dEnd), at<int32_t>(c.hDown, dKf), at<uint8_t>(c.hDown, dOl),
+                 obs_start, obs_kf, obs_level);
+  if (np) {
+    std::memcpy(ref_kf, at<void>(c.hDown, dRef), 4 * np); std::memcpy(pos, at<void>(c.hDown, dPos), 12 * np);
+    std::memcpy(bad, at<void>(c.hDown, dBad), np); std::memcpy(ref_level, at<void>(c.hDown, dLvl), np);
+  }
+  if (nk) std::memcpy(centre, at<void>(c.hDown, dCen), 12 * nk);
+  return YDORB_OK;
+}

@@ -1,0 +1,369 @@
+// Host side of the resident map table (include/ydorb/c_api.h, "Resident map table"): the validation of its
+// entries, the host mirror of the per-slot fixed records, the coalescing of staged changes, the packing of one delta, the pool policy
+// and a plain-C++ execution of a packed delta on host arrays in the record format the kernels read (mapdb_kernels.hip.h), so that the
+// whole state machine runs without a device (tests/cpu_harness/mapdb_host_check.cpp).  No HIP here: a plain host compiler builds it.
+//   staging   set_points / set_positions / set_centres validate, then write the mirror and mark the slot dirty.  A point slot is clean,
+//             position-dirty or fully dirty; a full record supersedes a position record and a later position lands in the full record,
+//             so one slot yields one record and the apply kernel never has two lanes writing one address.  Staged spans wait in a host
+//             arena; of a slot staged several times only the last span is packed.
+//   delta     [point records][position records][centre records][payload keyframe slots][payload level bytes][repack offsets], every
+//             section 16-byte aligned.  Records are in the order their slots were first dirtied.
+//   pool      spans are appended at the tail; a replaced span becomes garbage.  When used + incoming > capacity the survivors are
+//             repacked in ascending slot order into a fresh arena: the same capacity when survivors + incoming <= capacity / 2, else
+//             min(2 x (survivors + incoming), INT32_MAX).  The host computes every survivor's new offset; the delta carries them.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/ydorb/c_api.h"
+#include "map_table.h"
+
+namespace ydorb {
+namespace mapdb {
+
+using maptable::fail;
+
+struct PointRec {   // one fully dirty point
+  int32_t slot, off, len, refKf;
+  float pos[3];
+  uint8_t bad, refLevel, pad[2];
+};
+struct Vec3Rec {    // a position or a camera centre
+  int32_t slot;
+  float v[3];
+};
+static_assert(sizeof(PointRec) == 32 && sizeof(Vec3Rec) == 16, "the kernels read these layouts");
+
+enum { kNoRepack = 0, kRepackKept = 1, kRepackGrown = 2 };
+
+// What one sync does, decided before anything is written: the driver sizes its buffers from it, the kernels get their counts from it.
+struct Plan {
+  int32_t nPointRec = 0, nPosRec = 0, nCentreRec = 0;
+  int64_t nPayload = 0;
+  size_t oPoint = 0, oPos = 0, oCentre = 0, oPayKf = 0, oPayLevel = 0, oNewOff = 0, bytes = 0;
+  int32_t nPointsBefore = 0, nKeyframesBefore = 0;   // what the device tables hold: the repack covers the point slots below nPointsBefore
+  int32_t pointCapBefore = 0, pointCap = 0, kfCapBefore = 0, kfCap = 0;
+  int repack = kNoRepack;
+  int64_t poolCapBefore = 0, poolCap = 0, usedBefore = 0, survivors = 0, tail = 0;   // the payload goes to [tail, tail + nPayload)
+};
+
+// The arrays the kernels read, on the host: the state-machine check executes deltas on them, the driver flattens its read-back with
+// the same flatten().
+struct HostTables {
+  std::vector<int32_t> start, end, refKf, poolKf;
+  std::vector<uint8_t> bad, refLevel, poolLevel;
+  std::vector<float> pos, centre;
+  void sizePoints(size_t cap) {   // a slot never set reads as bad with no observations
+    start.resize(cap, 0); end.resize(cap, 0); refKf.resize(cap, 0); bad.resize(cap, 1); refLevel.resize(cap, 0); pos.resize(3 * cap, 0.f);
+  }
+  void resetPoints() { const size_t cap = start.size(); start.clear(); end.clear(); refKf.clear(); bad.clear(); refLevel.clear(); pos.clear(); sizePoints(cap); }
+};
+
+// One flat table from per-slot spans: obsStart [nPoints + 1], obsKf / obsLevel [sum of the spans]
+inline void flatten(int32_t nPoints, const int32_t* start, const int32_t* end, const int32_t* poolKf, const uint8_t* poolLevel,
+                    int32_t* obsStart, int32_t* obsKf, uint8_t* obsLevel) {
+  int32_t at = 0;
+  obsStart[0] = 0;
+  for (int32_t p = 0; p < nPoints; p++) {
+    const int32_t len = end[p] - start[p];
+    if (len > 0) {
+      memcpy(obsKf + at, poolKf + start[p], 4 * (size_t)len);
+      memcpy(obsLevel + at, poolLevel + start[p], (size_t)len);
+    }
+    at += len;
+    obsStart[p + 1] = at;
+  }
+}
+
+inline bool checkPoolTotal(int64_t total, std::string& err) {
+  return total <= INT32_MAX ? true : fail(err, "the pool would hold %lld observations, past INT32_MAX", total);
+}
+
+class Host {
+ public:
+  Host(int32_t pointCap, int32_t kfCap, int64_t poolCap) : pointCap_(std::max(pointCap, 1)), kfCap_(std::max(kfCap, 1)), poolCap_(std::max<int64_t>(poolCap, 1)) {}
+
+  int32_t nPoints() const { return (int32_t)len_.size(); }
+  int32_t nKeyframes() const { return (int32_t)(centre_.size() / 3); }
+  int32_t pointCap() const { return pointCap_; }
+  int32_t kfCap() const { return kfCap_; }
+  int64_t poolCap() const { return poolCap_; }
+  int64_t poolUsed() const { return poolUsed_; }
+  int64_t liveAfterSync() const { return pendingLive_; }
+  bool dirty() const { return !dirtyPoints_.empty() || !dirtyKf_.empty(); }
+  int32_t spanOf(int32_t slot) const { return state_[slot] == kFull ? stLen_[slot] : len_[slot]; }   // staged changes included
+
+  void clear() {
+    len_.clear(); off_.clear(); refKf_.clear(); bad_.clear(); refLevel_.clear(); pos_.clear(); centre_.clear();
+    state_.clear(); stOff_.clear(); stLen_.clear(); kfDirty_.clear();
+    dropStaged();
+    poolUsed_ = poolLive_ = pendingLive_ = 0;
+    nPointsSynced_ = nKfSynced_ = 0;
+    lastSyncBytes_ = lastSyncRecords_ = 0;
+  }
+
+  bool setCentres(const int32_t* slots, int32_t n, const float* centre, std::string& err) {
+    if (n < 0) return fail(err, "negative number of keyframe slots: %lld", n);
+    if (n > 0 && (!slots || !centre)) return fail(err, "null kf_slots or centre");
+    for (int32_t i = 0; i < n; i++)
+      if (slots[i] < 0) return fail(err, "kf_slots[%lld]: negative keyframe slot %lld", i, slots[i]);
+    for (int32_t i = 0; i < n; i++) {
+      const int32_t s = slots[i];
+      if (s >= nKeyframes()) { centre_.resize(3 * ((size_t)s + 1), 0.f); kfDirty_.resize((size_t)s + 1, 0); }
+      memcpy(&centre_[3 * (size_t)s], centre + 3 * (size_t)i, 12);
+      if (!kfDirty_[s]) { kfDirty_[s] = 1; dirtyKf_.push_back(s); }
+    }
+    return true;
+  }
+
+  bool setPoints(const int32_t* slots, int32_t n, const int32_t* obsStart, const int32_t* obsKf, const uint8_t* obsLevel, const uint8_t* bad,
+                 const int32_t* refKf, const uint8_t* refLevel, const float* pos, std::string& err) {
+    if (n < 0) return fail(err, "negative number of point slots: %lld", n);
+    if (!maptable::checkStarts("obs_start", obsStart, n, err)) return false;
+    if (n == 0) return true;
+    if (!slots || !bad || !refKf || !refLevel || !pos) return fail(err, "null slots, bad, ref_kf, ref_level or pos");
+    const int32_t N = obsStart[n];
+    if (N > 0 && (!obsKf || !obsLevel)) return fail(err, "null obs_kf or obs_level");
+    for (int32_t i = 0; i < n; i++)
+      if (slots[i] < 0) return fail(err, "slots[%lld]: negative point slot %lld", i, slots[i]);
+    for (int32_t q = 0; q < N; q++)
+      if (obsKf[q] < 0 || obsKf[q] >= nKeyframes())
+        return fail(err, "observation %lld: keyframe slot %lld outside 0..%lld", q, obsKf[q], (long long)nKeyframes() - 1);
+    for (int32_t i = 0; i < n; i++)
+      if (refKf[i] < 0 || refKf[i] >= nKeyframes())
+        return fail(err, "point %lld: reference keyframe slot %lld outside 0..%lld", i, refKf[i], (long long)nKeyframes() - 1);
+    if (pendingLive_ + (int64_t)N > INT32_MAX) {   // only then the exact figure: what the named slots hold now leaves, each slot's last span enters
+      std::unordered_map<int32_t, int32_t> last;
+      for (int32_t i = 0; i < n; i++) last[slots[i]] = obsStart[i + 1] - obsStart[i];
+      int64_t total = pendingLive_;
+      for (const auto& kv : last) total += (int64_t)kv.second - (kv.first < nPoints() ? spanOf(kv.first) : 0);
+      if (!checkPoolTotal(total, err)) return false;
+    }
+    for (int32_t i = 0; i < n; i++) {
+      const int32_t s = slots[i], len = obsStart[i + 1] - obsStart[i];
+      growPointsTo(s);
+      if (state_[s] != kFull) {
+        if (state_[s] == kClean) dirtyPoints_.push_back(s);
+        state_[s] = kFull;
+        pendingLive_ -= len_[s];
+      } else {
+        pendingLive_ -= stLen_[s];
+      }
+      stOff_[s] = stKf_.size(); stLen_[s] = len;
+      stKf_.insert(stKf_.end(), obsKf + obsStart[i], obsKf + obsStart[i] + len);
+      stLevel_.insert(stLevel_.end(), obsLevel + obsStart[i], obsLevel + obsStart[i] + len);
+      pendingLive_ += len;
+      bad_[s] = bad[i] ? 1 : 0; refKf_[s] = refKf[i]; refLevel_[s] = refLevel[i];
+      memcpy(&pos_[3 * (size_t)s], pos + 3 * (size_t)i, 12);
+    }
+    return true;
+  }
+
+  bool setPositions(const int32_t* slots, int32_t n, const float* pos, std::string& err) {
+    if (n < 0) return fail(err, "negative number of point slots: %lld", n);
+    if (n > 0 && (!slots || !pos)) return fail(err, "null slots or pos");
+    for (int32_t i = 0; i < n; i++)
+      if (slots[i] < 0 || slots[i] >= nPoints()) return fail(err, "slots[%lld]: point slot %lld outside 0..%lld", i, slots[i], (long long)nPoints() - 1);
+    for (int32_t i = 0; i < n; i++) {
+      const int32_t s = slots[i];
+      memcpy(&pos_[3 * (size_t)s], pos + 3 * (size_t)i, 12);
+      if (state_[s] == kClean) { state_[s] = kPos; dirtyPoints_.push_back(s); }
+    }
+    return true;
+  }
+
+  // the named slots of a query
+  bool checkSlots(const int32_t* slots, int32_t n, std::string& err) const {
+    if (n < 0) return fail(err, "negative number of point slots: %lld", n);
+    if (n > 0 && !slots) return fail(err, "null slots");
+    for (int32_t i = 0; i < n; i++)
+      if (slots[i] < 0 || slots[i] >= nPoints()) return fail(err, "slots[%lld]: point slot %lld outside 0..%lld", i, slots[i], (long long)nPoints() - 1);
+    return true;
+  }
+  bool checkNormalDepth(const int32_t* slots, int32_t n, const float* scaleFactors, int32_t nLevels, const float* normal, const float* minD,
+                        const float* maxD, const uint8_t* status, std::string& err) const {
+    if (nLevels < 1 || nLevels > maptable::kMaxLevels) return fail(err, "n_levels %lld outside 1..8", nLevels);
+    if (!scaleFactors) return fail(err, "null scale_factors");
+    if (!checkSlots(slots, n, err)) return false;
+    if (n > 0 && (!normal || !minD || !maxD || !status)) return fail(err, "null output arrays");
+    for (int32_t i = 0; i < n; i++) {
+      const int32_t s = slots[i];
+      if (bad_[s] || spanOf(s) == 0) continue;   // not updated: the level is not read
+      if (refLevel_[s] >= nLevels) return fail(err, "slots[%lld]: reference level %lld of point slot %lld >= n_levels", i, refLevel_[s], s);
+    }
+    return true;
+  }
+  // a table header for map_table.h's list checks: they read the two counts only
+  YdObservationTable counts() const { return YdObservationTable{nPoints(), nKeyframes(), nullptr, nullptr, nullptr, nullptr}; }
+
+  void stats(YdMapDbStats& s) const {
+    s.n_points = nPoints(); s.n_keyframes = nKeyframes();
+    s.n_observations = pendingLive_; s.pool_used = poolUsed_; s.pool_capacity = poolCap_;
+    s.repacks_kept = repacksKept_; s.repacks_grown = repacksGrown_;
+    s.point_table_growths = pointGrowths_; s.keyframe_table_growths = kfGrowths_;
+    s.point_capacity = pointCap_; s.keyframe_capacity = kfCap_;
+    s.last_sync_bytes = lastSyncBytes_; s.last_sync_records = lastSyncRecords_;
+  }
+  void nothingToSync() { lastSyncBytes_ = lastSyncRecords_ = 0; }
+
+  Plan plan() const {
+    Plan P;
+    P.nPointsBefore = nPointsSynced_; P.nKeyframesBefore = nKfSynced_;
+    P.pointCapBefore = P.pointCap = pointCap_; P.kfCapBefore = P.kfCap = kfCap_;
+    P.poolCapBefore = P.poolCap = poolCap_; P.usedBefore = poolUsed_;
+    int64_t replaced = 0;
+    for (const int32_t s : dirtyPoints_) {
+      if (state_[s] == kFull) { P.nPointRec++; P.nPayload += stLen_[s]; replaced += len_[s]; }
+      else P.nPosRec++;
+    }
+    P.nCentreRec = (int32_t)dirtyKf_.size();
+    if (nPoints() > pointCap_) P.pointCap = (int32_t)std::min<int64_t>(std::max<int64_t>(nPoints(), 2 * (int64_t)pointCap_), INT32_MAX);
+    if (nKeyframes() > kfCap_) P.kfCap = (int32_t)std::min<int64_t>(std::max<int64_t>(nKeyframes(), 2 * (int64_t)kfCap_), INT32_MAX);
+    P.survivors = poolLive_ - replaced;
+    P.tail = poolUsed_;
+    if (poolUsed_ + P.nPayload > poolCap_) {
+      const int64_t need = P.survivors + P.nPayload;   // <= INT32_MAX: set_points refused what would pass it
+      P.repack = need <= poolCap_ / 2 ? kRepackKept : kRepackGrown;
+      if (P.repack == kRepackGrown) P.poolCap = std::min<int64_t>(2 * need, INT32_MAX);
+      P.tail = P.survivors;
+    }
+    size_t at = 0;
+    auto add = [&at](size_t n) { const size_t o = at; at += (n + 15) & ~(size_t)15; return o; };
+    P.oPoint = add(sizeof(PointRec) * (size_t)P.nPointRec); P.oPos = add(sizeof(Vec3Rec) * (size_t)P.nPosRec);
+    P.oCentre = add(sizeof(Vec3Rec) * (size_t)P.nCentreRec);
+    P.oPayKf = add(4 * (size_t)P.nPayload); P.oPayLevel = add((size_t)P.nPayload);
+    P.oNewOff = add(P.repack ? 4 * (size_t)P.nPointsBefore : 0);
+    P.bytes = at;
+    return P;
+  }
+
+  // Writes the delta of `P` (made by plan() with nothing staged since) into dst [P.bytes] and takes it as applied: the mirror's offsets
+  // move, the dirty marks go, the counters advance.
+  void pack(const Plan& P, uint8_t* dst) {
+    memset(dst, 0, P.bytes);
+    if (P.repack) {   // survivors in ascending slot order; a slot this delta replaces is skipped (-1): apply gives it its new span
+      int32_t* newOff = reinterpret_cast<int32_t*>(dst + P.oNewOff);
+      int64_t at = 0;
+      for (int32_t s = 0; s < P.nPointsBefore; s++) {
+        if (state_[s] == kFull) { newOff[s] = -1; continue; }
+        newOff[s] = (int32_t)at; off_[s] = (int32_t)at;
+        at += len_[s];
+      }
+    }
+    PointRec* pr = reinterpret_cast<PointRec*>(dst + P.oPoint);
+    Vec3Rec* qr = reinterpret_cast<Vec3Rec*>(dst + P.oPos);
+    int32_t* payKf = reinterpret_cast<int32_t*>(dst + P.oPayKf);
+    uint8_t* payLevel = dst + P.oPayLevel;
+    int64_t cursor = 0;
+    for (const int32_t s : dirtyPoints_) {
+      if (state_[s] == kFull) {
+        const int32_t len = stLen_[s];
+        off_[s] = (int32_t)(P.tail + cursor); len_[s] = len;
+        PointRec r;
+        memset(&r, 0, sizeof(r));
+        r.slot = s; r.off = off_[s]; r.len = len; r.refKf = refKf_[s];
+        memcpy(r.pos, &pos_[3 * (size_t)s], 12);
+        r.bad = bad_[s]; r.refLevel = refLevel_[s];
+        *pr++ = r;
+        if (len) { memcpy(payKf + cursor, &stKf_[stOff_[s]], 4 * (size_t)len); memcpy(payLevel + cursor, &stLevel_[stOff_[s]], (size_t)len); }
+        cursor += len;
+      } else {
+        Vec3Rec r;
+        r.slot = s;
+        memcpy(r.v, &pos_[3 * (size_t)s], 12);
+        *qr++ = r;
+      }
+      state_[s] = kClean;
+    }
+    Vec3Rec* cr = reinterpret_cast<Vec3Rec*>(dst + P.oCentre);
+    for (const int32_t k : dirtyKf_) {
+      Vec3Rec r;
+      r.slot = k;
+      memcpy(r.v, &centre_[3 * (size_t)k], 12);
+      *cr++ = r;
+      kfDirty_[k] = 0;
+    }
+    dropStaged();
+    poolLive_ = P.survivors + P.nPayload; poolUsed_ = P.tail + P.nPayload; poolCap_ = P.poolCap;
+    if (P.repack == kRepackKept) repacksKept_++;
+    if (P.repack == kRepackGrown) repacksGrown_++;
+    if (P.pointCap != pointCap_) { pointCap_ = P.pointCap; pointGrowths_++; }
+    if (P.kfCap != kfCap_) { kfCap_ = P.kfCap; kfGrowths_++; }
+    nPointsSynced_ = nPoints(); nKfSynced_ = nKeyframes();
+    lastSyncBytes_ = (int64_t)P.bytes; lastSyncRecords_ = (int64_t)P.nPointRec + P.nPosRec + P.nCentreRec;
+  }
+
+ private:
+  enum : uint8_t { kClean = 0, kPos = 1, kFull = 2 };
+  void growPointsTo(int32_t s) {
+    if (s < nPoints()) return;
+    const size_t n = (size_t)s + 1;
+    len_.resize(n, 0); off_.resize(n, 0); refKf_.resize(n, 0); bad_.resize(n, 1); refLevel_.resize(n, 0); pos_.resize(3 * n, 0.f);
+    state_.resize(n, kClean); stOff_.resize(n, 0); stLen_.resize(n, 0);
+  }
+  void dropStaged() { dirtyPoints_.clear(); dirtyKf_.clear(); stKf_.clear(); stLevel_.clear(); }
+
+  // the mirror: what the device holds once the staged changes are applied (off_ / len_: what it holds now)
+  std::vector<int32_t> len_, off_, refKf_;
+  std::vector<uint8_t> bad_, refLevel_;
+  std::vector<float> pos_, centre_;
+  // staged
+  std::vector<uint8_t> state_, kfDirty_;
+  std::vector<size_t> stOff_;
+  std::vector<int32_t> stLen_, dirtyPoints_, dirtyKf_, stKf_;
+  std::vector<uint8_t> stLevel_;
+  // device capacities and pool use as of the last sync
+  int32_t pointCap_, kfCap_, nPointsSynced_ = 0, nKfSynced_ = 0;
+  int64_t poolCap_, poolUsed_ = 0, poolLive_ = 0, pendingLive_ = 0;
+  int32_t repacksKept_ = 0, repacksGrown_ = 0, pointGrowths_ = 0, kfGrowths_ = 0;
+  int64_t lastSyncBytes_ = 0, lastSyncRecords_ = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The packed delta executed on host arrays, step for step what the driver does on the device: grow the tables (contents kept, new
+// slots bad and empty), repack (k_mapdb_repack), apply (k_mapdb_apply).
+inline void repack(const Plan& P, const uint8_t* delta, HostTables& T) {
+  const int32_t* newOff = reinterpret_cast<const int32_t*>(delta + P.oNewOff);
+  std::vector<int32_t> kf((size_t)P.poolCap);
+  std::vector<uint8_t> level((size_t)P.poolCap);
+  for (int32_t p = 0; p < P.nPointsBefore; p++) {
+    if (newOff[p] < 0) continue;
+    const int32_t b = T.start[p], e = T.end[p];
+    for (int32_t q = b; q < e; q++) { kf.at((size_t)(newOff[p] + q - b)) = T.poolKf.at((size_t)q); level.at((size_t)(newOff[p] + q - b)) = T.poolLevel.at((size_t)q); }
+    T.start[p] = newOff[p]; T.end[p] = newOff[p] + (e - b);
+  }
+  T.poolKf.swap(kf); T.poolLevel.swap(level);
+}
+
+inline void apply(const Plan& P, const uint8_t* delta, HostTables& T) {
+  const PointRec* pr = reinterpret_cast<const PointRec*>(delta + P.oPoint);
+  for (int32_t i = 0; i < P.nPointRec; i++) {
+    const PointRec& r = pr[i];
+    T.start.at((size_t)r.slot) = r.off; T.end.at((size_t)r.slot) = r.off + r.len; T.refKf.at((size_t)r.slot) = r.refKf;
+    T.bad.at((size_t)r.slot) = r.bad; T.refLevel.at((size_t)r.slot) = r.refLevel;
+    memcpy(&T.pos.at(3 * (size_t)r.slot), r.pos, 12);
+  }
+  const Vec3Rec* qr = reinterpret_cast<const Vec3Rec*>(delta + P.oPos);
+  for (int32_t i = 0; i < P.nPosRec; i++) memcpy(&T.pos.at(3 * (size_t)qr[i].slot), qr[i].v, 12);
+  const Vec3Rec* cr = reinterpret_cast<const Vec3Rec*>(delta + P.oCentre);
+  for (int32_t i = 0; i < P.nCentreRec; i++) memcpy(&T.centre.at(3 * (size_t)cr[i].slot), cr[i].v, 12);
+  const int32_t* payKf = reinterpret_cast<const int32_t*>(delta + P.oPayKf);
+  const uint8_t* payLevel = delta + P.oPayLevel;
+  for (int64_t i = 0; i < P.nPayload; i++) { T.poolKf.at((size_t)(P.tail + i)) = payKf[i]; T.poolLevel.at((size_t)(P.tail + i)) = payLevel[i]; }
+}
+
+inline void execute(const Plan& P, const uint8_t* delta, HostTables& T) {
+  if (T.start.size() != (size_t)P.pointCap) T.sizePoints((size_t)P.pointCap);
+  if (T.centre.size() != 3 * (size_t)P.kfCap) T.centre.resize(3 * (size_t)P.kfCap, 0.f);
+  if (T.poolKf.size() != (size_t)P.poolCapBefore) { T.poolKf.resize((size_t)P.poolCapBefore); T.poolLevel.resize((size_t)P.poolCapBefore); }
+  if (P.repack) repack(P, delta, T);
+  apply(P, delta, T);
+}
+
+}  // namespace mapdb
+}  // namespace ydorb

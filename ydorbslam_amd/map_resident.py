@@ -1,0 +1,125 @@
+"""The resident map table through the C ABI (include/ydorb/c_api.h, "Resident map table"): the observation table
+of map maintenance kept in HBM between calls, changed by deltas and queried with no table upload.  MapDb owns one ydorb_mapdb_t.  Its
+three queries go through map_maintenance's own wrappers (same argument preparation, same result dictionaries), with the handle in place
+of the flat table."""
+import ctypes as C
+
+import numpy as np
+
+from . import map_maintenance as M
+from ._lib import YdMapDbStats, check, lib
+
+_p = M._p
+
+
+class MapDb:
+    """One resident table on `device`.  The capacities are initial: every table grows on demand.  Slots are the caller's."""
+
+    def __init__(self, device=0, point_capacity=1024, keyframe_capacity=64, observation_capacity=8192):
+        self._h = C.c_void_p()
+        check(lib().ydorb_mapdb_create(device, point_capacity, keyframe_capacity, observation_capacity, C.byref(self._h)))
+        self._span = np.zeros(0, np.int64)   # span length per point slot, for the covisibility capacity bound
+
+    def close(self):
+        if self._h:
+            lib().ydorb_mapdb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the loader may be gone already
+            pass
+
+    def clear(self):
+        check(lib().ydorb_mapdb_clear(self._h))
+        self._span = np.zeros(0, np.int64)
+
+    # ------------------------------------------------------------------------------------------------------------ staging
+    def set_centres(self, kf_slots, centre):
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        centre = np.ascontiguousarray(centre, np.float32).reshape(-1, 3)
+        assert len(centre) == len(kf_slots)
+        check(lib().ydorb_mapdb_set_centres(self._h, _p(kf_slots), len(kf_slots), _p(centre)))
+
+    def set_points(self, slots, observers, levels, bad, ref_kf, ref_level, pos):
+        """observers[i] / levels[i] = the observing keyframe slots of point slots[i] in the container's order and their level bytes (bit 7 =
+        stereo); bad, ref_kf, ref_level [n]; pos [n, 3]."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(slots)
+        start, kf = M._csr(observers, np.int32)
+        _, lv = M._csr(levels, np.uint8)
+        bad, ref_level = np.ascontiguousarray(bad, np.uint8).reshape(-1), np.ascontiguousarray(ref_level, np.uint8).reshape(-1)
+        ref_kf, pos = np.ascontiguousarray(ref_kf, np.int32).reshape(-1), np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        assert len(observers) == len(levels) == len(bad) == len(ref_kf) == len(ref_level) == len(pos) == n and len(kf) == len(lv)
+        check(lib().ydorb_mapdb_set_points(self._h, _p(slots), n, _p(start), _p(kf), _p(lv), _p(bad), _p(ref_kf), _p(ref_level), _p(pos)))
+        if n:
+            if slots.max() >= len(self._span):
+                self._span = np.concatenate([self._span, np.zeros(int(slots.max()) + 1 - len(self._span), np.int64)])
+            self._span[slots] = np.diff(start.astype(np.int64))   # a repeated slot keeps its last span, as the table does
+
+    def set_positions(self, slots, pos):
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        assert len(pos) == len(slots)
+        check(lib().ydorb_mapdb_set_positions(self._h, _p(slots), len(slots), _p(pos)))
+
+    # ------------------------------------------------------------------------------------------------------------ what the wrappers read
+    @property
+    def n_points(self):
+        return self.stats()["n_points"]
+
+    @property
+    def n_keyframes(self):
+        return self.stats()["n_keyframes"]
+
+    def span_lengths(self):
+        return self._span
+
+    # ------------------------------------------------------------------------------------------------------------ queries
+    def update_normal_depth(self, slots, scale_factors):
+        """ydorb_mapdb_update_normal_depth for the named slots.  Returns dict(normal [n, 3], min_distance, max_distance, status [n])."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        n = len(slots)
+        normal, mn, mx, st = np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.uint8)
+        check(lib().ydorb_mapdb_update_normal_depth(self._h, _p(slots), n, _p(sf), len(sf), _p(normal), _p(mn), _p(mx), _p(st)))
+        return dict(normal=normal[:n], min_distance=mn[:n], max_distance=mx[:n], status=st[:n])
+
+    def covisibility(self, query_kf, lists, capacities=None):
+        def fn(_table, q, Q, ls, idx, os_, _device, kf, w, counts, status):
+            return lib().ydorb_mapdb_covisibility(self._h, q, Q, ls, idx, os_, kf, w, counts, status)
+        return M.covisibility(_Header(self), query_kf, lists, capacities, fn=fn)
+
+    def keyframe_redundancy(self, cand_kf, lists, own_levels, removed=None, th_obs=3):
+        def fn(_table, c, K, ls, idx, own, rem, th, _device, nc, nr, cull):
+            return lib().ydorb_mapdb_keyframe_redundancy(self._h, c, K, ls, idx, own, rem, th, nc, nr, cull)
+        return M.keyframe_redundancy(_Header(self), cand_kf, lists, own_levels, removed, th_obs, fn=fn)
+
+    # ------------------------------------------------------------------------------------------------------------ inspection
+    def stats(self):
+        s = YdMapDbStats()
+        check(lib().ydorb_mapdb_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in YdMapDbStats._fields_}
+
+    def export(self):
+        """The device's table read back: dict(table [ObservationTable], ref_kf, ref_level, pos, centre)."""
+        s = self.stats()
+        n, k, N = s["n_points"], s["n_keyframes"], s["n_observations"]
+        start, kf, lv = np.zeros(n + 1, np.int32), np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.uint8)
+        bad, ref_kf, ref_level = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        pos, centre = np.zeros((max(n, 1), 3), np.float32), np.zeros((max(k, 1), 3), np.float32)
+        check(lib().ydorb_mapdb_export(self._h, _p(start), _p(kf), _p(lv), _p(bad), _p(ref_kf), _p(ref_level), _p(pos), _p(centre)))
+        assert int(start[-1]) == N
+        return dict(table=M.ObservationTable.from_arrays(k, start, kf[:N], lv[:N], bad[:n]), ref_kf=ref_kf[:n], ref_level=ref_level[:n], pos=pos[:n],
+                    centre=centre[:k])
+
+
+class _Header:
+    """What map_maintenance's wrappers read of a table, answered once per call from the handle."""
+
+    def __init__(self, db):
+        self.n_keyframes, self.struct, self._db = db.n_keyframes, C.c_int(0), db
+
+    def span_lengths(self):
+        return self._db.span_lengths()
