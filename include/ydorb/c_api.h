@@ -1055,6 +1055,68 @@ int ydorb_mapdb_stats(ydorb_mapdb_t* db, YdMapDbStats* stats);
 int ydorb_mapdb_export(ydorb_mapdb_t* db, int32_t* obs_start, int32_t* obs_kf, uint8_t* obs_level, uint8_t* bad, int32_t* ref_kf,
                        uint8_t* ref_level, float* pos, float* centre);
 
+/* Map correction (DESIGN.md section 2 "Map correction", section 6n): the three loops of LoopClosing that move map points through a
+ * pair of per-keyframe transforms, run on the resident table in place.  Only per-keyframe tables go up; the new positions (and, when
+ * asked for, normals and distances) come back, and the table - device and host mirror - holds them afterwards.  The reference source
+ * is absent from this repository; the loops are restated from ORB-SLAM2:
+ *   A  LoopClosing::correctLoop: for every keyframe of CorrectedSim3 in the container's order, every map point of
+ *      getMapPointMatches() that is not null, not bad and not yet marked mnCorrectedByKF gets
+ *      P' = float(correctedSwi.map(Siw.map(double(P)))), setWorldPos, the mark, and updateNormalAndDepth() at once; the keyframe's
+ *      own setPose follows its points, so the normals see the new centres of the keyframes before it only.
+ *      One call: SIM3 + INTERLEAVED, the entries = the keyframes' lists concatenated, corrector = the list's rank.
+ *   B  the tail of Optimizer::optimizeEssentialGraph: all poses are set, then every non-bad point gets
+ *      P' = float(correctedSwr.map(Srw.map(double(P)))) with r = mnCorrectedReference where loop A corrected the point, else its
+ *      reference keyframe, and updateNormalAndDepth().  One call: SIM3 + POSES_FIRST, slots NULL, corrector = that rank or -1.
+ *   C  the map update of LoopClosing::runGlobalBundleAdjust: a point the BA held takes mPosGBA (ydorb_mapdb_set_positions); every
+ *      other point whose reference keyframe was reached gets Xc = Rcw_bef P + tcw_bef (mTcwBefGBA), P' = Rwc Xc + twc
+ *      (getPoseInverse() after the update) in CV_32F, and no updateNormalAndDepth.  One call: SE3, no normals, -1 correctors with
+ *      the reached keyframes in kf_slots (the others come back NOT_COVERED).  The spanning-tree propagation stays with the caller.
+ * Assumptions for a maintainer who holds the reference to check: the marks (mnCorrectedByKF, mnCorrectedReference) have no other
+ * reader inside the loops; setWorldPos stores the float matrix it is given; the CV_32F products of loop C are OpenCV's gemm (each
+ * product exact in double, summed in ascending index with the addend, rounded once); Sim3::map is s * (r * xyz) + t in double;
+ * the camera centre after a pose change is what setPose computes (-Rcw^T tcw), which the caller passes as centre_after.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG naming the first offender before any device work, stages nothing and changes
+ * nothing: null arrays the mode needs, a point slot outside 0..n_points-1, a keyframe slot outside 0..n_keyframes-1 or repeated, a
+ * corrector outside -1..n_kf-1, n != n_points with null slots, a non-positive or non-finite Sim3 scale, n_levels outside 1..8,
+ * ref_level >= n_levels for a point whose normals are computed, an unknown arithmetic or centres value, a centres rule without
+ * centre_after.
+ * ---------------------------------------------------------------------------------------- */
+#define YDORB_MAPCORR_SIM3 0          /* before / after: double [n_kf][8], qx qy qz qw tx ty tz s as in YdEssentialGraph::sim3 */
+#define YDORB_MAPCORR_SE3 1           /* before / after: float [n_kf][12], a row-major 3x3 followed by the translation */
+#define YDORB_MAPCORR_RESIDENT 0      /* every observer shows the centre the table held when the call began */
+#define YDORB_MAPCORR_INTERLEAVED 1   /* an observer whose rank in kf_slots is below the correcting keyframe's shows its centre_after */
+#define YDORB_MAPCORR_POSES_FIRST 2   /* every keyframe of the call shows its centre_after */
+/* status byte of an entry: the first that matches, in this order */
+#define YDORB_MAPCORR_BAD 1           /* the resident bad flag is set (a slot never set included): isBad() */
+#define YDORB_MAPCORR_CLAIMED 2       /* an earlier entry of this call that was not bad named the slot: mnCorrectedByKF */
+#define YDORB_MAPCORR_NOT_COVERED 3   /* corrector -1 and the resident ref_kf is not among kf_slots */
+#define YDORB_MAPCORR_DONE 0          /* the position is corrected and, when asked for, the normals are recomputed */
+#define YDORB_MAPCORR_DONE_NO_OBSERVATIONS 4   /* corrected; the span is empty, the normals stay zero (the reference's early return) */
+typedef struct YdMapCorrection {
+  int32_t n_kf;                /* keyframes of the call */
+  int32_t arithmetic;          /* YDORB_MAPCORR_SIM3 / _SE3 */
+  const int32_t* kf_slots;     /* [n_kf] distinct keyframe slots in the caller's order (loop A: the iteration order of CorrectedSim3) */
+  const void* before;          /* SIM3: Siw as it was (g2oSiw / Srw).  SE3: Rcw | tcw of the pose before (mTcwBefGBA) */
+  const void* after;           /* SIM3: the corrected Siw (g2oCorrectedSiw); the entry inverts it.  SE3: Rwc | twc of getPoseInverse() after */
+  const float* centre_after;   /* [n_kf][3] the camera centres after the correction, or NULL.  When given the table holds them once the
+                                  call returns (what setPose leaves in getCameraCenter()) */
+  int32_t centres;             /* YDORB_MAPCORR_RESIDENT / _INTERLEAVED / _POSES_FIRST: which centres the normals see */
+  int32_t n;                   /* entries */
+  const int32_t* slots;        /* [n] point slots; NULL with n == n_points: every slot 0 .. n_points-1 in order */
+  const int32_t* corrector;    /* [n] the index into kf_slots of the keyframe that corrects the entry, -1 = the point's resident ref_kf;
+                                  NULL: all -1 */
+  const float* scale_factors;  /* [n_levels], as in ydorb_mapdb_update_normal_depth; not read when no normals are asked for */
+  int32_t n_levels;
+  int32_t reserved;            /* 0 */
+  float* normal;               /* [n][3] \                                                                         */
+  float* min_distance;         /* [n]     > updateNormalAndDepth() with the new position; all three NULL: no normals pass */
+  float* max_distance;         /* [n]    /                                                                         */
+  float* pos_out;              /* [n][3] the corrected position, the floats the table now holds */
+  uint8_t* status;             /* [n] YDORB_MAPCORR_*; an entry that is not DONE* has zero rows and leaves the table alone */
+} YdMapCorrection;
+/* Applies what is staged, then corrects.  n == 0 still writes the centres.  Holds the handle's mutex. */
+int ydorb_mapdb_correct(ydorb_mapdb_t* db, const YdMapCorrection* correction);
+
 #ifdef __cplusplus
 }
 #endif

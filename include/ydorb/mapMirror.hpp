@@ -10,7 +10,12 @@
 // three queries flush first and then walk only the keyframes' map-point vectors, never the observation maps.  A missed touch does not
 // fail: results then differ from the reference's, and verify() names the slot.
 // One thread at a time per MapMirror (the handle below it has its own mutex; the pointer maps here do not).
-// Assumed spellings: those of mapPoint.hpp, keyFrame.hpp and localMapping.hpp.
+// correctLoopPoints, correctAfterEssentialGraph and correctAfterGlobalBA run the point loops of loop closing on the table in place
+// (DESIGN.md section 6n); their comments below state what each takes from the caller.
+// Assumed spellings: those of mapPoint.hpp, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
+// MapPoint::setPosInWorld(cv::Mat), m_int_correctedByKeyFrameID, m_int_correctedReference and the Sim3 members rotation().x() .. w(),
+// translation()[k], scale().  The camera centre after a corrected pose is not read from a member: correctLoopPoints computes it from
+// the corrected Sim3 as setPose would (see there), correctAfterEssentialGraph reads getCameraOriginInWorld() after the caller's setPose.
 #ifndef YDORB_ADAPTER_MAPMIRROR_HPP
 #define YDORB_ADAPTER_MAPMIRROR_HPP
 
@@ -220,6 +225,104 @@ class MapMirror {
     return flagged;
   }
 
+  // ------------------------------------------------------------------------------------------------------------ map correction
+  // The three point loops of loop closing over ydorb_mapdb_correct (c_api.h "Map correction"): the positions are
+  // corrected where the table lives and come back once.  Each method flushes, walks only the keyframes' map-point vectors or the
+  // caller's point list, makes one call, and for every corrected point, in order,
+  //   - hands the new position to the container's own setter (setPosInWorld): the floats the device holds, so verify() stays empty
+  //     without a touchPosition;
+  //   - calls apply(mp, pos, normal, minDistance, maxDistance) (3x1 CV_32F matrices), where the caller stores the normal and the
+  //     distances as updateNormalAndDepth would; `normal` is an empty cv::Mat where the reference's updateNormalAndDepth returns
+  //     early (no observations) and in correctAfterGlobalBA, which computes none.
+  // Each returns the number of corrected points.  The keyframes' poses stay with the caller, as in the reference.
+  //
+  // correctLoopPoints: the point loop of LoopClosing::correctLoop.  correctedSim3 / nonCorrectedSim3 = KeyFrameAndPose maps (any
+  // Sim3T read through rotation().x() .. w(), translation()[k], scale(), as in optimizer.hpp).  The marks are set here:
+  // m_int_correctedByKeyFrameID = currentKF's id, m_int_correctedReference = the correcting keyframe's id; a point that already
+  // carries currentKF's mark is skipped.  The centre each keyframe shows after its setPose is computed here from its corrected Sim3
+  // the way the reference builds correctedTiw and setPose its origin: R = rotation().toRotationMatrix() and t = translation() * (1. / s)
+  // in double, both converted to float, Ow = -Rcw^T tcw as one CV_32F product (exact products summed in double in ascending index,
+  // rounded once).  The caller still calls setPose on each keyframe (after this method or before: the table does not read it); if its
+  // origin differs from the one computed here, verify() names the keyframe and touch(kf) mends it.
+  template <class PoseMap, class Apply>
+  int correctLoopPoints(const PoseMap& correctedSim3, const PoseMap& nonCorrectedSim3, const KeyFramePtr& currentKF, Apply apply) {
+    Correction c;
+    c.sim3 = true;
+    for (const auto& kv : correctedSim3) {   // the container's own order
+      const KeyFramePtr& kf = kv.first;
+      const int32_t rank = (int32_t)c.kfSlots.size();
+      c.kfs.push_back(kf);
+      c.kfSlots.push_back(kfSlotFor(kf));
+      pushSim3(c.after, kv.second);
+      pushSim3(c.before, nonCorrectedSim3.at(kf));
+      float O[3];
+      originOfSim3(kv.second, O);
+      c.centreAfter.insert(c.centreAfter.end(), O, O + 3);
+      for (const MapPointPtr& mp : kf->getMapPointMatches()) {
+        if (!mp) continue;
+        if (mp->m_int_correctedByKeyFrameID == currentKF->m_int_keyFrameID) continue;
+        c.points.push_back(mp); c.slots.push_back(known(mp)); c.corrector.push_back(rank);
+      }
+    }
+    return run(c, YDORB_MAPCORR_INTERLEAVED, true, [&](const MapPointPtr& mp, int32_t rank) {
+      mp->m_int_correctedByKeyFrameID = currentKF->m_int_keyFrameID;
+      mp->m_int_correctedReference = c.kfs[(size_t)rank]->m_int_keyFrameID;
+    }, apply);
+  }
+
+  // The tail of Optimizer::optimizeEssentialGraph, after every keyframe's setPose: keyFrames = the keyframes with a vertex, points = the
+  // map's points; scwBefore(kf) / scwAfter(kf) return the keyframe's Sim3 before the optimisation (vScw) and the optimised one
+  // (vCorrectedSwc's inverse: the entry inverts it).  A point marked by currentKF's correctLoop is corrected by the keyframe whose id is
+  // its m_int_correctedReference, every other by its reference keyframe.  The centres are read from the keyframes: getCameraOriginInWorld().
+  template <class KeyFrames, class Points, class Before, class After, class Apply>
+  int correctAfterEssentialGraph(const KeyFrames& keyFrames, const Points& points, const KeyFramePtr& currentKF, Before scwBefore, After scwAfter,
+                                 Apply apply) {
+    Correction c;
+    c.sim3 = true;
+    std::map<long, int32_t> rankOfId;
+    for (const KeyFramePtr& kf : keyFrames) {
+      rankOfId[(long)kf->m_int_keyFrameID] = (int32_t)c.kfSlots.size();
+      c.kfs.push_back(kf);
+      c.kfSlots.push_back(kfSlotFor(kf));
+      pushSim3(c.before, scwBefore(kf));
+      pushSim3(c.after, scwAfter(kf));
+      const cv::Mat O = kf->getCameraOriginInWorld();
+      for (int r = 0; r < 3; r++) c.centreAfter.push_back(O.template at<float>(r));
+    }
+    for (const MapPointPtr& mp : points) {
+      if (!mp) continue;
+      int32_t rank = -1;
+      if (mp->m_int_correctedByKeyFrameID == currentKF->m_int_keyFrameID) {
+        const auto it = rankOfId.find((long)mp->m_int_correctedReference);
+        if (it == rankOfId.end()) continue;   // its corrector has no vertex: left alone (optimizer.hpp does the same)
+        rank = it->second;
+      }
+      c.points.push_back(mp); c.slots.push_back(known(mp)); c.corrector.push_back(rank);
+    }
+    return run(c, YDORB_MAPCORR_POSES_FIRST, true, [](const MapPointPtr&, int32_t) {}, apply);
+  }
+
+  // The map update of LoopClosing::runGlobalBundleAdjust for the points the BA did not hold (those take mPosGBA: setPosInWorld and
+  // touchPosition, as before).  keyFrames = the keyframes the spanning-tree propagation reached (it stays with the caller); points = the
+  // other points; poseBefore(kf) = Tcw before (mTcwBefGBA), poseInverseAfter(kf) = Twc after (getPoseInverse()), 4x4 CV_32F.  A point
+  // whose reference keyframe is not among keyFrames is skipped, as in the reference.
+  template <class KeyFrames, class Points, class PoseBefore, class PoseInverseAfter, class Apply>
+  int correctAfterGlobalBA(const KeyFrames& keyFrames, const Points& points, PoseBefore poseBefore, PoseInverseAfter poseInverseAfter, Apply apply) {
+    Correction c;
+    c.sim3 = false;
+    for (const KeyFramePtr& kf : keyFrames) {
+      c.kfs.push_back(kf);
+      c.kfSlots.push_back(kfSlotFor(kf));
+      pushSE3(c.beforeF, poseBefore(kf));
+      pushSE3(c.afterF, poseInverseAfter(kf));
+    }
+    for (const MapPointPtr& mp : points) {
+      if (!mp) continue;
+      c.points.push_back(mp); c.slots.push_back(known(mp)); c.corrector.push_back(-1);
+    }
+    return run(c, YDORB_MAPCORR_RESIDENT, false, [](const MapPointPtr&, int32_t) {}, apply);
+  }
+
   struct Difference {
     std::vector<int32_t> pointSlots, keyFrameSlots;
     bool empty() const { return pointSlots.empty() && keyFrameSlots.empty(); }
@@ -266,6 +369,76 @@ class MapMirror {
     int32_t refKf = 0;
     float pos[3] = {0.f, 0.f, 0.f};
   };
+
+  struct Correction {   // the arrays of one ydorb_mapdb_correct call, built by the three correction methods
+    bool sim3 = true;
+    std::vector<KeyFramePtr> kfs;
+    std::vector<int32_t> kfSlots, slots, corrector;
+    std::vector<double> before, after;       // Sim3
+    std::vector<float> beforeF, afterF;      // SE3
+    std::vector<float> centreAfter;
+    std::vector<MapPointPtr> points;
+  };
+  template <class Sim3T>
+  static void pushSim3(std::vector<double>& to, const Sim3T& S) {
+    const double v[8] = {S.rotation().x(), S.rotation().y(), S.rotation().z(), S.rotation().w(), S.translation()[0], S.translation()[1],
+                         S.translation()[2], S.scale()};
+    to.insert(to.end(), v, v + 8);
+  }
+  static void pushSE3(std::vector<float>& to, const cv::Mat& T) {   // rows 0..2 of a 4x4 CV_32F: the 3x3 row-major, then the translation
+    for (int r = 0; r < 3; r++) for (int col = 0; col < 3; col++) to.push_back(T.template at<float>(r, col));
+    for (int r = 0; r < 3; r++) to.push_back(T.template at<float>(r, 3));
+  }
+  // The origin setPose leaves for correctedTiw = [R | t / s] of a corrected Sim3 (see correctLoopPoints)
+  template <class Sim3T>
+  static void originOfSim3(const Sim3T& S, float* O) {
+    const double x = S.rotation().x(), y = S.rotation().y(), z = S.rotation().z(), w = S.rotation().w();
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y,
+                 tyz = tz * y, tzz = tz * z;   // Eigen's toRotationMatrix
+    const float R[3][3] = {{(float)(1 - (tyy + tzz)), (float)(txy - twz), (float)(txz + twy)},
+                           {(float)(txy + twz), (float)(1 - (txx + tzz)), (float)(tyz - twx)},
+                           {(float)(txz - twy), (float)(tyz + twx), (float)(1 - (txx + tyy))}};
+    const double inv = 1. / S.scale();
+    const float t[3] = {(float)(S.translation()[0] * inv), (float)(S.translation()[1] * inv), (float)(S.translation()[2] * inv)};
+    for (int i = 0; i < 3; i++)
+      O[i] = (float)-(((double)R[0][i] * (double)t[0] + (double)R[1][i] * (double)t[1]) + (double)R[2][i] * (double)t[2]);
+  }
+  template <class Mark, class Apply>
+  int run(Correction& c, int32_t centres, bool normals, Mark markPoint, Apply apply) {
+    flush();
+    const size_t n = c.slots.size();
+    const std::vector<float> sf = scaleFactors();
+    std::vector<float> pos(3 * n + 3), normal(3 * n + 3), minD(n + 1), maxD(n + 1);
+    std::vector<uint8_t> status(n + 1);
+    YdMapCorrection m;
+    std::memset(&m, 0, sizeof(m));
+    m.n_kf = (int32_t)c.kfSlots.size(); m.kf_slots = c.kfSlots.data();
+    m.arithmetic = c.sim3 ? YDORB_MAPCORR_SIM3 : YDORB_MAPCORR_SE3;
+    m.before = c.sim3 ? (const void*)c.before.data() : (const void*)c.beforeF.data();
+    m.after = c.sim3 ? (const void*)c.after.data() : (const void*)c.afterF.data();
+    m.centre_after = c.centreAfter.empty() ? nullptr : c.centreAfter.data();
+    m.centres = m.centre_after ? centres : YDORB_MAPCORR_RESIDENT;
+    if (n > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX correction entries");
+    m.n = (int32_t)n; m.slots = c.slots.data(); m.corrector = c.corrector.data();
+    if (normals) { m.scale_factors = sf.data(); m.n_levels = (int32_t)sf.size(); m.normal = normal.data(); m.min_distance = minD.data(); m.max_distance = maxD.data(); }
+    m.pos_out = pos.data(); m.status = status.data();
+    mapCheck(ydorb_mapdb_correct(db_, &m));
+    int corrected = 0;
+    for (size_t i = 0; i < n; i++) {
+      if (status[i] != YDORB_MAPCORR_DONE && status[i] != YDORB_MAPCORR_DONE_NO_OBSERVATIONS) continue;
+      cv::Mat P(3, 1, CV_32F), nrm;
+      for (int r = 0; r < 3; r++) P.template at<float>(r) = pos[3 * i + r];
+      if (normals && status[i] == YDORB_MAPCORR_DONE) {
+        nrm = cv::Mat(3, 1, CV_32F);
+        for (int r = 0; r < 3; r++) nrm.template at<float>(r) = normal[3 * i + r];
+      }
+      c.points[i]->setPosInWorld(P);
+      if (c.corrector[i] >= 0) markPoint(c.points[i], c.corrector[i]);
+      apply(c.points[i], P, nrm, minD[i], maxD[i]);
+      corrected++;
+    }
+    return corrected;
+  }
 
   static void mark(std::vector<uint8_t>& state, std::vector<int32_t>& list, int32_t s, uint8_t how) {
     if (state[s] == kClean) list.push_back(s);

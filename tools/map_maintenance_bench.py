@@ -16,6 +16,9 @@ redundancy calls for the local window's lists; outputs are compared exactly befo
 spare pool room, each time one query that has to repack: the map-size table, and 20 000 points of 300 observers.  It ends with tests/cpp_host/mapdb_run.cpp
 on local-size stand-ins: the three adapters through MapMirror beside the flattening adapters, and the price of a flush.  The kernels
 k_mapdb_apply / k_mapdb_repack: `rocprofv3 --kernel-trace --stats -- python tools/map_maintenance_bench.py --resident --reps 5`.
+--correct times the map correction on the resident table (ydorb_mapdb_correct) beside the route it replaces, for
+the three loops of loop closing; see bench_correct.  Its kernels k_mapdb_correct / k_mapdb_correct_centres: the same rocprofv3 line
+with --correct.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -304,6 +307,121 @@ def bench_resident(reps):
     return out
 
 
+def bench_correct(reps):
+    """ydorb_mapdb_correct against the route it replaces, alternating in one run on two handles that hold the same
+    map-size table: the restatement's host loop for the positions (tests/mapcorrect_ref, one thread, flat arrays), then
+    ydorb_mapdb_set_positions, ydorb_mapdb_set_centres and ydorb_mapdb_update_normal_depth.  Shape A: loop A on the 31-keyframe window;
+    B: loop B on the whole map; C: loop C on the whole map (no normals; the old route's staged positions are landed by a one-point
+    query).  The transforms are small, so that the repetitions do not carry the map away.  With complete map-point lists no point of loop A
+    has an observer before its corrector, so the old route reproduces A's normals by asking for them before it sets the centres."""
+    import mapcorrect_support as K
+    from ydorbslam_amd.map_resident import correction
+    n_kf, n_points, window = SIZES["map"]
+    L, R = y.lib(), K.ref()
+    d = make_map(n_kf, n_points, window)
+    T, sf = d["T"], S.scale_factors()
+    out = dict(keyframes=n_kf, points=n_points, observations=d["n_obs"])
+    all_slots, kf_all = np.arange(n_points, dtype=np.int32), np.arange(n_kf, dtype=np.int32)
+    hs = []
+    for _ in range(2):
+        h = C.c_void_p()
+        y._lib.check(L.ydorb_mapdb_create(0, n_points, n_kf, d["n_obs"] + 1000, C.byref(h)))
+        assert L.ydorb_mapdb_set_centres(h, p(kf_all), n_kf, p(d["centre"])) == 0
+        assert L.ydorb_mapdb_set_points(h, p(all_slots), n_points, p(T.obs_start), p(T.obs_kf), p(T.obs_level), p(T.bad), p(d["ref_kf"]), p(d["ref_level"]), p(d["pos"])) == 0
+        hs.append(h)
+    new, old = hs
+    rng = np.random.default_rng(7)
+
+    def small_sim3(k):
+        before, _ = K.sim3_pairs(11, k)
+        after = before.copy()
+        after[:, :4] += rng.uniform(-1e-3, 1e-3, (k, 4))
+        after[:, :4] /= np.linalg.norm(after[:, :4], axis=1, keepdims=True)
+        after[:, 4:7] += rng.uniform(-1e-2, 1e-2, (k, 3))
+        after[:, 7] = rng.uniform(0.999, 1.001, k)
+        return before, after
+
+    k0 = n_kf // 2
+    win = np.arange(k0, k0 + window, dtype=np.int32)
+    a_slots = np.concatenate([d["kf_points"][d["kf_start"][k]:d["kf_start"][k + 1]] for k in win]).astype(np.int32)
+    a_corr = np.concatenate([np.full(d["kf_start"][k + 1] - d["kf_start"][k], r, np.int32) for r, k in enumerate(win)])
+    ba, aa = small_sim3(window)
+    bb, ab = small_sim3(n_kf)
+    reached = np.setdiff1d(kf_all, kf_all[::50]).astype(np.int32)
+    bc, ac = K.se3_pairs(5, len(reached))
+    for i in range(len(reached)):                                  # after = the inverse of before, moved a little: the map stays in place
+        Rcw, tcw = bc[i, :9].reshape(3, 3).astype(np.float64), bc[i, 9:].astype(np.float64)
+        ac[i, :9], ac[i, 9:] = Rcw.T.reshape(-1), -Rcw.T @ tcw + rng.uniform(-1e-2, 1e-2, 3)
+    cen = lambda kfs, s: (d["centre"][kfs] + np.random.default_rng(s).uniform(-0.05, 0.05, (len(kfs), 3))).astype(np.float32)
+    shapes = dict(
+        A=dict(kf_slots=win, before=ba, after=aa, slots=a_slots, corrector=a_corr, arithmetic="sim3", centre_after=cen(win, 1), centres="interleaved", scale_factors=sf),
+        B=dict(kf_slots=kf_all, before=bb, after=ab, slots=None, corrector=None, arithmetic="sim3", centre_after=cen(kf_all, 2), centres="poses_first", scale_factors=sf),
+        C=dict(kf_slots=reached, before=bc, after=ac, slots=None, corrector=None, arithmetic="se3", centre_after=None, centres="resident", scale_factors=None))
+    flat = dict(table=T, pos=d["pos"].copy(), centre=d["centre"].copy(), ref_kf=d["ref_kf"], ref_level=d["ref_level"])
+    one = np.zeros(1, np.int32)
+    one_out = [np.zeros((1, 3), np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.uint8)]
+    for name, args in shapes.items():
+        corr, res, _keep = correction(args["kf_slots"], args["before"], args["after"], n_points if args["slots"] is None else None, args["slots"],
+                                      args["corrector"], args["arithmetic"], args["centre_after"], args["centres"], args["scale_factors"])
+        # the old route's host loop: the same call without normals, on the flat arrays
+        hcorr, hres, _hkeep = correction(args["kf_slots"], args["before"], args["after"], n_points if args["slots"] is None else None, args["slots"],
+                                         args["corrector"], args["arithmetic"], args["centre_after"], "resident", None)
+        n = len(res["status"])
+        slots = all_slots if args["slots"] is None else args["slots"]
+        nd = [np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)]
+        K_ = len(args["kf_slots"])
+
+        def new_route():
+            assert L.ydorb_mapdb_correct(new, C.byref(corr)) == 0, L.ydorb_last_error()
+
+        def old_route():
+            assert R.mapcorrect_ref(C.byref(T.struct), p(flat["pos"]), p(flat["centre"]), p(flat["ref_kf"]), p(flat["ref_level"]), C.byref(hcorr)) == 0
+            done = np.flatnonzero((hres["status"] == 0) | (hres["status"] == 4))
+            moved = np.ascontiguousarray(slots[done])
+            moved_pos = np.ascontiguousarray(hres["pos"][done])
+            if name == "B":
+                assert L.ydorb_mapdb_set_centres(old, p(args["kf_slots"]), K_, p(args["centre_after"])) == 0
+            assert L.ydorb_mapdb_set_positions(old, p(moved), len(moved), p(moved_pos)) == 0
+            if name == "C":
+                assert L.ydorb_mapdb_update_normal_depth(old, p(one), 1, p(sf), 8, *[p(a) for a in one_out]) == 0
+                return done
+            assert L.ydorb_mapdb_update_normal_depth(old, p(slots), n, p(sf), 8, *[p(a) for a in nd]) == 0, L.ydorb_last_error()
+            if name == "A":
+                assert L.ydorb_mapdb_set_centres(old, p(args["kf_slots"]), K_, p(args["centre_after"])) == 0
+            return done
+
+        tn, to = [], []
+        for r in range(reps + 1):
+            t0 = time.perf_counter(); new_route(); t1 = time.perf_counter(); done = old_route(); t2 = time.perf_counter()
+            if r == 0:                                             # the two routes agree exactly before anything is timed
+                assert np.array_equal(res["pos"].view(np.uint32), hres["pos"].view(np.uint32)), name
+                if name != "C":
+                    for k, a in zip(("normal", "min_distance", "max_distance"), nd):
+                        assert np.array_equal(res[k][done].view(np.uint32), a[done].view(np.uint32)), (name, k)
+            else:
+                tn.append(t1 - t0); to.append(t2 - t1)
+        nc = int(len(done))
+        per_kf = 64 if args["arithmetic"] == "sim3" else 48
+        up = 2 * per_kf * K_ + 4 * n_kf + 4 * K_ + (12 * K_ if args["centre_after"] is not None else 0) + 8 * nc
+        down = nc * (13 + (20 if args["scale_factors"] is not None else 0))
+        old_up = 16 * nc + (16 * K_ if args["centre_after"] is not None else 0) + (4 * n if name != "C" else 4)
+        old_down = 21 * n if name != "C" else 21
+        out[name] = dict(entries=int(n), corrected=nc, keyframes=K_, correct_ms=stat(tn), previous_route_ms=stat(to), correct_bytes_up=up, correct_bytes_down=down,
+                         previous_route_bytes_up=old_up, previous_route_bytes_down=old_down)
+    ex = []
+    for h in hs:                                                   # and the two tables ended up the same
+        pos, centre = np.zeros((n_points, 3), np.float32), np.zeros((n_kf, 3), np.float32)
+        st, kf, lv = np.zeros(n_points + 1, np.int32), np.zeros(d["n_obs"], np.int32), np.zeros(d["n_obs"], np.uint8)
+        bad, rk, rl = np.zeros(n_points, np.uint8), np.zeros(n_points, np.int32), np.zeros(n_points, np.uint8)
+        assert L.ydorb_mapdb_export(h, p(st), p(kf), p(lv), p(bad), p(rk), p(rl), p(pos), p(centre)) == 0
+        ex.append((pos, centre))
+        L.ydorb_mapdb_destroy(h)
+    out["tables_equal_afterwards"] = bool(np.array_equal(ex[0][0].view(np.uint32), ex[1][0].view(np.uint32)) and
+                                          np.array_equal(ex[0][1].view(np.uint32), ex[1][1].view(np.uint32)))
+    assert out["tables_equal_afterwards"]
+    return out
+
+
 def flatten_times():
     """Host time of the adapters' three flattenings on stand-ins at the local size (31 keyframes, 7 750 points)."""
     m = S.random_map(5, 31, 7750, 4, 8, level_spread=1)
@@ -321,7 +439,13 @@ def main():
     ap.add_argument("--flatten", action="store_true")
     ap.add_argument("--resident", action="store_true", help="time the resident map table (ydorb_mapdb_*) beside the flat entries instead")
     ap.add_argument("--kernel-ms", action="append", default=[], help="SIZE=MS: k_normal_depth's time from a kernel trace, for the bytes-per-second figure")
+    ap.add_argument("--correct", action="store_true", help="time ydorb_mapdb_correct beside the route it replaces instead")
     a = ap.parse_args()
+    if a.correct:
+        res = bench_correct(a.reps)
+        M.release()
+        print(json.dumps(res))
+        return
     if a.resident:
         res = bench_resident(a.reps)
         M.release()

@@ -134,6 +134,7 @@ SYMBOLS = {
     "ydorb_mapdb_keyframe_redundancy": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "ydorb_mapdb_stats": (C.c_int, [_VP, _VP]),
     "ydorb_mapdb_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_correct": (C.c_int, [_VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -222,6 +223,12 @@ class YdMapDbStats(C.Structure):
     _fields_ = [("n_points", _I), ("n_keyframes", _I), ("n_observations", C.c_int64), ("pool_used", C.c_int64), ("pool_capacity", C.c_int64),
                 ("repacks_kept", _I), ("repacks_grown", _I), ("point_table_growths", _I), ("keyframe_table_growths", _I),
                 ("point_capacity", _I), ("keyframe_capacity", _I), ("last_sync_bytes", C.c_int64), ("last_sync_records", C.c_int64)]
+
+
+class YdMapCorrection(C.Structure):
+    _fields_ = [("n_kf", _I), ("arithmetic", _I), ("kf_slots", _VP), ("before", _VP), ("after", _VP), ("centre_after", _VP), ("centres", _I),
+                ("n", _I), ("slots", _VP), ("corrector", _VP), ("scale_factors", _VP), ("n_levels", _I), ("reserved", _I), ("normal", _VP),
+                ("min_distance", _VP), ("max_distance", _VP), ("pos_out", _VP), ("status", _VP)]
 
 
 class YdCamera(C.Structure):

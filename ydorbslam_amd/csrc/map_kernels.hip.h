@@ -60,6 +60,32 @@ __device__ __forceinline__ double norm3(float x, float y, float z) {
   return sqrt(((double)x * (double)x + (double)y * (double)y) + (double)z * (double)z);
 }
 
+struct NormalDepth { float nx, ny, nz, mn, mx; };
+
+// MapPoint::updateNormalAndDepth of one point with a non-empty span [b, e): position P, reference keyframe slot r at level lr.
+// centreOf(k) returns a pointer to the three floats of keyframe slot k's camera centre: the table's for k_normal_depth, the rule of
+// the map correction for k_mapdb_correct (mapcorrect_kernels.hip.h).  The one copy of the ordered sum.
+template <class CentreOf>
+__device__ __forceinline__ NormalDepth normalDepthOf(const int* obsKf, int b, int e, float Px, float Py, float Pz, int r, int lr,
+                                                     const float (&scaleFactors)[8], int nLevels, CentreOf centreOf) {
+  float nx = 0.f, ny = 0.f, nz = 0.f;
+  for (int q = b; q < e; q++) {
+    const float* c = centreOf(obsKf[q]);
+    const float dx = Px - c[0], dy = Py - c[1], dz = Pz - c[2];
+    const float inv = (float)(1.0 / norm3(dx, dy, dz));
+    nx = nx + dx * inv; ny = ny + dy * inv; nz = nz + dz * inv;
+  }
+  const float f = (float)(1.0 / (double)(e - b));
+  nx = nx * f; ny = ny * f; nz = nz * f;
+  const float* cr = centreOf(r);
+  const float dist = (float)norm3(Px - cr[0], Py - cr[1], Pz - cr[2]);
+  float sfRef = scaleFactors[0], sfTop = scaleFactors[0];
+#pragma unroll
+  for (int i = 1; i < 8; i++) { sfRef = lr == i ? scaleFactors[i] : sfRef; sfTop = nLevels - 1 == i ? scaleFactors[i] : sfTop; }
+  const float mx = dist * sfRef;
+  return {nx, ny, nz, mx / sfTop, mx};
+}
+
 static __global__ __launch_bounds__(kThreads) void k_normal_depth(NormalArgs g) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= g.n) return;
@@ -70,23 +96,10 @@ static __global__ __launch_bounds__(kThreads) void k_normal_depth(NormalArgs g) 
   if (g.t.bad[p]) code = YDORB_MAP_BAD;
   else if (b == e) code = YDORB_MAP_NO_OBSERVATIONS;
   else {
-    const float Px = g.pos[3 * p], Py = g.pos[3 * p + 1], Pz = g.pos[3 * p + 2];
-    for (int q = b; q < e; q++) {
-      const int k = g.t.obsKf[q];
-      const float dx = Px - g.centre[3 * k], dy = Py - g.centre[3 * k + 1], dz = Pz - g.centre[3 * k + 2];
-      const float inv = (float)(1.0 / norm3(dx, dy, dz));
-      nx = nx + dx * inv; ny = ny + dy * inv; nz = nz + dz * inv;
-    }
-    const float f = (float)(1.0 / (double)(e - b));
-    nx = nx * f; ny = ny * f; nz = nz * f;
-    const int r = g.refKf[p];
-    const float dist = (float)norm3(Px - g.centre[3 * r], Py - g.centre[3 * r + 1], Pz - g.centre[3 * r + 2]);
-    float sfRef = g.scaleFactors[0], sfTop = g.scaleFactors[0];
-    const int lr = g.refLevel[p];
-#pragma unroll
-    for (int i = 1; i < 8; i++) { sfRef = lr == i ? g.scaleFactors[i] : sfRef; sfTop = g.nLevels - 1 == i ? g.scaleFactors[i] : sfTop; }
-    mx = dist * sfRef;
-    mn = mx / sfTop;
+    const float* centre = g.centre;
+    const NormalDepth nd = normalDepthOf(g.t.obsKf, b, e, g.pos[3 * p], g.pos[3 * p + 1], g.pos[3 * p + 2], g.refKf[p], g.refLevel[p], g.scaleFactors,
+                                         g.nLevels, [centre](int k) { return centre + 3 * k; });
+    nx = nd.nx; ny = nd.ny; nz = nd.nz; mn = nd.mn; mx = nd.mx;
   }
   g.normal[3 * i] = nx; g.normal[3 * i + 1] = ny; g.normal[3 * i + 2] = nz;
   g.minDistance[i] = mn; g.maxDistance[i] = mx;

@@ -3,6 +3,7 @@
 // and plans.  The set_* entries only stage.  A query, on the handle's one stream: if anything is staged, one upload of the packed delta,
 // the table growths (device-to-device copies), k_mapdb_repack if the pool needs it and k_mapdb_apply; then the query's own arrays in one
 // upload, the pass of map_kernels.hip.h, one read-back and one synchronise.  With nothing staged no table byte moves.
+// ydorb_mapdb_correct (mapcorrect_kernels.hip.h) is the one query that writes the table: positions in place, then centres.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -14,6 +15,7 @@
 #include "host_buffers.h"
 #include "map_kernels.hip.h"
 #include "map_table.h"
+#include "mapcorrect_kernels.hip.h"
 #include "mapdb_host.h"
 #include "mapdb_kernels.hip.h"
 #include "ydorb_host.h"
@@ -363,6 +365,82 @@ extern "C" int ydorb_mapdb_keyframe_redundancy(ydorb_mapdb_t* h, const int32_t* 
   std::memcpy(n_counted, at<void>(c.hDown, dCnt), 4 * nc);
   std::memcpy(n_redundant, at<void>(c.hDown, dRed), 4 * nc);
   for (size_t k = 0; k < nc; k++) cull[k] = maptable::cullVerdict(n_redundant[k], n_counted[k]);
+  return YDORB_OK;
+}
+
+// sync; one upload of the keyframe tables, the rank table, the claimed list and the centres; the pass; the centre write; one read-back;
+// one synchronise; the scatter to entry order.  Point positions travel only as results.
+extern "C" int ydorb_mapdb_correct(ydorb_mapdb_t* h, const YdMapCorrection* c) {
+  if (!h) {   // without a device no handle exists: say that first, there is no CPU path to fall back to
+    const int rc = require_device(0);
+    return rc ? rc : invalid("null handle");
+  }
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  mapdb::Host::CorrectionPlan P;
+  if (!h->host.planCorrection(c, P, err)) return invalid(err);
+  const size_t n = (size_t)c->n, nKf = (size_t)c->n_kf, nc = P.slot.size(), nk = (size_t)h->host.nKeyframes();
+  const bool writeCentres = c->centre_after && nKf > 0;
+  if (n == 0 && !writeCentres) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& ctx = h->c;
+  const size_t perKf = c->arithmetic == YDORB_MAPCORR_SIM3 ? 8 * sizeof(double) : 12 * sizeof(float);
+  const size_t pairBytes = nc ? perKf * nKf : 0;
+  Layout U;
+  const size_t oBefore = U.add(pairBytes), oAfter = U.add(pairBytes), oRankOf = U.add(4 * nk), oKf = U.add(4 * nKf),
+               oCen = U.add(c->centre_after ? 12 * nKf : 0), oSlot = U.add(4 * nc), oRank = U.add(4 * nc);
+  Layout D;
+  const size_t dPos = D.add(12 * nc), dNrm = D.add(P.normals ? 12 * nc : 0), dMin = D.add(P.normals ? 4 * nc : 0), dMax = D.add(P.normals ? 4 * nc : 0),
+               dSt = D.add(nc);
+  U.add(16); D.add(16);   // never an empty buffer
+  if ((rc = ensure(ctx, U, D))) return rc;
+  if (pairBytes) { std::memcpy(at<void>(ctx.hUp, oBefore), c->before, pairBytes); std::memcpy(at<void>(ctx.hUp, oAfter), c->after, pairBytes); }
+  if (nk) std::memcpy(at<void>(ctx.hUp, oRankOf), P.rankOf.data(), 4 * nk);
+  if (nKf) std::memcpy(at<void>(ctx.hUp, oKf), c->kf_slots, 4 * nKf);
+  if (writeCentres) std::memcpy(at<void>(ctx.hUp, oCen), c->centre_after, 12 * nKf);
+  if (nc) { std::memcpy(at<void>(ctx.hUp, oSlot), P.slot.data(), 4 * nc); std::memcpy(at<void>(ctx.hUp, oRank), P.rank.data(), 4 * nc); }
+  hipStream_t s = ctx.stream;
+  HIPCHK(hipMemcpyAsync(ctx.up.p, ctx.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  if (nc) {
+    mapcorrect::CorrectArgs a;
+    a.nClaimed = (int)nc; a.nKf = c->n_kf; a.arithmetic = c->arithmetic; a.centres = c->centres; a.normals = P.normals ? 1 : 0;
+    a.slot = at<int>(ctx.up, oSlot); a.rank = at<int>(ctx.up, oRank); a.rankOf = at<int>(ctx.up, oRankOf);
+    a.before = at<void>(ctx.up, oBefore); a.after = at<void>(ctx.up, oAfter); a.centreAfter = at<float>(ctx.up, oCen);
+    a.pos = h->T.pos; a.centre = h->T.centre; a.obsStart = h->T.start; a.obsEnd = h->T.end; a.obsKf = h->poolKf;
+    a.refKf = h->T.refKf; a.refLevel = h->T.refLevel;
+    for (int i = 0; i < 8; i++) a.scaleFactors[i] = P.normals && i < c->n_levels ? c->scale_factors[i] : 0.f;
+    a.nLevels = P.normals ? c->n_levels : 1;
+    a.posOut = at<float>(ctx.down, dPos); a.normal = at<float>(ctx.down, dNrm); a.minDistance = at<float>(ctx.down, dMin);
+    a.maxDistance = at<float>(ctx.down, dMax); a.status = at<uint8_t>(ctx.down, dSt);
+    hipLaunchKernelGGL(mapcorrect::k_mapdb_correct, dim3((unsigned)((nc + mapcorrect::kThreads - 1) / mapcorrect::kThreads)), dim3(mapcorrect::kThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (writeCentres) {   // after the pass: its lanes read the old centres
+    mapcorrect::CentreArgs a;
+    a.nKf = c->n_kf; a.kfSlots = at<int>(ctx.up, oKf); a.centreAfter = at<float>(ctx.up, oCen); a.centre = h->T.centre;
+    hipLaunchKernelGGL(mapcorrect::k_mapdb_correct_centres, dim3((unsigned)((nKf + mapcorrect::kThreads - 1) / mapcorrect::kThreads)), dim3(mapcorrect::kThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (nc) HIPCHK(hipMemcpyAsync(ctx.hDown.p, ctx.down.p, D.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  h->host.correctionApplied(c, P, at<float>(ctx.hDown, dPos));
+  if (n == 0) return YDORB_OK;
+  std::memset(c->pos_out, 0, 12 * n);
+  if (P.normals) { std::memset(c->normal, 0, 12 * n); std::memset(c->min_distance, 0, 4 * n); std::memset(c->max_distance, 0, 4 * n); }
+  std::memcpy(c->status, P.status.data(), n);
+  const float* hPos = at<float>(ctx.hDown, dPos);
+  const float* hNrm = at<float>(ctx.hDown, dNrm);
+  const float* hMin = at<float>(ctx.hDown, dMin);
+  const float* hMax = at<float>(ctx.hDown, dMax);
+  const uint8_t* hSt = at<uint8_t>(ctx.hDown, dSt);
+  for (size_t j = 0; j < nc; j++) {
+    const size_t i = (size_t)P.entry[j];
+    std::memcpy(c->pos_out + 3 * i, hPos + 3 * j, 12);
+    c->status[i] = hSt[j];
+    if (P.normals) { std::memcpy(c->normal + 3 * i, hNrm + 3 * j, 12); c->min_distance[i] = hMin[j]; c->max_distance[i] = hMax[j]; }
+  }
   return YDORB_OK;
 }
 

@@ -11,6 +11,8 @@
 //   pool      spans are appended at the tail; a replaced span becomes garbage.  When used + incoming > capacity the survivors are
 //             repacked in ascending slot order into a fresh arena: the same capacity when survivors + incoming <= capacity / 2, else
 //             min(2 x (survivors + incoming), INT32_MAX).  The host computes every survivor's new offset; the delta carries them.
+//   correct   ydorb_mapdb_correct's validation, keyframe rank table and claim pass (planCorrection), and what the mirror takes from the
+//             read-back (correctionApplied): DESIGN.md section 6n.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -201,6 +203,86 @@ class Host {
   // a table header for map_table.h's list checks: they read the two counts only
   YdObservationTable counts() const { return YdObservationTable{nPoints(), nKeyframes(), nullptr, nullptr, nullptr, nullptr}; }
 
+  // ------------------------------------------------------------------------------------------------------------- map correction
+  // ydorb_mapdb_correct.  planCorrection validates the call, builds the keyframe slot -> rank table and runs
+  // the claim pass over the entries in order: the mnCorrectedByKF rule, a stamp per slot.  It reads the mirror with the staged changes
+  // in it, which is what the device holds once the query's sync has run.  It writes only its plan and the stamps (scratch): a refused
+  // call changes neither mirror nor staging.  No two claimed entries share a slot, so the kernel never has two lanes writing one
+  // address.  Every status is final here but DONE against DONE_NO_OBSERVATIONS, which the kernel reports.
+  struct CorrectionPlan {
+    std::vector<int32_t> rankOf;               // [n_keyframes] rank in kf_slots, -1: not in the call
+    std::vector<uint8_t> status;               // [n]
+    std::vector<int32_t> entry, slot, rank;    // the claimed entries, in order
+    bool normals = false;
+  };
+  bool planCorrection(const YdMapCorrection* c, CorrectionPlan& P, std::string& err) {
+    if (!c) return fail(err, "null correction");
+    if (c->arithmetic != YDORB_MAPCORR_SIM3 && c->arithmetic != YDORB_MAPCORR_SE3) return fail(err, "unknown arithmetic %lld", c->arithmetic);
+    if (c->centres != YDORB_MAPCORR_RESIDENT && c->centres != YDORB_MAPCORR_INTERLEAVED && c->centres != YDORB_MAPCORR_POSES_FIRST)
+      return fail(err, "unknown centres rule %lld", c->centres);
+    if (c->n_kf < 0) return fail(err, "negative number of keyframe slots: %lld", c->n_kf);
+    if (c->n < 0) return fail(err, "negative number of entries: %lld", c->n);
+    if (c->centres != YDORB_MAPCORR_RESIDENT && !c->centre_after) return fail(err, "a centres rule without centre_after");
+    if (c->n_kf > 0 && !c->kf_slots) return fail(err, "null kf_slots");
+    if (c->n_kf > 0 && c->n > 0 && (!c->before || !c->after)) return fail(err, "null before or after");
+    if (c->n > 0 && (!c->pos_out || !c->status)) return fail(err, "null pos_out or status");
+    const int nrm = (c->normal ? 1 : 0) + (c->min_distance ? 1 : 0) + (c->max_distance ? 1 : 0);
+    if (nrm != 0 && nrm != 3) return fail(err, "normal, min_distance and max_distance: all three or none");
+    P.normals = nrm == 3 && c->n > 0;
+    if (P.normals) {
+      if (c->n_levels < 1 || c->n_levels > maptable::kMaxLevels) return fail(err, "n_levels %lld outside 1..8", c->n_levels);
+      if (!c->scale_factors) return fail(err, "null scale_factors");
+    }
+    if (!c->slots && c->n != nPoints() && c->n > 0) return fail(err, "null slots with n = %lld, not n_points = %lld", c->n, nPoints());
+    P.rankOf.assign((size_t)nKeyframes(), -1);
+    for (int32_t k = 0; k < c->n_kf; k++) {
+      const int32_t s = c->kf_slots[k];
+      if (s < 0 || s >= nKeyframes()) return fail(err, "kf_slots[%lld]: keyframe slot %lld outside 0..%lld", k, s, (long long)nKeyframes() - 1);
+      if (P.rankOf[s] >= 0) return fail(err, "kf_slots[%lld]: keyframe slot %lld repeats kf_slots[%lld]", k, s, P.rankOf[s]);
+      P.rankOf[s] = k;
+    }
+    if (c->arithmetic == YDORB_MAPCORR_SIM3 && c->n > 0)
+      for (int32_t k = 0; k < c->n_kf; k++) {
+        const double sb = static_cast<const double*>(c->before)[8 * (size_t)k + 7], sa = static_cast<const double*>(c->after)[8 * (size_t)k + 7];
+        // !(s > 0) also catches NaN; s - s != 0 catches infinity
+        if (!(sb > 0.0) || sb - sb != 0.0) return fail(err, "before[%lld]: the Sim3 scale is not positive and finite", k);
+        if (!(sa > 0.0) || sa - sa != 0.0) return fail(err, "after[%lld]: the Sim3 scale is not positive and finite", k);
+      }
+    for (int32_t i = 0; i < c->n; i++) {
+      if (c->slots && (c->slots[i] < 0 || c->slots[i] >= nPoints()))
+        return fail(err, "slots[%lld]: point slot %lld outside 0..%lld", i, c->slots[i], (long long)nPoints() - 1);
+      if (c->corrector && (c->corrector[i] < -1 || c->corrector[i] >= c->n_kf))
+        return fail(err, "corrector[%lld]: %lld outside -1..%lld", i, c->corrector[i], (long long)c->n_kf - 1);
+    }
+    // the claim pass
+    P.status.assign((size_t)c->n, 0);
+    P.entry.clear(); P.slot.clear(); P.rank.clear();
+    if (stamp_.size() < (size_t)nPoints()) stamp_.resize((size_t)nPoints(), 0);
+    if (++stampNow_ == 0) { std::fill(stamp_.begin(), stamp_.end(), 0u); stampNow_ = 1; }
+    for (int32_t i = 0; i < c->n; i++) {
+      const int32_t s = c->slots ? c->slots[i] : i;
+      if (bad_[s]) { P.status[i] = YDORB_MAPCORR_BAD; continue; }
+      if (stamp_[s] == stampNow_) { P.status[i] = YDORB_MAPCORR_CLAIMED; continue; }
+      stamp_[s] = stampNow_;
+      const int32_t r = c->corrector && c->corrector[i] >= 0 ? c->corrector[i] : P.rankOf[refKf_[s]];
+      if (r < 0) { P.status[i] = YDORB_MAPCORR_NOT_COVERED; continue; }
+      P.status[i] = spanOf(s) == 0 ? YDORB_MAPCORR_DONE_NO_OBSERVATIONS : YDORB_MAPCORR_DONE;   // the kernel's word replaces it
+      if (P.normals && spanOf(s) > 0 && refLevel_[s] >= c->n_levels)
+        return fail(err, "slots[%lld]: reference level %lld of point slot %lld >= n_levels", i, refLevel_[s], s);
+      P.entry.push_back(i); P.slot.push_back(s); P.rank.push_back(r);
+    }
+    return true;
+  }
+  // After the read-back: the mirror takes the corrected positions (pos [claimed][3]) and the new centres, with no staged record left
+  // behind - the device holds the same floats already.
+  void correctionApplied(const YdMapCorrection* c, const CorrectionPlan& P, const float* pos) {
+    for (size_t j = 0; j < P.slot.size(); j++) memcpy(&pos_[3 * (size_t)P.slot[j]], pos + 3 * j, 12);
+    if (c->centre_after)
+      for (int32_t k = 0; k < c->n_kf; k++) memcpy(&centre_[3 * (size_t)c->kf_slots[k]], c->centre_after + 3 * (size_t)k, 12);
+  }
+  const std::vector<float>& mirrorPos() const { return pos_; }
+  const std::vector<float>& mirrorCentres() const { return centre_; }
+
   void stats(YdMapDbStats& s) const {
     s.n_points = nPoints(); s.n_keyframes = nKeyframes();
     s.n_observations = pendingLive_; s.pool_used = poolUsed_; s.pool_capacity = poolCap_;
@@ -322,6 +404,9 @@ class Host {
   int64_t poolCap_, poolUsed_ = 0, poolLive_ = 0, pendingLive_ = 0;
   int32_t repacksKept_ = 0, repacksGrown_ = 0, pointGrowths_ = 0, kfGrowths_ = 0;
   int64_t lastSyncBytes_ = 0, lastSyncRecords_ = 0;
+  // the claim pass of planCorrection: a slot is claimed in this call when its stamp is the call's
+  std::vector<uint32_t> stamp_;
+  uint32_t stampNow_ = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------------

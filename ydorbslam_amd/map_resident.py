@@ -1,15 +1,46 @@
 """The resident map table through the C ABI (include/ydorb/c_api.h, "Resident map table"): the observation table
 of map maintenance kept in HBM between calls, changed by deltas and queried with no table upload.  MapDb owns one ydorb_mapdb_t.  Its
 three queries go through map_maintenance's own wrappers (same argument preparation, same result dictionaries), with the handle in place
-of the flat table."""
+of the flat table.  MapDb.correct (ydorb_mapdb_correct) runs the point loops of loop closing on the table in place."""
 import ctypes as C
 
 import numpy as np
 
 from . import map_maintenance as M
-from ._lib import YdMapDbStats, check, lib
+from ._lib import YdMapCorrection, YdMapDbStats, check, lib
 
 _p = M._p
+
+ARITHMETIC = {"sim3": 0, "se3": 1}                              # YDORB_MAPCORR_SIM3 / _SE3
+CENTRES = {"resident": 0, "interleaved": 1, "poses_first": 2}   # YDORB_MAPCORR_RESIDENT / _INTERLEAVED / _POSES_FIRST
+CORRECTION_STATUS = {"done": 0, "bad": 1, "claimed": 2, "not_covered": 3, "done_no_observations": 4}
+
+
+def correction(kf_slots, before, after, n_all, slots, corrector, arithmetic, centre_after, centres, scale_factors):
+    """A YdMapCorrection over numpy arrays.  n_all = the table's n_points when slots is None.  Returns (struct, outputs, the arrays the
+    struct points into)."""
+    kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+    K = len(kf_slots)
+    se3 = ARITHMETIC[arithmetic] == 1
+    before = np.ascontiguousarray(before, np.float32 if se3 else np.float64).reshape(K, 12 if se3 else 8)
+    after = np.ascontiguousarray(after, np.float32 if se3 else np.float64).reshape(K, 12 if se3 else 8)
+    slots = None if slots is None else np.ascontiguousarray(slots, np.int32).reshape(-1)
+    n = n_all if slots is None else len(slots)
+    corrector = None if corrector is None else np.ascontiguousarray(corrector, np.int32).reshape(-1)
+    centre_after = None if centre_after is None else np.ascontiguousarray(centre_after, np.float32).reshape(K, 3)
+    sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+    assert corrector is None or len(corrector) == n
+    m = max(n, 1)
+    out = dict(pos=np.zeros((m, 3), np.float32), status=np.zeros(m, np.uint8))
+    if sf is not None:
+        out.update(normal=np.zeros((m, 3), np.float32), min_distance=np.zeros(m, np.float32), max_distance=np.zeros(m, np.float32))
+    c = YdMapCorrection(n_kf=K, arithmetic=ARITHMETIC[arithmetic], kf_slots=_p(kf_slots), before=_p(before), after=_p(after),
+                        centre_after=_p(centre_after), centres=CENTRES[centres], n=n, slots=_p(slots), corrector=_p(corrector),
+                        scale_factors=_p(sf), n_levels=0 if sf is None else len(sf), reserved=0, normal=_p(out.get("normal")),
+                        min_distance=_p(out.get("min_distance")), max_distance=_p(out.get("max_distance")), pos_out=_p(out["pos"]),
+                        status=_p(out["status"]))
+    keep = (kf_slots, before, after, slots, corrector, centre_after, sf, out)
+    return c, {k: v[:n] for k, v in out.items()}, keep
 
 
 class MapDb:
@@ -95,6 +126,18 @@ class MapDb:
         def fn(_table, c, K, ls, idx, own, rem, th, _device, nc, nr, cull):
             return lib().ydorb_mapdb_keyframe_redundancy(self._h, c, K, ls, idx, own, rem, th, nc, nr, cull)
         return M.keyframe_redundancy(_Header(self), cand_kf, lists, own_levels, removed, th_obs, fn=fn)
+
+    def correct(self, kf_slots, before, after, slots=None, corrector=None, arithmetic="sim3", centre_after=None, centres="resident",
+                scale_factors=None):
+        """ydorb_mapdb_correct: the point loops of loop closing in place on the table.  kf_slots [K]; before / after [K, 8] doubles
+        (arithmetic "sim3") or [K, 12] floats ("se3"); slots [n] or None = every slot in order; corrector [n] ranks into kf_slots, -1 =
+        the point's reference keyframe, None = all -1; centre_after [K, 3] or None; centres "resident" / "interleaved" / "poses_first";
+        scale_factors given = the normals pass runs.  Returns dict(pos [n, 3], status [n]) plus normal, min_distance, max_distance
+        with scale_factors."""
+        corr, out, _keep = correction(kf_slots, before, after, self.n_points if slots is None else None, slots, corrector, arithmetic,
+                                      centre_after, centres, scale_factors)
+        check(lib().ydorb_mapdb_correct(self._h, C.byref(corr)))
+        return out
 
     # ------------------------------------------------------------------------------------------------------------ inspection
     def stats(self):
