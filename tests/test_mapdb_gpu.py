@@ -159,6 +159,54 @@ def test_culling_boundaries_and_the_masked_walk_over_the_resident_entry():
     db.close()
 
 
+def test_resident_list_queries_refuse_bad_arguments_with_the_flat_entries_words():
+    """Covisibility and redundancy through the C ABI, flat and resident, on one table of 3 points over 4 keyframe slots: every bad call
+    is YDORB_ERR_INVALID_ARG on both routes, with the same message behind the route's prefix."""
+    import ctypes as C
+    from ydorbslam_amd import map_maintenance as M
+    from ydorbslam_amd._lib import lib
+    T = M.ObservationTable(4, [[0, 1], [1, 2, 3], [0]], [[0, 1], [1, 0, 2], [0]])
+    obs, lev = D.split_levels(T)
+    db = _db(4, 4, 16)
+    db.set_centres(np.arange(4), np.zeros((4, 3), np.float32))
+    db.set_points(np.arange(3), obs, lev, T.bad, np.zeros(3, np.int32), np.zeros(3, np.uint8), np.zeros((3, 3), np.float32))
+    i32 = lambda *v: np.array(v, np.int32)
+    out = lambda: np.zeros(4, np.int32)
+    good_c = dict(kf=i32(0, 1), n=2, ls=i32(0, 1, 2), idx=i32(0, 1), os=i32(0, 3, 6), conn=np.zeros(6, np.int32), w=np.zeros(6, np.int32),
+                  counts=out(), status=np.zeros(4, np.uint8))
+    good_r = dict(kf=i32(0, 1), n=2, ls=i32(0, 1, 2), idx=i32(0, 1), own=np.zeros(2, np.uint8), nc=out(), nr=out(), cull=np.zeros(4, np.uint8))
+
+    def covis(a, resident):
+        tail = (M._p(a["conn"]), M._p(a["w"]), M._p(a["counts"]), M._p(a["status"]))
+        head = (M._p(a["kf"]), a["n"], M._p(a["ls"]), M._p(a["idx"]), M._p(a["os"]))
+        return lib().ydorb_mapdb_covisibility(db._h, *head, *tail) if resident else lib().ydorb_map_covisibility(C.byref(T.struct), *head, 0, *tail)
+
+    def redundancy(a, resident):
+        tail = (M._p(a["nc"]), M._p(a["nr"]), M._p(a["cull"]))
+        head = (M._p(a["kf"]), a["n"], M._p(a["ls"]), M._p(a["idx"]), M._p(a["own"]), None, 3)
+        return lib().ydorb_mapdb_keyframe_redundancy(db._h, *head, *tail) if resident else lib().ydorb_map_keyframe_redundancy(C.byref(T.struct), *head, 0, *tail)
+
+    assert covis(good_c, False) == 0 and covis(good_c, True) == 0 and redundancy(good_r, False) == 0 and redundancy(good_r, True) == 0
+    bad = [(covis, dict(good_c, kf=i32(4, 1)), "query_kf[0]: keyframe slot 4 outside 0..3"),
+           (covis, dict(good_c, idx=i32(0, 3)), "list entry 1: point index 3 outside the table of 3"),
+           (covis, dict(good_c, os=i32(0, 3, 2)), "out_start decreases at 2: 2 after 3"),
+           (covis, dict(good_c, counts=None), "null counts or status"),
+           (covis, dict(good_c, conn=None), "null conn_kf or conn_weight"),
+           (redundancy, dict(good_r, kf=i32(0, 4)), "cand_kf[1]: keyframe slot 4 outside 0..3"),
+           (redundancy, dict(good_r, idx=i32(3, 1)), "list entry 0: point index 3 outside the table of 3"),
+           (redundancy, dict(good_r, own=None), "null own_level"),
+           (redundancy, dict(good_r, nc=None), "null output arrays")]
+    for fn, args, words in bad:
+        said = []
+        for resident, prefix in ((False, "map maintenance: "), (True, "resident map table: ")):
+            assert fn(args, resident) == -1, (words, resident)     # YDORB_ERR_INVALID_ARG
+            text = lib().ydorb_last_error().decode()
+            assert text.startswith(prefix), text
+            said.append(text[len(prefix):])
+        assert said[0] == said[1] == words
+    db.close()
+
+
 def _touch_three(db, m):
     T = m["table"]
     obs, lev = D.split_levels(T)

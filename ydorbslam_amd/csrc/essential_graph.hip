@@ -205,7 +205,7 @@ int begin(Run& R_) {
   int rc;
   UpPtrs tmpU; WorkPtrs tmpW; DownPtrs tmpD;
   const size_t ub = layUp(G, nullptr, tmpU), wb = layWork(G, nullptr, tmpW), db = layDown(G, nullptr, tmpD);
-  if ((rc = c.up.ensure(ub)) || (rc = c.hUp.ensure(ub)) || (rc = c.scratch.ensure(wb)) || (rc = c.down.ensure(db)) || (rc = c.hDown.ensure(db))) return rc;
+  if ((rc = c.ensure(ub, db, wb))) return rc;
   layUp(G, c.up.p, R_.u); layUp(G, c.hUp.p, R_.hu); layWork(G, c.scratch.p, R_.w); layDown(G, c.down.p, R_.d); layDown(G, c.hDown.p, R_.hd);
   UpPtrs& h = R_.hu;
   const size_t E = G.nE, P = G.nP, nInc = G.incE.size();
@@ -509,11 +509,9 @@ extern "C" int ydorb_essential_graph_set_profiling(int32_t device, int32_t on) {
 }
 
 extern "C" int ydorb_essential_graph_release(int32_t device) {
-  if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
-  int rc = require_device(device);
+  const int rc = release_staged(g_ctx, device);   // waits for the stream: no event is in flight behind it
   if (rc) return rc;
   EssCtx& c = g_ctx[device];
-  if ((rc = release_staged(c, device))) return rc;   // waits for the stream: no event is in flight behind it
   std::lock_guard<std::mutex> lock(c.mu);
   for (hipEvent_t& e : c.ev)
     if (e) { (void)hipEventDestroy(e); e = nullptr; }

@@ -72,7 +72,7 @@ int checkGrid(const int32_t* cellStart, const int32_t* cellIdx, const float* bou
 int undistortStaged(StagedCtx& c, const YdCamera& cam, const float* xy, int n, float* out) {
   int rc;
   const size_t bytes = sizeof(float2) * (size_t)n;
-  if ((rc = c.up.ensure(bytes)) || (rc = c.hUp.ensure(bytes)) || (rc = c.down.ensure(bytes)) || (rc = c.hDown.ensure(bytes))) return rc;
+  if ((rc = c.ensure(bytes, bytes))) return rc;
   std::memcpy(c.hUp.p, xy, bytes);
   hipStream_t s = c.stream;
   HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, bytes, hipMemcpyHostToDevice, s));
@@ -191,7 +191,7 @@ extern "C" int ydorb_frame_tail(const YdFrameTail* B, YdKeyPoint* kpsUn, float* 
   const size_t oN = U.add(4 * (size_t)nF), oKps = U.add(sizeof(YdKeyPoint) * total),
                oDepth = U.add(image ? imgBytes * nF : type == YDORB_DEPTH_SAMPLES ? 4 * total : 0);
   const DownLayout L(nF, cap, kpsUn, rightX, depth, cellStart, status);
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(L.D.bytes)) || (rc = c.hDown.ensure(L.D.bytes))) return rc;
+  if ((rc = c.ensure(U.bytes, L.D.bytes))) return rc;
   std::memcpy(at<void>(c.hUp, oN), B->n, 4 * (size_t)nF);
   for (int f = 0; f < nF; f++) {
     const size_t n = B->n[f];
@@ -263,7 +263,7 @@ extern "C" int ydorb_extract_rgbd(ydorb_extractor_t* h, const uint8_t* gray, int
   const size_t oN = X.add(4), oRaw = X.add(sizeof(YdKeyPoint) * (size_t)Q), oDesc = X.add((size_t)32 * Q);
   const DownLayout L(1, Q, kpsUn, rightX, depthOut, cellStart, status);
   const size_t downBytes = X.bytes + L.D.bytes;
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(downBytes)) || (rc = c.hDown.ensure(downBytes))) return rc;
+  if ((rc = c.ensure(U.bytes, downBytes))) return rc;
   for (int r = 0; r < hgt; r++) {
     std::memcpy(at<uint8_t>(c.hUp, oGray) + (size_t)r * w, gray + (size_t)r * stride, w);
     if (rowBytes) std::memcpy(at<uint8_t>(c.hUp, oDepth) + (size_t)r * rowBytes, static_cast<const uint8_t*>(depthImg) + (size_t)r * depthStride, rowBytes);
@@ -300,9 +300,4 @@ extern "C" int ydorb_extract_rgbd(ydorb_extractor_t* h, const uint8_t* gray, int
   return YDORB_OK;
 }
 
-extern "C" int ydorb_frame_release(int32_t device) {
-  if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
-  int rc = require_device(device);
-  if (rc) return rc;
-  return release_staged(g_ctx[device], device);
-}
+extern "C" int ydorb_frame_release(int32_t device) { return release_staged(g_ctx, device); }

@@ -56,7 +56,7 @@ extern "C" int ydorb_frustum_cull(const YdFrustumBatch* B, YdTrackView* rows, ui
                oMax = U.add(4 * (size_t)np), oIdx = U.add(4 * l), oSkip = U.add(l);
   Layout D;
   const size_t dRows = D.add(sizeof(YdTrackView) * l), dSt = D.add(l);
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(D.bytes)) || (rc = c.hDown.ensure(D.bytes))) return rc;
+  if ((rc = c.ensure(U.bytes, D.bytes))) return rc;
   std::memcpy(at<void>(c.hUp, oStart), B->list_start, 4 * (size_t)(nv + 1));
   std::memcpy(at<void>(c.hUp, oView), B->views, sizeof(ViewDev) * nv);
   std::memcpy(at<void>(c.hUp, oPos), B->table.pos_min, 16 * (size_t)np);
@@ -84,9 +84,4 @@ extern "C" int ydorb_frustum_cull(const YdFrustumBatch* B, YdTrackView* rows, ui
   return YDORB_OK;
 }
 
-extern "C" int ydorb_frustum_release(int32_t device) {
-  if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
-  int rc = require_device(device);
-  if (rc) return rc;
-  return release_staged(g_ctx[device], device);
-}
+extern "C" int ydorb_frustum_release(int32_t device) { return release_staged(g_ctx, device); }

@@ -97,11 +97,23 @@ struct StagedCtx {
     if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     return YDORB_OK;
   }
+  // Grows the upload area and its staging to upBytes, the read-back area and its staging to downBytes, scratch when asked for.  A
+  // buffer that grows moves: take device pointers only afterwards.
+  int ensure(size_t upBytes, size_t downBytes, size_t scratchBytes = 0) {
+    int rc;
+    if ((rc = up.ensure(upBytes)) || (rc = hUp.ensure(upBytes)) || (rc = down.ensure(downBytes)) || (rc = hDown.ensure(downBytes))) return rc;
+    return scratchBytes ? scratch.ensure(scratchBytes) : YDORB_OK;
+  }
   void releaseBuffers() { up.release(); down.release(); scratch.release(); hUp.release(); hDown.release(); }
 };
 
-// Body of a solver's ydorb_*_release(device): waits for the context's stream and gives its buffers back (the stream stays).
-inline int release_staged(StagedCtx& c, int device) {
+// Body of a solver's ydorb_*_release(device) over its array of contexts (StagedCtx or a context derived from it): checks the
+// ordinal, waits for the context's stream and gives its buffers back (the stream stays).
+template <class Ctx> int release_staged(Ctx (&ctx)[16], int device) {
+  if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
+  int rc = require_device(device);
+  if (rc) return rc;
+  StagedCtx& c = ctx[device];
   std::lock_guard<std::mutex> lock(c.mu);
   HIPCHK(hipSetDevice(device));
   if (c.stream) (void)hipStreamSynchronize(c.stream);

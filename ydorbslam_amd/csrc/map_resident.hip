@@ -13,7 +13,7 @@
 
 #include "../../include/ydorb/c_api.h"
 #include "host_buffers.h"
-#include "map_kernels.hip.h"
+#include "map_queries.h"
 #include "map_table.h"
 #include "mapcorrect_kernels.hip.h"
 #include "mapdb_host.h"
@@ -139,17 +139,14 @@ int sync(ydorb_mapdb* h) {
   return YDORB_OK;
 }
 
-mapmaint::Table tableOf(const ydorb_mapdb* h) {
-  mapmaint::Table t;
+// the table and the point attributes as the queries of map_queries.h read them: call after sync(), which may move the arenas
+mapmaint::MapSource sourceOf(const ydorb_mapdb* h) {
+  mapmaint::MapSource src;
+  mapmaint::Table& t = src.resident;
   t.nPoints = h->host.nPoints(); t.nKeyframes = h->host.nKeyframes();
   t.obsStart = h->T.start; t.obsEnd = h->T.end; t.obsKf = h->poolKf; t.obsLevel = h->poolLevel; t.bad = h->T.bad;
-  return t;
-}
-
-int ensure(StagedCtx& c, const Layout& U, const Layout& D) {
-  int rc;
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(D.bytes)) || (rc = c.hDown.ensure(D.bytes))) return rc;
-  return YDORB_OK;
+  src.pos = h->T.pos; src.centre = h->T.centre; src.refKf = h->T.refKf; src.refLevel = h->T.refLevel;
+  return src;
 }
 
 }  // namespace
@@ -237,33 +234,9 @@ extern "C" int ydorb_mapdb_update_normal_depth(ydorb_mapdb_t* h, const int32_t* 
   HIPCHK(hipSetDevice(h->device));
   int rc = sync(h);
   if (rc) return rc;
-  StagedCtx& c = h->c;
-  const size_t np = (size_t)n;
-  Layout U;
-  const size_t oSlots = U.add(4 * np);
-  Layout D;
-  const size_t dNrm = D.add(12 * np), dMin = D.add(4 * np), dMax = D.add(4 * np), dSt = D.add(np);
-  if ((rc = ensure(c, U, D))) return rc;
-  std::memcpy(at<void>(c.hUp, oSlots), slots, 4 * np);
-  hipStream_t s = c.stream;
-  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
-  mapmaint::NormalArgs a;
-  a.t = tableOf(h);
-  a.pos = h->T.pos; a.centre = h->T.centre; a.refKf = h->T.refKf; a.refLevel = h->T.refLevel;
-  for (int i = 0; i < 8; i++) a.scaleFactors[i] = i < n_levels ? scale_factors[i] : 0.f;
-  a.nLevels = n_levels;
-  a.slots = at<int>(c.up, oSlots); a.n = n;
-  a.normal = at<float>(c.down, dNrm); a.minDistance = at<float>(c.down, dMin); a.maxDistance = at<float>(c.down, dMax);
-  a.status = at<uint8_t>(c.down, dSt);
-  hipLaunchKernelGGL(mapmaint::k_normal_depth, dim3((unsigned)((np + mapmaint::kThreads - 1) / mapmaint::kThreads)), dim3(mapmaint::kThreads), 0, s, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  std::memcpy(normal, at<void>(c.hDown, dNrm), 12 * np);
-  std::memcpy(min_distance, at<void>(c.hDown, dMin), 4 * np);
-  std::memcpy(max_distance, at<void>(c.hDown, dMax), 4 * np);
-  std::memcpy(status, at<void>(c.hDown, dSt), np);
-  return YDORB_OK;
+  mapmaint::MapSource src = sourceOf(h);
+  src.slots = slots;
+  return mapmaint::runNormalDepth(h->c, src, n, scale_factors, n_levels, normal, min_distance, max_distance, status);
 }
 
 extern "C" int ydorb_mapdb_covisibility(ydorb_mapdb_t* h, const int32_t* query_kf, int32_t n_queries, const int32_t* list_start,
@@ -273,48 +246,14 @@ extern "C" int ydorb_mapdb_covisibility(ydorb_mapdb_t* h, const int32_t* query_k
   std::lock_guard<std::mutex> lock(h->c.mu);
   std::string err;
   const YdObservationTable hdr = h->host.counts();
-  if (!maptable::checkLists(&hdr, "query_kf", query_kf, n_queries, list_start, point_idx, err) ||
-      !maptable::checkStarts("out_start", out_start, n_queries, err))
+  if (!maptable::checkCovisibilityArgs(&hdr, query_kf, n_queries, list_start, point_idx, out_start, conn_kf, conn_weight, counts, status, err))
     return invalid(err);
-  if (n_queries > 0 && (!counts || !status)) return invalid("null counts or status");
-  if (out_start[n_queries] > 0 && (!conn_kf || !conn_weight)) return invalid("null conn_kf or conn_weight");
-  const size_t nq = (size_t)n_queries;
-  if (nq == 0) return YDORB_OK;
+  if (n_queries == 0) return YDORB_OK;
   HIPCHK(hipSetDevice(h->device));
   int rc = sync(h);
   if (rc) return rc;
-  StagedCtx& c = h->c;
-  const size_t L = (size_t)list_start[nq], cap = (size_t)out_start[nq];
-  Layout U;
-  const size_t oQ = U.add(4 * nq), oLs = U.add(4 * (nq + 1)), oIdx = U.add(4 * L), oOs = U.add(4 * (nq + 1));
-  Layout D;
-  const size_t dKf = D.add(4 * cap), dW = D.add(4 * cap), dCnt = D.add(4 * nq), dSt = D.add(nq);
-  if ((rc = ensure(c, U, D))) return rc;
-  std::memcpy(at<void>(c.hUp, oQ), query_kf, 4 * nq);
-  std::memcpy(at<void>(c.hUp, oLs), list_start, 4 * (nq + 1));
-  if (L) std::memcpy(at<void>(c.hUp, oIdx), point_idx, 4 * L);
-  std::memcpy(at<void>(c.hUp, oOs), out_start, 4 * (nq + 1));
-  hipStream_t s = c.stream;
-  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
-  mapmaint::CovisArgs a;
-  a.t = tableOf(h);
-  a.nQueries = n_queries;
-  a.queryKf = at<int>(c.up, oQ); a.listStart = at<int>(c.up, oLs); a.pointIdx = at<int>(c.up, oIdx); a.outStart = at<int>(c.up, oOs);
-  a.connKf = at<int>(c.down, dKf); a.connWeight = at<int>(c.down, dW); a.counts = at<int>(c.down, dCnt); a.status = at<uint8_t>(c.down, dSt);
-  hipLaunchKernelGGL(mapmaint::k_covisibility, dim3((unsigned)nq), dim3(mapmaint::kThreads), 0, s, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  std::memcpy(counts, at<void>(c.hDown, dCnt), 4 * nq);
-  std::memcpy(status, at<void>(c.hDown, dSt), nq);
-  const int32_t* hKf = at<int32_t>(c.hDown, dKf);
-  const int32_t* hW = at<int32_t>(c.hDown, dW);
-  for (size_t q = 0; q < nq; q++) {   // only what a query wrote, as in the flat entry
-    if (status[q] != 0 || counts[q] == 0) continue;
-    std::memcpy(conn_kf + out_start[q], hKf + out_start[q], 4 * (size_t)counts[q]);
-    std::memcpy(conn_weight + out_start[q], hW + out_start[q], 4 * (size_t)counts[q]);
-  }
-  return YDORB_OK;
+  mapmaint::MapSource src = sourceOf(h);
+  return mapmaint::runCovisibility(h->c, src, query_kf, n_queries, list_start, point_idx, out_start, conn_kf, conn_weight, counts, status);
 }
 
 extern "C" int ydorb_mapdb_keyframe_redundancy(ydorb_mapdb_t* h, const int32_t* cand_kf, int32_t n_candidates, const int32_t* list_start,
@@ -324,48 +263,19 @@ extern "C" int ydorb_mapdb_keyframe_redundancy(ydorb_mapdb_t* h, const int32_t* 
   std::lock_guard<std::mutex> lock(h->c.mu);
   std::string err;
   const YdObservationTable hdr = h->host.counts();
-  if (!maptable::checkLists(&hdr, "cand_kf", cand_kf, n_candidates, list_start, point_idx, err)) return invalid(err);
-  if (list_start[n_candidates] > 0 && !own_level) return invalid("null own_level");
-  if (n_candidates > 0 && (!n_counted || !n_redundant || !cull)) return invalid("null output arrays");
-  const size_t nc = (size_t)n_candidates, nk = (size_t)hdr.n_keyframes;
+  if (!maptable::checkRedundancyArgs(&hdr, cand_kf, n_candidates, list_start, point_idx, own_level, n_counted, n_redundant, cull, err))
+    return invalid(err);
+  const size_t nc = (size_t)n_candidates;
   if (nc == 0) return YDORB_OK;
-  const size_t L = (size_t)list_start[nc];
   std::memset(n_counted, 0, 4 * nc);
   std::memset(n_redundant, 0, 4 * nc);
-  std::memset(cull, 0, nc);
-  if (L == 0) return YDORB_OK;
+  std::memset(cull, 0, nc);               // an empty list: 0 > 0.9 * 0 is false
+  if (list_start[nc] == 0) return YDORB_OK;
   HIPCHK(hipSetDevice(h->device));
   int rc = sync(h);
   if (rc) return rc;
-  StagedCtx& c = h->c;
-  Layout U;
-  const size_t oC = U.add(4 * nc), oLs = U.add(4 * (nc + 1)), oIdx = U.add(4 * L), oOwn = U.add(L), oRem = U.add(nk);
-  Layout D;
-  const size_t dCnt = D.add(4 * nc), dRed = D.add(4 * nc);
-  if ((rc = ensure(c, U, D))) return rc;
-  std::memcpy(at<void>(c.hUp, oC), cand_kf, 4 * nc);
-  std::memcpy(at<void>(c.hUp, oLs), list_start, 4 * (nc + 1));
-  std::memcpy(at<void>(c.hUp, oIdx), point_idx, 4 * L);
-  std::memcpy(at<void>(c.hUp, oOwn), own_level, L);
-  if (removed) std::memcpy(at<void>(c.hUp, oRem), removed, nk);
-  else std::memset(at<void>(c.hUp, oRem), 0, nk);
-  hipStream_t s = c.stream;
-  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(c.down.p, 0, D.bytes, s));
-  mapmaint::RedundancyArgs a;
-  a.t = tableOf(h);
-  a.nCand = n_candidates; a.nEntries = (int)L; a.thObs = th_obs;
-  a.candKf = at<int>(c.up, oC); a.listStart = at<int>(c.up, oLs); a.pointIdx = at<int>(c.up, oIdx); a.ownLevel = at<uint8_t>(c.up, oOwn);
-  a.removed = at<uint8_t>(c.up, oRem);
-  a.nCounted = at<int>(c.down, dCnt); a.nRedundant = at<int>(c.down, dRed);
-  hipLaunchKernelGGL(mapmaint::k_redundancy, dim3((unsigned)((L + mapmaint::kThreads - 1) / mapmaint::kThreads)), dim3(mapmaint::kThreads), 0, s, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  std::memcpy(n_counted, at<void>(c.hDown, dCnt), 4 * nc);
-  std::memcpy(n_redundant, at<void>(c.hDown, dRed), 4 * nc);
-  for (size_t k = 0; k < nc; k++) cull[k] = maptable::cullVerdict(n_redundant[k], n_counted[k]);
-  return YDORB_OK;
+  mapmaint::MapSource src = sourceOf(h);
+  return mapmaint::runRedundancy(h->c, src, cand_kf, n_candidates, list_start, point_idx, own_level, removed, th_obs, n_counted, n_redundant, cull);
 }
 
 // sync; one upload of the keyframe tables, the rank table, the claimed list and the centres; the pass; the centre write; one read-back;
@@ -395,7 +305,7 @@ extern "C" int ydorb_mapdb_correct(ydorb_mapdb_t* h, const YdMapCorrection* c) {
   const size_t dPos = D.add(12 * nc), dNrm = D.add(P.normals ? 12 * nc : 0), dMin = D.add(P.normals ? 4 * nc : 0), dMax = D.add(P.normals ? 4 * nc : 0),
                dSt = D.add(nc);
   U.add(16); D.add(16);   // never an empty buffer
-  if ((rc = ensure(ctx, U, D))) return rc;
+  if ((rc = ctx.ensure(U.bytes, D.bytes))) return rc;
   if (pairBytes) { std::memcpy(at<void>(ctx.hUp, oBefore), c->before, pairBytes); std::memcpy(at<void>(ctx.hUp, oAfter), c->after, pairBytes); }
   if (nk) std::memcpy(at<void>(ctx.hUp, oRankOf), P.rankOf.data(), 4 * nk);
   if (nKf) std::memcpy(at<void>(ctx.hUp, oKf), c->kf_slots, 4 * nKf);

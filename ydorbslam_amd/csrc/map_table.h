@@ -108,23 +108,40 @@ inline bool checkNormalDepth(const YdObservationTable* T, const float* pos, cons
   return true;
 }
 
-inline bool checkCovisibility(const YdObservationTable* T, const int32_t* queryKf, int32_t nQueries, const int32_t* listStart,
-                              const int32_t* pointIdx, const int32_t* outStart, int32_t device, const int32_t* connKf,
-                              const int32_t* connWeight, const int32_t* counts, const uint8_t* status, std::string& err) {
-  if (!checkDevice(device, err) || !checkTable(T, err) || !checkLists(T, "query_kf", queryKf, nQueries, listStart, pointIdx, err)) return false;
+// What a covisibility call's own arrays must satisfy.  Of T only the header (n_points, n_keyframes) is read: the resident table
+// passes its counts, the flat entry its table after checkTable.
+inline bool checkCovisibilityArgs(const YdObservationTable* T, const int32_t* queryKf, int32_t nQueries, const int32_t* listStart,
+                                  const int32_t* pointIdx, const int32_t* outStart, const int32_t* connKf, const int32_t* connWeight,
+                                  const int32_t* counts, const uint8_t* status, std::string& err) {
+  if (!checkLists(T, "query_kf", queryKf, nQueries, listStart, pointIdx, err)) return false;
   if (!checkStarts("out_start", outStart, nQueries, err)) return false;
   if (nQueries > 0 && (!counts || !status)) return fail(err, "null counts or status");
   if (outStart[nQueries] > 0 && (!connKf || !connWeight)) return fail(err, "null conn_kf or conn_weight");
   return true;
 }
 
-inline bool checkRedundancy(const YdObservationTable* T, const int32_t* candKf, int32_t nCand, const int32_t* listStart, const int32_t* pointIdx,
-                            const uint8_t* ownLevel, int32_t device, const int32_t* nCounted, const int32_t* nRedundant,
-                            const uint8_t* cull, std::string& err) {
-  if (!checkDevice(device, err) || !checkTable(T, err) || !checkLists(T, "cand_kf", candKf, nCand, listStart, pointIdx, err)) return false;
+inline bool checkCovisibility(const YdObservationTable* T, const int32_t* queryKf, int32_t nQueries, const int32_t* listStart,
+                              const int32_t* pointIdx, const int32_t* outStart, int32_t device, const int32_t* connKf,
+                              const int32_t* connWeight, const int32_t* counts, const uint8_t* status, std::string& err) {
+  return checkDevice(device, err) && checkTable(T, err) &&
+         checkCovisibilityArgs(T, queryKf, nQueries, listStart, pointIdx, outStart, connKf, connWeight, counts, status, err);
+}
+
+// The same for a redundancy call: again only T's header is read.
+inline bool checkRedundancyArgs(const YdObservationTable* T, const int32_t* candKf, int32_t nCand, const int32_t* listStart,
+                                const int32_t* pointIdx, const uint8_t* ownLevel, const int32_t* nCounted, const int32_t* nRedundant,
+                                const uint8_t* cull, std::string& err) {
+  if (!checkLists(T, "cand_kf", candKf, nCand, listStart, pointIdx, err)) return false;
   if (listStart[nCand] > 0 && !ownLevel) return fail(err, "null own_level");
   if (nCand > 0 && (!nCounted || !nRedundant || !cull)) return fail(err, "null output arrays");
   return true;
+}
+
+inline bool checkRedundancy(const YdObservationTable* T, const int32_t* candKf, int32_t nCand, const int32_t* listStart, const int32_t* pointIdx,
+                            const uint8_t* ownLevel, int32_t device, const int32_t* nCounted, const int32_t* nRedundant,
+                            const uint8_t* cull, std::string& err) {
+  return checkDevice(device, err) && checkTable(T, err) &&
+         checkRedundancyArgs(T, candKf, nCand, listStart, pointIdx, ownLevel, nCounted, nRedundant, cull, err);
 }
 
 // What always fits one covisibility query: it can name no keyframe but the others, and no more than it walks observations.

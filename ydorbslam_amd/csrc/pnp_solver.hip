@@ -60,9 +60,7 @@ extern "C" int ydorb_pnp_ransac(YdPnpProblem* probs, int32_t n, int32_t chunk, i
   const size_t oOut = D.add(sizeof(ProbOut) * n), oCnt = D.add(4 * nHyp), oBest = D.add(nPts), oInl = D.add(nPts);
   Layout W;
   const size_t wPose = W.add(96 * nHyp), wIdx = W.add(4 * nPts), wAl = W.add(32 * nPts), wPc = W.add(24 * nPts);
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(D.bytes)) || (rc = c.hDown.ensure(D.bytes)) ||
-      (rc = c.scratch.ensure(W.bytes)))
-    return rc;
+  if ((rc = c.ensure(U.bytes, D.bytes, W.bytes))) return rc;
   ProbDev* dev = at<ProbDev>(c.hUp, oDev);
   for (int p = 0; p < n; p++) {
     const YdPnpProblem& q = probs[p];
@@ -130,9 +128,4 @@ extern "C" int ydorb_pnp_ransac(YdPnpProblem* probs, int32_t n, int32_t chunk, i
   return YDORB_OK;
 }
 
-extern "C" int ydorb_pnp_release(int32_t device) {
-  if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
-  int rc = require_device(device);
-  if (rc) return rc;
-  return release_staged(g_ctx[device], device);
-}
+extern "C" int ydorb_pnp_release(int32_t device) { return release_staged(g_ctx, device); }

@@ -56,7 +56,7 @@ extern "C" int ydorb_sim3_ransac(YdSim3Problem* probs, int32_t n, int32_t chunk,
                oM2 = U.add(4 * (size_t)nPairs), oTri = U.add(12 * (size_t)nHyp);
   Layout D;
   const size_t oOut = D.add(sizeof(RansacOut) * n), oCnt = D.add(4 * (size_t)nHyp), oMask = D.add(nPairs);
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(D.bytes)) || (rc = c.hDown.ensure(D.bytes))) return rc;
+  if ((rc = c.ensure(U.bytes, D.bytes))) return rc;
   RansacDev* dev = at<RansacDev>(c.hUp, oDev);
   for (int p = 0; p < n; p++) {
     const YdSim3Problem& q = probs[p];
@@ -149,9 +149,7 @@ extern "C" int ydorb_sim3_optimize(const YdSim3Batch* B, uint8_t* outlier, int32
   const size_t dS = D.add(64 * (size_t)n), dChi = D.add(16 * (size_t)n), dIn = D.add(4 * (size_t)n), dTr = D.add(4 * (size_t)n), dOut = D.add(e);
   Layout W;
   const size_t wErr = W.add(32 * e), wAct = W.add(e);
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(D.bytes)) || (rc = c.hDown.ensure(D.bytes)) ||
-      (rc = c.scratch.ensure(W.bytes)))
-    return rc;
+  if ((rc = c.ensure(U.bytes, D.bytes, W.bytes))) return rc;
   std::memcpy(at<void>(c.hUp, oStart), B->corr_start, 4 * (size_t)(n + 1));
   std::memcpy(at<void>(c.hUp, oS), B->S12, 64 * (size_t)n);
   std::memcpy(at<void>(c.hUp, oK1), B->K1, 32 * (size_t)n);
@@ -188,9 +186,4 @@ extern "C" int ydorb_sim3_optimize(const YdSim3Batch* B, uint8_t* outlier, int32
   return YDORB_OK;
 }
 
-extern "C" int ydorb_sim3_release(int32_t device) {
-  if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
-  int rc = require_device(device);
-  if (rc) return rc;
-  return release_staged(g_ctx[device], device);
-}
+extern "C" int ydorb_sim3_release(int32_t device) { return release_staged(g_ctx, device); }

@@ -73,7 +73,7 @@ extern "C" int ydorb_triangulate_matches(const YdTriBatch* B, float* x3d, uint8_
                oF1 = U.add(16 * m), oF2 = U.add(16 * m), oLv = U.add(16 * m);
   Layout D;
   const size_t dX = D.add(12 * m), dSt = D.add(m);
-  if ((rc = c.up.ensure(U.bytes)) || (rc = c.hUp.ensure(U.bytes)) || (rc = c.down.ensure(D.bytes)) || (rc = c.hDown.ensure(D.bytes))) return rc;
+  if ((rc = c.ensure(U.bytes, D.bytes))) return rc;
   std::memcpy(at<void>(c.hUp, oStart), B->match_start, 4 * (size_t)(n + 1));
   ProblemDev* prob = at<ProblemDev>(c.hUp, oProb);
   for (int p = 0; p < n; p++) prob[p] = ProblemDev{B->first_view[p], B->second_view[p], B->ratio_factor[p], 0};
@@ -114,9 +114,4 @@ extern "C" int ydorb_triangulate_matches(const YdTriBatch* B, float* x3d, uint8_
   return YDORB_OK;
 }
 
-extern "C" int ydorb_triangulate_release(int32_t device) {
-  if (device < 0 || device >= 16) { set_error("invalid device"); return YDORB_ERR_INVALID_ARG; }
-  int rc = require_device(device);
-  if (rc) return rc;
-  return release_staged(g_ctx[device], device);
-}
+extern "C" int ydorb_triangulate_release(int32_t device) { return release_staged(g_ctx, device); }
