@@ -1117,6 +1117,58 @@ typedef struct YdMapCorrection {
 /* Applies what is staged, then corrects.  n == 0 still writes the centres.  Holds the handle's mutex. */
 int ydorb_mapdb_correct(ydorb_mapdb_t* db, const YdMapCorrection* correction);
 
+/* Keyframe rows (DESIGN.md section 2 "Local map", section 6o): the second relation of the resident table, keyframe -> map points.
+ * A row is a keyframe's map-point vector (getMapPointMatches()) as point slots in keypoint order, -1 = a null entry; a keyframe slot
+ * whose row was never set has length 0.  The device keeps rowStart / rowLen per keyframe slot and one row pool, under the
+ * observation pool's policy (append at the tail, a replaced or erased row becomes garbage, repack in ascending keyframe slot when an
+ * append does not fit, same capacity when live + incoming <= capacity / 2, else 2 x (live + incoming), at most INT32_MAX entries).
+ * The two setters validate and stage; the next query or export applies rows after points, so a row may name a point staged in the
+ * same interval.  A row named several times between two syncs is applied once with its last value; an entry change to a row staged
+ * in the same interval lands inside it; entry changes to a resident row are coalesced per (keyframe, index), last value wins.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG naming the first offender, before any device work, and stages nothing: null
+ * arrays, a row_start that does not begin at 0 or decreases, a negative keyframe slot, a point slot outside -1..n_points-1 (staged
+ * points count: set the point before a row names it), idx outside the row's current length (a staged row's length counts), a row
+ * pool past INT32_MAX entries.  Row traffic is accounted in YdMapDbRowStats only; YdMapDbStats keeps its meaning.
+ * The two queries restate Tracking::updateLocalPoints / updateLocalKeyFrames of ORB-SLAM2 (the reference source is absent from this
+ * repository).  Assumptions for a maintainer who holds the reference to check: updateLocalPoints walks m_v_localKeyFrames in order and
+ * each keyframe's getMapPointMatches() in keypoint order, skips null and isBad() points and those already carrying this frame's
+ * trackReferenceForFrame mark, and pushes the rest; updateLocalKeyFrames counts, per frame map point that is not bad, every keyframe
+ * of getObservations() once (a bad point's frame entry is nulled instead); searchLocalPoints skips the frame's own matches.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdMapDbRowStats {
+  int64_t n_entries;                    /* entries of all rows, null ones included (staged changes included): what export_rows returns */
+  int64_t pool_used, pool_capacity;     /* row pool entries used (live + garbage) and allocated, as of the last sync */
+  int32_t repacks_kept, repacks_grown;
+  int32_t header_growths, header_capacity;   /* the rowStart / rowLen tables, as of the last sync */
+  int64_t last_row_sync_bytes;          /* what the most recent query (or export) uploaded for the rows: 0 when none was staged */
+  int64_t last_row_sync_records;        /* ... and its row header + single entry records */
+} YdMapDbRowStats;
+/* Replaces the whole row of each named keyframe: row_start [n+1] / point_slot.  A row of length 0 erases it (a culled keyframe).
+ * n_keyframes becomes 1 + the highest slot named, as for set_centres (a new slot's centre is zero until set). */
+int ydorb_mapdb_set_keyframe_rows(ydorb_mapdb_t* db, const int32_t* kf_slots, int32_t n, const int32_t* row_start,
+                                  const int32_t* point_slot);
+/* Single entries: row kf_slot[i], position idx[i] becomes point_slot[i] (addMapPoint, eraseMapPointMatch, replaceMapPointMatch). */
+int ydorb_mapdb_set_row_entries(ydorb_mapdb_t* db, const int32_t* kf_slot, const int32_t* idx, const int32_t* point_slot, int32_t n);
+/* Reads the device's rows back (after applying what is staged): row_start [n_keyframes+1], point_slot [n_entries]. */
+int ydorb_mapdb_export_rows(ydorb_mapdb_t* db, int32_t* row_start, int32_t* point_slot);
+int ydorb_mapdb_row_stats(ydorb_mapdb_t* db, YdMapDbRowStats* stats);
+/* The points of a keyframe set (updateLocalPoints; the local points of localBundleAdjust).  E = the resident rows of kf_slots
+ * concatenated in the order given.  An entry is kept when it is not -1, the point's resident bad flag is clear (a never-set slot reads
+ * as bad) and no earlier position of E holds the same slot.  out_slots [count] = the kept entries in the order of E; out_seen[i] = 1
+ * when out_slots[i] occurs among seen_points [n_seen] (-1 entries there are ignored; NULL with n_seen = 0).  A keyframe slot may
+ * repeat (its second copy keeps nothing); a slot with no row contributes nothing.  capacity >= min(|E|, n_points) always fits; with
+ * count > capacity status = 1, out_* are not written and *count is the size needed.  n_kf == 0: count = 0, nothing is applied.
+ * Refused up front: null arrays, a keyframe slot outside 0..n_keyframes-1, a seen slot outside -1..n_points-1, negative counts. */
+int ydorb_mapdb_points_of_keyframes(ydorb_mapdb_t* db, const int32_t* kf_slots, int32_t n_kf, const int32_t* seen_points, int32_t n_seen,
+                                    int32_t capacity, int32_t* out_slots, uint8_t* out_seen, int32_t* count, uint8_t* status);
+/* The observer counter of point lists (updateLocalKeyFrames; the fixed keyframes of localBundleAdjust).  Per list the keyframes with
+ * a non-zero count ascending by slot with their counts: ydorb_mapdb_covisibility's result and capacity rule with no own slot
+ * excluded.  -1 entries of point_slots are skipped; a point listed twice counts twice; point_bad [list_start[n_lists]] = the resident
+ * bad flag of each listed point (0 for a -1 entry). */
+int ydorb_mapdb_observer_counter(ydorb_mapdb_t* db, int32_t n_lists, const int32_t* list_start, const int32_t* point_slots,
+                                 const int32_t* out_start, int32_t* conn_kf, int32_t* conn_weight, int32_t* counts, uint8_t* status,
+                                 uint8_t* point_bad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,13 +5,17 @@
 //   touch(mp)          re-reads the point's observations, bad flag, reference keyframe and position at the next flush
 //   touchPosition(mp)  re-reads its position only (a BA write-back)
 //   touch(kf)          re-reads the camera centre
-//   forget(mp / kf)    gives the slot back (a forgotten point is erased from the table)
+//   forget(mp / kf)    gives the slot back (a forgotten point is erased from the table, a forgotten keyframe's row is emptied)
+//   touchRow(kf)       re-reads getMapPointMatches() at the next flush (keyframe rows)
+//   touchEntry(kf, i)  re-reads entry i of getMapPointMatches() only (addMapPoint, eraseMapPointMatch, replaceMapPointMatch)
 // INTEGRATION.md ("Resident map table") lists where the reference needs each.  flush() makes at most one call of each set_* entry; the
 // three queries flush first and then walk only the keyframes' map-point vectors, never the observation maps.  A missed touch does not
 // fail: results then differ from the reference's, and verify() names the slot.
 // One thread at a time per MapMirror (the handle below it has its own mutex; the pointer maps here do not).
 // correctLoopPoints, correctAfterEssentialGraph and correctAfterGlobalBA run the point loops of loop closing on the table in place
 // (DESIGN.md section 6n); their comments below state what each takes from the caller.
+// keyFrameCounter and localPoints are the two set queries of Tracking::updateLocalMap over the keyframe rows (tracking.hpp's
+// updateLocalKeyFramesImpl / updateLocalPointsImpl); verifyRows() is verify() for the rows.
 // Assumed spellings: those of mapPoint.hpp, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
 // MapPoint::setPosInWorld(cv::Mat), m_int_correctedByKeyFrameID, m_int_correctedReference and the Sim3 members rotation().x() .. w(),
 // translation()[k], scale().  The camera centre after a corrected pose is not read from a member: correctLoopPoints computes it from
@@ -24,6 +28,7 @@
 #include <cstring>
 #include <map>
 #include <stdexcept>
+#include <utility>
 #include <vector>
 
 #include <opencv2/core.hpp>
@@ -60,10 +65,17 @@ class MapMirror {
     freePoints_.push_back(s);
     mark(pointDirty_, dirtyPoints_, s, kFull);   // the next flush erases it, or writes the point that took the slot since
   }
+  void touchRow(const KeyFramePtr& kf) { markRow(kfSlotFor(kf)); }
+  void touchEntry(const KeyFramePtr& kf, size_t idx) {
+    const int32_t s = kfSlotFor(kf);
+    if (!rowSent_[s]) { markRow(s); return; }   // the table has no row to change yet: the whole row goes
+    if (!rowDirty_[s]) dirtyEntries_.push_back(std::make_pair(s, (int32_t)idx));
+  }
   void forget(const KeyFramePtr& kf) {
     const auto it = kfSlot_.find(kf);
     if (it == kfSlot_.end()) return;
     kfOf_[it->second] = KeyFramePtr();
+    if (rowSent_[it->second]) markRow(it->second);   // the next flush empties the row, or writes the row of the keyframe that took the slot since
     freeKfs_.push_back(it->second);
     kfSlot_.erase(it);
   }
@@ -71,10 +83,31 @@ class MapMirror {
     mapCheck(ydorb_mapdb_clear(db_));
     pointSlot_.clear(); pointOf_.clear(); freePoints_.clear(); pointDirty_.clear(); dirtyPoints_.clear(); span_.clear();
     kfSlot_.clear(); kfOf_.clear(); freeKfs_.clear(); kfDirty_.clear(); dirtyKfs_.clear();
+    rowDirty_.clear(); rowSent_.clear(); dirtyRows_.clear(); dirtyEntries_.clear();
   }
 
   // At most one call of each set_* entry: the centres first (a point may name a keyframe that got its slot while the point was read).
+  // The rows are read first (a row may name a point the mirror meets there for the first time) and sent last, after the points.
   void flush() {
+    std::vector<int32_t> rowKf, rowStart{0}, rowSlots, entKf, entIdx, entSlot;
+    for (const int32_t k : dirtyRows_) {
+      rowKf.push_back(k);
+      if (kfOf_[k])
+        for (const MapPointPtr& mp : kfOf_[k]->getMapPointMatches()) rowSlots.push_back(mp ? known(mp) : -1);
+      if (rowSlots.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX row entries in one flush");
+      rowStart.push_back((int32_t)rowSlots.size());
+      rowSent_[k] = kfOf_[k] ? 1 : 0;
+    }
+    int32_t readKf = -1;
+    std::vector<MapPointPtr> matches;
+    for (const std::pair<int32_t, int32_t>& e : dirtyEntries_) {
+      if (rowDirty_[e.first] || !kfOf_[e.first]) continue;   // the whole row travels, or the keyframe is gone
+      if (readKf != e.first) { matches = kfOf_[e.first]->getMapPointMatches(); readKf = e.first; }   // one copy per run of a keyframe's entries
+      const MapPointPtr mp = matches.at((size_t)e.second);
+      entKf.push_back(e.first); entIdx.push_back(e.second); entSlot.push_back(mp ? known(mp) : -1);
+    }
+    for (const int32_t k : dirtyRows_) rowDirty_[k] = kClean;
+    dirtyRows_.clear(); dirtyEntries_.clear();
     std::vector<int32_t> slots, start{0}, obsKf, refKf, posSlots;
     std::vector<uint8_t> obsLevel, bad, refLevel;
     std::vector<float> pos, posOnly;
@@ -115,6 +148,86 @@ class MapMirror {
       mapCheck(ydorb_mapdb_set_points(db_, slots.data(), (int32_t)slots.size(), start.data(), obsKf.data(), obsLevel.data(), bad.data(), refKf.data(),
                                       refLevel.data(), pos.data()));
     if (!posSlots.empty()) mapCheck(ydorb_mapdb_set_positions(db_, posSlots.data(), (int32_t)posSlots.size(), posOnly.data()));
+    if (!rowKf.empty()) mapCheck(ydorb_mapdb_set_keyframe_rows(db_, rowKf.data(), (int32_t)rowKf.size(), rowStart.data(), rowSlots.data()));
+    if (!entKf.empty()) mapCheck(ydorb_mapdb_set_row_entries(db_, entKf.data(), entIdx.data(), entSlot.data(), (int32_t)entKf.size()));
+  }
+
+  // The counting loop of Tracking::updateLocalKeyFrames over the resident table (ydorb_mapdb_observer_counter): per keyframe how many
+  // of the frame's map points it observes, a point listed twice counted twice.  Nulls nothing itself: badIndices receives the indices
+  // of framePoints whose point is bad, which the reference nulls in the frame.
+  std::map<KeyFramePtr, int> keyFrameCounter(const std::vector<MapPointPtr>& framePoints, std::vector<size_t>* badIndices = nullptr) {
+    std::vector<int32_t> slots;
+    for (const MapPointPtr& mp : framePoints) slots.push_back(mp ? known(mp) : -1);
+    flush();
+    std::map<KeyFramePtr, int> counter;
+    if (badIndices) badIndices->clear();
+    if (slots.empty()) return counter;
+    const int32_t capacity = (int32_t)kfOf_.size();   // no list names more keyframes than the table has
+    const int32_t listStart[2] = {0, (int32_t)slots.size()}, outStart[2] = {0, capacity};
+    std::vector<int32_t> kf((size_t)capacity + 1), weight((size_t)capacity + 1);
+    std::vector<uint8_t> pointBad(slots.size());
+    int32_t count = 0;
+    uint8_t status = 0;
+    mapCheck(ydorb_mapdb_observer_counter(db_, 1, listStart, slots.data(), outStart, kf.data(), weight.data(), &count, &status, pointBad.data()));
+    if (status != 0) throw std::runtime_error("ydorb: observer counter capacity bound violated");
+    for (int32_t i = 0; i < count; i++)
+      if (kfOf_[kf[i]]) counter[kfOf_[kf[i]]] = weight[i];
+    if (badIndices)
+      for (size_t i = 0; i < slots.size(); i++) if (pointBad[i]) badIndices->push_back(i);
+    return counter;
+  }
+
+  // Tracking::updateLocalPoints over the keyframe rows (ydorb_mapdb_points_of_keyframes): every live point of the local keyframes'
+  // map-point vectors once, in the reference's order.  seen[i] = 1 when the i-th returned point is among framePoints (the frame's own
+  // matches, which searchLocalPoints skips).  A keyframe whose row the table never got is read now.
+  std::vector<MapPointPtr> localPoints(const std::vector<KeyFramePtr>& localKeyFrames, const std::vector<MapPointPtr>& framePoints,
+                                       std::vector<uint8_t>* seen = nullptr) {
+    std::vector<int32_t> kfs, seenSlots;
+    for (const KeyFramePtr& kf : localKeyFrames) {
+      const int32_t s = kfSlotFor(kf);
+      if (!rowSent_[s]) markRow(s);
+      kfs.push_back(s);
+    }
+    for (const MapPointPtr& mp : framePoints) if (mp) seenSlots.push_back(known(mp));
+    flush();
+    std::vector<MapPointPtr> out;
+    if (seen) seen->clear();
+    if (kfs.empty()) return out;
+    const int32_t capacity = (int32_t)pointOf_.size();   // each point at most once
+    std::vector<int32_t> slots((size_t)capacity + 1);
+    std::vector<uint8_t> flag((size_t)capacity + 1);
+    int32_t count = 0;
+    uint8_t status = 0;
+    mapCheck(ydorb_mapdb_points_of_keyframes(db_, kfs.data(), (int32_t)kfs.size(), seenSlots.empty() ? nullptr : seenSlots.data(), (int32_t)seenSlots.size(),
+                                             capacity, slots.data(), flag.data(), &count, &status));
+    if (status != 0) throw std::runtime_error("ydorb: points-of-keyframes capacity bound violated");
+    for (int32_t i = 0; i < count; i++) {
+      out.push_back(pointOf_[slots[i]]);
+      if (seen) seen->push_back(flag[i]);
+    }
+    return out;
+  }
+
+  // Flushes and compares every known keyframe's getMapPointMatches() with the device's row (ydorb_mapdb_export_rows): the keyframe
+  // slots that differ.  Empty when every change was touched.
+  std::vector<int32_t> verifyRows() {
+    flush();
+    YdMapDbStats st;
+    YdMapDbRowStats rs;
+    mapCheck(ydorb_mapdb_stats(db_, &st));
+    mapCheck(ydorb_mapdb_row_stats(db_, &rs));
+    const size_t nk = (size_t)st.n_keyframes;
+    std::vector<int32_t> start(nk + 1), slot((size_t)rs.n_entries + 1);
+    mapCheck(ydorb_mapdb_export_rows(db_, start.data(), slot.data()));
+    std::vector<int32_t> differ;
+    for (size_t k = 0; k < kfOf_.size(); k++) {
+      std::vector<int32_t> want;
+      if (kfOf_[k] && rowSent_[k])
+        for (const MapPointPtr& mp : kfOf_[k]->getMapPointMatches()) want.push_back(mp ? (slotOf(mp) >= 0 ? slotOf(mp) : -2) : -1);
+      const size_t len = k < nk ? (size_t)(start[k + 1] - start[k]) : 0;
+      if (len != want.size() || (len > 0 && std::memcmp(&slot[start[k]], want.data(), 4 * len) != 0)) differ.push_back((int32_t)k);
+    }
+    return differ;
   }
 
   // updateNormalAndDepthBatch of mapPoint.hpp over the resident table: apply(mp, normal (3x1 CV_32F), minDistance, maxDistance) for every
@@ -440,6 +553,7 @@ class MapMirror {
     return corrected;
   }
 
+  void markRow(int32_t s) { mark(rowDirty_, dirtyRows_, s, kFull); }
   static void mark(std::vector<uint8_t>& state, std::vector<int32_t>& list, int32_t s, uint8_t how) {
     if (state[s] == kClean) list.push_back(s);
     state[s] = std::max(state[s], how);
@@ -459,7 +573,7 @@ class MapMirror {
     if (it != kfSlot_.end()) return it->second;
     int32_t s;
     if (!freeKfs_.empty()) { s = freeKfs_.back(); freeKfs_.pop_back(); }
-    else { s = (int32_t)kfOf_.size(); kfOf_.push_back(KeyFramePtr()); kfDirty_.push_back(kClean); }
+    else { s = (int32_t)kfOf_.size(); kfOf_.push_back(KeyFramePtr()); kfDirty_.push_back(kClean); rowDirty_.push_back(kClean); rowSent_.push_back(0); }
     kfOf_[s] = kf;
     kfSlot_[kf] = s;
     mark(kfDirty_, dirtyKfs_, s, kFull);
@@ -511,6 +625,9 @@ class MapMirror {
   std::vector<KeyFramePtr> kfOf_;
   std::vector<int32_t> freeKfs_, dirtyKfs_;
   std::vector<uint8_t> kfDirty_;
+  std::vector<uint8_t> rowDirty_, rowSent_;   // per keyframe slot: the row is re-read at the next flush / the table holds a row of it
+  std::vector<int32_t> dirtyRows_;
+  std::vector<std::pair<int32_t, int32_t> > dirtyEntries_;   // (keyframe slot, index)
 };
 
 }  // namespace adapter

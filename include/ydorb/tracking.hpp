@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -178,6 +179,80 @@ inline int searchLocalPointsImpl(ydorb_matcher_t* m, FrameT& frame, const std::v
   for (size_t i = 0; i < assigned.size(); i++)
     if (assigned[i] >= 0) frame.m_v_sptrMapPoints[i] = localMapPoints[assigned[i]];
   return nToMatch > 0 ? nMatches : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Tracking::updateLocalMap's two halves over a MapMirror's keyframe rows (mapMirror.hpp), restated from
+// ORB-SLAM2's Tracking::UpdateLocalKeyFrames / UpdateLocalPoints (the reference source is absent from this repository).  The member
+// functions become forwards ("Local map"):
+//   void Tracking::updateLocalKeyFrames() { ydorb::adapter::updateLocalKeyFramesImpl(mirror, m_frame_currentFrame, m_v_sptrLocalKeyFrames, m_sptr_referenceKeyFrame); }
+//   void Tracking::updateLocalPoints()    { ydorb::adapter::updateLocalPointsImpl(mirror, m_frame_currentFrame, m_v_sptrLocalKeyFrames, m_v_sptrLocalMapPoints); }
+// Assumed spellings beyond those above: Frame m_sptr_referenceKeyFrame; KeyFrame isBad(), m_int_trackReferenceForFrameID,
+// getBestCovisibilityKeyFrames(int), getChildren() (a std::set of keyframes), getParent(); MapPoint m_int_trackReferenceForFrameID.
+
+// The counter comes from the mirror (one query, no observation map is walked); the frame entries whose point is bad are nulled here;
+// then the reference's tail as written: the keyframes of the counter in the container's order, the reference keyframe by the largest
+// count (the first of equals), and one neighbour, one child and the parent per keyframe until more than 80 are held.  The `break`
+// after the parent leaves the outer loop, as in the reference.
+template <class Mirror, class FrameT, class KeyFramePtr>
+inline void updateLocalKeyFramesImpl(Mirror& mirror, FrameT& frame, std::vector<KeyFramePtr>& localKeyFrames, KeyFramePtr& referenceKeyFrame) {
+  std::vector<size_t> badIndices;
+  const std::map<KeyFramePtr, int> keyFrameCounter = mirror.keyFrameCounter(frame.m_v_sptrMapPoints, &badIndices);
+  for (const size_t i : badIndices) frame.m_v_sptrMapPoints[i].reset();
+  if (keyFrameCounter.empty()) return;
+  int max = 0;
+  KeyFramePtr keyFrameMax;
+  localKeyFrames.clear();
+  localKeyFrames.reserve(3 * keyFrameCounter.size());
+  for (const auto& kv : keyFrameCounter) {
+    const KeyFramePtr& kf = kv.first;
+    if (kf->isBad()) continue;
+    if (kv.second > max) { max = kv.second; keyFrameMax = kf; }
+    localKeyFrames.push_back(kf);
+    kf->m_int_trackReferenceForFrameID = frame.m_int_ID;
+  }
+  const size_t nFirst = localKeyFrames.size();   // the reference's end iterator is taken before the loop pushes
+  for (size_t i = 0; i < nFirst; i++) {
+    if (localKeyFrames.size() > 80) break;
+    const KeyFramePtr kf = localKeyFrames[i];
+    for (const KeyFramePtr& neighbour : kf->getBestCovisibilityKeyFrames(10)) {
+      if (neighbour->isBad()) continue;
+      if (neighbour->m_int_trackReferenceForFrameID != frame.m_int_ID) {
+        localKeyFrames.push_back(neighbour);
+        neighbour->m_int_trackReferenceForFrameID = frame.m_int_ID;
+        break;
+      }
+    }
+    for (const KeyFramePtr& child : kf->getChildren()) {
+      if (child->isBad()) continue;
+      if (child->m_int_trackReferenceForFrameID != frame.m_int_ID) {
+        localKeyFrames.push_back(child);
+        child->m_int_trackReferenceForFrameID = frame.m_int_ID;
+        break;
+      }
+    }
+    const KeyFramePtr parent = kf->getParent();
+    if (parent && parent->m_int_trackReferenceForFrameID != frame.m_int_ID) {
+      localKeyFrames.push_back(parent);
+      parent->m_int_trackReferenceForFrameID = frame.m_int_ID;
+      break;   // leaves the outer loop
+    }
+  }
+  if (keyFrameMax) {
+    referenceKeyFrame = keyFrameMax;
+    frame.m_sptr_referenceKeyFrame = referenceKeyFrame;
+  }
+}
+
+// One query in place of the walk over every local keyframe's map-point vector.  Returns, per local map point, whether it is one of the
+// frame's own matches: what searchLocalPoints' first loop marks m_int_lastSeenInFrameID for, and its `skip`.
+template <class Mirror, class FrameT, class KeyFramePtr, class MapPointPtr>
+inline std::vector<uint8_t> updateLocalPointsImpl(Mirror& mirror, FrameT& frame, const std::vector<KeyFramePtr>& localKeyFrames,
+                                                  std::vector<MapPointPtr>& localMapPoints) {
+  std::vector<uint8_t> seen;
+  localMapPoints = mirror.localPoints(localKeyFrames, frame.m_v_sptrMapPoints, &seen);
+  for (const MapPointPtr& mp : localMapPoints) mp->m_int_trackReferenceForFrameID = frame.m_int_ID;
+  return seen;
 }
 
 }  // namespace adapter

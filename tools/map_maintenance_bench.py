@@ -19,6 +19,8 @@ k_mapdb_apply / k_mapdb_repack: `rocprofv3 --kernel-trace --stats -- python tool
 --correct times the map correction on the resident table (ydorb_mapdb_correct) beside the route it replaces, for
 the three loops of loop closing; see bench_correct.  Its kernels k_mapdb_correct / k_mapdb_correct_centres: the same rocprofv3 line
 with --correct.
+--local-map times the two set queries of Tracking::updateLocalMap on the resident table's keyframe rows (DESIGN.md section 6o); see
+bench_local_map.  Its kernels k_rowset_mark / _count / _emit and k_mapdb_rows_apply / _repack: the same rocprofv3 line with --local-map.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -422,6 +424,134 @@ def bench_correct(reps):
     return out
 
 
+def bench_local_map(reps):
+    """--local-map: the two set queries of Tracking::updateLocalMap on the resident table's keyframe rows (DESIGN.md section 6o) beside
+    the host restatement of the two reference loops (tests/localmap_ref, one thread, flat arrays) on the same data, alternating in one
+    process.  The map-size table and every keyframe's row (the map's own density) are loaded once; the window is 80 keyframes round
+    keyframe 2 500.  Timed: points_of_keyframes with nothing staged and with 200 row entries staged (staging + query), the observer
+    counter of one frame of 1 000 points, and the same points query over synthetic rows of 2 000 entries, half of them null.  Outputs are
+    compared exactly before and after timing.  It ends with tests/cpp_host/localmap_run.cpp: updateLocalKeyFramesImpl / updateLocalPointsImpl
+    through MapMirror beside the two reference loops on the same stand-ins, alternating."""
+    import mapdb_rows_support as R
+    n_kf, n_points, window = SIZES["map"]
+    L, ref = y.lib(), R.ref()
+    d = make_map(n_kf, n_points, window)
+    T = d["T"]
+    db = y.MapDb(0, n_points, n_kf, 2 * d["n_obs"])
+    h = db._h
+    all_slots, kf_slots = np.arange(n_points, dtype=np.int32), np.arange(n_kf, dtype=np.int32)
+    assert L.ydorb_mapdb_set_centres(h, p(kf_slots), n_kf, p(d["centre"])) == 0
+    assert L.ydorb_mapdb_set_points(h, p(all_slots), n_points, p(T.obs_start), p(T.obs_kf), p(T.obs_level), p(T.bad), p(d["ref_kf"]), p(d["ref_level"]), p(d["pos"])) == 0
+    out = dict(keyframes=n_kf, points=n_points, observations=d["n_obs"], reps=reps)
+    rng = np.random.default_rng(7)
+    win = np.arange(n_kf // 2 - 40, n_kf // 2 + 40, dtype=np.int32)
+
+    def run(tag, row_start, row_slot):
+        """One row configuration: row_start [n_kf + 1] / row_slot for every keyframe slot."""
+        row_start, row_slot = np.ascontiguousarray(row_start, np.int32), np.ascontiguousarray(row_slot, np.int32)
+        t0 = time.perf_counter()
+        assert L.ydorb_mapdb_set_keyframe_rows(h, p(kf_slots), n_kf, p(row_start), p(row_slot)) == 0, L.ydorb_last_error()
+        got_rows = db.export_rows()
+        load_ms = (time.perf_counter() - t0) * 1e3
+        assert all(np.array_equal(got_rows[k], row_slot[row_start[k]:row_start[k + 1]]) for k in win)
+        E = int(sum(row_start[k + 1] - row_start[k] for k in win))
+        own = np.concatenate([row_slot[row_start[k]:row_start[k + 1]] for k in win[38:43]])
+        frame = np.ascontiguousarray(np.concatenate([own[own >= 0][:900], np.full(100, -1, np.int32)]), np.int32)   # one frame: 1 000 entries, 100 without a point
+        cap = min(E, n_points)
+        g_out, g_seen, r_out, r_seen = np.zeros(cap, np.int32), np.zeros(cap, np.uint8), np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+        cnt, st = C.c_int32(0), C.c_uint8(0)
+
+        def gpu_points():
+            assert L.ydorb_mapdb_points_of_keyframes(h, p(win), len(win), p(frame), len(frame), cap, p(g_out), p(g_seen), C.byref(cnt), C.byref(st)) == 0
+
+        def ref_points():
+            return ref.localmapref_points_of_keyframes(n_points, p(T.bad), p(row_start), p(row_slot), p(win), len(win), p(frame), len(frame), p(r_out), p(r_seen))
+
+        def same_points():
+            gpu_points()
+            n = ref_points()
+            assert st.value == 0 and cnt.value == n and np.array_equal(g_out[:n], r_out[:n]) and np.array_equal(g_seen[:n], r_seen[:n])
+            return n
+
+        # 200 entries of the window's rows, re-sent with the value they hold: the delta travels, the result stays
+        ek = rng.choice(win[[row_start[k + 1] > row_start[k] for k in win]], 200).astype(np.int32)
+        ei = np.array([rng.integers(0, row_start[k + 1] - row_start[k]) for k in ek], np.int32)
+        ev = np.ascontiguousarray(row_slot[row_start[ek] + ei], np.int32)
+
+        def staged_points():
+            assert L.ydorb_mapdb_set_row_entries(h, p(ek), p(ei), p(ev), 200) == 0
+            gpu_points()
+
+        kept = same_points()
+        # the observer counter of the frame
+        cap_kf = n_kf
+        ls, os_ = np.array([0, len(frame)], np.int32), np.array([0, cap_kf], np.int32)
+        ckf, cw, cc, cs, cb = np.zeros(cap_kf, np.int32), np.zeros(cap_kf, np.int32), np.zeros(1, np.int32), np.zeros(1, np.uint8), np.zeros(len(frame), np.uint8)
+        rkf, rw, rb = np.zeros(cap_kf, np.int32), np.zeros(cap_kf, np.int32), np.zeros(len(frame), np.uint8)
+
+        def gpu_counter():
+            assert L.ydorb_mapdb_observer_counter(h, 1, p(ls), p(frame), p(os_), p(ckf), p(cw), p(cc), p(cs), p(cb)) == 0
+
+        def ref_counter():
+            return ref.localmapref_observer_counter(p(T.obs_start), p(T.obs_kf), p(T.bad), p(frame), len(frame), p(rkf), p(rw), p(rb))
+
+        def same_counter():
+            gpu_counter()
+            n = ref_counter()
+            assert cs[0] == 0 and cc[0] == n and np.array_equal(ckf[:n], rkf[:n]) and np.array_equal(cw[:n], rw[:n]) and np.array_equal(cb, rb)
+            return n
+
+        n_conn = same_counter()
+        ts = {k: [] for k in ("points_gpu", "points_ref", "points_gpu_200_staged", "counter_gpu", "counter_ref")}
+        fns = dict(points_gpu=gpu_points, points_ref=ref_points, points_gpu_200_staged=staged_points, counter_gpu=gpu_counter, counter_ref=ref_counter)
+        sync_bytes = 0
+        for r in range(reps + 1):
+            for k, fn in fns.items():
+                t0 = time.perf_counter()
+                fn()
+                dt = time.perf_counter() - t0
+                if r:
+                    ts[k].append(dt)
+                if k == "points_gpu_200_staged":
+                    sync_bytes = db.row_stats()["last_row_sync_bytes"]
+        assert same_points() == kept and same_counter() == n_conn
+        res = {k + "_ms": stat(v) for k, v in ts.items()}
+        res.update(entries_walked=E, local_points=kept, frame_keyframes=n_conn, rows_load_ms=round(load_ms, 1), delta_bytes_200_entries=sync_bytes,
+                   delta_bytes_nothing_staged=0, query_upload_bytes=4 * (2 * len(win) + 1 + len(frame)), query_readback_bytes=5 * cap + 4,
+                   counter_upload_bytes=4 * (2 + 2 + 1 + int((frame >= 0).sum())), row_stats=db.row_stats())
+        out[tag] = res
+
+    run("map_density", d["kf_start"], d["kf_points"])
+    # synthetic rows of 2 000 entries, half of them null, for the window's keyframes; the other keyframes keep their rows
+    lens = np.diff(d["kf_start"].astype(np.int64))
+    lens[win] = 2000
+    start = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    slot = np.zeros(int(start[-1]), np.int32)
+    in_window = np.zeros(n_kf, bool)
+    in_window[win] = True
+    for k in range(n_kf):
+        if in_window[k]:
+            near = d["kf_points"][d["kf_start"][max(k - 15, 0)]:d["kf_start"][min(k + 16, n_kf)]]
+            row = rng.choice(near, 2000).astype(np.int32)
+            row[rng.permutation(2000)[:1000]] = -1
+            slot[start[k]:start[k + 1]] = row
+        else:
+            slot[start[k]:start[k + 1]] = d["kf_points"][d["kf_start"][k]:d["kf_start"][k + 1]]
+    run("rows_of_2000_half_null", start, slot)
+    db.close()
+    # the adapter level: tests/cpp_host/localmap_run.cpp's stand-ins (140 keyframes, 4 000 points, five frames per repetition)
+    import subprocess
+    exe = os.path.join(tempfile.mkdtemp(prefix="lmbench"), "localmap_run")
+    lib_dir = os.path.join(ROOT, "ydorbslam_amd")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "cpu_harness", "mockrt"), "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp_host", "localmap_run.cpp"), "-o", exe, "-L" + lib_dir, "-l:libydorb.so", "-Wl,-rpath," + lib_dir])
+    r = subprocess.run([exe, str(reps)], stdout=subprocess.PIPE, text=True, check=True)
+    lines = {w[0]: w[1:] for w in (ln.split() for ln in r.stdout.splitlines())}
+    assert all(lines["A_%s_same" % k] == ["1"] for k in ("local_keyframes", "reference_keyframe", "local_points", "seen", "nulled"))
+    out["adapter_five_frames"] = {k: [float(v) for v in lines[k]] for k in lines if k.startswith("time_")}
+    return out
+
+
 def flatten_times():
     """Host time of the adapters' three flattenings on stand-ins at the local size (31 keyframes, 7 750 points)."""
     m = S.random_map(5, 31, 7750, 4, 8, level_spread=1)
@@ -440,7 +570,13 @@ def main():
     ap.add_argument("--resident", action="store_true", help="time the resident map table (ydorb_mapdb_*) beside the flat entries instead")
     ap.add_argument("--kernel-ms", action="append", default=[], help="SIZE=MS: k_normal_depth's time from a kernel trace, for the bytes-per-second figure")
     ap.add_argument("--correct", action="store_true", help="time ydorb_mapdb_correct beside the route it replaces instead")
+    ap.add_argument("--local-map", action="store_true", help="time the keyframe-row queries of updateLocalMap (DESIGN.md section 6o) beside the host restatement instead")
     a = ap.parse_args()
+    if a.local_map:
+        res = bench_local_map(a.reps)
+        M.release()
+        print(json.dumps(res))
+        return
     if a.correct:
         res = bench_correct(a.reps)
         M.release()

@@ -135,6 +135,12 @@ SYMBOLS = {
     "ydorb_mapdb_stats": (C.c_int, [_VP, _VP]),
     "ydorb_mapdb_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ydorb_mapdb_correct": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_set_keyframe_rows": (C.c_int, [_VP, _VP, _I, _VP, _VP]),
+    "ydorb_mapdb_set_row_entries": (C.c_int, [_VP, _VP, _VP, _VP, _I]),
+    "ydorb_mapdb_export_rows": (C.c_int, [_VP, _VP, _VP]),
+    "ydorb_mapdb_row_stats": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_points_of_keyframes": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_observer_counter": (C.c_int, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -223,6 +229,11 @@ class YdMapDbStats(C.Structure):
     _fields_ = [("n_points", _I), ("n_keyframes", _I), ("n_observations", C.c_int64), ("pool_used", C.c_int64), ("pool_capacity", C.c_int64),
                 ("repacks_kept", _I), ("repacks_grown", _I), ("point_table_growths", _I), ("keyframe_table_growths", _I),
                 ("point_capacity", _I), ("keyframe_capacity", _I), ("last_sync_bytes", C.c_int64), ("last_sync_records", C.c_int64)]
+
+
+class YdMapDbRowStats(C.Structure):
+    _fields_ = [("n_entries", C.c_int64), ("pool_used", C.c_int64), ("pool_capacity", C.c_int64), ("repacks_kept", _I), ("repacks_grown", _I),
+                ("header_growths", _I), ("header_capacity", _I), ("last_row_sync_bytes", C.c_int64), ("last_row_sync_records", C.c_int64)]
 
 
 class YdMapCorrection(C.Structure):

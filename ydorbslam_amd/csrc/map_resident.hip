@@ -4,6 +4,8 @@
 // the table growths (device-to-device copies), k_mapdb_repack if the pool needs it and k_mapdb_apply; then the query's own arrays in one
 // upload, the pass of map_kernels.hip.h, one read-back and one synchronise.  With nothing staged no table byte moves.
 // ydorb_mapdb_correct (mapcorrect_kernels.hip.h) is the one query that writes the table: positions in place, then centres.
+// The keyframe rows (mapdb_rows_host.h, mapdb_rows_kernels.hip.h) are a second state machine in the same handle,
+// synced after the points under the same mutex: ydorb_mapdb_points_of_keyframes and ydorb_mapdb_observer_counter at the end of this file.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -18,6 +20,8 @@
 #include "mapcorrect_kernels.hip.h"
 #include "mapdb_host.h"
 #include "mapdb_kernels.hip.h"
+#include "mapdb_rows_host.h"
+#include "mapdb_rows_kernels.hip.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
@@ -32,7 +36,14 @@ struct ydorb_mapdb {
   mapdb::SlotTables T{};
   int* poolKf = nullptr;
   uint8_t* poolLevel = nullptr;
-  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc) {}
+  // keyframe rows: a state machine, arenas and a delta of their own
+  mapdb::RowsHost rows;
+  Mem rowHdr, rowPoolMem, rowDelta, rowset;   // rowset: first / seenStamp of the points-of-keyframes query, one entry per point slot
+  PinnedMem hRowDelta;
+  int *rowStart = nullptr, *rowLen = nullptr, *rowPool = nullptr, *first = nullptr, *seenStamp = nullptr;
+  size_t rowsetCap = 0;
+  int stamp = 0;
+  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc) {}
 };
 
 namespace {
@@ -77,17 +88,25 @@ int allocPool(Mem& m, int*& kf, uint8_t*& level, size_t cap) {
   return YDORB_OK;
 }
 
+int allocRowHeaders(hipStream_t s, Mem& m, int*& rowStart, int*& rowLen, size_t cap) {   // every slot: no row
+  int rc = m.alloc(8 * cap);
+  if (rc) return rc;
+  rowStart = m.as<int>(); rowLen = rowStart + cap;
+  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
+  return YDORB_OK;
+}
+
 #define D2D(dst, src, bytes) \
   do { if ((bytes) > 0) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, s)); } while (0)
 
 // Applies what is staged.  Called with the mutex held and the device set; everything it enqueues goes to the handle's stream, and the
 // arenas it replaces are freed only after that stream has drained.
-int sync(ydorb_mapdb* h) {
+int syncPoints(ydorb_mapdb* h) {
   if (!h->host.dirty()) { h->host.nothingToSync(); return YDORB_OK; }
   hipStream_t s = h->c.stream;
   const mapdb::Plan P = h->host.plan();
   int rc;
-  if ((rc = h->delta.ensure(P.bytes)) || (rc = h->hDelta.ensure(P.bytes))) return rc;
+  if ((rc = h->delta.ensure(P.bytes + 16)) || (rc = h->hDelta.ensure(P.bytes + 16))) return rc;   // never empty: rows may grow the keyframe count alone
   ScopedMem newPoints, newCentres, newPool;   // become the handle's arenas below; freed here on an early return
   mapdb::SlotTables T = h->T;
   int* poolKf = h->poolKf;
@@ -102,7 +121,7 @@ int sync(ydorb_mapdb* h) {
     if ((rc = allocPool(newPool, poolKf, poolLevel, (size_t)P.poolCap))) return rc;
   }
   h->host.pack(P, h->hDelta.as<uint8_t>());   // nothing below can be refused for a reason of the caller's: the delta counts as applied
-  HIPCHK(hipMemcpyAsync(h->delta.p, h->hDelta.p, P.bytes, hipMemcpyHostToDevice, s));
+  if (P.bytes) HIPCHK(hipMemcpyAsync(h->delta.p, h->hDelta.p, P.bytes, hipMemcpyHostToDevice, s));
   if (newPoints.p) {
     const size_t n = (size_t)P.nPointsBefore;
     D2D(T.start, h->T.start, 4 * n); D2D(T.end, h->T.end, 4 * n); D2D(T.refKf, h->T.refKf, 4 * n); D2D(T.pos, h->T.pos, 12 * n);
@@ -139,6 +158,72 @@ int sync(ydorb_mapdb* h) {
   return YDORB_OK;
 }
 
+// The staged rows, after the points: a row may name a point that got its slot in the same interval.
+int syncRows(ydorb_mapdb* h) {
+  if (!h->rows.dirty()) { h->rows.nothingToSync(); return YDORB_OK; }
+  hipStream_t s = h->c.stream;
+  const mapdb::RowPlan P = h->rows.plan();
+  int rc;
+  if ((rc = h->rowDelta.ensure(P.bytes + 16)) || (rc = h->hRowDelta.ensure(P.bytes + 16))) return rc;
+  ScopedMem newHdr, newPool;
+  int *rowStart = h->rowStart, *rowLen = h->rowLen, *pool = h->rowPool;
+  if (P.hdrCap != P.hdrCapBefore) {
+    if ((rc = allocRowHeaders(s, newHdr, rowStart, rowLen, (size_t)P.hdrCap))) return rc;
+  }
+  if (P.repack) {
+    if ((rc = newPool.alloc(4 * (size_t)P.poolCap))) return rc;
+    pool = newPool.as<int>();
+  }
+  h->rows.pack(P, h->hRowDelta.as<uint8_t>());
+  if (P.bytes) HIPCHK(hipMemcpyAsync(h->rowDelta.p, h->hRowDelta.p, P.bytes, hipMemcpyHostToDevice, s));
+  if (newHdr.p) { D2D(rowStart, h->rowStart, 4 * (size_t)P.nKfBefore); D2D(rowLen, h->rowLen, 4 * (size_t)P.nKfBefore); }
+  if (P.repack && P.nKfBefore > 0) {
+    mapdb::RowsRepackArgs a;
+    a.nKf = P.nKfBefore; a.rowStart = rowStart; a.rowLen = rowLen; a.newOff = at<int>(h->rowDelta, P.oNewOff); a.oldPool = h->rowPool; a.newPool = pool;
+    hipLaunchKernelGGL(mapdb::k_mapdb_rows_repack, dim3((unsigned)((P.nKfBefore + mapdb::kRowWaves - 1) / mapdb::kRowWaves)), dim3(mapdb::kRowThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  {
+    mapdb::RowsApplyArgs a;
+    a.nHeaderRec = P.nHeaderRec; a.nEntryRec = P.nEntryRec; a.nPayload = (int)P.nPayload; a.tail = (int)P.tail;
+    a.header = at<mapdb::RowHeaderRec>(h->rowDelta, P.oHeader); a.entry = at<mapdb::RowEntryRec>(h->rowDelta, P.oEntry);
+    a.payload = at<int>(h->rowDelta, P.oPayload);
+    a.rowStart = rowStart; a.rowLen = rowLen; a.pool = pool;
+    const size_t nFixed = (size_t)P.nHeaderRec + P.nEntryRec;
+    const size_t forFixed = (nFixed + mapdb::kRowThreads - 1) / mapdb::kRowThreads;
+    const size_t forPayload = std::min<size_t>(((size_t)P.nPayload + mapdb::kRowThreads - 1) / mapdb::kRowThreads, 2048);   // lanes stride past that
+    hipLaunchKernelGGL(mapdb::k_mapdb_rows_apply, dim3((unsigned)std::max<size_t>(std::max(forFixed, forPayload), 1)), dim3(mapdb::kRowThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (newHdr.p || newPool.p) {   // the old arenas are still read by what was enqueued
+    HIPCHK(hipStreamSynchronize(s));
+    if (newHdr.p) h->rowHdr.take(newHdr);
+    if (newPool.p) h->rowPoolMem.take(newPool);
+  }
+  h->rowStart = rowStart; h->rowLen = rowLen; h->rowPool = pool;
+  return YDORB_OK;
+}
+
+int sync(ydorb_mapdb* h) {
+  const int rc = syncPoints(h);
+  return rc ? rc : syncRows(h);
+}
+
+// first / seenStamp cover the point table's capacity: a fresh pair when it grew.  first is INT32_MAX everywhere between calls.
+int ensureRowset(ydorb_mapdb* h) {
+  const size_t cap = (size_t)h->host.pointCap();
+  if (h->rowsetCap == cap) return YDORB_OK;
+  h->rowsetCap = 0;
+  int rc = h->rowset.alloc(8 * cap);
+  if (rc) return rc;
+  h->first = h->rowset.as<int>(); h->seenStamp = h->first + cap;
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->first, INT32_MAX, cap, h->c.stream));
+  HIPCHK(hipMemsetAsync(h->seenStamp, 0, 4 * cap, h->c.stream));
+  h->stamp = 0;
+  h->rowsetCap = cap;
+  return YDORB_OK;
+}
+
 // the table and the point attributes as the queries of map_queries.h read them: call after sync(), which may move the arenas
 mapmaint::MapSource sourceOf(const ydorb_mapdb* h) {
   mapmaint::MapSource src;
@@ -163,11 +248,14 @@ extern "C" int ydorb_mapdb_create(int32_t device, int32_t point_capacity, int32_
   h->device = device;
   if (!(rc = h->c.init(device)) && !(rc = allocPoints(h->c.stream, h->points, h->T, (size_t)h->host.pointCap())) &&
       !(rc = allocCentres(h->c.stream, h->centres, h->T.centre, (size_t)h->host.kfCap())) &&
-      !(rc = allocPool(h->pool, h->poolKf, h->poolLevel, (size_t)h->host.poolCap())) && hipStreamSynchronize(h->c.stream) != hipSuccess) {
+      !(rc = allocPool(h->pool, h->poolKf, h->poolLevel, (size_t)h->host.poolCap())) &&
+      !(rc = allocRowHeaders(h->c.stream, h->rowHdr, h->rowStart, h->rowLen, (size_t)h->rows.hdrCap())) &&
+      !(rc = h->rowPoolMem.alloc(4 * (size_t)h->rows.poolCap())) && hipStreamSynchronize(h->c.stream) != hipSuccess) {
     set_error("hipStreamSynchronize failed");
     rc = YDORB_ERR_HIP;
   }
   if (rc) { ydorb_mapdb_destroy(h); return rc; }
+  h->rowPool = h->rowPoolMem.as<int>();
   *out = h;
   return YDORB_OK;
 }
@@ -178,6 +266,7 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   if (h->c.stream) { (void)hipStreamSynchronize(h->c.stream); (void)hipStreamDestroy(h->c.stream); }
   h->c.releaseBuffers();
   h->points.release(); h->centres.release(); h->pool.release(); h->delta.release(); h->hDelta.release();
+  h->rowHdr.release(); h->rowPoolMem.release(); h->rowDelta.release(); h->hRowDelta.release(); h->rowset.release();
   delete h;
 }
 
@@ -186,7 +275,14 @@ extern "C" int ydorb_mapdb_clear(ydorb_mapdb_t* h) {
   std::lock_guard<std::mutex> lock(h->c.mu);
   HIPCHK(hipSetDevice(h->device));
   h->host.clear();
+  h->rows.clear();
   hipStream_t s = h->c.stream;   // every slot reads as never set again
+  HIPCHK(hipMemsetAsync(h->rowHdr.p, 0, h->rowHdr.cap, s));
+  if (h->rowsetCap) {
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->first, INT32_MAX, h->rowsetCap, s));
+    HIPCHK(hipMemsetAsync(h->seenStamp, 0, 4 * h->rowsetCap, s));
+    h->stamp = 0;
+  }
   HIPCHK(hipMemsetAsync(h->points.p, 0, h->points.cap, s));
   HIPCHK(hipMemsetAsync(h->T.bad, 1, (size_t)h->host.pointCap(), s));
   HIPCHK(hipMemsetAsync(h->centres.p, 0, h->centres.cap, s));
@@ -389,4 +485,166 @@ extern "C" int ydorb_mapdb_export(ydorb_mapdb_t* h, int32_t* obs_start, int32_t*
   }
   if (nk) std::memcpy(centre, at<void>(c.hDown, dCen), 12 * nk);
   return YDORB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ keyframe rows
+extern "C" int ydorb_mapdb_set_keyframe_rows(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n, const int32_t* row_start,
+                                             const int32_t* point_slot) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!h->rows.setRows(kf_slots, n, row_start, point_slot, h->host.nPoints(), err)) return invalid(err);
+  h->host.growKeyframes(h->rows.nKeyframes());
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_set_row_entries(ydorb_mapdb_t* h, const int32_t* kf_slot, const int32_t* idx, const int32_t* point_slot, int32_t n) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  return h->rows.setEntries(kf_slot, idx, point_slot, n, h->host.nPoints(), err) ? YDORB_OK : invalid(err);
+}
+
+extern "C" int ydorb_mapdb_row_stats(ydorb_mapdb_t* h, YdMapDbRowStats* stats) {
+  if (!h || !stats) return invalid("null handle or stats");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  h->rows.stats(*stats);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_export_rows(ydorb_mapdb_t* h, int32_t* row_start, int32_t* point_slot) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (!row_start) return invalid("null row_start");
+  if (h->rows.liveAfterSync() > 0 && !point_slot) return invalid("null point_slot");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  const size_t held = (size_t)h->rows.nKeyframes(), used = (size_t)h->rows.poolUsed();
+  Layout D;
+  const size_t dStart = D.add(4 * held), dLen = D.add(4 * held), dPool = D.add(4 * used);
+  D.add(16);
+  if ((rc = c.hDown.ensure(D.bytes))) return rc;
+  hipStream_t s = c.stream;
+  if (held) {
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dStart), h->rowStart, 4 * held, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dLen), h->rowLen, 4 * held, hipMemcpyDeviceToHost, s));
+  }
+  if (used) HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dPool), h->rowPool, 4 * used, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  mapdb::flattenRows(h->host.nKeyframes(), (int32_t)held, at<int32_t>(c.hDown, dStart), at<int32_t>(c.hDown, dLen), at<int32_t>(c.hDown, dPool),
+                     row_start, point_slot);
+  return YDORB_OK;
+}
+
+// sync; one upload of the keyframe slots, their starts in E and the seen list; mark, count, emit with no host round trip between
+// them; one read-back; one synchronise.
+extern "C" int ydorb_mapdb_points_of_keyframes(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n_kf, const int32_t* seen_points,
+                                               int32_t n_seen, int32_t capacity, int32_t* out_slots, uint8_t* out_seen, int32_t* count,
+                                               uint8_t* status) {
+  if (n_kf < 0 || n_seen < 0 || capacity < 0) return invalid("negative n_kf, n_seen or capacity");
+  if (!count || !status) return invalid("null count or status");
+  if ((n_kf > 0 && !kf_slots) || (n_seen > 0 && !seen_points)) return invalid("null kf_slots or seen_points");
+  if (capacity > 0 && (!out_slots || !out_seen)) return invalid("null out_slots or out_seen");
+  if (!h) {   // without a device no handle exists: say that, there is no CPU path to fall back to
+    const int rc = require_device(0);
+    return rc ? rc : invalid("null handle");
+  }
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!mapdb::RowsHost::checkKfSlots(kf_slots, n_kf, h->host.nKeyframes(), err) ||
+      !mapdb::RowsHost::checkSeen(seen_points, n_seen, h->host.nPoints(), err))
+    return invalid(err);
+  *count = 0; *status = 0;
+  if (n_kf == 0) return YDORB_OK;
+  const size_t nk = (size_t)n_kf, ns = (size_t)n_seen;
+  std::vector<int32_t> eStart(nk + 1, 0);
+  int64_t total = 0;
+  for (size_t r = 0; r < nk; r++) {   // the mirror with its staged rows: what the device holds after the sync below
+    total += h->rows.lenOf(kf_slots[r]);
+    if (total > INT32_MAX) return invalid("the rows of kf_slots hold more than INT32_MAX entries");
+    eStart[r + 1] = (int32_t)total;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  if (total == 0) return YDORB_OK;
+  if ((rc = ensureRowset(h))) return rc;
+  StagedCtx& c = h->c;
+  hipStream_t s = c.stream;
+  if (h->stamp == INT32_MAX) { HIPCHK(hipMemsetAsync(h->seenStamp, 0, 4 * h->rowsetCap, s)); h->stamp = 0; }
+  h->stamp++;
+  const size_t nE = (size_t)total, nB = (nE + mapdb::kRowThreads - 1) / mapdb::kRowThreads, capOut = std::min<size_t>((size_t)capacity, nE);
+  Layout U;
+  const size_t oKf = U.add(4 * nk), oEs = U.add(4 * (nk + 1)), oSeen = U.add(4 * ns);
+  Layout D;
+  const size_t dSlots = D.add(4 * capOut), dSeen = D.add(capOut), dTotal = D.add(4);
+  Layout W;
+  const size_t wEnt = W.add(4 * nE), wBlock = W.add(4 * nB);
+  U.add(16);
+  if ((rc = c.ensure(U.bytes, D.bytes, W.bytes))) return rc;
+  std::memcpy(at<void>(c.hUp, oKf), kf_slots, 4 * nk);
+  std::memcpy(at<void>(c.hUp, oEs), eStart.data(), 4 * (nk + 1));
+  if (ns) std::memcpy(at<void>(c.hUp, oSeen), seen_points, 4 * ns);
+  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  mapdb::RowsetArgs a;
+  a.nKf = n_kf; a.nE = (int)nE; a.nSeen = n_seen; a.stamp = h->stamp; a.capacity = (int)capOut; a.nBlocks = (int)nB;
+  a.kfSlots = at<int>(c.up, oKf); a.eStart = at<int>(c.up, oEs); a.seen = at<int>(c.up, oSeen);
+  a.rowStart = h->rowStart; a.rowLen = h->rowLen; a.pool = h->rowPool; a.bad = h->T.bad;
+  a.first = h->first; a.seenStamp = h->seenStamp;
+  a.ent = at<int>(c.scratch, wEnt); a.blockTotal = at<int>(c.scratch, wBlock);
+  a.outSlots = at<int>(c.down, dSlots); a.outSeen = at<uint8_t>(c.down, dSeen); a.total = at<int>(c.down, dTotal);
+  const size_t forMark = (std::max(nE, ns) + mapdb::kRowThreads - 1) / mapdb::kRowThreads;
+  hipLaunchKernelGGL(mapdb::k_rowset_mark, dim3((unsigned)forMark), dim3(mapdb::kRowThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mapdb::k_rowset_count, dim3((unsigned)nB), dim3(mapdb::kRowThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mapdb::k_rowset_emit, dim3((unsigned)nB), dim3(mapdb::kRowThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const int32_t kept = *at<int32_t>(c.hDown, dTotal);
+  *count = kept;
+  if (kept > capacity) { *status = 1; return YDORB_OK; }
+  if (kept) { std::memcpy(out_slots, at<void>(c.hDown, dSlots), 4 * (size_t)kept); std::memcpy(out_seen, at<void>(c.hDown, dSeen), (size_t)kept); }
+  return YDORB_OK;
+}
+
+// k_covisibility with a self slot of -1 (no keyframe is excluded: a Frame is not in the table), over the lists without their -1 entries
+extern "C" int ydorb_mapdb_observer_counter(ydorb_mapdb_t* h, int32_t n_lists, const int32_t* list_start, const int32_t* point_slots,
+                                            const int32_t* out_start, int32_t* conn_kf, int32_t* conn_weight, int32_t* counts,
+                                            uint8_t* status, uint8_t* point_bad) {
+  std::string err;
+  if (n_lists < 0) return invalid("negative number of lists: " + std::to_string(n_lists));
+  if (!maptable::checkStarts("list_start", list_start, n_lists, err) || !maptable::checkStarts("out_start", out_start, n_lists, err)) return invalid(err);
+  const int32_t L = list_start[n_lists];
+  if (L > 0 && (!point_slots || !point_bad)) return invalid("null point_slots or point_bad");
+  if (n_lists > 0 && (!counts || !status)) return invalid("null counts or status");
+  if (out_start[n_lists] > 0 && (!conn_kf || !conn_weight)) return invalid("null conn_kf or conn_weight");
+  if (!h) {
+    const int rc = require_device(0);
+    return rc ? rc : invalid("null handle");
+  }
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  for (int32_t e = 0; e < L; e++)
+    if (point_slots[e] < -1 || point_slots[e] >= h->host.nPoints())
+      return invalid("list entry " + std::to_string(e) + ": point slot " + std::to_string(point_slots[e]) + " outside -1.." + std::to_string(h->host.nPoints() - 1));
+  if (n_lists == 0) return YDORB_OK;
+  const size_t nl = (size_t)n_lists;
+  std::vector<int32_t> self(nl, -1), ls(nl + 1, 0), idx;
+  idx.reserve((size_t)L);
+  for (size_t q = 0; q < nl; q++) {
+    for (int32_t e = list_start[q]; e < list_start[q + 1]; e++) {
+      const int32_t p = point_slots[e];
+      point_bad[e] = p >= 0 && h->host.isBad(p) ? 1 : 0;   // the mirror with its staged points: what the device holds after the sync
+      if (p >= 0) idx.push_back(p);
+    }
+    ls[q + 1] = (int32_t)idx.size();
+  }
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  mapmaint::MapSource src = sourceOf(h);
+  return mapmaint::runCovisibility(h->c, src, self.data(), n_lists, ls.data(), idx.data(), out_start, conn_kf, conn_weight, counts, status);
 }

@@ -97,7 +97,12 @@ class Host {
   int64_t poolCap() const { return poolCap_; }
   int64_t poolUsed() const { return poolUsed_; }
   int64_t liveAfterSync() const { return pendingLive_; }
-  bool dirty() const { return !dirtyPoints_.empty() || !dirtyKf_.empty(); }
+  bool dirty() const { return !dirtyPoints_.empty() || !dirtyKf_.empty() || nKeyframes() != nKfSynced_; }
+  bool isBad(int32_t slot) const { return bad_[slot] != 0; }   // staged changes included
+  // keyframe rows (mapdb_rows_host.h) named slots up to n - 1: the new slots' centres are zero, as the device's are, and no record travels
+  void growKeyframes(int32_t n) {
+    if (n > nKeyframes()) { centre_.resize(3 * (size_t)n, 0.f); kfDirty_.resize((size_t)n, 0); }
+  }
   int32_t spanOf(int32_t slot) const { return state_[slot] == kFull ? stLen_[slot] : len_[slot]; }   // staged changes included
 
   void clear() {

@@ -1,13 +1,14 @@
 """The resident map table through the C ABI (include/ydorb/c_api.h, "Resident map table"): the observation table
 of map maintenance kept in HBM between calls, changed by deltas and queried with no table upload.  MapDb owns one ydorb_mapdb_t.  Its
 three queries go through map_maintenance's own wrappers (same argument preparation, same result dictionaries), with the handle in place
-of the flat table.  MapDb.correct (ydorb_mapdb_correct) runs the point loops of loop closing on the table in place."""
+of the flat table.  MapDb.correct (ydorb_mapdb_correct) runs the point loops of loop closing on the table in place.
+The keyframe rows add the relation keyframe -> map points and the two set queries of Tracking::updateLocalMap."""
 import ctypes as C
 
 import numpy as np
 
 from . import map_maintenance as M
-from ._lib import YdMapCorrection, YdMapDbStats, check, lib
+from ._lib import YdMapCorrection, YdMapDbRowStats, YdMapDbStats, check, lib
 
 _p = M._p
 
@@ -138,6 +139,61 @@ class MapDb:
                                       centre_after, centres, scale_factors)
         check(lib().ydorb_mapdb_correct(self._h, C.byref(corr)))
         return out
+
+    # ------------------------------------------------------------------------------------------------------------ keyframe rows
+    def set_keyframe_rows(self, kf_slots, rows):
+        """rows[i] = the map-point vector of keyframe slot kf_slots[i] as point slots in keypoint order, -1 = null; an empty row erases."""
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        assert len(rows) == len(kf_slots)
+        start, slot = M._csr(rows, np.int32)
+        check(lib().ydorb_mapdb_set_keyframe_rows(self._h, _p(kf_slots), len(kf_slots), _p(start), _p(slot)))
+
+    def set_row_entries(self, kf_slot, idx, point_slot):
+        kf_slot, idx, point_slot = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (kf_slot, idx, point_slot))
+        assert len(kf_slot) == len(idx) == len(point_slot)
+        check(lib().ydorb_mapdb_set_row_entries(self._h, _p(kf_slot), _p(idx), _p(point_slot), len(kf_slot)))
+
+    def row_stats(self):
+        s = YdMapDbRowStats()
+        check(lib().ydorb_mapdb_row_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in YdMapDbRowStats._fields_}
+
+    def export_rows(self):
+        """The device's rows read back: one int32 array per keyframe slot 0 .. n_keyframes-1."""
+        k, n = self.n_keyframes, self.row_stats()["n_entries"]
+        start, slot = np.zeros(k + 1, np.int32), np.zeros(max(n, 1), np.int32)
+        check(lib().ydorb_mapdb_export_rows(self._h, _p(start), _p(slot)))
+        assert int(start[-1]) == n
+        return [slot[start[i]:start[i + 1]].copy() for i in range(k)]
+
+    def points_of_keyframes(self, kf_slots, seen_points=None, capacity=None):
+        """ydorb_mapdb_points_of_keyframes.  capacity None = what always fits.  Returns dict(slots, seen, count, status); slots / seen
+        are empty when status is 1."""
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        seen = np.zeros(0, np.int32) if seen_points is None else np.ascontiguousarray(seen_points, np.int32).reshape(-1)
+        if capacity is None:
+            capacity = self.n_points
+        out, flag = np.full(max(capacity, 1), -7, np.int32), np.full(max(capacity, 1), 7, np.uint8)
+        count, status = C.c_int32(-1), C.c_uint8(9)
+        check(lib().ydorb_mapdb_points_of_keyframes(self._h, _p(kf_slots), len(kf_slots), _p(seen) if len(seen) else None, len(seen), capacity,
+                                                    _p(out), _p(flag), C.byref(count), C.byref(status)))
+        n = count.value if status.value == 0 else 0
+        return dict(slots=out[:n], seen=flag[:n], count=count.value, status=status.value, raw_slots=out, raw_seen=flag)
+
+    def observer_counter(self, lists, capacities=None):
+        """ydorb_mapdb_observer_counter.  lists[q] = point slots (-1 allowed).  capacities None = n_keyframes per list.  Returns
+        dict(kf, weight [per list], counts, status, point_bad [per list])."""
+        nl = len(lists)
+        ls, idx = M._csr(lists, np.int32)
+        caps = [self.n_keyframes] * nl if capacities is None else list(capacities)
+        os_ = np.concatenate([[0], np.cumsum(caps)]).astype(np.int32)
+        tot = int(os_[-1])
+        kf, w = np.full(max(tot, 1), -7, np.int32), np.full(max(tot, 1), -7, np.int32)
+        counts, status, pbad = np.zeros(max(nl, 1), np.int32), np.zeros(max(nl, 1), np.uint8), np.zeros(max(len(idx), 1), np.uint8)
+        check(lib().ydorb_mapdb_observer_counter(self._h, nl, _p(ls), _p(idx), _p(os_), _p(kf), _p(w), _p(counts), _p(status), _p(pbad)))
+        take = [int(counts[q]) if status[q] == 0 else 0 for q in range(nl)]
+        return dict(kf=[kf[os_[q]:os_[q] + take[q]] for q in range(nl)], weight=[w[os_[q]:os_[q] + take[q]] for q in range(nl)],
+                    counts=counts[:nl], status=status[:nl], point_bad=[pbad[ls[q]:ls[q + 1]] for q in range(nl)], raw_kf=kf, raw_weight=w)
 
     # ------------------------------------------------------------------------------------------------------------ inspection
     def stats(self):
