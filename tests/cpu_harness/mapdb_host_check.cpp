@@ -21,16 +21,12 @@
 
 #include "../../ydorbslam_amd/csrc/mapdb_host.h"
 
+constexpr int kNameWidth = 52;
+#include "check_common.h"
+
 using namespace ydorb::mapdb;
 
-static int g_failed = 0;
 static FILE* g_ops = nullptr;
-
-static void expect(const char* name, bool ok, const std::string& err, const char* needle) {
-  const bool pass = needle ? (!ok && err.find(needle) != std::string::npos) : ok;
-  printf("%-52s %s%s%s\n", name, pass ? "ok" : "FAILED", err.empty() ? "" : ": ", err.c_str());
-  if (!pass) g_failed++;
-}
 
 static int32_t bits(float f) { int32_t b; memcpy(&b, &f, 4); return b; }
 
@@ -40,14 +36,7 @@ struct Db {   // the handle without a device: the Host and the arrays the kernel
   std::vector<uint8_t> delta;
   Plan last;
   Db(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc) {}
-  void sync() {
-    if (!host.dirty()) { host.nothingToSync(); return; }
-    last = host.plan();
-    delta.assign(last.bytes + 1, 0xee);   // one guard byte: pack() must stay inside P.bytes
-    host.pack(last, delta.data());
-    if (delta[last.bytes] != 0xee) { printf("pack wrote past the delta FAILED\n"); g_failed++; }
-    execute(last, delta.data(), T);
-  }
+  void sync() { syncOnHost(host, last, delta, [this](const Plan& P, const uint8_t* d) { execute(P, d, T); }); }
   YdMapDbStats stats() const { YdMapDbStats s; host.stats(s); return s; }
 };
 

@@ -21,16 +21,12 @@
 #include "../../ydorbslam_amd/csrc/mapdb_rows_host.h"
 #include "../localmap_ref/localmap_ref.cpp"
 
+constexpr int kNameWidth = 60;
+#include "check_common.h"
+
 using namespace ydorb::mapdb;
 
-static int g_failed = 0;
 static FILE* g_ops = nullptr;
-
-static void expect(const char* name, bool ok, const std::string& err, const char* needle) {
-  const bool pass = needle ? (!ok && err.find(needle) != std::string::npos) : ok;
-  printf("%-60s %s%s%s\n", name, pass ? "ok" : "FAILED", err.empty() ? "" : ": ", err.c_str());
-  if (!pass) g_failed++;
-}
 
 constexpr int32_t kPoints = 500;   // the point table the rows name: slots 0 .. 499 (the GPU replay sets them first)
 
@@ -40,14 +36,7 @@ struct Db {   // the handle's rows without a device
   std::vector<uint8_t> delta;
   RowPlan last;
   Db(int32_t kc, int64_t oc) : rows(kc, oc) {}
-  void sync() {
-    if (!rows.dirty()) { rows.nothingToSync(); return; }
-    last = rows.plan();
-    delta.assign(last.bytes + 1, 0xee);   // one guard byte: pack() must stay inside P.bytes
-    rows.pack(last, delta.data());
-    if (delta[last.bytes] != 0xee) { printf("pack wrote past the delta FAILED\n"); g_failed++; }
-    executeRows(last, delta.data(), T);
-  }
+  void sync() { syncOnHost(rows, last, delta, [this](const RowPlan& P, const uint8_t* d) { executeRows(P, d, T); }); }
   YdMapDbRowStats stats() const { YdMapDbRowStats s; rows.stats(s); return s; }
   std::vector<std::vector<int32_t>> exported() const {
     const int32_t n = rows.nKeyframes();

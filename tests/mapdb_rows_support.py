@@ -8,6 +8,7 @@ import tempfile
 
 import numpy as np
 
+from mapdb_support import check_ops
 from mapmaint_support import ROOT, _flags
 
 CHECK_SRC = os.path.join(ROOT, "tests", "cpu_harness", "mapdb_rows_check.cpp")
@@ -32,10 +33,7 @@ def parse_trace(lines):
 def sequence(tmp):
     """Runs the check program and returns its operations, one list per round: ("R", kf_slots, rows), ("E", kf, idx, slot), each round
     closed by ("S", trace)."""
-    exe, ops = os.path.join(tmp, "mapdb_rows_check"), os.path.join(tmp, "ops.txt")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", CHECK_SRC, "-o", exe])
-    subprocess.run([exe, ops], stdout=subprocess.DEVNULL, check=True)
-    lines = open(ops).read().splitlines()
+    lines = check_ops(CHECK_SRC, tmp)
     rounds, cur, at = [], [], 0
     while at < len(lines):
         w = lines[at].split()

@@ -28,13 +28,18 @@ def _f32(words):
     return np.array([int(w) for w in words], np.int32).view(np.float32)
 
 
+def check_ops(src, tmp):
+    """Builds a check program of tests/cpu_harness without sanitizers, runs it and returns the lines of the operations file it wrote."""
+    exe, ops = os.path.join(tmp, os.path.splitext(os.path.basename(src))[0]), os.path.join(tmp, "ops.txt")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", src, "-o", exe])
+    subprocess.run([exe, ops], stdout=subprocess.DEVNULL, check=True)
+    return open(ops).read().splitlines()
+
+
 def sequence(tmp):
     """Runs the check program and returns its operations, one list per round: ("C", slots, centre), ("P", slots, observers, levels, bad,
     ref_kf, ref_level, pos), ("X", slots, pos), each round closed by ("S", trace)."""
-    exe, ops = os.path.join(tmp, "mapdb_host_check"), os.path.join(tmp, "ops.txt")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", CHECK_SRC, "-o", exe])
-    subprocess.run([exe, ops], stdout=subprocess.DEVNULL, check=True)
-    lines = open(ops).read().splitlines()
+    lines = check_ops(CHECK_SRC, tmp)
     rounds, cur, at = [], [], 0
     while at < len(lines):
         w = lines[at].split()

@@ -1,7 +1,8 @@
 """The resident map table without a GPU: the sanitized stand-alone check of ydorbslam_amd/csrc/mapdb_host.h (validation, coalescing,
-delta packing, pool policy and the seeded state-machine sequence against a naive model, tests/cpu_harness/mapdb_host_check.cpp), what
-the C entries do on a machine with no device, and the adapter's type check.  The program is its own process: nothing is loaded into
-this one under a sanitizer."""
+delta packing, pool policy and the seeded state-machine sequence against a naive model, tests/cpu_harness/mapdb_host_check.cpp), that
+of the pool policy on its own (ydorbslam_amd/csrc/span_pool.h, tests/cpu_harness/span_pool_check.cpp), what the C entries do on a
+machine with no device, and the adapter's type check.  Each program is its own process: nothing is loaded into this one under a
+sanitizer."""
 import ctypes as C
 import os
 import subprocess
@@ -12,15 +13,18 @@ import mapdb_support as D
 from mapmaint_support import ROOT
 
 
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("mapdb") / "mapdb_host_check")
+def _sanitized_report(src, exe):
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", D.CHECK_SRC, "-o", exe])
+                           "-fno-sanitize-recover=undefined", src, "-o", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     print(r.stdout)
     assert r.returncode == 0, r.stdout
     return r.stdout.splitlines()
+
+
+@pytest.fixture(scope="module")
+def report(tmp_path_factory):
+    return _sanitized_report(D.CHECK_SRC, str(tmp_path_factory.mktemp("mapdb") / "mapdb_host_check"))
 
 
 def _case(report, name):
@@ -67,6 +71,24 @@ def test_the_seeded_sequence_equals_the_model_and_meets_every_path(report):
     last = trace[-1]
     assert min(last["repacks_kept"], last["repacks_grown"], last["point_table_growths"], last["keyframe_table_growths"]) >= 1
     assert last["n_points"] > 900 and min(t["n_observations"] for t in trace) < trace[0]["n_observations"] * 0.6      # half of the spans went empty once
+
+
+def test_span_pool_check_runs_clean_under_the_sanitizers(tmp_path):
+    """Every rule of span_pool.h at the smallest numbers at which it can go wrong: the case names are the rules."""
+    report = _sanitized_report(os.path.join(ROOT, "tests", "cpu_harness", "span_pool_check.cpp"), str(tmp_path / "span_pool_check"))
+    assert report[-1] == "0 failed" and len(report) == 37 and not any("FAILED" in ln for ln in report)
+    for name in ("used + incoming == capacity: no repack, tail = used", "used + incoming == capacity + 1: repack, tail = survivors",
+                 "capacity 8: need 4 keeps the capacity", "capacity 8: need 5 grows it to 10", "capacity 9: need 4 keeps the capacity",
+                 "capacity 9: need 5 grows it to 10", "need 2^30 + 1: the capacity is INT32_MAX", "all live entries replaced: survivors 0, tail 0 on repack",
+                 "nothing incoming with a full pool: no repack", "commit without a repack: no counter moves", "commit of a kept repack: live, used, one counter",
+                 "commit of a grown repack: live, used, the other counter", "survivors in ascending slot order", "a replaced slot gets -1, adds nothing",
+                 "a zero-length survivor shares the next slot's offset", "the last offset plus its length equals the survivors",
+                 "table growth: needed <= capacity is unchanged", "table growth: capacity + 1 gives 2 x capacity",
+                 "table growth: 3 x capacity gives 3 x capacity", "table growth: capacity 2^30 + 1 gives INT32_MAX", "a total of INT32_MAX passes",
+                 "one slot named twice counts its last length only", "delta sections: 16-byte aligned"):
+        _case(report, name)
+    assert "the pool would hold 2147483648 observations, past INT32_MAX" in _case(report, "INT32_MAX + 1 observations")
+    assert "the row pool would hold 2147483648 entries, past INT32_MAX" in _case(report, "INT32_MAX + 1 row entries")
 
 
 def test_create_without_a_device_is_no_device_and_bad_arguments_come_first():

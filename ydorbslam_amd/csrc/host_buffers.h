@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/ydorb/c_api.h"
+#include "layout.h"
 #include "ydorb_host.h"
 
 // A macro, so that __FILE__ / __LINE__ name the call site.
@@ -67,14 +68,6 @@ struct ScopedMem : Mem {   // for function-local buffers only (see Mem)
 };
 
 template <class T> T* at(Mem& m, size_t off) { return m.at<T>(off); }
-
-// Lays arrays out at aligned offsets of one area: the same offsets address the pinned staging and the device copy.  `align` is a
-// power of two, set before the first add(): 16 bytes serve any element type; the arenas (Carve) ask for 256 so that every array of
-// one starts on the boundary a buffer of its own had (hipMalloc returns at least that).
-struct Layout {
-  size_t bytes = 0, align = 16;
-  size_t add(size_t n) { const size_t at = bytes; bytes += (n + align - 1) & ~(align - 1); return at; }
-};
 
 // Hands out the arrays of an arena in order, every one 256-byte aligned.  A driver's lay*() functions run twice per (re)layout: over a
 // null base for the size the arena needs, then over the arena for the pointers.

@@ -1,8 +1,9 @@
 // Host driver of the resident map table + its C ABI (include/ydorb/c_api.h, "Resident map table").  The handle
 // owns the slot tables, the camera centres and the observation pool in device arenas, and mapdb_host.h's Host, which validates, stages
-// and plans.  The set_* entries only stage.  A query, on the handle's one stream: if anything is staged, one upload of the packed delta,
-// the table growths (device-to-device copies), k_mapdb_repack if the pool needs it and k_mapdb_apply; then the query's own arrays in one
-// upload, the pass of map_kernels.hip.h, one read-back and one synchronise.  With nothing staged no table byte moves.
+// and plans (the pool policy of both state machines: span_pool.h).  The set_* entries only stage.  A query, on the handle's one stream:
+// if anything is staged, one upload of the packed delta, the table growths (device-to-device copies), k_mapdb_repack if the pool needs
+// it and k_mapdb_apply; then the query's own arrays in one upload, the pass of map_kernels.hip.h, one read-back and one synchronise.
+// With nothing staged no table byte moves.
 // ydorb_mapdb_correct (mapcorrect_kernels.hip.h) is the one query that writes the table: positions in place, then centres.
 // The keyframe rows (mapdb_rows_host.h, mapdb_rows_kernels.hip.h) are a second state machine in the same handle,
 // synced after the points under the same mutex: ydorb_mapdb_points_of_keyframes and ydorb_mapdb_observer_counter at the end of this file.
@@ -26,20 +27,26 @@
 
 using namespace ydorb;
 
+struct DeltaPair {   // a packed delta on the device and its pinned staging; never empty: rows may grow the keyframe count alone
+  Mem dev;
+  PinnedMem host;
+  int ensure(size_t bytes) { const int rc = dev.ensure(bytes + 16); return rc ? rc : host.ensure(bytes + 16); }
+  void release() { dev.release(); host.release(); }
+};
+
 struct ydorb_mapdb {
   int device = 0;
   StagedCtx c;                 // c.mu: LocalMapping stages while LoopClosing queries.  c.up / c.down: a query's arrays and results
   mapdb::Host host;
   Mem points, centres, pool;   // arenas: T and the pool pointers point into them
-  Mem delta;                   // the packed delta on the device, staged in hDelta
-  PinnedMem hDelta;
+  DeltaPair delta;
   mapdb::SlotTables T{};
   int* poolKf = nullptr;
   uint8_t* poolLevel = nullptr;
   // keyframe rows: a state machine, arenas and a delta of their own
   mapdb::RowsHost rows;
-  Mem rowHdr, rowPoolMem, rowDelta, rowset;   // rowset: first / seenStamp of the points-of-keyframes query, one entry per point slot
-  PinnedMem hRowDelta;
+  Mem rowHdr, rowPoolMem, rowset;   // rowset: first / seenStamp of the points-of-keyframes query, one entry per point slot
+  DeltaPair rowDelta;
   int *rowStart = nullptr, *rowLen = nullptr, *rowPool = nullptr, *first = nullptr, *seenStamp = nullptr;
   size_t rowsetCap = 0;
   int stamp = 0;
@@ -99,6 +106,22 @@ int allocRowHeaders(hipStream_t s, Mem& m, int*& rowStart, int*& rowLen, size_t 
 #define D2D(dst, src, bytes) \
   do { if ((bytes) > 0) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, s)); } while (0)
 
+// The blocks of an apply kernel: a lane per fixed record; over the payload 2048 blocks at the most, lanes stride past that
+unsigned applyBlocks(size_t nFixed, int64_t nPayload, size_t threads) {
+  const size_t forFixed = (nFixed + threads - 1) / threads, forPayload = std::min<size_t>(((size_t)nPayload + threads - 1) / threads, 2048);
+  return (unsigned)std::max<size_t>(std::max(forFixed, forPayload), 1);
+}
+
+// The end of a sync: what was enqueued still reads the old arenas, so the stream drains before the handle takes each new one made
+struct NewArena { Mem* mine; ScopedMem* fresh; };
+int handOver(hipStream_t s, std::initializer_list<NewArena> arenas) {
+  bool any = false;
+  for (const NewArena& a : arenas) any = any || a.fresh->p;
+  if (any) HIPCHK(hipStreamSynchronize(s));
+  for (const NewArena& a : arenas) if (a.fresh->p) a.mine->take(*a.fresh);
+  return YDORB_OK;
+}
+
 // Applies what is staged.  Called with the mutex held and the device set; everything it enqueues goes to the handle's stream, and the
 // arenas it replaces are freed only after that stream has drained.
 int syncPoints(ydorb_mapdb* h) {
@@ -106,22 +129,16 @@ int syncPoints(ydorb_mapdb* h) {
   hipStream_t s = h->c.stream;
   const mapdb::Plan P = h->host.plan();
   int rc;
-  if ((rc = h->delta.ensure(P.bytes + 16)) || (rc = h->hDelta.ensure(P.bytes + 16))) return rc;   // never empty: rows may grow the keyframe count alone
+  if ((rc = h->delta.ensure(P.bytes))) return rc;
   ScopedMem newPoints, newCentres, newPool;   // become the handle's arenas below; freed here on an early return
   mapdb::SlotTables T = h->T;
   int* poolKf = h->poolKf;
   uint8_t* poolLevel = h->poolLevel;
-  if (P.pointCap != P.pointCapBefore) {
-    if ((rc = allocPoints(s, newPoints, T, (size_t)P.pointCap))) return rc;
-  }
-  if (P.kfCap != P.kfCapBefore) {
-    if ((rc = allocCentres(s, newCentres, T.centre, (size_t)P.kfCap))) return rc;
-  }
-  if (P.repack) {
-    if ((rc = allocPool(newPool, poolKf, poolLevel, (size_t)P.poolCap))) return rc;
-  }
-  h->host.pack(P, h->hDelta.as<uint8_t>());   // nothing below can be refused for a reason of the caller's: the delta counts as applied
-  if (P.bytes) HIPCHK(hipMemcpyAsync(h->delta.p, h->hDelta.p, P.bytes, hipMemcpyHostToDevice, s));
+  if (P.pointCap != P.pointCapBefore && (rc = allocPoints(s, newPoints, T, (size_t)P.pointCap))) return rc;
+  if (P.kfCap != P.kfCapBefore && (rc = allocCentres(s, newCentres, T.centre, (size_t)P.kfCap))) return rc;
+  if (P.repack && (rc = allocPool(newPool, poolKf, poolLevel, (size_t)P.poolCap))) return rc;
+  h->host.pack(P, h->delta.host.as<uint8_t>());   // nothing below can be refused for a reason of the caller's: the delta counts as applied
+  if (P.bytes) HIPCHK(hipMemcpyAsync(h->delta.dev.p, h->delta.host.p, P.bytes, hipMemcpyHostToDevice, s));
   if (newPoints.p) {
     const size_t n = (size_t)P.nPointsBefore;
     D2D(T.start, h->T.start, 4 * n); D2D(T.end, h->T.end, 4 * n); D2D(T.refKf, h->T.refKf, 4 * n); D2D(T.pos, h->T.pos, 12 * n);
@@ -130,7 +147,7 @@ int syncPoints(ydorb_mapdb* h) {
   if (newCentres.p) D2D(T.centre, h->T.centre, 12 * (size_t)P.nKeyframesBefore);
   if (P.repack && P.nPointsBefore > 0) {
     mapdb::RepackArgs a;
-    a.nPoints = P.nPointsBefore; a.start = T.start; a.end = T.end; a.newOff = at<int>(h->delta, P.oNewOff);
+    a.nPoints = P.nPointsBefore; a.start = T.start; a.end = T.end; a.newOff = at<int>(h->delta.dev, P.oNewOff);
     a.oldKf = h->poolKf; a.oldLevel = h->poolLevel; a.newKf = poolKf; a.newLevel = poolLevel;
     hipLaunchKernelGGL(mapdb::k_mapdb_repack, dim3((unsigned)((P.nPointsBefore + mapdb::kThreads - 1) / mapdb::kThreads)), dim3(mapdb::kThreads), 0, s, a);
     HIPCHK(hipGetLastError());
@@ -139,21 +156,14 @@ int syncPoints(ydorb_mapdb* h) {
     mapdb::ApplyArgs a;
     a.t = T;
     a.nPointRec = P.nPointRec; a.nPosRec = P.nPosRec; a.nCentreRec = P.nCentreRec; a.nPayload = (int)P.nPayload; a.tail = (int)P.tail;
-    a.point = at<mapdb::PointRec>(h->delta, P.oPoint); a.position = at<mapdb::Vec3Rec>(h->delta, P.oPos); a.centre = at<mapdb::Vec3Rec>(h->delta, P.oCentre);
-    a.payKf = at<int>(h->delta, P.oPayKf); a.payLevel = at<uint8_t>(h->delta, P.oPayLevel);
+    a.point = at<mapdb::PointRec>(h->delta.dev, P.oPoint); a.position = at<mapdb::Vec3Rec>(h->delta.dev, P.oPos); a.centre = at<mapdb::Vec3Rec>(h->delta.dev, P.oCentre);
+    a.payKf = at<int>(h->delta.dev, P.oPayKf); a.payLevel = at<uint8_t>(h->delta.dev, P.oPayLevel);
     a.poolKf = poolKf; a.poolLevel = poolLevel;
-    const size_t nFixed = (size_t)P.nPointRec + P.nPosRec + P.nCentreRec;
-    const size_t forFixed = (nFixed + mapdb::kThreads - 1) / mapdb::kThreads;
-    const size_t forPayload = std::min<size_t>(((size_t)P.nPayload + mapdb::kThreads - 1) / mapdb::kThreads, 2048);   // lanes stride past that
-    hipLaunchKernelGGL(mapdb::k_mapdb_apply, dim3((unsigned)std::max<size_t>(std::max(forFixed, forPayload), 1)), dim3(mapdb::kThreads), 0, s, a);
+    const unsigned blocks = applyBlocks((size_t)P.nPointRec + P.nPosRec + P.nCentreRec, P.nPayload, mapdb::kThreads);
+    hipLaunchKernelGGL(mapdb::k_mapdb_apply, dim3(blocks), dim3(mapdb::kThreads), 0, s, a);
     HIPCHK(hipGetLastError());
   }
-  if (newPoints.p || newCentres.p || newPool.p) {   // the old arenas are still read by what was enqueued
-    HIPCHK(hipStreamSynchronize(s));
-    if (newPoints.p) h->points.take(newPoints);
-    if (newCentres.p) h->centres.take(newCentres);
-    if (newPool.p) h->pool.take(newPool);
-  }
+  if ((rc = handOver(s, {{&h->points, &newPoints}, {&h->centres, &newCentres}, {&h->pool, &newPool}}))) return rc;
   h->T = T; h->poolKf = poolKf; h->poolLevel = poolLevel;
   return YDORB_OK;
 }
@@ -164,42 +174,32 @@ int syncRows(ydorb_mapdb* h) {
   hipStream_t s = h->c.stream;
   const mapdb::RowPlan P = h->rows.plan();
   int rc;
-  if ((rc = h->rowDelta.ensure(P.bytes + 16)) || (rc = h->hRowDelta.ensure(P.bytes + 16))) return rc;
+  if ((rc = h->rowDelta.ensure(P.bytes))) return rc;
   ScopedMem newHdr, newPool;
   int *rowStart = h->rowStart, *rowLen = h->rowLen, *pool = h->rowPool;
-  if (P.hdrCap != P.hdrCapBefore) {
-    if ((rc = allocRowHeaders(s, newHdr, rowStart, rowLen, (size_t)P.hdrCap))) return rc;
-  }
-  if (P.repack) {
-    if ((rc = newPool.alloc(4 * (size_t)P.poolCap))) return rc;
-    pool = newPool.as<int>();
-  }
-  h->rows.pack(P, h->hRowDelta.as<uint8_t>());
-  if (P.bytes) HIPCHK(hipMemcpyAsync(h->rowDelta.p, h->hRowDelta.p, P.bytes, hipMemcpyHostToDevice, s));
+  if (P.hdrCap != P.hdrCapBefore && (rc = allocRowHeaders(s, newHdr, rowStart, rowLen, (size_t)P.hdrCap))) return rc;
+  if (P.repack && (rc = newPool.alloc(4 * (size_t)P.poolCap))) return rc;
+  if (newPool.p) pool = newPool.as<int>();
+  h->rows.pack(P, h->rowDelta.host.as<uint8_t>());
+  if (P.bytes) HIPCHK(hipMemcpyAsync(h->rowDelta.dev.p, h->rowDelta.host.p, P.bytes, hipMemcpyHostToDevice, s));
   if (newHdr.p) { D2D(rowStart, h->rowStart, 4 * (size_t)P.nKfBefore); D2D(rowLen, h->rowLen, 4 * (size_t)P.nKfBefore); }
   if (P.repack && P.nKfBefore > 0) {
     mapdb::RowsRepackArgs a;
-    a.nKf = P.nKfBefore; a.rowStart = rowStart; a.rowLen = rowLen; a.newOff = at<int>(h->rowDelta, P.oNewOff); a.oldPool = h->rowPool; a.newPool = pool;
+    a.nKf = P.nKfBefore; a.rowStart = rowStart; a.rowLen = rowLen; a.newOff = at<int>(h->rowDelta.dev, P.oNewOff); a.oldPool = h->rowPool; a.newPool = pool;
     hipLaunchKernelGGL(mapdb::k_mapdb_rows_repack, dim3((unsigned)((P.nKfBefore + mapdb::kRowWaves - 1) / mapdb::kRowWaves)), dim3(mapdb::kRowThreads), 0, s, a);
     HIPCHK(hipGetLastError());
   }
   {
     mapdb::RowsApplyArgs a;
     a.nHeaderRec = P.nHeaderRec; a.nEntryRec = P.nEntryRec; a.nPayload = (int)P.nPayload; a.tail = (int)P.tail;
-    a.header = at<mapdb::RowHeaderRec>(h->rowDelta, P.oHeader); a.entry = at<mapdb::RowEntryRec>(h->rowDelta, P.oEntry);
-    a.payload = at<int>(h->rowDelta, P.oPayload);
+    a.header = at<mapdb::RowHeaderRec>(h->rowDelta.dev, P.oHeader); a.entry = at<mapdb::RowEntryRec>(h->rowDelta.dev, P.oEntry);
+    a.payload = at<int>(h->rowDelta.dev, P.oPayload);
     a.rowStart = rowStart; a.rowLen = rowLen; a.pool = pool;
-    const size_t nFixed = (size_t)P.nHeaderRec + P.nEntryRec;
-    const size_t forFixed = (nFixed + mapdb::kRowThreads - 1) / mapdb::kRowThreads;
-    const size_t forPayload = std::min<size_t>(((size_t)P.nPayload + mapdb::kRowThreads - 1) / mapdb::kRowThreads, 2048);   // lanes stride past that
-    hipLaunchKernelGGL(mapdb::k_mapdb_rows_apply, dim3((unsigned)std::max<size_t>(std::max(forFixed, forPayload), 1)), dim3(mapdb::kRowThreads), 0, s, a);
+    const unsigned blocks = applyBlocks((size_t)P.nHeaderRec + P.nEntryRec, P.nPayload, mapdb::kRowThreads);
+    hipLaunchKernelGGL(mapdb::k_mapdb_rows_apply, dim3(blocks), dim3(mapdb::kRowThreads), 0, s, a);
     HIPCHK(hipGetLastError());
   }
-  if (newHdr.p || newPool.p) {   // the old arenas are still read by what was enqueued
-    HIPCHK(hipStreamSynchronize(s));
-    if (newHdr.p) h->rowHdr.take(newHdr);
-    if (newPool.p) h->rowPoolMem.take(newPool);
-  }
+  if ((rc = handOver(s, {{&h->rowHdr, &newHdr}, {&h->rowPoolMem, &newPool}}))) return rc;
   h->rowStart = rowStart; h->rowLen = rowLen; h->rowPool = pool;
   return YDORB_OK;
 }
@@ -265,8 +265,8 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   (void)hipSetDevice(h->device);
   if (h->c.stream) { (void)hipStreamSynchronize(h->c.stream); (void)hipStreamDestroy(h->c.stream); }
   h->c.releaseBuffers();
-  h->points.release(); h->centres.release(); h->pool.release(); h->delta.release(); h->hDelta.release();
-  h->rowHdr.release(); h->rowPoolMem.release(); h->rowDelta.release(); h->hRowDelta.release(); h->rowset.release();
+  h->points.release(); h->centres.release(); h->pool.release(); h->delta.release();
+  h->rowHdr.release(); h->rowPoolMem.release(); h->rowDelta.release(); h->rowset.release();
   delete h;
 }
 

@@ -1,5 +1,5 @@
 // Host side of the resident map table (include/ydorb/c_api.h, "Resident map table"): the validation of its
-// entries, the host mirror of the per-slot fixed records, the coalescing of staged changes, the packing of one delta, the pool policy
+// entries, the host mirror of the per-slot fixed records, the coalescing of staged changes, the packing of one delta
 // and a plain-C++ execution of a packed delta on host arrays in the record format the kernels read (mapdb_kernels.hip.h), so that the
 // whole state machine runs without a device (tests/cpu_harness/mapdb_host_check.cpp).  No HIP here: a plain host compiler builds it.
 //   staging   set_points / set_positions / set_centres validate, then write the mirror and mark the slot dirty.  A point slot is clean,
@@ -8,9 +8,7 @@
 //             arena; of a slot staged several times only the last span is packed.
 //   delta     [point records][position records][centre records][payload keyframe slots][payload level bytes][repack offsets], every
 //             section 16-byte aligned.  Records are in the order their slots were first dirtied.
-//   pool      spans are appended at the tail; a replaced span becomes garbage.  When used + incoming > capacity the survivors are
-//             repacked in ascending slot order into a fresh arena: the same capacity when survivors + incoming <= capacity / 2, else
-//             min(2 x (survivors + incoming), INT32_MAX).  The host computes every survivor's new offset; the delta carries them.
+//   pool      the observation spans lie in a span_pool.h SpanPool: the policy, its accounting and the table growth rule are there.
 //   correct   ydorb_mapdb_correct's validation, keyframe rank table and claim pass (planCorrection), and what the mirror takes from the
 //             read-back (correctionApplied): DESIGN.md section 6n.
 #pragma once
@@ -19,16 +17,14 @@
 
 #include <algorithm>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
 #include "map_table.h"
+#include "span_pool.h"
 
 namespace ydorb {
 namespace mapdb {
-
-using maptable::fail;
 
 struct PointRec {   // one fully dirty point
   int32_t slot, off, len, refKf;
@@ -41,17 +37,12 @@ struct Vec3Rec {    // a position or a camera centre
 };
 static_assert(sizeof(PointRec) == 32 && sizeof(Vec3Rec) == 16, "the kernels read these layouts");
 
-enum { kNoRepack = 0, kRepackKept = 1, kRepackGrown = 2 };
-
 // What one sync does, decided before anything is written: the driver sizes its buffers from it, the kernels get their counts from it.
-struct Plan {
+struct Plan : PoolPlan {
   int32_t nPointRec = 0, nPosRec = 0, nCentreRec = 0;
-  int64_t nPayload = 0;
   size_t oPoint = 0, oPos = 0, oCentre = 0, oPayKf = 0, oPayLevel = 0, oNewOff = 0, bytes = 0;
   int32_t nPointsBefore = 0, nKeyframesBefore = 0;   // what the device tables hold: the repack covers the point slots below nPointsBefore
   int32_t pointCapBefore = 0, pointCap = 0, kfCapBefore = 0, kfCap = 0;
-  int repack = kNoRepack;
-  int64_t poolCapBefore = 0, poolCap = 0, usedBefore = 0, survivors = 0, tail = 0;   // the payload goes to [tail, tail + nPayload)
 };
 
 // The arrays the kernels read, on the host: the state-machine check executes deltas on them, the driver flattens its read-back with
@@ -82,21 +73,17 @@ inline void flatten(int32_t nPoints, const int32_t* start, const int32_t* end, c
   }
 }
 
-inline bool checkPoolTotal(int64_t total, std::string& err) {
-  return total <= INT32_MAX ? true : fail(err, "the pool would hold %lld observations, past INT32_MAX", total);
-}
-
 class Host {
  public:
-  Host(int32_t pointCap, int32_t kfCap, int64_t poolCap) : pointCap_(std::max(pointCap, 1)), kfCap_(std::max(kfCap, 1)), poolCap_(std::max<int64_t>(poolCap, 1)) {}
+  Host(int32_t pointCap, int32_t kfCap, int64_t poolCap) : pointCap_(std::max(pointCap, 1)), kfCap_(std::max(kfCap, 1)), pool_(poolCap) {}
 
   int32_t nPoints() const { return (int32_t)len_.size(); }
   int32_t nKeyframes() const { return (int32_t)(centre_.size() / 3); }
   int32_t pointCap() const { return pointCap_; }
   int32_t kfCap() const { return kfCap_; }
-  int64_t poolCap() const { return poolCap_; }
-  int64_t poolUsed() const { return poolUsed_; }
-  int64_t liveAfterSync() const { return pendingLive_; }
+  int64_t poolCap() const { return pool_.cap; }
+  int64_t poolUsed() const { return pool_.used; }
+  int64_t liveAfterSync() const { return pool_.pending; }
   bool dirty() const { return !dirtyPoints_.empty() || !dirtyKf_.empty() || nKeyframes() != nKfSynced_; }
   bool isBad(int32_t slot) const { return bad_[slot] != 0; }   // staged changes included
   // keyframe rows (mapdb_rows_host.h) named slots up to n - 1: the new slots' centres are zero, as the device's are, and no record travels
@@ -109,7 +96,7 @@ class Host {
     len_.clear(); off_.clear(); refKf_.clear(); bad_.clear(); refLevel_.clear(); pos_.clear(); centre_.clear();
     state_.clear(); stOff_.clear(); stLen_.clear(); kfDirty_.clear();
     dropStaged();
-    poolUsed_ = poolLive_ = pendingLive_ = 0;
+    pool_.clear();
     nPointsSynced_ = nKfSynced_ = 0;
     lastSyncBytes_ = lastSyncRecords_ = 0;
   }
@@ -144,27 +131,16 @@ class Host {
     for (int32_t i = 0; i < n; i++)
       if (refKf[i] < 0 || refKf[i] >= nKeyframes())
         return fail(err, "point %lld: reference keyframe slot %lld outside 0..%lld", i, refKf[i], (long long)nKeyframes() - 1);
-    if (pendingLive_ + (int64_t)N > INT32_MAX) {   // only then the exact figure: what the named slots hold now leaves, each slot's last span enters
-      std::unordered_map<int32_t, int32_t> last;
-      for (int32_t i = 0; i < n; i++) last[slots[i]] = obsStart[i + 1] - obsStart[i];
-      int64_t total = pendingLive_;
-      for (const auto& kv : last) total += (int64_t)kv.second - (kv.first < nPoints() ? spanOf(kv.first) : 0);
-      if (!checkPoolTotal(total, err)) return false;
-    }
+    if (!pool_.admits(slots, n, obsStart, [this](int32_t s) { return s < nPoints() ? spanOf(s) : 0; }, checkPoolTotal, err)) return false;
     for (int32_t i = 0; i < n; i++) {
       const int32_t s = slots[i], len = obsStart[i + 1] - obsStart[i];
       growPointsTo(s);
-      if (state_[s] != kFull) {
-        if (state_[s] == kClean) dirtyPoints_.push_back(s);
-        state_[s] = kFull;
-        pendingLive_ -= len_[s];
-      } else {
-        pendingLive_ -= stLen_[s];
-      }
+      pool_.restaged(spanOf(s), len);
+      if (state_[s] == kClean) dirtyPoints_.push_back(s);
+      state_[s] = kFull;
       stOff_[s] = stKf_.size(); stLen_[s] = len;
       stKf_.insert(stKf_.end(), obsKf + obsStart[i], obsKf + obsStart[i] + len);
       stLevel_.insert(stLevel_.end(), obsLevel + obsStart[i], obsLevel + obsStart[i] + len);
-      pendingLive_ += len;
       bad_[s] = bad[i] ? 1 : 0; refKf_[s] = refKf[i]; refLevel_[s] = refLevel[i];
       memcpy(&pos_[3 * (size_t)s], pos + 3 * (size_t)i, 12);
     }
@@ -290,8 +266,8 @@ class Host {
 
   void stats(YdMapDbStats& s) const {
     s.n_points = nPoints(); s.n_keyframes = nKeyframes();
-    s.n_observations = pendingLive_; s.pool_used = poolUsed_; s.pool_capacity = poolCap_;
-    s.repacks_kept = repacksKept_; s.repacks_grown = repacksGrown_;
+    s.n_observations = pool_.pending; s.pool_used = pool_.used; s.pool_capacity = pool_.cap;
+    s.repacks_kept = pool_.repacksKept; s.repacks_grown = pool_.repacksGrown;
     s.point_table_growths = pointGrowths_; s.keyframe_table_growths = kfGrowths_;
     s.point_capacity = pointCap_; s.keyframe_capacity = kfCap_;
     s.last_sync_bytes = lastSyncBytes_; s.last_sync_records = lastSyncRecords_;
@@ -300,32 +276,19 @@ class Host {
 
   Plan plan() const {
     Plan P;
-    P.nPointsBefore = nPointsSynced_; P.nKeyframesBefore = nKfSynced_;
-    P.pointCapBefore = P.pointCap = pointCap_; P.kfCapBefore = P.kfCap = kfCap_;
-    P.poolCapBefore = P.poolCap = poolCap_; P.usedBefore = poolUsed_;
-    int64_t replaced = 0;
+    int64_t replaced = 0, incoming = 0;
     for (const int32_t s : dirtyPoints_) {
-      if (state_[s] == kFull) { P.nPointRec++; P.nPayload += stLen_[s]; replaced += len_[s]; }
+      if (state_[s] == kFull) { P.nPointRec++; incoming += stLen_[s]; replaced += len_[s]; }
       else P.nPosRec++;
     }
-    P.nCentreRec = (int32_t)dirtyKf_.size();
-    if (nPoints() > pointCap_) P.pointCap = (int32_t)std::min<int64_t>(std::max<int64_t>(nPoints(), 2 * (int64_t)pointCap_), INT32_MAX);
-    if (nKeyframes() > kfCap_) P.kfCap = (int32_t)std::min<int64_t>(std::max<int64_t>(nKeyframes(), 2 * (int64_t)kfCap_), INT32_MAX);
-    P.survivors = poolLive_ - replaced;
-    P.tail = poolUsed_;
-    if (poolUsed_ + P.nPayload > poolCap_) {
-      const int64_t need = P.survivors + P.nPayload;   // <= INT32_MAX: set_points refused what would pass it
-      P.repack = need <= poolCap_ / 2 ? kRepackKept : kRepackGrown;
-      if (P.repack == kRepackGrown) P.poolCap = std::min<int64_t>(2 * need, INT32_MAX);
-      P.tail = P.survivors;
-    }
-    size_t at = 0;
-    auto add = [&at](size_t n) { const size_t o = at; at += (n + 15) & ~(size_t)15; return o; };
-    P.oPoint = add(sizeof(PointRec) * (size_t)P.nPointRec); P.oPos = add(sizeof(Vec3Rec) * (size_t)P.nPosRec);
-    P.oCentre = add(sizeof(Vec3Rec) * (size_t)P.nCentreRec);
-    P.oPayKf = add(4 * (size_t)P.nPayload); P.oPayLevel = add((size_t)P.nPayload);
-    P.oNewOff = add(P.repack ? 4 * (size_t)P.nPointsBefore : 0);
-    P.bytes = at;
+    static_cast<PoolPlan&>(P) = pool_.plan(replaced, incoming);
+    P.nCentreRec = (int32_t)dirtyKf_.size(); P.nPointsBefore = nPointsSynced_; P.nKeyframesBefore = nKfSynced_;
+    P.pointCapBefore = pointCap_; P.pointCap = grownCap(nPoints(), pointCap_); P.kfCapBefore = kfCap_; P.kfCap = grownCap(nKeyframes(), kfCap_);
+    Layout L;
+    P.oPoint = L.add(sizeof(PointRec) * (size_t)P.nPointRec); P.oPos = L.add(sizeof(Vec3Rec) * (size_t)P.nPosRec);
+    P.oCentre = L.add(sizeof(Vec3Rec) * (size_t)P.nCentreRec);
+    P.oPayKf = L.add(4 * (size_t)P.nPayload); P.oPayLevel = L.add((size_t)P.nPayload);
+    P.oNewOff = L.add(P.repack ? 4 * (size_t)P.nPointsBefore : 0); P.bytes = L.bytes;
     return P;
   }
 
@@ -333,15 +296,8 @@ class Host {
   // move, the dirty marks go, the counters advance.
   void pack(const Plan& P, uint8_t* dst) {
     memset(dst, 0, P.bytes);
-    if (P.repack) {   // survivors in ascending slot order; a slot this delta replaces is skipped (-1): apply gives it its new span
-      int32_t* newOff = reinterpret_cast<int32_t*>(dst + P.oNewOff);
-      int64_t at = 0;
-      for (int32_t s = 0; s < P.nPointsBefore; s++) {
-        if (state_[s] == kFull) { newOff[s] = -1; continue; }
-        newOff[s] = (int32_t)at; off_[s] = (int32_t)at;
-        at += len_[s];
-      }
-    }
+    if (P.repack)
+      survivorOffsets(P.nPointsBefore, len_.data(), off_.data(), reinterpret_cast<int32_t*>(dst + P.oNewOff), [this](int32_t s) { return state_[s] == kFull; });
     PointRec* pr = reinterpret_cast<PointRec*>(dst + P.oPoint);
     Vec3Rec* qr = reinterpret_cast<Vec3Rec*>(dst + P.oPos);
     int32_t* payKf = reinterpret_cast<int32_t*>(dst + P.oPayKf);
@@ -376,9 +332,7 @@ class Host {
       kfDirty_[k] = 0;
     }
     dropStaged();
-    poolLive_ = P.survivors + P.nPayload; poolUsed_ = P.tail + P.nPayload; poolCap_ = P.poolCap;
-    if (P.repack == kRepackKept) repacksKept_++;
-    if (P.repack == kRepackGrown) repacksGrown_++;
+    pool_.commit(P);
     if (P.pointCap != pointCap_) { pointCap_ = P.pointCap; pointGrowths_++; }
     if (P.kfCap != kfCap_) { kfCap_ = P.kfCap; kfGrowths_++; }
     nPointsSynced_ = nPoints(); nKfSynced_ = nKeyframes();
@@ -405,9 +359,8 @@ class Host {
   std::vector<int32_t> stLen_, dirtyPoints_, dirtyKf_, stKf_;
   std::vector<uint8_t> stLevel_;
   // device capacities and pool use as of the last sync
-  int32_t pointCap_, kfCap_, nPointsSynced_ = 0, nKfSynced_ = 0;
-  int64_t poolCap_, poolUsed_ = 0, poolLive_ = 0, pendingLive_ = 0;
-  int32_t repacksKept_ = 0, repacksGrown_ = 0, pointGrowths_ = 0, kfGrowths_ = 0;
+  int32_t pointCap_, kfCap_, nPointsSynced_ = 0, nKfSynced_ = 0, pointGrowths_ = 0, kfGrowths_ = 0;
+  SpanPool pool_;
   int64_t lastSyncBytes_ = 0, lastSyncRecords_ = 0;
   // the claim pass of planCorrection: a slot is claimed in this call when its stamp is the call's
   std::vector<uint32_t> stamp_;

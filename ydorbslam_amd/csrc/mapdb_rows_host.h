@@ -1,6 +1,6 @@
 // Host side of the resident table's keyframe rows (include/ydorb/c_api.h, "Keyframe rows"): a keyframe's
 // map-point vector as point slots in keypoint order, -1 = a null entry.  Beside mapdb_host.h's Host, a class and a delta of its own:
-// validation, the host mirror of every row, coalescing, the packing of one row delta, the pool policy and a plain-C++ execution of a
+// validation, the host mirror of every row, coalescing, the packing of one row delta and a plain-C++ execution of a
 // packed delta on host arrays in the record format the kernels read (mapdb_rows_kernels.hip.h), so that the state machine runs without
 // a device (tests/cpu_harness/mapdb_rows_check.cpp).  No HIP here: a plain host compiler builds it.
 //   staging   setRows / setEntries validate, then write the mirror.  A row is clean, entry-dirty or fully dirty.  A fully dirty row is
@@ -10,10 +10,8 @@
 //   delta     [header records][entry records][payload point slots][repack offsets], every section 16-byte aligned.  Records are in the
 //             order their rows / entries were first dirtied.  An entry record carries the pool position itself: the host knows where
 //             every row lies once the delta's own repack has run.
-//   pool      mapdb_host.h's policy: rows are appended at the tail, a replaced or erased row becomes garbage; when used + incoming >
-//             capacity the surviving rows are repacked in ascending keyframe slot into a fresh arena, of the same capacity when
-//             survivors + incoming <= capacity / 2, else of min(2 x (survivors + incoming), INT32_MAX).
-//   headers   rowStart / rowLen per keyframe slot, capacity grown like the keyframe table's: max(needed, 2 x capacity).
+//   pool      the rows lie in a SpanPool of their own, a replaced or erased row being its garbage: span_pool.h has the policy, and the
+//             growth rule of the headers (rowStart / rowLen per keyframe slot), which is the keyframe table's.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -25,6 +23,7 @@
 
 #include "../../include/ydorb/c_api.h"
 #include "map_table.h"
+#include "span_pool.h"
 
 namespace ydorb {
 namespace mapdb {
@@ -33,25 +32,16 @@ struct RowHeaderRec { int32_t kf, start, len, pad; };
 struct RowEntryRec { int32_t at, value; };   // at: the pool position
 static_assert(sizeof(RowHeaderRec) == 16 && sizeof(RowEntryRec) == 8, "the kernels read these layouts");
 
-enum { kRowsNoRepack = 0, kRowsRepackKept = 1, kRowsRepackGrown = 2 };
-
-struct RowPlan {
+struct RowPlan : PoolPlan {
   int32_t nHeaderRec = 0, nEntryRec = 0;
-  int64_t nPayload = 0;
   size_t oHeader = 0, oEntry = 0, oPayload = 0, oNewOff = 0, bytes = 0;
   int32_t nKfBefore = 0, hdrCapBefore = 0, hdrCap = 0;   // the device headers hold rows below nKfBefore: the repack covers those
-  int repack = kRowsNoRepack;
-  int64_t poolCapBefore = 0, poolCap = 0, usedBefore = 0, survivors = 0, tail = 0;   // the payload goes to [tail, tail + nPayload)
 };
 
 // the arrays the kernels keep, on the host
 struct RowTables {
   std::vector<int32_t> rowStart, rowLen, pool;
 };
-
-inline bool checkRowPoolTotal(int64_t total, std::string& err) {
-  return total <= INT32_MAX ? true : maptable::fail(err, "the row pool would hold %lld entries, past INT32_MAX", total);
-}
 
 // row_start [nKf + 1] / point_slot from per-slot headers; a slot at or past `nHeld` has no row
 inline void flattenRows(int32_t nKf, int32_t nHeld, const int32_t* rowStart, const int32_t* rowLen, const int32_t* pool, int32_t* outStart,
@@ -68,13 +58,13 @@ inline void flattenRows(int32_t nKf, int32_t nHeld, const int32_t* rowStart, con
 
 class RowsHost {
  public:
-  RowsHost(int32_t hdrCap, int64_t poolCap) : hdrCap_(std::max(hdrCap, 1)), poolCap_(std::max<int64_t>(poolCap, 1)) {}
+  RowsHost(int32_t hdrCap, int64_t poolCap) : hdrCap_(std::max(hdrCap, 1)), pool_(poolCap) {}
 
   int32_t nKeyframes() const { return (int32_t)row_.size(); }   // 1 + the highest slot a row call named
   int32_t hdrCap() const { return hdrCap_; }
-  int64_t poolCap() const { return poolCap_; }
-  int64_t poolUsed() const { return poolUsed_; }
-  int64_t liveAfterSync() const { return pendingLive_; }
+  int64_t poolCap() const { return pool_.cap; }
+  int64_t poolUsed() const { return pool_.used; }
+  int64_t liveAfterSync() const { return pool_.pending; }
   int32_t headerGrowths() const { return hdrGrowths_; }
   bool dirty() const { return !dirtyRows_.empty() || !dirtyEntries_.empty(); }
   int32_t lenOf(int32_t kf) const { return kf < nKeyframes() ? (int32_t)row_[(size_t)kf].size() : 0; }   // staged changes included
@@ -83,14 +73,13 @@ class RowsHost {
   void clear() {
     row_.clear(); off_.clear(); len_.clear(); state_.clear();
     dropStaged();
-    poolUsed_ = poolLive_ = pendingLive_ = 0;
+    pool_.clear();
     nKfSynced_ = 0;
     lastSyncBytes_ = lastSyncRecords_ = 0;
   }
 
   // nPoints: the point table's count with its staged points in it
   bool setRows(const int32_t* kfSlots, int32_t n, const int32_t* rowStart, const int32_t* pointSlot, int32_t nPoints, std::string& err) {
-    using maptable::fail;
     if (n < 0) return fail(err, "negative number of keyframe slots: %lld", n);
     if (!maptable::checkStarts("row_start", rowStart, n, err)) return false;
     if (n == 0) return true;
@@ -102,26 +91,18 @@ class RowsHost {
     for (int32_t q = 0; q < N; q++)
       if (pointSlot[q] < -1 || pointSlot[q] >= nPoints)
         return fail(err, "row entry %lld: point slot %lld outside -1..%lld; set the point before a row names it", q, pointSlot[q], (long long)nPoints - 1);
-    if (pendingLive_ + (int64_t)N > INT32_MAX) {   // only then the exact figure: what the named rows hold now leaves, each row's last value enters
-      std::unordered_map<int32_t, int32_t> last;
-      for (int32_t i = 0; i < n; i++) last[kfSlots[i]] = rowStart[i + 1] - rowStart[i];
-      int64_t total = pendingLive_;
-      for (const auto& kv : last) total += (int64_t)kv.second - lenOf(kv.first);
-      if (!checkRowPoolTotal(total, err)) return false;
-    }
+    if (!pool_.admits(kfSlots, n, rowStart, [this](int32_t k) { return lenOf(k); }, checkRowPoolTotal, err)) return false;
     for (int32_t i = 0; i < n; i++) {
       const int32_t k = kfSlots[i];
       growTo(k);
       if (state_[k] != kFull) { state_[k] = kFull; dirtyRows_.push_back(k); }
-      pendingLive_ -= (int64_t)row_[k].size();
+      pool_.restaged(lenOf(k), rowStart[i + 1] - rowStart[i]);
       row_[k].assign(pointSlot + rowStart[i], pointSlot + rowStart[i + 1]);
-      pendingLive_ += (int64_t)row_[k].size();
     }
     return true;
   }
 
   bool setEntries(const int32_t* kfSlot, const int32_t* idx, const int32_t* pointSlot, int32_t n, int32_t nPoints, std::string& err) {
-    using maptable::fail;
     if (n < 0) return fail(err, "negative number of row entries: %lld", n);
     if (n == 0) return true;
     if (!kfSlot || !idx || !pointSlot) return fail(err, "null kf_slot, idx or point_slot");
@@ -144,7 +125,6 @@ class RowsHost {
 
   // the keyframe slots of a query: below nKfAll, the table's n_keyframes
   static bool checkKfSlots(const int32_t* kfSlots, int32_t n, int32_t nKfAll, std::string& err) {
-    using maptable::fail;
     if (n < 0) return fail(err, "negative number of keyframe slots: %lld", n);
     if (n > 0 && !kfSlots) return fail(err, "null kf_slots");
     for (int32_t i = 0; i < n; i++)
@@ -152,7 +132,6 @@ class RowsHost {
     return true;
   }
   static bool checkSeen(const int32_t* seen, int32_t n, int32_t nPoints, std::string& err) {
-    using maptable::fail;
     if (n < 0) return fail(err, "negative number of seen points: %lld", n);
     if (n > 0 && !seen) return fail(err, "null seen_points");
     for (int32_t i = 0; i < n; i++)
@@ -161,8 +140,8 @@ class RowsHost {
   }
 
   void stats(YdMapDbRowStats& s) const {
-    s.n_entries = pendingLive_; s.pool_used = poolUsed_; s.pool_capacity = poolCap_;
-    s.repacks_kept = repacksKept_; s.repacks_grown = repacksGrown_;
+    s.n_entries = pool_.pending; s.pool_used = pool_.used; s.pool_capacity = pool_.cap;
+    s.repacks_kept = pool_.repacksKept; s.repacks_grown = pool_.repacksGrown;
     s.header_growths = hdrGrowths_; s.header_capacity = hdrCap_;
     s.last_row_sync_bytes = lastSyncBytes_; s.last_row_sync_records = lastSyncRecords_;
   }
@@ -170,43 +149,24 @@ class RowsHost {
 
   RowPlan plan() const {
     RowPlan P;
-    P.nKfBefore = nKfSynced_;
-    P.hdrCapBefore = P.hdrCap = hdrCap_;
-    P.poolCapBefore = P.poolCap = poolCap_; P.usedBefore = poolUsed_;
-    int64_t replaced = 0;
-    for (const int32_t k : dirtyRows_) { P.nHeaderRec++; P.nPayload += (int64_t)row_[k].size(); replaced += len_[k]; }
+    int64_t replaced = 0, incoming = 0;
+    for (const int32_t k : dirtyRows_) { P.nHeaderRec++; incoming += (int64_t)row_[k].size(); replaced += len_[k]; }
     for (const uint64_t key : dirtyEntries_)
       if (state_[(size_t)(key >> 32)] != kFull) P.nEntryRec++;   // a row staged after its entry change carries the entry itself
-    if (nKeyframes() > hdrCap_) P.hdrCap = (int32_t)std::min<int64_t>(std::max<int64_t>(nKeyframes(), 2 * (int64_t)hdrCap_), INT32_MAX);
-    P.survivors = poolLive_ - replaced;
-    P.tail = poolUsed_;
-    if (poolUsed_ + P.nPayload > poolCap_) {
-      const int64_t need = P.survivors + P.nPayload;   // <= INT32_MAX: setRows refused what would pass it
-      P.repack = need <= poolCap_ / 2 ? kRowsRepackKept : kRowsRepackGrown;
-      if (P.repack == kRowsRepackGrown) P.poolCap = std::min<int64_t>(2 * need, INT32_MAX);
-      P.tail = P.survivors;
-    }
-    size_t at = 0;
-    auto add = [&at](size_t n) { const size_t o = at; at += (n + 15) & ~(size_t)15; return o; };
-    P.oHeader = add(sizeof(RowHeaderRec) * (size_t)P.nHeaderRec); P.oEntry = add(sizeof(RowEntryRec) * (size_t)P.nEntryRec);
-    P.oPayload = add(4 * (size_t)P.nPayload);
-    P.oNewOff = add(P.repack ? 4 * (size_t)P.nKfBefore : 0);
-    P.bytes = at;
+    static_cast<PoolPlan&>(P) = pool_.plan(replaced, incoming);
+    P.nKfBefore = nKfSynced_; P.hdrCapBefore = hdrCap_; P.hdrCap = grownCap(nKeyframes(), hdrCap_);
+    Layout L;
+    P.oHeader = L.add(sizeof(RowHeaderRec) * (size_t)P.nHeaderRec); P.oEntry = L.add(sizeof(RowEntryRec) * (size_t)P.nEntryRec);
+    P.oPayload = L.add(4 * (size_t)P.nPayload);
+    P.oNewOff = L.add(P.repack ? 4 * (size_t)P.nKfBefore : 0); P.bytes = L.bytes;
     return P;
   }
 
   // Writes the delta of `P` (made by plan() with nothing staged since) into dst [P.bytes] and takes it as applied.
   void pack(const RowPlan& P, uint8_t* dst) {
     memset(dst, 0, P.bytes);
-    if (P.repack) {   // survivors in ascending keyframe slot; a row this delta replaces is skipped (-1): apply gives it its new place
-      int32_t* newOff = reinterpret_cast<int32_t*>(dst + P.oNewOff);
-      int64_t at = 0;
-      for (int32_t k = 0; k < P.nKfBefore; k++) {
-        if (state_[k] == kFull) { newOff[k] = -1; continue; }
-        newOff[k] = (int32_t)at; off_[k] = (int32_t)at;
-        at += len_[k];
-      }
-    }
+    if (P.repack)
+      survivorOffsets(P.nKfBefore, len_.data(), off_.data(), reinterpret_cast<int32_t*>(dst + P.oNewOff), [this](int32_t k) { return state_[k] == kFull; });
     RowHeaderRec* hr = reinterpret_cast<RowHeaderRec*>(dst + P.oHeader);
     int32_t* pay = reinterpret_cast<int32_t*>(dst + P.oPayload);
     int64_t cursor = 0;
@@ -225,9 +185,7 @@ class RowsHost {
     }
     for (const int32_t k : dirtyRows_) state_[k] = kClean;
     dropStaged();
-    poolLive_ = P.survivors + P.nPayload; poolUsed_ = P.tail + P.nPayload; poolCap_ = P.poolCap;
-    if (P.repack == kRowsRepackKept) repacksKept_++;
-    if (P.repack == kRowsRepackGrown) repacksGrown_++;
+    pool_.commit(P);
     if (P.hdrCap != hdrCap_) { hdrCap_ = P.hdrCap; hdrGrowths_++; }
     nKfSynced_ = nKeyframes();
     lastSyncBytes_ = (int64_t)P.bytes; lastSyncRecords_ = (int64_t)P.nHeaderRec + P.nEntryRec;
@@ -248,9 +206,8 @@ class RowsHost {
   std::vector<int32_t> dirtyRows_;
   std::vector<uint64_t> dirtyEntries_;      // (keyframe << 32) | index, in the order first changed
   std::unordered_map<uint64_t, size_t> entryAt_;
-  int32_t hdrCap_, nKfSynced_ = 0;
-  int64_t poolCap_, poolUsed_ = 0, poolLive_ = 0, pendingLive_ = 0;
-  int32_t repacksKept_ = 0, repacksGrown_ = 0, hdrGrowths_ = 0;
+  int32_t hdrCap_, nKfSynced_ = 0, hdrGrowths_ = 0;
+  SpanPool pool_;
   int64_t lastSyncBytes_ = 0, lastSyncRecords_ = 0;
 };
 
