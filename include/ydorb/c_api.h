@@ -1169,6 +1169,68 @@ int ydorb_mapdb_observer_counter(ydorb_mapdb_t* db, int32_t n_lists, const int32
                                  const int32_t* out_start, int32_t* conn_kf, int32_t* conn_weight, int32_t* counts, uint8_t* status,
                                  uint8_t* point_bad);
 
+/* Resident descriptors (DESIGN.md section 2 "Distinctive descriptor on the resident table", section 6p): two more relations of the
+ * resident table and the query that closes the pair computeDistinctiveDescriptors() / updateNormalAndDepth() on it.
+ *   blocks  keyframe slot -> the keyframe's descriptor matrix [n_k][32] in keypoint order (m_cvMat_descriptors).  A keyframe's
+ *           descriptors never change after it is made: a block goes up once.  A block of length 0 erases it: a culled keyframe, the
+ *           reference's pKF->isBad().  The pool is counted in descriptors of 32 bytes.
+ *   views   point slot -> where the point is seen, (keyframe slot, keypoint index) pairs in the order computeDistinctiveDescriptors
+ *           iterates getObservations() in: the order of obs_kf in ydorb_mapdb_set_points.  They are stored apart from the observation
+ *           pool, whose layout, records and YdMapDbStats keep their meaning.
+ * Both lie in pools under the observation pool's policy (append at the tail, a replaced or erased span becomes garbage, repack in
+ * ascending slot order when an append does not fit, same capacity when live + incoming <= capacity / 2, else 2 x (live + incoming), at
+ * most INT32_MAX entries; a view counts as two entries there).  The pools start empty-handed and grow on demand;
+ * ydorb_mapdb_reserve_descriptors sizes them, and is refused unless both are empty (before the first setter, or after clear).
+ * The two setters validate and stage and do no device work; the next query or export applies them after points and rows, so a view may
+ * name a keyframe, and a query a point, staged in the same interval.  A slot named several times between two syncs is applied once,
+ * with its last value.  With nothing staged for the two relations a sync launches nothing for them and moves no byte.  Their traffic
+ * is accounted in YdMapDbDescStats only.  set_keyframe_descriptors grows n_keyframes as set_keyframe_rows does.  ydorb_mapdb_clear
+ * empties both and keeps capacities and counters.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG naming the first offender, before any device work, and stages nothing: null
+ * arrays, a start array that does not begin at 0 or decreases, a negative slot, a view's point slot outside 0..n_points-1 (set the
+ * point before its views), view_kf outside 0..n_keyframes-1 (staged slots count),
+ * a negative view_idx, a view span longer than 65535, a pool past INT32_MAX entries, a query slot outside 0..n_points-1, null outputs
+ * with n > 0.  A view_idx at or past its keyframe's block length cannot be refused when staged (the block may come later, or change):
+ * the query finds it on the device and reports it per point as a status, in no error.
+ * The query restates MapPoint::computeDistinctiveDescriptors of ORB-SLAM2 (the reference source is absent from this repository) on the
+ * rule of ydorb_distinctive_descriptors above: the median is (int)(0.5 m) of the sorted distance row, the first row with the least
+ * median wins.  Assumptions for a maintainer who holds the reference to check: the function returns first for a bad point; it walks
+ * getObservations() in the container's order, skips observations whose keyframe isBad() and collects
+ * pKF->m_cvMat_descriptors.row(idx) of the others; it returns without a change when nothing was collected; m is the number of
+ * collected rows; m_descriptor becomes a copy of the winning row.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdMapDbDescStats {
+  int64_t n_views, n_descriptors;               /* live, staged changes included */
+  int64_t view_pool_used, view_pool_capacity;   /* as of the last sync, in views */
+  int64_t desc_pool_used, desc_pool_capacity;   /* ... in descriptors */
+  int32_t view_repacks_kept, view_repacks_grown, desc_repacks_kept, desc_repacks_grown;
+  int64_t last_desc_sync_bytes, last_desc_sync_records;   /* 0 when nothing of these two relations was staged */
+} YdMapDbDescStats;
+/* status byte of a queried point: the first that matches, in this order */
+#define YDORB_MAPDESC_BAD 1                 /* the resident bad flag is set (a slot never set included): the reference returns first */
+#define YDORB_MAPDESC_NO_DESCRIPTORS 2      /* after skipping views whose keyframe holds no block nothing is left */
+#define YDORB_MAPDESC_VIEW_OUT_OF_RANGE 3   /* a view of a keyframe with a block has idx >= the block's length; no descriptor was read */
+#define YDORB_MAPDESC_UPDATED 0             /* the winner was computed */
+/* Initial capacities of the view pool (in views) and of the descriptor pool (in descriptors); both pools must be empty. */
+int ydorb_mapdb_reserve_descriptors(ydorb_mapdb_t* db, int64_t view_capacity, int64_t descriptor_capacity);
+/* Replaces the whole block of each named keyframe: desc_start [n+1] / desc [desc_start[n]][32].  A block of length 0 erases it. */
+int ydorb_mapdb_set_keyframe_descriptors(ydorb_mapdb_t* db, const int32_t* kf_slots, int32_t n, const int32_t* desc_start,
+                                         const uint8_t* desc);
+/* Replaces the views of each named point: view_start [n+1] / view_kf / view_idx [view_start[n]].  An empty span erases them. */
+int ydorb_mapdb_set_point_views(ydorb_mapdb_t* db, const int32_t* slots, int32_t n, const int32_t* view_start, const int32_t* view_kf,
+                                const int32_t* view_idx);
+/* computeDistinctiveDescriptors() of the n named points with no descriptor upload; a slot may repeat, results in the order given.
+ * status [n] = YDORB_MAPDESC_*.  For an UPDATED point best = the position of the winning view within the point's view span (skipped
+ * views counted, so the caller can index its own list with it), best_view [n][2] = that view's (keyframe slot, keypoint index),
+ * desc_out [n][32] = the winning row.  Every other status: best = -1 and zero rows; the call still returns YDORB_OK. */
+int ydorb_mapdb_distinctive_descriptors(ydorb_mapdb_t* db, const int32_t* slots, int32_t n, int32_t* best, int32_t* best_view,
+                                        uint8_t* desc_out, uint8_t* status);
+/* Reads the device's views back (after applying what is staged): view_start [n_points+1], view_kf / view_idx [n_views]. */
+int ydorb_mapdb_export_views(ydorb_mapdb_t* db, int32_t* view_start, int32_t* view_kf, int32_t* view_idx);
+/* ... and its blocks: desc_start [n_keyframes+1], desc [n_descriptors][32]. */
+int ydorb_mapdb_export_descriptors(ydorb_mapdb_t* db, int32_t* desc_start, uint8_t* desc);
+int ydorb_mapdb_desc_stats(ydorb_mapdb_t* db, YdMapDbDescStats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,11 @@
 // (DESIGN.md section 6n); their comments below state what each takes from the caller.
 // keyFrameCounter and localPoints are the two set queries of Tracking::updateLocalMap over the keyframe rows (tracking.hpp's
 // updateLocalKeyFramesImpl / updateLocalPointsImpl); verifyRows() is verify() for the rows.
-// Assumed spellings: those of mapPoint.hpp, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
+// enableDescriptors() adds the keyframes' descriptor blocks and the points' views: touchDescriptors(kf) once
+// per keyframe, touch(mp) then also re-reads where the point is seen, forget() erases block and views, computeDistinctiveDescriptors
+// is MapPoint::computeDistinctiveDescriptors for a list of points with no descriptor upload, verifyDescriptors() is verify() for the two.
+// Off by default: without it no call of the descriptor entries is made.  Enable it before the first touch.
+// Assumed spellings: those of mapPoint.hpp; m_cvMat_descriptors (one CV_8U row of 32 bytes per keypoint) for the blocks, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
 // MapPoint::setPosInWorld(cv::Mat), m_int_correctedByKeyFrameID, m_int_correctedReference and the Sim3 members rotation().x() .. w(),
 // translation()[k], scale().  The camera centre after a corrected pose is not read from a member: correctLoopPoints computes it from
 // the corrected Sim3 as setPose would (see there), correctAfterEssentialGraph reads getCameraOriginInWorld() after the caller's setPose.
@@ -65,6 +69,15 @@ class MapMirror {
     freePoints_.push_back(s);
     mark(pointDirty_, dirtyPoints_, s, kFull);   // the next flush erases it, or writes the point that took the slot since
   }
+  // Resident descriptors.  The capacities (views, descriptors) size the two pools when given; both pools grow on demand anyway.
+  void enableDescriptors(int64_t viewCapacity = 0, int64_t descriptorCapacity = 0) {
+    descriptors_ = true;
+    if (viewCapacity > 0 || descriptorCapacity > 0) mapCheck(ydorb_mapdb_reserve_descriptors(db_, viewCapacity, descriptorCapacity));
+  }
+  bool descriptorsEnabled() const { return descriptors_; }
+  // re-reads m_cvMat_descriptors at the next flush: once per keyframe, its descriptors never change; again after setBadFlag(), whose
+  // isBad() empties the block (or forget(kf))
+  void touchDescriptors(const KeyFramePtr& kf) { mark(descDirty_, dirtyDescs_, kfSlotFor(kf), kFull); }
   void touchRow(const KeyFramePtr& kf) { markRow(kfSlotFor(kf)); }
   void touchEntry(const KeyFramePtr& kf, size_t idx) {
     const int32_t s = kfSlotFor(kf);
@@ -76,6 +89,7 @@ class MapMirror {
     if (it == kfSlot_.end()) return;
     kfOf_[it->second] = KeyFramePtr();
     if (rowSent_[it->second]) markRow(it->second);   // the next flush empties the row, or writes the row of the keyframe that took the slot since
+    if (descSent_[it->second]) mark(descDirty_, dirtyDescs_, it->second, kFull);   // ... and the block
     freeKfs_.push_back(it->second);
     kfSlot_.erase(it);
   }
@@ -84,6 +98,7 @@ class MapMirror {
     pointSlot_.clear(); pointOf_.clear(); freePoints_.clear(); pointDirty_.clear(); dirtyPoints_.clear(); span_.clear();
     kfSlot_.clear(); kfOf_.clear(); freeKfs_.clear(); kfDirty_.clear(); dirtyKfs_.clear();
     rowDirty_.clear(); rowSent_.clear(); dirtyRows_.clear(); dirtyEntries_.clear();
+    descDirty_.clear(); descSent_.clear(); dirtyDescs_.clear();
   }
 
   // At most one call of each set_* entry: the centres first (a point may name a keyframe that got its slot while the point was read).
@@ -111,6 +126,7 @@ class MapMirror {
     std::vector<int32_t> slots, start{0}, obsKf, refKf, posSlots;
     std::vector<uint8_t> obsLevel, bad, refLevel;
     std::vector<float> pos, posOnly;
+    std::vector<int32_t> viewStart{0}, viewKf, viewIdx;   // with descriptors enabled: the views of the points in `slots`
     for (const int32_t s : dirtyPoints_) {
       const uint8_t how = pointDirty_[s];
       pointDirty_[s] = kClean;
@@ -129,6 +145,12 @@ class MapMirror {
       bad.push_back(rec.bad); refKf.push_back(rec.refKf); refLevel.push_back(rec.refLevel);
       pos.insert(pos.end(), rec.pos, rec.pos + 3);
       span_[s] = (int32_t)rec.kf.size();
+      if (descriptors_) {
+        viewKf.insert(viewKf.end(), rec.kf.begin(), rec.kf.end()); viewIdx.insert(viewIdx.end(), rec.idx.begin(), rec.idx.end());
+        viewStart.push_back((int32_t)viewKf.size());
+        for (const int32_t k : rec.kf)   // a keyframe met here for the first time: its block is read now
+          if (!descSent_[k]) mark(descDirty_, dirtyDescs_, k, kFull);
+      }
     }
     dirtyPoints_.clear();
     if (!dirtyKfs_.empty()) {
@@ -150,6 +172,98 @@ class MapMirror {
     if (!posSlots.empty()) mapCheck(ydorb_mapdb_set_positions(db_, posSlots.data(), (int32_t)posSlots.size(), posOnly.data()));
     if (!rowKf.empty()) mapCheck(ydorb_mapdb_set_keyframe_rows(db_, rowKf.data(), (int32_t)rowKf.size(), rowStart.data(), rowSlots.data()));
     if (!entKf.empty()) mapCheck(ydorb_mapdb_set_row_entries(db_, entKf.data(), entIdx.data(), entSlot.data(), (int32_t)entKf.size()));
+    if (!dirtyDescs_.empty()) {   // the blocks before the views, both after the points: a view names a point slot the table holds
+      std::vector<int32_t> ks, descStart{0};
+      std::vector<uint8_t> desc;
+      for (const int32_t k : dirtyDescs_) {
+        descDirty_[k] = kClean;
+        const bool live = kfOf_[k] && !kfOf_[k]->isBad();   // a bad keyframe's observations are skipped: it holds no block
+        if (!live && !descSent_[k]) continue;
+        ks.push_back(k);
+        if (live) appendDescriptors(kfOf_[k], desc);
+        if (desc.size() / 32 > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX descriptors in one flush");
+        descStart.push_back((int32_t)(desc.size() / 32));
+        descSent_[k] = live ? 1 : 0;
+      }
+      dirtyDescs_.clear();
+      desc.resize(desc.size() + 32);   // never a null pointer
+      if (!ks.empty()) mapCheck(ydorb_mapdb_set_keyframe_descriptors(db_, ks.data(), (int32_t)ks.size(), descStart.data(), desc.data()));
+    }
+    if (descriptors_ && !slots.empty()) {
+      viewKf.push_back(0); viewIdx.push_back(0);
+      mapCheck(ydorb_mapdb_set_point_views(db_, slots.data(), (int32_t)slots.size(), viewStart.data(), viewKf.data(), viewIdx.data()));
+    }
+  }
+
+  // MapPoint::computeDistinctiveDescriptors for every point of `points` over the resident table (ydorb_mapdb_distinctive_descriptors):
+  // apply(mp, kf, idx, row) for every point the reference would have given a new m_descriptor, each distinct point once, in the order of
+  // `points`; row (1x32 CV_8U) = kf->m_cvMat_descriptors.row(idx), the winning descriptor, which the caller stores as m_descriptor.
+  // A bad point and a point none of whose observing keyframes is alive are left alone, as in the reference.  Returns their number.
+  template <class Points, class Apply>
+  int computeDistinctiveDescriptors(const Points& points, Apply apply) {
+    if (!descriptors_) throw std::runtime_error("ydorb: computeDistinctiveDescriptors without enableDescriptors()");
+    std::vector<int32_t> slots;
+    std::vector<MapPointPtr> asked;
+    std::vector<uint8_t> seen(pointOf_.size(), 0);
+    for (const MapPointPtr& mp : points) {
+      if (!mp) continue;
+      const int32_t s = known(mp);
+      if ((size_t)s >= seen.size()) seen.resize((size_t)s + 1, 0);
+      if (seen[s]) continue;
+      seen[s] = 1;
+      slots.push_back(s);
+      asked.push_back(mp);
+    }
+    flush();
+    const size_t n = slots.size();
+    if (n == 0) return 0;
+    std::vector<int32_t> best(n), view(2 * n);
+    std::vector<uint8_t> desc(32 * n), status(n);
+    mapCheck(ydorb_mapdb_distinctive_descriptors(db_, slots.data(), (int32_t)n, best.data(), view.data(), desc.data(), status.data()));
+    int updated = 0;
+    for (size_t p = 0; p < n; p++) {
+      if (status[p] == YDORB_MAPDESC_VIEW_OUT_OF_RANGE) throw std::runtime_error("ydorb: a view names a keypoint past its keyframe's descriptors");
+      if (status[p] != YDORB_MAPDESC_UPDATED) continue;
+      cv::Mat row(1, 32, CV_8U);
+      std::memcpy(row.template ptr<unsigned char>(), &desc[32 * p], 32);
+      apply(asked[p], kfOf_[view[2 * p]], (size_t)view[2 * p + 1], row);
+      updated++;
+    }
+    return updated;
+  }
+
+  struct Difference {   // of verify() and of verifyDescriptors()
+    std::vector<int32_t> pointSlots, keyFrameSlots;
+    bool empty() const { return pointSlots.empty() && keyFrameSlots.empty(); }
+  };
+  // Flushes, re-reads every known point's observations and every known keyframe's descriptors and compares them with the device's views
+  // and blocks (ydorb_mapdb_export_views / _descriptors): the point slots whose views differ and the keyframe slots whose block differs.
+  Difference verifyDescriptors() {
+    flush();
+    YdMapDbStats st;
+    YdMapDbDescStats ds;
+    mapCheck(ydorb_mapdb_stats(db_, &st));
+    mapCheck(ydorb_mapdb_desc_stats(db_, &ds));
+    const size_t np = (size_t)st.n_points, nk = (size_t)st.n_keyframes;
+    std::vector<int32_t> vStart(np + 1), vKf((size_t)ds.n_views + 1), vIdx((size_t)ds.n_views + 1), dStart(nk + 1);
+    std::vector<uint8_t> desc(32 * ((size_t)ds.n_descriptors + 1));
+    mapCheck(ydorb_mapdb_export_views(db_, vStart.data(), vKf.data(), vIdx.data()));
+    mapCheck(ydorb_mapdb_export_descriptors(db_, dStart.data(), desc.data()));
+    Difference d;
+    for (size_t s = 0; s < pointOf_.size(); s++) {
+      const Record want = pointOf_[s] ? read(pointOf_[s], false) : Record();
+      const size_t len = s < np ? (size_t)(vStart[s + 1] - vStart[s]) : 0;
+      const bool same = len == want.kf.size() && (len == 0 || (std::memcmp(&vKf[vStart[s]], want.kf.data(), 4 * len) == 0 &&
+                                                               std::memcmp(&vIdx[vStart[s]], want.idx.data(), 4 * len) == 0));
+      if (!same) d.pointSlots.push_back((int32_t)s);
+    }
+    for (size_t k = 0; k < kfOf_.size(); k++) {
+      std::vector<uint8_t> want;
+      if (kfOf_[k] && descSent_[k] && !kfOf_[k]->isBad()) appendDescriptors(kfOf_[k], want);
+      const size_t len = k < nk ? (size_t)(dStart[k + 1] - dStart[k]) : 0;
+      if (32 * len != want.size() || (len > 0 && std::memcmp(&desc[32 * (size_t)dStart[k]], want.data(), 32 * len) != 0)) d.keyFrameSlots.push_back((int32_t)k);
+    }
+    return d;
   }
 
   // The counting loop of Tracking::updateLocalKeyFrames over the resident table (ydorb_mapdb_observer_counter): per keyframe how many
@@ -436,10 +550,6 @@ class MapMirror {
     return run(c, YDORB_MAPCORR_RESIDENT, false, [](const MapPointPtr&, int32_t) {}, apply);
   }
 
-  struct Difference {
-    std::vector<int32_t> pointSlots, keyFrameSlots;
-    bool empty() const { return pointSlots.empty() && keyFrameSlots.empty(); }
-  };
   // Flushes, re-reads everything the mirror knows and compares it with the device's table (ydorb_mapdb_export): the point slots whose
   // record differs and the keyframe slots whose centre differs.  Empty when every change was touched.
   Difference verify() {
@@ -476,7 +586,7 @@ class MapMirror {
  private:
   enum : uint8_t { kClean = 0, kPos = 1, kFull = 2 };
   struct Record {   // what set_points takes for one point; the default is an erased point
-    std::vector<int32_t> kf;
+    std::vector<int32_t> kf, idx;   // idx: the keypoint index of each observation (the views)
     std::vector<uint8_t> level;
     uint8_t bad = 1, refLevel = 0;
     int32_t refKf = 0;
@@ -573,7 +683,11 @@ class MapMirror {
     if (it != kfSlot_.end()) return it->second;
     int32_t s;
     if (!freeKfs_.empty()) { s = freeKfs_.back(); freeKfs_.pop_back(); }
-    else { s = (int32_t)kfOf_.size(); kfOf_.push_back(KeyFramePtr()); kfDirty_.push_back(kClean); rowDirty_.push_back(kClean); rowSent_.push_back(0); }
+    else {
+      s = (int32_t)kfOf_.size();
+      kfOf_.push_back(KeyFramePtr()); kfDirty_.push_back(kClean); rowDirty_.push_back(kClean); rowSent_.push_back(0);
+      descDirty_.push_back(kClean); descSent_.push_back(0);
+    }
     kfOf_[s] = kf;
     kfSlot_[kf] = s;
     mark(kfDirty_, dirtyKfs_, s, kFull);
@@ -594,6 +708,7 @@ class MapMirror {
     const auto observations = mp->getObservations();
     for (const auto& ob : observations) {   // the container's own order
       r.kf.push_back(assign ? kfSlotFor(ob.first) : slotOf(ob.first));
+      r.idx.push_back((int32_t)ob.second);
       const int octave = ob.first->m_v_keyPoints[ob.second].octave;
       r.level.push_back((uint8_t)((octave & 0x7f) | (ob.first->m_v_rightXcords[ob.second] >= 0 ? 0x80 : 0)));
     }
@@ -611,6 +726,19 @@ class MapMirror {
     for (int i = 0; i < 3; i++) r.pos[i] = P.template at<float>(i);
     return r;
   }
+  // m_cvMat_descriptors, one 32-byte row per keypoint.  Chosen by overload so that a keyframe type without the member still builds the
+  // mirror (it cannot enable descriptors).
+  template <class K>
+  static auto appendDescriptorsOf(const K& kf, std::vector<uint8_t>& to, int) -> decltype((void)kf->m_cvMat_descriptors) {
+    const cv::Mat& D = kf->m_cvMat_descriptors;
+    for (int i = 0; i < D.rows; i++) {
+      const unsigned char* r = D.row(i).template ptr<unsigned char>();
+      to.insert(to.end(), r, r + 32);
+    }
+  }
+  template <class K>
+  static void appendDescriptorsOf(const K&, std::vector<uint8_t>&, long) { throw std::runtime_error("ydorb: the keyframe type has no m_cvMat_descriptors"); }
+  static void appendDescriptors(const KeyFramePtr& kf, std::vector<uint8_t>& to) { appendDescriptorsOf(kf, to, 0); }
   std::vector<float> scaleFactors() const {   // one pyramid for all keyframes
     for (const KeyFramePtr& kf : kfOf_) if (kf) return kf->m_v_scaleFactors;
     return std::vector<float>(1, 1.0f);
@@ -628,6 +756,9 @@ class MapMirror {
   std::vector<uint8_t> rowDirty_, rowSent_;   // per keyframe slot: the row is re-read at the next flush / the table holds a row of it
   std::vector<int32_t> dirtyRows_;
   std::vector<std::pair<int32_t, int32_t> > dirtyEntries_;   // (keyframe slot, index)
+  bool descriptors_ = false;
+  std::vector<uint8_t> descDirty_, descSent_;   // per keyframe slot: the block is re-read at the next flush / the table holds a block of it
+  std::vector<int32_t> dirtyDescs_;
 };
 
 }  // namespace adapter

@@ -21,6 +21,9 @@ the three loops of loop closing; see bench_correct.  Its kernels k_mapdb_correct
 with --correct.
 --local-map times the two set queries of Tracking::updateLocalMap on the resident table's keyframe rows (DESIGN.md section 6o); see
 bench_local_map.  Its kernels k_rowset_mark / _count / _emit and k_mapdb_rows_apply / _repack: the same rocprofv3 line with --local-map.
+--descriptors times MapPoint::computeDistinctiveDescriptors on the resident table's descriptor blocks and point views (DESIGN.md section
+6p) beside the flat path as a caller must run it and the CPU oracle; see bench_descriptors.  Its kernels k_mapdb_distinctive and
+k_mapdb_desc_apply / _repack: the same rocprofv3 line with --descriptors.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -552,6 +555,116 @@ def bench_local_map(reps):
     return out
 
 
+def bench_descriptors(reps):
+    """The map-size table of --resident with a descriptor block per keyframe (one row per entry of its map-point vector) and the views of
+    every point loaded once.  Then, for two point lists - the 300 points a LocalMapping pass touches and the local window's 7 750 - and
+    alternating in every repetition on the same lists:
+      resident   ydorb_mapdb_distinctive_descriptors with nothing staged, and with the lists' views re-staged first (staging timed apart);
+      flat       the path a caller of ydorb_distinctive_descriptors must run: the host gather of every observer's row and the call.  The
+                 gather here is one numpy fancy index over a flat descriptor matrix, which flatters it against the reference's walk
+                 through getObservations() and each keyframe's cv::Mat;
+      oracle     oracle.orb_oracle.distinctive_descriptor per point on the gathered rows, one thread (fewer repetitions).
+    Results are compared exactly before timing.  Bytes uploaded per pass: the resident query sends the slots (plus the delta when views
+    were staged, from ydorb_mapdb_desc_stats); the flat path sends every gathered row and the offsets."""
+    from oracle import orb_oracle
+    from ydorbslam_amd._lib import YdMapDbDescStats
+    orb_oracle.build()
+    n_kf, n_points, window = SIZES["map"]
+    L = y.lib()
+    d = make_map(n_kf, n_points, window)
+    T = d["T"]
+    rng = np.random.default_rng(7)
+    n_desc = int(d["kf_start"][-1])
+    base = rng.integers(0, 256, (64, 32)).astype(np.uint8)                        # near-duplicate rows, as matched descriptors are
+    desc = base[rng.integers(0, 64, n_desc)]
+    flips = rng.integers(0, 256, (n_desc, 3))
+    for j in range(3):
+        desc[np.arange(n_desc), flips[:, j] >> 3] ^= (1 << (flips[:, j] & 7)).astype(np.uint8)
+    desc = np.ascontiguousarray(desc)
+    # where each observation lies in its keyframe's block: kf_points is sorted by keyframe, stably, so the rank within the keyframe
+    by_kf = np.argsort(T.obs_kf, kind="stable")
+    view_idx = np.zeros(d["n_obs"], np.int32)
+    view_idx[by_kf] = (np.arange(d["n_obs"]) - d["kf_start"][T.obs_kf[by_kf]]).astype(np.int32)
+    row_of_obs = (d["kf_start"][T.obs_kf] + view_idx).astype(np.int64)             # the flat path's gather index
+    out = dict(keyframes=n_kf, points=n_points, observations=d["n_obs"], descriptors=n_desc)
+    h = C.c_void_p()
+    y._lib.check(L.ydorb_mapdb_create(0, n_points, n_kf, 2 * d["n_obs"], C.byref(h)))
+    y._lib.check(L.ydorb_mapdb_reserve_descriptors(h, 2 * d["n_obs"], 2 * n_desc))
+    all_slots, kf_slots = np.arange(n_points, dtype=np.int32), np.arange(n_kf, dtype=np.int32)
+
+    def dstats():
+        st = YdMapDbDescStats()
+        L.ydorb_mapdb_desc_stats(h, C.byref(st))
+        return {k: int(getattr(st, k)) for k, _ in YdMapDbDescStats._fields_}
+
+    t0 = time.perf_counter()
+    assert L.ydorb_mapdb_set_centres(h, p(kf_slots), n_kf, p(d["centre"])) == 0
+    assert L.ydorb_mapdb_set_points(h, p(all_slots), n_points, p(T.obs_start), p(T.obs_kf), p(T.obs_level), p(T.bad), p(d["ref_kf"]), p(d["ref_level"]), p(d["pos"])) == 0, L.ydorb_last_error()
+    assert L.ydorb_mapdb_set_keyframe_descriptors(h, p(kf_slots), n_kf, p(d["kf_start"]), p(desc)) == 0, L.ydorb_last_error()
+    assert L.ydorb_mapdb_set_point_views(h, p(all_slots), n_points, p(T.obs_start), p(T.obs_kf), p(view_idx)) == 0, L.ydorb_last_error()
+    one = np.zeros(1, np.int32)
+    o1 = [np.zeros(1, np.int32), np.zeros(2, np.int32), np.zeros(32, np.uint8), np.zeros(1, np.uint8)]
+    assert L.ydorb_mapdb_distinctive_descriptors(h, p(one), 1, *[p(a) for a in o1]) == 0, L.ydorb_last_error()
+    out["load_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
+    out["load_desc_sync_bytes"] = dstats()["last_desc_sync_bytes"]
+    matcher = y.OrbMatcher()
+    k0 = n_kf // 2
+    wide = np.arange(k0, min(k0 + 4 * window, n_kf))
+    local = np.unique(np.concatenate([d["kf_points"][d["kf_start"][k]:d["kf_start"][k + 1]] for k in wide]))[:SIZES["local"][1]].astype(np.int32)
+    for label, slots in (("pass_300_points", np.ascontiguousarray(local[:300])), ("local_window_points", local)):
+        n = len(slots)
+        res = [np.zeros(n, np.int32), np.zeros((n, 2), np.int32), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)]
+        resident = lambda: L.ydorb_mapdb_distinctive_descriptors(h, p(slots), n, *[p(a) for a in res])
+        m = np.diff(T.obs_start.astype(np.int64))[slots]
+        offsets = np.concatenate([[0], np.cumsum(m)]).astype(np.int32)
+        take = np.concatenate([np.arange(T.obs_start[q], T.obs_start[q + 1]) for q in slots])
+        sv = [np.ascontiguousarray(a) for a in (offsets, T.obs_kf[take], view_idx[take])]
+        stage = lambda: L.ydorb_mapdb_set_point_views(h, p(slots), n, *[p(a) for a in sv])
+        best = np.zeros(n, np.int32)
+        box = {}
+
+        def flat():
+            t = time.perf_counter()
+            box["rows"] = desc[row_of_obs[take]]                                   # the host gather, 32 bytes per observation
+            box["gather"] = time.perf_counter() - t
+            return matcher._L.ydorb_distinctive_descriptors(matcher._h, p(box["rows"]), p(offsets), n, p(best))
+
+        assert resident() == 0, L.ydorb_last_error()
+        assert flat() == 0, L.ydorb_last_error()
+        live = res[3] == 0
+        assert np.array_equal(res[0][live], best[live]) and np.array_equal(res[2][live], box["rows"][offsets[:-1][live] + best[live]])
+        assert (res[3][~live] == 1).all() and int((~live).sum()) == int(T.bad[slots].sum())      # the flat entry has no bad flag: a caller skips those
+        want = np.array([orb_oracle.distinctive_descriptor(box["rows"][offsets[i]:offsets[i + 1]]) for i in range(n)], np.int32)
+        assert np.array_equal(want, best)
+        ts = dict(resident=[], stage=[], resident_after_stage=[], flat=[], gather=[], oracle=[])
+        staged_bytes = 0
+        for r in range(reps + 1):
+            t = [time.perf_counter()]
+            assert resident() == 0
+            t.append(time.perf_counter())
+            assert flat() == 0
+            t.append(time.perf_counter())
+            assert stage() == 0
+            t.append(time.perf_counter())
+            assert resident() == 0
+            t.append(time.perf_counter())
+            staged_bytes = dstats()["last_desc_sync_bytes"]
+            if r:
+                ts["resident"].append(t[1] - t[0]); ts["flat"].append(t[2] - t[1]); ts["gather"].append(box["gather"])
+                ts["stage"].append(t[3] - t[2]); ts["resident_after_stage"].append(t[4] - t[3])
+            if r and r <= max(3, reps // 5):
+                u = time.perf_counter()
+                for i in range(n):
+                    orb_oracle.distinctive_descriptor(box["rows"][offsets[i]:offsets[i + 1]])
+                ts["oracle"].append(time.perf_counter() - u)
+        out[label] = dict(points=n, observations=int(offsets[-1]), resident_query_ms=stat(ts["resident"]), flat_gather_and_call_ms=stat(ts["flat"]),
+                          flat_gather_alone_ms=stat(ts["gather"]), stage_views_ms=stat(ts["stage"]), resident_query_after_staging_ms=stat(ts["resident_after_stage"]),
+                          cpu_oracle_ms=stat(ts["oracle"]), resident_upload_bytes=4 * n, resident_upload_bytes_after_staging=4 * n + staged_bytes,
+                          flat_upload_bytes=32 * int(offsets[-1]) + 4 * (n + 1))
+    L.ydorb_mapdb_destroy(h)
+    return out
+
+
 def flatten_times():
     """Host time of the adapters' three flattenings on stand-ins at the local size (31 keyframes, 7 750 points)."""
     m = S.random_map(5, 31, 7750, 4, 8, level_spread=1)
@@ -571,7 +684,13 @@ def main():
     ap.add_argument("--kernel-ms", action="append", default=[], help="SIZE=MS: k_normal_depth's time from a kernel trace, for the bytes-per-second figure")
     ap.add_argument("--correct", action="store_true", help="time ydorb_mapdb_correct beside the route it replaces instead")
     ap.add_argument("--local-map", action="store_true", help="time the keyframe-row queries of updateLocalMap (DESIGN.md section 6o) beside the host restatement instead")
+    ap.add_argument("--descriptors", action="store_true", help="time computeDistinctiveDescriptors on the resident descriptors (DESIGN.md section 6p) beside the flat path and the CPU oracle instead")
     a = ap.parse_args()
+    if a.descriptors:
+        res = bench_descriptors(a.reps)
+        M.release()
+        print(json.dumps(res))
+        return
     if a.local_map:
         res = bench_local_map(a.reps)
         M.release()

@@ -141,6 +141,13 @@ SYMBOLS = {
     "ydorb_mapdb_row_stats": (C.c_int, [_VP, _VP]),
     "ydorb_mapdb_points_of_keyframes": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP]),
     "ydorb_mapdb_observer_counter": (C.c_int, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_reserve_descriptors": (C.c_int, [_VP, C.c_int64, C.c_int64]),
+    "ydorb_mapdb_set_keyframe_descriptors": (C.c_int, [_VP, _VP, _I, _VP, _VP]),
+    "ydorb_mapdb_set_point_views": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP]),
+    "ydorb_mapdb_distinctive_descriptors": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_export_views": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_export_descriptors": (C.c_int, [_VP, _VP, _VP]),
+    "ydorb_mapdb_desc_stats": (C.c_int, [_VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -234,6 +241,12 @@ class YdMapDbStats(C.Structure):
 class YdMapDbRowStats(C.Structure):
     _fields_ = [("n_entries", C.c_int64), ("pool_used", C.c_int64), ("pool_capacity", C.c_int64), ("repacks_kept", _I), ("repacks_grown", _I),
                 ("header_growths", _I), ("header_capacity", _I), ("last_row_sync_bytes", C.c_int64), ("last_row_sync_records", C.c_int64)]
+
+
+class YdMapDbDescStats(C.Structure):
+    _fields_ = [("n_views", C.c_int64), ("n_descriptors", C.c_int64), ("view_pool_used", C.c_int64), ("view_pool_capacity", C.c_int64),
+                ("desc_pool_used", C.c_int64), ("desc_pool_capacity", C.c_int64), ("view_repacks_kept", _I), ("view_repacks_grown", _I),
+                ("desc_repacks_kept", _I), ("desc_repacks_grown", _I), ("last_desc_sync_bytes", C.c_int64), ("last_desc_sync_records", C.c_int64)]
 
 
 class YdMapCorrection(C.Structure):

@@ -6,7 +6,9 @@
 // With nothing staged no table byte moves.
 // ydorb_mapdb_correct (mapcorrect_kernels.hip.h) is the one query that writes the table: positions in place, then centres.
 // The keyframe rows (mapdb_rows_host.h, mapdb_rows_kernels.hip.h) are a second state machine in the same handle,
-// synced after the points under the same mutex: ydorb_mapdb_points_of_keyframes and ydorb_mapdb_observer_counter at the end of this file.
+// synced after the points under the same mutex: ydorb_mapdb_points_of_keyframes and ydorb_mapdb_observer_counter below.
+// The point views and the keyframe descriptor blocks (mapdb_desc_host.h, mapdb_desc_kernels.hip.h) are two more,
+// synced after the rows through the same syncSpans: ydorb_mapdb_distinctive_descriptors at the end of this file.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -19,6 +21,8 @@
 #include "map_queries.h"
 #include "map_table.h"
 #include "mapcorrect_kernels.hip.h"
+#include "mapdb_desc_host.h"
+#include "mapdb_desc_kernels.hip.h"
 #include "mapdb_host.h"
 #include "mapdb_kernels.hip.h"
 #include "mapdb_rows_host.h"
@@ -50,7 +54,13 @@ struct ydorb_mapdb {
   int *rowStart = nullptr, *rowLen = nullptr, *rowPool = nullptr, *first = nullptr, *seenStamp = nullptr;
   size_t rowsetCap = 0;
   int stamp = 0;
-  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc) {}
+  // point views and keyframe descriptor blocks: as the rows, twice
+  mapdb::DescHost desc;
+  Mem viewHdr, viewPoolMem, blockHdr, blockPoolMem;
+  DeltaPair viewDelta, blockDelta;
+  int *viewStart = nullptr, *viewLen = nullptr, *viewPool = nullptr, *blockStart = nullptr, *blockLen = nullptr;
+  mapdb::DescRow* blockPool = nullptr;
+  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc) {}
 };
 
 namespace {
@@ -168,45 +178,87 @@ int syncPoints(ydorb_mapdb* h) {
   return YDORB_OK;
 }
 
-// The staged rows, after the points: a row may name a point that got its slot in the same interval.
-int syncRows(ydorb_mapdb* h) {
-  if (!h->rows.dirty()) { h->rows.nothingToSync(); return YDORB_OK; }
+// One span relation (mapdb_rows_host.h's SpanHost: the keyframe rows, the point views, the descriptor blocks) brought up to date: one
+// upload of its packed delta, the header growth, the repack if the pool needs it, the apply.  repack(P, start, len, oldPool, newPool)
+// and apply(P, start, len, pool) launch the relation's two kernels on the handle's stream.
+template <class T, class Repack, class Apply>
+int syncSpans(ydorb_mapdb* h, mapdb::SpanHost<T>& host, DeltaPair& delta, Mem& hdrMem, Mem& poolMem, int*& start, int*& len, T*& pool, Repack repack,
+              Apply apply) {
+  if (!host.dirty()) { host.nothingToSync(); return YDORB_OK; }
   hipStream_t s = h->c.stream;
-  const mapdb::RowPlan P = h->rows.plan();
+  const mapdb::RowPlan P = host.plan();
   int rc;
-  if ((rc = h->rowDelta.ensure(P.bytes))) return rc;
+  if ((rc = delta.ensure(P.bytes))) return rc;
   ScopedMem newHdr, newPool;
-  int *rowStart = h->rowStart, *rowLen = h->rowLen, *pool = h->rowPool;
-  if (P.hdrCap != P.hdrCapBefore && (rc = allocRowHeaders(s, newHdr, rowStart, rowLen, (size_t)P.hdrCap))) return rc;
-  if (P.repack && (rc = newPool.alloc(4 * (size_t)P.poolCap))) return rc;
-  if (newPool.p) pool = newPool.as<int>();
-  h->rows.pack(P, h->rowDelta.host.as<uint8_t>());
-  if (P.bytes) HIPCHK(hipMemcpyAsync(h->rowDelta.dev.p, h->rowDelta.host.p, P.bytes, hipMemcpyHostToDevice, s));
-  if (newHdr.p) { D2D(rowStart, h->rowStart, 4 * (size_t)P.nKfBefore); D2D(rowLen, h->rowLen, 4 * (size_t)P.nKfBefore); }
+  int *st = start, *ln = len;
+  T* pl = pool;
+  if (P.hdrCap != P.hdrCapBefore && (rc = allocRowHeaders(s, newHdr, st, ln, (size_t)P.hdrCap))) return rc;
+  if (P.repack && (rc = newPool.alloc(sizeof(T) * (size_t)P.poolCap))) return rc;
+  if (newPool.p) pl = newPool.as<T>();
+  host.pack(P, delta.host.as<uint8_t>());
+  if (P.bytes) HIPCHK(hipMemcpyAsync(delta.dev.p, delta.host.p, P.bytes, hipMemcpyHostToDevice, s));
+  if (newHdr.p) { D2D(st, start, 4 * (size_t)P.nKfBefore); D2D(ln, len, 4 * (size_t)P.nKfBefore); }
   if (P.repack && P.nKfBefore > 0) {
-    mapdb::RowsRepackArgs a;
-    a.nKf = P.nKfBefore; a.rowStart = rowStart; a.rowLen = rowLen; a.newOff = at<int>(h->rowDelta.dev, P.oNewOff); a.oldPool = h->rowPool; a.newPool = pool;
-    hipLaunchKernelGGL(mapdb::k_mapdb_rows_repack, dim3((unsigned)((P.nKfBefore + mapdb::kRowWaves - 1) / mapdb::kRowWaves)), dim3(mapdb::kRowThreads), 0, s, a);
+    repack(P, st, ln, pool, pl);
     HIPCHK(hipGetLastError());
   }
-  {
-    mapdb::RowsApplyArgs a;
-    a.nHeaderRec = P.nHeaderRec; a.nEntryRec = P.nEntryRec; a.nPayload = (int)P.nPayload; a.tail = (int)P.tail;
-    a.header = at<mapdb::RowHeaderRec>(h->rowDelta.dev, P.oHeader); a.entry = at<mapdb::RowEntryRec>(h->rowDelta.dev, P.oEntry);
-    a.payload = at<int>(h->rowDelta.dev, P.oPayload);
-    a.rowStart = rowStart; a.rowLen = rowLen; a.pool = pool;
-    const unsigned blocks = applyBlocks((size_t)P.nHeaderRec + P.nEntryRec, P.nPayload, mapdb::kRowThreads);
-    hipLaunchKernelGGL(mapdb::k_mapdb_rows_apply, dim3(blocks), dim3(mapdb::kRowThreads), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  if ((rc = handOver(s, {{&h->rowHdr, &newHdr}, {&h->rowPoolMem, &newPool}}))) return rc;
-  h->rowStart = rowStart; h->rowLen = rowLen; h->rowPool = pool;
+  apply(P, st, ln, pl);
+  HIPCHK(hipGetLastError());
+  if ((rc = handOver(s, {{&hdrMem, &newHdr}, {&poolMem, &newPool}}))) return rc;
+  start = st; len = ln; pool = pl;
   return YDORB_OK;
 }
 
+// int32 spans: the keyframe rows and the point views share the two kernels of mapdb_rows_kernels.hip.h
+int syncIntSpans(ydorb_mapdb* h, mapdb::SpanHost<int32_t>& host, DeltaPair& delta, Mem& hdrMem, Mem& poolMem, int*& start, int*& len, int*& pool) {
+  hipStream_t s = h->c.stream;
+  return syncSpans(h, host, delta, hdrMem, poolMem, start, len, pool,
+    [&](const mapdb::RowPlan& P, int* st, int* ln, int* oldPool, int* newPool) {
+      mapdb::RowsRepackArgs a;
+      a.nKf = P.nKfBefore; a.rowStart = st; a.rowLen = ln; a.newOff = at<int>(delta.dev, P.oNewOff); a.oldPool = oldPool; a.newPool = newPool;
+      hipLaunchKernelGGL(mapdb::k_mapdb_rows_repack, dim3((unsigned)((P.nKfBefore + mapdb::kRowWaves - 1) / mapdb::kRowWaves)), dim3(mapdb::kRowThreads), 0, s, a);
+    },
+    [&](const mapdb::RowPlan& P, int* st, int* ln, int* pl) {
+      mapdb::RowsApplyArgs a;
+      a.nHeaderRec = P.nHeaderRec; a.nEntryRec = P.nEntryRec; a.nPayload = (int)P.nPayload; a.tail = (int)P.tail;
+      a.header = at<mapdb::RowHeaderRec>(delta.dev, P.oHeader); a.entry = at<mapdb::RowEntryRec>(delta.dev, P.oEntry);
+      a.payload = at<int>(delta.dev, P.oPayload);
+      a.rowStart = st; a.rowLen = ln; a.pool = pl;
+      const unsigned blocks = applyBlocks((size_t)P.nHeaderRec + P.nEntryRec, P.nPayload, mapdb::kRowThreads);
+      hipLaunchKernelGGL(mapdb::k_mapdb_rows_apply, dim3(blocks), dim3(mapdb::kRowThreads), 0, s, a);
+    });
+}
+
+// The staged rows, after the points: a row may name a point that got its slot in the same interval.
+int syncRows(ydorb_mapdb* h) { return syncIntSpans(h, h->rows, h->rowDelta, h->rowHdr, h->rowPoolMem, h->rowStart, h->rowLen, h->rowPool); }
+
+// The staged views and descriptor blocks, after points and rows: a view may name a keyframe, and a query a point, of the same interval.
+int syncDescriptors(ydorb_mapdb* h) {
+  int rc = syncIntSpans(h, h->desc.views, h->viewDelta, h->viewHdr, h->viewPoolMem, h->viewStart, h->viewLen, h->viewPool);
+  if (rc) return rc;
+  hipStream_t s = h->c.stream;
+  DeltaPair& delta = h->blockDelta;
+  return syncSpans(h, h->desc.blocks, delta, h->blockHdr, h->blockPoolMem, h->blockStart, h->blockLen, h->blockPool,
+    [&](const mapdb::RowPlan& P, int* st, int* ln, mapdb::DescRow* oldPool, mapdb::DescRow* newPool) {
+      mapdb::DescRepackArgs a;
+      a.nKf = P.nKfBefore; a.blockStart = st; a.blockLen = ln; a.newOff = at<int>(delta.dev, P.oNewOff);
+      a.oldPool = reinterpret_cast<const uint4*>(oldPool); a.newPool = reinterpret_cast<uint4*>(newPool);
+      hipLaunchKernelGGL(mapdb::k_mapdb_desc_repack, dim3((unsigned)((P.nKfBefore + mapdb::kDescWaves - 1) / mapdb::kDescWaves)), dim3(mapdb::kDescThreads), 0, s, a);
+    },
+    [&](const mapdb::RowPlan& P, int* st, int* ln, mapdb::DescRow* pl) {
+      mapdb::DescApplyArgs a;
+      a.nHeaderRec = P.nHeaderRec; a.nPayload16 = 2 * P.nPayload; a.tail = (int)P.tail;
+      a.header = at<mapdb::RowHeaderRec>(delta.dev, P.oHeader); a.payload = at<uint4>(delta.dev, P.oPayload);
+      a.blockStart = st; a.blockLen = ln; a.pool = reinterpret_cast<uint4*>(pl);
+      const unsigned blocks = applyBlocks((size_t)P.nHeaderRec, 2 * P.nPayload, mapdb::kDescThreads);
+      hipLaunchKernelGGL(mapdb::k_mapdb_desc_apply, dim3(blocks), dim3(mapdb::kDescThreads), 0, s, a);
+    });
+}
+
 int sync(ydorb_mapdb* h) {
-  const int rc = syncPoints(h);
-  return rc ? rc : syncRows(h);
+  int rc = syncPoints(h);
+  if (!rc) rc = syncRows(h);
+  return rc ? rc : syncDescriptors(h);
 }
 
 // first / seenStamp cover the point table's capacity: a fresh pair when it grew.  first is INT32_MAX everywhere between calls.
@@ -250,12 +302,17 @@ extern "C" int ydorb_mapdb_create(int32_t device, int32_t point_capacity, int32_
       !(rc = allocCentres(h->c.stream, h->centres, h->T.centre, (size_t)h->host.kfCap())) &&
       !(rc = allocPool(h->pool, h->poolKf, h->poolLevel, (size_t)h->host.poolCap())) &&
       !(rc = allocRowHeaders(h->c.stream, h->rowHdr, h->rowStart, h->rowLen, (size_t)h->rows.hdrCap())) &&
-      !(rc = h->rowPoolMem.alloc(4 * (size_t)h->rows.poolCap())) && hipStreamSynchronize(h->c.stream) != hipSuccess) {
+      !(rc = h->rowPoolMem.alloc(4 * (size_t)h->rows.poolCap())) &&
+      !(rc = allocRowHeaders(h->c.stream, h->viewHdr, h->viewStart, h->viewLen, (size_t)h->desc.views.hdrCap())) &&
+      !(rc = allocRowHeaders(h->c.stream, h->blockHdr, h->blockStart, h->blockLen, (size_t)h->desc.blocks.hdrCap())) &&
+      !(rc = h->viewPoolMem.alloc(4 * (size_t)h->desc.views.poolCap())) &&
+      !(rc = h->blockPoolMem.alloc(sizeof(mapdb::DescRow) * (size_t)h->desc.blocks.poolCap())) && hipStreamSynchronize(h->c.stream) != hipSuccess) {
     set_error("hipStreamSynchronize failed");
     rc = YDORB_ERR_HIP;
   }
   if (rc) { ydorb_mapdb_destroy(h); return rc; }
   h->rowPool = h->rowPoolMem.as<int>();
+  h->viewPool = h->viewPoolMem.as<int>(); h->blockPool = h->blockPoolMem.as<mapdb::DescRow>();
   *out = h;
   return YDORB_OK;
 }
@@ -267,6 +324,7 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   h->c.releaseBuffers();
   h->points.release(); h->centres.release(); h->pool.release(); h->delta.release();
   h->rowHdr.release(); h->rowPoolMem.release(); h->rowDelta.release(); h->rowset.release();
+  h->viewHdr.release(); h->viewPoolMem.release(); h->viewDelta.release(); h->blockHdr.release(); h->blockPoolMem.release(); h->blockDelta.release();
   delete h;
 }
 
@@ -276,8 +334,11 @@ extern "C" int ydorb_mapdb_clear(ydorb_mapdb_t* h) {
   HIPCHK(hipSetDevice(h->device));
   h->host.clear();
   h->rows.clear();
+  h->desc.clear();
   hipStream_t s = h->c.stream;   // every slot reads as never set again
   HIPCHK(hipMemsetAsync(h->rowHdr.p, 0, h->rowHdr.cap, s));
+  HIPCHK(hipMemsetAsync(h->viewHdr.p, 0, h->viewHdr.cap, s));
+  HIPCHK(hipMemsetAsync(h->blockHdr.p, 0, h->blockHdr.cap, s));
   if (h->rowsetCap) {
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->first, INT32_MAX, h->rowsetCap, s));
     HIPCHK(hipMemsetAsync(h->seenStamp, 0, 4 * h->rowsetCap, s));
@@ -647,4 +708,133 @@ extern "C" int ydorb_mapdb_observer_counter(ydorb_mapdb_t* h, int32_t n_lists, c
   if (rc) return rc;
   mapmaint::MapSource src = sourceOf(h);
   return mapmaint::runCovisibility(h->c, src, self.data(), n_lists, ls.data(), idx.data(), out_start, conn_kf, conn_weight, counts, status);
+}
+
+// ------------------------------------------------------------------------------------------- point views and descriptor blocks
+extern "C" int ydorb_mapdb_reserve_descriptors(ydorb_mapdb_t* h, int64_t view_capacity, int64_t descriptor_capacity) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!h->desc.reserve(view_capacity, descriptor_capacity, err)) return invalid(err);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->c.stream));   // nothing in flight reads the arenas given back below
+  int rc;
+  if ((rc = h->viewPoolMem.alloc(4 * (size_t)h->desc.views.poolCap())) || (rc = h->blockPoolMem.alloc(sizeof(mapdb::DescRow) * (size_t)h->desc.blocks.poolCap())))
+    return rc;
+  h->viewPool = h->viewPoolMem.as<int>(); h->blockPool = h->blockPoolMem.as<mapdb::DescRow>();
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_set_keyframe_descriptors(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n, const int32_t* desc_start,
+                                                    const uint8_t* desc) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!h->desc.setBlocks(kf_slots, n, desc_start, desc, err)) return invalid(err);
+  h->host.growKeyframes(h->desc.blocks.nKeyframes());
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_set_point_views(ydorb_mapdb_t* h, const int32_t* slots, int32_t n, const int32_t* view_start, const int32_t* view_kf,
+                                           const int32_t* view_idx) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  return h->desc.setViews(slots, n, view_start, view_kf, view_idx, h->host.nPoints(), h->host.nKeyframes(), err) ? YDORB_OK : invalid(err);
+}
+
+extern "C" int ydorb_mapdb_desc_stats(ydorb_mapdb_t* h, YdMapDbDescStats* stats) {
+  if (!h || !stats) return invalid("null handle or stats");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  h->desc.stats(*stats);
+  return YDORB_OK;
+}
+
+// sync; one upload of the slots; one wave per named point; one read-back; one synchronise.  No descriptor travels up.
+extern "C" int ydorb_mapdb_distinctive_descriptors(ydorb_mapdb_t* h, const int32_t* slots, int32_t n, int32_t* best, int32_t* best_view,
+                                                   uint8_t* desc_out, uint8_t* status) {
+  std::string err;
+  if (!mapdb::DescHost::checkQuery(slots, n, -1, best, best_view, desc_out, status, err)) return invalid(err);   // nulls and signs first
+  if (!h) {   // without a device no handle exists: say that, there is no CPU path to fall back to
+    const int rc = require_device(0);
+    return rc ? rc : invalid("null handle");
+  }
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (!mapdb::DescHost::checkQuery(slots, n, h->host.nPoints(), best, best_view, desc_out, status, err)) return invalid(err);
+  if (n == 0) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  const size_t nq = (size_t)n;
+  Layout D;
+  const size_t dDesc = D.add(32 * nq), dBest = D.add(4 * nq), dView = D.add(8 * nq), dSt = D.add(nq);
+  if ((rc = c.ensure(4 * nq + 16, D.bytes))) return rc;
+  std::memcpy(c.hUp.p, slots, 4 * nq);
+  hipStream_t s = c.stream;
+  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, 4 * nq, hipMemcpyHostToDevice, s));
+  mapdb::DistinctiveArgs a;
+  a.n = n; a.nViewHdr = h->desc.views.hdrCap(); a.nBlockHdr = h->desc.blocks.hdrCap();
+  a.slots = c.up.as<int>(); a.bad = h->T.bad;
+  a.viewStart = h->viewStart; a.viewLen = h->viewLen; a.viewPool = h->viewPool;
+  a.blockStart = h->blockStart; a.blockLen = h->blockLen; a.blockPool = reinterpret_cast<const uint4*>(h->blockPool);
+  a.best = at<int>(c.down, dBest); a.bestView = at<int>(c.down, dView); a.descOut = at<uint4>(c.down, dDesc); a.status = at<uint8_t>(c.down, dSt);
+  hipLaunchKernelGGL(mapdb::k_mapdb_distinctive, dim3((unsigned)((nq + mapdb::kDescWaves - 1) / mapdb::kDescWaves)), dim3(mapdb::kDescThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(desc_out, at<void>(c.hDown, dDesc), 32 * nq); std::memcpy(best, at<void>(c.hDown, dBest), 4 * nq);
+  std::memcpy(best_view, at<void>(c.hDown, dView), 8 * nq); std::memcpy(status, at<void>(c.hDown, dSt), nq);
+  return YDORB_OK;
+}
+
+// the headers and the used part of the pool of one span relation, read back into c.hDown
+template <class T> int downloadSpans(ydorb_mapdb* h, size_t held, size_t used, const int* start, const int* len, const T* pool, size_t& dStart,
+                                     size_t& dLen, size_t& dPool) {
+  StagedCtx& c = h->c;
+  Layout D;
+  dStart = D.add(4 * held); dLen = D.add(4 * held); dPool = D.add(sizeof(T) * used);
+  D.add(16);
+  int rc = c.hDown.ensure(D.bytes);
+  if (rc) return rc;
+  hipStream_t s = c.stream;
+  if (held) {
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dStart), start, 4 * held, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dLen), len, 4 * held, hipMemcpyDeviceToHost, s));
+  }
+  if (used) HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dPool), pool, sizeof(T) * used, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_export_views(ydorb_mapdb_t* h, int32_t* view_start, int32_t* view_kf, int32_t* view_idx) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (!view_start) return invalid("null view_start");
+  if (h->desc.views.liveAfterSync() > 0 && (!view_kf || !view_idx)) return invalid("null view_kf or view_idx");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  size_t dStart, dLen, dPool;
+  const size_t held = (size_t)h->desc.views.nKeyframes();
+  if ((rc = downloadSpans(h, held, (size_t)h->desc.views.poolUsed(), h->viewStart, h->viewLen, h->viewPool, dStart, dLen, dPool))) return rc;
+  mapdb::flattenViews(h->host.nPoints(), (int32_t)held, at<int32_t>(h->c.hDown, dStart), at<int32_t>(h->c.hDown, dLen), at<int32_t>(h->c.hDown, dPool),
+                      view_start, view_kf, view_idx);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_export_descriptors(ydorb_mapdb_t* h, int32_t* desc_start, uint8_t* desc) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (!desc_start) return invalid("null desc_start");
+  if (h->desc.blocks.liveAfterSync() > 0 && !desc) return invalid("null desc");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  size_t dStart, dLen, dPool;
+  const size_t held = (size_t)h->desc.blocks.nKeyframes();
+  if ((rc = downloadSpans(h, held, (size_t)h->desc.blocks.poolUsed(), h->blockStart, h->blockLen, h->blockPool, dStart, dLen, dPool))) return rc;
+  mapdb::flattenRows(h->host.nKeyframes(), (int32_t)held, at<int32_t>(h->c.hDown, dStart), at<int32_t>(h->c.hDown, dLen),
+                     at<mapdb::DescRow>(h->c.hDown, dPool), desc_start, reinterpret_cast<mapdb::DescRow*>(desc));
+  return YDORB_OK;
 }

@@ -12,6 +12,9 @@
 //             every row lies once the delta's own repack has run.
 //   pool      the rows lie in a SpanPool of their own, a replaced or erased row being its garbage: span_pool.h has the policy, and the
 //             growth rule of the headers (rowStart / rowLen per keyframe slot), which is the keyframe table's.
+// The state machine is a template over the span's element, SpanHost<T>; RowsHost is SpanHost<int32_t>.  mapdb_desc_host.h keeps two more
+// relations in it: a point's views (int32 spans keyed by point slot, staged through stage() after a validation of their own) and a
+// keyframe's descriptor block (spans of 32-byte rows).  setRows / setEntries and the two query checks belong to the keyframe rows.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -39,26 +42,28 @@ struct RowPlan : PoolPlan {
 };
 
 // the arrays the kernels keep, on the host
-struct RowTables {
-  std::vector<int32_t> rowStart, rowLen, pool;
+template <class T> struct SpanTables {
+  std::vector<int32_t> rowStart, rowLen;
+  std::vector<T> pool;
 };
+using RowTables = SpanTables<int32_t>;
 
 // row_start [nKf + 1] / point_slot from per-slot headers; a slot at or past `nHeld` has no row
-inline void flattenRows(int32_t nKf, int32_t nHeld, const int32_t* rowStart, const int32_t* rowLen, const int32_t* pool, int32_t* outStart,
-                        int32_t* outSlot) {
+template <class T> void flattenRows(int32_t nKf, int32_t nHeld, const int32_t* rowStart, const int32_t* rowLen, const T* pool, int32_t* outStart,
+                                    T* outSlot) {
   int32_t at = 0;
   outStart[0] = 0;
   for (int32_t k = 0; k < nKf; k++) {
     const int32_t len = k < nHeld ? rowLen[k] : 0;
-    if (len > 0) memcpy(outSlot + at, pool + rowStart[k], 4 * (size_t)len);
+    if (len > 0) memcpy(outSlot + at, pool + rowStart[k], sizeof(T) * (size_t)len);
     at += len;
     outStart[k + 1] = at;
   }
 }
 
-class RowsHost {
+template <class T> class SpanHost {
  public:
-  RowsHost(int32_t hdrCap, int64_t poolCap) : hdrCap_(std::max(hdrCap, 1)), pool_(poolCap) {}
+  SpanHost(int32_t hdrCap, int64_t poolCap) : hdrCap_(std::max(hdrCap, 1)), pool_(poolCap) {}
 
   int32_t nKeyframes() const { return (int32_t)row_.size(); }   // 1 + the highest slot a row call named
   int32_t hdrCap() const { return hdrCap_; }
@@ -68,7 +73,7 @@ class RowsHost {
   int32_t headerGrowths() const { return hdrGrowths_; }
   bool dirty() const { return !dirtyRows_.empty() || !dirtyEntries_.empty(); }
   int32_t lenOf(int32_t kf) const { return kf < nKeyframes() ? (int32_t)row_[(size_t)kf].size() : 0; }   // staged changes included
-  const std::vector<int32_t>& rowOf(int32_t kf) const { return row_[(size_t)kf]; }
+  const std::vector<T>& rowOf(int32_t kf) const { return row_[(size_t)kf]; }
 
   void clear() {
     row_.clear(); off_.clear(); len_.clear(); state_.clear();
@@ -91,14 +96,28 @@ class RowsHost {
     for (int32_t q = 0; q < N; q++)
       if (pointSlot[q] < -1 || pointSlot[q] >= nPoints)
         return fail(err, "row entry %lld: point slot %lld outside -1..%lld; set the point before a row names it", q, pointSlot[q], (long long)nPoints - 1);
-    if (!pool_.admits(kfSlots, n, rowStart, [this](int32_t k) { return lenOf(k); }, checkRowPoolTotal, err)) return false;
+    return stage(kfSlots, n, rowStart, pointSlot, checkRowPoolTotal, err);
+  }
+
+  // Stages whole spans the caller has validated (n > 0, starts well formed, no negative slot): value [start[n]].  check: the pool's
+  // INT32_MAX guard, as in SpanPool::admits.
+  template <class Check> bool stage(const int32_t* slots, int32_t n, const int32_t* start, const T* value, Check check, std::string& err) {
+    if (!pool_.admits(slots, n, start, [this](int32_t k) { return lenOf(k); }, check, err)) return false;
     for (int32_t i = 0; i < n; i++) {
-      const int32_t k = kfSlots[i];
+      const int32_t k = slots[i];
       growTo(k);
       if (state_[k] != kFull) { state_[k] = kFull; dirtyRows_.push_back(k); }
-      pool_.restaged(lenOf(k), rowStart[i + 1] - rowStart[i]);
-      row_[k].assign(pointSlot + rowStart[i], pointSlot + rowStart[i + 1]);
+      pool_.restaged(lenOf(k), start[i + 1] - start[i]);
+      if (start[i + 1] > start[i]) row_[k].assign(value + start[i], value + start[i + 1]);
+      else row_[k].clear();
     }
+    return true;
+  }
+
+  // An empty pool takes the capacity it is told: before anything was staged or synced, or after clear().
+  bool reserve(int64_t poolCap) {
+    if (pool_.used != 0 || pool_.pending != 0 || dirty()) return false;
+    pool_.cap = std::max<int64_t>(poolCap, 1);
     return true;
   }
 
@@ -157,7 +176,7 @@ class RowsHost {
     P.nKfBefore = nKfSynced_; P.hdrCapBefore = hdrCap_; P.hdrCap = grownCap(nKeyframes(), hdrCap_);
     Layout L;
     P.oHeader = L.add(sizeof(RowHeaderRec) * (size_t)P.nHeaderRec); P.oEntry = L.add(sizeof(RowEntryRec) * (size_t)P.nEntryRec);
-    P.oPayload = L.add(4 * (size_t)P.nPayload);
+    P.oPayload = L.add(sizeof(T) * (size_t)P.nPayload);
     P.oNewOff = L.add(P.repack ? 4 * (size_t)P.nKfBefore : 0); P.bytes = L.bytes;
     return P;
   }
@@ -168,20 +187,20 @@ class RowsHost {
     if (P.repack)
       survivorOffsets(P.nKfBefore, len_.data(), off_.data(), reinterpret_cast<int32_t*>(dst + P.oNewOff), [this](int32_t k) { return state_[k] == kFull; });
     RowHeaderRec* hr = reinterpret_cast<RowHeaderRec*>(dst + P.oHeader);
-    int32_t* pay = reinterpret_cast<int32_t*>(dst + P.oPayload);
+    T* pay = reinterpret_cast<T*>(dst + P.oPayload);
     int64_t cursor = 0;
     for (const int32_t k : dirtyRows_) {
       const int32_t len = (int32_t)row_[k].size();
       off_[k] = (int32_t)(P.tail + cursor); len_[k] = len;
       *hr++ = RowHeaderRec{k, off_[k], len, 0};
-      if (len) memcpy(pay + cursor, row_[k].data(), 4 * (size_t)len);
+      if (len) memcpy(pay + cursor, row_[k].data(), sizeof(T) * (size_t)len);
       cursor += len;
     }
     RowEntryRec* er = reinterpret_cast<RowEntryRec*>(dst + P.oEntry);
     for (const uint64_t key : dirtyEntries_) {
       const int32_t k = (int32_t)(key >> 32), i = (int32_t)(uint32_t)key;
       if (state_[k] == kFull) continue;
-      *er++ = RowEntryRec{off_[k] + i, row_[k][(size_t)i]};   // off_: after this delta's repack
+      *er++ = RowEntryRec{off_[k] + i, entryValue(row_[k][(size_t)i])};   // off_: after this delta's repack
     }
     for (const int32_t k : dirtyRows_) state_[k] = kClean;
     dropStaged();
@@ -199,8 +218,10 @@ class RowsHost {
     row_.resize(n); off_.resize(n, 0); len_.resize(n, 0); state_.resize(n, kClean);
   }
   void dropStaged() { dirtyRows_.clear(); dirtyEntries_.clear(); entryAt_.clear(); }
+  static int32_t entryValue(int32_t v) { return v; }
+  template <class U> static int32_t entryValue(const U&) { return 0; }   // only int32 spans have single-entry records
 
-  std::vector<std::vector<int32_t>> row_;   // the mirror: what the device holds once the staged changes are applied
+  std::vector<std::vector<T>> row_;   // the mirror: what the device holds once the staged changes are applied
   std::vector<int32_t> off_, len_;          // where the device holds each row now
   std::vector<uint8_t> state_;
   std::vector<int32_t> dirtyRows_;
@@ -210,16 +231,17 @@ class RowsHost {
   SpanPool pool_;
   int64_t lastSyncBytes_ = 0, lastSyncRecords_ = 0;
 };
+using RowsHost = SpanHost<int32_t>;
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The packed delta executed on host arrays, step for step what the driver does on the device: grow the headers (contents kept, new
 // slots empty), repack (k_mapdb_rows_repack), apply (k_mapdb_rows_apply).
-inline void executeRows(const RowPlan& P, const uint8_t* delta, RowTables& T) {
+template <class E> void executeRows(const RowPlan& P, const uint8_t* delta, SpanTables<E>& T) {
   if (T.rowStart.size() != (size_t)P.hdrCap) { T.rowStart.resize((size_t)P.hdrCap, 0); T.rowLen.resize((size_t)P.hdrCap, 0); }
   if (T.pool.size() != (size_t)P.poolCapBefore) T.pool.resize((size_t)P.poolCapBefore);
   if (P.repack) {
     const int32_t* newOff = reinterpret_cast<const int32_t*>(delta + P.oNewOff);
-    std::vector<int32_t> fresh((size_t)P.poolCap);
+    std::vector<E> fresh((size_t)P.poolCap);
     for (int32_t k = 0; k < P.nKfBefore; k++) {
       if (newOff[k] < 0) continue;
       for (int32_t q = 0; q < T.rowLen[k]; q++) fresh.at((size_t)(newOff[k] + q)) = T.pool.at((size_t)(T.rowStart[k] + q));
@@ -230,8 +252,8 @@ inline void executeRows(const RowPlan& P, const uint8_t* delta, RowTables& T) {
   const RowHeaderRec* hr = reinterpret_cast<const RowHeaderRec*>(delta + P.oHeader);
   for (int32_t i = 0; i < P.nHeaderRec; i++) { T.rowStart.at((size_t)hr[i].kf) = hr[i].start; T.rowLen.at((size_t)hr[i].kf) = hr[i].len; }
   const RowEntryRec* er = reinterpret_cast<const RowEntryRec*>(delta + P.oEntry);
-  for (int32_t i = 0; i < P.nEntryRec; i++) T.pool.at((size_t)er[i].at) = er[i].value;
-  const int32_t* pay = reinterpret_cast<const int32_t*>(delta + P.oPayload);
+  for (int32_t i = 0; i < P.nEntryRec; i++) memcpy(&T.pool.at((size_t)er[i].at), &er[i].value, 4);   // int32 spans only
+  const E* pay = reinterpret_cast<const E*>(delta + P.oPayload);
   for (int64_t i = 0; i < P.nPayload; i++) T.pool.at((size_t)(P.tail + i)) = pay[i];
 }
 

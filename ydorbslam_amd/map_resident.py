@@ -2,13 +2,15 @@
 of map maintenance kept in HBM between calls, changed by deltas and queried with no table upload.  MapDb owns one ydorb_mapdb_t.  Its
 three queries go through map_maintenance's own wrappers (same argument preparation, same result dictionaries), with the handle in place
 of the flat table.  MapDb.correct (ydorb_mapdb_correct) runs the point loops of loop closing on the table in place.
-The keyframe rows (DESIGN.md section 6o) add the relation keyframe -> map points and the two set queries of Tracking::updateLocalMap."""
+The keyframe rows (DESIGN.md section 6o) add the relation keyframe -> map points and the two set queries of Tracking::updateLocalMap.
+The resident descriptors add the keyframes' descriptor blocks and the points' views, and
+MapPoint::computeDistinctiveDescriptors over them with no descriptor upload."""
 import ctypes as C
 
 import numpy as np
 
 from . import map_maintenance as M
-from ._lib import YdMapCorrection, YdMapDbRowStats, YdMapDbStats, check, lib
+from ._lib import YdMapCorrection, YdMapDbDescStats, YdMapDbRowStats, YdMapDbStats, check, lib
 
 _p = M._p
 
@@ -194,6 +196,62 @@ class MapDb:
         take = [int(counts[q]) if status[q] == 0 else 0 for q in range(nl)]
         return dict(kf=[kf[os_[q]:os_[q] + take[q]] for q in range(nl)], weight=[w[os_[q]:os_[q] + take[q]] for q in range(nl)],
                     counts=counts[:nl], status=status[:nl], point_bad=[pbad[ls[q]:ls[q + 1]] for q in range(nl)], raw_kf=kf, raw_weight=w)
+
+    # ------------------------------------------------------------------------------------------------------------ resident descriptors
+    def reserve_descriptors(self, view_capacity, descriptor_capacity):
+        """Initial capacities of the view pool (views) and the descriptor pool (descriptors); both pools must be empty."""
+        check(lib().ydorb_mapdb_reserve_descriptors(self._h, view_capacity, descriptor_capacity))
+
+    def set_keyframe_descriptors(self, kf_slots, blocks):
+        """blocks[i] = the descriptor matrix [n_k, 32] uint8 of keyframe slot kf_slots[i] in keypoint order; an empty block erases."""
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        assert len(blocks) == len(kf_slots)
+        blocks = [np.ascontiguousarray(b, np.uint8).reshape(-1, 32) for b in blocks]
+        start = np.concatenate([[0], np.cumsum([len(b) for b in blocks])]).astype(np.int32)
+        desc = np.ascontiguousarray(np.concatenate(blocks + [np.zeros((1, 32), np.uint8)]))
+        check(lib().ydorb_mapdb_set_keyframe_descriptors(self._h, _p(kf_slots), len(kf_slots), _p(start), _p(desc)))
+
+    def set_point_views(self, slots, views):
+        """views[i] = the places point slots[i] is seen, [m, 2] int32 (keyframe slot, keypoint index) in the observation container's
+        order; an empty list erases."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        assert len(views) == len(slots)
+        views = [np.ascontiguousarray(v, np.int32).reshape(-1, 2) for v in views]
+        start = np.concatenate([[0], np.cumsum([len(v) for v in views])]).astype(np.int32)
+        flat = np.concatenate(views + [np.zeros((1, 2), np.int32)])
+        kf, idx = np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
+        check(lib().ydorb_mapdb_set_point_views(self._h, _p(slots), len(slots), _p(start), _p(kf), _p(idx)))
+
+    def distinctive_descriptors(self, slots):
+        """ydorb_mapdb_distinctive_descriptors for the named slots.  Returns dict(best [n], best_view [n, 2], desc [n, 32], status [n])."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(slots)
+        m = max(n, 1)
+        best, view = np.full(m, -7, np.int32), np.full((m, 2), -7, np.int32)
+        desc, st = np.full((m, 32), 7, np.uint8), np.full(m, 9, np.uint8)
+        check(lib().ydorb_mapdb_distinctive_descriptors(self._h, _p(slots), n, _p(best), _p(view), _p(desc), _p(st)))
+        return dict(best=best[:n], best_view=view[:n], desc=desc[:n], status=st[:n])
+
+    def desc_stats(self):
+        s = YdMapDbDescStats()
+        check(lib().ydorb_mapdb_desc_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in YdMapDbDescStats._fields_}
+
+    def export_views(self):
+        """The device's views read back: one [m, 2] int32 array per point slot 0 .. n_points-1."""
+        n, N = self.n_points, self.desc_stats()["n_views"]
+        start, kf, idx = np.zeros(n + 1, np.int32), np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int32)
+        check(lib().ydorb_mapdb_export_views(self._h, _p(start), _p(kf), _p(idx)))
+        assert int(start[-1]) == N
+        return [np.stack([kf[start[i]:start[i + 1]], idx[start[i]:start[i + 1]]], axis=1) for i in range(n)]
+
+    def export_descriptors(self):
+        """The device's blocks read back: one [n_k, 32] uint8 array per keyframe slot 0 .. n_keyframes-1."""
+        k, N = self.n_keyframes, self.desc_stats()["n_descriptors"]
+        start, desc = np.zeros(k + 1, np.int32), np.zeros((max(N, 1), 32), np.uint8)
+        check(lib().ydorb_mapdb_export_descriptors(self._h, _p(start), _p(desc)))
+        assert int(start[-1]) == N
+        return [desc[start[i]:start[i + 1]].copy() for i in range(k)]
 
     # ------------------------------------------------------------------------------------------------------------ inspection
     def stats(self):
