@@ -1,6 +1,7 @@
 // Stand-alone check of ydorbslam_amd/csrc/skyline_plan.h (no HIP, no GPU): the order and the envelope of the block-skyline Cholesky on
 // small graphs whose difficulties are known.  tests/test_essgraph_skyline_cpu.py builds it with -fsanitize=address,undefined and runs it
-// as its own process.  Prints one line per graph and ordering; the exit status is the number of failed properties.
+// as its own process.  Prints one line per graph and ordering; the exit status is the number of failed properties.  Then the two
+// directions between an envelope and the dense matrix (expandEnvelope, packEnvelope) for both block sizes, which print failures only.
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -141,6 +142,59 @@ void checkPlan(const TestGraph& g, int ordering, int nF, const std::vector<int>&
   EXPECT(sameArrays(P, again), "%s: two calls differ", nm);
 }
 
+// expandEnvelope / packEnvelope on plan P of B x B blocks.  The envelope holds distinct values, the upper triangle of a diagonal block
+// mirroring its lower one, so that both conventions for the diagonal have to give the same symmetric matrix and packing returns the bytes.
+template <int B> void checkEnvelope(const char* nm, const Plan& P) {
+  using namespace ydorb::sky;
+  const size_t N = (size_t)B * P.nF;
+  std::vector<double> env(B * B * (size_t)P.envBlocks);
+  for (size_t k = 0; k < env.size(); k++) env[k] = 1.0 + (double)k;
+  for (int i = 0; i < P.nF; i++) {
+    double* D = &env[B * B * (size_t)(P.rowOff[i + 1] - 1)];
+    for (int r = 0; r < B; r++)
+      for (int c = r + 1; c < B; c++) D[B * r + c] = D[B * c + r];
+  }
+  std::vector<double> whole(N * N, -1.0), lower(N * N, -2.0), back(env.size(), -3.0);
+  expandEnvelope<B>(P, env.data(), whole.data(), kDiagWhole);
+  expandEnvelope<B>(P, env.data(), lower.data(), kDiagLower);
+  EXPECT(whole == lower, "%s B = %d: the two diagonal conventions differ on symmetric diagonal blocks", nm, B);
+  size_t asym = 0, outside = 0, inside = 0;
+  for (size_t r = 0; r < N; r++)
+    for (size_t c = 0; c < N; c++) {
+      asym += whole[r * N + c] != whole[c * N + r];
+      const int pi = P.inv[r / B], pj = P.inv[c / B], i = std::max(pi, pj), j = std::min(pi, pj);
+      if (j < P.first[i]) outside += whole[r * N + c] != 0.0; else inside += whole[r * N + c] == 0.0;
+    }
+  EXPECT(asym == 0 && outside == 0 && inside == 0, "%s B = %d: %zu asymmetric, %zu set outside the envelope, %zu left zero inside", nm, B, asym, outside, inside);
+  packEnvelope<B>(P, whole.data(), back.data());
+  EXPECT(back == env, "%s B = %d: packing the expansion does not return the envelope", nm, B);
+  // where the conventions part: with a diagonal block's upper triangle spoilt, kDiagWhole copies it and kDiagLower does not read it
+  std::vector<double> spoilt = env;
+  spoilt[B * B * (size_t)(P.rowOff[1] - 1) + 1] = -7.0;   // entry (0, 1) of the first diagonal block
+  expandEnvelope<B>(P, spoilt.data(), whole.data(), kDiagWhole);
+  EXPECT(whole != lower, "%s B = %d: kDiagWhole did not copy the stored upper triangle", nm, B);
+  expandEnvelope<B>(P, spoilt.data(), whole.data(), kDiagLower);
+  EXPECT(whole == lower, "%s B = %d: kDiagLower read the upper triangle", nm, B);
+}
+
+void checkEnvelopes() {
+  using namespace ydorb::sky;
+  std::vector<std::pair<int, int>> star;
+  for (int v = 1; v < 5; v++) star.push_back({0, v});
+  const TestGraph gs[] = {{"closed ring 12", 12, {}, ring(12)}, {"star 5, hub first", 5, {}, star}};
+  for (const TestGraph& g : gs)
+    for (int ordering : {kOrderNatural, kOrderRcm}) {
+      int nF;
+      std::vector<int> a, b;
+      freePairs(g, nF, a, b);
+      Plan P = makePlan(nF, (int)a.size(), a.data(), b.data(), ordering);
+      buildColumns(P);
+      EXPECT(P.orderingUsed == ordering && nF == g.nV, "%s", g.name.c_str());
+      checkEnvelope<6>(g.name.c_str(), P);
+      checkEnvelope<7>(g.name.c_str(), P);
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -165,6 +219,7 @@ int main() {
     printf("%-36s free %3d  envelope natural %5lld  rcm %5lld  longest row %3d / %3d  smaller -> %s\n", g.name.c_str(), nF, (long long)nat.envBlocks,
            (long long)rcm.envBlocks, nat.maxRowBlocks, rcm.maxRowBlocks, smaller.orderingUsed == kOrderRcm ? "rcm" : "natural");
   }
+  checkEnvelopes();
   printf("%d failed\n", g_failed);
   return g_failed ? 1 : 0;
 }

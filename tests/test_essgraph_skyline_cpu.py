@@ -21,7 +21,10 @@ def test_plan_properties_in_a_sanitized_program(tmp_path):
     """perm is a permutation, every free edge lies inside the envelope, first[f] <= f and is attained, the column lists are ascending and
     match first, SMALLER is never larger than NATURAL (natural on a tie), a ring under RCM has rows of at most 3 blocks (n = 12, 101),
     two calls give identical arrays: on two, six, ring12 with repeated pairs, tree40, both stars, two components, a fixed vertex in
-    mid-numbering and two fixed vertices.  The program is its own process; nothing is loaded into this one."""
+    mid-numbering and two fixed vertices.  Then, for 6x6 and 7x7 blocks on a closed ring of 12 and a star of 5 with the hub first under
+    the natural and the RCM plan: an envelope of distinct values expands to a symmetric matrix that is zero outside the envelope under
+    both conventions for the diagonal blocks, and packing the expansion returns the envelope's bytes (failures only are printed).  The
+    program is its own process; nothing is loaded into this one."""
     exe = str(tmp_path / "skyline_plan_check")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=undefined", PLAN_SRC, "-o", exe])

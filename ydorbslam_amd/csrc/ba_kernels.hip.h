@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "g2o_math.hip.h"
+#include "sky_blocks.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -331,7 +332,9 @@ __global__ __launch_bounds__(256) void k_dinv(const R* __restrict__ Hll, const R
 // reduction, no atomics, fixed summation order (the first version issued 13 M FP64 atomics per trial: 0.87 ms).
 __device__ __forceinline__ int pair_bucket(int i1, int i2) { return i2 * (i2 + 1) / 2 + i1; }  // i2 >= i1
 
-__global__ __launch_bounds__(256) void k_pair_count(EdgeSoA Ed, const int* __restrict__ ptStart, int nL, int* __restrict__ cnt) {
+// The pairs of a thread's landmark: f(a, b, i1, i2) for every two edges a <= b of landmark l whose poses i1, i2 are free.  The dense and
+// the skyline pair kernels (ba_skyline.hip.h) are this walk with their own bucket of (i1, i2), counted or filled.
+template <class F> __device__ __forceinline__ void pair_walk(const EdgeSoA& Ed, const int* __restrict__ ptStart, int nL, F f) {
   const int l = blockIdx.x * 256 + threadIdx.x;
   if (l >= nL) return;
   for (int a = ptStart[l]; a < ptStart[l + 1]; a++) {
@@ -339,9 +342,12 @@ __global__ __launch_bounds__(256) void k_pair_count(EdgeSoA Ed, const int* __res
     if (i1 < 0) continue;
     for (int b = a; b < ptStart[l + 1]; b++) {
       const int i2 = Ed.pidx[b];  // edges of a landmark are sorted by pose index: i2 >= i1
-      if (i2 >= 0) atomicAdd(&cnt[pair_bucket(i1, i2)], 1);
+      if (i2 >= 0) f(a, b, i1, i2);
     }
   }
+}
+__global__ __launch_bounds__(256) void k_pair_count(EdgeSoA Ed, const int* __restrict__ ptStart, int nL, int* __restrict__ cnt) {
+  pair_walk(Ed, ptStart, nL, [&](int, int, int i1, int i2) { atomicAdd(&cnt[pair_bucket(i1, i2)], 1); });
 }
 // exclusive scan of n ints by one workgroup: out[0..n], out[n] = total
 __global__ __launch_bounds__(256) void k_excl_scan(const int* __restrict__ in, int n, int* __restrict__ out) {
@@ -369,16 +375,7 @@ __global__ __launch_bounds__(256) void k_excl_scan(const int* __restrict__ in, i
 }
 __global__ __launch_bounds__(256) void k_pair_fill(EdgeSoA Ed, const int* __restrict__ ptStart, int nL, int* __restrict__ cursor,
                                                    int2* __restrict__ items) {
-  const int l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= nL) return;
-  for (int a = ptStart[l]; a < ptStart[l + 1]; a++) {
-    const int i1 = Ed.pidx[a];
-    if (i1 < 0) continue;
-    for (int b = a; b < ptStart[l + 1]; b++) {
-      const int i2 = Ed.pidx[b];
-      if (i2 >= 0) items[atomicAdd(&cursor[pair_bucket(i1, i2)], 1)] = make_int2(a, b);
-    }
-  }
+  pair_walk(Ed, ptStart, nL, [&](int a, int b, int i1, int i2) { items[atomicAdd(&cursor[pair_bucket(i1, i2)], 1)] = make_int2(a, b); });
 }
 // order every bucket by its first edge index (== by landmark): rank sort from LDS, one wave per bucket, out of place.
 // Buckets with more than kSortCap entries are copied unsorted (their summation order is then not reproducible run to run).
@@ -457,32 +454,19 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 #define SCHUR_WAVES 4
 #endif
 constexpr int kSchurWaves = SCHUR_WAVES;   // waves per bucket
-__device__ __forceinline__ void b_schur_pairs(const int* __restrict__ start, const int2* __restrict__ items, int nP, int nBuckets,
-                                                     const R* __restrict__ BD, const R* __restrict__ Hpl, const R* __restrict__ Hpp, R lambda,
-                                                     R contrib, int n, R* __restrict__ S, R* __restrict__ bs) {
-  // One workgroup per bucket, its items split over the workgroup's waves (the buckets of poses that see the same landmarks hold hundreds of
-  // items while most others are empty: with one wave per bucket ~700 waves carried the whole launch); the partial blocks
-  // are added in wave order, so the result does not depend on timing.
+// The block of one bucket: items [b0, b1) of `items`, split over the workgroup's waves (the buckets of poses that see the same landmarks
+// hold hundreds of items while most others are empty: with one wave per bucket ~700 waves carried the whole launch); the partial blocks
+// are added in wave order, so the result does not depend on timing.  Threads 0 .. 35 hand entry (q, r) = (threadIdx.x / 6, threadIdx.x % 6)
+// of S(i2, i1), the diagonal term included, to store(q, r, v); every thread of the workgroup has to call it (one barrier).
+// b_schur_pairs and k_sky_schur_pairs (ba_skyline.hip.h) are this sum and a store of their own.
+template <class Store> __device__ __forceinline__ void schur_block(const int2* __restrict__ items, int b0, int b1, int i1, int i2,
+                                                                    const R* __restrict__ BD, const R* __restrict__ Hpl,
+                                                                    const R* __restrict__ Hpp, R lambda, R contrib, Store store) {
   __shared__ R part[kSchurWaves][36];
-  const int bkt = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (bkt >= nBuckets) {
-    if (bkt == nBuckets) {  // the extra workgroup; padding rows/cols 6 nP .. n-1: identity (scaled like the rest for the all-reduce)
-      for (int idx = threadIdx.x; idx < (n - 6 * nP) * n; idx += 64 * kSchurWaves) {
-        const int r = 6 * nP + idx / n, c = idx % n;
-        if (c <= r) S[(size_t)r * n + c] = r == c ? contrib : 0.0;
-      }
-      for (int r = 6 * nP + threadIdx.x; r < n; r += 64 * kSchurWaves) bs[r] = 0;
-    }
-    return;
-  }
-  int i2 = (int)((sqrt(8.0 * bkt + 1.0) - 1.0) * 0.5);
-  while ((i2 + 1) * (i2 + 2) / 2 <= bkt) i2++;
-  while (i2 * (i2 + 1) / 2 > bkt) i2--;
-  const int i1 = bkt - i2 * (i2 + 1) / 2;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i16 = lane & 15, kq = lane >> 4;
   const bool live = i16 < 6;
   double4_t acc = {0.0, 0.0, 0.0, 0.0};
-  const int b0 = start[bkt], b1 = start[bkt + 1];
   const int per = (((b1 - b0) + kSchurWaves - 1) / kSchurWaves + 3) & ~3;   // items per wave, a multiple of the 4 MFMA k-slots
   const int s0 = min(b0 + wv * per, b1), s1 = min(s0 + per, b1);
   // K ordering chosen for the loads, not for the landmarks: MFMA k-slot kq takes item 4g + kq and the three instructions of a
@@ -522,8 +506,26 @@ __device__ __forceinline__ void b_schur_pairs(const int* __restrict__ start, con
 #pragma unroll
     for (int w = 0; w < kSchurWaves; w++) v -= part[w][threadIdx.x];
     if (i1 == i2) v += contrib * (Hpp[(size_t)36 * i1 + q * 6 + r] + (q == r ? lambda : 0.0));
-    S[(size_t)(6 * i2 + q) * n + 6 * i1 + r] = v;
+    store(q, r, v);
   }
+}
+__device__ __forceinline__ void b_schur_pairs(const int* __restrict__ start, const int2* __restrict__ items, int nP, int nBuckets,
+                                                     const R* __restrict__ BD, const R* __restrict__ Hpl, const R* __restrict__ Hpp, R lambda,
+                                                     R contrib, int n, R* __restrict__ S, R* __restrict__ bs) {
+  const int bkt = blockIdx.x;
+  if (bkt >= nBuckets) {
+    if (bkt == nBuckets) {  // the extra workgroup; padding rows/cols 6 nP .. n-1: identity (scaled like the rest for the all-reduce)
+      for (int idx = threadIdx.x; idx < (n - 6 * nP) * n; idx += 64 * kSchurWaves) {
+        const int r = 6 * nP + idx / n, c = idx % n;
+        if (c <= r) S[(size_t)r * n + c] = r == c ? contrib : 0.0;
+      }
+      for (int r = 6 * nP + threadIdx.x; r < n; r += 64 * kSchurWaves) bs[r] = 0;
+    }
+    return;
+  }
+  const int i2 = sky::triRow(bkt), i1 = bkt - i2 * (i2 + 1) / 2;
+  schur_block(items, start[bkt], start[bkt + 1], i1, i2, BD, Hpl, Hpp, lambda, contrib,
+              [&](int q, int r, R v) { S[(size_t)(6 * i2 + q) * n + 6 * i1 + r] = v; });
 }
 __global__ __launch_bounds__(64 * kSchurWaves) void k_schur_pairs(const int* __restrict__ start, const int2* __restrict__ items, int nP, int nBuckets,
                                                      const R* __restrict__ BD, const R* __restrict__ Hpl, const R* __restrict__ Hpp, R lambda,
@@ -667,9 +669,7 @@ __device__ __forceinline__ void potrf_block(R (*D)[NBP], R (*Lp)[NB][4], R* rdia
 }
 
 __device__ __forceinline__ int tri_index(int t, int* row) {  // t -> (row, col) of a packed lower triangle, row-major
-  int r = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-  while ((r + 1) * (r + 2) / 2 <= t) r++;
-  while (r * (r + 1) / 2 > t) r--;
+  const int r = sky::triRow(t);
   *row = r;
   return t - r * (r + 1) / 2;
 }

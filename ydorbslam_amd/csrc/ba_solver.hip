@@ -25,6 +25,7 @@
 #include "ba_skyline.hip.h"
 #include "host_buffers.h"
 #include "lm_schedule.h"
+#include "skyline_dev.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
@@ -56,7 +57,7 @@ size_t layState(int K, int NP, void* base, StatePtrs& st) {
 // `up`: what the host orders and uploads for a stage, through the pinned staging area at the same offsets and with ONE copy (twelve
 // before: with 16 set-up threads of a batch the runtime's lock was the cost).  Written whole by that copy; k_cull later rewrites eInfo / eRobust.
 // SKYLINE adds the pair table (PairList: rowStart, i1, i2 and each bucket's place in the envelope) and the plan's arrays.
-struct SkyPtrs { int *pairRow, *pairI1, *pairI2, *perm, *first, *colRows; long long *pairDst, *rowOff, *colStart, *colBlk; };
+struct SkyPtrs : sky::PlanArrays { int *pairRow, *pairI1, *pairI2; long long* pairDst; };
 struct UpPtrs { int *ePose, *ePidx, *ePt, *eLm, *ptStart, *poseStart, *ptOf, *poseEdges, *poseOf; double *eMeas, *eInfo; uint8_t* eRobust; SkyPtrs k; };
 size_t layUp(const Sys& Y, void* base, UpPtrs& u) {
   Carve a(base);
@@ -65,9 +66,9 @@ size_t layUp(const Sys& Y, void* base, UpPtrs& u) {
   a.take(u.ptStart, Y.nL + 1); a.take(u.poseStart, Y.nPf + 1); a.take(u.ptOf, Y.nL); a.take(u.poseEdges, Y.nPoseEdges); a.take(u.poseOf, Y.nPf);
   u.k = SkyPtrs{};
   if (Y.sky) {
-    const size_t nB = Y.nBuckets, nF = Y.nPf, nCol = Y.plan.colRows.size();
-    a.take(u.k.pairRow, nF + 1); a.take(u.k.pairI1, nB); a.take(u.k.pairI2, nB); a.take(u.k.pairDst, nB); a.take(u.k.perm, nF); a.take(u.k.first, nF);
-    a.take(u.k.rowOff, nF + 1); a.take(u.k.colStart, nF + 1); a.take(u.k.colRows, nCol); a.take(u.k.colBlk, nCol);
+    const size_t nB = Y.nBuckets, nF = Y.nPf;
+    a.take(u.k.pairRow, nF + 1); a.take(u.k.pairI1, nB); a.take(u.k.pairI2, nB); a.take(u.k.pairDst, nB);
+    u.k.take(a, Y.plan, false);
   }
   return a.L.bytes;
 }
@@ -399,9 +400,8 @@ int prepareStage(Run& R_, bool reuse) {
       upv(u.eRobust, hRobust); upv(u.ptStart, hPtStart); upv(u.poseStart, hPoseStart); upv(u.ptOf, ptOf);
       upv(u.poseEdges, hPoseEdges); upv(u.poseOf, poseOf);
       if (Z.sky) {
-        const sky::Plan& K = Z.plan;
-        upv(u.k.pairRow, pairs.rowStart); upv(u.k.pairI1, pairs.i1); upv(u.k.pairI2, pairs.i2); upv(u.k.pairDst, pairDst); upv(u.k.perm, K.perm);
-        upv(u.k.first, K.first); upv(u.k.rowOff, K.rowOff); upv(u.k.colStart, K.colStart); upv(u.k.colRows, K.colRows); upv(u.k.colBlk, K.colBlk);
+        upv(u.k.pairRow, pairs.rowStart); upv(u.k.pairI1, pairs.i1); upv(u.k.pairI2, pairs.i2); upv(u.k.pairDst, pairDst);
+        u.k.fill(Z.plan, up);
       }
       HIPCHK(hipMemcpyAsync(c.up.p, c.hStage.p, upBytes, hipMemcpyHostToDevice, s));
       // the original information: the chi2 tests between and after the stages use it (k_cull)
@@ -1210,19 +1210,11 @@ int ydorb_ba_reduced_system_with(const YdBaProblem* P, const YdBaOptions* optIn,
   *solved = hst[0] == 0;
   for (int i = 0; i < n6; i++) x_out[i] = hx[i];
   // the lower triangle of either storage, mirrored
-  auto put = [&](int r, int cc, double v) { S_out[(size_t)r * n6 + cc] = v; S_out[(size_t)cc * n6 + r] = v; };
-  memset(S_out, 0, sizeof(double) * n6 * n6);
   if (!Y.sky) {
     for (int r = 0; r < n6; r++)
-      for (int cc = 0; cc <= r; cc++) put(r, cc, hS[(size_t)r * Y.n + cc]);
+      for (int cc = 0; cc <= r; cc++) S_out[(size_t)r * n6 + cc] = S_out[(size_t)cc * n6 + r] = hS[(size_t)r * Y.n + cc];
   } else {
-    const sky::Plan& K = Y.plan;
-    for (int i = 0; i < F; i++)
-      for (int j = K.first[i]; j <= i; j++) {
-        const double* B = &hS[36 * (size_t)(K.rowOff[i] + j - K.first[i])];
-        for (int r = 0; r < 6; r++)
-          for (int cc = 0; cc < (j == i ? r + 1 : 6); cc++) put(6 * K.perm[i] + r, 6 * K.perm[j] + cc, B[6 * r + cc]);
-      }
+    sky::expandEnvelope<6>(Y.plan, hS.data(), S_out, sky::kDiagLower);
   }
   return YDORB_OK;
 }
@@ -1250,36 +1242,31 @@ int ydorb_ba_skyline_solve(int32_t device, const double* A, int32_t n, const dou
   std::string err;
   if (!bapairs::planEnvelope(pairs, ordering, 0, true, K, err)) { set_error("%s", err.c_str()); return YDORB_ERR_UNSUPPORTED; }
   std::vector<double> env(36 * (size_t)K.envBlocks, 0.0);
-  for (int i = 0; i < F; i++)
-    for (int j = K.first[i]; j <= i; j++) {
-      double* B = &env[36 * (size_t)(K.rowOff[i] + j - K.first[i])];
-      for (int r = 0; r < 6; r++)
-        for (int cc = 0; cc < 6; cc++) B[6 * r + cc] = A[(size_t)(6 * K.perm[i] + r) * n + 6 * K.perm[j] + cc];
-    }
-  Layout L;
-  const size_t nCol = K.colRows.size();
-  const size_t oA = L.add(sizeof(double) * env.size()), ob = L.add(sizeof(double) * n), ow = L.add(sizeof(double) * 2 * n), ox = L.add(sizeof(double) * n),
-               ost = L.add(sizeof(int) * 2), oFirst = L.add(sizeof(int) * F), oPerm = L.add(sizeof(int) * F), oRow = L.add(sizeof(long long) * (F + 1)),
-               oCs = L.add(sizeof(long long) * (F + 1)), oCr = L.add(sizeof(int) * nCol), oCb = L.add(sizeof(long long) * nCol);
+  sky::packEnvelope<6>(K, A, env.data());
+  struct { double *A, *b, *w, *x; int* status; sky::PlanArrays k; } d;
+  auto lay = [&](void* base) {
+    Carve a(base);
+    a.take(d.A, env.size()); a.take(d.b, n); a.take(d.w, 2 * (size_t)n); a.take(d.x, n); a.take(d.status, 2);
+    d.k.take(a, K, false);
+    return a.L.bytes;
+  };
   ScopedMem m;   // exact size; freed on every return
-  if ((rc = m.alloc(L.bytes))) return rc;
-  HIPCHK(hipMemcpy(m.at<double>(oA), env.data(), sizeof(double) * env.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(m.at<double>(ob), b, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(m.at<int>(ost), 0, sizeof(int) * 2));
-  HIPCHK(hipMemcpy(m.at<int>(oFirst), K.first.data(), sizeof(int) * F, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(m.at<int>(oPerm), K.perm.data(), sizeof(int) * F, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(m.at<long long>(oRow), K.rowOff.data(), sizeof(long long) * (F + 1), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(m.at<long long>(oCs), K.colStart.data(), sizeof(long long) * (F + 1), hipMemcpyHostToDevice));
-  if (nCol) {
-    HIPCHK(hipMemcpy(m.at<int>(oCr), K.colRows.data(), sizeof(int) * nCol, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m.at<long long>(oCb), K.colBlk.data(), sizeof(long long) * nCol, hipMemcpyHostToDevice));
-  }
-  hipLaunchKernelGGL(k_sky_solve, dim3(1), dim3(kSkyThreads), 0, nullptr, F, m.at<int>(oFirst), m.at<long long>(oRow), m.at<long long>(oCs), m.at<int>(oCr),
-                     m.at<long long>(oCb), m.at<int>(oPerm), m.at<double>(ob), m.at<double>(oA), m.at<double>(ow), m.at<double>(ox), m.at<int>(ost));
+  if ((rc = m.alloc(lay(nullptr)))) return rc;
+  lay(m.p);
+  hipError_t upErr = hipSuccess;
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    if (bytes && upErr == hipSuccess) upErr = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+  };
+  up(d.A, env.data(), sizeof(double) * env.size()); up(d.b, b, sizeof(double) * n);
+  d.k.fill(K, up);
+  HIPCHK(upErr);
+  HIPCHK(hipMemset(d.status, 0, sizeof(int) * 2));
+  hipLaunchKernelGGL(k_sky_solve, dim3(1), dim3(kSkyThreads), 0, nullptr, F, d.k.first, d.k.rowOff, d.k.colStart, d.k.colRows, d.k.colBlk, d.k.perm, d.b, d.A, d.w,
+                     d.x, d.status);
   HIPCHK(hipGetLastError());
   int hst[2];
-  HIPCHK(hipMemcpy(x, m.at<double>(ox), sizeof(double) * n, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hst, m.at<int>(ost), sizeof(hst), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(x, d.x, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hst, d.status, sizeof(hst), hipMemcpyDeviceToHost));
   *ok = hst[0] == 0;
   return YDORB_OK;
 }

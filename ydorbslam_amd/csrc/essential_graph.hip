@@ -19,7 +19,7 @@
 #include "essential_skyline.hip.h"
 #include "host_buffers.h"
 #include "lm_schedule.h"
-#include "skyline_plan.h"
+#include "skyline_dev.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
@@ -147,19 +147,15 @@ int chooseSolver(const YdEssentialGraph* g, const YdEssentialSolverOptions* opt,
 }
 
 // The plan's arrays on the device (SKYLINE only; null otherwise)
-struct SkyPtrs { int *inv, *perm, *first, *colRows; long long *rowOff, *colStart, *colBlk; };
+using SkyPtrs = sky::PlanArrays;
 struct UpPtrs { double *est0, *meas; int *v0, *v1, *freeOf, *vertOf, *incStart, *incE, *incN, *incO, *pref; float* pts; SkyPtrs k; };
 size_t layUp(const Graph& G, void* base, UpPtrs& u) {
   Carve a(base);
   const size_t nInc = std::max<size_t>(G.incE.size(), 1), E = std::max(G.nE, 1), P = std::max(G.nP, 1);
   a.take(u.est0, 8 * (size_t)G.nV); a.take(u.meas, 8 * E); a.take(u.v0, E); a.take(u.v1, E); a.take(u.freeOf, G.nV); a.take(u.vertOf, G.nF);
   a.take(u.incStart, G.nF + 1); a.take(u.incE, nInc); a.take(u.incN, nInc); a.take(u.incO, nInc); a.take(u.pts, 3 * P); a.take(u.pref, P);
-  if (G.sky) {
-    a.take(u.k.inv, G.nF); a.take(u.k.perm, G.nF); a.take(u.k.first, G.nF); a.take(u.k.rowOff, G.nF + 1); a.take(u.k.colStart, G.nF + 1);
-    a.take(u.k.colRows, std::max<size_t>(G.P.colRows.size(), 1)); a.take(u.k.colBlk, std::max<size_t>(G.P.colBlk.size(), 1));
-  } else {
-    u.k = SkyPtrs{};
-  }
+  u.k = SkyPtrs{};
+  if (G.sky) u.k.take(a, G.P, true, 1);
   return a.L.bytes;
 }
 // The work area.  It keeps what earlier, differently sized calls left, so every array has a first writer inside the call:
@@ -216,14 +212,7 @@ int begin(Run& R_) {
   std::memcpy(h.incStart, G.incStart.data(), 4 * (size_t)(G.nF + 1));
   if (nInc) { std::memcpy(h.incE, G.incE.data(), 4 * nInc); std::memcpy(h.incN, G.incN.data(), 4 * nInc); std::memcpy(h.incO, G.incO.data(), 4 * nInc); }
   if (P) { std::memcpy(h.pts, g->points, 12 * P); std::memcpy(h.pref, g->point_ref, 4 * P); }
-  if (G.sky) {
-    const sky::Plan& K = G.P;
-    std::memcpy(h.k.inv, K.inv.data(), 4 * (size_t)G.nF); std::memcpy(h.k.perm, K.perm.data(), 4 * (size_t)G.nF);
-    std::memcpy(h.k.first, K.first.data(), 4 * (size_t)G.nF);
-    static_assert(sizeof(long long) == sizeof(int64_t), "the plan's offsets go to the device as they are");
-    std::memcpy(h.k.rowOff, K.rowOff.data(), 8 * (size_t)(G.nF + 1)); std::memcpy(h.k.colStart, K.colStart.data(), 8 * (size_t)(G.nF + 1));
-    if (!K.colRows.empty()) { std::memcpy(h.k.colRows, K.colRows.data(), 4 * K.colRows.size()); std::memcpy(h.k.colBlk, K.colBlk.data(), 8 * K.colBlk.size()); }
-  }
+  if (G.sky) h.k.fill(G.P, [](void* dst, const void* src, size_t bytes) { if (bytes) std::memcpy(dst, src, bytes); });
   hipStream_t s = c.stream;
   HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, ub, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(R_.w.est[0], R_.u.est0, 64 * (size_t)G.nV, hipMemcpyDeviceToDevice, s));
@@ -452,18 +441,7 @@ int copySystem(Run& R_, double* H_out, double* b_out) {
     for (size_t r = 0; r < N; r++) std::memcpy(H_out + r * N, S.data() + r * G.n, 8 * N);
     return YDORB_OK;
   }
-  std::fill(H_out, H_out + N * N, 0.0);
-  const sky::Plan& K = G.P;
-  for (int i = 0; i < G.nF; i++)
-    for (int j = K.first[i]; j <= i; j++) {
-      const double* B = S.data() + 49 * (size_t)(K.rowOff[i] + (j - K.first[i]));
-      const size_t a = 7 * (size_t)K.perm[i], o = 7 * (size_t)K.perm[j];
-      for (int r = 0; r < 7; r++)
-        for (int c = 0; c < 7; c++) {
-          H_out[(a + r) * N + o + c] = B[7 * r + c];
-          if (i != j) H_out[(o + c) * N + a + r] = B[7 * r + c];
-        }
-    }
+  sky::expandEnvelope<7>(G.P, S.data(), H_out, sky::kDiagWhole);
   return YDORB_OK;
 }
 

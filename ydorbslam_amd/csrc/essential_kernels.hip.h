@@ -12,6 +12,7 @@
 //                  temporaries of an evaluation; here a lane holds one 7-vector (DESIGN.md section 6i has the resource figures).
 // k_ess_assemble   one wave per free vertex: clears the vertex's 7 rows of the dense S, then sums the stored blocks of its incident
 //                  edges in edge order (diagonal) and per neighbour in edge order (off-diagonal), adds lambda, writes b.  No atomics.
+//                  The sums are ess_vertex_sums, which the skyline's k_ess_assemble_sky runs over the envelope.
 // k_ess_update     one lane per free vertex: trial estimate oplus(estimate, x) and the vertex's term of computeScale.
 // k_ess_chi2       one lane per edge: chi2 of the trial estimate.
 // k_ess_sum        one workgroup: the chi2 and scale sums in a fixed order, plus the factorisation's status, for the one read-back.
@@ -104,10 +105,61 @@ __global__ __launch_bounds__(64) void k_ess_linearize(int E, const R* __restrict
   }
 }
 
+// The three sums of free vertex a, one wave: lanes 0 .. 48 sum entry (r, c) of the diagonal block over the incident edges in edge order
+// (plus lambda) and of one block per free neighbour in edge order, lanes 49 .. 55 an entry of b.  incStart / incE: per free vertex its
+// incident edges as (edge << 1 | side) in edge order; incN / incO: the same entries ordered by the neighbour's free index (fixed
+// neighbours, -1, first), edge order kept inside a neighbour.  Where the sums go is the destination's business: dst.diag(r, c, v),
+// dst.nbr(o, r, c, v) for neighbour o's block (a destination may skip it), dst.b(r, v).  k_ess_assemble and k_ess_assemble_sky
+// (essential_skyline.hip.h) are this body over their own storage.
+template <class Dst> __device__ __forceinline__ void ess_vertex_sums(int a, int lane, R lambda, const int* __restrict__ incStart,
+                                                                     const int* __restrict__ incE, const int* __restrict__ incN,
+                                                                     const int* __restrict__ incO, const R* __restrict__ Hb,
+                                                                     const R* __restrict__ bb, const Dst& dst) {
+  const int q0 = incStart[a], q1 = incStart[a + 1];
+  if (lane < 49) {
+    const int r = lane / 7, c = lane - 7 * r;
+    R s = 0;
+    for (int q = q0; q < q1; q++) {
+      const int ent = incE[q];
+      s += Hb[kH * (size_t)(ent >> 1) + ((ent & 1) ? 98 : 0) + lane];
+    }
+    if (r == c) s += lambda;
+    dst.diag(r, c, s);
+    int cur = -1;
+    R acc = 0;
+    for (int q = q0; q < q1; q++) {
+      const int o = incO[q];
+      if (o < 0) continue;
+      if (o != cur) {
+        if (cur >= 0) dst.nbr(cur, r, c, acc);
+        cur = o; acc = 0;
+      }
+      const int ent = incN[q];
+      acc += Hb[kH * (size_t)(ent >> 1) + 49 + ((ent & 1) ? 7 * c + r : lane)];   // side 1: the block of (j, i) is the transpose
+    }
+    if (cur >= 0) dst.nbr(cur, r, c, acc);
+  } else if (lane < 56) {
+    const int r = lane - 49;
+    R s = 0;
+    for (int q = q0; q < q1; q++) {
+      const int ent = incE[q];
+      s += bb[kB * (size_t)(ent >> 1) + 7 * (ent & 1) + r];
+    }
+    dst.b(r, s);
+  }
+}
+
+// Vertex a's 7 rows of the dense S, every neighbour's block, and b by free vertex (twice)
+struct EssDenseDst {
+  R* rows; int n, a; R *bkeep, *bwork;
+  __device__ void diag(int r, int c, R v) const { rows[(size_t)r * n + 7 * a + c] = v; }
+  __device__ void nbr(int o, int r, int c, R v) const { rows[(size_t)r * n + 7 * o + c] = v; }
+  __device__ void b(int r, R v) const { bkeep[7 * a + r] = v; bwork[7 * a + r] = v; }
+};
+
 // H + lambda I into the dense S ([n][n] row-major, n = 7 nF padded to the factorisation's tile with a unit diagonal) and b (twice: the
-// factorisation's forward substitution consumes bwork).  incStart / incE: per free vertex its incident edges as (edge << 1 | side) in
-// edge order; incN / incO: the same entries ordered by the neighbour's free index (fixed neighbours, -1, first), edge order kept inside
-// a neighbour.  The whole of S is written on every call: the factorisation overwrites it, and the arena keeps earlier calls' contents.
+// factorisation's forward substitution consumes bwork).  The whole of S is written on every call: the factorisation overwrites it, and
+// the arena keeps earlier calls' contents.
 __global__ __launch_bounds__(64) void k_ess_assemble(int nF, int n, R lambda, const int* __restrict__ incStart, const int* __restrict__ incE,
                                                      const int* __restrict__ incN, const int* __restrict__ incO, const R* __restrict__ Hb,
                                                      const R* __restrict__ bb, R* __restrict__ S, R* __restrict__ bkeep, R* __restrict__ bwork,
@@ -124,38 +176,7 @@ __global__ __launch_bounds__(64) void k_ess_assemble(int nF, int n, R lambda, co
   R* rows = S + (size_t)7 * a * n;
   for (size_t i = lane; i < (size_t)7 * n; i += 64) rows[i] = 0;
   __syncthreads();   // the cleared rows are in memory before the blocks go over them
-  const int q0 = incStart[a], q1 = incStart[a + 1];
-  if (lane < 49) {
-    const int r = lane / 7, c = lane - 7 * r;
-    R s = 0;
-    for (int q = q0; q < q1; q++) {
-      const int ent = incE[q];
-      s += Hb[kH * (size_t)(ent >> 1) + ((ent & 1) ? 98 : 0) + lane];
-    }
-    if (r == c) s += lambda;
-    rows[(size_t)r * n + 7 * a + c] = s;
-    int cur = -1;
-    R acc = 0;
-    for (int q = q0; q < q1; q++) {
-      const int o = incO[q];
-      if (o < 0) continue;
-      if (o != cur) {
-        if (cur >= 0) rows[(size_t)r * n + 7 * cur + c] = acc;
-        cur = o; acc = 0;
-      }
-      const int ent = incN[q];
-      acc += Hb[kH * (size_t)(ent >> 1) + 49 + ((ent & 1) ? 7 * c + r : lane)];   // side 1: the block of (j, i) is the transpose
-    }
-    if (cur >= 0) rows[(size_t)r * n + 7 * cur + c] = acc;
-  } else if (lane < 56) {
-    const int r = lane - 49;
-    R s = 0;
-    for (int q = q0; q < q1; q++) {
-      const int ent = incE[q];
-      s += bb[kB * (size_t)(ent >> 1) + 7 * (ent & 1) + r];
-    }
-    bkeep[7 * a + r] = s; bwork[7 * a + r] = s;
-  }
+  ess_vertex_sums(a, lane, lambda, incStart, incE, incN, incO, Hb, bb, EssDenseDst{rows, n, a, bkeep, bwork});
 }
 
 // push + update(x): next[v] = oplus(cur[v], x_v) for every free vertex; sv[f] = sum_k x[k] (lambda x[k] + b[k]), its part of computeScale

@@ -4,10 +4,14 @@
 // Storage: row i (a position of the plan's order) holds the blocks of columns first[i] .. i, each [r][c] row-major, block (i, j) at
 // 49 * (rowOff[i] + j - first[i]).  Of a diagonal block the lower triangle is read.  b is held by position, x goes out by free vertex.
 //
-// k_ess_assemble_sky  k_ess_assemble's sums, the destination changed: one wave per free vertex clears its row of the envelope, sums
-//                     the diagonal block in edge order and one block per neighbour in edge order, and writes a neighbour's block only
-//                     when the neighbour comes earlier in the order (the other endpoint's wave writes it otherwise, from its own side
-//                     of the same edges: the transposed block).  No atomics.
+// Shared with the dense path (essential_kernels.hip.h): ess_vertex_sums, the sums of one free vertex.  Shared with the BA's skyline
+// solver (sky_blocks.hip.h): the Cholesky of a diagonal block, the row substitutions against it and the packed-triangle index.  The
+// walk over the block columns is this kernel's own.
+//
+// k_ess_assemble_sky  one wave per free vertex clears its row of the envelope and runs ess_vertex_sums over it: the diagonal block in
+//                     edge order and one block per neighbour in edge order, a neighbour's block written only when the neighbour comes
+//                     earlier in the order (the other endpoint's wave writes it otherwise, from its own side of the same edges: the
+//                     transposed block).  No atomics.
 // k_ess_sky_solve     one workgroup walks the block columns: every thread factorises the 7x7 diagonal block in registers (the same
 //                     arithmetic 256 times costs no more time than once and saves a barrier), the rows of the column's panel and b,
 //                     as one more row, are solved against it, barrier, the blocks of every pair of rows in the column's list take
@@ -18,11 +22,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "essential_kernels.hip.h"
+#include "sky_blocks.hip.h"
 
 #pragma clang fp contract(off)
 
 namespace ydorb {
 namespace ess {
+
+// Row pos of the envelope: the diagonal block, which ends the row, a neighbour's block only when the neighbour comes earlier in the
+// order (the other endpoint's wave writes it otherwise, from its own side of the same edges: the transposed block); b by free vertex
+// and by position
+struct EssEnvelopeDst {
+  R* row; size_t off; const int* inv; int pos, f0, a; R *bkeep, *bwork;   // off: the blocks before the diagonal one
+  __device__ void diag(int r, int c, R v) const { row[off + 7 * r + c] = v; }
+  __device__ void nbr(int o, int r, int c, R v) const { if (inv[o] < pos) row[49 * (size_t)(inv[o] - f0) + 7 * r + c] = v; }
+  __device__ void b(int r, R v) const { bkeep[7 * (size_t)a + r] = v; bwork[7 * (size_t)pos + r] = v; }
+};
 
 __global__ __launch_bounds__(64) void k_ess_assemble_sky(int nF, R lambda, const int* __restrict__ incStart, const int* __restrict__ incE,
                                                          const int* __restrict__ incN, const int* __restrict__ incO, const R* __restrict__ Hb,
@@ -39,74 +54,7 @@ __global__ __launch_bounds__(64) void k_ess_assemble_sky(int nF, R lambda, const
   const size_t off = 49 * (size_t)(pos - f0);   // the blocks before the diagonal one, which is written whole below
   for (size_t i = lane; i < off; i += 64) row[i] = 0;
   __syncthreads();   // the cleared row is in memory before the blocks go over it
-  const int q0 = incStart[a], q1 = incStart[a + 1];
-  if (lane < 49) {
-    const int r = lane / 7, c = lane - 7 * r;
-    R s = 0;
-    for (int q = q0; q < q1; q++) {
-      const int ent = incE[q];
-      s += Hb[kH * (size_t)(ent >> 1) + ((ent & 1) ? 98 : 0) + lane];
-    }
-    if (r == c) s += lambda;
-    row[off + lane] = s;
-    int cur = -1;
-    R acc = 0;
-    for (int q = q0; q < q1; q++) {
-      const int o = incO[q];
-      if (o < 0) continue;
-      if (o != cur) {
-        if (cur >= 0 && inv[cur] < pos) row[49 * (size_t)(inv[cur] - f0) + lane] = acc;
-        cur = o; acc = 0;
-      }
-      const int ent = incN[q];
-      acc += Hb[kH * (size_t)(ent >> 1) + 49 + ((ent & 1) ? 7 * c + r : lane)];
-    }
-    if (cur >= 0 && inv[cur] < pos) row[49 * (size_t)(inv[cur] - f0) + lane] = acc;
-  } else if (lane < 56) {
-    const int r = lane - 49;
-    R s = 0;
-    for (int q = q0; q < q1; q++) {
-      const int ent = incE[q];
-      s += bb[kB * (size_t)(ent >> 1) + 7 * (ent & 1) + r];
-    }
-    bkeep[7 * (size_t)a + r] = s; bwork[7 * (size_t)pos + r] = s;
-  }
-}
-
-__device__ __forceinline__ constexpr int tri(int r, int c) { return r * (r + 1) / 2 + c; }
-
-// L L^T of the lower triangle of D ([7][7]) into l (packed rows) and the reciprocals of its diagonal into inv; false when a pivot was
-// not positive (it is then taken as 1).  Every division by a pivot in the column, here, in the panel and in the back substitution, is
-// a product with inv: one division per pivot instead of seven and more on the column's chain of dependent fp64 operations.
-__device__ __forceinline__ bool factor7(const R* D, R* l, R* inv) {
-  bool ok = true;
-#pragma unroll
-  for (int r = 0; r < 7; r++)
-#pragma unroll
-    for (int c = 0; c <= r; c++) {
-      R s = D[7 * r + c];
-#pragma unroll
-      for (int q = 0; q < c; q++) s -= l[tri(r, q)] * l[tri(c, q)];
-      if (c == r) {
-        if (!(s > 0)) { ok = false; s = 1.0; }
-        l[tri(r, r)] = sqrt(s);
-        inv[r] = 1.0 / l[tri(r, r)];
-      } else {
-        l[tri(r, c)] = s * inv[c];
-      }
-    }
-  return ok;
-}
-
-// One row of a panel (or b_j) against the factor of the diagonal block: v L^T = row, in place
-__device__ __forceinline__ void solveRow7(R* v, const R* l, const R* inv) {
-#pragma unroll
-  for (int c = 0; c < 7; c++) {
-    R s = v[c];
-#pragma unroll
-    for (int q = 0; q < c; q++) s -= v[q] * l[tri(c, q)];
-    v[c] = s * inv[c];
-  }
+  ess_vertex_sums(a, lane, lambda, incStart, incE, incN, incO, Hb, bb, EssEnvelopeDst{row, off, inv, pos, f0, a, bkeep, bwork});
 }
 
 // One entry of the rank-7 update of column j: *dst -= a[0..6] . b[0..6].  Item w of the column addresses, from the plan alone,
@@ -119,9 +67,7 @@ __device__ __forceinline__ UpdateItem updateItem(long long w, long long pairs, i
   if (w < 49 * pairs) {
     const long long p = w / 49;
     const int e = (int)(w - 49 * p), r = e / 7, c = e - 7 * r;
-    int ia = (int)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);   // the two loops make the rounded root exact
-    while ((long long)ia * (ia + 1) / 2 > p) ia--;
-    while ((long long)(ia + 1) * (ia + 2) / 2 <= p) ia++;
+    const int ia = sky::triRow(p);
     const int ik = (int)(p - (long long)ia * (ia + 1) / 2);
     const long long bi = colBlk[cs + ia], bk = colBlk[cs + ik];
     u.a = A + 49 * (size_t)bi + 7 * r;
@@ -165,9 +111,9 @@ __global__ __launch_bounds__(256) void k_ess_sky_solve(int nF, const int* __rest
 #pragma unroll
       for (int c = 0; c < 7; c++) v[c] = row[c];
     }
-    if (!factor7(D, l, inv)) bad = true;
+    if (!sky::factorBlock<7>(D, l, inv)) bad = true;
     if (tid < nPanel) {
-      solveRow7(v, l, inv);
+      sky::solveRow<7>(v, l, inv);
 #pragma unroll
       for (int c = 0; c < 7; c++) row[c] = v[c];
     }
@@ -175,7 +121,7 @@ __global__ __launch_bounds__(256) void k_ess_sky_solve(int nF, const int* __rest
       row = panelRow(t);
 #pragma unroll
       for (int c = 0; c < 7; c++) v[c] = row[c];
-      solveRow7(v, l, inv);
+      sky::solveRow<7>(v, l, inv);
 #pragma unroll
       for (int c = 0; c < 7; c++) row[c] = v[c];
     }
@@ -184,14 +130,7 @@ __global__ __launch_bounds__(256) void k_ess_sky_solve(int nF, const int* __rest
     UpdateItem u0{nullptr, nullptr, nullptr};
     if (tid < items) u0 = updateItem(tid, pairs, j, cs, colRows, colBlk, A, bw);
     __syncthreads();   // the panel and y_j are written, and every thread has read D
-    if (tid == 0) {
-#pragma unroll
-      for (int r = 0; r < 7; r++)
-#pragma unroll
-        for (int c = 0; c <= r; c++) D[7 * r + c] = l[tri(r, c)];
-#pragma unroll
-      for (int c = 0; c < 7; c++) dinv[7 * (size_t)j + c] = inv[c];
-    }
+    if (tid == 0) sky::storeFactor<7>(D, dinv, j, l, inv);
     if (tid < items) applyUpdate(u0);
     for (long long w = tid + 256; w < items; w += 256) applyUpdate(updateItem(w, pairs, j, cs, colRows, colBlk, A, bw));
     __syncthreads();   // column j + 1 and b_{j+1} are final
@@ -210,13 +149,7 @@ __global__ __launch_bounds__(256) void k_ess_sky_solve(int nF, const int* __rest
       s0 = bw[7 * (size_t)f0 + tid];
     }
     R xv[7];
-#pragma unroll
-    for (int c = 6; c >= 0; c--) {
-      R s = bw[7 * (size_t)i + c];
-#pragma unroll
-      for (int q = c + 1; q < 7; q++) s -= D[7 * q + c] * xv[q];
-      xv[c] = s * dinv[7 * (size_t)i + c];
-    }
+    sky::solveDiagBack<7>(D, dinv, bw, i, xv);
     if (tid == 0) {
 #pragma unroll
       for (int c = 0; c < 7; c++) x[7 * (size_t)perm[i] + c] = xv[c];

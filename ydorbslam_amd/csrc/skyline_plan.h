@@ -158,5 +158,35 @@ inline void buildColumns(Plan& P) {
     }
 }
 
+// An envelope of B x B blocks ([r][c] row-major, block (i, j) of positions j <= i at B B (rowOff[i] + j - first[i])) against the dense
+// symmetric M ([N][N], N = B nF) in the caller's numbering.  expandEnvelope clears M and writes every stored block with its mirror
+// image; of a diagonal block it copies either what is stored or the lower triangle, mirrored.  packEnvelope reads the blocks back out
+// of M, whole.
+enum DiagBlock { kDiagWhole, kDiagLower };
+template <int B> void expandEnvelope(const Plan& P, const double* env, double* M, DiagBlock diag) {
+  const size_t N = (size_t)B * P.nF;
+  std::fill(M, M + N * N, 0.0);
+  for (int i = 0; i < P.nF; i++)
+    for (int j = P.first[i]; j <= i; j++) {
+      const double* blk = env + B * B * (size_t)(P.rowOff[i] + (j - P.first[i]));
+      const size_t a = (size_t)B * P.perm[i], o = (size_t)B * P.perm[j];
+      for (int r = 0; r < B; r++)
+        for (int c = 0; c < B; c++) {
+          if (i == j && c > r && diag == kDiagLower) continue;
+          M[(a + r) * N + o + c] = blk[B * r + c];
+          if (i != j || diag == kDiagLower) M[(o + c) * N + a + r] = blk[B * r + c];
+        }
+    }
+}
+template <int B> void packEnvelope(const Plan& P, const double* M, double* env) {
+  const size_t N = (size_t)B * P.nF;
+  for (int i = 0; i < P.nF; i++)
+    for (int j = P.first[i]; j <= i; j++) {
+      double* blk = env + B * B * (size_t)(P.rowOff[i] + (j - P.first[i]));
+      for (int r = 0; r < B; r++)
+        for (int c = 0; c < B; c++) blk[B * r + c] = M[((size_t)B * P.perm[i] + r) * N + (size_t)B * P.perm[j] + c];
+    }
+}
+
 }  // namespace sky
 }  // namespace ydorb
