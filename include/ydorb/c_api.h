@@ -1231,6 +1231,64 @@ int ydorb_mapdb_export_views(ydorb_mapdb_t* db, int32_t* view_start, int32_t* vi
 int ydorb_mapdb_export_descriptors(ydorb_mapdb_t* db, int32_t* desc_start, uint8_t* desc);
 int ydorb_mapdb_desc_stats(ydorb_mapdb_t* db, YdMapDbDescStats* stats);
 
+/* Resident point attributes (DESIGN.md section 2 "Local map on the resident table", section 6q): what Tracking::searchLocalPoints
+ * reads of a map point besides its position, kept where the resident queries compute it.  Per point slot: normal [3], the raw
+ * minDistance / maxDistance of updateNormalAndDepth (not the 0.8 / 1.2 multiples), desc [32] and a flag byte (bit 0: the geometry
+ * group normal + distances is set, bit 1: the descriptor is set).  The relation is opt-in: a handle that never calls
+ * ydorb_mapdb_enable_attributes allocates nothing for it, launches nothing for it and every entry below but enable and attr_stats
+ * returns YDORB_ERR_INVALID_ARG.  YdMapDbStats, YdMapDbRowStats and YdMapDbDescStats keep their meaning either way.
+ * The arrays lie in an arena of their own that covers the point table's capacity and grows with it (device-to-device copy, new slots
+ * zero).  set_point_attributes validates and stages and does no device work; the next query or export applies the delta after points,
+ * rows, views and blocks.  A slot named several times between two syncs yields one record, each group with its last value.
+ * ydorb_mapdb_set_points of a point with bad = 1 and an empty span (an erased point) stages a clear of that slot: flags 0 and all-zero
+ * values, what a slot never set reads as; attributes staged for the slot before the erase are dropped, those staged after it stay.
+ * ydorb_mapdb_clear zeroes the arrays and keeps capacity and counters.
+ * Write-through: with attributes enabled, ydorb_mapdb_update_normal_depth leaves normal and distances of every entry it computed
+ * (status 0) in the arrays and sets bit 0; ydorb_mapdb_correct does the same for the entries that end YDORB_MAPCORR_DONE in a call
+ * that asked for normals (DONE_NO_OBSERVATIONS, CLAIMED, BAD, NOT_COVERED and a call without a normals pass write nothing);
+ * ydorb_mapdb_distinctive_descriptors leaves the winning row of every YDORB_MAPDESC_UPDATED entry and sets bit 1.  The copy runs on the
+ * device behind the query, from its result buffer; attributes staged before the query are applied by the query's sync and so lose
+ * to it.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG naming the first offender, before any device work, and stages nothing. */
+typedef struct YdMapDbAttrStats {
+  int32_t enabled, growths;                 /* growths: of the attribute arena, with the point table */
+  int64_t capacity;                         /* point slots the arena covers as of the last sync; 0 when not enabled */
+  int64_t last_attr_sync_bytes, last_attr_sync_records;   /* 0 when nothing of this relation was staged */
+  int64_t last_write_through_records;       /* entries the last of the three write-through queries left in the arrays */
+} YdMapDbAttrStats;
+/* Turns the relation on; calling it twice is fine. */
+int ydorb_mapdb_enable_attributes(ydorb_mapdb_t* db);
+/* Stages attributes of the n named slots: normal [n][3], min_distance [n], max_distance [n] (all three or none) and desc [n][32] may
+ * each be NULL; a NULL group leaves that group and its flag alone.  Refused: null slots with n > 0, both groups NULL, a partial
+ * geometry group, a slot outside 0..n_points-1 (staged points count). */
+int ydorb_mapdb_set_point_attributes(ydorb_mapdb_t* db, const int32_t* slots, int32_t n, const float* normal, const float* min_distance,
+                                     const float* max_distance, const uint8_t* desc);
+/* Applies what is staged, then reads back: normal [n_points][3], min_distance / max_distance / flags [n_points], desc [n_points][32]. */
+int ydorb_mapdb_export_attributes(ydorb_mapdb_t* db, float* normal, float* min_distance, float* max_distance, uint8_t* desc,
+                                  uint8_t* flags);
+int ydorb_mapdb_attr_stats(ydorb_mapdb_t* db, YdMapDbAttrStats* stats);
+
+/* Tracking::searchLocalPoints on the resident table (DESIGN.md section 2 "Local map on the resident table"): the frustum test and the
+ * fused search read each listed point by slot and no map value travels up.  Row i of the table the flat entries would be given is
+ *   pos_min    = (resident position, 0.8f * minDistance)      one fp32 multiply: the bits getMinDistanceInvariance() returns
+ *   normal_max = (resident normal,   1.2f * maxDistance)      ... getMaxDistanceInvariance()
+ *   max_distance = the raw maxDistance, desc = the resident descriptor
+ * of point_slots[i]; has_observations = the resident observation span is not empty; the effective skip = the caller's skip byte OR
+ * the resident bad flag (a slot never set included). */
+#define YDORB_FRUSTUM_NO_ATTRIBUTES 7 /* listed, not skipped, and the geometry flag (fused search: or the descriptor flag) is not set:
+                                         treated as not in view, zero track row, query flags 0 */
+/* ydorb_frustum_cull over the resident values: views [n_views], list_start [n_views+1], point_slots / skip / rows / status
+ * [list_start[n_views]], n_in_view [n_views] or NULL.  Runs on the handle's own stream. */
+int ydorb_mapdb_frustum_cull(ydorb_mapdb_t* db, const YdFrustumView* views, int32_t n_views, const int32_t* list_start,
+                             const int32_t* point_slots, const uint8_t* skip, YdTrackView* rows, uint8_t* status, int32_t* n_in_view);
+/* ydorb_search_local_points with the table above; the query descriptors are copied on the device and never exist on the host.
+ * assigned[idx] = the list index i, not the slot.  A slot may repeat and then behaves as the flat entry does with equal rows.  Refused
+ * up front: null arguments, n < 0, a slot outside 0..n_points-1, n_levels outside 1..8, an invalid frame view, attributes not
+ * enabled, db and m on different devices.  n == 0 returns YDORB_OK with zero counts and launches nothing. */
+int ydorb_mapdb_search_local_points(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdFrameView* frame, const YdFrustumView* view,
+                                    const int32_t* point_slots, int32_t n, const uint8_t* skip, float th, float ratio, uint8_t* taken,
+                                    int32_t* assigned, YdTrackView* rows, uint8_t* status, int32_t* n_to_match, int32_t* n_matches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,13 @@
 // per keyframe, touch(mp) then also re-reads where the point is seen, forget() erases block and views, computeDistinctiveDescriptors
 // is MapPoint::computeDistinctiveDescriptors for a list of points with no descriptor upload, verifyDescriptors() is verify() for the two.
 // Off by default: without it no call of the descriptor entries is made.  Enable it before the first touch.
+// enableAttributes() adds the points' normal, raw distances and descriptor: touchAttributes(mp) after the host
+// set them (a constructor, replace()); updateNormalAndDepth, the three correction methods and computeDistinctiveDescriptors leave theirs
+// in the table themselves; a group whose member is still unset (an empty matrix) is not staged, and a slot the mirror reuses reads as
+// "no attributes" until the new point's are set; searchLocalPoints is the device part of Tracking::searchLocalPoints by slot (tracking.hpp's
+// searchLocalPointsImpl(Mirror&, ...)); verifyAttributes() is verify() for them.  Assumed spellings beyond the others: MapPoint
+// getNormal(), getDescriptor() and two one-line getters of the RAW members, getMinDistance() { lock; return m_flt_minDistance; } and
+// getMaxDistance() { lock; return m_flt_maxDistance; } (tracking.hpp requires the second already).
 // Assumed spellings: those of mapPoint.hpp; m_cvMat_descriptors (one CV_8U row of 32 bytes per keypoint) for the blocks, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
 // MapPoint::setPosInWorld(cv::Mat), m_int_correctedByKeyFrameID, m_int_correctedReference and the Sim3 members rotation().x() .. w(),
 // translation()[k], scale().  The camera centre after a corrected pose is not read from a member: correctLoopPoints computes it from
@@ -67,6 +74,7 @@ class MapMirror {
     pointSlot_.erase(it);
     pointOf_[s] = MapPointPtr();
     freePoints_.push_back(s);
+    if (attributes_) erasePending_[s] = 1;
     mark(pointDirty_, dirtyPoints_, s, kFull);   // the next flush erases it, or writes the point that took the slot since
   }
   // Resident descriptors.  The capacities (views, descriptors) size the two pools when given; both pools grow on demand anyway.
@@ -78,6 +86,18 @@ class MapMirror {
   // re-reads m_cvMat_descriptors at the next flush: once per keyframe, its descriptors never change; again after setBadFlag(), whose
   // isBad() empties the block (or forget(kf))
   void touchDescriptors(const KeyFramePtr& kf) { mark(descDirty_, dirtyDescs_, kfSlotFor(kf), kFull); }
+  // Resident point attributes: normal, raw distances and descriptor of every point stay in the table, and
+  // searchLocalPoints below reads them by slot.  Enable it before the first touch.
+  void enableAttributes() {
+    mapCheck(ydorb_mapdb_enable_attributes(db_));
+    attributes_ = true;
+  }
+  // re-reads getNormal(), getMinDistance(), getMaxDistance() and getDescriptor() at the next flush: after a constructor or replace() set
+  // them on the host.  What updateNormalAndDepth, the three correction methods and computeDistinctiveDescriptors of this class compute
+  // is in the table already (write-through) and needs no touch.
+  void touchAttributes(const MapPointPtr& mp) {
+    mark(attrDirty_, dirtyAttrs_, known(mp), kFull);
+  }
   void touchRow(const KeyFramePtr& kf) { markRow(kfSlotFor(kf)); }
   void touchEntry(const KeyFramePtr& kf, size_t idx) {
     const int32_t s = kfSlotFor(kf);
@@ -99,6 +119,7 @@ class MapMirror {
     kfSlot_.clear(); kfOf_.clear(); freeKfs_.clear(); kfDirty_.clear(); dirtyKfs_.clear();
     rowDirty_.clear(); rowSent_.clear(); dirtyRows_.clear(); dirtyEntries_.clear();
     descDirty_.clear(); descSent_.clear(); dirtyDescs_.clear();
+    attrDirty_.clear(); dirtyAttrs_.clear(); erasePending_.clear();
   }
 
   // At most one call of each set_* entry: the centres first (a point may name a keyframe that got its slot while the point was read).
@@ -137,20 +158,27 @@ class MapMirror {
         continue;
       }
       if (!pointOf_[s] && kfOf_.empty()) continue;   // no keyframe was ever named: nothing of this slot reached the table
-      const Record rec = pointOf_[s] ? read(pointOf_[s], true) : Record();
-      slots.push_back(s);
-      obsKf.insert(obsKf.end(), rec.kf.begin(), rec.kf.end()); obsLevel.insert(obsLevel.end(), rec.level.begin(), rec.level.end());
-      if (obsKf.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX observations in one flush");
-      start.push_back((int32_t)obsKf.size());
-      bad.push_back(rec.bad); refKf.push_back(rec.refKf); refLevel.push_back(rec.refLevel);
-      pos.insert(pos.end(), rec.pos, rec.pos + 3);
-      span_[s] = (int32_t)rec.kf.size();
-      if (descriptors_) {
-        viewKf.insert(viewKf.end(), rec.kf.begin(), rec.kf.end()); viewIdx.insert(viewIdx.end(), rec.idx.begin(), rec.idx.end());
-        viewStart.push_back((int32_t)viewKf.size());
-        for (const int32_t k : rec.kf)   // a keyframe met here for the first time: its block is read now
-          if (!descSent_[k]) mark(descDirty_, dirtyDescs_, k, kFull);
-      }
+      const auto send = [&](const Record& rec) {
+        slots.push_back(s);
+        obsKf.insert(obsKf.end(), rec.kf.begin(), rec.kf.end()); obsLevel.insert(obsLevel.end(), rec.level.begin(), rec.level.end());
+        if (obsKf.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX observations in one flush");
+        start.push_back((int32_t)obsKf.size());
+        bad.push_back(rec.bad); refKf.push_back(rec.refKf); refLevel.push_back(rec.refLevel);
+        pos.insert(pos.end(), rec.pos, rec.pos + 3);
+        span_[s] = (int32_t)rec.kf.size();
+        if (descriptors_) {
+          viewKf.insert(viewKf.end(), rec.kf.begin(), rec.kf.end()); viewIdx.insert(viewIdx.end(), rec.idx.begin(), rec.idx.end());
+          viewStart.push_back((int32_t)viewKf.size());
+          for (const int32_t k : rec.kf)   // a keyframe met here for the first time: its block is read now
+            if (!descSent_[k]) mark(descDirty_, dirtyDescs_, k, kFull);
+        }
+      };
+      // A slot forgotten and taken again since the last flush: the erased record goes first in the same call (of a slot named twice
+      // the table keeps the last record), so that the attributes of the point that left are cleared and the slot reads as "no
+      // attributes" until the new point's are set.
+      if (pointOf_[s] && erasePending_[s]) send(Record());
+      erasePending_[s] = 0;
+      send(pointOf_[s] ? read(pointOf_[s], true) : Record());
     }
     dirtyPoints_.clear();
     if (!dirtyKfs_.empty()) {
@@ -193,6 +221,76 @@ class MapMirror {
       viewKf.push_back(0); viewIdx.push_back(0);
       mapCheck(ydorb_mapdb_set_point_views(db_, slots.data(), (int32_t)slots.size(), viewStart.data(), viewKf.data(), viewIdx.data()));
     }
+    if (!dirtyAttrs_.empty()) {   // after the points: an erased point's clear is staged by set_points, a reused slot's values follow it
+      // Each group only where the member is set: a point made from a keyframe has no descriptor until computeDistinctiveDescriptors,
+      // and one whose normal is still empty has no geometry.  Hence up to two calls, one per group.
+      std::vector<int32_t> geoSlots, descSlots;
+      std::vector<float> normal, minD, maxD;
+      std::vector<uint8_t> desc;
+      for (const int32_t s : dirtyAttrs_) {
+        attrDirty_[s] = kClean;
+        if (!pointOf_[s]) continue;   // forgotten since
+        const size_t g = minD.size(), d = desc.size();
+        appendAttributes(pointOf_[s], normal, minD, maxD, desc);
+        if (minD.size() > g) geoSlots.push_back(s);
+        if (desc.size() > d) descSlots.push_back(s);
+      }
+      dirtyAttrs_.clear();
+      if (!geoSlots.empty())
+        mapCheck(ydorb_mapdb_set_point_attributes(db_, geoSlots.data(), (int32_t)geoSlots.size(), normal.data(), minD.data(), maxD.data(), nullptr));
+      if (!descSlots.empty())
+        mapCheck(ydorb_mapdb_set_point_attributes(db_, descSlots.data(), (int32_t)descSlots.size(), nullptr, nullptr, nullptr, desc.data()));
+    }
+  }
+
+  // The device part of Tracking::searchLocalPoints for a list of local map points (ydorb_mapdb_search_local_points): resolves the
+  // pointers to slots, flushes, and makes the one call.  skip [n] = the caller's flags (a point seen in this frame already); the table
+  // adds its own bad flag.  taken / assigned as ydorb_search_local_points takes them; assigned[idx] indexes localMapPoints.  Returns the
+  // number of matches; nToMatch = the points in view.
+  int searchLocalPoints(ydorb_matcher_t* matcher, const YdFrameView& frame, const YdFrustumView& view, const std::vector<MapPointPtr>& localMapPoints,
+                        const std::vector<uint8_t>& skip, float th, float ratio, std::vector<uint8_t>& taken, std::vector<int32_t>& assigned,
+                        std::vector<YdTrackView>& rows, std::vector<uint8_t>& status, int32_t& nToMatch) {
+    if (!attributes_) throw std::runtime_error("ydorb: searchLocalPoints without enableAttributes()");
+    const size_t n = localMapPoints.size();
+    std::vector<int32_t> slots(n + 1);
+    for (size_t i = 0; i < n; i++) slots[i] = known(localMapPoints[i]);
+    flush();
+    rows.resize(n + 1); status.resize(n + 1);
+    int32_t nMatches = 0;
+    nToMatch = 0;
+    std::vector<uint8_t> sk(skip);
+    sk.resize(n + 1, 0);
+    mapCheck(ydorb_mapdb_search_local_points(db_, matcher, &frame, &view, slots.data(), (int32_t)n, sk.data(), th, ratio, taken.data(), assigned.data(),
+                                             rows.data(), status.data(), &nToMatch, &nMatches));
+    rows.resize(n); status.resize(n);
+    return nMatches;
+  }
+
+  // Flushes and compares every known point's getNormal(), getMinDistance(), getMaxDistance() and getDescriptor() with the device's
+  // attributes (ydorb_mapdb_export_attributes): the point slots that differ in a group whose flag is set, and the slots of points that
+  // are not bad and lack a flag (the search reports those as YDORB_FRUSTUM_NO_ATTRIBUTES).  Empty when every host-side change was touched.
+  std::vector<int32_t> verifyAttributes() {
+    flush();
+    YdMapDbStats st;
+    mapCheck(ydorb_mapdb_stats(db_, &st));
+    const size_t np = (size_t)st.n_points;
+    std::vector<float> normal(3 * np + 3), minD(np + 1), maxD(np + 1);
+    std::vector<uint8_t> desc(32 * np + 32), flags(np + 1);
+    mapCheck(ydorb_mapdb_export_attributes(db_, normal.data(), minD.data(), maxD.data(), desc.data(), flags.data()));
+    std::vector<int32_t> differ;
+    for (size_t s = 0; s < pointOf_.size(); s++) {
+      if (!pointOf_[s]) continue;
+      if (s >= np) { differ.push_back((int32_t)s); continue; }
+      std::vector<float> n3, mn, mx;
+      std::vector<uint8_t> d;
+      appendAttributes(pointOf_[s], n3, mn, mx, d);
+      bool same = pointOf_[s]->isBad() || flags[s] == 3;
+      if (flags[s] & 1)   // a flag the object has no member for is a difference
+        same = same && !mn.empty() && std::memcmp(&normal[3 * s], n3.data(), 12) == 0 && std::memcmp(&minD[s], mn.data(), 4) == 0 && std::memcmp(&maxD[s], mx.data(), 4) == 0;
+      if (flags[s] & 2) same = same && !d.empty() && std::memcmp(&desc[32 * s], d.data(), 32) == 0;
+      if (!same) differ.push_back((int32_t)s);
+    }
+    return differ;
   }
 
   // MapPoint::computeDistinctiveDescriptors for every point of `points` over the resident table (ydorb_mapdb_distinctive_descriptors):
@@ -673,7 +771,10 @@ class MapMirror {
     if (it != pointSlot_.end()) return it->second;
     int32_t s;
     if (!freePoints_.empty()) { s = freePoints_.back(); freePoints_.pop_back(); }
-    else { s = (int32_t)pointOf_.size(); pointOf_.push_back(MapPointPtr()); pointDirty_.push_back(kClean); span_.push_back(0); }
+    else {
+      s = (int32_t)pointOf_.size();
+      pointOf_.push_back(MapPointPtr()); pointDirty_.push_back(kClean); span_.push_back(0); attrDirty_.push_back(kClean); erasePending_.push_back(0);
+    }
     pointOf_[s] = mp;
     pointSlot_[mp] = s;
     return s;
@@ -739,6 +840,29 @@ class MapMirror {
   template <class K>
   static void appendDescriptorsOf(const K&, std::vector<uint8_t>&, long) { throw std::runtime_error("ydorb: the keyframe type has no m_cvMat_descriptors"); }
   static void appendDescriptors(const KeyFramePtr& kf, std::vector<uint8_t>& to) { appendDescriptorsOf(kf, to, 0); }
+  // getNormal() (3x1 CV_32F), the raw getMinDistance() / getMaxDistance() and getDescriptor() (1x32 CV_8U) of one point, each group
+  // appended only when its matrix is not empty (the member is set).  Chosen by
+  // overload so that a map-point type without them still builds the mirror (it cannot touch attributes).
+  template <class P>
+  static auto appendAttributesOf(const P& mp, std::vector<float>& normal, std::vector<float>& minD, std::vector<float>& maxD, std::vector<uint8_t>& desc, int)
+      -> decltype((void)mp->getMinDistance(), (void)mp->getDescriptor()) {
+    const cv::Mat N = mp->getNormal(), D = mp->getDescriptor();
+    if (!N.empty()) {
+      for (int r = 0; r < 3; r++) normal.push_back(N.template at<float>(r));
+      minD.push_back(mp->getMinDistance()); maxD.push_back(mp->getMaxDistance());
+    }
+    if (!D.empty()) {
+      const unsigned char* d = D.template ptr<unsigned char>();
+      desc.insert(desc.end(), d, d + 32);
+    }
+  }
+  template <class P>
+  static void appendAttributesOf(const P&, std::vector<float>&, std::vector<float>&, std::vector<float>&, std::vector<uint8_t>&, long) {
+    throw std::runtime_error("ydorb: the map-point type has no getMinDistance() / getDescriptor()");
+  }
+  static void appendAttributes(const MapPointPtr& mp, std::vector<float>& normal, std::vector<float>& minD, std::vector<float>& maxD, std::vector<uint8_t>& desc) {
+    appendAttributesOf(mp, normal, minD, maxD, desc, 0);
+  }
   std::vector<float> scaleFactors() const {   // one pyramid for all keyframes
     for (const KeyFramePtr& kf : kfOf_) if (kf) return kf->m_v_scaleFactors;
     return std::vector<float>(1, 1.0f);
@@ -759,6 +883,10 @@ class MapMirror {
   bool descriptors_ = false;
   std::vector<uint8_t> descDirty_, descSent_;   // per keyframe slot: the block is re-read at the next flush / the table holds a block of it
   std::vector<int32_t> dirtyDescs_;
+  bool attributes_ = false;
+  std::vector<uint8_t> attrDirty_;   // per point slot: the attributes are re-read at the next flush
+  std::vector<uint8_t> erasePending_;   // per point slot: forgotten with attributes enabled, and the erased record has not gone yet
+  std::vector<int32_t> dirtyAttrs_;
 };
 
 }  // namespace adapter

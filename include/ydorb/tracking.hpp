@@ -181,6 +181,44 @@ inline int searchLocalPointsImpl(ydorb_matcher_t* m, FrameT& frame, const std::v
   return nToMatch > 0 ? nMatches : 0;
 }
 
+// Tracking::searchLocalPoints' body over a MapMirror with enableAttributes() (mapMirror.hpp): the same pre-loop
+// and post-loop, but position, normal, distances and descriptor of every local point are read on the device by slot and only the slot
+// list and a skip byte per point go up (ydorb_mapdb_search_local_points).  isBad() and getObservationsNum() are not asked per point:
+// the table's bad flag and observation span answer them.  seen (updateLocalPointsImpl's return value) may be given; a point it flags is
+// skipped as one whose m_int_lastSeenInFrameID is this frame's.  A point the table holds no complete attributes for comes back as
+// YDORB_FRUSTUM_NO_ATTRIBUTES and is handled as not in view (mirror.verifyAttributes() names it).
+template <class Mirror, class FrameT, class MapPointPtr>
+inline int searchLocalPointsImpl(Mirror& mirror, ydorb_matcher_t* m, FrameT& frame, const std::vector<MapPointPtr>& localMapPoints, float th, float ratio,
+                                 const std::vector<uint8_t>* seen = nullptr) {
+  for (auto& mp : frame.m_v_sptrMapPoints) {      // the points the frame already tracks are not searched again
+    if (!mp) continue;
+    if (mp->isBad()) { mp.reset(); continue; }
+    mp->increaseVisible();
+    mp->m_int_lastSeenInFrameID = frame.m_int_ID;
+    mp->m_b_isTrackInView = false;
+  }
+  const int n = (int)localMapPoints.size();
+  if (n == 0) return 0;
+  std::vector<uint8_t> skip(n), status;
+  for (int i = 0; i < n; i++) skip[i] = (localMapPoints[i]->m_int_lastSeenInFrameID == frame.m_int_ID || (seen && (*seen)[i])) ? 1 : 0;
+  const YdFrustumView view = frustumView(frame, 0.5f);
+  std::vector<YdTrackView> rows;
+  std::vector<uint8_t> taken;
+  takenMask(frame, false, taken);
+  std::vector<int32_t> assigned(taken.size(), -1);
+  int32_t nToMatch = 0;
+  const YdFrameView fv = frameView(frame);
+  const int nMatches = mirror.searchLocalPoints(m, fv, view, localMapPoints, skip, th, ratio, taken, assigned, rows, status, nToMatch);
+  for (int i = 0; i < n; i++) {
+    if (status[i] == YDORB_FRUSTUM_SKIPPED) continue;   // the reference does not call isInCameraFrustum for these
+    writeTrackFields(localMapPoints[i], status[i], rows[i]);   // YDORB_FRUSTUM_NO_ATTRIBUTES: not in view
+    if (status[i] == YDORB_FRUSTUM_IN_VIEW) localMapPoints[i]->increaseVisible();
+  }
+  for (size_t i = 0; i < assigned.size(); i++)
+    if (assigned[i] >= 0) frame.m_v_sptrMapPoints[i] = localMapPoints[assigned[i]];
+  return nToMatch > 0 ? nMatches : 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Tracking::updateLocalMap's two halves over a MapMirror's keyframe rows (mapMirror.hpp), restated from
 // ORB-SLAM2's Tracking::UpdateLocalKeyFrames / UpdateLocalPoints (the reference source is absent from this repository).  The member

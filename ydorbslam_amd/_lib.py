@@ -148,6 +148,13 @@ SYMBOLS = {
     "ydorb_mapdb_export_views": (C.c_int, [_VP, _VP, _VP, _VP]),
     "ydorb_mapdb_export_descriptors": (C.c_int, [_VP, _VP, _VP]),
     "ydorb_mapdb_desc_stats": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_enable_attributes": (C.c_int, [_VP]),
+    "ydorb_mapdb_set_point_attributes": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_export_attributes": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_attr_stats": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_frustum_cull": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_search_local_points": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP, C.POINTER(_I),
+                                                  C.POINTER(_I)]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -247,6 +254,11 @@ class YdMapDbDescStats(C.Structure):
     _fields_ = [("n_views", C.c_int64), ("n_descriptors", C.c_int64), ("view_pool_used", C.c_int64), ("view_pool_capacity", C.c_int64),
                 ("desc_pool_used", C.c_int64), ("desc_pool_capacity", C.c_int64), ("view_repacks_kept", _I), ("view_repacks_grown", _I),
                 ("desc_repacks_kept", _I), ("desc_repacks_grown", _I), ("last_desc_sync_bytes", C.c_int64), ("last_desc_sync_records", C.c_int64)]
+
+
+class YdMapDbAttrStats(C.Structure):
+    _fields_ = [("enabled", _I), ("growths", _I), ("capacity", C.c_int64), ("last_attr_sync_bytes", C.c_int64),
+                ("last_attr_sync_records", C.c_int64), ("last_write_through_records", C.c_int64)]
 
 
 class YdMapCorrection(C.Structure):

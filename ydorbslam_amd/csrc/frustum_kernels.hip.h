@@ -83,17 +83,10 @@ static __global__ __launch_bounds__(kThreads) void k_frustum_cull(Args g) {
   g.status[e] = (uint8_t)code;
 }
 
-// One view over the points 0 .. n-1: the track rows and status bytes of k_frustum_cull plus the query rows of
-// searchByProjectionInFrameAndMapPoint (orbMatcher.cpp:28-38) where k_gather_projection reads them (QueryT = match_kernels' QueryDev).
+// The query row of searchByProjectionInFrameAndMapPoint (orbMatcher.cpp:28-38) for one tested point where k_gather_projection reads it
+// (QueryT = match_kernels' QueryDev): all zero, flags 0, unless the point is in view.
 template <class QueryT>
-static __global__ __launch_bounds__(kThreads) void k_frustum_queries(ViewDev V, int n, const float4* __restrict__ posMin, const float4* __restrict__ normalMax,
-                                                              const float* __restrict__ maxDistance, const uint8_t* __restrict__ skip,
-                                                              const uint8_t* __restrict__ hasObs, float th, QueryT* __restrict__ queries,
-                                                              YdTrackView* __restrict__ rows, uint8_t* __restrict__ status) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  YdTrackView T;
-  const int code = frustum_test(V, posMin[i], normalMax[i], maxDistance[i], skip[i] != 0, T);
+__device__ __forceinline__ QueryT query_of(const ViewDev& V, const YdTrackView& T, int code, float th, bool hasObs) {
   QueryT Q;
   Q.u = 0.f; Q.v = 0.f; Q.r = 0.f; Q.minLevel = 0; Q.maxLevel = 0; Q.ur = 0.f; Q.rs = 0.f; Q.angle = 0.f; Q.level = 0; Q.flags = 0;
   if (code == YDORB_FRUSTUM_IN_VIEW) {
@@ -104,9 +97,22 @@ static __global__ __launch_bounds__(kThreads) void k_frustum_queries(ViewDev V, 
     Q.u = T.u; Q.v = T.v; Q.r = radius * sf;
     Q.minLevel = T.level - 1; Q.maxLevel = T.level;
     Q.ur = T.ur; Q.rs = Q.r; Q.level = T.level;
-    Q.flags = 1 | (hasObs[i] ? 2 : 0);
+    Q.flags = 1 | (hasObs ? 2 : 0);
   }
-  queries[i] = Q;
+  return Q;
+}
+
+// One view over the points 0 .. n-1: the track rows and status bytes of k_frustum_cull plus the query rows of the projection search.
+template <class QueryT>
+static __global__ __launch_bounds__(kThreads) void k_frustum_queries(ViewDev V, int n, const float4* __restrict__ posMin, const float4* __restrict__ normalMax,
+                                                              const float* __restrict__ maxDistance, const uint8_t* __restrict__ skip,
+                                                              const uint8_t* __restrict__ hasObs, float th, QueryT* __restrict__ queries,
+                                                              YdTrackView* __restrict__ rows, uint8_t* __restrict__ status) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  YdTrackView T;
+  const int code = frustum_test(V, posMin[i], normalMax[i], maxDistance[i], skip[i] != 0, T);
+  queries[i] = query_of<QueryT>(V, T, code, th, hasObs[i] != 0);
   rows[i] = T;
   status[i] = (uint8_t)code;
 }

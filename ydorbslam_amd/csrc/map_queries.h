@@ -75,9 +75,16 @@ struct MapSource {
   }
 };
 
+// Where runNormalDepth left the slots it was given and its results on the device; they stay until the context's buffers are used again
+struct NormalDepthOnDevice {
+  const int* slots = nullptr;
+  const float *normal = nullptr, *minDistance = nullptr, *maxDistance = nullptr;
+  const uint8_t* status = nullptr;
+};
+
 // n > 0 points: all of a flat table's, or the resident table's `slots`
 inline int runNormalDepth(StagedCtx& c, MapSource& src, int32_t n, const float* scale_factors, int32_t n_levels, float* normal,
-                          float* min_distance, float* max_distance, uint8_t* status) {
+                          float* min_distance, float* max_distance, uint8_t* status, NormalDepthOnDevice* where = nullptr) {
   const size_t np = (size_t)n;
   Layout U;
   src.lay(U);
@@ -106,6 +113,7 @@ inline int runNormalDepth(StagedCtx& c, MapSource& src, int32_t n, const float* 
   std::memcpy(min_distance, at<void>(c.hDown, dMin), 4 * np);
   std::memcpy(max_distance, at<void>(c.hDown, dMax), 4 * np);
   std::memcpy(status, at<void>(c.hDown, dSt), np);
+  if (where) { where->slots = a.slots; where->normal = a.normal; where->minDistance = a.minDistance; where->maxDistance = a.maxDistance; where->status = a.status; }
   return YDORB_OK;
 }
 

@@ -8,7 +8,9 @@
 // The keyframe rows (mapdb_rows_host.h, mapdb_rows_kernels.hip.h) are a second state machine in the same handle,
 // synced after the points under the same mutex: ydorb_mapdb_points_of_keyframes and ydorb_mapdb_observer_counter below.
 // The point views and the keyframe descriptor blocks (mapdb_desc_host.h, mapdb_desc_kernels.hip.h) are two more,
-// synced after the rows through the same syncSpans: ydorb_mapdb_distinctive_descriptors at the end of this file.
+// synced after the rows through the same syncSpans: ydorb_mapdb_distinctive_descriptors below.
+// The point attributes (mapdb_attr_host.h, mapdb_attr_kernels.hip.h) are an opt-in fifth, synced last; three
+// queries write their results through to them, and ydorb_mapdb_frustum_cull / lockResident at the end of this file read them by slot.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -21,10 +23,14 @@
 #include "map_queries.h"
 #include "map_table.h"
 #include "mapcorrect_kernels.hip.h"
+#include "mapdb_attr_host.h"
+#include "mapdb_attr_kernels.hip.h"
 #include "mapdb_desc_host.h"
 #include "mapdb_desc_kernels.hip.h"
+#include "mapdb_frustum_kernels.hip.h"
 #include "mapdb_host.h"
 #include "mapdb_kernels.hip.h"
+#include "mapdb_resident_points.h"
 #include "mapdb_rows_host.h"
 #include "mapdb_rows_kernels.hip.h"
 #include "ydorb_host.h"
@@ -60,6 +66,11 @@ struct ydorb_mapdb {
   DeltaPair viewDelta, blockDelta;
   int *viewStart = nullptr, *viewLen = nullptr, *viewPool = nullptr, *blockStart = nullptr, *blockLen = nullptr;
   mapdb::DescRow* blockPool = nullptr;
+  // point attributes: nothing of this is allocated or launched until ydorb_mapdb_enable_attributes
+  mapdb::AttrHost attr;
+  Mem attrMem;
+  DeltaPair attrDelta;
+  mapdb::AttrArrays A{};
   ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc) {}
 };
 
@@ -255,10 +266,81 @@ int syncDescriptors(ydorb_mapdb* h) {
     });
 }
 
+size_t layAttributes(Carve& C, mapdb::AttrArrays& A, size_t cap) {
+  C.take(A.normal, 3 * cap); C.take(A.minDistance, cap); C.take(A.maxDistance, cap); C.take(A.desc, 2 * cap); C.take(A.flags, cap);
+  return C.L.bytes;
+}
+// A fresh attribute arena of `cap` slots: all zero, what a slot never set reads as
+int allocAttributes(hipStream_t s, Mem& m, mapdb::AttrArrays& A, size_t cap) {
+  mapdb::AttrArrays sizing{};
+  Carve sz(nullptr);
+  int rc = m.alloc(layAttributes(sz, sizing, cap));
+  if (rc) return rc;
+  Carve cv(m.p);
+  layAttributes(cv, A, cap);
+  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
+  return YDORB_OK;
+}
+
+// The staged attributes, after everything else: the arena follows the point table's capacity (syncPoints may just have grown it), then
+// one upload of the records and k_mapdb_attr_apply.
+int syncAttributes(ydorb_mapdb* h) {
+  mapdb::AttrHost& host = h->attr;
+  if (!host.needsSync(h->host.pointCap())) { host.nothingToSync(); return YDORB_OK; }
+  hipStream_t s = h->c.stream;
+  const mapdb::AttrPlan P = host.plan(h->host.pointCap());
+  int rc;
+  if ((rc = h->attrDelta.ensure(P.bytes))) return rc;
+  ScopedMem fresh;
+  mapdb::AttrArrays A = h->A;
+  if (P.cap != P.capBefore && (rc = allocAttributes(s, fresh, A, (size_t)P.cap))) return rc;
+  host.pack(P, h->attrDelta.host.as<uint8_t>());   // every allocation is made: only a HIP error can fail below, and the delta counts as applied
+  if (P.bytes) HIPCHK(hipMemcpyAsync(h->attrDelta.dev.p, h->attrDelta.host.p, P.bytes, hipMemcpyHostToDevice, s));
+  if (fresh.p) {
+    const size_t n = (size_t)P.capBefore;
+    D2D(A.normal, h->A.normal, 12 * n); D2D(A.minDistance, h->A.minDistance, 4 * n); D2D(A.maxDistance, h->A.maxDistance, 4 * n);
+    D2D(A.desc, h->A.desc, 32 * n); D2D(A.flags, h->A.flags, n);
+  }
+  if (P.nRec) {
+    hipLaunchKernelGGL(mapdb::k_mapdb_attr_apply, dim3((unsigned)((P.nRec + mapdb::kAttrThreads - 1) / mapdb::kAttrThreads)), dim3(mapdb::kAttrThreads), 0, s,
+                       P.nRec, h->attrDelta.dev.as<mapdb::AttrRec>(), A);
+    HIPCHK(hipGetLastError());
+  }
+  if ((rc = handOver(s, {{&h->attrMem, &fresh}}))) return rc;
+  h->A = A;
+  return YDORB_OK;
+}
+
 int sync(ydorb_mapdb* h) {
   int rc = syncPoints(h);
   if (!rc) rc = syncRows(h);
-  return rc ? rc : syncDescriptors(h);
+  if (!rc) rc = syncDescriptors(h);
+  return rc || !h->attr.enabled() ? rc : syncAttributes(h);
+}
+
+unsigned attrBlocks(size_t n) { return (unsigned)((n + mapdb::kAttrThreads - 1) / mapdb::kAttrThreads); }
+
+// Write-through of a query that has just run and synchronised: its device result buffer still holds normal, distances and status,
+// and `slots` [n] is where it uploaded them.  Queued behind it on the handle's stream and not waited for: whatever reads the arrays
+// next is either on that stream or synchronises it first (lockResident).  hStatus: the statuses as read back, for the count.
+int writeThroughGeometry(ydorb_mapdb* h, int n, const int* slots, const float* normal, const float* minDistance, const float* maxDistance,
+                         const uint8_t* status, const uint8_t* hStatus, int want) {
+  int64_t wrote = 0;
+  for (int i = 0; i < n; i++) wrote += hStatus[i] == want;
+  h->attr.wroteThrough(wrote);
+  if (!wrote) return YDORB_OK;
+  hipLaunchKernelGGL(mapdb::k_attr_scatter_geometry, dim3(attrBlocks((size_t)n)), dim3(mapdb::kAttrThreads), 0, h->c.stream, n, slots, normal, minDistance,
+                     maxDistance, status, want, h->A);
+  HIPCHK(hipGetLastError());
+  return YDORB_OK;
+}
+
+mapdb::ResidentPoints residentOf(const ydorb_mapdb* h) {   // call after sync(), which may move the arenas
+  mapdb::ResidentPoints R;
+  R.pos = h->T.pos; R.bad = h->T.bad; R.obsStart = h->T.start; R.obsEnd = h->T.end;
+  R.normal = h->A.normal; R.minDistance = h->A.minDistance; R.maxDistance = h->A.maxDistance;
+  R.desc = reinterpret_cast<const mapdb::Desc16*>(h->A.desc); R.flags = h->A.flags;
+  return R;
 }
 
 // first / seenStamp cover the point table's capacity: a fresh pair when it grew.  first is INT32_MAX everywhere between calls.
@@ -325,6 +407,7 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   h->points.release(); h->centres.release(); h->pool.release(); h->delta.release();
   h->rowHdr.release(); h->rowPoolMem.release(); h->rowDelta.release(); h->rowset.release();
   h->viewHdr.release(); h->viewPoolMem.release(); h->viewDelta.release(); h->blockHdr.release(); h->blockPoolMem.release(); h->blockDelta.release();
+  h->attrMem.release(); h->attrDelta.release();
   delete h;
 }
 
@@ -335,7 +418,9 @@ extern "C" int ydorb_mapdb_clear(ydorb_mapdb_t* h) {
   h->host.clear();
   h->rows.clear();
   h->desc.clear();
+  h->attr.clear();
   hipStream_t s = h->c.stream;   // every slot reads as never set again
+  if (h->attrMem.p) HIPCHK(hipMemsetAsync(h->attrMem.p, 0, h->attrMem.cap, s));
   HIPCHK(hipMemsetAsync(h->rowHdr.p, 0, h->rowHdr.cap, s));
   HIPCHK(hipMemsetAsync(h->viewHdr.p, 0, h->viewHdr.cap, s));
   HIPCHK(hipMemsetAsync(h->blockHdr.p, 0, h->blockHdr.cap, s));
@@ -364,7 +449,9 @@ extern "C" int ydorb_mapdb_set_points(ydorb_mapdb_t* h, const int32_t* slots, in
   if (!h) return invalid("null handle");
   std::lock_guard<std::mutex> lock(h->c.mu);
   std::string err;
-  return h->host.setPoints(slots, n, obs_start, obs_kf, obs_level, bad, ref_kf, ref_level, pos, err) ? YDORB_OK : invalid(err);
+  if (!h->host.setPoints(slots, n, obs_start, obs_kf, obs_level, bad, ref_kf, ref_level, pos, err)) return invalid(err);
+  h->attr.pointsSet(slots, n, obs_start, bad);   // an erased point clears its attributes
+  return YDORB_OK;
 }
 
 extern "C" int ydorb_mapdb_set_positions(ydorb_mapdb_t* h, const int32_t* slots, int32_t n, const float* pos) {
@@ -393,7 +480,9 @@ extern "C" int ydorb_mapdb_update_normal_depth(ydorb_mapdb_t* h, const int32_t* 
   if (rc) return rc;
   mapmaint::MapSource src = sourceOf(h);
   src.slots = slots;
-  return mapmaint::runNormalDepth(h->c, src, n, scale_factors, n_levels, normal, min_distance, max_distance, status);
+  mapmaint::NormalDepthOnDevice dev;
+  if ((rc = mapmaint::runNormalDepth(h->c, src, n, scale_factors, n_levels, normal, min_distance, max_distance, status, &dev)) || !h->attr.enabled()) return rc;
+  return writeThroughGeometry(h, n, dev.slots, dev.normal, dev.minDistance, dev.maxDistance, dev.status, status, YDORB_MAP_UPDATED);
 }
 
 extern "C" int ydorb_mapdb_covisibility(ydorb_mapdb_t* h, const int32_t* query_kf, int32_t n_queries, const int32_t* list_start,
@@ -493,6 +582,12 @@ extern "C" int ydorb_mapdb_correct(ydorb_mapdb_t* h, const YdMapCorrection* c) {
   if (nc) HIPCHK(hipMemcpyAsync(ctx.hDown.p, ctx.down.p, D.bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   h->host.correctionApplied(c, P, at<float>(ctx.hDown, dPos));
+  if (h->attr.enabled()) {   // a call without a normals pass computed none: it writes nothing
+    h->attr.wroteThrough(0);
+    if (P.normals && nc && (rc = writeThroughGeometry(h, (int)nc, at<int>(ctx.up, oSlot), at<float>(ctx.down, dNrm), at<float>(ctx.down, dMin),
+                                                      at<float>(ctx.down, dMax), at<uint8_t>(ctx.down, dSt), at<uint8_t>(ctx.hDown, dSt), YDORB_MAPCORR_DONE)))
+      return rc;
+  }
   if (n == 0) return YDORB_OK;
   std::memset(c->pos_out, 0, 12 * n);
   if (P.normals) { std::memset(c->normal, 0, 12 * n); std::memset(c->min_distance, 0, 4 * n); std::memset(c->max_distance, 0, 4 * n); }
@@ -785,6 +880,16 @@ extern "C" int ydorb_mapdb_distinctive_descriptors(ydorb_mapdb_t* h, const int32
   HIPCHK(hipStreamSynchronize(s));
   std::memcpy(desc_out, at<void>(c.hDown, dDesc), 32 * nq); std::memcpy(best, at<void>(c.hDown, dBest), 4 * nq);
   std::memcpy(best_view, at<void>(c.hDown, dView), 8 * nq); std::memcpy(status, at<void>(c.hDown, dSt), nq);
+  if (h->attr.enabled()) {   // the winning rows stay: see writeThroughGeometry for the ordering
+    int64_t wrote = 0;
+    for (size_t i = 0; i < nq; i++) wrote += status[i] == YDORB_MAPDESC_UPDATED;
+    h->attr.wroteThrough(wrote);
+    if (wrote) {
+      hipLaunchKernelGGL(mapdb::k_attr_scatter_descriptor, dim3(attrBlocks(nq)), dim3(mapdb::kAttrThreads), 0, s, n, c.up.as<int>(), at<uint4>(c.down, dDesc),
+                         at<uint8_t>(c.down, dSt), YDORB_MAPDESC_UPDATED, h->A);
+      HIPCHK(hipGetLastError());
+    }
+  }
   return YDORB_OK;
 }
 
@@ -838,3 +943,129 @@ extern "C" int ydorb_mapdb_export_descriptors(ydorb_mapdb_t* h, int32_t* desc_st
                      at<mapdb::DescRow>(h->c.hDown, dPool), desc_start, reinterpret_cast<mapdb::DescRow*>(desc));
   return YDORB_OK;
 }
+
+// --------------------------------------------------------------------------------------------------------------- point attributes
+extern "C" int ydorb_mapdb_enable_attributes(ydorb_mapdb_t* h) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (h->attr.enabled()) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc = allocAttributes(h->c.stream, h->attrMem, h->A, (size_t)h->host.pointCap());
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->c.stream));
+  h->attr.enable(h->host.pointCap());
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_set_point_attributes(ydorb_mapdb_t* h, const int32_t* slots, int32_t n, const float* normal, const float* min_distance,
+                                                const float* max_distance, const uint8_t* desc) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  return h->attr.set(slots, n, normal, min_distance, max_distance, desc, h->host.nPoints(), err) ? YDORB_OK : invalid(err);
+}
+
+extern "C" int ydorb_mapdb_attr_stats(ydorb_mapdb_t* h, YdMapDbAttrStats* stats) {
+  if (!h || !stats) return invalid("null handle or stats");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  h->attr.stats(*stats);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_export_attributes(ydorb_mapdb_t* h, float* normal, float* min_distance, float* max_distance, uint8_t* desc, uint8_t* flags) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!mapdb::AttrHost::checkEnabled(h->attr.enabled(), err)) return invalid(err);
+  const size_t np = (size_t)h->host.nPoints();
+  if (np > 0 && (!normal || !min_distance || !max_distance || !desc || !flags)) return invalid("null normal, min_distance, max_distance, desc or flags");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  if (np == 0) return YDORB_OK;
+  StagedCtx& c = h->c;
+  Layout D;
+  const size_t dNrm = D.add(12 * np), dMin = D.add(4 * np), dMax = D.add(4 * np), dDesc = D.add(32 * np), dFlg = D.add(np);
+  if ((rc = c.hDown.ensure(D.bytes))) return rc;
+  hipStream_t s = c.stream;
+  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dNrm), h->A.normal, 12 * np, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dMin), h->A.minDistance, 4 * np, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dMax), h->A.maxDistance, 4 * np, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dDesc), h->A.desc, 32 * np, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dFlg), h->A.flags, np, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(normal, at<void>(c.hDown, dNrm), 12 * np); std::memcpy(min_distance, at<void>(c.hDown, dMin), 4 * np);
+  std::memcpy(max_distance, at<void>(c.hDown, dMax), 4 * np); std::memcpy(desc, at<void>(c.hDown, dDesc), 32 * np);
+  std::memcpy(flags, at<void>(c.hDown, dFlg), np);
+  return YDORB_OK;
+}
+
+// sync; one upload of views, list starts, slots and skip bytes; one lane per list entry; one read-back; one synchronise
+extern "C" int ydorb_mapdb_frustum_cull(ydorb_mapdb_t* h, const YdFrustumView* views, int32_t n_views, const int32_t* list_start,
+                                        const int32_t* point_slots, const uint8_t* skip, YdTrackView* rows, uint8_t* status, int32_t* n_in_view) {
+  std::string err;
+  if (n_views < 0) return invalid("negative number of views: " + std::to_string(n_views));
+  if (!maptable::checkStarts("list_start", list_start, n_views, err)) return invalid(err);
+  if (n_views > 0 && !views) return invalid("null views");
+  const int32_t L = list_start[n_views];
+  if (L > 0 && (!point_slots || !skip || !rows || !status)) return invalid("null point_slots, skip, rows or status");
+  for (int32_t f = 0; f < n_views; f++)
+    if (views[f].n_levels < 1 || views[f].n_levels > 8) return invalid("view " + std::to_string(f) + ": n_levels " + std::to_string(views[f].n_levels) + " outside 1..8");
+  if (!h) {   // without a device no handle exists: say that, there is no CPU path to fall back to
+    const int rc = require_device(0);
+    return rc ? rc : invalid("null handle");
+  }
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (!mapdb::AttrHost::checkEnabled(h->attr.enabled(), err) || !mapdb::AttrHost::checkSlots(point_slots, L, h->host.nPoints(), err)) return invalid(err);
+  if (n_in_view) std::memset(n_in_view, 0, 4 * (size_t)n_views);
+  if (L == 0) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  const size_t nv = (size_t)n_views, nl = (size_t)L;
+  Layout U;
+  const size_t oViews = U.add(sizeof(YdFrustumView) * nv), oStart = U.add(4 * (nv + 1)), oSlots = U.add(4 * nl), oSkip = U.add(nl);
+  Layout D;
+  const size_t dRows = D.add(sizeof(YdTrackView) * nl), dSt = D.add(nl);
+  if ((rc = c.ensure(U.bytes, D.bytes))) return rc;
+  std::memcpy(at<void>(c.hUp, oViews), views, sizeof(YdFrustumView) * nv);
+  std::memcpy(at<void>(c.hUp, oStart), list_start, 4 * (nv + 1));
+  std::memcpy(at<void>(c.hUp, oSlots), point_slots, 4 * nl);
+  std::memcpy(at<void>(c.hUp, oSkip), skip, nl);
+  hipStream_t s = c.stream;
+  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  frustum::ResidentCullArgs a;
+  a.nViews = n_views; a.nEntries = L;
+  a.start = at<int>(c.up, oStart); a.views = at<frustum::ViewDev>(c.up, oViews); a.slots = at<int>(c.up, oSlots); a.skip = at<uint8_t>(c.up, oSkip);
+  a.rows = at<YdTrackView>(c.down, dRows); a.status = at<uint8_t>(c.down, dSt);
+  a.R = residentOf(h);
+  hipLaunchKernelGGL(frustum::k_mapdb_frustum_cull, dim3((unsigned)((nl + frustum::kThreads - 1) / frustum::kThreads)), dim3(frustum::kThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(rows, at<void>(c.hDown, dRows), sizeof(YdTrackView) * nl);
+  std::memcpy(status, at<void>(c.hDown, dSt), nl);
+  if (n_in_view)
+    for (int32_t f = 0; f < n_views; f++)
+      for (int32_t e = list_start[f]; e < list_start[f + 1]; e++) n_in_view[f] += status[e] == YDORB_FRUSTUM_IN_VIEW;
+  return YDORB_OK;
+}
+
+// What ydorb_mapdb_search_local_points (orb_matcher.hip) reads: mapdb_resident_points.h
+int ydorb::mapdb::lockResident(ydorb_mapdb_t* h, int32_t device, const int32_t* slots, int32_t n, ResidentPoints& out) {
+  std::unique_lock<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!AttrHost::checkEnabled(h->attr.enabled(), err) || !AttrHost::checkSlots(slots, n, h->host.nPoints(), err)) return invalid(err);
+  if (device != h->device) return invalid("the map table lives on device " + std::to_string(h->device) + ", the matcher on device " + std::to_string(device));
+  if (n > 0) {   // an empty list reads nothing: nothing is applied or launched for it
+    HIPCHK(hipSetDevice(h->device));
+    int rc = sync(h);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->c.stream));   // the delta and any write-through still queued: the reader runs on another stream
+  }
+  out = residentOf(h);
+  lock.release();   // held until unlockResident
+  return YDORB_OK;
+}
+void ydorb::mapdb::unlockResident(ydorb_mapdb_t* h) { h->c.mu.unlock(); }

@@ -15,6 +15,8 @@
 #include "../../include/ydorb/c_api.h"
 #include "frustum_kernels.hip.h"
 #include "host_buffers.h"
+#include "mapdb_frustum_kernels.hip.h"
+#include "mapdb_resident_points.h"
 #include "match_kernels.hip.h"
 #include "stereo_kernels.hip.h"
 #include "ydorb_host.h"
@@ -253,7 +255,8 @@ int ydorb_distinctive_descriptors(ydorb_matcher_t* m, const uint8_t* desc, const
 
 // laid != nullptr: the caller has laid the call arena out (layProjection) and the nq query rows are in laid->queries already
 // (ydorb_search_local_points builds them there with a kernel queued on m->stream; nothing below writes them or regrows the arena, so a
-// record-pool replay finds them unchanged)
+// record-pool replay finds them unchanged).  With laid given and qdesc == nullptr the query descriptors are in laid->qdesc already too
+// (ydorb_mapdb_search_local_points copies them there on the device) and their upload is skipped.
 static int searchProjectionImpl(ydorb_matcher_t* m, int32_t mode, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc,
                                 int32_t nq, float ratio, int32_t orbDist, int32_t checkOri, uint8_t* taken, int32_t* assigned,
                                 int32_t* nMatches, std::vector<uint32_t>* recordsOut, const float* invSigma2 = nullptr, int nLevels = 0,
@@ -282,7 +285,7 @@ static int searchProjectionImpl(ydorb_matcher_t* m, int32_t mode, const YdFrameV
     if ((rc = launchGridBuild(1, n, m->stream, p.frame))) return rc;
     HIPCHK(hipMemsetAsync(p.status, 0, 64, m->stream));
     if (queries) HIPCHK(hipMemcpyAsync(p.queries, queries, sizeof(YdQuery) * nq, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(p.qdesc, qdesc, (size_t)32 * nq, hipMemcpyHostToDevice, m->stream));
+    if (qdesc || !laid) HIPCHK(hipMemcpyAsync(p.qdesc, qdesc, (size_t)32 * nq, hipMemcpyHostToDevice, m->stream));
     if (taken) HIPCHK(hipMemcpyAsync(p.taken, taken, n, hipMemcpyHostToDevice, m->stream));
     else HIPCHK(hipMemsetAsync(p.taken, 0, n, m->stream));
     if (assigned) HIPCHK(hipMemcpyAsync(p.assigned, assigned, sizeof(int) * n, hipMemcpyHostToDevice, m->stream));
@@ -465,6 +468,64 @@ int ydorb_search_local_points(ydorb_matcher_t* m, const YdFrameView* fv, const Y
   // the search follows on the same stream without a host round trip: with no point in view every query has flags 0, nothing matches and
   // assigned / taken come back as they went up, which is the reference's skipped search
   if ((rc = searchProjectionImpl(m, YDORB_SEARCH_FRAME_MAPPOINT, fv, nullptr, table->desc, np, ratio, 0, 0, taken, assigned, nMatches, nullptr, nullptr, 0,
+                                 nullptr, &q)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(m->stream));   // the search returns early, without one, for a frame without keypoints
+  std::memcpy(rows, at<void>(m->hDown, dRows), sizeof(YdTrackView) * p);
+  std::memcpy(status, at<void>(m->hDown, dSt), p);
+  for (int i = 0; i < np; i++) *nToMatch += status[i] == YDORB_FRUSTUM_IN_VIEW;
+  return YDORB_OK;
+}
+
+// ydorb_search_local_points over a resident map table (map_resident.hip, mapdb_resident_points.h): what goes up is the slot list and
+// the skip bytes; k_mapdb_local_queries reads the points by slot and leaves query rows and query descriptors in the call arena.  The
+// table's mutex is held from its sync to the end of the call.  The matcher's stream is ordered behind that sync by a synchronise of
+// the table's stream inside lockResident (DESIGN.md section 6q says why not an event).  Every return after the first launch, an error
+// included, synchronises the matcher's stream before the mutex goes.
+int ydorb_mapdb_search_local_points(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdFrameView* fv, const YdFrustumView* view, const int32_t* slots,
+                                    int32_t np, const uint8_t* skip, float th, float ratio, uint8_t* taken, int32_t* assigned, YdTrackView* rows,
+                                    uint8_t* status, int32_t* nToMatch, int32_t* nMatches) {
+  if (!db || !m || !fv || !view || !nToMatch || !nMatches) { set_error("mapdb_search_local_points: null argument"); return YDORB_ERR_INVALID_ARG; }
+  if (view->n_levels < 1 || view->n_levels > 8) { set_error("mapdb_search_local_points: n_levels %d outside 1..8", view->n_levels); return YDORB_ERR_INVALID_ARG; }
+  if (np < 0) { set_error("mapdb_search_local_points: negative number of point slots: %d", np); return YDORB_ERR_INVALID_ARG; }
+  if (np > 0 && (!slots || !skip || !rows || !status)) {
+    set_error("mapdb_search_local_points: null point_slots, skip, rows or status");
+    return YDORB_ERR_INVALID_ARG;
+  }
+  const int n = fv->n;
+  if (!validFrameView(fv) || (n > 0 && !assigned)) {
+    set_error("mapdb_search_local_points: invalid frame view");
+    return YDORB_ERR_INVALID_ARG;
+  }
+  *nToMatch = 0; *nMatches = 0;
+  mapdb::ResidentPoints R;
+  mapdb::ResidentLock lock;
+  int rc;
+  if ((rc = mapdb::lockResident(db, m->device, slots, np, R))) return rc;   // also refuses a table without attributes
+  lock.db = db;
+  if (np == 0) return YDORB_OK;
+  if (n > 65535) { set_error("frames with more than 65535 keypoints are not supported"); return YDORB_ERR_UNSUPPORTED; }   // before anything is queued
+  HIPCHK(hipSetDevice(m->device));
+  // From the first launch on, no way out of this function gives the table's mutex back while the matcher's stream may still read the
+  // resident arenas: declared after `lock`, so it drains the stream before the mutex is released, on the error returns too.
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};
+  const size_t p = np;
+  Layout U;
+  const size_t oSlots = U.add(4 * p), oSkip = U.add(p);
+  Layout D;
+  const size_t dRows = D.add(sizeof(YdTrackView) * p), dSt = D.add(p);
+  ProjPtrs q;
+  if ((rc = m->hUp.ensure(U.bytes)) || (rc = m->hDown.ensure(D.bytes))) return rc;
+  if ((rc = layOut(m->call, [&](void* base) { return layProjection(std::max(n, 1), fv->right_x, np, U.bytes, D.bytes, base, q); }))) return rc;
+  std::memcpy(at<void>(m->hUp, oSlots), slots, 4 * p);
+  std::memcpy(at<void>(m->hUp, oSkip), skip, p);
+  HIPCHK(hipMemcpyAsync(q.table, m->hUp.p, U.bytes, hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(frustum::k_mapdb_local_queries<QueryDev>, dim3((np + frustum::kThreads - 1) / frustum::kThreads), dim3(frustum::kThreads), 0, m->stream,
+                     *view, np, (const int*)(q.table + oSlots), q.table + oSkip, R, th, q.queries, (uint4*)q.qdesc, (YdTrackView*)(q.track + dRows),
+                     q.track + dSt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(m->hDown.p, q.track, D.bytes, hipMemcpyDeviceToHost, m->stream));
+  if ((rc = searchProjectionImpl(m, YDORB_SEARCH_FRAME_MAPPOINT, fv, nullptr, nullptr, np, ratio, 0, 0, taken, assigned, nMatches, nullptr, nullptr, 0,
                                  nullptr, &q)))
     return rc;
   HIPCHK(hipStreamSynchronize(m->stream));   // the search returns early, without one, for a frame without keypoints

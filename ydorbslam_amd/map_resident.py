@@ -4,13 +4,14 @@ three queries go through map_maintenance's own wrappers (same argument preparati
 of the flat table.  MapDb.correct (ydorb_mapdb_correct) runs the point loops of loop closing on the table in place.
 The keyframe rows (DESIGN.md section 6o) add the relation keyframe -> map points and the two set queries of Tracking::updateLocalMap.
 The resident descriptors add the keyframes' descriptor blocks and the points' views, and
-MapPoint::computeDistinctiveDescriptors over them with no descriptor upload."""
+MapPoint::computeDistinctiveDescriptors over them with no descriptor upload.  The resident point attributes (DESIGN.md section 6q) keep
+normal, distances and descriptor of every point where those queries compute them, and Tracking::searchLocalPoints reads them by slot."""
 import ctypes as C
 
 import numpy as np
 
 from . import map_maintenance as M
-from ._lib import YdMapCorrection, YdMapDbDescStats, YdMapDbRowStats, YdMapDbStats, check, lib
+from ._lib import YdMapCorrection, YdMapDbAttrStats, YdMapDbDescStats, YdMapDbRowStats, YdMapDbStats, check, lib
 
 _p = M._p
 
@@ -252,6 +253,69 @@ class MapDb:
         check(lib().ydorb_mapdb_export_descriptors(self._h, _p(start), _p(desc)))
         assert int(start[-1]) == N
         return [desc[start[i]:start[i + 1]].copy() for i in range(k)]
+
+    # ------------------------------------------------------------------------------------------------------------ point attributes
+    def enable_attributes(self):
+        """Turns the resident point attributes on; calling it twice is fine."""
+        check(lib().ydorb_mapdb_enable_attributes(self._h))
+
+    def set_point_attributes(self, slots, normal=None, min_distance=None, max_distance=None, desc=None):
+        """Stages normal [n, 3], min_distance, max_distance [n] (the raw values; all three or none) and / or desc [n, 32] of the slots."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(slots)
+        normal = None if normal is None else np.ascontiguousarray(normal, np.float32).reshape(n, 3)
+        mn, mx = (None if a is None else np.ascontiguousarray(a, np.float32).reshape(n) for a in (min_distance, max_distance))
+        desc = None if desc is None else np.ascontiguousarray(desc, np.uint8).reshape(n, 32)
+        check(lib().ydorb_mapdb_set_point_attributes(self._h, _p(slots), n, _p(normal), _p(mn), _p(mx), _p(desc)))
+
+    def export_attributes(self):
+        """The device's attributes read back: dict(normal [n, 3], min_distance, max_distance [n], desc [n, 32], flags [n])."""
+        n = self.n_points
+        m = max(n, 1)
+        normal, mn, mx = np.zeros((m, 3), np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        desc, flags = np.zeros((m, 32), np.uint8), np.zeros(m, np.uint8)
+        check(lib().ydorb_mapdb_export_attributes(self._h, _p(normal), _p(mn), _p(mx), _p(desc), _p(flags)))
+        return dict(normal=normal[:n], min_distance=mn[:n], max_distance=mx[:n], desc=desc[:n], flags=flags[:n])
+
+    def attr_stats(self):
+        s = YdMapDbAttrStats()
+        check(lib().ydorb_mapdb_attr_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in YdMapDbAttrStats._fields_}
+
+    def frustum_cull(self, views, lists, skips):
+        """ydorb_mapdb_frustum_cull: views [YdFrustumView], per view a list of point slots and its skip bytes.  Returns per view
+        dict(rows [m] TRACK_DTYPE, status [m] uint8, n_in_view), as ydorbslam_amd.frustum.frustum_cull does."""
+        from ._lib import YdFrustumView
+        from .frustum import TRACK_DTYPE
+        F = len(views)
+        v = (YdFrustumView * max(F, 1))(*views)
+        idx = [np.asarray(a, np.int32).reshape(-1) for a in lists]
+        sk = [np.asarray(a, np.uint8).reshape(-1) for a in skips]
+        assert len(idx) == len(sk) == F and all(len(a) == len(b) for a, b in zip(idx, sk))
+        start = np.concatenate([[0], np.cumsum([len(a) for a in idx])]).astype(np.int32)
+        slots = np.ascontiguousarray(np.concatenate(idx + [np.zeros(0, np.int32)]))
+        skip = np.ascontiguousarray(np.concatenate(sk + [np.zeros(0, np.uint8)]))
+        L = int(start[-1])
+        rows, status, n_in = np.zeros(max(L, 1), TRACK_DTYPE), np.full(max(L, 1), 9, np.uint8), np.zeros(max(F, 1), np.int32)
+        check(lib().ydorb_mapdb_frustum_cull(self._h, C.cast(v, C.c_void_p), F, _p(start), _p(slots), _p(skip), _p(rows), _p(status), _p(n_in)))
+        return [dict(rows=rows[start[f]:start[f + 1]].copy(), status=status[start[f]:start[f + 1]].copy(), n_in_view=int(n_in[f])) for f in range(F)]
+
+    def search_local_points(self, matcher, frame, view, point_slots, skip, th, taken=None, assigned=None):
+        """ydorb_mapdb_search_local_points on an OrbMatcher (ydorbslam_amd.matcher; its ratio is used) and one of its frames.  Returns
+        the dict of ydorbslam_amd.frustum.search_local_points; assigned holds list indices into point_slots."""
+        from .frustum import TRACK_DTYPE
+        slots = np.ascontiguousarray(point_slots, np.int32).reshape(-1)
+        skip = np.ascontiguousarray(skip, np.uint8).reshape(-1)
+        n = len(slots)
+        assert len(skip) == n
+        taken = np.zeros(frame.n, np.uint8) if taken is None else np.ascontiguousarray(taken, np.uint8).copy()
+        assigned = np.full(frame.n, -1, np.int32) if assigned is None else np.ascontiguousarray(assigned, np.int32).copy()
+        rows, status = np.zeros(max(n, 1), TRACK_DTYPE), np.full(max(n, 1), 9, np.uint8)
+        n_to, n_m = C.c_int32(-1), C.c_int32(-1)
+        fv = frame.c()
+        check(lib().ydorb_mapdb_search_local_points(self._h, matcher._h, C.byref(fv), C.byref(view), _p(slots), n, _p(skip), float(th), matcher.ratio,
+                                                    _p(taken), _p(assigned), _p(rows), _p(status), C.byref(n_to), C.byref(n_m)))
+        return dict(n_to_match=n_to.value, n_matches=n_m.value, assigned=assigned, taken=taken, rows=rows[:n], status=status[:n])
 
     # ------------------------------------------------------------------------------------------------------------ inspection
     def stats(self):
