@@ -513,6 +513,7 @@ int yo_ba_chol_solve(const double* A, int n, const double* b, double* x) {
   return 1;
 }
 void yo_ba_huber(double e, double delta, double* rho2) { huber(e, delta, rho2, rho2 + 1); }
+}  // extern "C"
 
 // ---- Optimizer::optimizePose (reference src/optimizer.cpp:358-501): pose-only LM on unary edges --------------------------------
 // g2o pieces: EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose (types_six_dof_expmap.h:230-320, .cpp:415-494: the
@@ -521,9 +522,15 @@ void yo_ba_huber(double e, double delta, double* rho2) { huber(e, delta, rho2, r
 // pose7 in/out (tx,ty,tz,qx,qy,qz,qw); Xw [E][3]; meas [E][3] (ur < 0: monocular); info [E]; outlier [E] out.
 // Returns initialCorrespondenceNum - badNum (:500), or 0 without touching anything when E < 3 (:443-445).
 // chi2Log: [4] robust chi2 after each episode's optimize (NaN when the episode did not run).
-int yo_pose_optimize(double* pose7, int E, const double* Xw, const double* meas, const double* info, const double* camera5,
-                     uint8_t* outlier, double* chi2Log, int* trialsOut) {
+// The traced form (yo_pose_optimize_trace, test infrastructure): the same body also records, for every episode that ran, the
+// outlier flags after its classification (flagTrace [4][E]), the float chi2 that classification compared with its threshold
+// (chiTrace [4][E]) and the LM trials made / accepted / made with a failed Cholesky, and whether the last trial was rejected
+// (epiStats [4][4]).  Rows of episodes that did not run are left as the caller filled them.  *episodesOut = the number of episodes that ran.
+static int poseOptimizeBody(double* pose7, int E, const double* Xw, const double* meas, const double* info, const double* camera5,
+                            uint8_t* outlier, double* chi2Log, int* trialsOut, uint8_t* flagTrace, float* chiTrace, int* epiStats,
+                            int* episodesOut) {
   if (trialsOut) *trialsOut = 0;
+  if (episodesOut) *episodesOut = 0;
   for (int k = 0; k < 4; k++) if (chi2Log) chi2Log[k] = std::numeric_limits<double>::quiet_NaN();
   if (E < 3) return 0;
   const Cam cam{camera5[0], camera5[1], camera5[2], camera5[3], camera5[4]};
@@ -593,6 +600,7 @@ int yo_pose_optimize(double* pose7, int E, const double* Xw, const double* meas,
           for (int e : act) errOf(e);
           R tempChi = robustChi2();
           if (!ok) tempChi = std::numeric_limits<R>::max();
+          if (epiStats) { epiStats[4 * epi]++; epiStats[4 * epi + 2] += !ok; }
           rho = currentChi - tempChi;
           R sc = 1e-3;
           for (int j = 0; j < 6; j++) sc += x6[j] * (lambda * x6[j] + b[j]);
@@ -603,9 +611,11 @@ int yo_pose_optimize(double* pose7, int E, const double* Xw, const double* meas,
             lambda *= std::max(1. / 3., alpha);
             ni = 2;
             currentChi = tempChi;
+            if (epiStats) { epiStats[4 * epi + 1]++; epiStats[4 * epi + 3] = 0; }
           } else {
             lambda *= ni; ni *= 2;
             T = bak;
+            if (epiStats) epiStats[4 * epi + 3] = 1;
             if (!std::isfinite(lambda)) { qmax++; trials++; break; }
           }
           qmax++; trials++;
@@ -621,11 +631,25 @@ int yo_pose_optimize(double* pose7, int E, const double* Xw, const double* meas,
       const float th = stereoOf(e) ? 7.815f : 5.991f;
       if (c2 > th) { outlier[e] = 1; level[e] = 1; bad++; } else { outlier[e] = 0; level[e] = 0; }
       if (epi == 2) robust[e] = 0;
+      if (flagTrace) flagTrace[(size_t)epi * E + e] = outlier[e];
+      if (chiTrace) chiTrace[(size_t)epi * E + e] = c2;
     }
+    if (episodesOut) *episodesOut = epi + 1;
     if (E < 10) break;                           // optimizer.edges().size() < 10, :494
   }
   pose7[0] = T.t.x; pose7[1] = T.t.y; pose7[2] = T.t.z; pose7[3] = T.q.x; pose7[4] = T.q.y; pose7[5] = T.q.z; pose7[6] = T.q.w;
   if (trialsOut) *trialsOut = trials;
   return E - bad;
+}
+
+extern "C" {
+int yo_pose_optimize(double* pose7, int E, const double* Xw, const double* meas, const double* info, const double* camera5,
+                     uint8_t* outlier, double* chi2Log, int* trialsOut) {
+  return poseOptimizeBody(pose7, E, Xw, meas, info, camera5, outlier, chi2Log, trialsOut, nullptr, nullptr, nullptr, nullptr);
+}
+int yo_pose_optimize_trace(double* pose7, int E, const double* Xw, const double* meas, const double* info, const double* camera5,
+                           uint8_t* outlier, double* chi2Log, int* trialsOut, uint8_t* flagTrace, float* chiTrace, int* epiStats,
+                           int* episodesOut) {
+  return poseOptimizeBody(pose7, E, Xw, meas, info, camera5, outlier, chi2Log, trialsOut, flagTrace, chiTrace, epiStats, episodesOut);
 }
 }

@@ -371,6 +371,34 @@ def pose_optimize(prob):
     return dict(pose=pose, outlier=outlier[:E], inliers=n, chi2=chi, trials=trials.value)
 
 
+def pose_optimize_trace(prob):
+    """pose_optimize with a per-episode trace (yo_pose_optimize_trace: the same body).  Adds to pose_optimize's dict:
+    episodes (how many ran), flag_trace u8 [episodes, E] (the outlier flags after each episode), chi_trace f32 [episodes, E] (the float
+    chi2 of every edge that the episode's classification compared with 5.991 / 7.815) and epi_trials / epi_accepted / epi_failed_solves
+    i32 [4] (LM trials per episode, those accepted, those whose Cholesky failed) and epi_last_rejected i32 [4] (1: the episode's last
+    trial was rejected, so its active edges kept the error of a pose that was popped)."""
+    pose = np.ascontiguousarray(prob["pose"], np.float64).copy()
+    X = np.ascontiguousarray(prob["points"], np.float64); z = np.ascontiguousarray(prob["meas"], np.float64)
+    w = np.ascontiguousarray(prob["info"], np.float64); cam = np.ascontiguousarray(prob["camera"], np.float64)
+    E = len(w)
+    outlier = np.zeros(max(E, 1), np.uint8)
+    chi = np.zeros(4, np.float64)
+    flags = np.full((4, max(E, 1)), 255, np.uint8)
+    c2 = np.full((4, max(E, 1)), np.nan, np.float32)
+    stats = np.zeros((4, 4), np.int32)
+    trials, episodes = C.c_int(0), C.c_int(0)
+    L = lib()
+    L.yo_pose_optimize_trace.restype = C.c_int
+    n = L.yo_pose_optimize_trace(_p(pose), E, _p(X), _p(z), _p(w), _p(cam), _p(outlier), _p(chi), C.byref(trials), _p(flags), _p(c2), _p(stats),
+                                 C.byref(episodes))
+    k = episodes.value
+    return dict(pose=pose, outlier=outlier[:E], inliers=n, chi2=chi, trials=trials.value, episodes=k,
+                flag_trace=flags[:k, :E].copy() if E else np.zeros((k, 0), np.uint8),
+                chi_trace=c2[:k, :E].copy() if E else np.zeros((k, 0), np.float32),
+                epi_trials=stats[:, 0].copy(), epi_accepted=stats[:, 1].copy(), epi_failed_solves=stats[:, 2].copy(),
+                epi_last_rejected=stats[:, 3].copy())
+
+
 def _stereo_call(kps_l, desc_l, kps_r, desc_r, levels_l, levels_r, scale, inv_scale, bf, b, index_by_keypoint, trace):
     L = lib()
     kl = np.ascontiguousarray(kps_l, KP_DTYPE); kr = np.ascontiguousarray(kps_r, KP_DTYPE)

@@ -8,6 +8,7 @@
 //   adapter_run proj    scenario.bin out.bin     searchByProjectionInLastAndCurrentFrame (orbMatcher.cpp:65-155)
 //   adapter_run bow     scenario.bin out.bin     searchByBowInKeyFrameAndFrame     (orbMatcher.cpp:303-379)
 //   adapter_run extract scenario.bin out.bin     OrbExtractor::extractAndCompute + m_v_imagePyramid (orbExtractor.cpp:355-399)
+//   adapter_run pose    scenario.bin out.bin     Optimizer::optimizePose           (optimizer.cpp:358-501)
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -215,6 +216,29 @@ int runProj(const char* in, const char* out) {
   return 0;
 }
 
+int runPose(const char* in, const char* out) {
+  Reader R(in);
+  readCamera(R);
+  std::vector<float> invSf2(8);
+  R.get(invSf2.data(), 8);
+  const int nMP = R.get<int32_t>();
+  std::vector<std::shared_ptr<MapPoint>> mps(nMP);
+  for (int i = 0; i < nMP; i++) {
+    mps[i] = std::make_shared<MapPoint>();
+    mps[i]->index = i;
+    mps[i]->pos = readMat32(R, 3, 1);
+  }
+  Frame f;
+  readFrame(R, f, mps);
+  f.m_v_invScaleFactorSquares = invSf2;
+  const int n = ydorb::adapter::optimizePoseImpl(f);
+  Writer W(out);
+  W.put<int32_t>(n);
+  for (size_t i = 0; i < f.m_v_isOutliers.size(); i++) W.put<int32_t>(f.m_v_isOutliers[i] ? 1 : 0);
+  W.put(f.m_cvMat_T_c2w.ptr<float>(), 16);
+  return 0;
+}
+
 int runBow(const char* in, const char* out) {
   Reader R(in);
   const int nMP = R.get<int32_t>();
@@ -272,13 +296,14 @@ int runExtract(const char* in, const char* out) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 4) { fprintf(stderr, "usage: adapter_run ba|proj|bow|extract scenario.bin out.bin\n"); return 2; }
+  if (argc != 4) { fprintf(stderr, "usage: adapter_run ba|proj|bow|extract|pose scenario.bin out.bin\n"); return 2; }
   try {
     const std::string what = argv[1];
     if (what == "ba") return runBa(argv[2], argv[3]);
     if (what == "proj") return runProj(argv[2], argv[3]);
     if (what == "bow") return runBow(argv[2], argv[3]);
     if (what == "extract") return runExtract(argv[2], argv[3]);
+    if (what == "pose") return runPose(argv[2], argv[3]);
   } catch (const std::exception& e) {
     fprintf(stderr, "adapter_run: %s\n", e.what());
     return 1;

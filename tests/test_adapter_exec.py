@@ -1,6 +1,6 @@
 """The C++ adapters of include/ydorb/*.hpp EXECUTED (not just parsed): tests/cpp_host/adapter_run.cpp instantiates
-localBundleAdjustImpl (SURVEY 8a rows B0 graph assembly + B10 write-back, optimizer.cpp:138-283, :336-351),
-searchByProjectionInLastAndCurrentFrame (orbMatcher.cpp:65-155), searchByBowInKeyFrameAndFrame (:303-379) and the OrbExtractor class
+localBundleAdjustImpl (SURVEY 8a rows B0 graph assembly + B10 write-back, optimizer.cpp:138-283, :336-351), optimizePoseImpl
+(optimizer.cpp:358-501), searchByProjectionInLastAndCurrentFrame (orbMatcher.cpp:65-155), searchByBowInKeyFrameAndFrame (:303-379) and the OrbExtractor class
 (orbExtractor.cpp:355-399 + the public m_v_imagePyramid) with stand-ins of Frame / KeyFrame / MapPoint / Map that carry real data,
 runs them on the GPU and dumps what they did to those objects.  Here the reference's host-side logic is stated independently in
 numpy (covisibility walk, vertex ids, edge filter, Converter round trips, float projections), the flat problem goes through the
@@ -341,3 +341,70 @@ def test_extractor_adapter_executed(tmp_path):
     levels, kpnum = struct.unpack_from("<2i", out, off); off += 8
     assert levels == 8 and kpnum == 8            # getKeyPointsNum() returns the level count in the reference too (orbExtractor.hpp:42)
     assert np.array_equal(np.frombuffer(out, np.float32, 8, off), ex.tables()["scale"])
+
+
+def _pose_frame_blob(T32, kps, right, mp_of, pts32, inv_s2, cam):
+    n = len(kps)
+    blob = _camera_blob(*[F32(v) for v in cam[:4]], F32(0.08), F32(cam[4]), (0, 640, 0, 480)) + inv_s2.tobytes()
+    blob += struct.pack("<i", len(pts32)) + pts32.tobytes()
+    blob += T32.tobytes() + struct.pack("<i", n) + _kp_blob(kps, np.zeros((n, 32), np.uint8), right)
+    return blob + mp_of.astype(np.int32).tobytes() + np.ones(n, np.int32).tobytes()          # m_v_isOutliers preset true everywhere
+
+
+@pytest.mark.gpu
+def test_optimize_pose_adapter_executed(tmp_path):
+    """optimizePoseImpl (include/ydorb/optimizer.hpp; optimizer.cpp:385-441 host side, :498-500 write-back) on a 400-keypoint frame:
+    about 30 % of the slots hold no map point, m_v_isOutliers is preset true everywhere, octaves 0-7 go through the float table
+    m_v_invScaleFactorSquares, mono (rightX < 0, not only -1) and stereo keypoints are mixed.  The host side restated in numpy - slots
+    with a map point in index order, float -> double, ur < 0 -> mono, the pose through Converter - goes through the ctypes call.
+    Then a frame with two map points: 0 returned, pose unchanged, both flags cleared (:392 runs before the < 3 exit)."""
+    import ydorbslam_amd as y
+    from ydorbslam_amd.synth import synth_pose_problem
+    exe = _build(str(tmp_path))
+    rng = np.random.default_rng(33)
+    N = 400
+    has = rng.random(N) >= 0.3
+    K = int(has.sum())
+    prob = synth_pose_problem(K, seed=33, outlier_frac=0.1, mono_frac=0.3)
+    inv_s2 = (1.0 / np.power(np.float32(1.2), 2 * np.arange(8))).astype(np.float32)
+    perm = rng.permutation(K)                                   # map point index != slot order
+    pts32 = np.zeros((K, 3), np.float32); pts32[perm] = prob["points"].astype(np.float32)
+    mp_of = np.full(N, -1, np.int32); mp_of[has] = perm
+    kps = np.zeros(N, y.KP_DTYPE)
+    kps["x"], kps["y"] = rng.uniform(0, 640, N).astype(np.float32), rng.uniform(0, 480, N).astype(np.float32)
+    kps["x"][has], kps["y"][has] = prob["meas"][:, 0].astype(np.float32), prob["meas"][:, 1].astype(np.float32)
+    kps["octave"] = rng.integers(0, 8, N)
+    right = np.where(rng.random(N) < 0.5, F32(-1), F32(-3.25)).astype(np.float32)
+    ur = prob["meas"][:, 2].astype(np.float32)
+    right[has] = np.where(ur >= 0, ur, right[has])
+    T32 = _se3quat_to_pose(prob["pose"])
+    cam = np.array([F32(v) for v in prob["camera"]], np.float64)
+
+    def flat(slots):                                            # optimizer.cpp:385-441
+        i = np.asarray(slots, np.int64)
+        r = right[i].astype(np.float64)
+        return dict(pose=_pose_to_se3quat(T32), points=pts32[mp_of[i]].astype(np.float64).reshape(-1, 3),
+                    meas=np.stack([kps["x"][i].astype(np.float64), kps["y"][i].astype(np.float64), np.where(r < 0, -1.0, r)], axis=1).reshape(-1, 3),
+                    info=inv_s2[kps["octave"][i]].astype(np.float64), camera=cam)
+
+    out = _run(exe, "pose", _pose_frame_blob(T32, kps, right, mp_of, pts32, inv_s2, cam), str(tmp_path))
+    n_adapter = struct.unpack_from("<i", out, 0)[0]
+    flags = np.frombuffer(out, np.int32, N, 4)
+    T = np.frombuffer(out, np.float32, 16, 4 + 4 * N).reshape(4, 4)
+    assert len(out) == 4 + 4 * N + 64
+    slots = np.flatnonzero(has)
+    ref = y.Optimizer.optimize_poses([flat(slots)])[0]
+    assert 0.25 * N < K < 0.8 * N and (right[slots] < 0).sum() > 20 and (right[slots] >= 0).sum() > 20
+    assert 10 < ref["outlier"].sum() < K // 2                   # both kinds of flag occur at slots with a map point
+    assert n_adapter == ref["inliers"] == K - int(ref["outlier"].sum())
+    assert np.array_equal(flags[slots], ref["outlier"].astype(np.int32))
+    assert (flags[~has] == 1).all()                             # :392 clears only slots with a map point
+    assert np.allclose(T, _se3quat_to_pose(ref["pose"]), rtol=1e-5, atol=1e-6) and not np.array_equal(T, T32)
+
+    two = np.full(N, -1, np.int32)
+    two[slots[[5, 77]]] = mp_of[slots[[5, 77]]]
+    out = _run(exe, "pose", _pose_frame_blob(T32, kps, right, two, pts32, inv_s2, cam), str(tmp_path))
+    flags = np.frombuffer(out, np.int32, N, 4)
+    assert struct.unpack_from("<i", out, 0)[0] == 0
+    assert np.array_equal(np.frombuffer(out, np.float32, 16, 4 + 4 * N).reshape(4, 4), T32)
+    assert not flags[slots[[5, 77]]].any() and flags.sum() == N - 2
