@@ -1289,6 +1289,80 @@ int ydorb_mapdb_search_local_points(ydorb_mapdb_t* db, ydorb_matcher_t* m, const
                                     const int32_t* point_slots, int32_t n, const uint8_t* skip, float th, float ratio, uint8_t* taken,
                                     int32_t* assigned, YdTrackView* rows, uint8_t* status, int32_t* n_to_match, int32_t* n_matches);
 
+/* Resident keyframe features (DESIGN.md section 2 "Fuse search on the resident table", section 6r): one more relation of the resident
+ * table and the query that runs the search of LocalMapping::searchInNeighbors / LoopClosing::searchAndFuse for all targets at once.
+ *   features  keyframe slot -> the keyframe's undistorted keypoints [n_k] (m_v_keyPoints) and right_x [n_k] (m_v_rightXcords), in
+ *             keypoint order: the order and the n_k of the keyframe's descriptor block.  A keyframe's features never change after
+ *             it is made: they go up once.  A span of length 0 erases them.  The pool is counted in features; one span per keyframe
+ *             indexes two device arrays, KeyPoint [n_k] and float [n_k], each contiguous.
+ * The relation is opt-in: a handle that never calls ydorb_mapdb_enable_features allocates nothing for it, launches nothing for it and
+ * every entry below but enable and feat_stats returns YDORB_ERR_INVALID_ARG.  YdMapDbStats, YdMapDbRowStats, YdMapDbDescStats and
+ * YdMapDbAttrStats keep their values either way.  The pool follows the observation pool's policy (append at the tail, a replaced or
+ * erased span becomes garbage, repack in ascending slot order when an append does not fit, same capacity when live + incoming <=
+ * capacity / 2, else 2 x (live + incoming), at most INT32_MAX features); it starts empty-handed and grows on demand.
+ * set_keyframe_features validates and stages and does no device work; the next query or export applies the delta after points, rows,
+ * views and blocks and before the attributes.  A slot named several times between two syncs is applied once, with its last value.
+ * It grows n_keyframes as set_keyframe_rows does.  ydorb_mapdb_clear empties the relation and keeps capacities and counters.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG naming the first offender, before any device work, and stages nothing: null
+ * arrays, a start array that does not begin at 0 or decreases, a negative slot, a span longer than 65535, an octave outside 0..7, a
+ * pool past INT32_MAX features.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdMapDbFeatStats {
+  int32_t enabled;
+  int32_t repacks_kept, repacks_grown;
+  int64_t n_features;                           /* live, staged changes included */
+  int64_t pool_used, pool_capacity;             /* as of the last sync, in features */
+  int64_t last_feat_sync_bytes, last_feat_sync_records;   /* 0 when nothing of this relation was staged */
+} YdMapDbFeatStats;
+/* Turns the relation on; calling it twice is fine. */
+int ydorb_mapdb_enable_features(ydorb_mapdb_t* db);
+/* Replaces the features of each named keyframe: feat_start [n+1], kps [feat_start[n]], right_x [feat_start[n]] or NULL (every entry
+ * is then stored as -1.0f: a monocular keyframe).  A span of length 0 erases them. */
+int ydorb_mapdb_set_keyframe_features(ydorb_mapdb_t* db, const int32_t* kf_slots, int32_t n, const int32_t* feat_start,
+                                      const YdKeyPoint* kps, const float* right_x);
+/* Reads the device's features back (after applying what is staged): feat_start [n_keyframes+1], kps / right_x [n_features]. */
+int ydorb_mapdb_export_features(ydorb_mapdb_t* db, int32_t* feat_start, YdKeyPoint* kps, float* right_x);
+int ydorb_mapdb_feat_stats(ydorb_mapdb_t* db, YdMapDbFeatStats* stats);
+
+/* OrbMatcher::fuseByProjection / fuseBySim3 for several target keyframes in one call (DESIGN.md section 2 "Fuse search on the resident
+ * table" fixes the fp32 operation order): per (target, listed point) the predicates of pass 1 on the resident position, normal and
+ * raw distances, then the window search of ydorb_fuse_search / ydorb_window_search on the target's resident features and descriptor
+ * block with the point's resident descriptor.  What travels up is the targets, the list starts, the slots and the skip bytes. */
+typedef struct YdFuseTarget {
+  int32_t kf_slot;          /* the target keyframe: its features and its descriptor block are read by slot */
+  YdFrustumView view;       /* Rcw, tcw, Ow, intrinsics, bounds, n_levels, level_ratio, scale_factors (viewing_cos_limit unused) */
+  float inv_sigma2[8];      /* m_v_invScaleFactorSquares; all zero disables the chi-square test (fuseBySim3) */
+  float th;
+  int32_t max_dist;         /* 50 for both fuse forms */
+  int32_t flags;            /* bit 0: skip a point the target already observes (isInKeyFrame, fuseByProjection);
+                               bit 1: ignore right_x, every feature takes the monocular branch (fuseBySim3) */
+} YdFuseTarget;
+#define YDORB_FUSE_SKIP_OBSERVED 1
+#define YDORB_FUSE_MONOCULAR 2
+/* status byte of a list entry: the first rule that fires, in this order; every status but 0 searches nothing (best_idx -1) */
+#define YDORB_FUSE_SEARCHED 0       /* every predicate held: the window was searched */
+#define YDORB_FUSE_SKIPPED 1        /* the caller's skip byte */
+#define YDORB_FUSE_BAD 2            /* the resident bad flag is set (a slot never set included) */
+#define YDORB_FUSE_OBSERVED 3       /* flag bit 0 and the point's resident observation span holds kf_slot */
+#define YDORB_FUSE_NO_ATTRIBUTES 4  /* the geometry flag or the descriptor flag of the attribute record is unset */
+#define YDORB_FUSE_REJECTED 5       /* zc >= 0, inside the image (half open), distance range and viewing angle: one does not hold; a NaN is rejected */
+/* target_status */
+#define YDORB_FUSE_TARGET_OK 0
+#define YDORB_FUSE_TARGET_NO_FEATURES 1      /* the keyframe has no feature span */
+#define YDORB_FUSE_TARGET_NO_BLOCK 2         /* ... no descriptor block */
+#define YDORB_FUSE_TARGET_LENGTH_MISMATCH 3  /* the two lengths differ */
+/* targets [n_targets], list_start [n_targets+1]; with L = list_start[n_targets]: point_slots / skip / best_idx / status [L]; n_found
+ * and target_status [n_targets].  Target t tests the points point_slots[list_start[t] .. list_start[t+1]).  best_idx[e] = the
+ * feature of the target the point matched, or -1; n_found[t] = the matches of target t.  A target with a non-zero target_status has
+ * all best_idx -1 and n_found 0 (its status bytes are the predicates' as usual, nothing is searched); the call still returns YDORB_OK.  A slot may repeat within a
+ * list and across lists.  The call is synchronous and exact: when the candidate records overflow their pool it grows and the search
+ * is replayed.  Refused up front: null arguments, a malformed list_start, a point slot outside 0..n_points-1, a kf_slot outside
+ * 0..n_keyframes-1, n_levels outside 1..8, max_dist outside 0..256, attributes or features not enabled, db and m on different
+ * devices.  L == 0 launches nothing. */
+int ydorb_mapdb_fuse_search(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdFuseTarget* targets, int32_t n_targets,
+                            const int32_t* list_start, const int32_t* point_slots, const uint8_t* skip, int32_t* best_idx,
+                            uint8_t* status, int32_t* n_found, uint8_t* target_status);
+
 #ifdef __cplusplus
 }
 #endif

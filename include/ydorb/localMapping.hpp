@@ -26,6 +26,7 @@
 #include "c_api.h"
 #include "mapPoint.hpp"
 #include "orbMatcher.hpp"
+#include "tracking.hpp"   // levelRatioTable, which orbMatcher.hpp's fuse overloads over a mirror call
 
 namespace ydorb {
 namespace adapter {
@@ -217,6 +218,58 @@ inline std::vector<KeyFramePtr> keyFrameCullingImpl(const KeyFramePtr& current, 
     at += k;
   }
   return flagged;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Drop-in body of LocalMapping::searchInNeighbors (ORB-SLAM2 LocalMapping::SearchInNeighbors) over a resident map table (mapMirror.hpp
+// with enableAttributes(), enableFeatures() and enableDescriptors()):
+//   void LocalMapping::searchInNeighbors()
+//   { ydorb::adapter::searchInNeighborsImpl<Frame, std::shared_ptr<KeyFrame>, std::shared_ptr<MapPoint>>(*m_mirror, ydorb::adapter::matcher(),
+//       m_sptr_currentKeyFrame, m_b_isMonocular ? 20 : 10, storeDescriptor, storeNormalAndDepth); }
+// The targets are collected as the reference collects them (the best covisible keyframes and five of each one's, marked with
+// m_int_fuseTargetForKeyFrameID).  Then TWO batched calls where the reference makes one fuse call per target and one more:
+//   direction 1  the current keyframe's map points into every target: fuseByProjection(mirror, m, targets, ...), one list per target;
+//   direction 2  the targets' map points (each once, marked with m_int_fuseCandidateForKeyFrameID, bad ones left out) into the
+//                current keyframe: the same overload with one target.  Its flush carries what direction 1 changed.
+// The tail - computeDistinctiveDescriptors() and updateNormalAndDepth() of the current keyframe's points - goes through the mirror's
+// two methods, whose write-through keeps the resident attributes current; storeDescriptor(mp, kf, idx, row) and
+// storeNormalAndDepth(mp, normal, minDistance, maxDistance) store the results in the objects (INTEGRATION.md shows both).  The
+// keyframe's updateConnections() stays the caller's last line.  Returns the fuse counts of direction 1 (per target) and direction 2.
+// Additional assumed spellings: KeyFrame getBestCovisibilityKeyFrames(n), m_int_fuseTargetForKeyFrameID, m_int_keyFrameID, isBad(),
+// getMapPointMatches(), m_flt_logScaleFactor, the static m_flt_minX .. m_flt_maxY; MapPoint m_int_fuseCandidateForKeyFrameID.
+template <class FrameT, class KeyFramePtr, class MapPointPtr, class Mirror, class StoreDescriptor, class StoreNormalDepth>
+inline std::pair<std::vector<int>, int> searchInNeighborsImpl(Mirror& mirror, ydorb_matcher_t* m, KeyFramePtr current, int nn, StoreDescriptor storeDescriptor,
+                                                              StoreNormalDepth storeNormalAndDepth, float th = 3.0f) {
+  std::vector<KeyFramePtr> targets;
+  for (const KeyFramePtr& kf : current->getBestCovisibilityKeyFrames(nn)) {
+    if (kf->isBad() || kf->m_int_fuseTargetForKeyFrameID == current->m_int_keyFrameID) continue;
+    targets.push_back(kf);
+    kf->m_int_fuseTargetForKeyFrameID = current->m_int_keyFrameID;
+    for (const KeyFramePtr& kf2 : kf->getBestCovisibilityKeyFrames(5)) {
+      if (kf2->isBad() || kf2->m_int_fuseTargetForKeyFrameID == current->m_int_keyFrameID || kf2->m_int_keyFrameID == current->m_int_keyFrameID) continue;
+      targets.push_back(kf2);
+      kf2->m_int_fuseTargetForKeyFrameID = current->m_int_keyFrameID;   // ORB-SLAM2 leaves this mark out and may list a keyframe twice; a second pass over it fuses nothing new
+    }
+  }
+  std::pair<std::vector<int>, int> fused(std::vector<int>(), 0);
+  if (targets.empty()) return fused;
+  const std::vector<MapPointPtr> own = current->getMapPointMatches();
+  fused.first = fuseByProjection<KeyFramePtr, MapPointPtr, FrameT>(mirror, m, targets, std::vector<std::vector<MapPointPtr> >(targets.size(), own), th);
+  std::vector<MapPointPtr> candidates;
+  for (const KeyFramePtr& kf : targets)
+    for (const MapPointPtr& mp : kf->getMapPointMatches()) {
+      if (!mp || mp->isBad() || mp->m_int_fuseCandidateForKeyFrameID == current->m_int_keyFrameID) continue;
+      mp->m_int_fuseCandidateForKeyFrameID = current->m_int_keyFrameID;
+      candidates.push_back(mp);
+    }
+  fused.second = fuseByProjection<KeyFramePtr, MapPointPtr, FrameT>(mirror, m, std::vector<KeyFramePtr>(1, current),
+                                                                     std::vector<std::vector<MapPointPtr> >(1, candidates), th)[0];
+  std::vector<MapPointPtr> live;
+  for (const MapPointPtr& mp : current->getMapPointMatches())
+    if (mp && !mp->isBad()) live.push_back(mp);
+  mirror.computeDistinctiveDescriptors(live, storeDescriptor);
+  mirror.updateNormalAndDepth(live, storeNormalAndDepth);
+  return fused;
 }
 
 }  // namespace adapter

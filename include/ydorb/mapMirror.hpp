@@ -27,6 +27,11 @@
 // searchLocalPointsImpl(Mirror&, ...)); verifyAttributes() is verify() for them.  Assumed spellings beyond the others: MapPoint
 // getNormal(), getDescriptor() and two one-line getters of the RAW members, getMinDistance() { lock; return m_flt_minDistance; } and
 // getMaxDistance() { lock; return m_flt_maxDistance; } (tracking.hpp requires the second already).
+// enableFeatures() adds the keyframes' undistorted keypoints and right coordinates: touchFeatures(kf) once per
+// keyframe, next to touchDescriptors(kf); forget(kf) erases the span; fuseSearch is the search of OrbMatcher::fuseByProjection /
+// fuseBySim3 for several target keyframes in ONE call (orbMatcher.hpp's overloads over a mirror run the bookkeeping on its result);
+// verifyFeatures() is verify() for them.  It needs enableAttributes() too.  Assumed spellings beyond the others: KeyFrame m_v_keyPoints
+// (the undistorted keypoints, cv::KeyPoint) and m_v_rightXcords, of one length with m_cvMat_descriptors' rows.
 // Assumed spellings: those of mapPoint.hpp; m_cvMat_descriptors (one CV_8U row of 32 bytes per keypoint) for the blocks, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
 // MapPoint::setPosInWorld(cv::Mat), m_int_correctedByKeyFrameID, m_int_correctedReference and the Sim3 members rotation().x() .. w(),
 // translation()[k], scale().  The camera centre after a corrected pose is not read from a member: correctLoopPoints computes it from
@@ -98,6 +103,16 @@ class MapMirror {
   void touchAttributes(const MapPointPtr& mp) {
     mark(attrDirty_, dirtyAttrs_, known(mp), kFull);
   }
+  // Resident keyframe features: fuseSearch below reads a target keyframe's keypoints, right coordinates and
+  // descriptor block by slot.  Enable it, and the attributes, before the first touch.
+  void enableFeatures() {
+    mapCheck(ydorb_mapdb_enable_features(db_));
+    features_ = true;
+  }
+  bool featuresEnabled() const { return features_; }
+  // re-reads m_v_keyPoints and m_v_rightXcords at the next flush: once per keyframe, they never change; again after setBadFlag(), whose
+  // isBad() erases the span (or forget(kf))
+  void touchFeatures(const KeyFramePtr& kf) { mark(featDirty_, dirtyFeats_, kfSlotFor(kf), kFull); }
   void touchRow(const KeyFramePtr& kf) { markRow(kfSlotFor(kf)); }
   void touchEntry(const KeyFramePtr& kf, size_t idx) {
     const int32_t s = kfSlotFor(kf);
@@ -110,6 +125,7 @@ class MapMirror {
     kfOf_[it->second] = KeyFramePtr();
     if (rowSent_[it->second]) markRow(it->second);   // the next flush empties the row, or writes the row of the keyframe that took the slot since
     if (descSent_[it->second]) mark(descDirty_, dirtyDescs_, it->second, kFull);   // ... and the block
+    if (featSent_[it->second]) mark(featDirty_, dirtyFeats_, it->second, kFull);   // ... and the features
     freeKfs_.push_back(it->second);
     kfSlot_.erase(it);
   }
@@ -119,6 +135,7 @@ class MapMirror {
     kfSlot_.clear(); kfOf_.clear(); freeKfs_.clear(); kfDirty_.clear(); dirtyKfs_.clear();
     rowDirty_.clear(); rowSent_.clear(); dirtyRows_.clear(); dirtyEntries_.clear();
     descDirty_.clear(); descSent_.clear(); dirtyDescs_.clear();
+    featDirty_.clear(); featSent_.clear(); dirtyFeats_.clear();
     attrDirty_.clear(); dirtyAttrs_.clear(); erasePending_.clear();
   }
 
@@ -217,6 +234,24 @@ class MapMirror {
       desc.resize(desc.size() + 32);   // never a null pointer
       if (!ks.empty()) mapCheck(ydorb_mapdb_set_keyframe_descriptors(db_, ks.data(), (int32_t)ks.size(), descStart.data(), desc.data()));
     }
+    if (!dirtyFeats_.empty()) {   // after the blocks: a query reads a keyframe's features and its block together
+      std::vector<int32_t> ks, featStart{0};
+      std::vector<YdKeyPoint> kps;
+      std::vector<float> rightX;
+      for (const int32_t k : dirtyFeats_) {
+        featDirty_[k] = kClean;
+        const bool live = kfOf_[k] && !kfOf_[k]->isBad();
+        if (!live && !featSent_[k]) continue;
+        ks.push_back(k);
+        if (live) appendFeatures(kfOf_[k], kps, rightX);
+        if (kps.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX features in one flush");
+        featStart.push_back((int32_t)kps.size());
+        featSent_[k] = live ? 1 : 0;
+      }
+      dirtyFeats_.clear();
+      kps.resize(kps.size() + 1); rightX.resize(rightX.size() + 1);   // never a null pointer
+      if (!ks.empty()) mapCheck(ydorb_mapdb_set_keyframe_features(db_, ks.data(), (int32_t)ks.size(), featStart.data(), kps.data(), rightX.data()));
+    }
     if (descriptors_ && !slots.empty()) {
       viewKf.push_back(0); viewIdx.push_back(0);
       mapCheck(ydorb_mapdb_set_point_views(db_, slots.data(), (int32_t)slots.size(), viewStart.data(), viewKf.data(), viewIdx.data()));
@@ -264,6 +299,86 @@ class MapMirror {
                                              rows.data(), status.data(), &nToMatch, &nMatches));
     rows.resize(n); status.resize(n);
     return nMatches;
+  }
+
+  // The search of OrbMatcher::fuseByProjection / fuseBySim3 for several target keyframes in one call (ydorb_mapdb_fuse_search): target
+  // t searches points[t] in keyFrames[t].  targets[t] holds the view, sigma table, th, max_dist and flags (orbMatcher.hpp's fuseTarget
+  // builds it); its kf_slot is set here.  skip[t][i] = the caller's byte for points[t][i]; a null entry is skipped whatever its byte.
+  // A keyframe the table holds no features or block of is read now.  Resolves pointers to slots, flushes, makes the one call.
+  struct FuseResult {
+    std::vector<std::vector<int32_t> > best;      // per target and list entry: the keyframe's feature index, or -1
+    std::vector<std::vector<uint8_t> > status;    // YDORB_FUSE_*
+    std::vector<int32_t> nFound;
+    std::vector<uint8_t> targetStatus;            // YDORB_FUSE_TARGET_*
+  };
+  FuseResult fuseSearch(ydorb_matcher_t* matcher, const std::vector<KeyFramePtr>& keyFrames, std::vector<YdFuseTarget>& targets,
+                        const std::vector<std::vector<MapPointPtr> >& points, const std::vector<std::vector<uint8_t> >& skip) {
+    if (!attributes_ || !features_) throw std::runtime_error("ydorb: fuseSearch without enableAttributes() and enableFeatures()");
+    const size_t nt = keyFrames.size();
+    if (targets.size() != nt || points.size() != nt || skip.size() != nt) throw std::runtime_error("ydorb: fuseSearch: one target, list and skip list per keyframe");
+    std::vector<int32_t> listStart(1, 0), slots;
+    std::vector<uint8_t> sk;
+    std::vector<std::vector<int32_t> > at(nt);   // per target: the list index of each entry sent (null entries are not sent)
+    for (size_t t = 0; t < nt; t++) {
+      const int32_t k = kfSlotFor(keyFrames[t]);
+      targets[t].kf_slot = k;
+      if (!featSent_[k]) mark(featDirty_, dirtyFeats_, k, kFull);
+      if (!descSent_[k]) mark(descDirty_, dirtyDescs_, k, kFull);
+      for (size_t i = 0; i < points[t].size(); i++) {
+        if (!points[t][i]) continue;
+        slots.push_back(known(points[t][i]));
+        sk.push_back(i < skip[t].size() ? skip[t][i] : 0);
+        at[t].push_back((int32_t)i);
+      }
+      if (slots.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX fuse entries");
+      listStart.push_back((int32_t)slots.size());
+    }
+    flush();
+    FuseResult r;
+    r.nFound.assign(nt + 1, 0); r.targetStatus.assign(nt + 1, 0);
+    const size_t L = slots.size();
+    std::vector<int32_t> best(L + 1, -1);
+    std::vector<uint8_t> status(L + 1, YDORB_FUSE_SKIPPED);
+    slots.resize(L + 1); sk.resize(L + 1);
+    if (nt > 0)
+      mapCheck(ydorb_mapdb_fuse_search(db_, matcher, targets.data(), (int32_t)nt, listStart.data(), slots.data(), sk.data(), best.data(), status.data(),
+                                       r.nFound.data(), r.targetStatus.data()));
+    r.nFound.resize(nt); r.targetStatus.resize(nt);
+    r.best.resize(nt); r.status.resize(nt);
+    for (size_t t = 0; t < nt; t++) {
+      r.best[t].assign(points[t].size(), -1); r.status[t].assign(points[t].size(), YDORB_FUSE_SKIPPED);
+      for (size_t j = 0; j < at[t].size(); j++) {
+        r.best[t][(size_t)at[t][j]] = best[(size_t)listStart[t] + j];
+        r.status[t][(size_t)at[t][j]] = status[(size_t)listStart[t] + j];
+      }
+    }
+    return r;
+  }
+
+  // Flushes and compares every known keyframe's m_v_keyPoints and m_v_rightXcords with the device's features
+  // (ydorb_mapdb_export_features): the keyframe slots that differ.  Empty when every keyframe was touched.
+  std::vector<int32_t> verifyFeatures() {
+    flush();
+    YdMapDbStats st;
+    YdMapDbFeatStats fs;
+    mapCheck(ydorb_mapdb_stats(db_, &st));
+    mapCheck(ydorb_mapdb_feat_stats(db_, &fs));
+    const size_t nk = (size_t)st.n_keyframes;
+    std::vector<int32_t> start(nk + 1);
+    std::vector<YdKeyPoint> kps((size_t)fs.n_features + 1);
+    std::vector<float> rightX((size_t)fs.n_features + 1);
+    mapCheck(ydorb_mapdb_export_features(db_, start.data(), kps.data(), rightX.data()));
+    std::vector<int32_t> differ;
+    for (size_t k = 0; k < kfOf_.size(); k++) {
+      std::vector<YdKeyPoint> wantKps;
+      std::vector<float> wantRx;
+      if (kfOf_[k] && featSent_[k] && !kfOf_[k]->isBad()) appendFeatures(kfOf_[k], wantKps, wantRx);
+      const size_t len = k < nk ? (size_t)(start[k + 1] - start[k]) : 0;
+      if (len != wantKps.size() || (len > 0 && (std::memcmp(&kps[(size_t)start[k]], wantKps.data(), sizeof(YdKeyPoint) * len) != 0 ||
+                                                 std::memcmp(&rightX[(size_t)start[k]], wantRx.data(), 4 * len) != 0)))
+        differ.push_back((int32_t)k);
+    }
+    return differ;
   }
 
   // Flushes and compares every known point's getNormal(), getMinDistance(), getMaxDistance() and getDescriptor() with the device's
@@ -788,6 +903,7 @@ class MapMirror {
       s = (int32_t)kfOf_.size();
       kfOf_.push_back(KeyFramePtr()); kfDirty_.push_back(kClean); rowDirty_.push_back(kClean); rowSent_.push_back(0);
       descDirty_.push_back(kClean); descSent_.push_back(0);
+      featDirty_.push_back(kClean); featSent_.push_back(0);
     }
     kfOf_[s] = kf;
     kfSlot_[kf] = s;
@@ -840,6 +956,15 @@ class MapMirror {
   template <class K>
   static void appendDescriptorsOf(const K&, std::vector<uint8_t>&, long) { throw std::runtime_error("ydorb: the keyframe type has no m_cvMat_descriptors"); }
   static void appendDescriptors(const KeyFramePtr& kf, std::vector<uint8_t>& to) { appendDescriptorsOf(kf, to, 0); }
+  // m_v_keyPoints and m_v_rightXcords of one keyframe
+  static void appendFeatures(const KeyFramePtr& kf, std::vector<YdKeyPoint>& kps, std::vector<float>& rightX) {
+    static_assert(sizeof(cv::KeyPoint) == sizeof(YdKeyPoint), "cv::KeyPoint layout");
+    const size_t n = kf->m_v_keyPoints.size(), at = kps.size();
+    if (kf->m_v_rightXcords.size() != n) throw std::runtime_error("ydorb: m_v_rightXcords and m_v_keyPoints differ in length");
+    kps.resize(at + n);
+    if (n) std::memcpy(&kps[at], kf->m_v_keyPoints.data(), sizeof(YdKeyPoint) * n);
+    rightX.insert(rightX.end(), kf->m_v_rightXcords.begin(), kf->m_v_rightXcords.end());
+  }
   // getNormal() (3x1 CV_32F), the raw getMinDistance() / getMaxDistance() and getDescriptor() (1x32 CV_8U) of one point, each group
   // appended only when its matrix is not empty (the member is set).  Chosen by
   // overload so that a map-point type without them still builds the mirror (it cannot touch attributes).
@@ -883,6 +1008,9 @@ class MapMirror {
   bool descriptors_ = false;
   std::vector<uint8_t> descDirty_, descSent_;   // per keyframe slot: the block is re-read at the next flush / the table holds a block of it
   std::vector<int32_t> dirtyDescs_;
+  bool features_ = false;
+  std::vector<uint8_t> featDirty_, featSent_;   // per keyframe slot: the features are re-read at the next flush / the table holds features of it
+  std::vector<int32_t> dirtyFeats_;
   bool attributes_ = false;
   std::vector<uint8_t> attrDirty_;   // per point slot: the attributes are re-read at the next flush
   std::vector<uint8_t> erasePending_;   // per point slot: forgotten with attributes enabled, and the erased record has not gone yet

@@ -390,6 +390,125 @@ int fuseBySim3(ydorb_matcher_t* m, KeyFramePtr kf, const cv::Mat& S, const std::
   return fuseNum;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The two fuse forms over a resident map table (mapMirror.hpp with enableAttributes() and enableFeatures()):
+// passes 1 and 2 of ALL targets are ONE Mirror::fuseSearch call - the predicates run on the device on the resident position, normal,
+// raw distances and descriptor, the search on the resident features and descriptor block of each target - and pass 3 then runs target
+// by target in the caller's order, unchanged.  Pass 3 evaluates isBad() / isInKeyFrame() again at each entry's turn, as the flat forms
+// do, so what an earlier target's bookkeeping changed is seen by the later ones.  ONE difference from a loop of flat calls remains and is
+// the caller's to weigh: all targets are searched with the points' descriptors as of the call, while in the loop a point that survived
+// a replacement at target t (MapPoint::replace ends in computeDistinctiveDescriptors) is searched at target t + 1 with its new
+// descriptor.  Positions, normals and distances are not written by pass 3, so the predicates agree.  After every replacement or added observation the mirror is touched (touch(mp), touchEntry(kf, idx)), so that the
+// next call - the other direction of searchInNeighbors - sees it through its flush.  replace(mp, by) is how the caller's MapPoint
+// replaces a point (mp->beReplacedBy(by)); it is a parameter because that member also walks keyframes the mirror must be told of: the
+// default touches both points and every keyframe entry the replaced point held.
+// levelRatioTable is tracking.hpp's, which includes this header: include tracking.hpp (localMapping.hpp does) where these are used.
+inline void levelRatioTable(float logScaleFactor, int nLevels, float* out);
+
+// one target keyframe of a Mirror::fuseSearch call: pose (Rcw, tcw, Ow as the flat form reads them), intrinsics and bounds of the
+// keyframe type's statics, the pyramid; sim3 = the fuseBySim3 form (no isInKeyFrame, no chi-square test, monocular branch)
+template <class FrameT, class KeyFramePtr>
+inline YdFuseTarget fuseTarget(const KeyFramePtr& kf, const cv::Mat& Rcw, const cv::Mat& tcw, const cv::Mat& Ow, float th, bool sim3) {
+  typedef typename std::remove_reference<decltype(*kf)>::type KeyFrameT;
+  YdFuseTarget G;
+  std::memset(&G, 0, sizeof G);
+  YdFrustumView& v = G.view;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) v.Rcw[3 * r + c] = Rcw.template at<float>(r, c);
+    v.tcw[r] = tcw.template at<float>(r);
+    v.Ow[r] = Ow.template at<float>(r);
+  }
+  v.fx = FrameT::m_flt_fx; v.fy = FrameT::m_flt_fy; v.cx = FrameT::m_flt_cx; v.cy = FrameT::m_flt_cy; v.bf = FrameT::m_flt_baseLineTimesFx;
+  v.min_x = KeyFrameT::m_flt_minX; v.max_x = KeyFrameT::m_flt_maxX; v.min_y = KeyFrameT::m_flt_minY; v.max_y = KeyFrameT::m_flt_maxY;
+  v.n_levels = (int32_t)kf->m_v_scaleFactors.size();
+  if (v.n_levels < 1 || v.n_levels > 8) throw std::runtime_error("ydorb: 1..8 pyramid levels are supported");
+  levelRatioTable(kf->m_flt_logScaleFactor, v.n_levels, v.level_ratio);
+  for (int k = 0; k < v.n_levels; k++) v.scale_factors[k] = kf->m_v_scaleFactors[k];
+  if (!sim3)
+    for (int k = 0; k < 8 && k < (int)kf->m_v_invScaleFactorSquares.size(); k++) G.inv_sigma2[k] = kf->m_v_invScaleFactorSquares[k];
+  G.th = th;
+  G.max_dist = 50;
+  G.flags = sim3 ? YDORB_FUSE_MONOCULAR : YDORB_FUSE_SKIP_OBSERVED;
+  return G;
+}
+
+// mp->beReplacedBy(by) with the touches the mirror needs: both points, and every keyframe entry the replaced point held
+template <class Mirror, class MapPointPtr>
+inline void replaceAndTouch(Mirror& mirror, const MapPointPtr& mp, const MapPointPtr& by) {
+  const auto held = mp->getObservations();
+  mp->beReplacedBy(by);
+  for (const auto& ob : held) mirror.touchEntry(ob.first, (size_t)ob.second);
+  mirror.touch(mp);
+  mirror.touch(by);
+}
+
+// fuseByProjection for several keyframes: returns the fuse count of each, in order
+template <class KeyFramePtr, class MapPointPtr, class FrameT, class Mirror>
+std::vector<int> fuseByProjection(Mirror& mirror, ydorb_matcher_t* m, const std::vector<KeyFramePtr>& kfs, const std::vector<std::vector<MapPointPtr> >& mps, float th) {
+  std::vector<YdFuseTarget> targets;
+  for (const KeyFramePtr& kf : kfs)
+    targets.push_back(fuseTarget<FrameT>(kf, kf->getRotation_c2w(), kf->getTranslation_c2w(), kf->getCameraOriginInWorld(), th, false));
+  const std::vector<std::vector<uint8_t> > skip(kfs.size());
+  const typename Mirror::FuseResult r = mirror.fuseSearch(m, kfs, targets, mps, skip);
+  std::vector<int> fused(kfs.size(), 0);
+  for (size_t t = 0; t < kfs.size(); t++) {
+    const KeyFramePtr& kf = kfs[t];
+    for (size_t i = 0; i < mps[t].size(); i++) {
+      const MapPointPtr& mp = mps[t][i];
+      if (r.best[t][i] < 0 || r.status[t][i] != YDORB_FUSE_SEARCHED || mp->isBad() || mp->isInKeyFrame(kf)) continue;
+      const int idx = r.best[t][i];
+      MapPointPtr inKF = kf->getMapPoint(idx);
+      if (inKF) {
+        if (!inKF->isBad() && inKF->getObservationsNum() > mp->getObservationsNum()) replaceAndTouch(mirror, mp, inKF);
+        else if (!inKF->isBad() && inKF->getObservationsNum() <= mp->getObservationsNum()) replaceAndTouch(mirror, inKF, mp);
+      } else {
+        mp->addObservation(kf, idx);
+        kf->addMapPoint(mp, idx);
+        mirror.touch(mp);
+        mirror.touchEntry(kf, (size_t)idx);
+      }
+      fused[t]++;
+    }
+  }
+  return fused;
+}
+
+// fuseBySim3 for several keyframes, each with its own Sim3 (LoopClosing::searchAndFuse): returns the fuse count of each, in order.
+// The found-set of each keyframe is a snapshot taken before the call, as in the reference; it travels as the skip byte.
+template <class KeyFramePtr, class MapPointPtr, class FrameT, class Mirror>
+std::vector<int> fuseBySim3(Mirror& mirror, ydorb_matcher_t* m, const std::vector<KeyFramePtr>& kfs, const std::vector<cv::Mat>& sims,
+                            const std::vector<std::vector<MapPointPtr> >& mps, float th) {
+  std::vector<YdFuseTarget> targets;
+  std::vector<std::vector<uint8_t> > skip(kfs.size());
+  for (size_t t = 0; t < kfs.size(); t++) {
+    const SimProjection P(sims[t]);
+    targets.push_back(fuseTarget<FrameT>(kfs[t], P.R, P.t, P.Ow, th, true));
+    const std::set<MapPointPtr> found = kfs[t]->getMatchedMapPointsSet();
+    skip[t].assign(mps[t].size(), 0);
+    for (size_t i = 0; i < mps[t].size(); i++) skip[t][i] = mps[t][i] && found.count(mps[t][i]) ? 1 : 0;
+  }
+  const typename Mirror::FuseResult r = mirror.fuseSearch(m, kfs, targets, mps, skip);
+  std::vector<int> fused(kfs.size(), 0);
+  for (size_t t = 0; t < kfs.size(); t++) {
+    const KeyFramePtr& kf = kfs[t];
+    for (size_t i = 0; i < mps[t].size(); i++) {
+      if (r.best[t][i] < 0 || r.status[t][i] != YDORB_FUSE_SEARCHED || mps[t][i]->isBad()) continue;
+      const int idx = r.best[t][i];
+      MapPointPtr inKF = kf->getMapPoint(idx);
+      if (inKF) {
+        if (!inKF->isBad()) replaceAndTouch(mirror, mps[t][i], inKF);
+      } else {
+        mps[t][i]->addObservation(kf, idx);
+        kf->addMapPoint(mps[t][i], idx);
+        mirror.touch(mps[t][i]);
+        mirror.touchEntry(kf, (size_t)idx);
+      }
+      fused[t]++;
+    }
+  }
+  return fused;
+}
+
 // searchBySim3, src/orbMatcher.cpp:566-681.  As written, the reference projects with the keyframes' own poses (the Sim3 products of :572-574
 // are computed and never used), each direction is an independent window search (level window, best distance <= TH_HIGH, nothing taken),
 // and a pair is kept when the two directions agree (:668-679).  Two ydorb_window_search calls + the agreement loop.

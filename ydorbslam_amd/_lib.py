@@ -155,6 +155,11 @@ SYMBOLS = {
     "ydorb_mapdb_frustum_cull": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ydorb_mapdb_search_local_points": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP, C.POINTER(_I),
                                                   C.POINTER(_I)]),
+    "ydorb_mapdb_enable_features": (C.c_int, [_VP]),
+    "ydorb_mapdb_set_keyframe_features": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP]),
+    "ydorb_mapdb_export_features": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_feat_stats": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_fuse_search": (C.c_int, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -259,6 +264,15 @@ class YdMapDbDescStats(C.Structure):
 class YdMapDbAttrStats(C.Structure):
     _fields_ = [("enabled", _I), ("growths", _I), ("capacity", C.c_int64), ("last_attr_sync_bytes", C.c_int64),
                 ("last_attr_sync_records", C.c_int64), ("last_write_through_records", C.c_int64)]
+
+
+class YdMapDbFeatStats(C.Structure):
+    _fields_ = [("enabled", _I), ("repacks_kept", _I), ("repacks_grown", _I), ("n_features", C.c_int64), ("pool_used", C.c_int64),
+                ("pool_capacity", C.c_int64), ("last_feat_sync_bytes", C.c_int64), ("last_feat_sync_records", C.c_int64)]
+
+
+class YdFuseTarget(C.Structure):
+    _fields_ = [("kf_slot", _I), ("view", YdFrustumView), ("inv_sigma2", C.c_float * 8), ("th", C.c_float), ("max_dist", _I), ("flags", _I)]
 
 
 class YdMapCorrection(C.Structure):

@@ -11,6 +11,8 @@
 // synced after the rows through the same syncSpans: ydorb_mapdb_distinctive_descriptors below.
 // The point attributes (mapdb_attr_host.h, mapdb_attr_kernels.hip.h) are an opt-in fifth, synced last; three
 // queries write their results through to them, and ydorb_mapdb_frustum_cull / lockResident at the end of this file read them by slot.
+// The keyframe features (mapdb_feat_host.h, mapdb_feat_kernels.hip.h) are an opt-in sixth span relation, synced
+// after the blocks and before the attributes; lockResidentFuse hands them and the blocks to ydorb_mapdb_fuse_search (orb_matcher.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -27,6 +29,8 @@
 #include "mapdb_attr_kernels.hip.h"
 #include "mapdb_desc_host.h"
 #include "mapdb_desc_kernels.hip.h"
+#include "mapdb_feat_host.h"
+#include "mapdb_feat_kernels.hip.h"
 #include "mapdb_frustum_kernels.hip.h"
 #include "mapdb_host.h"
 #include "mapdb_kernels.hip.h"
@@ -71,7 +75,14 @@ struct ydorb_mapdb {
   Mem attrMem;
   DeltaPair attrDelta;
   mapdb::AttrArrays A{};
-  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc) {}
+  // keyframe features: nothing of this is allocated or launched until ydorb_mapdb_enable_features.  One arena
+  // of 32 bytes per pool entry: KeyPoint [cap] at featPool, right_x [cap] behind it (featRightX)
+  mapdb::FeatHost feat;
+  Mem featHdr, featPoolMem;
+  DeltaPair featDelta;
+  int *featStart = nullptr, *featLen = nullptr;
+  mapdb::FeatRec* featPool = nullptr;
+  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc), feat(kc) {}
 };
 
 namespace {
@@ -266,6 +277,31 @@ int syncDescriptors(ydorb_mapdb* h) {
     });
 }
 
+// The two arrays of a feature arena of `cap` pool entries (mapdb_feat_host.h)
+uint32_t* featKps(mapdb::FeatRec* pool) { return reinterpret_cast<uint32_t*>(pool); }
+uint32_t* featRightX(mapdb::FeatRec* pool, int64_t cap) { return reinterpret_cast<uint32_t*>(pool) + 7 * (size_t)cap; }
+
+// The staged features, after the blocks: a query reads a keyframe's features and its block together.
+int syncFeatures(ydorb_mapdb* h) {
+  hipStream_t s = h->c.stream;
+  DeltaPair& delta = h->featDelta;
+  return syncSpans(h, h->feat.feats, delta, h->featHdr, h->featPoolMem, h->featStart, h->featLen, h->featPool,
+    [&](const mapdb::RowPlan& P, int* st, int* ln, mapdb::FeatRec* oldPool, mapdb::FeatRec* newPool) {
+      mapdb::FeatRepackArgs a;
+      a.nKf = P.nKfBefore; a.featStart = st; a.featLen = ln; a.newOff = at<int>(delta.dev, P.oNewOff);
+      a.oldKps = featKps(oldPool); a.oldRightX = featRightX(oldPool, P.poolCapBefore);
+      a.newKps = featKps(newPool); a.newRightX = featRightX(newPool, P.poolCap);
+      hipLaunchKernelGGL(mapdb::k_mapdb_feat_repack, dim3((unsigned)((P.nKfBefore + mapdb::kFeatWaves - 1) / mapdb::kFeatWaves)), dim3(mapdb::kFeatThreads), 0, s, a);
+    },
+    [&](const mapdb::RowPlan& P, int* st, int* ln, mapdb::FeatRec* pl) {
+      mapdb::FeatApplyArgs a;
+      a.nHeaderRec = P.nHeaderRec; a.tail = (int)P.tail;
+      a.header = at<mapdb::RowHeaderRec>(delta.dev, P.oHeader); a.payload = at<uint4>(delta.dev, P.oPayload);
+      a.featStart = st; a.featLen = ln; a.kps = featKps(pl); a.rightX = featRightX(pl, P.poolCap);
+      hipLaunchKernelGGL(mapdb::k_mapdb_feat_apply, dim3((unsigned)std::max((P.nHeaderRec + mapdb::kFeatWaves - 1) / mapdb::kFeatWaves, 1)), dim3(mapdb::kFeatThreads), 0, s, a);
+    });
+}
+
 size_t layAttributes(Carve& C, mapdb::AttrArrays& A, size_t cap) {
   C.take(A.normal, 3 * cap); C.take(A.minDistance, cap); C.take(A.maxDistance, cap); C.take(A.desc, 2 * cap); C.take(A.flags, cap);
   return C.L.bytes;
@@ -315,6 +351,7 @@ int sync(ydorb_mapdb* h) {
   int rc = syncPoints(h);
   if (!rc) rc = syncRows(h);
   if (!rc) rc = syncDescriptors(h);
+  if (!rc && h->feat.enabled()) rc = syncFeatures(h);
   return rc || !h->attr.enabled() ? rc : syncAttributes(h);
 }
 
@@ -408,6 +445,7 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   h->rowHdr.release(); h->rowPoolMem.release(); h->rowDelta.release(); h->rowset.release();
   h->viewHdr.release(); h->viewPoolMem.release(); h->viewDelta.release(); h->blockHdr.release(); h->blockPoolMem.release(); h->blockDelta.release();
   h->attrMem.release(); h->attrDelta.release();
+  h->featHdr.release(); h->featPoolMem.release(); h->featDelta.release();
   delete h;
 }
 
@@ -419,7 +457,9 @@ extern "C" int ydorb_mapdb_clear(ydorb_mapdb_t* h) {
   h->rows.clear();
   h->desc.clear();
   h->attr.clear();
+  h->feat.clear();
   hipStream_t s = h->c.stream;   // every slot reads as never set again
+  if (h->featHdr.p) HIPCHK(hipMemsetAsync(h->featHdr.p, 0, h->featHdr.cap, s));
   if (h->attrMem.p) HIPCHK(hipMemsetAsync(h->attrMem.p, 0, h->attrMem.cap, s));
   HIPCHK(hipMemsetAsync(h->rowHdr.p, 0, h->rowHdr.cap, s));
   HIPCHK(hipMemsetAsync(h->viewHdr.p, 0, h->viewHdr.cap, s));
@@ -1052,6 +1092,70 @@ extern "C" int ydorb_mapdb_frustum_cull(ydorb_mapdb_t* h, const YdFrustumView* v
   return YDORB_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------- keyframe features
+extern "C" int ydorb_mapdb_enable_features(ydorb_mapdb_t* h) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (h->feat.enabled()) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int rc;
+  if ((rc = allocRowHeaders(h->c.stream, h->featHdr, h->featStart, h->featLen, (size_t)h->feat.feats.hdrCap())) ||
+      (rc = h->featPoolMem.alloc(sizeof(mapdb::FeatRec) * (size_t)h->feat.feats.poolCap())))
+    return rc;
+  HIPCHK(hipStreamSynchronize(h->c.stream));
+  h->featPool = h->featPoolMem.as<mapdb::FeatRec>();
+  h->feat.enable();
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_set_keyframe_features(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n, const int32_t* feat_start,
+                                                 const YdKeyPoint* kps, const float* right_x) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!h->feat.set(kf_slots, n, feat_start, kps, right_x, err)) return invalid(err);
+  h->host.growKeyframes(h->feat.feats.nKeyframes());
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_feat_stats(ydorb_mapdb_t* h, YdMapDbFeatStats* stats) {
+  if (!h || !stats) return invalid("null handle or stats");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  h->feat.stats(*stats);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_export_features(ydorb_mapdb_t* h, int32_t* feat_start, YdKeyPoint* kps, float* right_x) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!mapdb::FeatHost::checkEnabled(h->feat.enabled(), err)) return invalid(err);
+  if (!feat_start) return invalid("null feat_start");
+  if (h->feat.feats.liveAfterSync() > 0 && (!kps || !right_x)) return invalid("null kps or right_x");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  StagedCtx& c = h->c;
+  const size_t held = (size_t)h->feat.feats.nKeyframes(), used = (size_t)h->feat.feats.poolUsed();
+  Layout D;
+  const size_t dStart = D.add(4 * held), dLen = D.add(4 * held), dKps = D.add(sizeof(YdKeyPoint) * used), dRx = D.add(4 * used);
+  D.add(16);
+  if ((rc = c.hDown.ensure(D.bytes))) return rc;
+  hipStream_t s = c.stream;
+  if (held) {
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dStart), h->featStart, 4 * held, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dLen), h->featLen, 4 * held, hipMemcpyDeviceToHost, s));
+  }
+  if (used) {
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dKps), featKps(h->featPool), sizeof(YdKeyPoint) * used, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dRx), featRightX(h->featPool, h->feat.feats.poolCap()), 4 * used, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  mapdb::flattenFeatures(h->host.nKeyframes(), (int32_t)held, at<int32_t>(c.hDown, dStart), at<int32_t>(c.hDown, dLen), at<YdKeyPoint>(c.hDown, dKps),
+                         at<float>(c.hDown, dRx), feat_start, kps, right_x);
+  return YDORB_OK;
+}
+
 // What ydorb_mapdb_search_local_points (orb_matcher.hip) reads: mapdb_resident_points.h
 int ydorb::mapdb::lockResident(ydorb_mapdb_t* h, int32_t device, const int32_t* slots, int32_t n, ResidentPoints& out) {
   std::unique_lock<std::mutex> lock(h->c.mu);
@@ -1069,3 +1173,33 @@ int ydorb::mapdb::lockResident(ydorb_mapdb_t* h, int32_t device, const int32_t* 
   return YDORB_OK;
 }
 void ydorb::mapdb::unlockResident(ydorb_mapdb_t* h) { h->c.mu.unlock(); }
+
+// What ydorb_mapdb_fuse_search (orb_matcher.hip) reads
+int ydorb::mapdb::lockResidentFuse(ydorb_mapdb_t* h, int32_t device, const int32_t* slots, int32_t n, const int32_t* kfSlots, int32_t nKf,
+                                   ResidentPoints& out, ResidentKeyframes& kf, int32_t* featStart, int32_t* featLen, int32_t* blockStart,
+                                   int32_t* blockLen) {
+  std::unique_lock<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!AttrHost::checkEnabled(h->attr.enabled(), err) || !FeatHost::checkEnabled(h->feat.enabled(), err) ||
+      !AttrHost::checkSlots(slots, n, h->host.nPoints(), err) || !RowsHost::checkKfSlots(kfSlots, nKf, h->host.nKeyframes(), err))
+    return invalid(err);
+  if (device != h->device) return invalid("the map table lives on device " + std::to_string(h->device) + ", the matcher on device " + std::to_string(device));
+  if (n > 0) {   // an empty list reads nothing: nothing is applied or launched for it
+    HIPCHK(hipSetDevice(h->device));
+    int rc = sync(h);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->c.stream));   // the deltas and any write-through still queued: the reader runs on another stream
+    for (int32_t t = 0; t < nKf; t++) {          // nothing is staged now: the mirrors say where the device holds each span
+      featStart[t] = h->feat.feats.offOf(kfSlots[t]); featLen[t] = h->feat.feats.lenOf(kfSlots[t]);
+      blockStart[t] = h->desc.blocks.offOf(kfSlots[t]); blockLen[t] = h->desc.blocks.lenOf(kfSlots[t]);
+    }
+  }
+  out = residentOf(h);
+  kf.obsKf = h->poolKf;
+  kf.nFeatHdr = h->feat.feats.hdrCap(); kf.nBlockHdr = h->desc.blocks.hdrCap();
+  kf.featStart = h->featStart; kf.featLen = h->featLen;
+  kf.kps = h->featPool; kf.rightX = reinterpret_cast<const float*>(featRightX(h->featPool, h->feat.feats.poolCap()));
+  kf.blockStart = h->blockStart; kf.blockLen = h->blockLen; kf.blockPool = reinterpret_cast<const uint8_t*>(h->blockPool);
+  lock.release();   // held until unlockResident
+  return YDORB_OK;
+}

@@ -29,6 +29,24 @@ struct ResidentPoints {
 int lockResident(ydorb_mapdb_t* db, int32_t device, const int32_t* slots, int32_t n, ResidentPoints& out);
 void unlockResident(ydorb_mapdb_t* db);
 
+// What ydorb_mapdb_fuse_search reads besides: the observation pool (isInKeyFrame), and per keyframe slot the feature span (DESIGN.md
+// section 6r; one span over two arrays) and the descriptor block (section 6p).
+struct ResidentKeyframes {
+  const int32_t* obsKf = nullptr;                                   // the observation pool: [obsStart[p], obsEnd[p]) of a point
+  int32_t nFeatHdr = 0, nBlockHdr = 0;                              // the header capacities: a slot at or past one has no span
+  const int32_t *featStart = nullptr, *featLen = nullptr;           // [nFeatHdr] in features
+  const void* kps = nullptr;                                        // KeyPoint [pool]: 28 bytes each
+  const float* rightX = nullptr;                                    // [pool]
+  const int32_t *blockStart = nullptr, *blockLen = nullptr;         // [nBlockHdr] in descriptors
+  const uint8_t* blockPool = nullptr;                               // [pool][32]
+};
+
+// lockResident for the fuse search: also checks that features are enabled and every kfSlots[i] lies in 0..n_keyframes-1, and hands out where the
+// device holds the two spans of each named keyframe after the sync, from the host mirrors: featStart / featLen / blockStart / blockLen
+// [nKf], so that the caller builds its FrameDev records without a read-back.
+int lockResidentFuse(ydorb_mapdb_t* db, int32_t device, const int32_t* slots, int32_t n, const int32_t* kfSlots, int32_t nKf, ResidentPoints& out,
+                     ResidentKeyframes& kf, int32_t* featStart, int32_t* featLen, int32_t* blockStart, int32_t* blockLen);
+
 struct ResidentLock {   // unlocks on every way out of the reader
   ydorb_mapdb_t* db = nullptr;
   ~ResidentLock() { if (db) unlockResident(db); }

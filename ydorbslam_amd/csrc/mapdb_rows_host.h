@@ -74,6 +74,7 @@ template <class T> class SpanHost {
   bool dirty() const { return !dirtyRows_.empty() || !dirtyEntries_.empty(); }
   int32_t lenOf(int32_t kf) const { return kf < nKeyframes() ? (int32_t)row_[(size_t)kf].size() : 0; }   // staged changes included
   const std::vector<T>& rowOf(int32_t kf) const { return row_[(size_t)kf]; }
+  int32_t offOf(int32_t kf) const { return kf < nKeyframes() ? off_[(size_t)kf] : 0; }   // where the device holds the span; with nothing staged
 
   void clear() {
     row_.clear(); off_.clear(); len_.clear(); state_.clear();

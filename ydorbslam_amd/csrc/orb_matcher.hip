@@ -15,7 +15,9 @@
 #include "../../include/ydorb/c_api.h"
 #include "frustum_kernels.hip.h"
 #include "host_buffers.h"
+#include "map_table.h"
 #include "mapdb_frustum_kernels.hip.h"
+#include "mapdb_fuse_kernels.hip.h"
 #include "mapdb_resident_points.h"
 #include "match_kernels.hip.h"
 #include "stereo_kernels.hip.h"
@@ -124,6 +126,24 @@ size_t layStereo(size_t nPairs, size_t nl, size_t nr, void* base, StereoPtrs& p)
   return a.L.bytes;
 }
 
+// `call`, ydorb_mapdb_fuse_search: nt targets over nf distinct target frames with sumN features in all, L list entries.  `up` is what one
+// upload brings (targets, list starts, slots, skip bytes, frame and call records), `down` what one read-back takes (matches, status
+// bytes, counts, pool heads, the overflow word).  The rows of all calls lie in list order; call t points at row list_start[t].
+struct FusePtrs {
+  uint8_t *up, *down;
+  QueryDev* queries; uint8_t* qdesc; int2* qInfo; uint2* qPre;
+  uint8_t* taken; int* assigned;
+  int *cellStart, *cellIdx; float4* sortedKp; uint8_t* sortedDesc;
+};
+size_t layFuse(size_t upBytes, size_t downBytes, size_t nt, size_t nf, size_t sumN, size_t maxN, size_t L, void* base, FusePtrs& p) {
+  Carve a(base);
+  a.take(p.up, upBytes); a.take(p.down, downBytes);
+  a.take(p.queries, L); a.take(p.qdesc, 32 * L); a.take(p.qInfo, L); a.take(p.qPre, L);
+  a.take(p.taken, (maxN + kTakenPad + 1) * nt); a.take(p.assigned, maxN * nt);
+  a.take(p.cellStart, (kGridCells + 1) * nf); a.take(p.cellIdx, sumN); a.take(p.sortedKp, sumN); a.take(p.sortedDesc, 32 * sumN);
+  return a.L.bytes;
+}
+
 }  // namespace
 
 // Host-call and batched paths share no device state on a handle: a batched call may still be running on its caller's stream, and its
@@ -134,6 +154,7 @@ struct ydorb_matcher {
   Mem call;              // every synchronous host-call entry point: each ends in a stream synchronise, so the next one lays it out afresh
   Mem pool;              // the host calls' record pool: grows by poolRecords, not by a call's shape, and a replay after an overflow
   size_t poolRecords = 1u << 20;   // ... finds everything else where it was
+  size_t fuseOvfPerCall = 1u << 14;   // ydorb_mapdb_fuse_search: the overflow region of each target's pool part, grown by a replay
   Mem stereo;            // ydorb_stereo_matches (layStereo)
   PinnedMem hUp, hDown;  // ydorb_search_local_points: pinned staging of the map-point table, read-back of track rows + status bytes
   // What ydorb_match_pairs_device / ydorb_match_consecutive_device keep; nothing but them, synchronize and destroy touches it.
@@ -533,6 +554,159 @@ int ydorb_mapdb_search_local_points(ydorb_mapdb_t* db, ydorb_matcher_t* m, const
   std::memcpy(status, at<void>(m->hDown, dSt), p);
   for (int i = 0; i < np; i++) *nToMatch += status[i] == YDORB_FRUSTUM_IN_VIEW;
   return YDORB_OK;
+}
+
+// OrbMatcher::fuseByProjection / fuseBySim3 for several target keyframes over a resident map table (map_resident.hip,
+// mapdb_resident_points.h): k_mapdb_fuse_queries builds every target's query rows and query descriptors from the resident points, the
+// target frames point into the resident feature and descriptor pools, and the batch kernels of ydorb_match_pairs_device run once over
+// all targets (mode 6).  One upload, one read-back.  The table's mutex is held from its sync to the end of the call, as in
+// ydorb_mapdb_search_local_points; every return after the first launch, an error included, synchronises the matcher's stream first.
+// The pool follows the batch layout, max_list fixed slots of kSlot records plus an overflow region per call; the overflow word is
+// read here, and a set one grows the region to what the heads asked for and replays (the kernels wrote nothing past the pool).
+int ydorb_mapdb_fuse_search(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdFuseTarget* targets, int32_t nTargets, const int32_t* listStart,
+                            const int32_t* pointSlots, const uint8_t* skip, int32_t* bestIdx, uint8_t* status, int32_t* nFound, uint8_t* targetStatus) {
+  if (!db || !m) { set_error("mapdb_fuse_search: null handle"); return YDORB_ERR_INVALID_ARG; }
+  if (nTargets < 0) { set_error("mapdb_fuse_search: negative number of targets: %d", nTargets); return YDORB_ERR_INVALID_ARG; }
+  std::string err;
+  if (!maptable::checkStarts("list_start", listStart, nTargets, err)) { set_error("mapdb_fuse_search: %s", err.c_str()); return YDORB_ERR_INVALID_ARG; }
+  const int32_t L = listStart[nTargets];
+  if ((nTargets > 0 && (!targets || !nFound || !targetStatus)) || (L > 0 && (!pointSlots || !skip || !bestIdx || !status))) {
+    set_error("mapdb_fuse_search: null targets, n_found, target_status, point_slots, skip, best_idx or status");
+    return YDORB_ERR_INVALID_ARG;
+  }
+  for (int t = 0; t < nTargets; t++) {
+    const YdFuseTarget& G = targets[t];
+    if (G.view.n_levels < 1 || G.view.n_levels > 8) { set_error("mapdb_fuse_search: target %d: n_levels %d outside 1..8", t, G.view.n_levels); return YDORB_ERR_INVALID_ARG; }
+    if (G.max_dist < 0 || G.max_dist > 256) { set_error("mapdb_fuse_search: target %d: max_dist %d outside 0..256", t, G.max_dist); return YDORB_ERR_INVALID_ARG; }
+    if (!(G.view.max_x > G.view.min_x && G.view.max_y > G.view.min_y)) { set_error("mapdb_fuse_search: target %d: empty image bounds", t); return YDORB_ERR_INVALID_ARG; }
+  }
+  const size_t nt = (size_t)nTargets, nl = (size_t)L;
+  std::vector<int32_t> kfSlots(nt), featStart(nt, 0), featLen(nt, 0), blockStart(nt, 0), blockLen(nt, 0);
+  for (size_t t = 0; t < nt; t++) kfSlots[t] = targets[t].kf_slot;
+  mapdb::ResidentPoints R;
+  mapdb::ResidentKeyframes K;
+  mapdb::ResidentLock lock;
+  int rc;
+  if ((rc = mapdb::lockResidentFuse(db, m->device, pointSlots, L, kfSlots.data(), nTargets, R, K, featStart.data(), featLen.data(), blockStart.data(),
+                                    blockLen.data())))
+    return rc;   // also refuses a table without attributes or features
+  lock.db = db;
+  for (size_t t = 0; t < nt; t++) { nFound[t] = 0; targetStatus[t] = YDORB_FUSE_TARGET_OK; }
+  if (L == 0) {   // nothing was synced: the mirrors' lengths were not read
+    return YDORB_OK;
+  }
+  // one FrameDev per distinct (keyframe, stereo or not, bounds); a target without a usable frame searches nothing
+  struct FrameKey { int32_t kf, mono; float b[4]; };
+  std::vector<FrameKey> keys;
+  std::vector<int> frameOf(nt, -1);
+  std::vector<size_t> frameAt;   // where each frame's grid arrays begin, in features
+  size_t sumN = 0, maxN = 0, maxList = 0;
+  for (size_t t = 0; t < nt; t++) {
+    const YdFuseTarget& G = targets[t];
+    if (featLen[t] == 0) targetStatus[t] = YDORB_FUSE_TARGET_NO_FEATURES;
+    else if (blockLen[t] == 0) targetStatus[t] = YDORB_FUSE_TARGET_NO_BLOCK;
+    else if (blockLen[t] != featLen[t]) targetStatus[t] = YDORB_FUSE_TARGET_LENGTH_MISMATCH;
+    if (targetStatus[t] != YDORB_FUSE_TARGET_OK) continue;
+    maxList = std::max(maxList, (size_t)(listStart[t + 1] - listStart[t]));
+    const FrameKey key{G.kf_slot, (G.flags & YDORB_FUSE_MONOCULAR) ? 1 : 0, {G.view.min_x, G.view.max_x, G.view.min_y, G.view.max_y}};
+    for (size_t f = 0; f < keys.size() && frameOf[t] < 0; f++)
+      if (!memcmp(&keys[f], &key, sizeof(FrameKey))) frameOf[t] = (int)f;
+    if (frameOf[t] >= 0) continue;
+    frameOf[t] = (int)keys.size();
+    keys.push_back(key);
+    frameAt.push_back(sumN);
+    sumN += (size_t)featLen[t];
+    maxN = std::max(maxN, (size_t)featLen[t]);
+  }
+  const size_t nf = keys.size();
+  HIPCHK(hipSetDevice(m->device));
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};   // before the mutex goes: see above
+  Layout U;
+  const size_t oTargets = U.add(sizeof(YdFuseTarget) * nt), oStart = U.add(4 * (nt + 1)), oSlots = U.add(4 * nl), oSkip = U.add(nl),
+               oFrames = U.add(sizeof(FrameDev) * nf), oCalls = U.add(sizeof(CallDev) * nt);
+  Layout D;
+  const size_t dMatch = D.add(4 * nl), dSt = D.add(nl), dCount = D.add(4 * nt), dHeads = D.add(4 * nt), dOvf = D.add(16);
+  FusePtrs p;
+  if ((rc = m->hUp.ensure(U.bytes)) || (rc = m->hDown.ensure(D.bytes))) return rc;
+  if ((rc = layOut(m->call, [&](void* base) { return layFuse(U.bytes, D.bytes, nt, nf, sumN, maxN, nl, base, p); }))) return rc;
+  const size_t takenStride = maxN + kTakenPad + 1;
+  std::memcpy(at<void>(m->hUp, oTargets), targets, sizeof(YdFuseTarget) * nt);
+  std::memcpy(at<void>(m->hUp, oStart), listStart, 4 * (nt + 1));
+  std::memcpy(at<void>(m->hUp, oSlots), pointSlots, 4 * nl);
+  std::memcpy(at<void>(m->hUp, oSkip), skip, nl);
+  FrameDev* hf = at<FrameDev>(m->hUp, oFrames);
+  CallDev* hc = at<CallDev>(m->hUp, oCalls);
+  std::memset(hf, 0, sizeof(FrameDev) * nf);
+  std::memset(hc, 0, sizeof(CallDev) * nt);
+  for (size_t t = 0; t < nt; t++) {
+    const int f = frameOf[t];
+    const YdFuseTarget& G = targets[t];
+    CallDev& C = hc[t];
+    C.frame = std::max(f, 0); C.qAngle = nullptr; C.nqPtr = nullptr; C.qkps = nullptr;
+    C.queries = p.queries + listStart[t]; C.qdesc = p.qdesc + 32 * (size_t)listStart[t];
+    C.nq = f < 0 ? 0 : listStart[t + 1] - listStart[t];
+    C.qInfo = p.qInfo + listStart[t]; C.qPre = p.qPre + listStart[t];
+    C.taken = p.taken + t * takenStride; C.takenClear = 1; C.assigned = p.assigned + t * maxN;
+    C.matchQ = reinterpret_cast<int*>(p.down + dMatch) + listStart[t]; C.count = reinterpret_cast<int*>(p.down + dCount) + t;
+    C.mode = 6; C.ratio = 0.f; C.orbDist = G.max_dist; C.checkOri = 0;
+    for (int i = 0; i < 8; i++) C.invSigma2[i] = G.inv_sigma2[i];
+    if (f < 0) continue;
+    FrameDev& F = hf[f];
+    if (F.kps) { C.tkps = F.kps; continue; }
+    F.kps = reinterpret_cast<const KeyPointDev*>(K.kps) + featStart[t];
+    F.desc = K.blockPool + 32 * (size_t)blockStart[t];
+    F.rightX = (G.flags & YDORB_FUSE_MONOCULAR) ? nullptr : K.rightX + featStart[t];
+    F.nPtr = nullptr; F.n = featLen[t];
+    F.minX = G.view.min_x; F.minY = G.view.min_y;
+    F.gridWInv = static_cast<float>(kGridCols) / (G.view.max_x - G.view.min_x);
+    F.gridHInv = static_cast<float>(kGridRows) / (G.view.max_y - G.view.min_y);
+    F.cellStart = p.cellStart + (size_t)f * (kGridCells + 1); F.cellIdx = p.cellIdx + frameAt[f];
+    F.sortedKp = p.sortedKp + frameAt[f]; F.sortedDesc = p.sortedDesc + 32 * frameAt[f];
+    C.tkps = F.kps;
+  }
+  hipStream_t s = m->stream;
+  HIPCHK(hipMemcpyAsync(p.up, m->hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(p.down, 0xFF, 4 * nl, s));   // best_idx -1 wherever no call writes it
+  fuse::QueryArgs qa;
+  qa.nTargets = nTargets; qa.nEntries = L;
+  qa.start = reinterpret_cast<const int*>(p.up + oStart); qa.targets = reinterpret_cast<const fuse::TargetDev*>(p.up + oTargets);
+  qa.slots = reinterpret_cast<const int*>(p.up + oSlots); qa.skip = p.up + oSkip;
+  qa.R = R; qa.obsKf = K.obsKf; qa.qdesc = reinterpret_cast<uint4*>(p.qdesc); qa.status = p.down + dSt;
+  hipLaunchKernelGGL(fuse::k_mapdb_fuse_queries<QueryDev>, dim3((unsigned)((nl + fuse::kThreads - 1) / fuse::kThreads)), dim3(fuse::kThreads), 0, s, qa, p.queries);
+  HIPCHK(hipGetLastError());
+  const FrameDev* dFrames = reinterpret_cast<const FrameDev*>(p.up + oFrames);
+  const CallDev* dCalls = reinterpret_cast<const CallDev*>(p.up + oCalls);
+  if (nf > 0 && (rc = launchGridBuild((int)nf, (int)maxN, s, dFrames))) return rc;   // once: a replay finds the grids where they are
+  const int takenWords = (int)((maxN + 31) / 32);
+  for (int attempt = 0; attempt < 6; attempt++) {
+    const size_t poolPerCall = maxList * kSlot + m->fuseOvfPerCall;
+    if (poolPerCall * nt > (size_t)INT32_MAX) { set_error("mapdb_fuse_search: a record pool of %zu entries, past INT32_MAX", poolPerCall * nt); return YDORB_ERR_CAPACITY; }
+    if ((rc = m->pool.ensure(sizeof(uint32_t) * poolPerCall * nt))) return rc;
+    HIPCHK(hipMemsetAsync(p.down + dCount, 0, D.bytes - dCount, s));   // counts, heads, overflow word
+    if (nf > 0 && maxList > 0) {
+      HIPCHK(hipMemsetAsync(p.taken, 0, takenStride * nt, s));
+      hipLaunchKernelGGL(k_gather_projection, dim3((unsigned)((maxList + 4 * kGatherQpw - 1) / (4 * kGatherQpw)), nTargets), dim3(256), 0, s, dCalls, dFrames,
+                         (int)maxList, m->pool.as<uint32_t>(), reinterpret_cast<unsigned*>(p.down + dHeads), (unsigned)poolPerCall,
+                         reinterpret_cast<int*>(p.down + dOvf));
+      hipLaunchKernelGGL(k_resolve, dim3(nTargets), dim3(64), 2 * sizeof(unsigned) * takenWords, s, dCalls, dFrames, m->pool.as<uint32_t>(), takenWords);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(m->hDown.p, p.down, D.bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (*at<int>(m->hDown, dOvf) != 0) {
+      const unsigned* heads = at<unsigned>(m->hDown, dHeads);
+      size_t asked = 0;
+      for (size_t t = 0; t < nt; t++) asked = std::max(asked, (size_t)heads[t]);
+      m->fuseOvfPerCall = std::max(m->fuseOvfPerCall * 2, asked + 1024);
+      continue;
+    }
+    std::memcpy(bestIdx, at<void>(m->hDown, dMatch), 4 * nl);
+    std::memcpy(status, at<void>(m->hDown, dSt), nl);
+    std::memcpy(nFound, at<void>(m->hDown, dCount), 4 * nt);
+    return YDORB_OK;
+  }
+  set_error("mapdb_fuse_search: candidate record pool kept overflowing");
+  return YDORB_ERR_CAPACITY;
 }
 
 int ydorb_fuse_search(ydorb_matcher_t* m, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc, int32_t nq,

@@ -5,13 +5,16 @@ of the flat table.  MapDb.correct (ydorb_mapdb_correct) ru
 The keyframe rows (DESIGN.md section 6o) add the relation keyframe -> map points and the two set queries of Tracking::updateLocalMap.
 The resident descriptors add the keyframes' descriptor blocks and the points' views, and
 MapPoint::computeDistinctiveDescriptors over them with no descriptor upload.  The resident point attributes (DESIGN.md section 6q) keep
-normal, distances and descriptor of every point where those queries compute them, and Tracking::searchLocalPoints reads them by slot."""
+normal, distances and descriptor of every point where those queries compute them, and Tracking::searchLocalPoints reads them by slot.  The resident keyframe features
+ add each keyframe's keypoints and right coordinates, and MapDb.fuse_search runs the search of fuseByProjection /
+fuseBySim3 for all target keyframes of a LocalMapping::searchInNeighbors direction in one call."""
 import ctypes as C
 
 import numpy as np
 
 from . import map_maintenance as M
-from ._lib import YdMapCorrection, YdMapDbAttrStats, YdMapDbDescStats, YdMapDbRowStats, YdMapDbStats, check, lib
+from .extractor import KP_DTYPE
+from ._lib import YdFuseTarget, YdMapCorrection, YdMapDbAttrStats, YdMapDbDescStats, YdMapDbFeatStats, YdMapDbRowStats, YdMapDbStats, check, lib
 
 _p = M._p
 
@@ -316,6 +319,58 @@ class MapDb:
         check(lib().ydorb_mapdb_search_local_points(self._h, matcher._h, C.byref(fv), C.byref(view), _p(slots), n, _p(skip), float(th), matcher.ratio,
                                                     _p(taken), _p(assigned), _p(rows), _p(status), C.byref(n_to), C.byref(n_m)))
         return dict(n_to_match=n_to.value, n_matches=n_m.value, assigned=assigned, taken=taken, rows=rows[:n], status=status[:n])
+
+    # ------------------------------------------------------------------------------------------------------------ keyframe features
+    def enable_features(self):
+        """Turns the resident keyframe features on; calling it twice is fine."""
+        check(lib().ydorb_mapdb_enable_features(self._h))
+
+    def set_keyframe_features(self, kf_slots, kps, right_x=None):
+        """Stages the features of the keyframes: kps = one KP_DTYPE array per slot, right_x = one float32 array per slot or None
+        (monocular: every entry is stored as -1).  An empty array erases a keyframe's features."""
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        kps = [np.ascontiguousarray(a, KP_DTYPE).reshape(-1) for a in kps]
+        assert len(kps) == len(kf_slots)
+        start = np.concatenate([[0], np.cumsum([len(a) for a in kps])]).astype(np.int32)
+        flat = np.ascontiguousarray(np.concatenate(kps + [np.zeros(0, KP_DTYPE)]))
+        rx = None
+        if right_x is not None:
+            right_x = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in right_x]
+            assert [len(a) for a in right_x] == [len(a) for a in kps]
+            rx = np.ascontiguousarray(np.concatenate(right_x + [np.zeros(0, np.float32)]))
+        check(lib().ydorb_mapdb_set_keyframe_features(self._h, _p(kf_slots), len(kf_slots), _p(start), _p(flat), _p(rx)))
+
+    def export_features(self):
+        """The device's features read back: per keyframe slot 0 .. n_keyframes-1 a (kps [n_k] KP_DTYPE, right_x [n_k]) pair."""
+        k, N = self.n_keyframes, self.feat_stats()["n_features"]
+        start, kps, rx = np.zeros(k + 1, np.int32), np.zeros(max(N, 1), KP_DTYPE), np.zeros(max(N, 1), np.float32)
+        check(lib().ydorb_mapdb_export_features(self._h, _p(start), _p(kps), _p(rx)))
+        assert int(start[-1]) == N
+        return [(kps[start[i]:start[i + 1]].copy(), rx[start[i]:start[i + 1]].copy()) for i in range(k)]
+
+    def feat_stats(self):
+        s = YdMapDbFeatStats()
+        check(lib().ydorb_mapdb_feat_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in YdMapDbFeatStats._fields_}
+
+    def fuse_search(self, matcher, targets, lists, skips):
+        """ydorb_mapdb_fuse_search on an OrbMatcher (ydorbslam_amd.matcher): targets [YdFuseTarget], per target a list of point slots and
+        its skip bytes.  Returns per target dict(best_idx [m] int32, status [m] uint8, n_found, target_status)."""
+        T = len(targets)
+        t = (YdFuseTarget * max(T, 1))(*targets)
+        idx = [np.asarray(a, np.int32).reshape(-1) for a in lists]
+        sk = [np.asarray(a, np.uint8).reshape(-1) for a in skips]
+        assert len(idx) == len(sk) == T and all(len(a) == len(b) for a, b in zip(idx, sk))
+        start = np.concatenate([[0], np.cumsum([len(a) for a in idx])]).astype(np.int32)
+        slots = np.ascontiguousarray(np.concatenate(idx + [np.zeros(0, np.int32)]))
+        skip = np.ascontiguousarray(np.concatenate(sk + [np.zeros(0, np.uint8)]))
+        L = int(start[-1])
+        best, status = np.full(max(L, 1), -7, np.int32), np.full(max(L, 1), 9, np.uint8)
+        n_found, t_status = np.full(max(T, 1), -7, np.int32), np.full(max(T, 1), 9, np.uint8)
+        check(lib().ydorb_mapdb_fuse_search(self._h, matcher._h, C.cast(t, C.c_void_p), T, _p(start), _p(slots), _p(skip), _p(best), _p(status),
+                                            _p(n_found), _p(t_status)))
+        return [dict(best_idx=best[start[f]:start[f + 1]].copy(), status=status[start[f]:start[f + 1]].copy(), n_found=int(n_found[f]),
+                     target_status=int(t_status[f])) for f in range(T)]
 
     # ------------------------------------------------------------------------------------------------------------ inspection
     def stats(self):
