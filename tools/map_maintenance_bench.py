@@ -20,10 +20,11 @@ k_mapdb_apply / k_mapdb_repack: `rocprofv3 --kernel-trace --stats -- python tool
 the three loops of loop closing; see bench_correct.  Its kernels k_mapdb_correct / k_mapdb_correct_centres: the same rocprofv3 line
 with --correct.
 --local-map times the two set queries of Tracking::updateLocalMap on the resident table's keyframe rows (DESIGN.md section 6o); see
-bench_local_map.  Its kernels k_rowset_mark / _count / _emit and k_mapdb_rows_apply / _repack: the same rocprofv3 line with --local-map.
+bench_local_map.  Its kernels k_rowset_mark / _count / _emit and the int instantiation of k_mapdb_span_apply / _repack (the trace
+names them k_mapdb_span_apply<int, 1> / k_mapdb_span_repack<int, 1>): the same rocprofv3 line with --local-map.
 --descriptors times MapPoint::computeDistinctiveDescriptors on the resident table's descriptor blocks and point views (DESIGN.md section
 6p) beside the flat path as a caller must run it and the CPU oracle; see bench_descriptors.  Its kernels k_mapdb_distinctive and
-k_mapdb_desc_apply / _repack: the same rocprofv3 line with --descriptors.
+k_mapdb_span_apply / _repack (<uint4, 2> for the blocks, <int, 1> for the views): the same rocprofv3 line with --descriptors.
 Prints one JSON line."""
 import argparse
 import ctypes as C

@@ -1,23 +1,29 @@
-// Host driver of the resident map table + its C ABI (include/ydorb/c_api.h, "Resident map table").  The handle
-// owns the slot tables, the camera centres and the observation pool in device arenas, and mapdb_host.h's Host, which validates, stages
-// and plans (the pool policy of both state machines: span_pool.h).  The set_* entries only stage.  A query, on the handle's one stream:
-// if anything is staged, one upload of the packed delta, the table growths (device-to-device copies), k_mapdb_repack if the pool needs
-// it and k_mapdb_apply; then the query's own arrays in one upload, the pass of map_kernels.hip.h, one read-back and one synchronise.
-// With nothing staged no table byte moves.
-// ydorb_mapdb_correct (mapcorrect_kernels.hip.h) is the one query that writes the table: positions in place, then centres.
-// The keyframe rows (mapdb_rows_host.h, mapdb_rows_kernels.hip.h) are a second state machine in the same handle,
-// synced after the points under the same mutex: ydorb_mapdb_points_of_keyframes and ydorb_mapdb_observer_counter below.
-// The point views and the keyframe descriptor blocks (mapdb_desc_host.h, mapdb_desc_kernels.hip.h) are two more,
-// synced after the rows through the same syncSpans: ydorb_mapdb_distinctive_descriptors below.
-// The point attributes (mapdb_attr_host.h, mapdb_attr_kernels.hip.h) are an opt-in fifth, synced last; three
-// queries write their results through to them, and ydorb_mapdb_frustum_cull / lockResident at the end of this file read them by slot.
-// The keyframe features (mapdb_feat_host.h, mapdb_feat_kernels.hip.h) are an opt-in sixth span relation, synced
-// after the blocks and before the attributes; lockResidentFuse hands them and the blocks to ydorb_mapdb_fuse_search (orb_matcher.hip).
+// Host driver of the resident map table + its C ABI (include/ydorb/c_api.h, "Resident map table").  One handle,
+// one mutex, one stream.  Every part has a host half that validates, stages and plans without HIP (the pool policy: span_pool.h) and a
+// device half here that owns the arenas and executes the packed delta:
+//   the point table       mapdb_host.h's Host over an SoA arena per point slot (PointColumns below), the camera centres per keyframe
+//                         slot and the observation pool; k_mapdb_repack / k_mapdb_apply (mapdb_kernels.hip.h).
+//   the attribute table   opt-in; mapdb_attr_host.h's AttrHost over an SoA arena per point slot (AttrColumns below) that follows the
+//                         point table's capacity; k_mapdb_attr_apply (mapdb_attr_kernels.hip.h).  Three queries
+//                         write their results through to it.
+//   four span relations   each a SpanHost<T> (mapdb_rows_host.h) and a SpanDev<T> below: the keyframe rows (section 6o), the point
+//                         views and the keyframe descriptor blocks (mapdb_desc_host.h, section 6p), which share the two kernels of
+//                         mapdb_span_kernels.hip.h, and the opt-in keyframe features (mapdb_feat_host.h, section 6r), whose one pool
+//                         arena holds two arrays and has kernels of its own (mapdb_feat_kernels.hip.h).
+// The set_* entries only stage.  A query calls sync() first, which applies what is staged in a fixed order: points, rows, views, blocks,
+// features if enabled, attributes if enabled.  A later part may name what an earlier one introduced in the same interval: a row a new
+// point, a view a new keyframe, the attribute arena the point capacity just grown.  Each part: one upload of its packed delta, the
+// growths (device-to-device copies), the repack if its pool needs it, the apply; an arena that was replaced is freed only after the
+// stream has drained (handOver).  With nothing staged no table byte moves.  Then the query's own arrays in one upload, its pass, one
+// read-back and one synchronise.  ydorb_mapdb_correct (mapcorrect_kernels.hip.h, section 6n) is the one query that writes the point
+// table: positions in place, then centres.  lockResident / lockResidentFuse at the end hand device pointers to the matcher
+// (orb_matcher.hip), which reads them on another stream: they synchronise first.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ydorb/c_api.h"
@@ -37,16 +43,125 @@
 #include "mapdb_resident_points.h"
 #include "mapdb_rows_host.h"
 #include "mapdb_rows_kernels.hip.h"
+#include "mapdb_span_kernels.hip.h"
 #include "ydorb_host.h"
 
 using namespace ydorb;
+
+namespace {
+
+int invalid(const std::string& what) { set_error("resident map table: %s", what.c_str()); return YDORB_ERR_INVALID_ARG; }
+
+int copyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {   // an empty run enqueues nothing
+  if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, kind, s));
+  return YDORB_OK;
+}
 
 struct DeltaPair {   // a packed delta on the device and its pinned staging; never empty: rows may grow the keyframe count alone
   Mem dev;
   PinnedMem host;
   int ensure(size_t bytes) { const int rc = dev.ensure(bytes + 16); return rc ? rc : host.ensure(bytes + 16); }
+  int upload(hipStream_t s, size_t bytes) { return copyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, s); }
   void release() { dev.release(); host.release(); }
 };
+
+int allocSpanHeaders(hipStream_t s, Mem& m, int*& start, int*& len, size_t cap) {   // every slot: no span
+  int rc = m.alloc(8 * cap);
+  if (rc) return rc;
+  start = m.as<int>(); len = start + cap;
+  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
+  return YDORB_OK;
+}
+
+// The end of a sync: what was enqueued still reads the old arenas, so the stream drains before the handle takes each new one made
+struct NewArena { Mem* mine; ScopedMem* fresh; };
+int handOver(hipStream_t s, std::initializer_list<NewArena> arenas) {
+  bool any = false;
+  for (const NewArena& a : arenas) any = any || a.fresh->p;
+  if (any) HIPCHK(hipStreamSynchronize(s));
+  for (const NewArena& a : arenas) if (a.fresh->p) a.mine->take(*a.fresh);
+  return YDORB_OK;
+}
+
+struct PoolPart { const void* src; size_t bytes, at; };   // a run of pool bytes for download(); at: where it lands in c.hDown
+
+// The device half of one SpanHost<T> (mapdb_rows_host.h): the header arena (start / len per slot), the pool arena and the delta.
+template <class T> struct SpanDev {
+  Mem hdr, poolMem;
+  DeltaPair delta;
+  int *start = nullptr, *len = nullptr;
+  T* pool = nullptr;
+
+  int allocPool(const mapdb::SpanHost<T>& host) {   // at first, and after a reserve: nothing in flight may read the old one
+    const int rc = poolMem.alloc(sizeof(T) * (size_t)host.poolCap());
+    pool = poolMem.as<T>();
+    return rc;
+  }
+  int alloc(hipStream_t s, const mapdb::SpanHost<T>& host) {
+    const int rc = allocSpanHeaders(s, hdr, start, len, (size_t)host.hdrCap());
+    return rc ? rc : allocPool(host);
+  }
+  int zeroHeaders(hipStream_t s) {   // every slot reads as never set again; a relation never enabled has none
+    if (hdr.p) HIPCHK(hipMemsetAsync(hdr.p, 0, hdr.cap, s));
+    return YDORB_OK;
+  }
+  void release() { hdr.release(); poolMem.release(); delta.release(); }
+
+  // Brings the relation up to date, everything on stream s: one upload of the packed delta, the header growth, the repack if the pool
+  // needs it, the apply.  repack(P, start, len, oldPool, newPool) and apply(P, start, len, pool) launch the relation's two kernels.
+  template <class Repack, class Apply> int sync(hipStream_t s, mapdb::SpanHost<T>& host, Repack repack, Apply apply) {
+    if (!host.dirty()) { host.nothingToSync(); return YDORB_OK; }
+    const mapdb::RowPlan P = host.plan();
+    int rc;
+    if ((rc = delta.ensure(P.bytes))) return rc;
+    ScopedMem newHdr, newPool;   // become this relation's arenas below; freed here on an early return
+    int *st = start, *ln = len;
+    T* pl = pool;
+    if (P.hdrCap != P.hdrCapBefore && (rc = allocSpanHeaders(s, newHdr, st, ln, (size_t)P.hdrCap))) return rc;
+    if (P.repack && (rc = newPool.alloc(sizeof(T) * (size_t)P.poolCap))) return rc;
+    if (newPool.p) pl = newPool.as<T>();
+    host.pack(P, delta.host.as<uint8_t>());   // every allocation is made: only a HIP error can fail below, and the delta counts as applied
+    if ((rc = delta.upload(s, P.bytes))) return rc;
+    if (newHdr.p && ((rc = copyAsync(st, start, 4 * (size_t)P.nKfBefore, hipMemcpyDeviceToDevice, s)) ||
+                     (rc = copyAsync(ln, len, 4 * (size_t)P.nKfBefore, hipMemcpyDeviceToDevice, s))))
+      return rc;
+    if (P.repack && P.nKfBefore > 0) {
+      repack(P, st, ln, pool, pl);
+      HIPCHK(hipGetLastError());
+    }
+    apply(P, st, ln, pl);
+    HIPCHK(hipGetLastError());
+    if ((rc = handOver(s, {{&hdr, &newHdr}, {&poolMem, &newPool}}))) return rc;
+    start = st; len = ln; pool = pl;
+    return YDORB_OK;
+  }
+
+  // The first `held` headers and the given runs of the pool read back into c.hDown, with one synchronise
+  template <size_t N> int download(StagedCtx& c, size_t held, size_t& dStart, size_t& dLen, PoolPart (&parts)[N]) {
+    Layout D;
+    dStart = D.add(4 * held); dLen = D.add(4 * held);
+    for (PoolPart& p : parts) p.at = D.add(p.bytes);
+    D.add(16);
+    int rc = c.hDown.ensure(D.bytes);
+    if (rc) return rc;
+    hipStream_t s = c.stream;
+    if ((rc = copyAsync(at<void>(c.hDown, dStart), start, 4 * held, hipMemcpyDeviceToHost, s)) ||
+        (rc = copyAsync(at<void>(c.hDown, dLen), len, 4 * held, hipMemcpyDeviceToHost, s)))
+      return rc;
+    for (const PoolPart& p : parts)
+      if ((rc = copyAsync(at<void>(c.hDown, p.at), p.src, p.bytes, hipMemcpyDeviceToHost, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    return YDORB_OK;
+  }
+  int download(StagedCtx& c, size_t held, size_t used, size_t& dStart, size_t& dLen, size_t& dPool) {   // the used part of a plain pool
+    PoolPart part[1] = {{pool, sizeof(T) * used, 0}};
+    const int rc = download(c, held, dStart, dLen, part);
+    dPool = part[0].at;
+    return rc;
+  }
+};
+
+}  // namespace
 
 struct ydorb_mapdb {
   int device = 0;
@@ -57,42 +172,74 @@ struct ydorb_mapdb {
   mapdb::SlotTables T{};
   int* poolKf = nullptr;
   uint8_t* poolLevel = nullptr;
-  // keyframe rows: a state machine, arenas and a delta of their own
+  // keyframe rows
   mapdb::RowsHost rows;
-  Mem rowHdr, rowPoolMem, rowset;   // rowset: first / seenStamp of the points-of-keyframes query, one entry per point slot
-  DeltaPair rowDelta;
-  int *rowStart = nullptr, *rowLen = nullptr, *rowPool = nullptr, *first = nullptr, *seenStamp = nullptr;
+  SpanDev<int32_t> dRows;
+  Mem rowset;   // first / seenStamp of the points-of-keyframes query, one entry per point slot
+  int *first = nullptr, *seenStamp = nullptr;
   size_t rowsetCap = 0;
   int stamp = 0;
-  // point views and keyframe descriptor blocks: as the rows, twice
+  // point views and keyframe descriptor blocks
   mapdb::DescHost desc;
-  Mem viewHdr, viewPoolMem, blockHdr, blockPoolMem;
-  DeltaPair viewDelta, blockDelta;
-  int *viewStart = nullptr, *viewLen = nullptr, *viewPool = nullptr, *blockStart = nullptr, *blockLen = nullptr;
-  mapdb::DescRow* blockPool = nullptr;
+  SpanDev<int32_t> dViews;
+  SpanDev<mapdb::DescRow> dBlocks;
   // point attributes: nothing of this is allocated or launched until ydorb_mapdb_enable_attributes
   mapdb::AttrHost attr;
   Mem attrMem;
   DeltaPair attrDelta;
   mapdb::AttrArrays A{};
-  // keyframe features: nothing of this is allocated or launched until ydorb_mapdb_enable_features.  One arena
-  // of 32 bytes per pool entry: KeyPoint [cap] at featPool, right_x [cap] behind it (featRightX)
+  // keyframe features: nothing of this is allocated or launched until ydorb_mapdb_enable_features.  The pool
+  // arena has 32 bytes per entry and holds two arrays: KeyPoint [cap] at its base (featKps), right_x [cap] behind it (featRightX)
   mapdb::FeatHost feat;
-  Mem featHdr, featPoolMem;
-  DeltaPair featDelta;
-  int *featStart = nullptr, *featLen = nullptr;
-  mapdb::FeatRec* featPool = nullptr;
+  SpanDev<mapdb::FeatRec> dFeats;
   ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc), feat(kc) {}
 };
 
 namespace {
 
-int invalid(const std::string& what) { set_error("resident map table: %s", what.c_str()); return YDORB_ERR_INVALID_ARG; }
+// The columns of the two SoA tables, each named here and nowhere else in this file as a list: each(f) calls f(pointer-to-member,
+// elements per slot).  An arena's layout, its growth copy and its export walk the list; the byte strides come from the element types.
+struct PointColumns {
+  using Table = mapdb::SlotTables;   // its centre is no column: the centres arena is per keyframe slot
+  template <class F> static void each(F f) {
+    f(&Table::start, 1); f(&Table::end, 1); f(&Table::refKf, 1); f(&Table::pos, 3); f(&Table::bad, 1); f(&Table::refLevel, 1);
+  }
+};
+struct AttrColumns {
+  using Table = mapdb::AttrArrays;
+  template <class F> static void each(F f) {
+    f(&Table::normal, 3); f(&Table::minDistance, 1); f(&Table::maxDistance, 1); f(&Table::desc, 2); f(&Table::flags, 1);
+  }
+};
 
-size_t layPoints(Carve& C, mapdb::SlotTables& T, size_t cap) {
-  C.take(T.start, cap); C.take(T.end, cap); C.take(T.refKf, cap); C.take(T.pos, 3 * cap); C.take(T.bad, cap); C.take(T.refLevel, cap);
+template <class Cols> size_t layColumns(Carve& C, typename Cols::Table& t, size_t slots) {
+  Cols::each([&](auto col, size_t per) { C.take(t.*col, per * slots); });
   return C.L.bytes;
 }
+// A fresh arena of `cap` slots, all zero
+template <class Cols> int allocColumns(hipStream_t s, Mem& m, typename Cols::Table& t, size_t cap) {
+  typename Cols::Table sizing{};
+  Carve sz(nullptr);
+  int rc = m.alloc(layColumns<Cols>(sz, sizing, cap));
+  if (rc) return rc;
+  Carve cv(m.p);
+  layColumns<Cols>(cv, t, cap);
+  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
+  return YDORB_OK;
+}
+// The first n slots of every column, from -> to: device to device for a growth, device to host for an export's read-back, host to
+// host (a plain memcpy) for its copy-out, where a column the caller does not take has a null pointer in `to`
+template <class Cols> int copyColumns(hipStream_t s, hipMemcpyKind kind, const typename Cols::Table& to, const typename Cols::Table& from, size_t n) {
+  int rc = YDORB_OK;
+  Cols::each([&](auto col, size_t per) {
+    const size_t bytes = sizeof(*(to.*col)) * per * n;
+    if (rc || !(to.*col)) return;
+    if (kind != hipMemcpyHostToHost) rc = copyAsync(to.*col, from.*col, bytes, kind, s);
+    else if (bytes) std::memcpy(to.*col, from.*col, bytes);
+  });
+  return rc;
+}
+
 size_t layPool(Carve& C, int*& kf, uint8_t*& level, size_t cap) {
   C.take(kf, cap); C.take(level, cap);
   return C.L.bytes;
@@ -100,13 +247,8 @@ size_t layPool(Carve& C, int*& kf, uint8_t*& level, size_t cap) {
 
 // A fresh point arena of `cap` slots: all zero, every slot bad (a slot never set reads as bad with no observations)
 int allocPoints(hipStream_t s, Mem& m, mapdb::SlotTables& T, size_t cap) {
-  mapdb::SlotTables sizing{};
-  Carve sz(nullptr);
-  int rc = m.alloc(layPoints(sz, sizing, cap));
+  const int rc = allocColumns<PointColumns>(s, m, T, cap);
   if (rc) return rc;
-  Carve cv(m.p);
-  layPoints(cv, T, cap);
-  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
   HIPCHK(hipMemsetAsync(T.bad, 1, cap, s));
   return YDORB_OK;
 }
@@ -127,31 +269,10 @@ int allocPool(Mem& m, int*& kf, uint8_t*& level, size_t cap) {
   return YDORB_OK;
 }
 
-int allocRowHeaders(hipStream_t s, Mem& m, int*& rowStart, int*& rowLen, size_t cap) {   // every slot: no row
-  int rc = m.alloc(8 * cap);
-  if (rc) return rc;
-  rowStart = m.as<int>(); rowLen = rowStart + cap;
-  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
-  return YDORB_OK;
-}
-
-#define D2D(dst, src, bytes) \
-  do { if ((bytes) > 0) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, s)); } while (0)
-
 // The blocks of an apply kernel: a lane per fixed record; over the payload 2048 blocks at the most, lanes stride past that
 unsigned applyBlocks(size_t nFixed, int64_t nPayload, size_t threads) {
   const size_t forFixed = (nFixed + threads - 1) / threads, forPayload = std::min<size_t>(((size_t)nPayload + threads - 1) / threads, 2048);
   return (unsigned)std::max<size_t>(std::max(forFixed, forPayload), 1);
-}
-
-// The end of a sync: what was enqueued still reads the old arenas, so the stream drains before the handle takes each new one made
-struct NewArena { Mem* mine; ScopedMem* fresh; };
-int handOver(hipStream_t s, std::initializer_list<NewArena> arenas) {
-  bool any = false;
-  for (const NewArena& a : arenas) any = any || a.fresh->p;
-  if (any) HIPCHK(hipStreamSynchronize(s));
-  for (const NewArena& a : arenas) if (a.fresh->p) a.mine->take(*a.fresh);
-  return YDORB_OK;
 }
 
 // Applies what is staged.  Called with the mutex held and the device set; everything it enqueues goes to the handle's stream, and the
@@ -170,13 +291,9 @@ int syncPoints(ydorb_mapdb* h) {
   if (P.kfCap != P.kfCapBefore && (rc = allocCentres(s, newCentres, T.centre, (size_t)P.kfCap))) return rc;
   if (P.repack && (rc = allocPool(newPool, poolKf, poolLevel, (size_t)P.poolCap))) return rc;
   h->host.pack(P, h->delta.host.as<uint8_t>());   // nothing below can be refused for a reason of the caller's: the delta counts as applied
-  if (P.bytes) HIPCHK(hipMemcpyAsync(h->delta.dev.p, h->delta.host.p, P.bytes, hipMemcpyHostToDevice, s));
-  if (newPoints.p) {
-    const size_t n = (size_t)P.nPointsBefore;
-    D2D(T.start, h->T.start, 4 * n); D2D(T.end, h->T.end, 4 * n); D2D(T.refKf, h->T.refKf, 4 * n); D2D(T.pos, h->T.pos, 12 * n);
-    D2D(T.bad, h->T.bad, n); D2D(T.refLevel, h->T.refLevel, n);
-  }
-  if (newCentres.p) D2D(T.centre, h->T.centre, 12 * (size_t)P.nKeyframesBefore);
+  if ((rc = h->delta.upload(s, P.bytes))) return rc;
+  if (newPoints.p && (rc = copyColumns<PointColumns>(s, hipMemcpyDeviceToDevice, T, h->T, (size_t)P.nPointsBefore))) return rc;
+  if (newCentres.p && (rc = copyAsync(T.centre, h->T.centre, 12 * (size_t)P.nKeyframesBefore, hipMemcpyDeviceToDevice, s))) return rc;
   if (P.repack && P.nPointsBefore > 0) {
     mapdb::RepackArgs a;
     a.nPoints = P.nPointsBefore; a.start = T.start; a.end = T.end; a.newOff = at<int>(h->delta.dev, P.oNewOff);
@@ -200,80 +317,27 @@ int syncPoints(ydorb_mapdb* h) {
   return YDORB_OK;
 }
 
-// One span relation (mapdb_rows_host.h's SpanHost: the keyframe rows, the point views, the descriptor blocks) brought up to date: one
-// upload of its packed delta, the header growth, the repack if the pool needs it, the apply.  repack(P, start, len, oldPool, newPool)
-// and apply(P, start, len, pool) launch the relation's two kernels on the handle's stream.
-template <class T, class Repack, class Apply>
-int syncSpans(ydorb_mapdb* h, mapdb::SpanHost<T>& host, DeltaPair& delta, Mem& hdrMem, Mem& poolMem, int*& start, int*& len, T*& pool, Repack repack,
-              Apply apply) {
-  if (!host.dirty()) { host.nothingToSync(); return YDORB_OK; }
-  hipStream_t s = h->c.stream;
-  const mapdb::RowPlan P = host.plan();
-  int rc;
-  if ((rc = delta.ensure(P.bytes))) return rc;
-  ScopedMem newHdr, newPool;
-  int *st = start, *ln = len;
-  T* pl = pool;
-  if (P.hdrCap != P.hdrCapBefore && (rc = allocRowHeaders(s, newHdr, st, ln, (size_t)P.hdrCap))) return rc;
-  if (P.repack && (rc = newPool.alloc(sizeof(T) * (size_t)P.poolCap))) return rc;
-  if (newPool.p) pl = newPool.as<T>();
-  host.pack(P, delta.host.as<uint8_t>());
-  if (P.bytes) HIPCHK(hipMemcpyAsync(delta.dev.p, delta.host.p, P.bytes, hipMemcpyHostToDevice, s));
-  if (newHdr.p) { D2D(st, start, 4 * (size_t)P.nKfBefore); D2D(ln, len, 4 * (size_t)P.nKfBefore); }
-  if (P.repack && P.nKfBefore > 0) {
-    repack(P, st, ln, pool, pl);
-    HIPCHK(hipGetLastError());
-  }
-  apply(P, st, ln, pl);
-  HIPCHK(hipGetLastError());
-  if ((rc = handOver(s, {{&hdrMem, &newHdr}, {&poolMem, &newPool}}))) return rc;
-  start = st; len = ln; pool = pl;
-  return YDORB_OK;
-}
-
-// int32 spans: the keyframe rows and the point views share the two kernels of mapdb_rows_kernels.hip.h
-int syncIntSpans(ydorb_mapdb* h, mapdb::SpanHost<int32_t>& host, DeltaPair& delta, Mem& hdrMem, Mem& poolMem, int*& start, int*& len, int*& pool) {
-  hipStream_t s = h->c.stream;
-  return syncSpans(h, host, delta, hdrMem, poolMem, start, len, pool,
-    [&](const mapdb::RowPlan& P, int* st, int* ln, int* oldPool, int* newPool) {
-      mapdb::RowsRepackArgs a;
-      a.nKf = P.nKfBefore; a.rowStart = st; a.rowLen = ln; a.newOff = at<int>(delta.dev, P.oNewOff); a.oldPool = oldPool; a.newPool = newPool;
-      hipLaunchKernelGGL(mapdb::k_mapdb_rows_repack, dim3((unsigned)((P.nKfBefore + mapdb::kRowWaves - 1) / mapdb::kRowWaves)), dim3(mapdb::kRowThreads), 0, s, a);
+// The plain span relations (the keyframe rows, the point views, the descriptor blocks) share the two kernels of
+// mapdb_span_kernels.hip.h: an element moves as sizeof(T) / sizeof(unit) units, an int for the int32 spans, a uint4 where it can.
+template <class T> int syncPlainSpans(hipStream_t s, SpanDev<T>& d, mapdb::SpanHost<T>& host) {
+  using U = std::conditional_t<sizeof(T) % sizeof(uint4) == 0, uint4, int>;
+  constexpr int kPer = sizeof(T) / sizeof(U);
+  return d.sync(s, host,
+    [&](const mapdb::RowPlan& P, int* st, int* ln, T* oldPool, T* newPool) {
+      mapdb::SpanRepackArgs<U> a;
+      a.nSlots = P.nKfBefore; a.start = st; a.len = ln; a.newOff = at<int>(d.delta.dev, P.oNewOff);
+      a.oldPool = reinterpret_cast<const U*>(oldPool); a.newPool = reinterpret_cast<U*>(newPool);
+      hipLaunchKernelGGL((mapdb::k_mapdb_span_repack<U, kPer>), dim3((unsigned)((P.nKfBefore + mapdb::kSpanWaves - 1) / mapdb::kSpanWaves)),
+                         dim3(mapdb::kSpanThreads), 0, s, a);
     },
-    [&](const mapdb::RowPlan& P, int* st, int* ln, int* pl) {
-      mapdb::RowsApplyArgs a;
-      a.nHeaderRec = P.nHeaderRec; a.nEntryRec = P.nEntryRec; a.nPayload = (int)P.nPayload; a.tail = (int)P.tail;
-      a.header = at<mapdb::RowHeaderRec>(delta.dev, P.oHeader); a.entry = at<mapdb::RowEntryRec>(delta.dev, P.oEntry);
-      a.payload = at<int>(delta.dev, P.oPayload);
-      a.rowStart = st; a.rowLen = ln; a.pool = pl;
-      const unsigned blocks = applyBlocks((size_t)P.nHeaderRec + P.nEntryRec, P.nPayload, mapdb::kRowThreads);
-      hipLaunchKernelGGL(mapdb::k_mapdb_rows_apply, dim3(blocks), dim3(mapdb::kRowThreads), 0, s, a);
-    });
-}
-
-// The staged rows, after the points: a row may name a point that got its slot in the same interval.
-int syncRows(ydorb_mapdb* h) { return syncIntSpans(h, h->rows, h->rowDelta, h->rowHdr, h->rowPoolMem, h->rowStart, h->rowLen, h->rowPool); }
-
-// The staged views and descriptor blocks, after points and rows: a view may name a keyframe, and a query a point, of the same interval.
-int syncDescriptors(ydorb_mapdb* h) {
-  int rc = syncIntSpans(h, h->desc.views, h->viewDelta, h->viewHdr, h->viewPoolMem, h->viewStart, h->viewLen, h->viewPool);
-  if (rc) return rc;
-  hipStream_t s = h->c.stream;
-  DeltaPair& delta = h->blockDelta;
-  return syncSpans(h, h->desc.blocks, delta, h->blockHdr, h->blockPoolMem, h->blockStart, h->blockLen, h->blockPool,
-    [&](const mapdb::RowPlan& P, int* st, int* ln, mapdb::DescRow* oldPool, mapdb::DescRow* newPool) {
-      mapdb::DescRepackArgs a;
-      a.nKf = P.nKfBefore; a.blockStart = st; a.blockLen = ln; a.newOff = at<int>(delta.dev, P.oNewOff);
-      a.oldPool = reinterpret_cast<const uint4*>(oldPool); a.newPool = reinterpret_cast<uint4*>(newPool);
-      hipLaunchKernelGGL(mapdb::k_mapdb_desc_repack, dim3((unsigned)((P.nKfBefore + mapdb::kDescWaves - 1) / mapdb::kDescWaves)), dim3(mapdb::kDescThreads), 0, s, a);
-    },
-    [&](const mapdb::RowPlan& P, int* st, int* ln, mapdb::DescRow* pl) {
-      mapdb::DescApplyArgs a;
-      a.nHeaderRec = P.nHeaderRec; a.nPayload16 = 2 * P.nPayload; a.tail = (int)P.tail;
-      a.header = at<mapdb::RowHeaderRec>(delta.dev, P.oHeader); a.payload = at<uint4>(delta.dev, P.oPayload);
-      a.blockStart = st; a.blockLen = ln; a.pool = reinterpret_cast<uint4*>(pl);
-      const unsigned blocks = applyBlocks((size_t)P.nHeaderRec, 2 * P.nPayload, mapdb::kDescThreads);
-      hipLaunchKernelGGL(mapdb::k_mapdb_desc_apply, dim3(blocks), dim3(mapdb::kDescThreads), 0, s, a);
+    [&](const mapdb::RowPlan& P, int* st, int* ln, T* pl) {
+      mapdb::SpanApplyArgs<U> a;
+      a.nHeaderRec = P.nHeaderRec; a.nEntryRec = P.nEntryRec; a.tail = (int)P.tail; a.nPayload = kPer * P.nPayload;
+      a.header = at<mapdb::RowHeaderRec>(d.delta.dev, P.oHeader); a.entry = at<mapdb::RowEntryRec>(d.delta.dev, P.oEntry);
+      a.payload = at<U>(d.delta.dev, P.oPayload);
+      a.start = st; a.len = ln; a.pool = reinterpret_cast<U*>(pl);
+      const unsigned blocks = applyBlocks((size_t)P.nHeaderRec + P.nEntryRec, kPer * P.nPayload, mapdb::kSpanThreads);
+      hipLaunchKernelGGL((mapdb::k_mapdb_span_apply<U, kPer>), dim3(blocks), dim3(mapdb::kSpanThreads), 0, s, a);
     });
 }
 
@@ -284,8 +348,8 @@ uint32_t* featRightX(mapdb::FeatRec* pool, int64_t cap) { return reinterpret_cas
 // The staged features, after the blocks: a query reads a keyframe's features and its block together.
 int syncFeatures(ydorb_mapdb* h) {
   hipStream_t s = h->c.stream;
-  DeltaPair& delta = h->featDelta;
-  return syncSpans(h, h->feat.feats, delta, h->featHdr, h->featPoolMem, h->featStart, h->featLen, h->featPool,
+  DeltaPair& delta = h->dFeats.delta;
+  return h->dFeats.sync(s, h->feat.feats,
     [&](const mapdb::RowPlan& P, int* st, int* ln, mapdb::FeatRec* oldPool, mapdb::FeatRec* newPool) {
       mapdb::FeatRepackArgs a;
       a.nKf = P.nKfBefore; a.featStart = st; a.featLen = ln; a.newOff = at<int>(delta.dev, P.oNewOff);
@@ -302,24 +366,8 @@ int syncFeatures(ydorb_mapdb* h) {
     });
 }
 
-size_t layAttributes(Carve& C, mapdb::AttrArrays& A, size_t cap) {
-  C.take(A.normal, 3 * cap); C.take(A.minDistance, cap); C.take(A.maxDistance, cap); C.take(A.desc, 2 * cap); C.take(A.flags, cap);
-  return C.L.bytes;
-}
-// A fresh attribute arena of `cap` slots: all zero, what a slot never set reads as
-int allocAttributes(hipStream_t s, Mem& m, mapdb::AttrArrays& A, size_t cap) {
-  mapdb::AttrArrays sizing{};
-  Carve sz(nullptr);
-  int rc = m.alloc(layAttributes(sz, sizing, cap));
-  if (rc) return rc;
-  Carve cv(m.p);
-  layAttributes(cv, A, cap);
-  HIPCHK(hipMemsetAsync(m.p, 0, m.cap, s));
-  return YDORB_OK;
-}
-
 // The staged attributes, after everything else: the arena follows the point table's capacity (syncPoints may just have grown it), then
-// one upload of the records and k_mapdb_attr_apply.
+// one upload of the records and k_mapdb_attr_apply.  A fresh arena is all zero, what a slot never set reads as.
 int syncAttributes(ydorb_mapdb* h) {
   mapdb::AttrHost& host = h->attr;
   if (!host.needsSync(h->host.pointCap())) { host.nothingToSync(); return YDORB_OK; }
@@ -329,14 +377,10 @@ int syncAttributes(ydorb_mapdb* h) {
   if ((rc = h->attrDelta.ensure(P.bytes))) return rc;
   ScopedMem fresh;
   mapdb::AttrArrays A = h->A;
-  if (P.cap != P.capBefore && (rc = allocAttributes(s, fresh, A, (size_t)P.cap))) return rc;
+  if (P.cap != P.capBefore && (rc = allocColumns<AttrColumns>(s, fresh, A, (size_t)P.cap))) return rc;
   host.pack(P, h->attrDelta.host.as<uint8_t>());   // every allocation is made: only a HIP error can fail below, and the delta counts as applied
-  if (P.bytes) HIPCHK(hipMemcpyAsync(h->attrDelta.dev.p, h->attrDelta.host.p, P.bytes, hipMemcpyHostToDevice, s));
-  if (fresh.p) {
-    const size_t n = (size_t)P.capBefore;
-    D2D(A.normal, h->A.normal, 12 * n); D2D(A.minDistance, h->A.minDistance, 4 * n); D2D(A.maxDistance, h->A.maxDistance, 4 * n);
-    D2D(A.desc, h->A.desc, 32 * n); D2D(A.flags, h->A.flags, n);
-  }
+  if ((rc = h->attrDelta.upload(s, P.bytes))) return rc;
+  if (fresh.p && (rc = copyColumns<AttrColumns>(s, hipMemcpyDeviceToDevice, A, h->A, (size_t)P.capBefore))) return rc;
   if (P.nRec) {
     hipLaunchKernelGGL(mapdb::k_mapdb_attr_apply, dim3((unsigned)((P.nRec + mapdb::kAttrThreads - 1) / mapdb::kAttrThreads)), dim3(mapdb::kAttrThreads), 0, s,
                        P.nRec, h->attrDelta.dev.as<mapdb::AttrRec>(), A);
@@ -347,10 +391,14 @@ int syncAttributes(ydorb_mapdb* h) {
   return YDORB_OK;
 }
 
+// Everything staged, in the one order: a row may name a point, a view a keyframe and a query a point that got its slot in the same
+// interval, and a query reads a keyframe's features and its block together.
 int sync(ydorb_mapdb* h) {
+  hipStream_t s = h->c.stream;
   int rc = syncPoints(h);
-  if (!rc) rc = syncRows(h);
-  if (!rc) rc = syncDescriptors(h);
+  if (!rc) rc = syncPlainSpans(s, h->dRows, h->rows);
+  if (!rc) rc = syncPlainSpans(s, h->dViews, h->desc.views);
+  if (!rc) rc = syncPlainSpans(s, h->dBlocks, h->desc.blocks);
   if (!rc && h->feat.enabled()) rc = syncFeatures(h);
   return rc || !h->attr.enabled() ? rc : syncAttributes(h);
 }
@@ -405,6 +453,19 @@ mapmaint::MapSource sourceOf(const ydorb_mapdb* h) {
   return src;
 }
 
+// Everything a new handle owns but the two opt-in parts, at the capacities its host halves start with
+int allocHandle(ydorb_mapdb* h) {
+  int rc = h->c.init(h->device);
+  if (rc) return rc;
+  hipStream_t s = h->c.stream;
+  if ((rc = allocPoints(s, h->points, h->T, (size_t)h->host.pointCap())) || (rc = allocCentres(s, h->centres, h->T.centre, (size_t)h->host.kfCap())) ||
+      (rc = allocPool(h->pool, h->poolKf, h->poolLevel, (size_t)h->host.poolCap())) || (rc = h->dRows.alloc(s, h->rows)) ||
+      (rc = h->dViews.alloc(s, h->desc.views)) || (rc = h->dBlocks.alloc(s, h->desc.blocks)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  return YDORB_OK;
+}
+
 }  // namespace
 
 extern "C" int ydorb_mapdb_create(int32_t device, int32_t point_capacity, int32_t keyframe_capacity, int64_t observation_capacity,
@@ -417,21 +478,7 @@ extern "C" int ydorb_mapdb_create(int32_t device, int32_t point_capacity, int32_
   if (rc) return rc;
   ydorb_mapdb* h = new ydorb_mapdb(point_capacity, keyframe_capacity, observation_capacity);
   h->device = device;
-  if (!(rc = h->c.init(device)) && !(rc = allocPoints(h->c.stream, h->points, h->T, (size_t)h->host.pointCap())) &&
-      !(rc = allocCentres(h->c.stream, h->centres, h->T.centre, (size_t)h->host.kfCap())) &&
-      !(rc = allocPool(h->pool, h->poolKf, h->poolLevel, (size_t)h->host.poolCap())) &&
-      !(rc = allocRowHeaders(h->c.stream, h->rowHdr, h->rowStart, h->rowLen, (size_t)h->rows.hdrCap())) &&
-      !(rc = h->rowPoolMem.alloc(4 * (size_t)h->rows.poolCap())) &&
-      !(rc = allocRowHeaders(h->c.stream, h->viewHdr, h->viewStart, h->viewLen, (size_t)h->desc.views.hdrCap())) &&
-      !(rc = allocRowHeaders(h->c.stream, h->blockHdr, h->blockStart, h->blockLen, (size_t)h->desc.blocks.hdrCap())) &&
-      !(rc = h->viewPoolMem.alloc(4 * (size_t)h->desc.views.poolCap())) &&
-      !(rc = h->blockPoolMem.alloc(sizeof(mapdb::DescRow) * (size_t)h->desc.blocks.poolCap())) && hipStreamSynchronize(h->c.stream) != hipSuccess) {
-    set_error("hipStreamSynchronize failed");
-    rc = YDORB_ERR_HIP;
-  }
-  if (rc) { ydorb_mapdb_destroy(h); return rc; }
-  h->rowPool = h->rowPoolMem.as<int>();
-  h->viewPool = h->viewPoolMem.as<int>(); h->blockPool = h->blockPoolMem.as<mapdb::DescRow>();
+  if ((rc = allocHandle(h))) { ydorb_mapdb_destroy(h); return rc; }
   *out = h;
   return YDORB_OK;
 }
@@ -441,11 +488,9 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   (void)hipSetDevice(h->device);
   if (h->c.stream) { (void)hipStreamSynchronize(h->c.stream); (void)hipStreamDestroy(h->c.stream); }
   h->c.releaseBuffers();
-  h->points.release(); h->centres.release(); h->pool.release(); h->delta.release();
-  h->rowHdr.release(); h->rowPoolMem.release(); h->rowDelta.release(); h->rowset.release();
-  h->viewHdr.release(); h->viewPoolMem.release(); h->viewDelta.release(); h->blockHdr.release(); h->blockPoolMem.release(); h->blockDelta.release();
+  h->points.release(); h->centres.release(); h->pool.release(); h->delta.release(); h->rowset.release();
   h->attrMem.release(); h->attrDelta.release();
-  h->featHdr.release(); h->featPoolMem.release(); h->featDelta.release();
+  h->dRows.release(); h->dViews.release(); h->dBlocks.release(); h->dFeats.release();
   delete h;
 }
 
@@ -459,11 +504,9 @@ extern "C" int ydorb_mapdb_clear(ydorb_mapdb_t* h) {
   h->attr.clear();
   h->feat.clear();
   hipStream_t s = h->c.stream;   // every slot reads as never set again
-  if (h->featHdr.p) HIPCHK(hipMemsetAsync(h->featHdr.p, 0, h->featHdr.cap, s));
+  int rc;
+  if ((rc = h->dRows.zeroHeaders(s)) || (rc = h->dViews.zeroHeaders(s)) || (rc = h->dBlocks.zeroHeaders(s)) || (rc = h->dFeats.zeroHeaders(s))) return rc;
   if (h->attrMem.p) HIPCHK(hipMemsetAsync(h->attrMem.p, 0, h->attrMem.cap, s));
-  HIPCHK(hipMemsetAsync(h->rowHdr.p, 0, h->rowHdr.cap, s));
-  HIPCHK(hipMemsetAsync(h->viewHdr.p, 0, h->viewHdr.cap, s));
-  HIPCHK(hipMemsetAsync(h->blockHdr.p, 0, h->blockHdr.cap, s));
   if (h->rowsetCap) {
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->first, INT32_MAX, h->rowsetCap, s));
     HIPCHK(hipMemsetAsync(h->seenStamp, 0, 4 * h->rowsetCap, s));
@@ -661,25 +704,28 @@ extern "C" int ydorb_mapdb_export(ydorb_mapdb_t* h, int32_t* obs_start, int32_t*
   if (rc) return rc;
   StagedCtx& c = h->c;
   const size_t used = (size_t)h->host.poolUsed();
-  Layout D;
-  const size_t dStart = D.add(4 * np), dEnd = D.add(4 * np), dRef = D.add(4 * np), dPos = D.add(12 * np), dBad = D.add(np), dLvl = D.add(np),
-               dCen = D.add(12 * nk), dKf = D.add(4 * used), dOl = D.add(used);
-  if ((rc = c.hDown.ensure(D.bytes))) return rc;
+  mapdb::SlotTables H{};   // the read-back area in c.hDown: the table's columns, the centres, the used part of the pool
+  int* hKf = nullptr;
+  uint8_t* hLevel = nullptr;
+  const auto lay = [&](void* base) {
+    Carve C(base);
+    layColumns<PointColumns>(C, H, np);
+    C.take(H.centre, 3 * nk);
+    return layPool(C, hKf, hLevel, used);
+  };
+  if ((rc = c.hDown.ensure(lay(nullptr)))) return rc;
+  lay(c.hDown.p);
   hipStream_t s = c.stream;
-#define DOWN(off, src, bytes) \
-  do { if ((bytes) > 0) HIPCHK(hipMemcpyAsync(at<void>(c.hDown, off), (src), (bytes), hipMemcpyDeviceToHost, s)); } while (0)
-  DOWN(dStart, h->T.start, 4 * np); DOWN(dEnd, h->T.end, 4 * np); DOWN(dRef, h->T.refKf, 4 * np); DOWN(dPos, h->T.pos, 12 * np);
-  DOWN(dBad, h->T.bad, np); DOWN(dLvl, h->T.refLevel, np); DOWN(dCen, h->T.centre, 12 * nk);
-  DOWN(dKf, h->poolKf, 4 * used); DOWN(dOl, h->poolLevel, used);
-#undef DOWN
+  if ((rc = copyColumns<PointColumns>(s, hipMemcpyDeviceToHost, H, h->T, np)) ||
+      (rc = copyAsync(H.centre, h->T.centre, 12 * nk, hipMemcpyDeviceToHost, s)) ||
+      (rc = copyAsync(hKf, h->poolKf, 4 * used, hipMemcpyDeviceToHost, s)) || (rc = copyAsync(hLevel, h->poolLevel, used, hipMemcpyDeviceToHost, s)))
+    return rc;
   HIPCHK(hipStreamSynchronize(s));
-  mapdb::flatten((int32_t)np, at<int32_t>(c.hDown, dStart), at<int32_t>(c.hDown, dEnd), at<int32_t>(c.hDown, dKf), at<uint8_t>(c.hDown, dOl),
-                 obs_start, obs_kf, obs_level);
-  if (np) {
-    std::memcpy(ref_kf, at<void>(c.hDown, dRef), 4 * np); std::memcpy(pos, at<void>(c.hDown, dPos), 12 * np);
-    std::memcpy(bad, at<void>(c.hDown, dBad), np); std::memcpy(ref_level, at<void>(c.hDown, dLvl), np);
-  }
-  if (nk) std::memcpy(centre, at<void>(c.hDown, dCen), 12 * nk);
+  mapdb::flatten((int32_t)np, H.start, H.end, hKf, hLevel, obs_start, obs_kf, obs_level);
+  mapdb::SlotTables out{};   // start / end stay null: they went out through flatten
+  out.refKf = ref_kf; out.pos = pos; out.bad = bad; out.refLevel = ref_level;
+  copyColumns<PointColumns>(s, hipMemcpyHostToHost, out, H, np);
+  if (nk) std::memcpy(centre, H.centre, 12 * nk);
   return YDORB_OK;
 }
 
@@ -717,18 +763,9 @@ extern "C" int ydorb_mapdb_export_rows(ydorb_mapdb_t* h, int32_t* row_start, int
   int rc = sync(h);
   if (rc) return rc;
   StagedCtx& c = h->c;
-  const size_t held = (size_t)h->rows.nKeyframes(), used = (size_t)h->rows.poolUsed();
-  Layout D;
-  const size_t dStart = D.add(4 * held), dLen = D.add(4 * held), dPool = D.add(4 * used);
-  D.add(16);
-  if ((rc = c.hDown.ensure(D.bytes))) return rc;
-  hipStream_t s = c.stream;
-  if (held) {
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dStart), h->rowStart, 4 * held, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dLen), h->rowLen, 4 * held, hipMemcpyDeviceToHost, s));
-  }
-  if (used) HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dPool), h->rowPool, 4 * used, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  const size_t held = (size_t)h->rows.nKeyframes();
+  size_t dStart, dLen, dPool;
+  if ((rc = h->dRows.download(c, held, (size_t)h->rows.poolUsed(), dStart, dLen, dPool))) return rc;
   mapdb::flattenRows(h->host.nKeyframes(), (int32_t)held, at<int32_t>(c.hDown, dStart), at<int32_t>(c.hDown, dLen), at<int32_t>(c.hDown, dPool),
                      row_start, point_slot);
   return YDORB_OK;
@@ -787,7 +824,7 @@ extern "C" int ydorb_mapdb_points_of_keyframes(ydorb_mapdb_t* h, const int32_t* 
   mapdb::RowsetArgs a;
   a.nKf = n_kf; a.nE = (int)nE; a.nSeen = n_seen; a.stamp = h->stamp; a.capacity = (int)capOut; a.nBlocks = (int)nB;
   a.kfSlots = at<int>(c.up, oKf); a.eStart = at<int>(c.up, oEs); a.seen = at<int>(c.up, oSeen);
-  a.rowStart = h->rowStart; a.rowLen = h->rowLen; a.pool = h->rowPool; a.bad = h->T.bad;
+  a.rowStart = h->dRows.start; a.rowLen = h->dRows.len; a.pool = h->dRows.pool; a.bad = h->T.bad;
   a.first = h->first; a.seenStamp = h->seenStamp;
   a.ent = at<int>(c.scratch, wEnt); a.blockTotal = at<int>(c.scratch, wBlock);
   a.outSlots = at<int>(c.down, dSlots); a.outSeen = at<uint8_t>(c.down, dSeen); a.total = at<int>(c.down, dTotal);
@@ -853,11 +890,8 @@ extern "C" int ydorb_mapdb_reserve_descriptors(ydorb_mapdb_t* h, int64_t view_ca
   if (!h->desc.reserve(view_capacity, descriptor_capacity, err)) return invalid(err);
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->c.stream));   // nothing in flight reads the arenas given back below
-  int rc;
-  if ((rc = h->viewPoolMem.alloc(4 * (size_t)h->desc.views.poolCap())) || (rc = h->blockPoolMem.alloc(sizeof(mapdb::DescRow) * (size_t)h->desc.blocks.poolCap())))
-    return rc;
-  h->viewPool = h->viewPoolMem.as<int>(); h->blockPool = h->blockPoolMem.as<mapdb::DescRow>();
-  return YDORB_OK;
+  const int rc = h->dViews.allocPool(h->desc.views);
+  return rc ? rc : h->dBlocks.allocPool(h->desc.blocks);
 }
 
 extern "C" int ydorb_mapdb_set_keyframe_descriptors(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n, const int32_t* desc_start,
@@ -911,8 +945,8 @@ extern "C" int ydorb_mapdb_distinctive_descriptors(ydorb_mapdb_t* h, const int32
   mapdb::DistinctiveArgs a;
   a.n = n; a.nViewHdr = h->desc.views.hdrCap(); a.nBlockHdr = h->desc.blocks.hdrCap();
   a.slots = c.up.as<int>(); a.bad = h->T.bad;
-  a.viewStart = h->viewStart; a.viewLen = h->viewLen; a.viewPool = h->viewPool;
-  a.blockStart = h->blockStart; a.blockLen = h->blockLen; a.blockPool = reinterpret_cast<const uint4*>(h->blockPool);
+  a.viewStart = h->dViews.start; a.viewLen = h->dViews.len; a.viewPool = h->dViews.pool;
+  a.blockStart = h->dBlocks.start; a.blockLen = h->dBlocks.len; a.blockPool = reinterpret_cast<const uint4*>(h->dBlocks.pool);
   a.best = at<int>(c.down, dBest); a.bestView = at<int>(c.down, dView); a.descOut = at<uint4>(c.down, dDesc); a.status = at<uint8_t>(c.down, dSt);
   hipLaunchKernelGGL(mapdb::k_mapdb_distinctive, dim3((unsigned)((nq + mapdb::kDescWaves - 1) / mapdb::kDescWaves)), dim3(mapdb::kDescThreads), 0, s, a);
   HIPCHK(hipGetLastError());
@@ -933,25 +967,6 @@ extern "C" int ydorb_mapdb_distinctive_descriptors(ydorb_mapdb_t* h, const int32
   return YDORB_OK;
 }
 
-// the headers and the used part of the pool of one span relation, read back into c.hDown
-template <class T> int downloadSpans(ydorb_mapdb* h, size_t held, size_t used, const int* start, const int* len, const T* pool, size_t& dStart,
-                                     size_t& dLen, size_t& dPool) {
-  StagedCtx& c = h->c;
-  Layout D;
-  dStart = D.add(4 * held); dLen = D.add(4 * held); dPool = D.add(sizeof(T) * used);
-  D.add(16);
-  int rc = c.hDown.ensure(D.bytes);
-  if (rc) return rc;
-  hipStream_t s = c.stream;
-  if (held) {
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dStart), start, 4 * held, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dLen), len, 4 * held, hipMemcpyDeviceToHost, s));
-  }
-  if (used) HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dPool), pool, sizeof(T) * used, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return YDORB_OK;
-}
-
 extern "C" int ydorb_mapdb_export_views(ydorb_mapdb_t* h, int32_t* view_start, int32_t* view_kf, int32_t* view_idx) {
   if (!h) return invalid("null handle");
   std::lock_guard<std::mutex> lock(h->c.mu);
@@ -962,7 +977,7 @@ extern "C" int ydorb_mapdb_export_views(ydorb_mapdb_t* h, int32_t* view_start, i
   if (rc) return rc;
   size_t dStart, dLen, dPool;
   const size_t held = (size_t)h->desc.views.nKeyframes();
-  if ((rc = downloadSpans(h, held, (size_t)h->desc.views.poolUsed(), h->viewStart, h->viewLen, h->viewPool, dStart, dLen, dPool))) return rc;
+  if ((rc = h->dViews.download(h->c, held, (size_t)h->desc.views.poolUsed(), dStart, dLen, dPool))) return rc;
   mapdb::flattenViews(h->host.nPoints(), (int32_t)held, at<int32_t>(h->c.hDown, dStart), at<int32_t>(h->c.hDown, dLen), at<int32_t>(h->c.hDown, dPool),
                       view_start, view_kf, view_idx);
   return YDORB_OK;
@@ -978,7 +993,7 @@ extern "C" int ydorb_mapdb_export_descriptors(ydorb_mapdb_t* h, int32_t* desc_st
   if (rc) return rc;
   size_t dStart, dLen, dPool;
   const size_t held = (size_t)h->desc.blocks.nKeyframes();
-  if ((rc = downloadSpans(h, held, (size_t)h->desc.blocks.poolUsed(), h->blockStart, h->blockLen, h->blockPool, dStart, dLen, dPool))) return rc;
+  if ((rc = h->dBlocks.download(h->c, held, (size_t)h->desc.blocks.poolUsed(), dStart, dLen, dPool))) return rc;
   mapdb::flattenRows(h->host.nKeyframes(), (int32_t)held, at<int32_t>(h->c.hDown, dStart), at<int32_t>(h->c.hDown, dLen),
                      at<mapdb::DescRow>(h->c.hDown, dPool), desc_start, reinterpret_cast<mapdb::DescRow*>(desc));
   return YDORB_OK;
@@ -990,7 +1005,7 @@ extern "C" int ydorb_mapdb_enable_attributes(ydorb_mapdb_t* h) {
   std::lock_guard<std::mutex> lock(h->c.mu);
   if (h->attr.enabled()) return YDORB_OK;
   HIPCHK(hipSetDevice(h->device));
-  int rc = allocAttributes(h->c.stream, h->attrMem, h->A, (size_t)h->host.pointCap());
+  int rc = allocColumns<AttrColumns>(h->c.stream, h->attrMem, h->A, (size_t)h->host.pointCap());
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(h->c.stream));
   h->attr.enable(h->host.pointCap());
@@ -1024,20 +1039,16 @@ extern "C" int ydorb_mapdb_export_attributes(ydorb_mapdb_t* h, float* normal, fl
   if (rc) return rc;
   if (np == 0) return YDORB_OK;
   StagedCtx& c = h->c;
-  Layout D;
-  const size_t dNrm = D.add(12 * np), dMin = D.add(4 * np), dMax = D.add(4 * np), dDesc = D.add(32 * np), dFlg = D.add(np);
-  if ((rc = c.hDown.ensure(D.bytes))) return rc;
+  mapdb::AttrArrays H{}, out{};   // the read-back area in c.hDown, and the caller's arrays
+  out.normal = normal; out.minDistance = min_distance; out.maxDistance = max_distance; out.desc = reinterpret_cast<uint4*>(desc); out.flags = flags;
+  Carve sz(nullptr);
+  if ((rc = c.hDown.ensure(layColumns<AttrColumns>(sz, H, np)))) return rc;
+  Carve cv(c.hDown.p);
+  layColumns<AttrColumns>(cv, H, np);
   hipStream_t s = c.stream;
-  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dNrm), h->A.normal, 12 * np, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dMin), h->A.minDistance, 4 * np, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dMax), h->A.maxDistance, 4 * np, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dDesc), h->A.desc, 32 * np, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dFlg), h->A.flags, np, hipMemcpyDeviceToHost, s));
+  if ((rc = copyColumns<AttrColumns>(s, hipMemcpyDeviceToHost, H, h->A, np))) return rc;
   HIPCHK(hipStreamSynchronize(s));
-  std::memcpy(normal, at<void>(c.hDown, dNrm), 12 * np); std::memcpy(min_distance, at<void>(c.hDown, dMin), 4 * np);
-  std::memcpy(max_distance, at<void>(c.hDown, dMax), 4 * np); std::memcpy(desc, at<void>(c.hDown, dDesc), 32 * np);
-  std::memcpy(flags, at<void>(c.hDown, dFlg), np);
-  return YDORB_OK;
+  return copyColumns<AttrColumns>(s, hipMemcpyHostToHost, out, H, np);
 }
 
 // sync; one upload of views, list starts, slots and skip bytes; one lane per list entry; one read-back; one synchronise
@@ -1098,12 +1109,9 @@ extern "C" int ydorb_mapdb_enable_features(ydorb_mapdb_t* h) {
   std::lock_guard<std::mutex> lock(h->c.mu);
   if (h->feat.enabled()) return YDORB_OK;
   HIPCHK(hipSetDevice(h->device));
-  int rc;
-  if ((rc = allocRowHeaders(h->c.stream, h->featHdr, h->featStart, h->featLen, (size_t)h->feat.feats.hdrCap())) ||
-      (rc = h->featPoolMem.alloc(sizeof(mapdb::FeatRec) * (size_t)h->feat.feats.poolCap())))
-    return rc;
+  const int rc = h->dFeats.alloc(h->c.stream, h->feat.feats);
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(h->c.stream));
-  h->featPool = h->featPoolMem.as<mapdb::FeatRec>();
   h->feat.enable();
   return YDORB_OK;
 }
@@ -1137,22 +1145,12 @@ extern "C" int ydorb_mapdb_export_features(ydorb_mapdb_t* h, int32_t* feat_start
   if (rc) return rc;
   StagedCtx& c = h->c;
   const size_t held = (size_t)h->feat.feats.nKeyframes(), used = (size_t)h->feat.feats.poolUsed();
-  Layout D;
-  const size_t dStart = D.add(4 * held), dLen = D.add(4 * held), dKps = D.add(sizeof(YdKeyPoint) * used), dRx = D.add(4 * used);
-  D.add(16);
-  if ((rc = c.hDown.ensure(D.bytes))) return rc;
-  hipStream_t s = c.stream;
-  if (held) {
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dStart), h->featStart, 4 * held, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dLen), h->featLen, 4 * held, hipMemcpyDeviceToHost, s));
-  }
-  if (used) {
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dKps), featKps(h->featPool), sizeof(YdKeyPoint) * used, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(at<void>(c.hDown, dRx), featRightX(h->featPool, h->feat.feats.poolCap()), 4 * used, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  mapdb::flattenFeatures(h->host.nKeyframes(), (int32_t)held, at<int32_t>(c.hDown, dStart), at<int32_t>(c.hDown, dLen), at<YdKeyPoint>(c.hDown, dKps),
-                         at<float>(c.hDown, dRx), feat_start, kps, right_x);
+  mapdb::FeatRec* pool = h->dFeats.pool;
+  PoolPart part[2] = {{featKps(pool), sizeof(YdKeyPoint) * used, 0}, {featRightX(pool, h->feat.feats.poolCap()), 4 * used, 0}};   // the arena's two arrays
+  size_t dStart, dLen;
+  if ((rc = h->dFeats.download(c, held, dStart, dLen, part))) return rc;
+  mapdb::flattenFeatures(h->host.nKeyframes(), (int32_t)held, at<int32_t>(c.hDown, dStart), at<int32_t>(c.hDown, dLen), at<YdKeyPoint>(c.hDown, part[0].at),
+                         at<float>(c.hDown, part[1].at), feat_start, kps, right_x);
   return YDORB_OK;
 }
 
@@ -1197,9 +1195,9 @@ int ydorb::mapdb::lockResidentFuse(ydorb_mapdb_t* h, int32_t device, const int32
   out = residentOf(h);
   kf.obsKf = h->poolKf;
   kf.nFeatHdr = h->feat.feats.hdrCap(); kf.nBlockHdr = h->desc.blocks.hdrCap();
-  kf.featStart = h->featStart; kf.featLen = h->featLen;
-  kf.kps = h->featPool; kf.rightX = reinterpret_cast<const float*>(featRightX(h->featPool, h->feat.feats.poolCap()));
-  kf.blockStart = h->blockStart; kf.blockLen = h->blockLen; kf.blockPool = reinterpret_cast<const uint8_t*>(h->blockPool);
+  kf.featStart = h->dFeats.start; kf.featLen = h->dFeats.len;
+  kf.kps = h->dFeats.pool; kf.rightX = reinterpret_cast<const float*>(featRightX(h->dFeats.pool, h->feat.feats.poolCap()));
+  kf.blockStart = h->dBlocks.start; kf.blockLen = h->dBlocks.len; kf.blockPool = reinterpret_cast<const uint8_t*>(h->dBlocks.pool);
   lock.release();   // held until unlockResident
   return YDORB_OK;
 }

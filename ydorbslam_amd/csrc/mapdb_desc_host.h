@@ -4,7 +4,8 @@
 //            every payload offset of a delta is a multiple of 16 bytes (the sections are 16-byte aligned, a row is 32 bytes).
 //   views    point slot -> where the point is seen: (keyframe slot, keypoint index) pairs interleaved in one int32 span of length 2m, in
 //            the order computeDistinctiveDescriptors iterates the observation container in.  The span format is the keyframe rows', and
-//            so are the delta, the kernels and the host execution (k_mapdb_rows_apply / k_mapdb_rows_repack, executeRows).
+//            so are the delta, the kernels and the host execution (k_mapdb_span_apply / k_mapdb_span_repack, executeRows).  The blocks
+//            use the same two kernels, moving a row as two uint4 (mapdb_span_kernels.hip.h).
 // This file adds what the two do not share with the rows: the validation of the two setters and of the query, the stats, and the
 // query executed on host tables as the reference's sequential loop (distinctiveOnHost).  No HIP here: a plain host compiler builds it
 // (tests/cpu_harness/mapdb_desc_check.cpp).

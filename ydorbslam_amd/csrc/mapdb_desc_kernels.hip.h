@@ -1,11 +1,6 @@
-// gfx950 HIP kernels of the resident table's descriptor blocks and of the distinctive-descriptor query on it (include/ydorb/c_api.h,
-// "Resident descriptors").  The point views are int32 spans and use the keyframe rows' two kernels
-// (mapdb_rows_kernels.hip.h).
-//   k_mapdb_desc_apply    executes one packed block delta (mapdb_desc_host.h): lane i below the header count scatters header record i
-//                         (start / length of its keyframe slot), then all lanes stride over the payload, 16 bytes each, into the
-//                         pool's tail.  The host coalesced the delta: no two lanes store to one address.  Plain vector stores.
-//   k_mapdb_desc_repack   one wave per keyframe slot, lanes striding over the block's 16-byte halves, from the old arena to the offset
-//                         the host computed in the new one.  A block the delta replaces carries -1 and is left to the apply.
+// gfx950 HIP kernel of the distinctive-descriptor query on the resident table's descriptor blocks and point views (include/ydorb/c_api.h,
+// "Resident descriptors").  The blocks and the views themselves are kept by the span kernels of
+// mapdb_span_kernels.hip.h.
 //   k_mapdb_distinctive   MapPoint::computeDistinctiveDescriptors for the named point slots: one wave per point, four per workgroup, as
 //                         k_distinctive (match_kernels.hip.h), whose bisection it runs.  Three passes over the point's views, 64 at
 //                         a time, a lane per view:
@@ -36,48 +31,6 @@ constexpr int kDescWaves = kDescThreads / 64;
 // Rows staged in LDS per wave: 128 x 32 B = 4 KiB, 16 KiB per workgroup.  A CU holds 32 waves = 8 such workgroups = 128 KiB of its
 // 160 KiB: occupancy stays bound by the wave cap, not by LDS.
 constexpr int kStageRows = 128;
-
-struct DescApplyArgs {
-  int nHeaderRec, tail;        // tail: in descriptors
-  long long nPayload16;        // the payload in 16-byte units
-  const RowHeaderRec* header;
-  const uint4* payload;
-  int* blockStart;   // [hdrCap]
-  int* blockLen;     // [hdrCap]
-  uint4* pool;       // [2 * poolCap]
-};
-
-static __global__ __launch_bounds__(kDescThreads) void k_mapdb_desc_apply(DescApplyArgs g) {
-  const int gid = blockIdx.x * kDescThreads + threadIdx.x, stride = gridDim.x * kDescThreads;
-  if (gid < g.nHeaderRec) {
-    const RowHeaderRec r = g.header[gid];
-    g.blockStart[r.kf] = r.start; g.blockLen[r.kf] = r.len;
-  }
-  uint4* to = g.pool + 2 * (size_t)g.tail;
-  for (long long i = gid; i < g.nPayload16; i += stride) to[i] = g.payload[i];
-}
-
-struct DescRepackArgs {
-  int nKf;
-  int* blockStart;        // [nKf] rewritten
-  const int* blockLen;    // [nKf]
-  const int* newOff;      // [nKf] -1: the block does not survive
-  const uint4* oldPool;
-  uint4* newPool;
-};
-
-static __global__ __launch_bounds__(kDescThreads) void k_mapdb_desc_repack(DescRepackArgs g) {
-  const int k = blockIdx.x * kDescWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (k >= g.nKf) return;   // uniform over the wave
-  const int to = g.newOff[k];
-  if (to < 0) return;
-  const int b = g.blockStart[k];
-  const long long n16 = 2 * (long long)g.blockLen[k];
-  const uint4* src = g.oldPool + 2 * (size_t)b;
-  uint4* dst = g.newPool + 2 * (size_t)to;
-  for (long long q = lane; q < n16; q += 64) dst[q] = src[q];
-  if (lane == 0) g.blockStart[k] = to;
-}
 
 struct DistinctiveArgs {
   int n, nViewHdr, nBlockHdr;

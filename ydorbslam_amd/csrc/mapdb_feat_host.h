@@ -8,7 +8,9 @@
 //             keypoint and its right_x side by side, so it moves as two 16-byte loads.
 //   device    ONE span (start, length) per keyframe indexes TWO arrays of one arena of 32 bytes per pool entry: KeyPoint [cap] at its
 //             base and float [cap] behind it at byte 28 * cap.  Both are contiguous per keyframe, so a FrameDev (grid_build.hip.h)
-//             points straight into them.  The apply kernel splits a payload element into the two.
+//             points straight into them.  The apply kernel splits a payload element into the two, which is why the relation keeps
+//             kernels of its own (mapdb_feat_kernels.hip.h) beside the span kernels the other three relations share; its driver
+//             side is the same SpanDev<T> (map_resident.hip).
 // This file holds the validation, the stats, the export's flattening and a plain-C++ execution of a packed delta on host arrays in the
 // layout the kernels keep (mapdb_feat_kernels.hip.h).  No HIP here: a plain host compiler builds it (tests/cpu_harness/mapdb_feat_check.cpp).
 #pragma once

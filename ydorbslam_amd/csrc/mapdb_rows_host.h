@@ -1,7 +1,7 @@
 // Host side of the resident table's keyframe rows (include/ydorb/c_api.h, "Keyframe rows"): a keyframe's
 // map-point vector as point slots in keypoint order, -1 = a null entry.  Beside mapdb_host.h's Host, a class and a delta of its own:
 // validation, the host mirror of every row, coalescing, the packing of one row delta and a plain-C++ execution of a
-// packed delta on host arrays in the record format the kernels read (mapdb_rows_kernels.hip.h), so that the state machine runs without
+// packed delta on host arrays in the record format the kernels read (mapdb_span_kernels.hip.h), so that the state machine runs without
 // a device (tests/cpu_harness/mapdb_rows_check.cpp).  No HIP here: a plain host compiler builds it.
 //   staging   setRows / setEntries validate, then write the mirror.  A row is clean, entry-dirty or fully dirty.  A fully dirty row is
 //             packed once from the mirror, so only its last value travels and a later entry change lands inside it.  Entry changes to a
@@ -236,7 +236,7 @@ using RowsHost = SpanHost<int32_t>;
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The packed delta executed on host arrays, step for step what the driver does on the device: grow the headers (contents kept, new
-// slots empty), repack (k_mapdb_rows_repack), apply (k_mapdb_rows_apply).
+// slots empty), repack (k_mapdb_span_repack), apply (k_mapdb_span_apply).
 template <class E> void executeRows(const RowPlan& P, const uint8_t* delta, SpanTables<E>& T) {
   if (T.rowStart.size() != (size_t)P.hdrCap) { T.rowStart.resize((size_t)P.hdrCap, 0); T.rowLen.resize((size_t)P.hdrCap, 0); }
   if (T.pool.size() != (size_t)P.poolCapBefore) T.pool.resize((size_t)P.poolCapBefore);

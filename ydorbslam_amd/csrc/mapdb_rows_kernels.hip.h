@@ -1,11 +1,5 @@
-// gfx950 HIP kernels of the resident table's keyframe rows (include/ydorb/c_api.h, "Keyframe rows").
-//   k_mapdb_rows_apply   executes one packed row delta (mapdb_rows_host.h): lane i below the record count scatters header record i
-//                        (rowStart / rowLen of its keyframe slot) or single entry i (one pool position), then all lanes stride over
-//                        the payload into the pool's tail.  The host coalesced the delta: no two lanes store to one address.  Plain
-//                        vector stores, no atomics.
-//   k_mapdb_rows_repack  one wave per keyframe slot, lanes striding over its row (rows are hundreds to thousands of entries), from the
-//                        old arena to the offset the host computed in the new one.  A row the delta replaces carries -1 and is left
-//                        to the apply.
+// gfx950 HIP kernels of the points-of-keyframes query on the resident table's keyframe rows (include/ydorb/c_api.h, "Keyframe rows";
+// DESIGN.md section 6o).  The rows themselves are kept by the span kernels of mapdb_span_kernels.hip.h.
 //   k_rowset_mark        the points of a keyframe set, pass 1: one lane per position e of E (the rows of the call's keyframes
 //                        concatenated).  The keyframe's rank comes from a search in the start table, as in k_redundancy.  The lane
 //                        stores its entry to ent[e] (-1 for a null or bad one) and does an integer atomicMin(&first[slot], e) for the
@@ -31,47 +25,6 @@ namespace mapdb {
 
 constexpr int kRowThreads = 256;
 constexpr int kRowWaves = kRowThreads / 64;
-
-struct RowsApplyArgs {
-  int nHeaderRec, nEntryRec, nPayload, tail;
-  const RowHeaderRec* header;
-  const RowEntryRec* entry;
-  const int* payload;
-  int* rowStart;   // [hdrCap]
-  int* rowLen;     // [hdrCap]
-  int* pool;       // [poolCap]
-};
-
-static __global__ __launch_bounds__(kRowThreads) void k_mapdb_rows_apply(RowsApplyArgs g) {
-  const int gid = blockIdx.x * kRowThreads + threadIdx.x, stride = gridDim.x * kRowThreads;
-  if (gid < g.nHeaderRec) {
-    const RowHeaderRec r = g.header[gid];
-    g.rowStart[r.kf] = r.start; g.rowLen[r.kf] = r.len;
-  } else if (gid < g.nHeaderRec + g.nEntryRec) {
-    const RowEntryRec r = g.entry[gid - g.nHeaderRec];
-    g.pool[r.at] = r.value;
-  }
-  for (int i = gid; i < g.nPayload; i += stride) g.pool[g.tail + i] = g.payload[i];
-}
-
-struct RowsRepackArgs {
-  int nKf;
-  int* rowStart;         // [nKf] rewritten
-  const int* rowLen;     // [nKf]
-  const int* newOff;     // [nKf] -1: the row does not survive
-  const int* oldPool;
-  int* newPool;
-};
-
-static __global__ __launch_bounds__(kRowThreads) void k_mapdb_rows_repack(RowsRepackArgs g) {
-  const int k = blockIdx.x * kRowWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (k >= g.nKf) return;   // uniform over the wave
-  const int to = g.newOff[k];
-  if (to < 0) return;
-  const int b = g.rowStart[k], len = g.rowLen[k];
-  for (int q = lane; q < len; q += 64) g.newPool[to + q] = g.oldPool[b + q];
-  if (lane == 0) g.rowStart[k] = to;
-}
 
 struct RowsetArgs {
   int nKf, nE, nSeen, stamp, capacity, nBlocks;
