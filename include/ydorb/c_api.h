@@ -320,6 +320,9 @@ int ydorb_matcher_synchronize(ydorb_matcher_t* h);
 /* average device ms of grid build / gather / resolve over calls since enabling (HIP events on the launch stream) */
 int ydorb_matcher_set_profiling(ydorb_matcher_t* h, int32_t on);
 int ydorb_matcher_stage_times(ydorb_matcher_t* h, int32_t max_stages, const char** names, float* ms, int32_t* n_stages);
+/* ydorb_mapdb_create_new_points with profiling on: ms [3] = average device ms per call of the join and gather, of the resolve
+ * launches of the chain and of its geometry launches (an event after every launch); n_calls = the calls averaged. */
+int ydorb_matcher_create_points_times(ydorb_matcher_t* h, float* ms, int32_t* n_calls);
 
 /* ------------------------------------------------------------------------------------------
  * Vocabulary.  Replaces DBoW3::Vocabulary::transform(features, BowVector&, FeatureVector&, levelsup)
@@ -1362,6 +1365,87 @@ typedef struct YdFuseTarget {
 int ydorb_mapdb_fuse_search(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdFuseTarget* targets, int32_t n_targets,
                             const int32_t* list_start, const int32_t* point_slots, const uint8_t* skip, int32_t* best_idx,
                             uint8_t* status, int32_t* n_found, uint8_t* target_status);
+
+/* Resident BoW feature vectors: a fifth span relation of the resident table.
+ *   bow  keyframe slot -> the keyframe's DBoW3::FeatureVector flattened in map order: nodes ascending, and within a node the
+ *        features in the vector's order.  The element is the pair (node id, feature index).  A keyframe's feature vector never
+ *        changes after it is made: it goes up once.  A span of length 0 erases it.  The pool is counted in entries.
+ * The relation is opt-in: a handle that never calls ydorb_mapdb_enable_bow allocates nothing for it, launches nothing for it and
+ * every entry below but enable and bow_stats returns YDORB_ERR_INVALID_ARG.  Every other stats struct keeps its values either way.
+ * The pool follows the observation pool's policy, as the feature pool does.  set_keyframe_bow validates and stages and does no device
+ * work; the next query or export applies the delta after the features and before the attributes.  A slot named several times between
+ * two syncs is applied once, with its last value.  It grows n_keyframes as set_keyframe_rows does.  ydorb_mapdb_clear empties the
+ * relation and keeps capacities and counters.
+ * Every malformed input returns YDORB_ERR_INVALID_ARG naming the first offender, before any device work, and stages nothing: null
+ * arrays, a start array that does not begin at 0 or decreases, a negative slot, a span longer than 65535, node ids that decrease
+ * inside a span, a node id of 2^31 or more, a feature index outside 0..65534, a feature index that repeats inside one span (DBoW3
+ * files each descriptor under one node), a pool past INT32_MAX entries.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct YdMapDbBowStats {
+  int32_t enabled;
+  int32_t repacks_kept, repacks_grown;
+  int64_t n_entries;                            /* live, staged changes included */
+  int64_t pool_used, pool_capacity;             /* as of the last sync, in entries */
+  int64_t last_bow_sync_bytes, last_bow_sync_records;   /* 0 when nothing of this relation was staged */
+} YdMapDbBowStats;
+/* Turns the relation on; calling it twice is fine. */
+int ydorb_mapdb_enable_bow(ydorb_mapdb_t* db);
+/* Replaces the feature vector of each named keyframe: bow_start [n+1], node_id / feat [bow_start[n]].  node_id is DBoW3's NodeId
+ * (unsigned int).  A span of length 0 erases. */
+int ydorb_mapdb_set_keyframe_bow(ydorb_mapdb_t* db, const int32_t* kf_slots, int32_t n, const int32_t* bow_start, const uint32_t* node_id,
+                                 const int32_t* feat);
+/* Reads the device's feature vectors back (after applying what is staged): bow_start [n_keyframes+1], node_id / feat [n_entries]. */
+int ydorb_mapdb_export_bow(ydorb_mapdb_t* db, int32_t* bow_start, uint32_t* node_id, int32_t* feat);
+int ydorb_mapdb_bow_stats(ydorb_mapdb_t* db, YdMapDbBowStats* stats);
+
+/* LocalMapping::createNewMapPoints over all neighbours in one call (DESIGN.md section 2 "createNewMapPoints on the resident table",
+ * section 6t): for neighbour i in the caller's order, OrbMatcher::searchForTriangulation(first, second_i) as
+ * ydorb_search_for_triangulation computes it, then the geometry of ydorb_triangulate_matches on its matches, on the table as of the
+ * call (staged deltas applied first).  "Has a map point" is "the keyframe's row entry is >= 0" on both sides; for the first keyframe
+ * it also covers every idx1 whose match with a neighbour j < i was accepted (status low nibble YDORB_TRI_ACCEPTED): an accepted
+ * match claims its idx1 for all later neighbours, as the reference's addMapPoint does.  Keypoints, right_x, descriptors, rows and
+ * feature vectors are read by slot; what travels up is the views and one depth array per keyframe. */
+typedef struct YdCreateView {   /* one keyframe: YdTriView's constants, with the slot in place of the keypoint pointers */
+  int32_t kf_slot;
+  int32_t n;                    /* the length of depth */
+  const float* depth;           /* host [n] m_v_depth */
+  float Tcw[12], Rwc[9], Ow[3];
+  float fx, fy, cx, cy, invfx, invfy, b, bf;
+  float level_sigma2[8];        /* m_v_scaleFactorSquares, [n_levels] used */
+  float scale_factors[8];       /* m_v_scaleFactors, [n_levels] used */
+  int32_t n_levels;             /* 1..8 */
+} YdCreateView;
+typedef struct YdCreateNeighbour {
+  YdCreateView view;
+  float F[9];                   /* F12 row-major, as ydorb_search_for_triangulation takes it */
+  float ex, ey;                 /* the epipole of the first keyframe in the second */
+  float ratio_factor;           /* 1.5f * the first keyframe's scale factor */
+} YdCreateNeighbour;
+#define YDORB_TRI_UNMATCHED 15  /* status low nibble of a feature the neighbour's search did not match */
+/* neighbour_status */
+#define YDORB_CREATE_NB_OK 0
+#define YDORB_CREATE_NB_NO_FEATURES 1      /* the keyframe has no feature span */
+#define YDORB_CREATE_NB_NO_BLOCK 2         /* ... no descriptor block */
+#define YDORB_CREATE_NB_NO_BOW 3           /* ... no BoW feature vector */
+#define YDORB_CREATE_NB_LENGTH_MISMATCH 4  /* features, descriptor block, row and depth differ in length */
+#define YDORB_CREATE_NB_BOW_INDEX 5        /* a feature index of the BoW feature vector is not below the feature count */
+/* first, neighbours [n_nb]; with n = first->n: matched_second / status [n_nb][n], x3d [n_nb][n][3]; n_matches, n_accepted and
+ * neighbour_status [n_nb].  The outputs are dense over the first keyframe's features, so a caller walks a neighbour's matches in
+ * ascending idx1 as the reference walks its pair vector: matched_second[i][idx1] = the feature of neighbour i matched to idx1, or -1;
+ * x3d / status = ydorb_triangulate_matches' point and byte of that match, 0 0 0 and YDORB_TRI_UNMATCHED where there is none.
+ * n_matches[i] = the matches of neighbour i, n_accepted[i] = those accepted.  An unusable neighbour gets a non-zero neighbour_status,
+ * searches nothing and has no matches; when the first keyframe is unusable every neighbour gets the first keyframe's status.  The
+ * call still returns YDORB_OK.  The results of neighbour i do not depend on any later neighbour, so a caller that makes the
+ * reference's abort check between neighbours and stops after neighbour k drops the tail unread.  The call is synchronous and exact:
+ * the candidate records start at 16384 per neighbour; when they overflow, the pool grows to what the search asked for and the whole
+ * call is replayed, claims reset.
+ * Refused up front: null arguments, n_levels outside 1..8, a kf_slot outside 0..n_keyframes-1, first->n not equal to the first
+ * keyframe's resident feature count, a second keyframe equal to the first, a second keyframe named twice (the claim rule is the
+ * reference's only when each occurs once), features or BoW feature vectors not enabled, db and m on different devices.  n_nb == 0
+ * launches nothing. */
+int ydorb_mapdb_create_new_points(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdCreateView* first, const YdCreateNeighbour* neighbours,
+                                  int32_t n_nb, int32_t stereo_only, int32_t check_orientation, int32_t* matched_second, float* x3d,
+                                  uint8_t* status, int32_t* n_matches, int32_t* n_accepted, uint8_t* neighbour_status);
 
 #ifdef __cplusplus
 }

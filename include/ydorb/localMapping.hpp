@@ -6,8 +6,9 @@
 //       m_sptr_map, m_list_recentAddedMapPoints, [this] { return checkNewKeyFrames(); }); }
 // Per neighbour of getBestCovisibilityKeyFrames(10), in the reference's order: abortCheck() for i > 0, the baseline test, F12 on the host,
 // the searchForTriangulation adapter (GPU), ONE ydorb_triangulate_matches call for the neighbour's matches (GPU), then the reference's
-// bookkeeping for the accepted matches in match order.  The loop stays one call per neighbour on purpose: a point accepted with
-// neighbour i sets the current keyframe's map point at idx1 and so changes what searchForTriangulation may match with neighbour i + 1.
+// bookkeeping for the accepted matches in match order.  This flat loop is one call per neighbour because a point accepted with
+// neighbour i sets the current keyframe's map point at idx1 and so changes what searchForTriangulation may match with neighbour i + 1;
+// the overload over a MapMirror below makes one call for all neighbours and carries that claim on the device.
 // Assumed spellings, as in the other adapters: m_v_keyPoints, m_v_rightXcords, m_v_depth, m_v_scaleFactors, m_v_scaleFactorSquares,
 // getRotation_c2w / getTranslation_c2w / getCameraOriginInWorld, FrameT::m_flt_fx .. m_flt_baseLineTimesFx; invfx = 1.0f / fx as the
 // reference stores it; the MapPoint constructor MapPoint(pos, keyFrame, map).
@@ -141,6 +142,92 @@ int createNewMapPointsImpl(ydorb_matcher_t* m, KeyFramePtr current, MapPtr map, 
       mp->updateNormalAndDepth();
       map->addMapPoint(mp);
       recentAddedMapPoints.push_back(mp);
+      created++;
+    }
+  }
+  return created;
+}
+
+// one keyframe as ydorb_mapdb_create_new_points reads it: triView's constants; kf_slot, n and depth are the mirror's to set
+template <class FrameT, class KeyFramePtr>
+inline YdCreateView createView(const KeyFramePtr& kf) {
+  const YdTriView t = triView<FrameT>(kf);
+  if (t.n_levels < 1 || t.n_levels > 8) throw std::runtime_error("ydorb: createNewMapPoints: a scale pyramid outside 1..8 levels");
+  YdCreateView v;
+  std::memset(&v, 0, sizeof v);
+  std::memcpy(v.Tcw, t.Tcw, sizeof v.Tcw); std::memcpy(v.Rwc, t.Rwc, sizeof v.Rwc); std::memcpy(v.Ow, t.Ow, sizeof v.Ow);
+  v.fx = t.fx; v.fy = t.fy; v.cx = t.cx; v.cy = t.cy; v.invfx = t.invfx; v.invfy = t.invfy; v.b = t.b; v.bf = t.bf;
+  for (int l = 0; l < t.n_levels; l++) { v.level_sigma2[l] = t.level_sigma2[l]; v.scale_factors[l] = t.scale_factors[l]; }
+  v.n_levels = t.n_levels;
+  return v;
+}
+
+// createNewMapPoints over a resident map table (mapMirror.hpp with enableDescriptors(), enableFeatures() and enableBow(); DESIGN.md
+// section 6t):
+//   void LocalMapping::createNewMapPoints()
+//   { ydorb::adapter::createNewMapPointsImpl<Frame, std::shared_ptr<KeyFrame>, MapPoint>(*m_mirror, ydorb::adapter::matcher(),
+//       m_sptr_currentKeyFrame, m_sptr_map, m_list_recentAddedMapPoints, [this] { return checkNewKeyFrames(); }); }
+// The same neighbour list, baseline test, computeF12, epipole and ratioFactor as the flat body above, computed for every neighbour
+// up front; then ONE createNewPoints call, whose device side carries the claim of an accepted idx1 from neighbour to neighbour; then the
+// walk, neighbour by neighbour with abortCheck() for i > 0 (over ALL neighbours, as the flat loop asks before its baseline test) and
+// per neighbour the accepted idx1 in ascending order with the flat body's bookkeeping.  Results of neighbour i do not depend on later
+// neighbours, so an abort after neighbour k drops the tail unread.  The new points, both row entries and the points' views are
+// registered with the mirror (touch, touchEntry), as searchInNeighborsImpl registers its changes.
+template <class FrameT, class KeyFramePtr, class MapPointT, class Mirror, class MapPtr, class RecentList, class AbortCheck>
+int createNewMapPointsImpl(Mirror& mirror, ydorb_matcher_t* m, KeyFramePtr current, MapPtr map, RecentList& recentAddedMapPoints, AbortCheck abortCheck) {
+  const std::vector<KeyFramePtr> neighbours = current->getBestCovisibilityKeyFrames(10);
+  const cv::Mat Ow1 = current->getCameraOriginInWorld();
+  const float ratioFactor = 1.5f * current->m_v_scaleFactors[1];   // 1.5f * mfScaleFactor
+  std::vector<KeyFramePtr> searched;
+  std::vector<int> callOf(neighbours.size(), -1);                  // the call's neighbour of each listed one; -1: the baseline test skips it
+  std::vector<YdCreateNeighbour> records;
+  for (size_t i = 0; i < neighbours.size(); i++) {
+    const KeyFramePtr& kf2 = neighbours[i];
+    const cv::Mat baselineVec = kf2->getCameraOriginInWorld() - Ow1;
+    const float baseline = (float)cv::norm(baselineVec);
+    if (baseline < FrameT::m_flt_baseLine) continue;
+    YdCreateNeighbour G;
+    std::memset(&G, 0, sizeof G);
+    G.view = createView<FrameT>(kf2);
+    const cv::Mat F12 = computeF12<FrameT>(current, kf2);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) G.F[r * 3 + c] = F12.at<float>(r, c);
+    const cv::Mat C2 = kf2->getRotation_c2w() * Ow1 + kf2->getTranslation_c2w();   // searchForTriangulation's epipole (orbMatcher.hpp)
+    G.ex = FrameT::m_flt_fx * C2.at<float>(0) / C2.at<float>(2) + FrameT::m_flt_cx;
+    G.ey = FrameT::m_flt_fy * C2.at<float>(1) / C2.at<float>(2) + FrameT::m_flt_cy;
+    G.ratio_factor = ratioFactor;
+    callOf[i] = (int)searched.size();
+    searched.push_back(kf2);
+    records.push_back(G);
+  }
+  if (searched.empty()) return 0;
+  const typename Mirror::CreateResult r = mirror.createNewPoints(m, current, searched, createView<FrameT>(current), records, false, false);   // ORBmatcher(0.6, false)
+  int created = 0;
+  for (size_t i = 0; i < neighbours.size(); i++) {
+    if (i > 0 && abortCheck()) return created;
+    if (callOf[i] < 0) continue;
+    const KeyFramePtr& kf2 = neighbours[i];
+    const size_t row = (size_t)callOf[i] * (size_t)r.n;
+    if (r.neighbourStatus[(size_t)callOf[i]] != YDORB_CREATE_NB_OK)
+      throw std::runtime_error("ydorb: createNewMapPoints: the resident table cannot search a neighbour (status " +
+                               std::to_string((int)r.neighbourStatus[(size_t)callOf[i]]) + ")");
+    for (int32_t idx1 = 0; idx1 < r.n; idx1++) {
+      if ((r.status[row + (size_t)idx1] & 15) != YDORB_TRI_ACCEPTED) continue;
+      const int32_t idx2 = r.matchedSecond[row + (size_t)idx1];
+      cv::Mat pos(3, 1, CV_32F);
+      for (int k = 0; k < 3; k++) pos.at<float>(k) = r.x3d[3 * (row + (size_t)idx1) + (size_t)k];
+      auto mp = std::make_shared<MapPointT>(pos, current, map);
+      mp->addObservation(current, idx1);
+      mp->addObservation(kf2, idx2);
+      current->addMapPoint(mp, idx1);
+      kf2->addMapPoint(mp, idx2);
+      mp->computeDistinctiveDescriptors();
+      mp->updateNormalAndDepth();
+      map->addMapPoint(mp);
+      recentAddedMapPoints.push_back(mp);
+      mirror.touch(mp);
+      mirror.touchEntry(current, (size_t)idx1);
+      mirror.touchEntry(kf2, (size_t)idx2);
       created++;
     }
   }

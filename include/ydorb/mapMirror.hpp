@@ -32,6 +32,10 @@
 // fuseBySim3 for several target keyframes in ONE call (orbMatcher.hpp's overloads over a mirror run the bookkeeping on its result);
 // verifyFeatures() is verify() for them.  It needs enableAttributes() too.  Assumed spellings beyond the others: KeyFrame m_v_keyPoints
 // (the undistorted keypoints, cv::KeyPoint) and m_v_rightXcords, of one length with m_cvMat_descriptors' rows.
+// enableBow() adds the keyframes' BoW feature vectors: touchBow(kf) once per keyframe, next to touchFeatures(kf);
+// forget(kf) erases the span; createNewPoints is the search and the geometry of LocalMapping::createNewMapPoints for all neighbours in
+// ONE call (localMapping.hpp's overload over a mirror runs the bookkeeping on its result); verifyBow() is verify() for them.  It needs
+// enableFeatures() and the descriptor blocks too.  Assumed spelling beyond the others: KeyFrame m_bow_keyPointsVec (DBoW3::FeatureVector).
 // Assumed spellings: those of mapPoint.hpp; m_cvMat_descriptors (one CV_8U row of 32 bytes per keypoint) for the blocks, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
 // MapPoint::setPosInWorld(cv::Mat), m_int_correctedByKeyFrameID, m_int_correctedReference and the Sim3 members rotation().x() .. w(),
 // translation()[k], scale().  The camera centre after a corrected pose is not read from a member: correctLoopPoints computes it from
@@ -113,6 +117,15 @@ class MapMirror {
   // re-reads m_v_keyPoints and m_v_rightXcords at the next flush: once per keyframe, they never change; again after setBadFlag(), whose
   // isBad() erases the span (or forget(kf))
   void touchFeatures(const KeyFramePtr& kf) { mark(featDirty_, dirtyFeats_, kfSlotFor(kf), kFull); }
+  // Resident BoW feature vectors: createNewPoints below reads a keyframe's feature vector by slot.
+  void enableBow() {
+    mapCheck(ydorb_mapdb_enable_bow(db_));
+    bow_ = true;
+  }
+  bool bowEnabled() const { return bow_; }
+  // re-reads m_bow_keyPointsVec at the next flush: once per keyframe, it never changes; again after setBadFlag(), whose isBad() erases
+  // the span (or forget(kf))
+  void touchBow(const KeyFramePtr& kf) { mark(bowDirty_, dirtyBows_, kfSlotFor(kf), kFull); }
   void touchRow(const KeyFramePtr& kf) { markRow(kfSlotFor(kf)); }
   void touchEntry(const KeyFramePtr& kf, size_t idx) {
     const int32_t s = kfSlotFor(kf);
@@ -126,6 +139,7 @@ class MapMirror {
     if (rowSent_[it->second]) markRow(it->second);   // the next flush empties the row, or writes the row of the keyframe that took the slot since
     if (descSent_[it->second]) mark(descDirty_, dirtyDescs_, it->second, kFull);   // ... and the block
     if (featSent_[it->second]) mark(featDirty_, dirtyFeats_, it->second, kFull);   // ... and the features
+    if (bowSent_[it->second]) mark(bowDirty_, dirtyBows_, it->second, kFull);      // ... and the feature vector
     freeKfs_.push_back(it->second);
     kfSlot_.erase(it);
   }
@@ -136,6 +150,7 @@ class MapMirror {
     rowDirty_.clear(); rowSent_.clear(); dirtyRows_.clear(); dirtyEntries_.clear();
     descDirty_.clear(); descSent_.clear(); dirtyDescs_.clear();
     featDirty_.clear(); featSent_.clear(); dirtyFeats_.clear();
+    bowDirty_.clear(); bowSent_.clear(); dirtyBows_.clear();
     attrDirty_.clear(); dirtyAttrs_.clear(); erasePending_.clear();
   }
 
@@ -252,6 +267,23 @@ class MapMirror {
       kps.resize(kps.size() + 1); rightX.resize(rightX.size() + 1);   // never a null pointer
       if (!ks.empty()) mapCheck(ydorb_mapdb_set_keyframe_features(db_, ks.data(), (int32_t)ks.size(), featStart.data(), kps.data(), rightX.data()));
     }
+    if (!dirtyBows_.empty()) {   // after the features: a query reads a keyframe's feature vector against its feature count
+      std::vector<int32_t> ks, bowStart{0}, feat;
+      std::vector<uint32_t> node;
+      for (const int32_t k : dirtyBows_) {
+        bowDirty_[k] = kClean;
+        const bool live = kfOf_[k] && !kfOf_[k]->isBad();
+        if (!live && !bowSent_[k]) continue;
+        ks.push_back(k);
+        if (live) appendBow(kfOf_[k], node, feat);
+        if (feat.size() > (size_t)INT32_MAX) throw std::runtime_error("ydorb: more than INT32_MAX BoW entries in one flush");
+        bowStart.push_back((int32_t)feat.size());
+        bowSent_[k] = live ? 1 : 0;
+      }
+      dirtyBows_.clear();
+      node.resize(node.size() + 1); feat.resize(feat.size() + 1);   // never a null pointer
+      if (!ks.empty()) mapCheck(ydorb_mapdb_set_keyframe_bow(db_, ks.data(), (int32_t)ks.size(), bowStart.data(), node.data(), feat.data()));
+    }
     if (descriptors_ && !slots.empty()) {
       viewKf.push_back(0); viewIdx.push_back(0);
       mapCheck(ydorb_mapdb_set_point_views(db_, slots.data(), (int32_t)slots.size(), viewStart.data(), viewKf.data(), viewIdx.data()));
@@ -353,6 +385,71 @@ class MapMirror {
       }
     }
     return r;
+  }
+
+  // The search and the geometry of LocalMapping::createNewMapPoints for all neighbours in one call (ydorb_mapdb_create_new_points):
+  // first / neighbours hold the views' constants (localMapping.hpp's createView builds them); their kf_slot, n and depth are set here
+  // from the keyframes.  A keyframe the table holds no row, features, block or feature vector of is read now.  Flushes, makes the call.
+  struct CreateResult {
+    int32_t n = 0;                        // the first keyframe's feature count: the stride of the three dense arrays
+    std::vector<int32_t> matchedSecond;   // [nNb][n]
+    std::vector<float> x3d;               // [nNb][n][3]
+    std::vector<uint8_t> status;          // [nNb][n]
+    std::vector<int32_t> nMatches, nAccepted;
+    std::vector<uint8_t> neighbourStatus; // YDORB_CREATE_NB_*
+  };
+  CreateResult createNewPoints(ydorb_matcher_t* matcher, const KeyFramePtr& current, const std::vector<KeyFramePtr>& neighbourKfs, YdCreateView first,
+                               std::vector<YdCreateNeighbour> neighbours, bool stereoOnly, bool checkOrientation) {
+    if (!features_ || !bow_ || !descriptors_) throw std::runtime_error("ydorb: createNewPoints without enableDescriptors(), enableFeatures() and enableBow()");
+    const size_t nn = neighbourKfs.size();
+    if (neighbours.size() != nn) throw std::runtime_error("ydorb: createNewPoints: one neighbour record per keyframe");
+    const auto bind = [this](const KeyFramePtr& kf, YdCreateView& v) {
+      const int32_t k = kfSlotFor(kf);
+      v.kf_slot = k; v.n = (int32_t)kf->m_v_depth.size(); v.depth = kf->m_v_depth.data();
+      if (!rowSent_[k]) markRow(k);
+      if (!featSent_[k]) mark(featDirty_, dirtyFeats_, k, kFull);
+      if (!descSent_[k]) mark(descDirty_, dirtyDescs_, k, kFull);
+      if (!bowSent_[k]) mark(bowDirty_, dirtyBows_, k, kFull);
+    };
+    bind(current, first);
+    for (size_t i = 0; i < nn; i++) bind(neighbourKfs[i], neighbours[i].view);
+    flush();
+    CreateResult r;
+    r.n = first.n;
+    const size_t cells = nn * (size_t)first.n;
+    r.matchedSecond.assign(cells + 1, -1); r.x3d.assign(3 * cells + 3, 0.f); r.status.assign(cells + 1, YDORB_TRI_UNMATCHED);
+    r.nMatches.assign(nn + 1, 0); r.nAccepted.assign(nn + 1, 0); r.neighbourStatus.assign(nn + 1, 0);
+    neighbours.resize(nn + 1);
+    mapCheck(ydorb_mapdb_create_new_points(db_, matcher, &first, neighbours.data(), (int32_t)nn, stereoOnly ? 1 : 0, checkOrientation ? 1 : 0,
+                                           r.matchedSecond.data(), r.x3d.data(), r.status.data(), r.nMatches.data(), r.nAccepted.data(),
+                                           r.neighbourStatus.data()));
+    r.nMatches.resize(nn); r.nAccepted.resize(nn); r.neighbourStatus.resize(nn);
+    return r;
+  }
+
+  // Flushes and compares every known keyframe's m_bow_keyPointsVec with the device's feature vectors (ydorb_mapdb_export_bow): the
+  // keyframe slots that differ.  Empty when every keyframe was touched.
+  std::vector<int32_t> verifyBow() {
+    flush();
+    YdMapDbStats st;
+    YdMapDbBowStats bs;
+    mapCheck(ydorb_mapdb_stats(db_, &st));
+    mapCheck(ydorb_mapdb_bow_stats(db_, &bs));
+    const size_t nk = (size_t)st.n_keyframes;
+    std::vector<int32_t> start(nk + 1), feat((size_t)bs.n_entries + 1);
+    std::vector<uint32_t> node((size_t)bs.n_entries + 1);
+    mapCheck(ydorb_mapdb_export_bow(db_, start.data(), node.data(), feat.data()));
+    std::vector<int32_t> differ;
+    for (size_t k = 0; k < kfOf_.size(); k++) {
+      std::vector<uint32_t> wantNode;
+      std::vector<int32_t> wantFeat;
+      if (kfOf_[k] && bowSent_[k] && !kfOf_[k]->isBad()) appendBow(kfOf_[k], wantNode, wantFeat);
+      const size_t len = k < nk ? (size_t)(start[k + 1] - start[k]) : 0;
+      if (len != wantFeat.size() || (len > 0 && (std::memcmp(&node[(size_t)start[k]], wantNode.data(), 4 * len) != 0 ||
+                                                 std::memcmp(&feat[(size_t)start[k]], wantFeat.data(), 4 * len) != 0)))
+        differ.push_back((int32_t)k);
+    }
+    return differ;
   }
 
   // Flushes and compares every known keyframe's m_v_keyPoints and m_v_rightXcords with the device's features
@@ -904,6 +1001,7 @@ class MapMirror {
       kfOf_.push_back(KeyFramePtr()); kfDirty_.push_back(kClean); rowDirty_.push_back(kClean); rowSent_.push_back(0);
       descDirty_.push_back(kClean); descSent_.push_back(0);
       featDirty_.push_back(kClean); featSent_.push_back(0);
+      bowDirty_.push_back(kClean); bowSent_.push_back(0);
     }
     kfOf_[s] = kf;
     kfSlot_[kf] = s;
@@ -965,6 +1063,16 @@ class MapMirror {
     if (n) std::memcpy(&kps[at], kf->m_v_keyPoints.data(), sizeof(YdKeyPoint) * n);
     rightX.insert(rightX.end(), kf->m_v_rightXcords.begin(), kf->m_v_rightXcords.end());
   }
+  // m_bow_keyPointsVec of one keyframe, flattened in map order: nodes ascending, a node's features in the vector's order.  Chosen by
+  // overload so that a keyframe type without the member still builds the mirror (it cannot enable the feature vectors).
+  template <class K>
+  static auto appendBowOf(const K& kf, std::vector<uint32_t>& node, std::vector<int32_t>& feat, int) -> decltype((void)kf->m_bow_keyPointsVec) {
+    for (const auto& kv : kf->m_bow_keyPointsVec)
+      for (const auto f : kv.second) { node.push_back((uint32_t)kv.first); feat.push_back((int32_t)f); }
+  }
+  template <class K>
+  static void appendBowOf(const K&, std::vector<uint32_t>&, std::vector<int32_t>&, long) { throw std::runtime_error("ydorb: the keyframe type has no m_bow_keyPointsVec"); }
+  static void appendBow(const KeyFramePtr& kf, std::vector<uint32_t>& node, std::vector<int32_t>& feat) { appendBowOf(kf, node, feat, 0); }
   // getNormal() (3x1 CV_32F), the raw getMinDistance() / getMaxDistance() and getDescriptor() (1x32 CV_8U) of one point, each group
   // appended only when its matrix is not empty (the member is set).  Chosen by
   // overload so that a map-point type without them still builds the mirror (it cannot touch attributes).
@@ -1011,6 +1119,9 @@ class MapMirror {
   bool features_ = false;
   std::vector<uint8_t> featDirty_, featSent_;   // per keyframe slot: the features are re-read at the next flush / the table holds features of it
   std::vector<int32_t> dirtyFeats_;
+  bool bow_ = false;
+  std::vector<uint8_t> bowDirty_, bowSent_;   // per keyframe slot: the feature vector is re-read at the next flush / the table holds one of it
+  std::vector<int32_t> dirtyBows_;
   bool attributes_ = false;
   std::vector<uint8_t> attrDirty_;   // per point slot: the attributes are re-read at the next flush
   std::vector<uint8_t> erasePending_;   // per point slot: forgotten with attributes enabled, and the erased record has not gone yet

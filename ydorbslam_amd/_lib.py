@@ -160,6 +160,12 @@ SYMBOLS = {
     "ydorb_mapdb_export_features": (C.c_int, [_VP, _VP, _VP, _VP]),
     "ydorb_mapdb_feat_stats": (C.c_int, [_VP, _VP]),
     "ydorb_mapdb_fuse_search": (C.c_int, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_enable_bow": (C.c_int, [_VP]),
+    "ydorb_mapdb_set_keyframe_bow": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP]),
+    "ydorb_mapdb_export_bow": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_bow_stats": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_create_new_points": (C.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_matcher_create_points_times": (C.c_int, [_VP, _VP, C.POINTER(_I)]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -269,6 +275,21 @@ class YdMapDbAttrStats(C.Structure):
 class YdMapDbFeatStats(C.Structure):
     _fields_ = [("enabled", _I), ("repacks_kept", _I), ("repacks_grown", _I), ("n_features", C.c_int64), ("pool_used", C.c_int64),
                 ("pool_capacity", C.c_int64), ("last_feat_sync_bytes", C.c_int64), ("last_feat_sync_records", C.c_int64)]
+
+
+class YdMapDbBowStats(C.Structure):
+    _fields_ = [("enabled", _I), ("repacks_kept", _I), ("repacks_grown", _I), ("n_entries", C.c_int64), ("pool_used", C.c_int64),
+                ("pool_capacity", C.c_int64), ("last_bow_sync_bytes", C.c_int64), ("last_bow_sync_records", C.c_int64)]
+
+
+class YdCreateView(C.Structure):
+    _fields_ = [("kf_slot", _I), ("n", _I), ("depth", _VP), ("Tcw", C.c_float * 12), ("Rwc", C.c_float * 9), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
+                ("b", C.c_float), ("bf", C.c_float), ("level_sigma2", C.c_float * 8), ("scale_factors", C.c_float * 8), ("n_levels", _I)]
+
+
+class YdCreateNeighbour(C.Structure):
+    _fields_ = [("view", YdCreateView), ("F", C.c_float * 9), ("ex", C.c_float), ("ey", C.c_float), ("ratio_factor", C.c_float)]
 
 
 class YdFuseTarget(C.Structure):

@@ -6,13 +6,14 @@
 //   the attribute table   opt-in; mapdb_attr_host.h's AttrHost over an SoA arena per point slot (AttrColumns below) that follows the
 //                         point table's capacity; k_mapdb_attr_apply (mapdb_attr_kernels.hip.h).  Three queries
 //                         write their results through to it.
-//   four span relations   each a SpanHost<T> (mapdb_rows_host.h) and a SpanDev<T> below: the keyframe rows (section 6o), the point
-//                         views and the keyframe descriptor blocks (mapdb_desc_host.h, section 6p), which share the two kernels of
-//                         mapdb_span_kernels.hip.h, and the opt-in keyframe features (mapdb_feat_host.h, section 6r), whose one pool
-//                         arena holds two arrays and has kernels of its own (mapdb_feat_kernels.hip.h).
+//   five span relations   each a SpanHost<T> (mapdb_rows_host.h) and a SpanDev<T> below: the keyframe rows (section 6o), the point
+//                         views and the keyframe descriptor blocks (mapdb_desc_host.h, section 6p) and the opt-in BoW feature vectors
+//                         (mapdb_bow_host.h, section 6t), which share the two kernels of mapdb_span_kernels.hip.h, and the opt-in
+//                         keyframe features (mapdb_feat_host.h, section 6r), whose one pool arena holds two arrays and has kernels
+//                         of its own (mapdb_feat_kernels.hip.h).
 // The set_* entries only stage.  A query calls sync() first, which applies what is staged in a fixed order: points, rows, views, blocks,
-// features if enabled, attributes if enabled.  A later part may name what an earlier one introduced in the same interval: a row a new
-// point, a view a new keyframe, the attribute arena the point capacity just grown.  Each part: one upload of its packed delta, the
+// features if enabled, BoW feature vectors if enabled, attributes if enabled.  A later part may name what an earlier one introduced
+// in the same interval: a row a new point, a view a new keyframe, the attribute arena the point capacity just grown.  Each part: one upload of its packed delta, the
 // growths (device-to-device copies), the repack if its pool needs it, the apply; an arena that was replaced is freed only after the
 // stream has drained (handOver).  With nothing staged no table byte moves.  Then the query's own arrays in one upload, its pass, one
 // read-back and one synchronise.  ydorb_mapdb_correct (mapcorrect_kernels.hip.h, section 6n) is the one query that writes the point
@@ -33,6 +34,7 @@
 #include "mapcorrect_kernels.hip.h"
 #include "mapdb_attr_host.h"
 #include "mapdb_attr_kernels.hip.h"
+#include "mapdb_bow_host.h"
 #include "mapdb_desc_host.h"
 #include "mapdb_desc_kernels.hip.h"
 #include "mapdb_feat_host.h"
@@ -192,7 +194,10 @@ struct ydorb_mapdb {
   // arena has 32 bytes per entry and holds two arrays: KeyPoint [cap] at its base (featKps), right_x [cap] behind it (featRightX)
   mapdb::FeatHost feat;
   SpanDev<mapdb::FeatRec> dFeats;
-  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc), feat(kc) {}
+  // keyframe BoW feature vectors: nothing of this is allocated or launched until ydorb_mapdb_enable_bow
+  mapdb::BowHost bow;
+  SpanDev<mapdb::BowRec> dBow;
+  ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc), feat(kc), bow(kc) {}
 };
 
 namespace {
@@ -317,8 +322,9 @@ int syncPoints(ydorb_mapdb* h) {
   return YDORB_OK;
 }
 
-// The plain span relations (the keyframe rows, the point views, the descriptor blocks) share the two kernels of
-// mapdb_span_kernels.hip.h: an element moves as sizeof(T) / sizeof(unit) units, an int for the int32 spans, a uint4 where it can.
+// The plain span relations (the keyframe rows, the point views, the descriptor blocks, the BoW feature vectors) share the two kernels
+// of mapdb_span_kernels.hip.h: an element moves as sizeof(T) / sizeof(unit) units, an int for the int32 spans and the two-int BoW
+// pairs, a uint4 where it can.
 template <class T> int syncPlainSpans(hipStream_t s, SpanDev<T>& d, mapdb::SpanHost<T>& host) {
   using U = std::conditional_t<sizeof(T) % sizeof(uint4) == 0, uint4, int>;
   constexpr int kPer = sizeof(T) / sizeof(U);
@@ -400,6 +406,7 @@ int sync(ydorb_mapdb* h) {
   if (!rc) rc = syncPlainSpans(s, h->dViews, h->desc.views);
   if (!rc) rc = syncPlainSpans(s, h->dBlocks, h->desc.blocks);
   if (!rc && h->feat.enabled()) rc = syncFeatures(h);
+  if (!rc && h->bow.enabled()) rc = syncPlainSpans(s, h->dBow, h->bow.spans);
   return rc || !h->attr.enabled() ? rc : syncAttributes(h);
 }
 
@@ -490,7 +497,7 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   h->c.releaseBuffers();
   h->points.release(); h->centres.release(); h->pool.release(); h->delta.release(); h->rowset.release();
   h->attrMem.release(); h->attrDelta.release();
-  h->dRows.release(); h->dViews.release(); h->dBlocks.release(); h->dFeats.release();
+  h->dRows.release(); h->dViews.release(); h->dBlocks.release(); h->dFeats.release(); h->dBow.release();
   delete h;
 }
 
@@ -503,9 +510,12 @@ extern "C" int ydorb_mapdb_clear(ydorb_mapdb_t* h) {
   h->desc.clear();
   h->attr.clear();
   h->feat.clear();
+  h->bow.clear();
   hipStream_t s = h->c.stream;   // every slot reads as never set again
   int rc;
-  if ((rc = h->dRows.zeroHeaders(s)) || (rc = h->dViews.zeroHeaders(s)) || (rc = h->dBlocks.zeroHeaders(s)) || (rc = h->dFeats.zeroHeaders(s))) return rc;
+  if ((rc = h->dRows.zeroHeaders(s)) || (rc = h->dViews.zeroHeaders(s)) || (rc = h->dBlocks.zeroHeaders(s)) || (rc = h->dFeats.zeroHeaders(s)) ||
+      (rc = h->dBow.zeroHeaders(s)))
+    return rc;
   if (h->attrMem.p) HIPCHK(hipMemsetAsync(h->attrMem.p, 0, h->attrMem.cap, s));
   if (h->rowsetCap) {
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->first, INT32_MAX, h->rowsetCap, s));
@@ -1154,6 +1164,54 @@ extern "C" int ydorb_mapdb_export_features(ydorb_mapdb_t* h, int32_t* feat_start
   return YDORB_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------- BoW feature vectors
+extern "C" int ydorb_mapdb_enable_bow(ydorb_mapdb_t* h) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (h->bow.enabled()) return YDORB_OK;
+  HIPCHK(hipSetDevice(h->device));
+  const int rc = h->dBow.alloc(h->c.stream, h->bow.spans);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->c.stream));
+  h->bow.enable();
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_set_keyframe_bow(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n, const int32_t* bow_start,
+                                            const uint32_t* node_id, const int32_t* feat) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!h->bow.set(kf_slots, n, bow_start, node_id, feat, err)) return invalid(err);
+  h->host.growKeyframes(h->bow.spans.nKeyframes());
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_bow_stats(ydorb_mapdb_t* h, YdMapDbBowStats* stats) {
+  if (!h || !stats) return invalid("null handle or stats");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  h->bow.stats(*stats);
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_export_bow(ydorb_mapdb_t* h, int32_t* bow_start, uint32_t* node_id, int32_t* feat) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!mapdb::BowHost::checkEnabled(h->bow.enabled(), err)) return invalid(err);
+  if (!bow_start) return invalid("null bow_start");
+  if (h->bow.spans.liveAfterSync() > 0 && (!node_id || !feat)) return invalid("null node_id or feat");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = sync(h);
+  if (rc) return rc;
+  size_t dStart, dLen, dPool;
+  const size_t held = (size_t)h->bow.spans.nKeyframes();
+  if ((rc = h->dBow.download(h->c, held, (size_t)h->bow.spans.poolUsed(), dStart, dLen, dPool))) return rc;
+  mapdb::flattenBow(h->host.nKeyframes(), (int32_t)held, at<int32_t>(h->c.hDown, dStart), at<int32_t>(h->c.hDown, dLen),
+                    at<mapdb::BowRec>(h->c.hDown, dPool), bow_start, node_id, feat);
+  return YDORB_OK;
+}
+
 // What ydorb_mapdb_search_local_points (orb_matcher.hip) reads: mapdb_resident_points.h
 int ydorb::mapdb::lockResident(ydorb_mapdb_t* h, int32_t device, const int32_t* slots, int32_t n, ResidentPoints& out) {
   std::unique_lock<std::mutex> lock(h->c.mu);
@@ -1198,6 +1256,50 @@ int ydorb::mapdb::lockResidentFuse(ydorb_mapdb_t* h, int32_t device, const int32
   kf.featStart = h->dFeats.start; kf.featLen = h->dFeats.len;
   kf.kps = h->dFeats.pool; kf.rightX = reinterpret_cast<const float*>(featRightX(h->dFeats.pool, h->feat.feats.poolCap()));
   kf.blockStart = h->dBlocks.start; kf.blockLen = h->dBlocks.len; kf.blockPool = reinterpret_cast<const uint8_t*>(h->dBlocks.pool);
+  lock.release();   // held until unlockResident
+  return YDORB_OK;
+}
+
+// What ydorb_mapdb_create_new_points (orb_matcher.hip) reads
+int ydorb::mapdb::lockResidentTri(ydorb_mapdb_t* h, int32_t device, const int32_t* kfSlots, const int32_t* nDepth, int32_t nNb, ResidentTriPools& pools,
+                                  ResidentTriSpans* spans, uint8_t* status) {
+  std::unique_lock<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!FeatHost::checkEnabled(h->feat.enabled(), err) || !BowHost::checkEnabled(h->bow.enabled(), err) ||
+      !RowsHost::checkKfSlots(kfSlots, nNb + 1, h->host.nKeyframes(), err))
+    return invalid(err);
+  if (device != h->device) return invalid("the map table lives on device " + std::to_string(h->device) + ", the matcher on device " + std::to_string(device));
+  if (nDepth[0] != h->feat.feats.lenOf(kfSlots[0]))
+    return invalid("the first keyframe has " + std::to_string(h->feat.feats.lenOf(kfSlots[0])) + " resident features, n is " + std::to_string(nDepth[0]));
+  for (int32_t i = 1; i <= nNb; i++) {
+    if (kfSlots[i] == kfSlots[0]) return invalid("neighbour " + std::to_string(i - 1) + " is the first keyframe");
+    for (int32_t j = 1; j < i; j++)
+      if (kfSlots[j] == kfSlots[i]) return invalid("neighbours " + std::to_string(j - 1) + " and " + std::to_string(i - 1) + " name keyframe slot " + std::to_string(kfSlots[i]) + " twice");
+  }
+  if (nNb > 0) {   // no neighbour reads nothing: nothing is applied or launched for it
+    HIPCHK(hipSetDevice(h->device));
+    int rc = sync(h);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->c.stream));   // the deltas and any write-through still queued: the reader runs on another stream
+    for (int32_t i = 0; i <= nNb; i++) {         // nothing is staged now: the mirrors say where the device holds each span
+      const int32_t k = kfSlots[i];
+      ResidentTriSpans& S = spans[i];
+      S.featStart = h->feat.feats.offOf(k); S.n = h->feat.feats.lenOf(k);
+      S.blockStart = h->desc.blocks.offOf(k); S.rowStart = h->rows.offOf(k);
+      S.bowStart = h->bow.spans.offOf(k); S.bowLen = h->bow.spans.lenOf(k);
+      status[i] = YDORB_CREATE_NB_OK;
+      if (S.n == 0) status[i] = YDORB_CREATE_NB_NO_FEATURES;
+      else if (h->desc.blocks.lenOf(k) == 0) status[i] = YDORB_CREATE_NB_NO_BLOCK;
+      else if (S.bowLen == 0) status[i] = YDORB_CREATE_NB_NO_BOW;
+      else if (h->desc.blocks.lenOf(k) != S.n || h->rows.lenOf(k) != S.n || nDepth[i] != S.n) status[i] = YDORB_CREATE_NB_LENGTH_MISMATCH;
+      else
+        for (const BowRec& r : h->bow.spans.rowOf(k))
+          if (r.feat >= S.n) { status[i] = YDORB_CREATE_NB_BOW_INDEX; break; }
+    }
+  }
+  pools.rowPool = h->dRows.pool; pools.bowPool = reinterpret_cast<const int32_t*>(h->dBow.pool);
+  pools.kps = h->dFeats.pool; pools.rightX = reinterpret_cast<const float*>(featRightX(h->dFeats.pool, h->feat.feats.poolCap()));
+  pools.blockPool = reinterpret_cast<const uint8_t*>(h->dBlocks.pool);
   lock.release();   // held until unlockResident
   return YDORB_OK;
 }

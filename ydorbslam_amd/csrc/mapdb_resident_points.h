@@ -47,6 +47,24 @@ struct ResidentKeyframes {
 int lockResidentFuse(ydorb_mapdb_t* db, int32_t device, const int32_t* slots, int32_t n, const int32_t* kfSlots, int32_t nKf, ResidentPoints& out,
                      ResidentKeyframes& kf, int32_t* featStart, int32_t* featLen, int32_t* blockStart, int32_t* blockLen);
 
+// What ydorb_mapdb_create_new_points reads: the pools of four keyframe relations (rows section 6o, blocks 6p, features 6r, BoW feature
+// vectors 6t) and, per named keyframe, where the device holds its four spans after the sync, from the host mirrors.
+struct ResidentTriPools {
+  const int32_t* rowPool = nullptr;       // point slot per keypoint, -1 = none
+  const int32_t* bowPool = nullptr;       // (node id, feature index) pairs
+  const void* kps = nullptr;              // KeyPoint [pool]: 28 bytes each
+  const float* rightX = nullptr;          // [pool]
+  const uint8_t* blockPool = nullptr;     // [pool][32]
+};
+struct ResidentTriSpans { int32_t featStart, n, blockStart, rowStart, bowStart, bowLen; };   // n: the keyframe's feature count
+
+// lockResident for createNewPoints: refuses features or BoW not enabled, another device, a keyframe slot outside 0..n_keyframes-1, a
+// second keyframe equal to the first or named twice and nFirst != the first keyframe's resident feature count.  kfSlots [1 + nNb], the
+// first keyframe at 0; nDepth [1 + nNb] = the caller's depth lengths; spans / status [1 + nNb] out.  status[i] is a
+// YDORB_CREATE_NB_* of keyframe i on its own (0 = usable); with nNb == 0 nothing is synced and nothing is written.
+int lockResidentTri(ydorb_mapdb_t* db, int32_t device, const int32_t* kfSlots, const int32_t* nDepth, int32_t nNb, ResidentTriPools& pools,
+                    ResidentTriSpans* spans, uint8_t* status);
+
 struct ResidentLock {   // unlocks on every way out of the reader
   ydorb_mapdb_t* db = nullptr;
   ~ResidentLock() { if (db) unlockResident(db); }

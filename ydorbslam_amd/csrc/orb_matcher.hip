@@ -19,6 +19,7 @@
 #include "mapdb_frustum_kernels.hip.h"
 #include "mapdb_fuse_kernels.hip.h"
 #include "mapdb_resident_points.h"
+#include "mapdb_tri_kernels.hip.h"
 #include "match_kernels.hip.h"
 #include "stereo_kernels.hip.h"
 #include "ydorb_host.h"
@@ -144,6 +145,22 @@ size_t layFuse(size_t upBytes, size_t downBytes, size_t nt, size_t nf, size_t su
   return a.L.bytes;
 }
 
+// `call`, ydorb_mapdb_create_new_points: nNb neighbours, nq queries each (the first keyframe's BoW span), n features of the first
+// keyframe.  `up` is what one upload brings (the first keyframe's record, the neighbour and call records, the depths), `down` what one
+// read-back takes (the three dense outputs, match counts, pool heads, the overflow word).
+struct TriPtrs {
+  uint8_t *up, *down;
+  int2 *qRange, *qInfo; int *qFeat, *matchQ, *assigned; float* qAngle;
+};
+size_t layTri(size_t upBytes, size_t downBytes, size_t nNb, size_t nq, void* base, TriPtrs& p) {
+  Carve a(base);
+  a.take(p.up, upBytes); a.take(p.down, downBytes);
+  a.take(p.qRange, nNb * nq); a.take(p.qInfo, nNb * nq); a.take(p.qFeat, nq); a.take(p.qAngle, nq); a.take(p.matchQ, nNb * nq); a.take(p.assigned, nNb * nq);
+  return a.L.bytes;
+}
+
+enum { TS_SEARCH = 0, TS_RESOLVE, TS_GEOMETRY, TS_COUNT };   // ydorb_matcher_create_points_times
+
 }  // namespace
 
 // Host-call and batched paths share no device state on a handle: a batched call may still be running on its caller's stream, and its
@@ -155,6 +172,10 @@ struct ydorb_matcher {
   Mem pool;              // the host calls' record pool: grows by poolRecords, not by a call's shape, and a replay after an overflow
   size_t poolRecords = 1u << 20;   // ... finds everything else where it was
   size_t fuseOvfPerCall = 1u << 14;   // ydorb_mapdb_fuse_search: the overflow region of each target's pool part, grown by a replay
+  size_t triPoolPerNb = 1u << 14;     // ydorb_mapdb_create_new_points: each neighbour's part of the pool, grown by a replay
+  std::vector<hipEvent_t> triEv;      // ... its per-launch events, made when a profiled call first needs them
+  double triMs[TS_COUNT]{};
+  int triCalls = 0;
   Mem stereo;            // ydorb_stereo_matches (layStereo)
   PinnedMem hUp, hDown;  // ydorb_search_local_points: pinned staging of the map-point table, read-back of track rows + status bytes
   // What ydorb_match_pairs_device / ydorb_match_consecutive_device keep; nothing but them, synchronize and destroy touches it.
@@ -202,6 +223,7 @@ void ydorb_matcher_destroy(ydorb_matcher_t* m) {
   (void)hipStreamSynchronize(m->stream);
   for (Mem* b : m->buffers()) b->release();
   for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
+  for (auto& e : m->triEv) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(m->stream);
   delete m;
 }
@@ -709,6 +731,186 @@ int ydorb_mapdb_fuse_search(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdFuseT
   return YDORB_ERR_CAPACITY;
 }
 
+// LocalMapping::createNewMapPoints for all neighbours over a resident map table (mapdb_tri_kernels.hip.h has the kernels and what each
+// does).  The join and the gather run once over all neighbours; then, per usable neighbour in order and with nothing crossing the host,
+// the unchanged k_resolve (mode 5) and the geometry kernel, whose accepted matches empty their queries for the neighbours still to
+// come.  One upload, one read-back.  The table's mutex is held from its sync to the end of the call, as in ydorb_mapdb_fuse_search;
+// every return after the first launch, an error included, synchronises the matcher's stream first.  The geometry reads k_resolve's
+// `assigned` row, not matchQ: with check_orientation the histogram cull clears the former only.  A set overflow word grows every
+// neighbour's part of the pool to what the heads asked for and replays the whole call: the gather rewrites every qInfo, so the claims
+// of the abandoned attempt are gone.
+int ydorb_mapdb_create_new_points(ydorb_mapdb_t* db, ydorb_matcher_t* m, const YdCreateView* first, const YdCreateNeighbour* nbs, int32_t nNb,
+                                  int32_t stereoOnly, int32_t checkOri, int32_t* matched, float* x3d, uint8_t* status, int32_t* nMatches,
+                                  int32_t* nAccepted, uint8_t* nbStatus) {
+  if (!db || !m) { set_error("mapdb_create_new_points: null handle"); return YDORB_ERR_INVALID_ARG; }
+  if (!first) { set_error("mapdb_create_new_points: null first keyframe"); return YDORB_ERR_INVALID_ARG; }
+  if (nNb < 0) { set_error("mapdb_create_new_points: negative number of neighbours: %d", nNb); return YDORB_ERR_INVALID_ARG; }
+  if (first->n < 0 || (first->n > 0 && !first->depth)) { set_error("mapdb_create_new_points: first keyframe: negative n or null depth"); return YDORB_ERR_INVALID_ARG; }
+  if (first->n_levels < 1 || first->n_levels > 8) { set_error("mapdb_create_new_points: first keyframe: n_levels %d outside 1..8", first->n_levels); return YDORB_ERR_INVALID_ARG; }
+  if (nNb > 0 && (!nbs || !nMatches || !nAccepted || !nbStatus || (first->n > 0 && (!matched || !x3d || !status)))) {
+    set_error("mapdb_create_new_points: null neighbours, matched_second, x3d, status, n_matches, n_accepted or neighbour_status");
+    return YDORB_ERR_INVALID_ARG;
+  }
+  const size_t nn = (size_t)nNb, n1 = (size_t)first->n;
+  std::vector<int32_t> kfSlots(nn + 1), nDepth(nn + 1);
+  kfSlots[0] = first->kf_slot; nDepth[0] = first->n;
+  size_t nDepthAll = n1;
+  for (size_t i = 0; i < nn; i++) {
+    const YdCreateView& V = nbs[i].view;
+    if (V.n < 0 || (V.n > 0 && !V.depth)) { set_error("mapdb_create_new_points: neighbour %zu: negative n or null depth", i); return YDORB_ERR_INVALID_ARG; }
+    if (V.n_levels < 1 || V.n_levels > 8) { set_error("mapdb_create_new_points: neighbour %zu: n_levels %d outside 1..8", i, V.n_levels); return YDORB_ERR_INVALID_ARG; }
+    kfSlots[i + 1] = V.kf_slot; nDepth[i + 1] = V.n;
+    nDepthAll += (size_t)V.n;
+  }
+  mapdb::ResidentTriPools P;
+  std::vector<mapdb::ResidentTriSpans> spans(nn + 1);
+  std::vector<uint8_t> kfStatus(nn + 1, 0);
+  mapdb::ResidentLock lock;
+  int rc;
+  if ((rc = mapdb::lockResidentTri(db, m->device, kfSlots.data(), nDepth.data(), nNb, P, spans.data(), kfStatus.data()))) return rc;
+  lock.db = db;
+  if (nNb == 0) return YDORB_OK;
+  bool any = false;
+  for (size_t i = 0; i < nn; i++) {
+    nbStatus[i] = kfStatus[0] ? kfStatus[0] : kfStatus[i + 1];
+    nMatches[i] = 0; nAccepted[i] = 0;
+    any = any || !nbStatus[i];
+  }
+  for (size_t o = 0; o < nn * n1; o++) { matched[o] = -1; status[o] = YDORB_TRI_UNMATCHED; }
+  if (nn * n1) std::memset(x3d, 0, 12 * nn * n1);
+  if (!any) return YDORB_OK;
+  static_assert(sizeof(mapdbtri::Spans) == sizeof(mapdb::ResidentTriSpans), "one layout");
+  const size_t nq = (size_t)spans[0].bowLen;
+  HIPCHK(hipSetDevice(m->device));
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};   // before the mutex goes: see ydorb_mapdb_search_local_points
+  Layout U;
+  const size_t oFirst = U.add(sizeof(mapdbtri::FirstDev)), oNb = U.add(sizeof(mapdbtri::NbDev) * nn), oCalls = U.add(sizeof(CallDev) * nn),
+               oDepth = U.add(4 * nDepthAll);
+  Layout D;
+  const size_t dMatched = D.add(4 * nn * n1), dX = D.add(12 * nn * n1), dSt = D.add(nn * n1), dCount = D.add(4 * nn), dHeads = D.add(4 * nn), dOvf = D.add(16);
+  TriPtrs p;
+  if ((rc = m->hUp.ensure(U.bytes)) || (rc = m->hDown.ensure(D.bytes))) return rc;
+  if ((rc = layOut(m->call, [&](void* base) { return layTri(U.bytes, D.bytes, nn, nq, base, p); }))) return rc;
+  auto viewOf = [](const YdCreateView& V, tri::ViewDev& d) {
+    std::memcpy(d.Tcw, V.Tcw, sizeof d.Tcw); std::memcpy(d.Rwc, V.Rwc, sizeof d.Rwc); std::memcpy(d.Ow, V.Ow, sizeof d.Ow);
+    d.fx = V.fx; d.fy = V.fy; d.cx = V.cx; d.cy = V.cy; d.invfx = V.invfx; d.invfy = V.invfy; d.b = V.b; d.bf = V.bf;
+  };
+  mapdbtri::FirstDev* hFirst = at<mapdbtri::FirstDev>(m->hUp, oFirst);
+  mapdbtri::NbDev* hNb = at<mapdbtri::NbDev>(m->hUp, oNb);
+  CallDev* hc = at<CallDev>(m->hUp, oCalls);
+  float* hDepth = at<float>(m->hUp, oDepth);
+  std::memset(hFirst, 0, sizeof(mapdbtri::FirstDev));
+  std::memset(hNb, 0, sizeof(mapdbtri::NbDev) * nn);
+  std::memset(hc, 0, sizeof(CallDev) * nn);
+  std::memcpy(&hFirst->k1, &spans[0], sizeof(mapdbtri::Spans));
+  viewOf(*first, hFirst->view);
+  for (int l = 0; l < first->n_levels; l++) { hFirst->sigma2[l] = first->level_sigma2[l]; hFirst->sf[l] = first->scale_factors[l]; }
+  if (n1) std::memcpy(hDepth, first->depth, 4 * n1);
+  const KeyPointDev* kps = reinterpret_cast<const KeyPointDev*>(P.kps);
+  size_t depthAt = n1;
+  for (size_t i = 0; i < nn; i++) {
+    const YdCreateNeighbour& G = nbs[i];
+    mapdbtri::NbDev& N = hNb[i];
+    std::memcpy(&N.k2, &spans[i + 1], sizeof(mapdbtri::Spans));
+    N.usable = nbStatus[i] == YDORB_CREATE_NB_OK; N.depthAt = (int)depthAt; N.ratioFactor = G.ratio_factor;
+    N.geom.tri = 1;
+    for (int k = 0; k < 9; k++) N.geom.F[k] = G.F[k];
+    N.geom.ex = G.ex; N.geom.ey = G.ey;
+    for (int l = 0; l < G.view.n_levels; l++) { N.geom.sfB[l] = G.view.scale_factors[l]; N.geom.sf2B[l] = G.view.level_sigma2[l]; }
+    viewOf(G.view, N.view);
+    if (G.view.n) std::memcpy(hDepth + depthAt, G.view.depth, 4 * (size_t)G.view.n);
+    depthAt += (size_t)G.view.n;
+    CallDev& C = hc[i];   // no frame, query rows or taken flags, as in the flat search
+    C.tkps = kps + N.k2.featStart; C.qAngle = p.qAngle; C.nq = N.usable ? (int)nq : 0; C.qInfo = p.qInfo + i * nq;
+    C.assigned = p.assigned + i * nq; C.matchQ = p.matchQ + i * nq; C.count = reinterpret_cast<int*>(p.down + dCount) + i;
+    C.mode = 5; C.ratio = 0.f; C.checkOri = checkOri;
+  }
+  hipStream_t s = m->stream;
+  HIPCHK(hipMemcpyAsync(p.up, m->hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  const mapdbtri::NbDev* dNb = reinterpret_cast<const mapdbtri::NbDev*>(p.up + oNb);
+  const CallDev* dCalls = reinterpret_cast<const CallDev*>(p.up + oCalls);
+  mapdbtri::SearchArgs sa;
+  sa.R.rowPool = P.rowPool; sa.R.bowPool = reinterpret_cast<const int2*>(P.bowPool); sa.R.kps = kps; sa.R.rightX = P.rightX; sa.R.blockPool = P.blockPool;
+  sa.k1 = hFirst->k1; sa.nq = (int)nq; sa.stereoOnly = stereoOnly ? 1 : 0; sa.nb = dNb;
+  sa.qRange = p.qRange; sa.qFeat = p.qFeat; sa.qAngle = p.qAngle; sa.qInfo = p.qInfo;
+  sa.heads = reinterpret_cast<unsigned*>(p.down + dHeads); sa.overflow = reinterpret_cast<int*>(p.down + dOvf);
+  mapdbtri::GeometryArgs ga;
+  ga.R = sa.R; ga.first = reinterpret_cast<const mapdbtri::FirstDev*>(p.up + oFirst); ga.nNb = nNb; ga.nq = (int)nq; ga.nbs = dNb;
+  ga.depth = reinterpret_cast<const float*>(p.up + oDepth); ga.qFeat = p.qFeat; ga.assigned = p.assigned; ga.qInfo = p.qInfo;
+  ga.matched = reinterpret_cast<int*>(p.down + dMatched); ga.x3d = reinterpret_cast<float*>(p.down + dX); ga.status = p.down + dSt;
+  const bool prof = m->profiling;
+  const size_t nEv = 3 + 2 * nn;
+  if (prof)
+    while (m->triEv.size() < nEv) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreate(&e));
+      m->triEv.push_back(e);
+    }
+  const unsigned qBlocks = (unsigned)((nq + mapdbtri::kThreads - 1) / mapdbtri::kThreads);
+  for (int attempt = 0; attempt < 6; attempt++) {
+    if (m->triPoolPerNb * nn > (size_t)INT32_MAX) { set_error("mapdb_create_new_points: a record pool of %zu entries, past INT32_MAX", m->triPoolPerNb * nn); return YDORB_ERR_CAPACITY; }
+    if ((rc = m->pool.ensure(sizeof(uint32_t) * m->triPoolPerNb * nn))) return rc;
+    sa.pool = m->pool.as<uint32_t>(); sa.poolPerNb = (unsigned)m->triPoolPerNb;
+    HIPCHK(hipMemsetAsync(p.down + dMatched, 0xFF, 4 * nn * n1, s));
+    HIPCHK(hipMemsetAsync(p.down + dX, 0, 12 * nn * n1, s));
+    HIPCHK(hipMemsetAsync(p.down + dSt, YDORB_TRI_UNMATCHED, nn * n1, s));
+    HIPCHK(hipMemsetAsync(p.down + dCount, 0, D.bytes - dCount, s));   // counts, heads, overflow word
+    size_t ev = 0;
+    if (nq > 0) {
+      HIPCHK(hipMemsetAsync(p.assigned, 0xFF, 4 * nn * nq, s));
+      if (prof) HIPCHK(hipEventRecord(m->triEv[ev++], s));
+      hipLaunchKernelGGL(mapdbtri::k_mapdb_tri_join, dim3(qBlocks, nNb), dim3(mapdbtri::kThreads), 0, s, sa);
+      hipLaunchKernelGGL(mapdbtri::k_mapdb_tri_gather, dim3((unsigned)((nq + 3) / 4), nNb), dim3(256), 0, s, sa);
+      HIPCHK(hipGetLastError());
+      if (prof) HIPCHK(hipEventRecord(m->triEv[ev++], s));
+      for (int i = 0; i < nNb; i++) {
+        if (!hNb[i].usable) continue;
+        const int takenWords = (hNb[i].k2.n + 31) / 32;
+        hipLaunchKernelGGL(k_resolve, dim3(1), dim3(64), 2 * sizeof(unsigned) * takenWords, s, dCalls + i, (const FrameDev*)nullptr, m->pool.as<uint32_t>(), takenWords);
+        if (prof) HIPCHK(hipEventRecord(m->triEv[ev++], s));
+        ga.nb = i;
+        hipLaunchKernelGGL(mapdbtri::k_mapdb_tri_geometry, dim3(qBlocks), dim3(mapdbtri::kThreads), 0, s, ga);
+        if (prof) HIPCHK(hipEventRecord(m->triEv[ev++], s));
+      }
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(m->hDown.p, p.down, D.bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (*at<int>(m->hDown, dOvf) != 0) {
+      const unsigned* heads = at<unsigned>(m->hDown, dHeads);
+      size_t asked = 0;
+      for (size_t i = 0; i < nn; i++) asked = std::max(asked, (size_t)heads[i]);
+      m->triPoolPerNb = std::max(m->triPoolPerNb * 2, asked + 1024);
+      continue;
+    }
+    if (prof && ev >= 2) {   // the chain's events alternate: after a resolve, after a geometry
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, m->triEv[0], m->triEv[1]) == hipSuccess) m->triMs[TS_SEARCH] += ms;
+      for (size_t e = 2; e < ev; e++)
+        if (hipEventElapsedTime(&ms, m->triEv[e - 1], m->triEv[e]) == hipSuccess) m->triMs[e % 2 == 0 ? TS_RESOLVE : TS_GEOMETRY] += ms;
+      m->triCalls++;
+    }
+    if (nn * n1) {
+      std::memcpy(matched, at<void>(m->hDown, dMatched), 4 * nn * n1);
+      std::memcpy(x3d, at<void>(m->hDown, dX), 12 * nn * n1);
+      std::memcpy(status, at<void>(m->hDown, dSt), nn * n1);
+    }
+    std::memcpy(nMatches, at<void>(m->hDown, dCount), 4 * nn);
+    for (size_t i = 0; i < nn; i++)
+      for (size_t k = 0; k < n1; k++) nAccepted[i] += (status[i * n1 + k] & 15) == YDORB_TRI_ACCEPTED;
+    return YDORB_OK;
+  }
+  set_error("mapdb_create_new_points: candidate record pool kept overflowing");
+  return YDORB_ERR_CAPACITY;
+}
+
+int ydorb_matcher_create_points_times(ydorb_matcher_t* m, float* ms, int32_t* nCalls) {
+  if (!m || !ms || !nCalls) return YDORB_ERR_INVALID_ARG;
+  for (int i = 0; i < TS_COUNT; i++) ms[i] = m->triCalls ? (float)(m->triMs[i] / m->triCalls) : 0.f;
+  *nCalls = m->triCalls;
+  return YDORB_OK;
+}
+
 int ydorb_fuse_search(ydorb_matcher_t* m, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc, int32_t nq,
                       const float* invSigma2, int32_t nLevels, int32_t* best, int32_t* nFound) {
   return ydorb_window_search(m, fv, queries, qdesc, nq, invSigma2, nLevels, 50, best, nFound);
@@ -1084,6 +1286,8 @@ int ydorb_matcher_set_profiling(ydorb_matcher_t* m, int32_t on) {
   for (double& v : m->stageMs) v = 0;
   m->stageCalls = 0;
   m->evPending = false;
+  for (double& v : m->triMs) v = 0;
+  m->triCalls = 0;
   return YDORB_OK;
 }
 

@@ -139,19 +139,11 @@ __device__ __forceinline__ float dist3(float x, float y, float z, const float* O
   return (float)sqrt(((double)nx * (double)nx + (double)ny * (double)ny) + (double)nz * (double)nz);
 }
 
-__global__ __launch_bounds__(kThreads) void k_triangulate_matches(Args g) {
-  const int m = blockIdx.x * kThreads + threadIdx.x;
-  if (m >= g.nMatches) return;
-  // the problem whose range holds m: the last p with start[p] <= m (empty problems share a start and are skipped by "last")
-  int lo = 0, hi = g.nProblems - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (g.start[mid] <= m) lo = mid; else hi = mid - 1;
-  }
-  const ProblemDev P = g.problems[lo];
-  const ViewDev& V1 = g.views[P.first];
-  const ViewDev& V2 = g.views[P.second];
-  const float4 f1 = g.f1[m], f2 = g.f2[m], lv = g.lv[m];
+// The geometry of one match, shared by k_triangulate_matches and k_mapdb_tri_geometry (mapdb_tri_kernels.hip.h): f1 / f2 = (x, y, right_x,
+// depth) of the two features, lv = (levelSigma2[octave1], levelSigma2[octave2], scaleFactors[octave1], scaleFactors[octave2]).  Writes the
+// point where a source produced one (0 0 0 otherwise) and returns the status byte of c_api.h.
+__device__ __forceinline__ uint8_t triangulate_match(const ViewDev& V1, const ViewDev& V2, const float4 f1, const float4 f2, const float4 lv,
+                                                     const float ratioFactor, float& X, float& Y, float& Z) {
   const bool stereo1 = f1.z >= 0, stereo2 = f2.z >= 0;
 
   const float xn1x = (f1.x - V1.cx) * V1.invfx, xn1y = (f1.y - V1.cy) * V1.invfy;
@@ -166,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void k_triangulate_matches(Args g) {
   else if (stereo2) cosS2 = cos_stereo(V2.b, f2.w);
   const float cosS = cosS2 < cosS1 ? cosS2 : cosS1;   // std::min(cosS1, cosS2) literally: a NaN cosS1 stays
 
-  float X = 0, Y = 0, Z = 0;
+  X = 0; Y = 0; Z = 0;
   int src = 0, code = -1;
   if (cosRays < cosS && cosRays > 0 && (stereo1 || stereo2 || (double)cosRays < 0.9998)) {
     src = 1;
@@ -216,12 +208,29 @@ __global__ __launch_bounds__(kThreads) void k_triangulate_matches(Args g) {
       if (d1 == 0 || d2 == 0) code = 7;
       else {
         const float ratioDist = d2 / d1, ratioOctave = lv.z / lv.w;
-        code = (ratioDist * P.ratioFactor < ratioOctave || ratioDist > ratioOctave * P.ratioFactor) ? 8 : 0;
+        code = (ratioDist * ratioFactor < ratioOctave || ratioDist > ratioOctave * ratioFactor) ? 8 : 0;
       }
     }
   }
+  return (uint8_t)(code | (src << 4) | (notFinite ? 0x80 : 0));
+}
+
+static __global__ __launch_bounds__(kThreads) void k_triangulate_matches(Args g) {
+  const int m = blockIdx.x * kThreads + threadIdx.x;
+  if (m >= g.nMatches) return;
+  // the problem whose range holds m: the last p with start[p] <= m (empty problems share a start and are skipped by "last")
+  int lo = 0, hi = g.nProblems - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (g.start[mid] <= m) lo = mid; else hi = mid - 1;
+  }
+  const ProblemDev P = g.problems[lo];
+  const ViewDev& V1 = g.views[P.first];
+  const ViewDev& V2 = g.views[P.second];
+  float X, Y, Z;
+  const uint8_t st = triangulate_match(V1, V2, g.f1[m], g.f2[m], g.lv[m], P.ratioFactor, X, Y, Z);
   g.x3d[3 * (size_t)m] = X; g.x3d[3 * (size_t)m + 1] = Y; g.x3d[3 * (size_t)m + 2] = Z;
-  g.status[m] = (uint8_t)(code | (src << 4) | (notFinite ? 0x80 : 0));
+  g.status[m] = st;
 }
 
 }  // namespace tri

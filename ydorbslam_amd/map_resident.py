@@ -7,14 +7,17 @@ The resident descriptors add the keyframes' descriptor bl
 MapPoint::computeDistinctiveDescriptors over them with no descriptor upload.  The resident point attributes (DESIGN.md section 6q) keep
 normal, distances and descriptor of every point where those queries compute them, and Tracking::searchLocalPoints reads them by slot.  The resident keyframe features
  add each keyframe's keypoints and right coordinates, and MapDb.fuse_search runs the search of fuseByProjection /
-fuseBySim3 for all target keyframes of a LocalMapping::searchInNeighbors direction in one call."""
+fuseBySim3 for all target keyframes of a LocalMapping::searchInNeighbors direction in one call.  The resident BoW feature vectors
+ add each keyframe's DBoW3::FeatureVector, and MapDb.create_new_points runs LocalMapping::createNewMapPoints'
+search and geometry for all neighbours in one call."""
 import ctypes as C
 
 import numpy as np
 
 from . import map_maintenance as M
 from .extractor import KP_DTYPE
-from ._lib import YdFuseTarget, YdMapCorrection, YdMapDbAttrStats, YdMapDbDescStats, YdMapDbFeatStats, YdMapDbRowStats, YdMapDbStats, check, lib
+from ._lib import (YdCreateNeighbour, YdCreateView, YdFuseTarget, YdMapCorrection, YdMapDbAttrStats, YdMapDbBowStats, YdMapDbDescStats,
+                   YdMapDbFeatStats, YdMapDbRowStats, YdMapDbStats, check, lib)
 
 _p = M._p
 
@@ -372,6 +375,50 @@ class MapDb:
         return [dict(best_idx=best[start[f]:start[f + 1]].copy(), status=status[start[f]:start[f + 1]].copy(), n_found=int(n_found[f]),
                      target_status=int(t_status[f])) for f in range(T)]
 
+    # ------------------------------------------------------------------------------------------------------------ BoW feature vectors
+    def enable_bow(self):
+        """Turns the resident BoW feature vectors on; calling it twice is fine."""
+        check(lib().ydorb_mapdb_enable_bow(self._h))
+
+    def set_keyframe_bow(self, kf_slots, bows):
+        """Stages the feature vectors of the keyframes: bows[i] = [m, 2] (node id, feature index) in map order, nodes ascending.  An
+        empty array erases."""
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        bows = [np.asarray(b, np.int64).reshape(-1, 2) for b in bows]
+        assert len(bows) == len(kf_slots)
+        start = np.concatenate([[0], np.cumsum([len(b) for b in bows])]).astype(np.int32)
+        flat = np.concatenate(bows + [np.zeros((0, 2), np.int64)])
+        assert not len(flat) or (0 <= flat[:, 0].min() and flat[:, 0].max() < 2 ** 32)
+        node, feat = np.ascontiguousarray(flat[:, 0].astype(np.uint32)), np.ascontiguousarray(np.clip(flat[:, 1], -2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        check(lib().ydorb_mapdb_set_keyframe_bow(self._h, _p(kf_slots), len(kf_slots), _p(start), _p(node), _p(feat)))
+
+    def export_bow(self):
+        """The device's feature vectors read back: one [m, 2] int64 array (node id, feature index) per keyframe slot 0 .. n_keyframes-1."""
+        k, N = self.n_keyframes, self.bow_stats()["n_entries"]
+        start, node, feat = np.zeros(k + 1, np.int32), np.zeros(max(N, 1), np.uint32), np.zeros(max(N, 1), np.int32)
+        check(lib().ydorb_mapdb_export_bow(self._h, _p(start), _p(node), _p(feat)))
+        assert int(start[-1]) == N
+        return [np.stack([node[start[i]:start[i + 1]].astype(np.int64), feat[start[i]:start[i + 1]].astype(np.int64)], axis=1) for i in range(k)]
+
+    def bow_stats(self):
+        s = YdMapDbBowStats()
+        check(lib().ydorb_mapdb_bow_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in YdMapDbBowStats._fields_}
+
+    def create_new_points(self, matcher, first, neighbours, stereo_only=False, check_orientation=False):
+        """ydorb_mapdb_create_new_points on an OrbMatcher: first = a YdCreateView (create_view), neighbours = [YdCreateNeighbour]
+        (create_neighbour) in the caller's order.  Returns dict(matched_second [n_nb, n], x3d [n_nb, n, 3], status [n_nb, n],
+        n_matches, n_accepted, neighbour_status [n_nb])."""
+        nn, n = len(neighbours), int(first.n)
+        nb = (YdCreateNeighbour * max(nn, 1))(*neighbours)
+        shape = (max(nn, 1), n)   # n == 0: the call gets no output arrays to fill
+        matched, x3d, status = np.full(shape, -7, np.int32), np.full(shape + (3,), 7, np.float32), np.full(shape, 9, np.uint8)
+        n_m, n_a, nb_st = np.full(max(nn, 1), -7, np.int32), np.full(max(nn, 1), -7, np.int32), np.full(max(nn, 1), 9, np.uint8)
+        check(lib().ydorb_mapdb_create_new_points(self._h, matcher._h, C.byref(first), C.cast(nb, C.c_void_p), nn, int(bool(stereo_only)),
+                                                  int(bool(check_orientation)), _p(matched) if n else None, _p(x3d) if n else None,
+                                                  _p(status) if n else None, _p(n_m), _p(n_a), _p(nb_st)))
+        return dict(matched_second=matched[:nn], x3d=x3d[:nn], status=status[:nn], n_matches=n_m[:nn], n_accepted=n_a[:nn], neighbour_status=nb_st[:nn])
+
     # ------------------------------------------------------------------------------------------------------------ inspection
     def stats(self):
         s = YdMapDbStats()
@@ -399,3 +446,24 @@ class _Header:
 
     def span_lengths(self):
         return self._db.span_lengths()
+
+
+def create_view(kf_slot, depth, Tcw, Ow, fx, fy, cx, cy, b, bf, level_sigma2, scale_factors):
+    """A YdCreateView over numpy arrays: Tcw [3, 4], Ow [3]; Rwc = Rcw^T; invfx = 1.0f / fx as the reference stores it.  The struct
+    points into `depth`: the returned pair keeps it alive."""
+    depth = np.ascontiguousarray(depth, np.float32).reshape(-1)
+    Tcw = np.ascontiguousarray(Tcw, np.float32).reshape(3, 4)
+    Rwc = np.ascontiguousarray(Tcw[:, :3].T)
+    s2, sf = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (level_sigma2, scale_factors))
+    assert len(s2) == len(sf)
+    L = len(sf)
+    pad = lambda a: (C.c_float * 8)(*([float(x) for x in a[:8]] + [0.0] * max(8 - L, 0)))
+    v = YdCreateView(kf_slot=int(kf_slot), n=len(depth), depth=_p(depth) if len(depth) else None, Tcw=(C.c_float * 12)(*Tcw.reshape(-1)),
+                     Rwc=(C.c_float * 9)(*Rwc.reshape(-1)), Ow=(C.c_float * 3)(*np.asarray(Ow, np.float32).reshape(-1)), fx=fx, fy=fy, cx=cx, cy=cy,
+                     invfx=float(np.float32(1.0) / np.float32(fx)), invfy=float(np.float32(1.0) / np.float32(fy)), b=b, bf=bf,
+                     level_sigma2=pad(s2), scale_factors=pad(sf), n_levels=L)
+    return v, depth
+
+
+def create_neighbour(view, F, ex, ey, ratio_factor):
+    return YdCreateNeighbour(view=view, F=(C.c_float * 9)(*np.asarray(F, np.float32).reshape(-1)), ex=ex, ey=ey, ratio_factor=ratio_factor)
