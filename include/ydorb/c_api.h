@@ -1172,6 +1172,70 @@ int ydorb_mapdb_observer_counter(ydorb_mapdb_t* db, int32_t n_lists, const int32
                                  const int32_t* out_start, int32_t* conn_kf, int32_t* conn_weight, int32_t* counts, uint8_t* status,
                                  uint8_t* point_bad);
 
+/* Local BA graph (DESIGN.md section 2 "Local BA graph on the resident table: the integer contract", section 6u): the flat graph that
+ * the adapter's localBundleAdjustImpl (include/ydorb/optimizer.hpp:59-113; the reference's src/optimizer.cpp:140-283) assembles by
+ * walking keyframes, map points and observation maps on the host, assembled on the device from what is resident: the keyframe rows,
+ * the point views, the keyframe features (ydorb_mapdb_enable_features, declared below), the fp32 positions and the bad flags.  Only the
+ * poses are not resident; the caller fills them.  The result is integer selection plus exact fp32 -> fp64 widening, and equals the
+ * sequential loops bit for bit, edge order included (the BA's fixed-order sums depend on it).
+ *   1. local points   the rows of kf_slots concatenated in the order given; the entries that are not -1, not bad and the first
+ *                     occurrence of their slot, in that order: ydorb_mapdb_points_of_keyframes with n_seen = 0.
+ *   2. usable         a keyframe is usable (= !isBad()) when it has a feature span of length > 0; a view is usable when its keyframe
+ *                     is and idx is below that length.
+ *   3. fixed          walk the local points in order and each point's views in span order: a usable keyframe that is not in kf_slots
+ *                     is appended at its first occurrence, whatever that view's idx (a view past the feature length still names
+ *                     a keyframe that is not bad; such a keyframe may end up with a pose and no edge).
+ *   4. edges          the same walk emits one edge per usable view.  Every usable observer is local or fixed, so the reference's
+ *                     poseIndex lookup (optimizer.hpp:104-105) never misses and its maxKFid test (:103) is vacuous.  edge_pose = the
+ *                     keyframe's index in the pose list, edge_point = the point's rank in the local point list, meas = ((double)kp.x,
+ *                     (double)kp.y, right_x < 0 ? -1.0 : (double)right_x), inv_sigma2 = (double)inv_level_sigma2[kp.octave];
+ *                     points[p] = the resident fp32 position widened to double.
+ *   5. point_status   an OR of the bits below; 0 = every view was usable.  A point without an edge stays in the point list, as in the
+ *                     reference.
+ * Every keyframe of kf_slots gets a pose, pose i < n_local being kf_slots[i], with pose_fixed = 0: the caller leaves bad keyframes out
+ * of the list, as the adapter does, and marks keyframe id 0 as fixed itself.
+ * Result memory: the arrays live in pinned host memory owned by the handle and stay valid until the next ydorb_mapdb_local_ba_graph,
+ * ydorb_mapdb_clear or destroy on that handle; problem.poses ([n_poses][7], left for the caller) and problem.pose_fixed are writable
+ * there.  A caller-capacity protocol like points_of_keyframes' was considered and rejected: the edge count has no cheap bound on the
+ * caller's side, and the BA's upload is faster from pinned memory.
+ * Refused up front on the host with YDORB_ERR_INVALID_ARG naming the first offender, before any device work and with the handle and
+ * the previous result unchanged: null arguments, n_kf < 0, a slot outside 0..n_keyframes-1, a slot repeated in kf_slots, features not
+ * enabled.  (The view relation of this handle is always present; MapMirror::localBaGraph of include/ydorb/mapMirror.hpp refuses when
+ * enableDescriptors() was not called, because the mirror stages views only then.)
+ * n_kf == 0 gives an empty graph, launches nothing and leaves what is staged staged.  Otherwise the call applies what is staged, in
+ * the handle's usual order, before it reads, and takes the table's mutex as the other queries do.
+ * Assumptions for a maintainer who holds the reference to check: the order of MapPoint::getObservations() is that of the view spans
+ * (the caller stages views in that order, as for computeDistinctiveDescriptors); KeyFrame::isBad() <=> the keyframe has no feature
+ * span (a culled keyframe's features are erased with a span of length 0); every keyframe observing a local point carries the
+ * m_int_localBAForKeyFrameID / m_int_fixedBAForKeyFrameID tags only from this call (optimizer.hpp:61-76). */
+#define YDORB_LBA_POINT_SKIPPED_VIEWS 1      /* some view named an unusable keyframe: normal */
+#define YDORB_LBA_POINT_VIEW_OUT_OF_RANGE 2  /* a view of a usable keyframe has idx >= the feature length: it emits nothing, nothing is read for it */
+#define YDORB_LBA_POINT_NO_EDGES 4           /* the point produced no edge */
+typedef struct YdLocalBaGraph {
+  YdBaProblem problem;         /* all arrays filled except: poses (allocated [n_poses][7], left for the caller), fx..bf and stop
+                                  (caller); pose_fixed = 0 for local, 1 for fixed keyframes */
+  int32_t n_local, n_fixed;    /* problem.n_poses = n_local + n_fixed; pose i < n_local is kf_slots[i] */
+  const int32_t* pose_kf;      /* [n_poses] keyframe slot of every pose */
+  const int32_t* point_slot;   /* [n_points] */
+  const int32_t* edge_kf;      /* [n_edges] keyframe slot and */
+  const int32_t* edge_idx;     /* [n_edges] keypoint index of every edge: what the write-back erases */
+  const uint8_t* point_status; /* [n_points] YDORB_LBA_POINT_* */
+} YdLocalBaGraph;
+typedef struct YdMapDbLbaStats {
+  int64_t n_calls;                      /* calls that passed validation */
+  int64_t last_launches, last_syncs;    /* kernels launched (the staged deltas' not counted) and stream synchronisations of the last call */
+  int64_t last_upload_bytes, last_download_bytes;   /* the call's own arrays up; the counts and the result down */
+  int64_t last_n_local, last_n_fixed, last_n_points, last_n_edges;
+  /* device time of the last call's phases from event pairs, filled only after ydorb_mapdb_lba_set_profiling(db, 1), else 0:
+   * the local points (k_rowset_*), the view walk (rank, mark, count, scan), the emit (fixed, edges, reset), the result's read-back */
+  double last_ms_points, last_ms_walk, last_ms_emit, last_ms_copy;
+} YdMapDbLbaStats;
+int ydorb_mapdb_local_ba_graph(ydorb_mapdb_t* db, const int32_t* kf_slots, int32_t n_kf, const float* inv_level_sigma2 /*[8]*/,
+                               YdLocalBaGraph* out);
+int ydorb_mapdb_lba_stats(ydorb_mapdb_t* db, YdMapDbLbaStats* stats);
+/* Opt-in: six stream events round the phases of every later call (a few microseconds of stream time each); off by default. */
+int ydorb_mapdb_lba_set_profiling(ydorb_mapdb_t* db, int32_t on);
+
 /* Resident descriptors (DESIGN.md section 2 "Distinctive descriptor on the resident table", section 6p): two more relations of the
  * resident table and the query that closes the pair computeDistinctiveDescriptors() / updateNormalAndDepth() on it.
  *   blocks  keyframe slot -> the keyframe's descriptor matrix [n_k][32] in keypoint order (m_cvMat_descriptors).  A keyframe's

@@ -36,6 +36,9 @@
 // forget(kf) erases the span; createNewPoints is the search and the geometry of LocalMapping::createNewMapPoints for all neighbours in
 // ONE call (localMapping.hpp's overload over a mirror runs the bookkeeping on its result); verifyBow() is verify() for them.  It needs
 // enableFeatures() and the descriptor blocks too.  Assumed spelling beyond the others: KeyFrame m_bow_keyPointsVec (DBoW3::FeatureVector).
+// localBaGraph(localKeyFrames) is the flat graph of Optimizer::localBundleAdjust assembled on the table in ONE call (DESIGN.md section
+// 6u; optimizer.hpp's overload over a mirror fills the poses, solves and runs the write-back with its touches).  It needs
+// enableDescriptors() and enableFeatures().  Assumed spelling beyond the others: KeyFrame m_v_invScaleFactorSquares.
 // Assumed spellings: those of mapPoint.hpp; m_cvMat_descriptors (one CV_8U row of 32 bytes per keypoint) for the blocks, keyFrame.hpp and localMapping.hpp; for the three correction methods also optimizer.hpp's
 // MapPoint::setPosInWorld(cv::Mat), m_int_correctedByKeyFrameID, m_int_correctedReference and the Sim3 members rotation().x() .. w(),
 // translation()[k], scale().  The camera centre after a corrected pose is not read from a member: correctLoopPoints computes it from
@@ -687,6 +690,37 @@ class MapMirror {
       updated++;
     }
     return updated;
+  }
+
+  // The flat graph of localBundleAdjust for the local keyframes given (ydorb_mapdb_local_ba_graph), with the
+  // slots translated back.  `graph` points into pinned memory the handle owns: it stays valid until the next localBaGraph or clear(),
+  // and graph.problem.poses / pose_fixed are the caller's to fill.  Needs enableDescriptors() (the points' views) and enableFeatures():
+  // without either it refuses.  The caller leaves bad keyframes out of the list, as the flat body does.
+  struct LocalBaGraph {
+    YdLocalBaGraph graph;
+    std::vector<KeyFramePtr> poseKF;     // [n_poses]
+    std::vector<MapPointPtr> pointMP;    // [n_points]
+    std::vector<KeyFramePtr> edgeKF;     // [n_edges]; graph.edge_idx has the keypoint index
+  };
+  LocalBaGraph localBaGraph(const std::vector<KeyFramePtr>& localKeyFrames) {
+    if (!descriptors_) throw std::runtime_error("ydorb: localBaGraph without enableDescriptors(): the points' views are not resident");
+    if (!features_) throw std::runtime_error("ydorb: localBaGraph without enableFeatures()");
+    std::vector<int32_t> slots;
+    for (const KeyFramePtr& kf : localKeyFrames) slots.push_back(kfSlotFor(kf));
+    flush();
+    float sigma[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // one pyramid for all keyframes
+    for (const KeyFramePtr& kf : kfOf_)
+      if (kf) {
+        for (size_t l = 0; l < 8 && l < kf->m_v_invScaleFactorSquares.size(); l++) sigma[l] = kf->m_v_invScaleFactorSquares[l];
+        break;
+      }
+    LocalBaGraph G;
+    mapCheck(ydorb_mapdb_local_ba_graph(db_, slots.data(), (int32_t)slots.size(), sigma, &G.graph));
+    const YdBaProblem& P = G.graph.problem;
+    for (int32_t i = 0; i < P.n_poses; i++) G.poseKF.push_back(kfOf_.at((size_t)G.graph.pose_kf[i]));
+    for (int32_t p = 0; p < P.n_points; p++) G.pointMP.push_back(pointOf_.at((size_t)G.graph.point_slot[p]));
+    for (int32_t e = 0; e < P.n_edges; e++) G.edgeKF.push_back(kfOf_.at((size_t)G.graph.edge_kf[e]));
+    return G;
   }
 
   // covisibilityCounter of keyFrame.hpp over the resident table

@@ -139,6 +139,64 @@ void localBundleAdjustImpl(KeyFramePtr kf0, MapPtr map, const volatile bool* sto
   }
 }
 
+// localBundleAdjust over a MapMirror (mapMirror.hpp) with enableDescriptors() and enableFeatures(): the body of the reference becomes
+//   ydorb::adapter::localBundleAdjustImpl<Frame>(mirror, kf, map, &stop == nullptr ? nullptr : &stop, apply);
+// The covisibility list (kf0 + getOrderedConnectedKeyFrames() minus bad) stays on the host; the local points, the fixed keyframes and
+// every edge come from ONE mirror.localBaGraph call on the resident table (ydorb_mapdb_local_ba_graph), in the
+// flat body's order, so the solve is the flat body's bit for bit.  Only the poses are read from the keyframes.  The write-back follows
+// the flat body and tells the mirror what it changed: an erased observation touches the point and the keyframe's row entry (the
+// keypoint index is the graph's edge_idx), a moved keyframe its centre, a moved point its position; then ONE
+// mirror.updateNormalAndDepth over all points in place of a call per point, apply(mp, normal, minDistance, maxDistance) storing what
+// MapPoint::updateNormalAndDepth would.  Of the reference's BA tags only the local keyframes' m_int_localBAForKeyFrameID is written:
+// the point and fixed-keyframe tags exist to build the lists, which the table does here.
+template <class FrameT, class MirrorT, class KeyFramePtr, class MapPtr, class Apply>
+void localBundleAdjustImpl(MirrorT& mirror, KeyFramePtr kf0, MapPtr map, const volatile bool* stop, Apply apply, int solver = YDORB_BA_SOLVER_AUTO) {
+  const long int tag = kf0->m_int_keyFrameID;
+  std::vector<KeyFramePtr> localKFs{kf0};
+  kf0->m_int_localBAForKeyFrameID = tag;
+  for (const KeyFramePtr& c : kf0->getOrderedConnectedKeyFrames()) {
+    c->m_int_localBAForKeyFrameID = tag;
+    if (!c->isBad()) localKFs.push_back(c);
+  }
+  auto G = mirror.localBaGraph(localKFs);
+  YdBaProblem P = G.graph.problem;
+  const size_t nLocal = (size_t)G.graph.n_local, nPoints = (size_t)P.n_points, nEdges = (size_t)P.n_edges;
+  uint8_t* fixed = const_cast<uint8_t*>(P.pose_fixed);   // writable in the handle's result (c_api.h)
+  for (size_t k = 0; k < G.poseKF.size(); k++) {
+    poseToSE3Quat(G.poseKF[k]->getCameraPoseByTransform_c2w(), P.poses + 7 * k);
+    if (k < nLocal && G.poseKF[k]->m_int_keyFrameID == 0) fixed[k] = 1;
+  }
+  if (stop && *stop) return;  // :284-286
+  P.fx = FrameT::m_flt_fx; P.fy = FrameT::m_flt_fy; P.cx = FrameT::m_flt_cx; P.cy = FrameT::m_flt_cy; P.bf = FrameT::m_flt_baseLineTimesFx;
+  P.stop = reinterpret_cast<const volatile uint8_t*>(stop);
+  std::vector<uint8_t> outlier(nEdges + 1, 0);
+  YdBaResult res{};
+  res.edge_outlier = outlier.data();
+  const YdBaSolverOptions SO = {solver, YDORB_ESS_ORDER_SMALLER, 0};
+  if (ydorb_ba_solve_with(&P, nullptr, &SO, &res, nullptr) != YDORB_OK) throw std::runtime_error(std::string("ydorb: ") + ydorb_last_error());
+  // write-back (:336-351)
+  std::unique_lock<std::mutex> lock(map->m_mutex_updateMap);
+  for (size_t e = 0; e < nEdges; e++) {
+    const auto& mp = G.pointMP[(size_t)P.edge_point[e]];
+    if (!outlier[e] || mp->isBad()) continue;
+    G.edgeKF[e]->eraseMatchedMapPoint(mp);
+    mp->eraseObservation(G.edgeKF[e]);
+    mirror.touch(mp);
+    mirror.touchEntry(G.edgeKF[e], (size_t)G.graph.edge_idx[e]);
+  }
+  for (size_t k = 0; k < nLocal; k++) {
+    G.poseKF[k]->setCameraPoseByTransform_c2w(se3QuatToPose(P.poses + 7 * k));
+    mirror.touch(G.poseKF[k]);
+  }
+  for (size_t p = 0; p < nPoints; p++) {
+    cv::Mat X(3, 1, CV_32F);
+    for (int d = 0; d < 3; d++) X.at<float>(d) = (float)P.points[3 * p + d];
+    G.pointMP[p]->setPosInWorld(X);
+    mirror.touchPosition(G.pointMP[p]);
+  }
+  mirror.updateNormalAndDepth(G.pointMP, apply);
+}
+
 // Optimizer::bundleAdjust (optimizer.cpp:7-137): every given keyframe (id 0 fixed) and map point, ONE optimize(iterNum) call, Huber
 // optional; results go to the vertices' GBA fields when loopKeyFrameID != 0 (:113-136).  Same C ABI call with
 // YDORB_BA_SINGLE_STAGE; the body of

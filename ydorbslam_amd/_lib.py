@@ -141,6 +141,9 @@ SYMBOLS = {
     "ydorb_mapdb_row_stats": (C.c_int, [_VP, _VP]),
     "ydorb_mapdb_points_of_keyframes": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP]),
     "ydorb_mapdb_observer_counter": (C.c_int, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_local_ba_graph": (C.c_int, [_VP, _VP, _I, _VP, _VP]),
+    "ydorb_mapdb_lba_stats": (C.c_int, [_VP, _VP]),
+    "ydorb_mapdb_lba_set_profiling": (C.c_int, [_VP, _I]),
     "ydorb_mapdb_reserve_descriptors": (C.c_int, [_VP, C.c_int64, C.c_int64]),
     "ydorb_mapdb_set_keyframe_descriptors": (C.c_int, [_VP, _VP, _I, _VP, _VP]),
     "ydorb_mapdb_set_point_views": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP]),
@@ -280,6 +283,17 @@ class YdMapDbFeatStats(C.Structure):
 class YdMapDbBowStats(C.Structure):
     _fields_ = [("enabled", _I), ("repacks_kept", _I), ("repacks_grown", _I), ("n_entries", C.c_int64), ("pool_used", C.c_int64),
                 ("pool_capacity", C.c_int64), ("last_bow_sync_bytes", C.c_int64), ("last_bow_sync_records", C.c_int64)]
+
+
+class YdMapDbLbaStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_calls", "last_launches", "last_syncs", "last_upload_bytes", "last_download_bytes", "last_n_local",
+                                         "last_n_fixed", "last_n_points", "last_n_edges")] + \
+               [(n, C.c_double) for n in ("last_ms_points", "last_ms_walk", "last_ms_emit", "last_ms_copy")]
+
+
+class YdLocalBaGraph(C.Structure):
+    _fields_ = [("problem", YdBaProblem), ("n_local", _I), ("n_fixed", _I), ("pose_kf", _VP), ("point_slot", _VP), ("edge_kf", _VP),
+                ("edge_idx", _VP), ("point_status", _VP)]
 
 
 class YdCreateView(C.Structure):

@@ -11,6 +11,9 @@
 //                         (mapdb_bow_host.h, section 6t), which share the two kernels of mapdb_span_kernels.hip.h, and the opt-in
 //                         keyframe features (mapdb_feat_host.h, section 6r), whose one pool arena holds two arrays and has kernels
 //                         of its own (mapdb_feat_kernels.hip.h).
+//   the local-BA graph    no relation of its own: ydorb_mapdb_local_ba_graph reads rows, views, features, positions and bad flags and
+//                         keeps two per-keyframe tables that are clean between calls and a pinned result (mapdb_lba_host.h,
+//                         mapdb_lba_kernels.hip.h, section 6u).
 // The set_* entries only stage.  A query calls sync() first, which applies what is staged in a fixed order: points, rows, views, blocks,
 // features if enabled, BoW feature vectors if enabled, attributes if enabled.  A later part may name what an earlier one introduced
 // in the same interval: a row a new point, a view a new keyframe, the attribute arena the point capacity just grown.  Each part: one upload of its packed delta, the
@@ -42,6 +45,8 @@
 #include "mapdb_frustum_kernels.hip.h"
 #include "mapdb_host.h"
 #include "mapdb_kernels.hip.h"
+#include "mapdb_lba_host.h"
+#include "mapdb_lba_kernels.hip.h"
 #include "mapdb_resident_points.h"
 #include "mapdb_rows_host.h"
 #include "mapdb_rows_kernels.hip.h"
@@ -197,6 +202,19 @@ struct ydorb_mapdb {
   // keyframe BoW feature vectors: nothing of this is allocated or launched until ydorb_mapdb_enable_bow
   mapdb::BowHost bow;
   SpanDev<mapdb::BowRec> dBow;
+  // local-BA graph: nothing of this is allocated or launched until ydorb_mapdb_local_ba_graph.  lbaFirst / lbaPoseOf
+  // have one entry per keyframe slot and are UINT64_MAX / -1 everywhere between calls (mapdb_lba_kernels.hip.h); lbaDirty: a call failed
+  // between its first launch and its last synchronise, the next one fills both before it starts.  The result lives in lbaHost.
+  Mem lbaTables, lbaDev;
+  PinnedMem lbaHost;
+  unsigned long long* lbaFirst = nullptr;
+  int* lbaPoseOf = nullptr;
+  size_t lbaCap = 0;
+  bool lbaDirty = false;
+  std::vector<uint8_t> lbaMark;   // scratch of the repeat test
+  YdMapDbLbaStats lbaStats{};
+  bool lbaProfiling = false;
+  hipEvent_t lbaEvent[6] = {};    // created by the first ydorb_mapdb_lba_set_profiling(db, 1)
   ydorb_mapdb(int32_t pc, int32_t kc, int64_t oc) : host(pc, kc, oc), rows(kc, oc), desc(pc, kc), feat(kc), bow(kc) {}
 };
 
@@ -450,6 +468,45 @@ int ensureRowset(ydorb_mapdb* h) {
   return YDORB_OK;
 }
 
+// mark, count, emit with no host round trip between them (mapdb_rows_kernels.hip.h)
+int launchRowset(hipStream_t s, const mapdb::RowsetArgs& a) {
+  const size_t forMark = ((size_t)std::max(a.nE, a.nSeen) + mapdb::kRowThreads - 1) / mapdb::kRowThreads;
+  hipLaunchKernelGGL(mapdb::k_rowset_mark, dim3((unsigned)forMark), dim3(mapdb::kRowThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mapdb::k_rowset_count, dim3((unsigned)a.nBlocks), dim3(mapdb::kRowThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mapdb::k_rowset_emit, dim3((unsigned)a.nBlocks), dim3(mapdb::kRowThreads), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return YDORB_OK;
+}
+
+// the call's stamp for seenStamp: a later call has a later stamp
+int nextRowsetStamp(ydorb_mapdb* h) {
+  if (h->stamp == INT32_MAX) { HIPCHK(hipMemsetAsync(h->seenStamp, 0, 4 * h->rowsetCap, h->c.stream)); h->stamp = 0; }
+  h->stamp++;
+  return YDORB_OK;
+}
+
+// lbaFirst / lbaPoseOf cover the table's keyframe slots: a fresh pair when they outgrew it, every byte 0xff (UINT64_MAX and -1)
+int ensureLbaTables(ydorb_mapdb* h) {
+  const size_t need = (size_t)h->host.nKeyframes();
+  hipStream_t s = h->c.stream;
+  if (need > h->lbaCap) {
+    const size_t cap = std::max<size_t>(2 * need, 64);
+    h->lbaCap = 0;
+    int rc = h->lbaTables.alloc(12 * cap);
+    if (rc) return rc;
+    h->lbaFirst = h->lbaTables.as<unsigned long long>(); h->lbaPoseOf = reinterpret_cast<int*>(h->lbaFirst + cap);
+    h->lbaCap = cap;
+    h->lbaDirty = true;
+  }
+  if (h->lbaDirty) {
+    HIPCHK(hipMemsetAsync(h->lbaTables.p, 0xff, 12 * h->lbaCap, s));
+    h->lbaDirty = false;
+  }
+  return YDORB_OK;
+}
+
 // the table and the point attributes as the queries of map_queries.h read them: call after sync(), which may move the arenas
 mapmaint::MapSource sourceOf(const ydorb_mapdb* h) {
   mapmaint::MapSource src;
@@ -498,6 +555,8 @@ extern "C" void ydorb_mapdb_destroy(ydorb_mapdb_t* h) {
   h->points.release(); h->centres.release(); h->pool.release(); h->delta.release(); h->rowset.release();
   h->attrMem.release(); h->attrDelta.release();
   h->dRows.release(); h->dViews.release(); h->dBlocks.release(); h->dFeats.release(); h->dBow.release();
+  h->lbaTables.release(); h->lbaDev.release(); h->lbaHost.release();
+  for (hipEvent_t e : h->lbaEvent) if (e) (void)hipEventDestroy(e);
   delete h;
 }
 
@@ -816,8 +875,7 @@ extern "C" int ydorb_mapdb_points_of_keyframes(ydorb_mapdb_t* h, const int32_t* 
   if ((rc = ensureRowset(h))) return rc;
   StagedCtx& c = h->c;
   hipStream_t s = c.stream;
-  if (h->stamp == INT32_MAX) { HIPCHK(hipMemsetAsync(h->seenStamp, 0, 4 * h->rowsetCap, s)); h->stamp = 0; }
-  h->stamp++;
+  if ((rc = nextRowsetStamp(h))) return rc;
   const size_t nE = (size_t)total, nB = (nE + mapdb::kRowThreads - 1) / mapdb::kRowThreads, capOut = std::min<size_t>((size_t)capacity, nE);
   Layout U;
   const size_t oKf = U.add(4 * nk), oEs = U.add(4 * (nk + 1)), oSeen = U.add(4 * ns);
@@ -838,13 +896,7 @@ extern "C" int ydorb_mapdb_points_of_keyframes(ydorb_mapdb_t* h, const int32_t* 
   a.first = h->first; a.seenStamp = h->seenStamp;
   a.ent = at<int>(c.scratch, wEnt); a.blockTotal = at<int>(c.scratch, wBlock);
   a.outSlots = at<int>(c.down, dSlots); a.outSeen = at<uint8_t>(c.down, dSeen); a.total = at<int>(c.down, dTotal);
-  const size_t forMark = (std::max(nE, ns) + mapdb::kRowThreads - 1) / mapdb::kRowThreads;
-  hipLaunchKernelGGL(mapdb::k_rowset_mark, dim3((unsigned)forMark), dim3(mapdb::kRowThreads), 0, s, a);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(mapdb::k_rowset_count, dim3((unsigned)nB), dim3(mapdb::kRowThreads), 0, s, a);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(mapdb::k_rowset_emit, dim3((unsigned)nB), dim3(mapdb::kRowThreads), 0, s, a);
-  HIPCHK(hipGetLastError());
+  if ((rc = launchRowset(s, a))) return rc;
   HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, D.bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   const int32_t kept = *at<int32_t>(c.hDown, dTotal);
@@ -890,6 +942,162 @@ extern "C" int ydorb_mapdb_observer_counter(ydorb_mapdb_t* h, int32_t n_lists, c
   if (rc) return rc;
   mapmaint::MapSource src = sourceOf(h);
   return mapmaint::runCovisibility(h->c, src, self.data(), n_lists, ls.data(), idx.data(), out_start, conn_kf, conn_weight, counts, status);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- local BA graph
+// sync; one upload of the keyframe slots, their starts in E and the sigma table; the rowset kernels, rank, mark, count, scan; a 16-byte
+// read-back of the three counts and the first synchronise; the result area laid out for them; fixed, edges, reset; one read-back of
+// what the device wrote into the pinned result and the second synchronise.  The point count is not read back on its own: mark, count
+// and scan are launched over its bound min(|E|, n_points) and the lanes past the device-side count return.
+extern "C" int ydorb_mapdb_local_ba_graph(ydorb_mapdb_t* h, const int32_t* kf_slots, int32_t n_kf, const float* inv_level_sigma2, YdLocalBaGraph* out) {
+  if (!h) {   // without a device no handle exists: say that, there is no CPU path to fall back to
+    const int rc = require_device(0);
+    return rc ? rc : invalid("null handle");
+  }
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!mapdb::checkLbaArgs(kf_slots, n_kf, inv_level_sigma2, out, h->host.nKeyframes(), h->feat.enabled(), h->lbaMark, err)) return invalid(err);
+  HIPCHK(hipSetDevice(h->device));
+  StagedCtx& c = h->c;
+  hipStream_t s = c.stream;
+  YdMapDbLbaStats st{};
+  st.n_calls = h->lbaStats.n_calls + 1;
+  st.last_n_local = n_kf;
+  const size_t nk = (size_t)n_kf;
+  int rc;
+  std::vector<int32_t> eStart(nk + 1, 0);
+  int64_t total = 0;
+  for (size_t r = 0; r < nk; r++) {   // the mirror with its staged rows: what the device holds after the sync below
+    total += h->rows.lenOf(kf_slots[r]);
+    if (total > INT32_MAX) return invalid("the rows of kf_slots hold more than INT32_MAX entries");
+    eStart[r + 1] = (int32_t)total;
+  }
+  if (n_kf > 0 && (rc = sync(h))) return rc;
+  const size_t nE = (size_t)total, bound = std::min<size_t>(nE, (size_t)h->host.nPoints());
+  if (bound == 0) {   // no keyframe (nothing synced: what is staged stays staged), or none with a row: the poses alone, nothing launched
+    const mapdb::LbaLayout L(nk, 0, 0);
+    if ((rc = h->lbaHost.ensure(L.bytes))) return rc;
+    uint8_t* base = h->lbaHost.as<uint8_t>();
+    std::memset(base, 0, L.bytes);
+    if (nk) std::memcpy(base + L.oPoseKf, kf_slots, 4 * nk);
+    mapdb::lbaPointResult(L, base, n_kf, 0, 0, 0, out);
+    h->lbaStats = st;
+    return YDORB_OK;
+  }
+  if ((rc = ensureRowset(h)) || (rc = nextRowsetStamp(h)) || (rc = ensureLbaTables(h))) return rc;
+  const size_t nBr = (nE + mapdb::kRowThreads - 1) / mapdb::kRowThreads, nBp = (bound + mapdb::kLbaThreads - 1) / mapdb::kLbaThreads;
+  Layout U;
+  const size_t oKf = U.add(4 * nk), oEs = U.add(4 * (nk + 1)), oSigma = U.add(32);
+  Layout W;
+  const size_t wEnt = W.add(4 * nE), wBlock = W.add(4 * nBr), wSlots = W.add(4 * bound), wSeen = W.add(bound), wTotal = W.add(4), wStatus = W.add(bound),
+               wEdgeCount = W.add(4 * bound), wWinCount = W.add(4 * bound), wEdgeOff = W.add(4 * bound), wWinOff = W.add(4 * bound),
+               wBlockEdge = W.add(4 * nBp), wBlockWin = W.add(4 * nBp);
+  if ((rc = c.ensure(U.bytes, 16, W.bytes))) return rc;
+  std::memcpy(at<void>(c.hUp, oKf), kf_slots, 4 * nk);
+  std::memcpy(at<void>(c.hUp, oEs), eStart.data(), 4 * (nk + 1));
+  std::memcpy(at<void>(c.hUp, oSigma), inv_level_sigma2, 32);
+  HIPCHK(hipMemcpyAsync(c.up.p, c.hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  st.last_upload_bytes = (int64_t)U.bytes;
+  const bool timed = h->lbaProfiling;
+  const auto stampEvent = [&](int i) { return timed ? hipEventRecord(h->lbaEvent[i], s) : hipSuccess; };
+  HIPCHK(stampEvent(0));
+  mapdb::RowsetArgs r;
+  r.nKf = n_kf; r.nE = (int)nE; r.nSeen = 0; r.stamp = h->stamp; r.capacity = (int)bound; r.nBlocks = (int)nBr;
+  r.kfSlots = at<int>(c.up, oKf); r.eStart = at<int>(c.up, oEs); r.seen = nullptr;
+  r.rowStart = h->dRows.start; r.rowLen = h->dRows.len; r.pool = h->dRows.pool; r.bad = h->T.bad;
+  r.first = h->first; r.seenStamp = h->seenStamp;
+  r.ent = at<int>(c.scratch, wEnt); r.blockTotal = at<int>(c.scratch, wBlock);
+  r.outSlots = at<int>(c.scratch, wSlots); r.outSeen = at<uint8_t>(c.scratch, wSeen); r.total = at<int>(c.scratch, wTotal);
+  if ((rc = launchRowset(s, r))) return rc;
+  HIPCHK(stampEvent(1));
+  mapdb::LbaArgs a{};
+  a.nLocal = n_kf; a.nKfAll = h->host.nKeyframes(); a.bound = (int)bound; a.nBlocks = (int)nBp;
+  a.nViewHdr = h->desc.views.hdrCap(); a.nFeatHdr = h->feat.feats.hdrCap();
+  a.invLevelSigma2 = at<float>(c.up, oSigma); a.kfSlots = at<int>(c.up, oKf);
+  a.nPoints = r.total; a.pointSlot = r.outSlots;
+  a.viewStart = h->dViews.start; a.viewLen = h->dViews.len; a.viewPool = h->dViews.pool;
+  a.featStart = h->dFeats.start; a.featLen = h->dFeats.len;
+  a.kps = reinterpret_cast<const YdKeyPoint*>(featKps(h->dFeats.pool));
+  a.rightX = reinterpret_cast<const float*>(featRightX(h->dFeats.pool, h->feat.feats.poolCap()));
+  a.pos = h->T.pos; a.poseOf = h->lbaPoseOf; a.first = h->lbaFirst;
+  a.status = at<uint8_t>(c.scratch, wStatus); a.edgeCount = at<int>(c.scratch, wEdgeCount); a.winCount = at<int>(c.scratch, wWinCount);
+  a.edgeOff = at<int>(c.scratch, wEdgeOff); a.winOff = at<int>(c.scratch, wWinOff);
+  a.blockEdge = at<int>(c.scratch, wBlockEdge); a.blockWin = at<int>(c.scratch, wBlockWin); a.counts = c.down.as<int>();
+  const auto blocks = [](size_t n) { return dim3((unsigned)std::max<size_t>((n + mapdb::kLbaThreads - 1) / mapdb::kLbaThreads, 1)); };
+  const dim3 threads(mapdb::kLbaThreads);
+  h->lbaDirty = true;   // until the reset below has run
+  hipLaunchKernelGGL(mapdb::k_lba_rank, blocks(nk), threads, 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mapdb::k_lba_mark, dim3((unsigned)nBp), threads, 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mapdb::k_lba_count, dim3((unsigned)nBp), threads, 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mapdb::k_lba_scan, dim3((unsigned)nBp), threads, 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(stampEvent(2));
+  HIPCHK(hipMemcpyAsync(c.hDown.p, c.down.p, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const int32_t nP = c.hDown.as<int32_t>()[0], nEdges = c.hDown.as<int32_t>()[1], nFixed = c.hDown.as<int32_t>()[2];
+  if (nP < 0 || (size_t)nP > bound || nEdges < 0 || nFixed < 0 || nFixed > a.nKfAll) {
+    set_error("resident map table: local BA graph: counts %d points, %d edges, %d fixed keyframes are out of range", nP, nEdges, nFixed);
+    return YDORB_ERR_HIP;
+  }
+  const mapdb::LbaLayout L(nk + (size_t)nFixed, (size_t)nP, (size_t)nEdges);
+  if ((rc = h->lbaDev.ensure(L.devBytes)) || (rc = h->lbaHost.ensure(L.bytes))) return rc;
+  Mem& d = h->lbaDev;
+  a.outPoseFixed = at<uint8_t>(d, L.oPoseFixed); a.outPoseKf = at<int>(d, L.oPoseKf); a.outPointSlot = at<int>(d, L.oPointSlot);
+  a.outStatus = at<uint8_t>(d, L.oStatus); a.outPoints = at<double>(d, L.oPoints);
+  a.outEdgePose = at<int>(d, L.oEdgePose); a.outEdgePoint = at<int>(d, L.oEdgePoint); a.outEdgeKf = at<int>(d, L.oEdgeKf); a.outEdgeIdx = at<int>(d, L.oEdgeIdx);
+  a.outMeas = at<double>(d, L.oMeas); a.outInfo = at<double>(d, L.oInfo);
+  HIPCHK(stampEvent(3));
+  hipLaunchKernelGGL(mapdb::k_lba_fixed, blocks(std::max((size_t)nP, nk)), threads, 0, s, a);
+  HIPCHK(hipGetLastError());
+  st.last_launches = 8;
+  if (nP > 0) {
+    hipLaunchKernelGGL(mapdb::k_lba_edges, blocks((size_t)nP), threads, 0, s, a);
+    HIPCHK(hipGetLastError());
+    st.last_launches++;
+  }
+  hipLaunchKernelGGL(mapdb::k_lba_reset, blocks((size_t)a.nKfAll), threads, 0, s, a.nKfAll, h->lbaPoseOf, h->lbaFirst);
+  HIPCHK(hipGetLastError());
+  st.last_launches++;
+  HIPCHK(stampEvent(4));
+  HIPCHK(hipMemcpyAsync(h->lbaHost.p, d.p, L.devBytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(stampEvent(5));
+  HIPCHK(hipStreamSynchronize(s));
+  h->lbaDirty = false;
+  if (timed) {
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    HIPCHK(hipEventElapsedTime(&ms[0], h->lbaEvent[0], h->lbaEvent[1]));
+    HIPCHK(hipEventElapsedTime(&ms[1], h->lbaEvent[1], h->lbaEvent[2]));
+    HIPCHK(hipEventElapsedTime(&ms[2], h->lbaEvent[3], h->lbaEvent[4]));
+    HIPCHK(hipEventElapsedTime(&ms[3], h->lbaEvent[4], h->lbaEvent[5]));
+    st.last_ms_points = ms[0]; st.last_ms_walk = ms[1]; st.last_ms_emit = ms[2]; st.last_ms_copy = ms[3];
+  }
+  std::memset(h->lbaHost.as<uint8_t>() + L.oPoses, 0, L.bytes - L.oPoses);
+  mapdb::lbaPointResult(L, h->lbaHost.as<uint8_t>(), n_kf, nFixed, nP, nEdges, out);
+  st.last_syncs = 2; st.last_download_bytes = 16 + (int64_t)L.devBytes;
+  st.last_n_fixed = nFixed; st.last_n_points = nP; st.last_n_edges = nEdges;
+  h->lbaStats = st;
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_lba_stats(ydorb_mapdb_t* h, YdMapDbLbaStats* stats) {
+  if (!h || !stats) return invalid("null handle or stats");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  *stats = h->lbaStats;
+  return YDORB_OK;
+}
+
+extern "C" int ydorb_mapdb_lba_set_profiling(ydorb_mapdb_t* h, int32_t on) {
+  if (!h) return invalid("null handle");
+  std::lock_guard<std::mutex> lock(h->c.mu);
+  if (on) {
+    HIPCHK(hipSetDevice(h->device));
+    for (hipEvent_t& e : h->lbaEvent) if (!e) HIPCHK(hipEventCreate(&e));
+  }
+  h->lbaProfiling = on != 0;
+  return YDORB_OK;
 }
 
 // ------------------------------------------------------------------------------------------- point views and descriptor blocks

@@ -16,8 +16,8 @@ import numpy as np
 
 from . import map_maintenance as M
 from .extractor import KP_DTYPE
-from ._lib import (YdCreateNeighbour, YdCreateView, YdFuseTarget, YdMapCorrection, YdMapDbAttrStats, YdMapDbBowStats, YdMapDbDescStats,
-                   YdMapDbFeatStats, YdMapDbRowStats, YdMapDbStats, check, lib)
+from ._lib import (YdCreateNeighbour, YdCreateView, YdFuseTarget, YdLocalBaGraph, YdMapCorrection, YdMapDbAttrStats, YdMapDbBowStats,
+                   YdMapDbDescStats, YdMapDbFeatStats, YdMapDbLbaStats, YdMapDbRowStats, YdMapDbStats, check, lib)
 
 _p = M._p
 
@@ -203,6 +203,40 @@ class MapDb:
         take = [int(counts[q]) if status[q] == 0 else 0 for q in range(nl)]
         return dict(kf=[kf[os_[q]:os_[q] + take[q]] for q in range(nl)], weight=[w[os_[q]:os_[q] + take[q]] for q in range(nl)],
                     counts=counts[:nl], status=status[:nl], point_bad=[pbad[ls[q]:ls[q + 1]] for q in range(nl)], raw_kf=kf, raw_weight=w)
+
+    # ------------------------------------------------------------------------------------------------------------ local BA graph
+    def local_ba_graph(self, kf_slots, inv_level_sigma2):
+        """ydorb_mapdb_local_ba_graph: the flat graph of localBundleAdjust for the local keyframes kf_slots, assembled
+        on the device.  inv_level_sigma2 [8].  Returns numpy arrays copied out of the handle's memory: dict(n_local, n_fixed, pose_kf,
+        pose_fixed [n_poses], point_slot, point_status [n_points], points [n_points, 3] float64, edge_pose, edge_point, edge_kf, edge_idx
+        [n_edges], edge_meas [n_edges, 3], edge_inv_sigma2 [n_edges])."""
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        sig = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+        assert len(sig) == 8
+        g = YdLocalBaGraph()
+        check(lib().ydorb_mapdb_local_ba_graph(self._h, _p(kf_slots), len(kf_slots), _p(sig), C.byref(g)))
+        P = g.problem
+
+        def take(ptr, dtype, *shape):
+            n = int(np.prod(shape))
+            if n == 0:
+                return np.zeros(shape, dtype)
+            return np.frombuffer(C.string_at(ptr, n * np.dtype(dtype).itemsize), dtype).reshape(shape).copy()
+        return dict(n_local=g.n_local, n_fixed=g.n_fixed, pose_kf=take(g.pose_kf, np.int32, P.n_poses), pose_fixed=take(P.pose_fixed, np.uint8, P.n_poses),
+                    point_slot=take(g.point_slot, np.int32, P.n_points), point_status=take(g.point_status, np.uint8, P.n_points),
+                    points=take(P.points, np.float64, P.n_points, 3), edge_pose=take(P.edge_pose, np.int32, P.n_edges),
+                    edge_point=take(P.edge_point, np.int32, P.n_edges), edge_kf=take(g.edge_kf, np.int32, P.n_edges),
+                    edge_idx=take(g.edge_idx, np.int32, P.n_edges), edge_meas=take(P.edge_meas, np.float64, P.n_edges, 3),
+                    edge_inv_sigma2=take(P.edge_inv_sigma2, np.float64, P.n_edges))
+
+    def lba_stats(self):
+        s = YdMapDbLbaStats()
+        check(lib().ydorb_mapdb_lba_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in YdMapDbLbaStats._fields_}
+
+    def lba_set_profiling(self, on=True):
+        """Event pairs round the phases of every later local_ba_graph call; lba_stats() then carries last_ms_*."""
+        check(lib().ydorb_mapdb_lba_set_profiling(self._h, int(bool(on))))
 
     # ------------------------------------------------------------------------------------------------------------ resident descriptors
     def reserve_descriptors(self, view_capacity, descriptor_capacity):
