@@ -1511,6 +1511,62 @@ int ydorb_mapdb_create_new_points(ydorb_mapdb_t* db, ydorb_matcher_t* m, const Y
                                   int32_t n_nb, int32_t stereo_only, int32_t check_orientation, int32_t* matched_second, float* x3d,
                                   uint8_t* status, int32_t* n_matches, int32_t* n_accepted, uint8_t* neighbour_status);
 
+/* The BoW searches over all candidate keyframes in one call (DESIGN.md section 2 "BoW searches on the resident table", section 6v), on
+ * the table as of the call: staged deltas are applied first, in the order ydorb_mapdb_create_new_points applies them.
+ * ydorb_mapdb_search_by_bow_keyframes is OrbMatcher::searchByBowInTwoKeyFrames(first, second_i) for every i < n_second
+ * (LoopClosing::computeSim3), ydorb_mapdb_search_by_bow_frame is OrbMatcher::searchByBowInKeyFrameAndFrame(kf_i, frame) for every
+ * i < n_kf (Tracking::relocalize; n_kf == 1: trackReferenceKeyFrame).  Each pair answers as ydorb_search_by_bow (mode 4 / mode 3) does
+ * on the keyframes' resident keypoints, descriptor blocks and feature vectors, with "has a good map point" decided on the device in
+ * place of `valid` for every resident side: the keyframe's row entry p is >= 0, below the point table's capacity, and the resident
+ * bad flag of p is clear (a slot never set reads as bad: the rule of YDORB_FUSE_BAD).  The frame keeps YdBowSide.valid as the flat
+ * call reads it, NULL = every feature.
+ * Outputs.  matched_second[i][idx1] (keyframes) / matched_kf_feature[i][idxF] (frame) = the flat call's out[] of pair i, -1 where
+ * there is no match.  matched_point = the point slot the reference's match vector would hold, i.e. the row entry of the second
+ * keyframe (keyframes) or of the keyframe (frame) at the matched feature, -1 with no match.  n_matches[i] = the reference's return
+ * value, histogram culls subtracted.  pair_status[i] = a YDORB_BOW_PAIR_*: an unusable keyframe searches nothing, its outputs are all
+ * -1 and its count 0, and the call still returns YDORB_OK; an unusable first keyframe gives every pair its status.
+ * The pairs are independent of each other: each has match flags of its own.  So, unlike ydorb_mapdb_create_new_points, whose
+ * neighbours claim features from each other, a keyframe may be named several times and a second keyframe may equal the first;
+ * repeats answer alike.
+ * Refused up front, before any device work, with the first offender named and nothing changed (no staged delta is applied, no
+ * counter moves): null arguments, negative counts, a slot outside 0..n_keyframes-1, n_first not equal to the first keyframe's
+ * resident feature count, features or BoW feature vectors not enabled (rows and descriptor blocks are not opt-in), db and m on
+ * different devices, a ratio that is not finite; for the frame: n outside 0..65535 (a candidate record packs its index in 16 bits),
+ * null kps / desc with n > 0, a malformed feature vector (node_start not starting at 0 or decreasing, node ids not strictly
+ * ascending, a feature index outside 0..n-1).  These return YDORB_ERR_INVALID_ARG.  More than 65535 pairs in one call (n_second or
+ * n_kf: the pairs are one dimension of the launch grid) are refused in the same way with YDORB_ERR_UNSUPPORTED.  n_second == 0 or
+ * n_kf == 0 launches nothing and synchronises nothing.
+ * The call is synchronous and exact: the candidate records start at 16384 per pair (the pool ydorb_mapdb_create_new_points uses, and
+ * the same counter); when they overflow, the pool grows to what the gather asked for and the whole call is replayed.  Four launches,
+ * one upload, one read-back and one synchronisation of the matcher's stream per attempt, whatever the number of pairs. */
+#define YDORB_BOW_PAIR_OK 0
+#define YDORB_BOW_PAIR_NO_FEATURES 1      /* the keyframe has no feature span */
+#define YDORB_BOW_PAIR_NO_BLOCK 2         /* ... no descriptor block */
+#define YDORB_BOW_PAIR_NO_BOW 3           /* ... no BoW feature vector */
+#define YDORB_BOW_PAIR_LENGTH_MISMATCH 4  /* features, descriptor block and row differ in length */
+#define YDORB_BOW_PAIR_BOW_INDEX 5        /* a feature index of the BoW feature vector is not below the feature count */
+/* second_kf_slots [n_second]; matched_second / matched_point [n_second][n_first]; n_matches / pair_status [n_second] */
+int ydorb_mapdb_search_by_bow_keyframes(ydorb_mapdb_t* db, ydorb_matcher_t* m, int32_t first_kf_slot, const int32_t* second_kf_slots,
+                                        int32_t n_second, float ratio, int32_t check_orientation, int32_t n_first,
+                                        int32_t* matched_second, int32_t* matched_point, int32_t* n_matches, uint8_t* pair_status);
+/* kf_slots [n_kf]; matched_kf_feature / matched_point [n_kf][frame->n]; n_matches / pair_status [n_kf] */
+int ydorb_mapdb_search_by_bow_frame(ydorb_mapdb_t* db, ydorb_matcher_t* m, const int32_t* kf_slots, int32_t n_kf, const YdBowSide* frame,
+                                    float ratio, int32_t check_orientation, int32_t* matched_kf_feature, int32_t* matched_point,
+                                    int32_t* n_matches, uint8_t* pair_status);
+/* What the two entries above did on this matcher.  launches counts kernel launches (the memsets that clear the outputs are not
+ * kernels of this library), a replay after an overflow adds its attempt to attempts, launches, synchronisations and bytes_down.  With
+ * profiling on (ydorb_matcher_set_profiling), ms [3] = average device ms per profiled call of the join and gather, of the resolve
+ * and of the emit; all zero otherwise. */
+typedef struct YdBowSearchStats {
+  int64_t calls, attempts;                /* since the matcher was created; calls that reached the device only */
+  int64_t launches, synchronisations;     /* of the last such call, over its attempts */
+  int64_t bytes_up, bytes_down;           /* of the last such call */
+  int64_t pool_per_pair;                  /* candidate records each pair's part of the pool holds now */
+  int32_t profiled_calls;
+  float ms[3];
+} YdBowSearchStats;
+int ydorb_matcher_bow_search_stats(ydorb_matcher_t* m, YdBowSearchStats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,9 @@
 // forget(kf) erases the span; createNewPoints is the search and the geometry of LocalMapping::createNewMapPoints for all neighbours in
 // ONE call (localMapping.hpp's overload over a mirror runs the bookkeeping on its result); verifyBow() is verify() for them.  It needs
 // enableFeatures() and the descriptor blocks too.  Assumed spelling beyond the others: KeyFrame m_bow_keyPointsVec (DBoW3::FeatureVector).
+// searchByBowKeyFrames / searchByBowFrame are OrbMatcher::searchByBowInTwoKeyFrames / searchByBowInKeyFrameAndFrame for all candidate
+// keyframes of a loop or relocalisation round in ONE call each (orbMatcher.hpp's overloads over a mirror build
+// the frame's side and hand the match vectors on).  They need enableDescriptors(), enableFeatures() and enableBow() and no new touch.
 // localBaGraph(localKeyFrames) is the flat graph of Optimizer::localBundleAdjust assembled on the table in ONE call (DESIGN.md section
 // 6u; optimizer.hpp's overload over a mirror fills the poses, solves and runs the write-back with its touches).  It needs
 // enableDescriptors() and enableFeatures().  Assumed spelling beyond the others: KeyFrame m_v_invScaleFactorSquares.
@@ -428,6 +431,48 @@ class MapMirror {
                                            r.neighbourStatus.data()));
     r.nMatches.resize(nn); r.nAccepted.resize(nn); r.neighbourStatus.resize(nn);
     return r;
+  }
+
+  // OrbMatcher::searchByBowInTwoKeyFrames(kf1, kf2s[i]) for all candidates of a loop round in one call
+  // (ydorb_mapdb_search_by_bow_keyframes), and searchByBowInKeyFrameAndFrame(kfs[i], frame) for all candidates of a relocalisation in
+  // one call (ydorb_mapdb_search_by_bow_frame; one keyframe: trackReferenceKeyFrame).  A keyframe the table holds no row, features,
+  // block or feature vector of is read now, as in createNewPoints.  Flushes, makes the call.  matched[i] is the vector the reference
+  // fills for candidate i: per feature of kf1 (keyframes) or of the frame (frame) the matched map point or null; nMatches[i] the
+  // reference's return value.  "Has a good map point" is the table's: touch(mp) after setBadFlag(), touchRow / touchEntry after a row
+  // changes.  The candidates are independent of each other: one may be named twice, and kf1 may be among them.
+  struct BowSearchResult {
+    std::vector<std::vector<MapPointPtr>> matched;
+    std::vector<int> nMatches;
+    std::vector<uint8_t> pairStatus;   // YDORB_BOW_PAIR_*: a candidate with a non-zero status was not searched
+  };
+  BowSearchResult searchByBowKeyFrames(ydorb_matcher_t* matcher, const KeyFramePtr& kf1, const std::vector<KeyFramePtr>& kf2s, float ratio, bool checkOrientation) {
+    if (!features_ || !bow_ || !descriptors_) throw std::runtime_error("ydorb: searchByBowKeyFrames without enableDescriptors(), enableFeatures() and enableBow()");
+    const int32_t first = bindForBow(kf1);
+    std::vector<int32_t> second;
+    for (const KeyFramePtr& kf : kf2s) second.push_back(bindForBow(kf));
+    flush();
+    // n_first is the table's count: a bad kf1 holds no features after the flush (computeSim3 never passes one), so every candidate
+    // answers with YDORB_BOW_PAIR_NO_FEATURES and an all-null vector of kf1's length, as a bad candidate does, instead of a refusal
+    const size_t np = kf2s.size(), full = kf1->m_v_keyPoints.size(), n = featSent_[first] ? full : 0;
+    std::vector<int32_t> feature(np * n + 1, -1), point(np * n + 1, -1), count(np + 1, 0);
+    std::vector<uint8_t> status(np + 1, 0);
+    second.push_back(0);
+    mapCheck(ydorb_mapdb_search_by_bow_keyframes(db_, matcher, first, second.data(), (int32_t)np, ratio, checkOrientation ? 1 : 0, (int32_t)n, feature.data(),
+                                                 point.data(), count.data(), status.data()));
+    return bowResult(np, n, full, point, count, status);
+  }
+  BowSearchResult searchByBowFrame(ydorb_matcher_t* matcher, const std::vector<KeyFramePtr>& kfs, const YdBowSide& frame, float ratio, bool checkOrientation) {
+    if (!features_ || !bow_ || !descriptors_) throw std::runtime_error("ydorb: searchByBowFrame without enableDescriptors(), enableFeatures() and enableBow()");
+    std::vector<int32_t> slots;
+    for (const KeyFramePtr& kf : kfs) slots.push_back(bindForBow(kf));
+    flush();
+    const size_t np = kfs.size(), n = (size_t)(frame.n > 0 ? frame.n : 0);
+    std::vector<int32_t> feature(np * n + 1, -1), point(np * n + 1, -1), count(np + 1, 0);
+    std::vector<uint8_t> status(np + 1, 0);
+    slots.push_back(0);
+    mapCheck(ydorb_mapdb_search_by_bow_frame(db_, matcher, slots.data(), (int32_t)np, &frame, ratio, checkOrientation ? 1 : 0, feature.data(), point.data(), count.data(),
+                                             status.data()));
+    return bowResult(np, n, n, point, count, status);
   }
 
   // Flushes and compares every known keyframe's m_bow_keyPointsVec with the device's feature vectors (ydorb_mapdb_export_bow): the
@@ -1041,6 +1086,29 @@ class MapMirror {
     kfSlot_[kf] = s;
     mark(kfDirty_, dirtyKfs_, s, kFull);
     return s;
+  }
+  // the slot of a keyframe a BoW search names; what the table does not hold of it yet is read at the flush that follows
+  int32_t bindForBow(const KeyFramePtr& kf) {
+    const int32_t k = kfSlotFor(kf);
+    if (!rowSent_[k]) markRow(k);
+    if (!featSent_[k]) mark(featDirty_, dirtyFeats_, k, kFull);
+    if (!descSent_[k]) mark(descDirty_, dirtyDescs_, k, kFull);
+    if (!bowSent_[k]) mark(bowDirty_, dirtyBows_, k, kFull);
+    return k;
+  }
+  // point slots [np][n] -> the map points, in vectors of `length` >= n entries; the table's slots are the mirror's
+  BowSearchResult bowResult(size_t np, size_t n, size_t length, const std::vector<int32_t>& point, const std::vector<int32_t>& count,
+                            const std::vector<uint8_t>& status) const {
+    BowSearchResult r;
+    r.matched.assign(np, std::vector<MapPointPtr>(length));
+    for (size_t i = 0; i < np; i++)
+      for (size_t j = 0; j < n; j++) {
+        const int32_t s = point[i * n + j];
+        if (s >= 0 && (size_t)s < pointOf_.size()) r.matched[i][j] = pointOf_[(size_t)s];
+      }
+    r.nMatches.assign(count.begin(), count.begin() + (long)np);
+    r.pairStatus.assign(status.begin(), status.begin() + (long)np);
+    return r;
   }
   // the slot of a point a query names; one the mirror has never been told of is read now (its observation map is walked this once)
   int32_t known(const MapPointPtr& mp) {

@@ -248,6 +248,33 @@ int searchByBowInTwoKeyFrames(ydorb_matcher_t* m, KeyFramePtr kf1, KeyFramePtr k
   return n;
 }
 
+// searchByBowInTwoKeyFrames(kf1, kf2s[i]) for every candidate of a LoopClosing::computeSim3 round in one call over a resident map
+// table (mapMirror.hpp, searchByBowKeyFrames): matched[i] is the vector the flat overload fills for kf2s[i], the
+// return value holds the flat overload's counts.  The candidates are independent of each other.  A candidate the table cannot search
+// (MapMirror::BowSearchResult::pairStatus) has an all-null vector and count 0, which computeSim3 discards like any candidate below
+// its match threshold.
+template <class Mirror, class KeyFramePtr, class MapPointPtr>
+std::vector<int> searchByBowInTwoKeyFrames(Mirror& mirror, ydorb_matcher_t* m, KeyFramePtr kf1, const std::vector<KeyFramePtr>& kf2s,
+                                           std::vector<std::vector<MapPointPtr>>& matched, float ratio, bool checkOri) {
+  auto r = mirror.searchByBowKeyFrames(m, kf1, kf2s, ratio, checkOri);
+  matched = std::move(r.matched);
+  return r.nMatches;
+}
+
+// searchByBowInKeyFrameAndFrame(kfs[i], frame) for every candidate of a Tracking::relocalize round in one call over a resident map
+// table (searchByBowFrame): matched[i] is the vector the flat overload fills for kfs[i].  The frame travels as in the flat overload,
+// keypoints, descriptors and feature vector, once for all candidates; every frame feature is a candidate (valid == NULL).
+template <class Mirror, class KeyFramePtr, class FrameT, class MapPointPtr>
+std::vector<int> searchByBowInKeyFrameAndFrame(Mirror& mirror, ydorb_matcher_t* m, const std::vector<KeyFramePtr>& kfs, FrameT& frame,
+                                               std::vector<std::vector<MapPointPtr>>& matched, float ratio, bool checkOri) {
+  BowCsr<decltype(frame.m_bow_keyPointsVec)> b(frame.m_bow_keyPointsVec);
+  const YdBowSide B{reinterpret_cast<const YdKeyPoint*>(frame.m_v_keyPoints.data()), frame.m_cvMat_descriptors.template ptr<uint8_t>(), nullptr,
+                    (int32_t)frame.m_v_keyPoints.size(), b.c()};
+  auto r = mirror.searchByBowFrame(m, kfs, B, ratio, checkOri);
+  matched = std::move(r.matched);
+  return r.nMatches;
+}
+
 // fuseByProjection, src/orbMatcher.cpp:682-745.  Pass 1 (host, the reference's own float cv::Mat arithmetic): projection, predicted
 // level and the predicates of :688 / :704-708 for every map point.  Pass 2 (GPU): the window search with the level and chi-square tests.
 // Pass 3 (host, list order): the replace / add bookkeeping of :726-737 on the search results.  A replacement can make a LATER list entry

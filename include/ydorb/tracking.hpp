@@ -293,6 +293,21 @@ inline std::vector<uint8_t> updateLocalPointsImpl(Mirror& mirror, FrameT& frame,
   return seen;
 }
 
+// The search of Tracking::trackReferenceKeyFrame over a resident map table: searchByBowInKeyFrameAndFrame(refKF, frame) as the
+// one-keyframe case of orbMatcher.hpp's batched overload.  Optional: with one keyframe there is no round trip to save, only the
+// keyframe's side of the upload (DESIGN.md section 6v has what was measured); Tracking::relocalize, which names every candidate in one
+// call, is where the batched form pays.
+//   int nmatches = ydorb::adapter::trackReferenceKeyFrameSearchImpl(mirror, ydorb::adapter::matcher(), m_frame_currentFrame,
+//                                                                   m_sptr_referenceKeyFrame, vpMapPointMatches);   // ratio 0.7, orientation check on
+template <class Mirror, class FrameT, class KeyFramePtr, class MapPointPtr>
+inline int trackReferenceKeyFrameSearchImpl(Mirror& mirror, ydorb_matcher_t* m, FrameT& frame, const KeyFramePtr& referenceKeyFrame,
+                                            std::vector<MapPointPtr>& matched, float ratio = 0.7f, bool checkOrientation = true) {
+  std::vector<std::vector<MapPointPtr>> all;
+  const std::vector<int> n = searchByBowInKeyFrameAndFrame(mirror, m, std::vector<KeyFramePtr>{referenceKeyFrame}, frame, all, ratio, checkOrientation);
+  matched = std::move(all[0]);
+  return n[0];
+}
+
 }  // namespace adapter
 }  // namespace ydorb
 #endif

@@ -169,6 +169,9 @@ SYMBOLS = {
     "ydorb_mapdb_bow_stats": (C.c_int, [_VP, _VP]),
     "ydorb_mapdb_create_new_points": (C.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ydorb_matcher_create_points_times": (C.c_int, [_VP, _VP, C.POINTER(_I)]),
+    "ydorb_mapdb_search_by_bow_keyframes": (C.c_int, [_VP, _VP, _I, _VP, _I, C.c_float, _I, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_mapdb_search_by_bow_frame": (C.c_int, [_VP, _VP, _VP, _I, _VP, C.c_float, _I, _VP, _VP, _VP, _VP]),
+    "ydorb_matcher_bow_search_stats": (C.c_int, [_VP, _VP]),
 }
 
 BA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -294,6 +297,11 @@ class YdMapDbLbaStats(C.Structure):
 class YdLocalBaGraph(C.Structure):
     _fields_ = [("problem", YdBaProblem), ("n_local", _I), ("n_fixed", _I), ("pose_kf", _VP), ("point_slot", _VP), ("edge_kf", _VP),
                 ("edge_idx", _VP), ("point_status", _VP)]
+
+
+class YdBowSearchStats(C.Structure):
+    _fields_ = [("calls", C.c_int64), ("attempts", C.c_int64), ("launches", C.c_int64), ("synchronisations", C.c_int64), ("bytes_up", C.c_int64),
+                ("bytes_down", C.c_int64), ("pool_per_pair", C.c_int64), ("profiled_calls", _I), ("ms", C.c_float * 3)]
 
 
 class YdCreateView(C.Structure):

@@ -1468,6 +1468,32 @@ int ydorb::mapdb::lockResidentFuse(ydorb_mapdb_t* h, int32_t device, const int32
   return YDORB_OK;
 }
 
+// Where the device holds the four spans of keyframe k after a sync, from the host mirrors, and whether a BoW-guided search can use the
+// keyframe on its own: a YDORB_CREATE_NB_* / YDORB_BOW_PAIR_* value (0 = usable).  nExtra >= 0: one more length that must equal the
+// feature count (createNewPoints' depth array).  Both locks below apply this rule and no other.
+static uint8_t residentKeyframeSpans(const ydorb_mapdb* h, int32_t k, int32_t nExtra, ydorb::mapdb::ResidentTriSpans& S) {
+  S.featStart = h->feat.feats.offOf(k); S.n = h->feat.feats.lenOf(k);
+  S.blockStart = h->desc.blocks.offOf(k); S.rowStart = h->rows.offOf(k);
+  S.bowStart = h->bow.spans.offOf(k); S.bowLen = h->bow.spans.lenOf(k);
+  if (S.n == 0) return YDORB_CREATE_NB_NO_FEATURES;
+  if (h->desc.blocks.lenOf(k) == 0) return YDORB_CREATE_NB_NO_BLOCK;
+  if (S.bowLen == 0) return YDORB_CREATE_NB_NO_BOW;
+  if (h->desc.blocks.lenOf(k) != S.n || h->rows.lenOf(k) != S.n || (nExtra >= 0 && nExtra != S.n)) return YDORB_CREATE_NB_LENGTH_MISMATCH;
+  for (const ydorb::mapdb::BowRec& r : h->bow.spans.rowOf(k))
+    if (r.feat >= S.n) return YDORB_CREATE_NB_BOW_INDEX;
+  return YDORB_CREATE_NB_OK;
+}
+static_assert(YDORB_BOW_PAIR_OK == YDORB_CREATE_NB_OK && YDORB_BOW_PAIR_NO_FEATURES == YDORB_CREATE_NB_NO_FEATURES && YDORB_BOW_PAIR_NO_BLOCK == YDORB_CREATE_NB_NO_BLOCK &&
+                  YDORB_BOW_PAIR_NO_BOW == YDORB_CREATE_NB_NO_BOW && YDORB_BOW_PAIR_LENGTH_MISMATCH == YDORB_CREATE_NB_LENGTH_MISMATCH &&
+                  YDORB_BOW_PAIR_BOW_INDEX == YDORB_CREATE_NB_BOW_INDEX,
+              "one usability rule, one set of values");
+
+static void residentTriPoolsOf(const ydorb_mapdb* h, ydorb::mapdb::ResidentTriPools& pools) {
+  pools.rowPool = h->dRows.pool; pools.bowPool = reinterpret_cast<const int32_t*>(h->dBow.pool);
+  pools.kps = h->dFeats.pool; pools.rightX = reinterpret_cast<const float*>(featRightX(h->dFeats.pool, h->feat.feats.poolCap()));
+  pools.blockPool = reinterpret_cast<const uint8_t*>(h->dBlocks.pool);
+}
+
 // What ydorb_mapdb_create_new_points (orb_matcher.hip) reads
 int ydorb::mapdb::lockResidentTri(ydorb_mapdb_t* h, int32_t device, const int32_t* kfSlots, const int32_t* nDepth, int32_t nNb, ResidentTriPools& pools,
                                   ResidentTriSpans* spans, uint8_t* status) {
@@ -1489,25 +1515,37 @@ int ydorb::mapdb::lockResidentTri(ydorb_mapdb_t* h, int32_t device, const int32_
     int rc = sync(h);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->c.stream));   // the deltas and any write-through still queued: the reader runs on another stream
-    for (int32_t i = 0; i <= nNb; i++) {         // nothing is staged now: the mirrors say where the device holds each span
-      const int32_t k = kfSlots[i];
-      ResidentTriSpans& S = spans[i];
-      S.featStart = h->feat.feats.offOf(k); S.n = h->feat.feats.lenOf(k);
-      S.blockStart = h->desc.blocks.offOf(k); S.rowStart = h->rows.offOf(k);
-      S.bowStart = h->bow.spans.offOf(k); S.bowLen = h->bow.spans.lenOf(k);
-      status[i] = YDORB_CREATE_NB_OK;
-      if (S.n == 0) status[i] = YDORB_CREATE_NB_NO_FEATURES;
-      else if (h->desc.blocks.lenOf(k) == 0) status[i] = YDORB_CREATE_NB_NO_BLOCK;
-      else if (S.bowLen == 0) status[i] = YDORB_CREATE_NB_NO_BOW;
-      else if (h->desc.blocks.lenOf(k) != S.n || h->rows.lenOf(k) != S.n || nDepth[i] != S.n) status[i] = YDORB_CREATE_NB_LENGTH_MISMATCH;
-      else
-        for (const BowRec& r : h->bow.spans.rowOf(k))
-          if (r.feat >= S.n) { status[i] = YDORB_CREATE_NB_BOW_INDEX; break; }
-    }
+    for (int32_t i = 0; i <= nNb; i++)           // nothing is staged now: the mirrors say where the device holds each span
+      status[i] = residentKeyframeSpans(h, kfSlots[i], nDepth[i], spans[i]);
   }
-  pools.rowPool = h->dRows.pool; pools.bowPool = reinterpret_cast<const int32_t*>(h->dBow.pool);
-  pools.kps = h->dFeats.pool; pools.rightX = reinterpret_cast<const float*>(featRightX(h->dFeats.pool, h->feat.feats.poolCap()));
-  pools.blockPool = reinterpret_cast<const uint8_t*>(h->dBlocks.pool);
+  residentTriPoolsOf(h, pools);
+  lock.release();   // held until unlockResident
+  return YDORB_OK;
+}
+
+// What ydorb_mapdb_search_by_bow_keyframes / _frame (orb_matcher.hip) read.  Descriptor blocks and rows are not opt-in, so only features
+// and BoW feature vectors can be "not enabled".
+int ydorb::mapdb::lockResidentBow(ydorb_mapdb_t* h, int32_t device, const int32_t* kfSlots, int32_t nKf, int32_t nSearched, int32_t nFirst, ResidentBowPools& pools,
+                                  ResidentTriSpans* spans, uint8_t* status) {
+  std::unique_lock<std::mutex> lock(h->c.mu);
+  std::string err;
+  if (!FeatHost::checkEnabled(h->feat.enabled(), err) || !BowHost::checkEnabled(h->bow.enabled(), err)) return invalid(err);
+  for (int32_t i = 0; i < nKf; i++)
+    if (kfSlots[i] < 0 || kfSlots[i] >= h->host.nKeyframes())
+      return invalid((nFirst < 0 ? "kf_slots[" + std::to_string(i) + "]" : i == 0 ? std::string("first_kf_slot") : "second_kf_slots[" + std::to_string(i - 1) + "]") +
+                     ": keyframe slot " + std::to_string(kfSlots[i]) + " outside 0.." + std::to_string((long long)h->host.nKeyframes() - 1));
+  if (device != h->device) return invalid("the map table lives on device " + std::to_string(h->device) + ", the matcher on device " + std::to_string(device));
+  if (nFirst >= 0 && nFirst != h->feat.feats.lenOf(kfSlots[0]))
+    return invalid("the first keyframe has " + std::to_string(h->feat.feats.lenOf(kfSlots[0])) + " resident features, n_first is " + std::to_string(nFirst));
+  if (nSearched > 0) {   // no candidate reads nothing: nothing is applied or launched for it
+    HIPCHK(hipSetDevice(h->device));
+    int rc = sync(h);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->c.stream));   // the deltas and any write-through still queued: the reader runs on another stream
+    for (int32_t i = 0; i < nKf; i++) status[i] = residentKeyframeSpans(h, kfSlots[i], -1, spans[i]);
+  }
+  residentTriPoolsOf(h, pools.tri);
+  pools.bad = h->T.bad; pools.pointCap = h->host.pointCap();
   lock.release();   // held until unlockResident
   return YDORB_OK;
 }

@@ -65,6 +65,21 @@ struct ResidentTriSpans { int32_t featStart, n, blockStart, rowStart, bowStart, 
 int lockResidentTri(ydorb_mapdb_t* db, int32_t device, const int32_t* kfSlots, const int32_t* nDepth, int32_t nNb, ResidentTriPools& pools,
                     ResidentTriSpans* spans, uint8_t* status);
 
+// What the batched BoW searches read: createNewPoints' pools and, for "has a good map point", the point table's bad flags
+// [pointCap] (1 for a slot never set).
+struct ResidentBowPools {
+  ResidentTriPools tri;
+  const uint8_t* bad = nullptr;
+  int32_t pointCap = 0;
+};
+
+// lockResident for the BoW searches: refuses features or BoW not enabled, another device, a keyframe slot outside 0..n_keyframes-1 and,
+// with nFirst >= 0, nFirst != the resident feature count of kfSlots[0].  kfSlots / spans / status [nKf]; status[i] is a
+// YDORB_BOW_PAIR_* of keyframe i on its own, by the rule lockResidentTri applies (0 = usable).  A slot may repeat.  nSearched = the
+// number of candidates: with 0 nothing is synced and nothing is written.
+int lockResidentBow(ydorb_mapdb_t* db, int32_t device, const int32_t* kfSlots, int32_t nKf, int32_t nSearched, int32_t nFirst, ResidentBowPools& pools,
+                    ResidentTriSpans* spans, uint8_t* status);
+
 struct ResidentLock {   // unlocks on every way out of the reader
   ydorb_mapdb_t* db = nullptr;
   ~ResidentLock() { if (db) unlockResident(db); }

@@ -16,6 +16,8 @@
 #include "frustum_kernels.hip.h"
 #include "host_buffers.h"
 #include "map_table.h"
+#include "mapdb_bow_kernels.hip.h"
+#include "mapdb_bowsearch_host.h"
 #include "mapdb_frustum_kernels.hip.h"
 #include "mapdb_fuse_kernels.hip.h"
 #include "mapdb_resident_points.h"
@@ -161,6 +163,23 @@ size_t layTri(size_t upBytes, size_t downBytes, size_t nNb, size_t nq, void* bas
 
 enum { TS_SEARCH = 0, TS_RESOLVE, TS_GEOMETRY, TS_COUNT };   // ydorb_matcher_create_points_times
 
+// `call`, ydorb_mapdb_search_by_bow_keyframes / _frame: nqAll query slots over all pairs, nShared entries of the A-side arrays (the first
+// keyframe's span once, or one per query slot), nAssigned entries of k_resolve's result.  `up` is what one upload brings (the pair and
+// call records, the frame's feature vector, keypoints, descriptors and valid bytes), `down` what one read-back takes (the two dense
+// outputs, match counts, pool heads, the overflow word).
+struct BowBatchPtrs {
+  uint8_t *up, *down;
+  int2 *qRange, *qInfo; int *qFeat, *matchQ, *assigned; float* qAngle;
+};
+size_t layBowBatch(size_t upBytes, size_t downBytes, size_t nqAll, size_t nShared, size_t nAssigned, void* base, BowBatchPtrs& p) {
+  Carve a(base);
+  a.take(p.up, upBytes); a.take(p.down, downBytes);
+  a.take(p.qRange, nqAll); a.take(p.qInfo, nqAll); a.take(p.qFeat, nShared); a.take(p.qAngle, nShared); a.take(p.matchQ, nqAll); a.take(p.assigned, nAssigned);
+  return a.L.bytes;
+}
+
+enum { BS_SEARCH = 0, BS_RESOLVE, BS_EMIT, BS_COUNT };   // YdBowSearchStats::ms (ydorb_matcher_bow_search_stats)
+
 }  // namespace
 
 // Host-call and batched paths share no device state on a handle: a batched call may still be running on its caller's stream, and its
@@ -172,10 +191,13 @@ struct ydorb_matcher {
   Mem pool;              // the host calls' record pool: grows by poolRecords, not by a call's shape, and a replay after an overflow
   size_t poolRecords = 1u << 20;   // ... finds everything else where it was
   size_t fuseOvfPerCall = 1u << 14;   // ydorb_mapdb_fuse_search: the overflow region of each target's pool part, grown by a replay
-  size_t triPoolPerNb = 1u << 14;     // ydorb_mapdb_create_new_points: each neighbour's part of the pool, grown by a replay
+  size_t triPoolPerNb = 1u << 14;     // ydorb_mapdb_create_new_points and ydorb_mapdb_search_by_bow_*: each neighbour's or pair's part of the pool, grown by a replay
   std::vector<hipEvent_t> triEv;      // ... its per-launch events, made when a profiled call first needs them
   double triMs[TS_COUNT]{};
   int triCalls = 0;
+  hipEvent_t bowEv[BS_COUNT + 1]{};   // ydorb_mapdb_search_by_bow_*: made when a profiled call first needs them
+  double bowMs[BS_COUNT]{};
+  YdBowSearchStats bowStats{};
   Mem stereo;            // ydorb_stereo_matches (layStereo)
   PinnedMem hUp, hDown;  // ydorb_search_local_points: pinned staging of the map-point table, read-back of track rows + status bytes
   // What ydorb_match_pairs_device / ydorb_match_consecutive_device keep; nothing but them, synchronize and destroy touches it.
@@ -224,6 +246,7 @@ void ydorb_matcher_destroy(ydorb_matcher_t* m) {
   for (Mem* b : m->buffers()) b->release();
   for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : m->triEv) (void)hipEventDestroy(e);
+  for (auto& e : m->bowEv) if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(m->stream);
   delete m;
 }
@@ -911,6 +934,203 @@ int ydorb_matcher_create_points_times(ydorb_matcher_t* m, float* ms, int32_t* nC
   return YDORB_OK;
 }
 
+}  // extern "C"
+
+// The one body of ydorb_mapdb_search_by_bow_keyframes (mode 4) and ydorb_mapdb_search_by_bow_frame (mode 3) over a resident map table
+// (mapdb_bow_kernels.hip.h has the kernels and what each does).  The pairs are independent, so the join, the gather, the unchanged
+// k_resolve (one workgroup per pair) and the emit each run once over all of them: four launches, one upload, one read-back and one
+// synchronisation of the matcher's stream per attempt.  kfSlots: mode 4 the first keyframe at 0, then the nPairs second keyframes;
+// mode 3 the nPairs keyframes.  The arguments have passed the entries' own checks.  The table's mutex is held from its sync to the end
+// of the call, as in ydorb_mapdb_create_new_points; every return after the first launch, an error included, synchronises the
+// matcher's stream first.  A set overflow word grows every pair's part of the pool to what the heads asked for and replays the call.
+static int bowSearchResident(const char* who, ydorb_mapdb_t* db, ydorb_matcher_t* m, int mode, const int32_t* kfSlots, int32_t nPairs, int32_t nFirst,
+                             const YdBowSide* frame, float ratio, int32_t checkOri, int32_t* matched, int32_t* point, int32_t* nMatches, uint8_t* pairStatus) {
+  const size_t np = (size_t)nPairs, nKf = np + (mode == 4 ? 1 : 0), lead = mode == 4 ? 1 : 0;
+  mapdb::ResidentBowPools P;
+  std::vector<mapdb::ResidentTriSpans> spans(nKf);
+  std::vector<uint8_t> kfStatus(nKf, 0);
+  mapdb::ResidentLock lock;
+  int rc;
+  if ((rc = mapdb::lockResidentBow(db, m->device, kfSlots, (int32_t)nKf, nPairs, nFirst, P, spans.data(), kfStatus.data()))) return rc;
+  lock.db = db;
+  if (nPairs == 0) return YDORB_OK;
+  const size_t nOut = (size_t)(mode == 4 ? nFirst : frame->n);
+  int writer = -1;
+  for (size_t i = 0; i < np; i++) {
+    pairStatus[i] = (mode == 4 && kfStatus[0]) ? kfStatus[0] : kfStatus[i + lead];
+    nMatches[i] = 0;
+    if (!pairStatus[i] && writer < 0) writer = (int)i;
+  }
+  for (size_t o = 0; o < np * nOut; o++) { matched[o] = -1; point[o] = -1; }
+  if (writer < 0 || nOut == 0) return YDORB_OK;
+  static_assert(sizeof(mapdbbow::Spans) == sizeof(mapdb::ResidentTriSpans), "one layout");
+  static_assert(sizeof(mapdb::BowRec) == sizeof(int2), "the frame's feature vector goes up as the resident ones lie");
+  // where each pair's queries begin, the grid's extents and the largest B side
+  std::vector<int32_t> qStart(np + 1, 0);
+  size_t nq = 0, maxQ = 0, maxB = 0;
+  if (mode == 4) {
+    nq = (size_t)spans[0].bowLen;
+    if (nq * np > (size_t)INT32_MAX) { set_error("%s: %zu queries, past INT32_MAX", who, nq * np); return YDORB_ERR_CAPACITY; }
+    for (size_t i = 0; i <= np; i++) qStart[i] = (int32_t)(i * nq);
+    maxQ = nq;
+    for (size_t i = 0; i < np; i++) if (!pairStatus[i]) maxB = std::max(maxB, (size_t)spans[i + 1].n);
+  } else {
+    std::vector<int32_t> len(np);
+    for (size_t i = 0; i < np; i++) { len[i] = spans[i].bowLen; if (!pairStatus[i]) maxQ = std::max(maxQ, (size_t)len[i]); }
+    if (!mapdb::bowQueryStarts(len.data(), pairStatus, nPairs, qStart)) { set_error("%s: the keyframes' BoW spans hold more than INT32_MAX entries", who); return YDORB_ERR_CAPACITY; }
+    maxB = nOut;
+    if (np * nOut > (size_t)INT32_MAX) { set_error("%s: %zu output elements, past INT32_MAX", who, np * nOut); return YDORB_ERR_CAPACITY; }
+  }
+  const size_t nqAll = (size_t)qStart[np], nShared = mode == 4 ? nq : nqAll, nAssigned = mode == 4 ? nqAll : np * nOut;
+  maxB = std::min<size_t>(maxB, 65535);   // a feature index of a BoW span lies below 65535 (mapdb_bow_host.h, checkBowFrame)
+  std::vector<mapdb::BowRec> frameBow;
+  if (mode == 3) mapdb::flattenFrameBow(frame->fv, frameBow);
+  const size_t nfb = frameBow.size(), nf = mode == 3 ? (size_t)frame->n : 0;
+  HIPCHK(hipSetDevice(m->device));
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};   // before the mutex goes: see ydorb_mapdb_search_local_points
+  Layout U;
+  const size_t oPairs = U.add(sizeof(mapdbbow::PairDev) * np), oCalls = U.add(sizeof(CallDev) * np), oBow = U.add(sizeof(int2) * nfb),
+               oKps = U.add(sizeof(YdKeyPoint) * nf), oDesc = U.add(32 * nf), oValid = U.add(mode == 3 && frame->valid ? nf : 0);
+  Layout D;
+  const size_t dMatched = D.add(4 * np * nOut), dPoint = D.add(4 * np * nOut), dCount = D.add(4 * np), dHeads = D.add(4 * np), dOvf = D.add(16);
+  BowBatchPtrs p;
+  if ((rc = m->hUp.ensure(U.bytes)) || (rc = m->hDown.ensure(D.bytes))) return rc;
+  if ((rc = layOut(m->call, [&](void* base) { return layBowBatch(U.bytes, D.bytes, nqAll, nShared, nAssigned, base, p); }))) return rc;
+  mapdbbow::PairDev* hp = at<mapdbbow::PairDev>(m->hUp, oPairs);
+  CallDev* hc = at<CallDev>(m->hUp, oCalls);
+  std::memset(hp, 0, sizeof(mapdbbow::PairDev) * np);
+  std::memset(hc, 0, sizeof(CallDev) * np);
+  if (mode == 3) {
+    if (nfb) std::memcpy(at<void>(m->hUp, oBow), frameBow.data(), sizeof(int2) * nfb);
+    std::memcpy(at<void>(m->hUp, oKps), frame->kps, sizeof(YdKeyPoint) * nf);
+    std::memcpy(at<void>(m->hUp, oDesc), frame->desc, 32 * nf);
+    if (frame->valid) std::memcpy(at<void>(m->hUp, oValid), frame->valid, nf);
+  }
+  const KeyPointDev* kps = reinterpret_cast<const KeyPointDev*>(P.tri.kps);
+  for (size_t i = 0; i < np; i++) {
+    mapdbbow::PairDev& N = hp[i];
+    std::memcpy(&N.kf, &spans[i + lead], sizeof(mapdbbow::Spans));
+    N.usable = pairStatus[i] == YDORB_BOW_PAIR_OK; N.qStart = qStart[i];
+    CallDev& C = hc[i];   // no frame, query rows or taken flags, as in the flat search
+    C.tkps = mode == 4 ? kps + N.kf.featStart : reinterpret_cast<const KeyPointDev*>(p.up + oKps);
+    C.qAngle = p.qAngle + (mode == 4 ? 0 : qStart[i]);
+    C.nq = !N.usable ? 0 : mode == 4 ? (int)nq : N.kf.bowLen;
+    C.qInfo = p.qInfo + qStart[i]; C.matchQ = p.matchQ + qStart[i];
+    C.assigned = p.assigned + (mode == 4 ? (size_t)qStart[i] : i * nOut);
+    C.count = reinterpret_cast<int*>(p.down + dCount) + i;
+    C.mode = mode; C.ratio = ratio; C.checkOri = checkOri;
+  }
+  hipStream_t s = m->stream;
+  HIPCHK(hipMemcpyAsync(p.up, m->hUp.p, U.bytes, hipMemcpyHostToDevice, s));
+  mapdbbow::SearchArgs sa{};
+  sa.R.rowPool = P.tri.rowPool; sa.R.bowPool = reinterpret_cast<const int2*>(P.tri.bowPool); sa.R.kps = kps; sa.R.blockPool = P.tri.blockPool;
+  sa.R.bad = P.bad; sa.R.pointCap = P.pointCap;
+  sa.mode = mode; sa.nq = (int)maxQ; sa.nOut = (int)nOut; sa.writer = writer;
+  if (mode == 4) std::memcpy(&sa.first, &spans[0], sizeof(mapdbbow::Spans));
+  sa.pairs = reinterpret_cast<const mapdbbow::PairDev*>(p.up + oPairs);
+  if (mode == 3) {
+    sa.frameBow = reinterpret_cast<const int2*>(p.up + oBow); sa.frameBowLen = (int)nfb;
+    sa.frameDesc = p.up + oDesc; sa.frameValid = frame->valid ? p.up + oValid : nullptr;
+  }
+  sa.qRange = p.qRange; sa.qFeat = p.qFeat; sa.qAngle = p.qAngle; sa.qInfo = p.qInfo; sa.assigned = p.assigned;
+  sa.matched = reinterpret_cast<int*>(p.down + dMatched); sa.point = reinterpret_cast<int*>(p.down + dPoint);
+  sa.heads = reinterpret_cast<unsigned*>(p.down + dHeads); sa.overflow = reinterpret_cast<int*>(p.down + dOvf);
+  const CallDev* dCalls = reinterpret_cast<const CallDev*>(p.up + oCalls);
+  const bool prof = m->profiling;
+  if (prof)
+    for (auto& e : m->bowEv)
+      if (!e) HIPCHK(hipEventCreate(&e));
+  const int takenWords = (int)((maxB + 31) / 32);
+  const size_t emitN = mode == 4 ? nq : nOut;
+  YdBowSearchStats& st = m->bowStats;
+  st.calls++;
+  st.launches = 0; st.synchronisations = 0; st.bytes_up = (int64_t)U.bytes; st.bytes_down = 0;
+  for (int attempt = 0; attempt < 6; attempt++) {
+    st.attempts++;
+    if (m->triPoolPerNb * np > (size_t)INT32_MAX) { set_error("%s: a record pool of %zu entries, past INT32_MAX", who, m->triPoolPerNb * np); return YDORB_ERR_CAPACITY; }
+    if ((rc = m->pool.ensure(sizeof(uint32_t) * m->triPoolPerNb * np))) return rc;
+    sa.pool = m->pool.as<uint32_t>(); sa.poolPerPair = (unsigned)m->triPoolPerNb;
+    HIPCHK(hipMemsetAsync(p.down + dMatched, 0xFF, dCount - dMatched, s));     // both dense outputs
+    HIPCHK(hipMemsetAsync(p.down + dCount, 0, D.bytes - dCount, s));           // counts, heads, overflow word
+    HIPCHK(hipMemsetAsync(p.assigned, 0xFF, 4 * nAssigned, s));
+    if (prof) HIPCHK(hipEventRecord(m->bowEv[0], s));
+    hipLaunchKernelGGL(mapdbbow::k_mapdb_bow_join, dim3((unsigned)((maxQ + mapdbbow::kThreads - 1) / mapdbbow::kThreads), nPairs), dim3(mapdbbow::kThreads), 0, s, sa);
+    hipLaunchKernelGGL(mapdbbow::k_mapdb_bow_gather, dim3((unsigned)((maxQ + 3) / 4), nPairs), dim3(256), 0, s, sa);
+    if (prof) HIPCHK(hipEventRecord(m->bowEv[1], s));
+    hipLaunchKernelGGL(k_resolve, dim3(nPairs), dim3(64), 2 * sizeof(unsigned) * takenWords, s, dCalls, (const FrameDev*)nullptr, m->pool.as<uint32_t>(), takenWords);
+    if (prof) HIPCHK(hipEventRecord(m->bowEv[2], s));
+    hipLaunchKernelGGL(mapdbbow::k_mapdb_bow_emit, dim3((unsigned)((emitN + mapdbbow::kThreads - 1) / mapdbbow::kThreads), nPairs), dim3(mapdbbow::kThreads), 0, s, sa);
+    HIPCHK(hipGetLastError());
+    if (prof) HIPCHK(hipEventRecord(m->bowEv[3], s));
+    HIPCHK(hipMemcpyAsync(m->hDown.p, p.down, D.bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    st.launches += 4; st.synchronisations += 1; st.bytes_down += (int64_t)D.bytes;
+    if (*at<int>(m->hDown, dOvf) != 0) {
+      const unsigned* heads = at<unsigned>(m->hDown, dHeads);
+      size_t asked = 0;
+      for (size_t i = 0; i < np; i++) asked = std::max(asked, (size_t)heads[i]);
+      m->triPoolPerNb = std::max(m->triPoolPerNb * 2, asked + 1024);
+      continue;
+    }
+    if (prof) {
+      float ms = 0;
+      for (int e = 0; e < BS_COUNT; e++)
+        if (hipEventElapsedTime(&ms, m->bowEv[e], m->bowEv[e + 1]) == hipSuccess) m->bowMs[e] += ms;
+      st.profiled_calls++;
+    }
+    std::memcpy(matched, at<void>(m->hDown, dMatched), 4 * np * nOut);
+    std::memcpy(point, at<void>(m->hDown, dPoint), 4 * np * nOut);
+    std::memcpy(nMatches, at<void>(m->hDown, dCount), 4 * np);
+    return YDORB_OK;
+  }
+  set_error("%s: candidate record pool kept overflowing", who);
+  return YDORB_ERR_CAPACITY;
+}
+
+extern "C" {
+
+int ydorb_mapdb_search_by_bow_keyframes(ydorb_mapdb_t* db, ydorb_matcher_t* m, int32_t firstKfSlot, const int32_t* secondKfSlots, int32_t nSecond, float ratio,
+                                        int32_t checkOri, int32_t nFirst, int32_t* matchedSecond, int32_t* matchedPoint, int32_t* nMatches, uint8_t* pairStatus) {
+  const char* who = "mapdb_search_by_bow_keyframes";
+  if (!db || !m) { set_error("%s: null handle", who); return YDORB_ERR_INVALID_ARG; }
+  if (nSecond < 0) { set_error("%s: negative number of second keyframes: %d", who, nSecond); return YDORB_ERR_INVALID_ARG; }
+  if (nFirst < 0) { set_error("%s: negative n_first: %d", who, nFirst); return YDORB_ERR_INVALID_ARG; }
+  if (nSecond > 65535) { set_error("%s: %d second keyframes, more than 65535", who, nSecond); return YDORB_ERR_UNSUPPORTED; }
+  if (nSecond > 0 && (!secondKfSlots || !nMatches || !pairStatus || (nFirst > 0 && (!matchedSecond || !matchedPoint)))) {
+    set_error("%s: null second_kf_slots, matched_second, matched_point, n_matches or pair_status", who);
+    return YDORB_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(ratio)) { set_error("%s: ratio is not finite", who); return YDORB_ERR_INVALID_ARG; }
+  std::vector<int32_t> kfSlots((size_t)nSecond + 1);
+  kfSlots[0] = firstKfSlot;
+  for (int32_t i = 0; i < nSecond; i++) kfSlots[(size_t)i + 1] = secondKfSlots[i];
+  return bowSearchResident(who, db, m, 4, kfSlots.data(), nSecond, nFirst, nullptr, ratio, checkOri ? 1 : 0, matchedSecond, matchedPoint, nMatches, pairStatus);
+}
+
+int ydorb_mapdb_search_by_bow_frame(ydorb_mapdb_t* db, ydorb_matcher_t* m, const int32_t* kfSlots, int32_t nKf, const YdBowSide* frame, float ratio,
+                                    int32_t checkOri, int32_t* matchedKfFeature, int32_t* matchedPoint, int32_t* nMatches, uint8_t* pairStatus) {
+  const char* who = "mapdb_search_by_bow_frame";
+  if (!db || !m) { set_error("%s: null handle", who); return YDORB_ERR_INVALID_ARG; }
+  if (nKf < 0) { set_error("%s: negative number of keyframes: %d", who, nKf); return YDORB_ERR_INVALID_ARG; }
+  if (nKf > 65535) { set_error("%s: %d keyframes, more than 65535", who, nKf); return YDORB_ERR_UNSUPPORTED; }
+  std::string err;
+  if (!mapdb::checkBowFrame(frame, err)) { set_error("%s: %s", who, err.c_str()); return YDORB_ERR_INVALID_ARG; }
+  if (nKf > 0 && (!kfSlots || !nMatches || !pairStatus || (frame->n > 0 && (!matchedKfFeature || !matchedPoint)))) {
+    set_error("%s: null kf_slots, matched_kf_feature, matched_point, n_matches or pair_status", who);
+    return YDORB_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(ratio)) { set_error("%s: ratio is not finite", who); return YDORB_ERR_INVALID_ARG; }
+  return bowSearchResident(who, db, m, 3, kfSlots, nKf, -1, frame, ratio, checkOri ? 1 : 0, matchedKfFeature, matchedPoint, nMatches, pairStatus);
+}
+
+int ydorb_matcher_bow_search_stats(ydorb_matcher_t* m, YdBowSearchStats* stats) {
+  if (!m || !stats) { set_error("matcher_bow_search_stats: null handle or stats"); return YDORB_ERR_INVALID_ARG; }
+  *stats = m->bowStats;
+  stats->pool_per_pair = (int64_t)m->triPoolPerNb;
+  for (int i = 0; i < BS_COUNT; i++) stats->ms[i] = stats->profiled_calls ? (float)(m->bowMs[i] / stats->profiled_calls) : 0.f;
+  return YDORB_OK;
+}
+
 int ydorb_fuse_search(ydorb_matcher_t* m, const YdFrameView* fv, const YdQuery* queries, const uint8_t* qdesc, int32_t nq,
                       const float* invSigma2, int32_t nLevels, int32_t* best, int32_t* nFound) {
   return ydorb_window_search(m, fv, queries, qdesc, nq, invSigma2, nLevels, 50, best, nFound);
@@ -1288,6 +1508,8 @@ int ydorb_matcher_set_profiling(ydorb_matcher_t* m, int32_t on) {
   m->evPending = false;
   for (double& v : m->triMs) v = 0;
   m->triCalls = 0;
+  for (double& v : m->bowMs) v = 0;
+  m->bowStats.profiled_calls = 0;
   return YDORB_OK;
 }
 

@@ -9,14 +9,15 @@ normal, distances and descriptor of every point where those queries compute them
  add each keyframe's keypoints and right coordinates, and MapDb.fuse_search runs the search of fuseByProjection /
 fuseBySim3 for all target keyframes of a LocalMapping::searchInNeighbors direction in one call.  The resident BoW feature vectors
  add each keyframe's DBoW3::FeatureVector, and MapDb.create_new_points runs LocalMapping::createNewMapPoints'
-search and geometry for all neighbours in one call."""
+search and geometry for all neighbours in one call.  MapDb.search_by_bow_keyframes / search_by_bow_frame run
+OrbMatcher::searchByBowInTwoKeyFrames / searchByBowInKeyFrameAndFrame for all candidate keyframes of a loop or relocalisation round in one call."""
 import ctypes as C
 
 import numpy as np
 
 from . import map_maintenance as M
 from .extractor import KP_DTYPE
-from ._lib import (YdCreateNeighbour, YdCreateView, YdFuseTarget, YdLocalBaGraph, YdMapCorrection, YdMapDbAttrStats, YdMapDbBowStats,
+from ._lib import (YdBowSide, YdCreateNeighbour, YdCreateView, YdFuseTarget, YdLocalBaGraph, YdMapCorrection, YdMapDbAttrStats, YdMapDbBowStats,
                    YdMapDbDescStats, YdMapDbFeatStats, YdMapDbLbaStats, YdMapDbRowStats, YdMapDbStats, check, lib)
 
 _p = M._p
@@ -452,6 +453,41 @@ class MapDb:
                                                   int(bool(check_orientation)), _p(matched) if n else None, _p(x3d) if n else None,
                                                   _p(status) if n else None, _p(n_m), _p(n_a), _p(nb_st)))
         return dict(matched_second=matched[:nn], x3d=x3d[:nn], status=status[:nn], n_matches=n_m[:nn], n_accepted=n_a[:nn], neighbour_status=nb_st[:nn])
+
+    def search_by_bow_keyframes(self, matcher, first_kf_slot, second_kf_slots, n_first, ratio=None, check_orientation=None):
+        """ydorb_mapdb_search_by_bow_keyframes on an OrbMatcher (its ratio and check_orientation unless given): searchByBowInTwoKeyFrames
+        (first, second_i) for every second keyframe, independently.  Returns dict(matched_second [n_second, n_first], matched_point
+        [n_second, n_first], n_matches, pair_status [n_second])."""
+        second = np.ascontiguousarray(second_kf_slots, np.int32).reshape(-1)
+        ns, n = len(second), int(n_first)
+        shape = (max(ns, 1), max(n, 0))
+        matched, point = np.full(shape, -7, np.int32), np.full(shape, -7, np.int32)
+        n_m, st = np.full(max(ns, 1), -7, np.int32), np.full(max(ns, 1), 9, np.uint8)
+        check(lib().ydorb_mapdb_search_by_bow_keyframes(self._h, matcher._h, int(first_kf_slot), _p(second) if ns else None, ns,
+                                                        float(matcher.ratio if ratio is None else ratio),
+                                                        int(bool(matcher.check_orientation if check_orientation is None else check_orientation)), n,
+                                                        _p(matched) if n > 0 else None, _p(point) if n > 0 else None, _p(n_m), _p(st)))
+        return dict(matched_second=matched[:ns], matched_point=point[:ns], n_matches=n_m[:ns], pair_status=st[:ns])
+
+    def search_by_bow_frame(self, matcher, kf_slots, kps, desc, valid, fv, ratio=None, check_orientation=None):
+        """ydorb_mapdb_search_by_bow_frame on an OrbMatcher: searchByBowInKeyFrameAndFrame(kf_i, frame) for every keyframe, independently.
+        The frame: kps [n] KP_DTYPE, desc [n, 32], valid [n] or None (every feature), fv a matcher.FeatureVector.  Returns
+        dict(matched_kf_feature [n_kf, n], matched_point [n_kf, n], n_matches, pair_status [n_kf])."""
+        slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        kps = np.ascontiguousarray(kps, KP_DTYPE).reshape(-1)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        valid = None if valid is None else np.ascontiguousarray(valid, np.uint8).reshape(-1)
+        nk, n = len(slots), len(kps)
+        assert len(desc) == n and (valid is None or len(valid) == n)
+        frame = YdBowSide(_p(kps) if n else None, _p(desc) if n else None, _p(valid) if valid is not None and n else None, n, fv.c())
+        shape = (max(nk, 1), n)
+        matched, point = np.full(shape, -7, np.int32), np.full(shape, -7, np.int32)
+        n_m, st = np.full(max(nk, 1), -7, np.int32), np.full(max(nk, 1), 9, np.uint8)
+        check(lib().ydorb_mapdb_search_by_bow_frame(self._h, matcher._h, _p(slots) if nk else None, nk, C.byref(frame),
+                                                    float(matcher.ratio if ratio is None else ratio),
+                                                    int(bool(matcher.check_orientation if check_orientation is None else check_orientation)),
+                                                    _p(matched) if n else None, _p(point) if n else None, _p(n_m), _p(st)))
+        return dict(matched_kf_feature=matched[:nk], matched_point=point[:nk], n_matches=n_m[:nk], pair_status=st[:nk])
 
     # ------------------------------------------------------------------------------------------------------------ inspection
     def stats(self):

@@ -223,6 +223,13 @@ class OrbMatcher:
     def synchronize(self):
         check(self._L.ydorb_matcher_synchronize(self._h))
 
+    def bow_search_stats(self):
+        """ydorb_matcher_bow_search_stats: what MapDb.search_by_bow_keyframes / search_by_bow_frame did on this matcher."""
+        from ._lib import YdBowSearchStats
+        st = YdBowSearchStats()
+        check(self._L.ydorb_matcher_bow_search_stats(self._h, C.byref(st)))
+        return {name: (list(st.ms) if name == "ms" else int(getattr(st, name))) for name, _ in YdBowSearchStats._fields_}
+
     def set_profiling(self, on=True):
         check(self._L.ydorb_matcher_set_profiling(self._h, int(on)))
 
