@@ -1,6 +1,8 @@
 """The C++ adapters (include/ydorb/*.hpp, reference signatures over the C ABI) type-check against declarations of the
 reference types they touch.  OpenCV is absent here, so a declaration-only mock stands in for <opencv2/core.hpp>, and the Eigen
-stand-in of tests/cpu_harness/mockrt for <Eigen/Core> / <Eigen/Geometry> (test-only)."""
+stand-in of tests/cpu_harness/mockrt for <Eigen/Core> / <Eigen/Geometry> (test-only).  This is the type check alone: the bodies are
+EXECUTED by the *_adapter_gpu.py modules, tests/test_adapter_exec.py and, for the projection, Sim3, fuse, triangulation and stereo
+bodies of orbMatcher.hpp / frame.hpp, tests/test_matcher_adapters_gpu.py; DESIGN.md section 6w lists every body with its test."""
 import os
 import subprocess
 
