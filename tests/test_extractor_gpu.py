@@ -276,6 +276,7 @@ def test_device_path_reports_capacity_errors_once():
         ex.synchronize()
     ex.synchronize()                                                         # reported once
     d_img.copy_(torch.from_numpy(good).to(dev))
+    torch.cuda.synchronize()                                                 # the copy runs on torch's stream, the call on the handle's own (non-blocking) one
     ex.extract_batch_device(d_img.data_ptr(), 1200, 1000, 1200, 1200 * 1000, 1, d_kps.data_ptr(), d_desc.data_ptr(), cap, d_n.data_ptr())
     ex.synchronize()
     n = int(d_n.item())

@@ -8,8 +8,7 @@ import math
 import numpy as np
 import pytest
 
-CIRCLE = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1),
-          (-2, 2), (-1, 3)]
+from extractor_edge_support import CIRCLE, _fast_score_definition, _patch   # noqa: F401  (one copy, shared with the edge-case table)
 
 
 def test_cv_round_half_even(oracle_lib):
@@ -65,22 +64,6 @@ def test_resize_linear(oracle_lib):
     assert (np.diff(out.astype(int), axis=1) >= 0).all() and (out[0] == out[-1]).all()
 
 
-def _fast_score_definition(d16, thr):
-    """Largest t for which the pixel is still a FAST-9/16 corner at threshold t (brute force), or None."""
-    def corner(t):
-        for s in range(16):
-            arc = [d16[(s + k) % 16] for k in range(9)]
-            if all(v > t for v in arc) or all(v < -t for v in arc):
-                return True
-        return False
-    if not corner(thr):
-        return None
-    t = thr
-    while corner(t + 1):
-        t += 1
-    return t
-
-
 def test_corner_score_equals_definition(oracle_lib):
     rng = np.random.default_rng(1)
     hits = 0
@@ -99,13 +82,6 @@ def test_corner_score_equals_definition(oracle_lib):
         d25 = np.concatenate([d, d[:9]]).astype(np.int32)
         assert oracle_lib.corner_score16(d25, 20) == ref
     assert hits > 500
-
-
-def _patch(center, ring_vals):
-    p = np.full((7, 7), center, np.uint8)
-    for (dx, dy), v in zip(CIRCLE, ring_vals):
-        p[3 + dy, 3 + dx] = v
-    return p
 
 
 def test_fast_hand_built_patches(oracle_lib):
